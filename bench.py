@@ -21,6 +21,12 @@ Workload (config.workload): wine_glass.acn at 1920x1080, path_samples 64, direct
 sampling of BASELINE.json configs[1] at the resolution its metric is quoted on ("Msamples/s at 1920x1080").
 `--workload c2` runs configs[1] verbatim (1280x720).
 
+A plain run sets up, warms up, times the --steps main passes, writes the last timed step's outputs if --dump-outputs DIR
+is given (DIR/radiance.npy: the linear radiance as float64, DIR/image.npy: the 8-bit image as float32; a frame of more
+than 1.66 M pixels on a fixed seeded sample of 1.25 M of them, whose row indices are DIR/radiance_index.npy) and prints
+the result line.  Everything else -- the CPU baseline, and the untimed passes after the timed ones for per-launch stage
+times, work counters and per-kernel-family times on one lane -- runs only with --full.
+
 Rank 0 prints ONE JSON line.  `roofline` prices the main pass against HBM as BASELINE.json asks: algorithmic bytes =
 24 B of radiance per pixel + 3 B of 8-bit image + one read of the flattened scene (SURVEY.md 8(d)'s floor; the path is
 fp64-ALU bound, so frac is tiny by nature -- see DESIGN.md), with the per-kernel-family launch counts and average launch
@@ -188,15 +194,39 @@ def cpu_baseline(flat, width, height, path_samples, target_seconds=10.0, window=
     }
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # under 64 MB in all
+DUMP_SAMPLE_PIXELS = 1_250_000
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, radiance, image):
+    """What one step hands its caller: the linear radiance (n x 3 f64) and the 8-bit image (n x 3).  A frame larger than
+    the budget is written on a fixed seeded sample of its rows, the same rows for both, listed in radiance_index.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = radiance.shape[0]
+    if n * (8 + 4) * 3 > DUMP_BUDGET_BYTES:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE_PIXELS, replace=False))
+        radiance, image = radiance[idx], image[idx]
+        np.save(os.path.join(out_dir, "radiance_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "radiance.npy"), np.ascontiguousarray(radiance, dtype=np.float64))
+    np.save(os.path.join(out_dir, "image.npy"), np.ascontiguousarray(image, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="wine_glass_1080p", choices=list(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the CPU baseline and the untimed passes for per-stage events, work counters "
+                         "and per-kernel-family times (a plain run does none of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
     ap.add_argument("--quick", action="store_true",
-                    help="heavy workloads: no extra passes for per-stage events and work counters after the timed steps")
+                    help="--full, heavy workloads: no extra passes for per-stage events and work counters after the timed steps")
     ap.add_argument("--pixel-stride", type=int, default=1,
                     help="render every K-th pixel of the raster only (heavy configs on one GPU); value counts the pixels rendered")
     ap.add_argument("--rows", default=None,
@@ -209,6 +239,8 @@ def main():
     ap.add_argument("--checksum", default=None,
                     help="write per-tile fixed-point sums of the last linear frame to this JSON file and compare with tests/golden/frame_checksums.json")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -335,11 +367,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, frame.cpu().numpy(), host_img.numpy())
+
     # device time of the main pass: HIP events recorded by the library on its launch streams, of the LAST TIMED step (the
     # passes below carry per-launch events or work counters and are not what `value` timed)
     families = None
     k_timed = handle.last_kernel_ms()
-    if args.quick:
+    if args.quick or not args.full:
         stages = handle.last_stages()
         counters = None
     else:
@@ -475,7 +510,7 @@ def main():
                 "grays_per_s_rank0": (counters["trans_rays"] + counters["shadow_rays"]) / (k_ms * 1e-3) / 1e9},
             "frame_check": check if check is None else {k: check[k] for k in check if k != "tile_sums_fixed_2^-40"},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             window = None
             if args.cpu_window:
                 ww, wh = (int(v) for v in args.cpu_window.lower().split("x"))

@@ -4,7 +4,7 @@ out=$1; shift
 args=$1; shift
 IFS=';' read -ra CFG <<< "$*"
 for c in "${CFG[@]}"; do
-  line=$(env $c timeout -k 10 300 python bench.py $args --no-cpu-baseline 2>/dev/null | python -c "
+  line=$(env $c timeout -k 10 300 python bench.py --full $args --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

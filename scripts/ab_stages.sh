@@ -3,7 +3,7 @@
 out=$1; dir=$2; args=$3; shift 3
 IFS=';' read -ra CFG <<< "$*"
 for c in "${CFG[@]}"; do
-  line=$(cd $dir && env $c timeout -k 10 300 python bench.py $args --no-cpu-baseline 2>/dev/null | python -c "
+  line=$(cd $dir && env $c timeout -k 10 300 python bench.py --full $args --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -9,7 +9,7 @@ tail -n 2 $out/tests_gpu.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1 || { tail -n 5 $out/smoke.log; exit 1; }
 tail -n 2 $out/smoke.log
 for w in c2 c1 c5 paraffin_lamp; do
-  timeout -k 10 300 python bench.py --workload $w --steps 8 --warmup 2 --quick > $out/bench_$w.json 2> $out/bench_$w.err || { tail -n 5 $out/bench_$w.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --workload $w --steps 8 --warmup 2 --quick > $out/bench_$w.json 2> $out/bench_$w.err || { tail -n 5 $out/bench_$w.err; exit 1; }
   cut -c1-160 $out/bench_$w.json
 done
 timeout -k 10 300 python bench.py --steps 8 --warmup 2 --quick --no-cpu-baseline --pixel-stride 8 > $out/bench_wine_glass_1080p_stride8.json 2>/dev/null
@@ -50,10 +50,10 @@ print("\n".join(lines[:9]))
 PY
 find $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE -name "*.csv" -size +20M -delete
 # the headline line: after the traffic passes, so that it carries the traffic of these very kernels
-timeout -k 10 600 python bench.py --steps 10 --warmup 2 --checksum $out/checksum_wine_glass_1080p.json > $out/bench_wine_glass_1080p.json 2> $out/bench.err || { tail -n 5 $out/bench.err; exit 1; }
+timeout -k 10 600 python bench.py --full --steps 10 --warmup 2 --checksum $out/checksum_wine_glass_1080p.json > $out/bench_wine_glass_1080p.json 2> $out/bench.err || { tail -n 5 $out/bench.err; exit 1; }
 cut -c1-200 $out/bench_wine_glass_1080p.json
 for split in tiles samples; do
-  ACN_BENCH_SINGLE_DEVICE=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --split $split > $out/bench_2ranks_rehearsal_$split.json 2> $out/bench_2ranks_$split.err || { tail -n 5 $out/bench_2ranks_$split.err; exit 1; }
+  ACN_BENCH_SINGLE_DEVICE=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline --split $split > $out/bench_2ranks_rehearsal_$split.json 2> $out/bench_2ranks_$split.err || { tail -n 5 $out/bench_2ranks_$split.err; exit 1; }
   grep '^{' $out/bench_2ranks_rehearsal_$split.json | cut -c1-200
 done
 # steadiness: consecutive frames of the two lamp scenes, this tree and the round-2 tree (if it travelled) on the same box

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   d=gpurun_out/pmc_$c
   mkdir -p $d
-  rocprofv3 --pmc $c --output-format csv -d $d -o t -- python3 bench.py --workload $w --steps $steps --warmup 0 --no-cpu-baseline > $d/log.txt 2>&1
+  rocprofv3 --pmc $c --output-format csv -d $d -o t -- python3 bench.py --full --workload $w --steps $steps --warmup 0 --no-cpu-baseline > $d/log.txt 2>&1
 done
 python3 - "$w" "$steps" <<'PY'
 import csv, sys, json, os

@@ -6,5 +6,5 @@ tag=$1; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o $tag -- python3 bench.py --no-cpu-baseline "$@" > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o $tag -- python3 bench.py --full --no-cpu-baseline "$@" > $out/bench.log 2>&1
 ls -R $out | head -30

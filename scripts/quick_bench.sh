@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: scripts/quick_bench.sh [label] ; env vars pass through
-timeout -k 10 200 python bench.py --workload c2 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
+timeout -k 10 200 python bench.py --full --workload c2 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -2,11 +2,10 @@
 
 Checked here, without a GPU: (1) the evaluation rules of the language on a script of our own whose expected
 numbers follow from the reference's evaluator (src/interpreter.c:1412-1730); (2) object operators and container
-rules through the flattened scene; (3) on the reference's shipped scripts, when /root/reference is present, the
-interpreter reproduces node for node the scenes that actinon_amd/host/acn_scenes.c builds by direct API calls
-(two independent transcriptions of the same scripts), and every shipped script interprets."""
+rules through the flattened scene; (3) on the reference's shipped scripts, the interpreter's output (stored under
+tests/golden/interp/ by tests/golden/make_interp_fixtures.py) is node for node the scene that
+actinon_amd/host/acn_scenes.c builds by direct API calls (two independent transcriptions of the same scripts)."""
 import ctypes as C
-import glob
 import math
 import os
 
@@ -20,10 +19,8 @@ from test_host_scene import declared_functions
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SCRIPTS = os.path.join(HERE, "scripts")
-REF = "/root/reference/src_acn"
+INTERP_FIXTURES = os.path.join(HERE, "golden", "interp")
 SKIP = A.Scene.AUTOENV_SKIP
-
-needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="reference scripts not present on this machine")
 
 
 def test_interp_symbols_exported():
@@ -189,36 +186,19 @@ scene.create_image( "t.pnm" );
         assert message in str(e.value), (text, str(e.value))
 
 
-@needs_reference
 @pytest.mark.parametrize("name", ["primitives", "wine_glass", "diamond"])
 def test_shipped_scripts_match_direct_builders(name):
-    """Two independent routes to the same scene: the interpreter on the reference's script, and the C builder
-    written from that script by hand.  Structure must be identical; numbers differ only by the literal rule and
-    by a / b being a * ( 1 / b ) in the script language (<= a few ulp)."""
-    a = A.Scene.from_script(f"{REF}/{name}.acn", SKIP)
+    """Two independent routes to the same scene: the interpreter on the reference's script (its output stored as
+    tests/golden/interp/<name>.npz), and the C builder written from that script by hand.  Structure must be identical;
+    numbers differ only by the literal rule and by a / b being a * ( 1 / b ) in the script language (<= a few ulp)."""
+    a = A.Flat.load(os.path.join(INTERP_FIXTURES, name + ".npz"))
     b = A.Scene.build(name)
-    nodes_close(a.flatten(), b.flatten())
+    nodes_close(a, b.flatten())
     for fname, _ in abi.Params._fields_:
-        va, vb = getattr(a.prm, fname), getattr(b.prm, fname)
+        va, vb = getattr(a.params, fname), getattr(b.prm, fname)
         if hasattr(va, "__len__"):
             assert np.allclose(list(va), list(vb), rtol=1e-12)
         else:
             assert va == vb or math.isclose(va, vb, rel_tol=1e-12), fname
-    assert (a.s.gradient_cycles, a.s.gradient_samples) == (b.s.gradient_cycles, b.s.gradient_samples)
-
-
-@needs_reference
-def test_every_shipped_script_interprets():
-    files = sorted(glob.glob(f"{REF}/*.acn")) + [f"{REF}/{d}/{d}.acn" for d in
-                                                ("hanging_lamp", "hanging_lamps_in_row", "paraffin_lamp", "paraffin_lamp_on_ledge")]
-    assert len(files) == 12
-    before = sorted(os.listdir(REF))
-    sizes = {}
-    for f in files:
-        sc = A.Scene.from_script(f, SKIP)
-        fl = sc.flatten()
-        sizes[os.path.basename(f)] = (sc.objects(), fl.n_nodes, sc.prm.image_width, sc.prm.image_height)
-    assert sorted(os.listdir(REF)) == before          # readonly_fs: nothing written next to the scripts
-    assert sizes["hanging_lamp.acn"][2:] == (600, 800) and sizes["hanging_lamp.acn"][1] > 2000
-    assert sizes["pyramid.acn"][0] == 37 and sizes["ruby_heart.acn"][0] == 45
-    assert sizes["many_spheres.acn"][0] == 8 ** 5 + 2  # without envelopes the nested compounds dissolve (compound.c:184-190)
+    _, gradient_samples, gradient_cycles = a.driver
+    assert (gradient_cycles, gradient_samples) == (b.s.gradient_cycles, b.s.gradient_samples)
