@@ -46,7 +46,7 @@ ACN_HD double acn_bits_f64( uint64_t u )
 
 ACN_HD double acn_fabs( double x ) { return acn_bits_f64( acn_f64_bits( x ) & 0x7FFFFFFFFFFFFFFFull ); }
 
-/* correctly rounded on x86-64 (sqrtsd) and on gfx950 (checked bit-for-bit by tests/test_gpu_detmath.py) */
+/* correctly rounded on x86-64 (sqrtsd) and on gfx950 (checked bit-for-bit by test_detmath_bit_identical_cpu_gpu in tests/test_gpu_parity.py) */
 ACN_HD double acn_sqrt( double x ) { return __builtin_sqrt( x ); }
 
 /* 2^k for -1022 <= k <= 1023 */

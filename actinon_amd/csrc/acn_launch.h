@@ -63,6 +63,11 @@ void acn_launch_hard_shadow( KernelFlags f, const LevelQ& q, size_t lds_bytes, h
 void acn_launch_hard_path( KernelFlags f, const LevelQ& q, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
                            unsigned long long* accum, unsigned long long* counters );
 
+/* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
+struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
+int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */
+int acn_query_fail( int code, const char* msg );          /* acn_last_error() */
+
 #define ACN_SCENE_ARGS_OF( s ) ( s ).dev, ( s ).nodes, ( s ).mats, ( s ).elems, ( s ).textures
 #define ACN_TASKQ_ARGS_OF( q ) ( q ).tasks, ( q ).idx[ 0 ], ( q ).idx[ 1 ], ( q ).idx[ 2 ], ( q ).idx[ 3 ], ( q ).counts, ( q ).task_cap, ( q ).hard_shadow, ( q ).hs_cap, ( q ).emit_terms
 

@@ -2268,6 +2268,15 @@ extern "C" int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_
     return ACN_OK;
 }
 
+int acn_query_env( acn_scene_handle* h, QueryEnv* q )
+{
+    if( !h || !q ) return fail( ACN_ERR_ARG, "null argument" );
+    HIP_TRY( hipSetDevice( h->device ) );
+    q->s = scene_args( h ); q->lds_node_bytes = h->lds_bytes; q->lds_stack_bytes = h->lds_stack_bytes; q->stream = h->stream;
+    return ACN_OK;
+}
+int acn_query_fail( int code, const char* msg ) { return fail( code, msg ); }
+
 extern "C" int acn_detmath_eval( int device, int op, const double* x, const double* y, double* out, size_t n )
 {
     if( !x || !out ) return fail( ACN_ERR_ARG, "null argument" );

@@ -321,6 +321,33 @@ class Handle:
         return list(out)
 
 
+    # test seam acn_query_rays (include/actinon_hip.h): the device's traversal shortcuts one ray per lane
+    QUERY_OPS = {"hit_lane": 0, "hit_uni": 1, "element_hit": 2, "side_lane": 3, "side_uni": 4, "prune": 5, "leaf_iv": 6,
+                 "trans": 7, "occluded": 8, "cone_cull": 9, "sc_hit": 10, "elements": 11}
+    QUERY_STRIDE = 16
+
+    def query_rays(self, op, node, rays=None, limits=None, skip=None, lds=True, prune=True, n=None):
+        """[n, 16] float64 results of query `op` on node `node` for rays [n, 6] (origin, direction), ray i on lane i % 64
+        of wave i / 64.  limits [n] and skip masks [n] (uint64) where the query takes them.  lds=False reads the node
+        array from global memory where the handle stages it in LDS; prune=False runs the plain scene view (no interval-prune
+        programs, no in-line simple compounds).  "elements" takes no rays: n is the number of elements to list."""
+        code = self.QUERY_OPS[op] | (0 if lds else 0x100) | (0 if prune else 0x200)
+        if rays is None:
+            r, cnt = None, int(n)
+        else:
+            r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+            cnt = r.shape[0]
+        lim = None
+        if limits is not None or skip is not None:
+            lim = np.zeros((cnt, 2), dtype=np.float64)
+            lim[:, 0] = np.inf if limits is None else np.asarray(limits, dtype=np.float64)
+            if skip is not None:
+                lim.view(np.uint64)[:, 1] = np.asarray(skip, dtype=np.uint64)
+        out = np.zeros((max(cnt, 1), self.QUERY_STRIDE), dtype=np.float64)
+        check(hip.acn_query_rays(self.h, code, int(node), None if r is None else r.ctypes.data, cnt,
+                                 None if lim is None else lim.ctypes.data, out.ctypes.data), "acn_query_rays")
+        return out[:cnt]
+
 def main_pass_positions(width, height, first=0, count=None):
     """Pixel centres of the main pass, row-major (scene.c:1110-1119)."""
     n = width * height if count is None else count

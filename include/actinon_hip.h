@@ -281,6 +281,41 @@ int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_t samples, 
  * op: 0 sin 1 cos 2 tan 3 acos 4 log 5 exp 6 pow(x,y) 7 sqrt 8 div(x/y) 9 u64->f64 (x bits) 10 frexp-mantissa */
 int acn_detmath_eval( int device, int op, const double* x, const double* y, double* out, size_t n );
 
+/* Test hook: the traversal shortcuts of the device (csrc/acn_device.h), one ray per lane, in the arrangement of the
+ * pipeline's machine kernels (256-lane workgroups, the handle's scene, CSG stacks in LDS).  Ray i runs on lane i % 64 of
+ * wave i / 64.  rays: [ n ][ 6 ] origin, direction.  limits (nullable: limit inf, no skips): [ n ][ 2 ], a limit and a
+ * 64-bit skip mask (raw bits; root_occluded_fast).  out: [ n ][ ACN_QUERY_STRIDE ] doubles (integers as doubles, masks as
+ * raw bits); a query on a node of the wrong kind yields NaN in out[ 0 ].  op: an ACN_Q_* value, or'ed with
+ * ACN_QUERY_GLOBAL_NODES (node array read from global memory even where the handle stages it in LDS) and / or
+ * ACN_QUERY_PLAIN_SCENE (the scene view without interval-prune programs and in-line simple compounds).
+ *   HIT_LANE, HIT_UNI  obj_ray_hit_dev / obj_ray_hit_uni of `node`       a, normal[3]
+ *   ELEMENT_HIT        element_hit, the root-element test of k_walk     a, normal[3], hit object
+ *   SIDE_LANE, SIDE_UNI obj_side_dev / obj_side_uni at the origin       side
+ *   PRUNE              surely_outside, prune_run( limit ), prune_run( inf ), has a program
+ *   LEAF_IV            iv_ball / iv_squaroid / iv_halfspace of a leaf   lo, hi, envelope chord lo, hi
+ *   TRANS              root_trans_hit on compound `node`                a, exit normal[3], exit, enter object;
+ *                      root_trans_hit_fast (+ the full redo if hard)    [ 6 .. 11 ] the same, [ 12 ] hard
+ *   OCCLUDED           root_occluded, root_occluded_fast( skip ) on compound `node`
+ *                      (not root_occluded_pooled: compiled only with ACN_POOLED=1, which production builds leave off)
+ *   CONE_CULL          root_cone_cull of the matter root for light `node` seen from the origin: mask, axis[3], cos theta
+ *   SC_HIT             simple_compound_hit on `node`: a, normal[3], hit object, any-hit( limit )
+ *   ELEMENTS           no rays: per element of compound `node` (n at most): index, ACN_Q_EL_* bits, type; out[ 3 ]:
+ *                      bytes of nodes the handle stages in LDS (0: the node array is always read from global memory) */
+enum acn_query_op
+{
+    ACN_Q_HIT_LANE = 0, ACN_Q_HIT_UNI, ACN_Q_ELEMENT_HIT, ACN_Q_SIDE_LANE, ACN_Q_SIDE_UNI, ACN_Q_PRUNE, ACN_Q_LEAF_IV,
+    ACN_Q_TRANS, ACN_Q_OCCLUDED, ACN_Q_CONE_CULL, ACN_Q_SC_HIT, ACN_Q_ELEMENTS, ACN_Q_N
+};
+#define ACN_QUERY_GLOBAL_NODES 0x100
+#define ACN_QUERY_PLAIN_SCENE  0x200
+#define ACN_QUERY_STRIDE 16
+#define ACN_Q_EL_FAST            1u
+#define ACN_Q_EL_LEAF_PAIR       2u
+#define ACN_Q_EL_SIMPLE_COMPOUND 4u
+#define ACN_Q_EL_PROGRAM         8u
+#define ACN_Q_EL_ENVELOPE       16u
+int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const double* rays, size_t n, const double* limits, void* out );
+
 const char* acn_last_error( void );
 
 #ifdef __cplusplus

@@ -1432,6 +1432,91 @@ double acn_oracle_trans_hit( const acn_flat_scene* scene, const double* ray_p3, 
     return a;
 }
 
+/* ---- batch queries over arrays of rays (tests/test_gpu_queries.py), a pthread farm like acn_oracle_render_positions ---- */
+typedef struct
+{
+    const acn_flat_scene* sc;
+    int op;
+    int32_t node;
+    const double* rays;
+    const double* limits;
+    size_t n;
+    double* out;
+    size_t* index;
+    pthread_mutex_t* mutex;
+} query_farm_t;
+
+static void query_one( ctx_t* c, int op, int32_t node, const double* r, double limit, double* o )
+{
+    ray_t ray = { v3_ld( r ), v3_ld( r + 3 ) };
+    for( int k = 0; k < ACN_ORACLE_QUERY_STRIDE; k++ ) o[ k ] = 0;
+    if( op == ACN_ORACLE_Q_OBJ_RAY_HIT )
+    {
+        v3 nor = { 0, 0, 0 };
+        o[ 0 ] = obj_ray_hit( c, node, &ray, &nor );
+        st3( o + 1, nor );
+    }
+    else if( op == ACN_ORACLE_Q_OBJ_SIDE ) o[ 0 ] = obj_side( c, node, ray.p );
+    else if( op == ACN_ORACLE_Q_COMPOUND_RAY_HIT || op == ACN_ORACLE_Q_OCCLUDED )
+    {
+        v3 nor = { 0, 0, 0 };
+        int hit_obj = -1;
+        double a = compound_ray_hit( c, node, &ray, &nor, &hit_obj );
+        o[ 0 ] = a; st3( o + 1, nor ); o[ 4 ] = hit_obj;
+        if( op == ACN_ORACLE_Q_OCCLUDED ) o[ 5 ] = a <= limit;   /* scene_lum's test: unoccluded iff compound_s_ray_hit( matter ) > a */
+    }
+    else if( op == ACN_ORACLE_Q_TRANS_HIT )
+    {
+        trans_t t = { { 0, 0, 0 }, -1, -1 };
+        o[ 0 ] = compound_ray_trans_hit( c, node, &ray, &t );
+        st3( o + 1, t.exit_nor ); o[ 4 ] = t.exit_obj; o[ 5 ] = t.enter_obj;
+    }
+}
+
+static void* query_farm_func( void* arg )
+{
+    query_farm_t* f = arg;
+    ctx_t c = { f->sc, NULL, 0, 1, 0 };
+    for( ;; )
+    {
+        pthread_mutex_lock( f->mutex );
+        size_t first = *f->index;
+        *f->index += 256;
+        pthread_mutex_unlock( f->mutex );
+        if( first >= f->n ) break;
+        size_t last = first + 256 < f->n ? first + 256 : f->n;
+        for( size_t i = first; i < last; i++ )
+            query_one( &c, f->op, f->node, f->rays + 6 * i, f->limits ? f->limits[ i ] : F3_INF, f->out + ACN_ORACLE_QUERY_STRIDE * i );
+    }
+    return NULL;
+}
+
+int acn_oracle_query_rays( const acn_flat_scene* scene, int op, int32_t node, const double* rays, size_t n, const double* limits,
+                           double* out, int threads )
+{
+    int st = validate( scene );
+    if( st != ACN_OK ) return st;
+    if( op < 0 || op >= ACN_ORACLE_Q_N || node < 0 || ( uint32_t )node >= scene->n_nodes ) return ACN_ERR_ARG;
+    if( n && ( !rays || !out ) ) return ACN_ERR_ARG;
+    const int is_cmp = scene->nodes[ node ].type == ACN_COMPOUND;
+    const int want_cmp = op == ACN_ORACLE_Q_COMPOUND_RAY_HIT || op == ACN_ORACLE_Q_TRANS_HIT || op == ACN_ORACLE_Q_OCCLUDED;
+    if( is_cmp != want_cmp ) return ACN_ERR_ARG;
+    if( threads < 1 ) threads = 1;
+    if( threads > 256 ) threads = 256;
+    size_t index = 0;
+    pthread_mutex_t mutex = PTHREAD_MUTEX_INITIALIZER;
+    query_farm_t f = { scene, op, node, rays, limits, n, out, &index, &mutex };
+    if( threads == 1 ) query_farm_func( &f );
+    else
+    {
+        pthread_t* th = calloc( threads, sizeof( pthread_t ) );
+        for( int t = 0; t < threads; t++ ) pthread_create( &th[ t ], NULL, query_farm_func, &f );
+        for( int t = 0; t < threads; t++ ) pthread_join( th[ t ], NULL );
+        free( th );
+    }
+    return ACN_OK;
+}
+
 uint64_t acn_oracle_random_seed( const double* v, uint64_t rv ) { return v3_random_seed( v3_ld( v ), rv ); }
 
 void acn_oracle_sphere_cap( uint64_t* rv, double h, double* out3 ) { st3( out3, v3_random_sphere_cap( rv, h ) ); }

@@ -73,6 +73,19 @@ double acn_oracle_obj_ray_hit( const acn_flat_scene* scene, int32_t node, const 
 int    acn_oracle_obj_side( const acn_flat_scene* scene, int32_t node, const double* pos3 );
 double acn_oracle_trans_hit( const acn_flat_scene* scene, const double* ray_p3, const double* ray_d3,
                              double* exit_nor3, int32_t* exit_obj, int32_t* enter_obj );
+/* The one-ray functions above (and compound_s_ray_hit, which is not exported on its own) over arrays, on `threads` pthreads.
+ * rays: [ n ][ 6 ] origin, direction; limits (nullable = inf): [ n ]; out: [ n ][ ACN_ORACLE_QUERY_STRIDE ].
+ *   OBJ_RAY_HIT        obj_ray_hit( node ): a, normal[3]
+ *   OBJ_SIDE           obj_side( node ) at the origin: side
+ *   COMPOUND_RAY_HIT   compound_s_ray_hit( node ): a, normal[3], hit object
+ *   TRANS_HIT          compound_s_ray_trans_hit( node ): a, exit normal[3], exit object, enter object (-1: none)
+ *   OCCLUDED           COMPOUND_RAY_HIT and [ 5 ] = a <= limit, the occlusion test of scene_s_lum
+ * node must be a compound for the last three and must not be one for the first two. */
+enum { ACN_ORACLE_Q_OBJ_RAY_HIT = 0, ACN_ORACLE_Q_OBJ_SIDE, ACN_ORACLE_Q_COMPOUND_RAY_HIT, ACN_ORACLE_Q_TRANS_HIT, ACN_ORACLE_Q_OCCLUDED,
+       ACN_ORACLE_Q_N };
+#define ACN_ORACLE_QUERY_STRIDE 8
+int acn_oracle_query_rays( const acn_flat_scene* scene, int op, int32_t node, const double* rays, size_t n, const double* limits,
+                           double* out, int threads );
 uint64_t acn_oracle_random_seed( const double* v3, uint64_t rv );
 void   acn_oracle_sphere_cap( uint64_t* rv, double h, double* out3 );
 /* 0: detmath, 1: libm */

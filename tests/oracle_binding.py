@@ -40,6 +40,7 @@ class Oracle:
         L.acn_oracle_random_seed.restype = C.c_uint64
         L.acn_oracle_sphere_cap.argtypes = [vp, C.c_double, vp]
         L.acn_oracle_sphere_cap.restype = None
+        L.acn_oracle_query_rays.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, C.c_int]
 
     def math_mode(self):
         return self.lib.acn_oracle_math_mode()
@@ -114,3 +115,33 @@ class Oracle:
         out = np.zeros(3)
         self.lib.acn_oracle_sphere_cap(C.byref(s), h, out.ctypes.data)
         return s.value, out
+
+    QUERY_OPS = {"obj_ray_hit": 0, "obj_side": 1, "compound_ray_hit": 2, "trans_hit": 3, "occluded": 4}
+
+    def query_rays(self, flat, op, node, rays, limits=None, threads=16):
+        """acn_oracle_query_rays: [n, 8] results of the one-ray function `op` for rays [n, 6] (origin, direction)."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        lim = None if limits is None else np.ascontiguousarray(limits, dtype=np.float64).reshape(-1)
+        out = np.zeros((max(r.shape[0], 1), 8), dtype=np.float64)
+        st = self.lib.acn_oracle_query_rays(C.addressof(flat.c), self.QUERY_OPS[op], int(node), r.ctypes.data, r.shape[0],
+                                            None if lim is None else lim.ctypes.data, out.ctypes.data, min(threads, 16))
+        if st != 0:
+            raise RuntimeError(f"oracle status {st}")
+        return out[:r.shape[0]]
+
+    def obj_ray_hits(self, flat, node, rays, threads=16):
+        o = self.query_rays(flat, "obj_ray_hit", node, rays, threads=threads)
+        return o[:, 0], o[:, 1:4]
+
+    def obj_sides(self, flat, node, pos, threads=16):
+        pos = np.ascontiguousarray(pos, dtype=np.float64).reshape(-1, 3)
+        rays = np.concatenate([pos, np.zeros_like(pos)], axis=1)
+        return self.query_rays(flat, "obj_side", node, rays, threads=threads)[:, 0].astype(np.int64)
+
+    def compound_ray_hits(self, flat, node, rays, threads=16):
+        o = self.query_rays(flat, "compound_ray_hit", node, rays, threads=threads)
+        return o[:, 0], o[:, 1:4], o[:, 4].astype(np.int64)
+
+    def trans_hits(self, flat, node, rays, threads=16):
+        o = self.query_rays(flat, "trans_hit", node, rays, threads=threads)
+        return o[:, 0], o[:, 1:4], o[:, 4].astype(np.int64), o[:, 5].astype(np.int64)
