@@ -63,6 +63,15 @@ void acn_launch_hard_shadow( KernelFlags f, const LevelQ& q, size_t lds_bytes, h
 void acn_launch_hard_path( KernelFlags f, const LevelQ& q, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
                            unsigned long long* accum, unsigned long long* counters );
 
+/* caller-supplied primary rays (k_rays.hip).  rays: [ n ][ 6 ] origin, direction.
+ * seed: slots [ base, base + cnt ) of the call's TileOrder -> generation 0 of the level's ray queue ( q.rays[ 0 ], the count
+ * QC_GEN + 0 ), as k_walk would make them of camera rays; cnt <= q.ray_cap (no slot past it is written).
+ * check: *first_bad = min( *first_bad, index of a ray with a non-finite component or a direction of no length ).
+ * camera: out[ i ] = camera_ray( pos_xy[ i ] ), the rays k_walk casts for sample positions. */
+void acn_launch_seed_rays( const double* rays, uint32_t base, uint32_t cnt, TileOrder order, int depth, const LevelQ& q, hipStream_t stream );
+void acn_launch_check_rays( const double* rays, size_t n, unsigned long long* first_bad, hipStream_t stream );
+void acn_launch_camera_rays( const DevScene& sc, const double* pos_xy, size_t n, double* out, hipStream_t stream );
+
 /* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
 struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
 int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */

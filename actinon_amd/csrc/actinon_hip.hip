@@ -241,8 +241,11 @@ struct acn_scene_handle
     int early_status = 0; std::string early_message;
     LaneWorker* worker = nullptr;              /* of a lane */
     size_t scene_bytes[ 4 ] = { 0, 0, 0, 0 };
-    double* d_lane_pos = nullptr; double* d_lane_out = nullptr; size_t lane_buf_cap = 0;   /* a lane's gathered positions / results */
+    double* d_lane_in = nullptr; size_t lane_in_cap = 0;       /* a lane's gathered positions or rays (doubles) */
+    double* d_lane_out = nullptr; size_t lane_out_cap = 0;     /* ... and its results */
     double* d_shard_pos = nullptr; size_t shard_pos_cap = 0;                                /* acn_render_main_pass_shard_dev: the rank's positions */
+    unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
+    bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
     std::string lane_error;
     bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
     int  lanes_used = 0;                       /* ... the first lanes_used of them */
@@ -1053,9 +1056,10 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( h->d_counts ) hipFree( h->d_counts );
     if( h->h_counts ) hipHostFree( h->h_counts );
     if( h->d_accum ) hipFree( h->d_accum );
-    if( h->d_lane_pos ) hipFree( h->d_lane_pos );
+    if( h->d_lane_in ) hipFree( h->d_lane_in );
     if( h->d_lane_out ) hipFree( h->d_lane_out );
     if( h->d_shard_pos ) hipFree( h->d_shard_pos );
+    if( h->d_ray_check ) hipFree( h->d_ray_check );
     if( !h->is_lane )   /* a lane borrows the resident scene of its parent */
     {
         if( h->d_nodes ) hipFree( h->d_nodes );
@@ -1091,6 +1095,11 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
 #define ACN_STARTER_RECORDS ( ( size_t )1 << 20 )
 static double f_max_host( double a, double b ) { return a > b ? a : b; }
 static bool rates_known( const acn_scene_handle* h ) { return h->rate[ WQ_TASKS ] > 0 || h->rate[ WQ_RAYS ] > 0 || h->rate[ WQ_HARD_SHADOW ] > 0; }
+/* records per position a queue of the current call needs: the learned rate, and in the ray queue of a ray call at least one
+ * slot per position whatever earlier calls taught the handle -- its seeded generation is a KNOWN demand, kept out of the
+ * learned rates (render_chunk) */
+static double queue_demand( const double* rate, int q, bool seeded ) { return seeded && q == WQ_RAYS && rate[ q ] < 1.0 ? 1.0 : rate[ q ]; }
+static double demand( const acn_scene_handle* h, int q ) { return queue_demand( h->rate, q, h->seeded ); }
 
 /* positions a chunk may have so that every queue stays below 70 % of its capacity */
 static size_t chunk_for_caps( const acn_scene_handle* h )
@@ -1098,7 +1107,7 @@ static size_t chunk_for_caps( const acn_scene_handle* h )
     double chunk = 2.0e9;
     for( int q = 0; q < WQ_N; q++ )
     {
-        const double r = h->rate[ q ] > 1e-3 ? h->rate[ q ] : 1e-3;
+        const double r = demand( h, q ) > 1e-3 ? demand( h, q ) : 1e-3;
         const double c = h->ctl.fill_target * ( double )h->ws.cap[ q ] / r;
         if( c < chunk ) chunk = c;
     }
@@ -1144,12 +1153,12 @@ static int ensure_workspace( acn_scene_handle* h, size_t n )
          * cent short turns one chunk per lane into two (a second chain of launches: c2 36 -> 50 ms) or, worse, makes the
          * lane re-allocate in the middle of a frame (hipFree synchronises the device: paraffin_lamp 440 -> 700 ms) */
         const double slack = 1.4;
-        for( int q = 0; q < WQ_N; q++ ) bytes += ( slack * h->rate[ q ] * positions / 0.7 + 65536.0 ) * ( double )wq_bytes[ q ];
+        for( int q = 0; q < WQ_N; q++ ) bytes += ( slack * demand( h, q ) * positions / 0.7 + 65536.0 ) * ( double )wq_bytes[ q ];
         const double room = budget > stack_bytes ? ( double )( budget - stack_bytes ) : 0.0;
         if( bytes > room ) positions *= room / bytes;
         for( int q = 0; q < WQ_N; q++ )
         {
-            double c = slack * h->rate[ q ] * positions / 0.7 + 65536.0;
+            double c = slack * demand( h, q ) * positions / 0.7 + 65536.0;
             want[ q ] = c > 4.0e9 ? 0xFFFFFF00ull : ( size_t )c;
         }
     }
@@ -1300,12 +1309,26 @@ static unsigned learned_grid( const acn_scene_handle* h, uint32_t seen, uint32_t
 #define ACN_LAUNCH( h, stage, stream, call ) do { int st_ = stage_begin( h, stage, stream ); if( st_ != ACN_OK ) return st_; call; \
     HIP_TRY( hipGetLastError() ); if( ( st_ = stage_end( h, stream ) ) != ACN_OK ) return st_; } while( 0 )
 
+/* What the primary rays of a call come from, handed down the whole chain (render_dispatch -> launch_render / render_lanes ->
+ * learn_rates -> render_chunk -> acn_launch_walk): sample positions [ n ][ 2 ], the pixel centres of the main pass from pixel
+ * `first` on (pos_xy == nullptr), or the caller's rays [ n ][ 6 ] -- seeded into the level-0 ray queue (k_rays.hip), where the
+ * first walk pass reads them instead of making camera rays. */
+struct Primary
+{
+    const double* pos_xy = nullptr;
+    size_t first = 0;
+    const double* rays = nullptr;
+};
+static Primary primary_positions( const double* pos_xy ) { Primary p; p.pos_xy = pos_xy; return p; }
+static Primary primary_main_pass( size_t first ) { Primary p; p.first = first; return p; }
+static Primary primary_rays( const double* rays ) { Primary p; p.rays = rays; return p; }
+
 /* One chunk of positions [ base, base + cnt ).  The whole chain -- per path level: ( k_shade_hits -> ) the passes of
  * k_walk -> k_shade x 4 size classes -> k_hard_shadow -> k_hard_path -- is enqueued blind: every kernel takes
  * its input count from the counter block of its level on the device, and a level that turns out to be empty costs a few
  * launches of waves that exit at once.  The host synchronises ONCE, at the end, to read the counter blocks: overflow
  * flags (the chunk is then redone smaller) and statistics. */
-static int render_chunk( acn_scene_handle* h, const double* d_pos_xy, size_t first_pixel, uint32_t base, uint32_t cnt, TileOrder order,
+static int render_chunk( acn_scene_handle* h, const Primary& prim, uint32_t base, uint32_t cnt, TileOrder order,
                          hipStream_t stream, int* overflow, uint32_t* fill, double* dead_share )
 {
     *overflow = 0;
@@ -1316,6 +1339,14 @@ static int render_chunk( acn_scene_handle* h, const double* d_pos_xy, size_t fir
     const SceneArgs s = scene_args( h );
     const size_t lds = machine_lds_bytes( h );
     HIP_TRY( hipMemsetAsync( h->d_counts, 0, sizeof( uint32_t ) * QC_N * levels, stream ) );
+    if( prim.rays )
+    {
+        /* the caller's rays are generation 0 of level 0, one slot each (launch_render keeps a chunk within the ray queue) */
+        if( cnt > h->ws.cap[ WQ_RAYS ] ) return fail( ACN_ERR_DEVICE, "a chunk of rays larger than the ray queue" );
+        /* (a walk launch of the statistics: it does what k_walk's first pass does for positions, make the primary rays) */
+        ACN_LAUNCH( h, 0, stream, acn_launch_seed_rays( prim.rays, base, cnt, order, ( int )h->dev.prm.trace_depth, level_queues( h, 0 ), stream ) );
+    }
+    const uint32_t n_cam = prim.rays ? 0u : cnt;
     for( int level = 0; level < levels; level++ )
     {
         const LevelQ q = level_queues( h, level );
@@ -1343,8 +1374,8 @@ static int render_chunk( acn_scene_handle* h, const double* d_pos_xy, size_t fir
             /* (k_walk keeps its full grid unless the pass had no input at all: its rays multiply on the private stacks, and
              * hanging_lamp 600x800 lost 7 % with grids sized to the input) */
             qg.grid = ( level == 0 && pass == 0 ) || seen != 0 ? h->walk_grid : learned_grid( h, 0, cnt, 512u, h->walk_grid );
-            ACN_LAUNCH( h, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes, qg, lds, stream, s, d_pos_xy, first_pixel, base,
-                                                       level == 0 && pass == 0 ? cnt : 0u, order, h->d_accum, h->d_counters ) );
+            ACN_LAUNCH( h, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes, qg, lds, stream, s, prim.pos_xy, prim.first, base,
+                                                       level == 0 && pass == 0 ? n_cam : 0u, order, h->d_accum, h->d_counters ) );
         }
         /* ACN_SHADE_FISSION=1 (off by default: measured slower, see Tunables).  The two sample loops of a shading point share
          * nothing but the task record, so the level can fork: the direct-light loops and the shadow rays they defer on the side
@@ -1392,6 +1423,9 @@ static int render_chunk( acn_scene_handle* h, const double* d_pos_xy, size_t fir
     HIP_TRY( hipMemcpyAsync( h->h_counts, h->d_counts, sizeof( uint32_t ) * QC_N * levels, hipMemcpyDeviceToHost, stream ) );
     HIP_TRY( hipStreamSynchronize( stream ) );
     h->host_syncs++;
+    /* the seeded generation of a ray call is a known demand (demand), not a learned one: with its word cleared the queue marks,
+     * the learned passes and learn_rates see the counts of a position call, where level 0 has no generation 0 */
+    if( prim.rays ) h->h_counts[ QC_GEN + 0 ] = 0;
     uint32_t flags = 0;
     for( int level = 0; level < levels; level++ )
     {
@@ -1486,7 +1520,7 @@ static void set_rates( acn_scene_handle* h, uint32_t cnt, const uint32_t* fill, 
  * for itself and re-sized its queues in the middle of the frame.  A sample over the whole frame costs one short chain of
  * launches (a few ms; nothing next to a frame whose queues must be allocated anyway) and is trusted like a large chunk: the
  * queues are then sized ONCE, while the device is idle (launch_render; render_lanes for all lanes of a call). */
-static int learn_rates( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, hipStream_t stream, size_t plan_positions, unsigned plan_grid )
+static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipStream_t stream, size_t plan_positions, unsigned plan_grid )
 {
     if( rates_known( h ) || !h->tun.learn_sample || h->tun.chunk || h->tun.ws_uniform || n < 16384 ) return ACN_OK;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -1526,7 +1560,7 @@ static int learn_rates( acn_scene_handle* h, const double* d_pos_xy, size_t firs
         int overflow = 0;
         uint32_t fill[ WQ_N ];
         double dead_share = 0;
-        st = render_chunk( h, d_pos_xy, first, 0u, cnt, order, stream, &overflow, fill, &dead_share );
+        st = render_chunk( h, prim, 0u, cnt, order, stream, &overflow, fill, &dead_share );
         if( st != ACN_OK ) break;
         if( h->tun.debug_chunks )
             fprintf( stderr, "[acn sample] chain done after %.2f ms\n", since() );
@@ -1578,12 +1612,13 @@ static int learn_rates( acn_scene_handle* h, const double* d_pos_xy, size_t firs
     return st;
 }
 
-static int launch_render( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, double* d_out_rgb,
+static int launch_render( acn_scene_handle* h, const Primary& prim, size_t n, double* d_out_rgb,
                           const acn_render_opts* opts, hipStream_t stream )
 {
     if( opts && opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
     if( n == 0 ) return ACN_OK;
     if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many positions in one call" );
+    h->seeded = prim.rays != nullptr;
     int linear = ( opts && ( opts->flags & ACN_OPT_LINEAR_OUT ) ) ? 1 : 0;
     h->count_work = ( opts && ( opts->flags & ACN_OPT_COUNT_WORK ) ) || h->tun.count_work;
     h->shard_rank = 0; h->shard_world = 1;
@@ -1594,7 +1629,7 @@ static int launch_render( acn_scene_handle* h, const double* d_pos_xy, size_t fi
     }
     else if( opts && opts->shard_mode > ACN_SHARD_SAMPLES ) return fail( ACN_ERR_ARG, "unknown shard_mode" );
     h->stage_timing = ( opts && ( opts->flags & ACN_OPT_STAGE_TIMING ) ) || h->tun.stage_timing;
-    int st = learn_rates( h, d_pos_xy, first, n, stream, n, h->walk_grid > h->grid ? h->walk_grid : h->grid );
+    int st = learn_rates( h, prim, n, stream, n, h->walk_grid > h->grid ? h->walk_grid : h->grid );
     if( st != ACN_OK ) return st;
     /* (shard fields again: the learning pass renders unsharded) */
     if( opts && opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 ) { h->shard_rank = opts->shard_rank; h->shard_world = opts->shard_world; }
@@ -1658,13 +1693,17 @@ static int launch_render( acn_scene_handle* h, const double* d_pos_xy, size_t fi
         /* the planned chunk; a rest that is predicted to fill no queue beyond 85 % is taken whole (a second chunk would be
          * another whole chain of launches for a few positions); a retry is at most half of the chunk that overflowed
          * (acn_chunkplan.h) */
-        uint32_t cnt = acn_ctl_next( &h->ctl, n_slots - base, chunk, h->tun.chunk != 0, rates_known( h ), h->rate, h->ws.cap );
+        double plan[ WQ_N ];
+        for( int q = 0; q < WQ_N; q++ ) plan[ q ] = demand( h, q );
+        uint32_t cnt = acn_ctl_next( &h->ctl, n_slots - base, chunk, h->tun.chunk != 0, rates_known( h ), plan, h->ws.cap );
+        /* (the seeded generation of a ray call takes one ray-queue slot per position, also under ACN_CHUNK) */
+        if( prim.rays && cnt > h->ws.cap[ WQ_RAYS ] ) cnt = h->ws.cap[ WQ_RAYS ];
         int overflow = 0;
         uint32_t fill[ WQ_N ];
         double dead_share = 0;
         /* the work counters of a chunk that has to be redone must not count twice */
         if( h->count_work ) HIP_TRY( hipMemcpyAsync( h->d_counters_keep, h->d_counters, sizeof( unsigned long long ) * ACN_CNT_SLOTS, hipMemcpyDeviceToDevice, stream ) );
-        st = render_chunk( h, d_pos_xy, first, ( uint32_t )base, cnt, order, stream, &overflow, fill, &dead_share );
+        st = render_chunk( h, prim, ( uint32_t )base, cnt, order, stream, &overflow, fill, &dead_share );
         if( st != ACN_OK ) return st;
         if( h->tun.debug_chunks )
             fprintf( stderr, "[acn chunk] base %zu cnt %u %s target %.2f dead %.2f | fill T %u C %u HS %u HP %u R %u | per pos T %.1f C %.1f HS %.1f HP %.1f R %.1f | rate T %.1f C %.1f HS %.1f HP %.1f R %.1f | cap T %u C %u HS %u HP %u R %u\n",
@@ -1777,6 +1816,15 @@ __global__ void k_lane_scatter( const double* __restrict__ lane_out, size_t n_la
     out_rgb[ g * 3 ] = lane_out[ i * 3 ]; out_rgb[ g * 3 + 1 ] = lane_out[ i * 3 + 1 ]; out_rgb[ g * 3 + 2 ] = lane_out[ i * 3 + 2 ];
 }
 
+/* lane_rays[ i ] = the lane's i-th ray of a ray call (k_lane_gather for six doubles) */
+__global__ void k_lane_gather_rays( const double* __restrict__ rays, size_t n_lane, int lanes, int lane, double* __restrict__ lane_rays )
+{
+    size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
+    if( i >= n_lane ) return;
+    size_t g = lane_global_index( i, lanes, lane );
+    for( int k = 0; k < 6; k++ ) lane_rays[ i * 6 + k ] = rays[ g * 6 + k ];
+}
+
 /* A lane = a clone of the handle that borrows the resident scene and owns two streams, its events, counter blocks and a host
  * thread.  Making a stream takes ~10 ms of host time (tools/bench_alloc: 12 streams 120 - 130 ms, one after the other whatever thread
  * asks; events, pinned memory and hipMalloc of any size are free beside that), so six lanes with two streams each were 60 - 100 ms of
@@ -1820,6 +1868,17 @@ static int lane_objects( int device, bool side_stream, bool debug, acn_scene_han
     return ACN_OK;
 }
 
+/* a device buffer of at least `want` doubles: grown, never shrunk */
+static int grow_buffer( double** p, size_t* cap, size_t want )
+{
+    if( *cap >= want ) return ACN_OK;
+    if( *p ) hipFree( *p );
+    *p = nullptr; *cap = 0;
+    HIP_TRY( hipMalloc( p, sizeof( double ) * want ) );
+    *cap = want;
+    return ACN_OK;
+}
+
 static unsigned lane_grid( const acn_scene_handle* parent ) { return parent->tun.grid ? parent->tun.grid : parent->cus * 1u; }
 static void bind_lane( const acn_scene_handle* parent, int lanes, acn_scene_handle* l )
 {
@@ -1853,7 +1912,7 @@ static int lanes_for_counts( int tun_lanes, size_t n, uint64_t path_samples )
 }
 static int lanes_for( const acn_scene_handle* h, size_t n ) { return lanes_for_counts( h->tun.lanes, n, h->dev.prm.path_samples ); }
 
-static int render_lanes( acn_scene_handle* h, int lanes, const double* d_pos_xy, size_t first, size_t n, double* d_out_rgb,
+static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, size_t n, double* d_out_rgb,
                          const acn_render_opts* opts, hipStream_t stream )
 {
     /* ACN_DEBUG_CHUNKS: where a call's wall time goes before and after the lanes run (one line per call on stderr) */
@@ -1889,7 +1948,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const double* d_pos_xy,
     if( drained == hipSuccess && learn )
     {
         h->budget_div = 1;
-        learned = learn_rates( h, d_pos_xy, first, n, stream, n / ( size_t )lanes, lane_grid( h ) );
+        learned = learn_rates( h, prim, n, stream, n / ( size_t )lanes, lane_grid( h ) );
         if( learned == ACN_OK ) drained = hipStreamSynchronize( stream );
     }
     if( maker.joinable() ) maker.join();
@@ -1929,19 +1988,18 @@ static int render_lanes( acn_scene_handle* h, int lanes, const double* d_pos_xy,
             {
                 HIP_TRY( hipSetDevice( h->device ) );
                 if( cnt == 0 ) { l->events_used = 0; HIP_TRY( hipMemset( l->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) ); return ACN_OK; }
-                if( l->lane_buf_cap < cnt )
-                {
-                    if( l->d_lane_pos ) hipFree( l->d_lane_pos );
-                    if( l->d_lane_out ) hipFree( l->d_lane_out );
-                    l->d_lane_pos = l->d_lane_out = nullptr; l->lane_buf_cap = 0;
-                    HIP_TRY( hipMalloc( &l->d_lane_pos, sizeof( double ) * 2 * cnt ) );
-                    HIP_TRY( hipMalloc( &l->d_lane_out, sizeof( double ) * 3 * cnt ) );
-                    l->lane_buf_cap = cnt;
-                }
-                hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
-                                    d_pos_xy, first, ( uint64_t )h->dev.prm.image_width, cnt, lanes, k, l->d_lane_pos );
+                /* the lane's share of the input: positions (2 doubles each) or rays (6) */
+                int st = grow_buffer( &l->d_lane_in, &l->lane_in_cap, ( prim.rays ? 6 : 2 ) * cnt );
+                if( st == ACN_OK ) st = grow_buffer( &l->d_lane_out, &l->lane_out_cap, 3 * cnt );
+                if( st != ACN_OK ) return st;
+                if( prim.rays )
+                    hipLaunchKernelGGL( k_lane_gather_rays, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
+                                        prim.rays, cnt, lanes, k, l->d_lane_in );
+                else
+                    hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
+                                        prim.pos_xy, prim.first, ( uint64_t )h->dev.prm.image_width, cnt, lanes, k, l->d_lane_in );
                 HIP_TRY( hipGetLastError() );
-                int st = launch_render( l, l->d_lane_pos, 0, cnt, l->d_lane_out, &lane_opts, l->stream );
+                st = launch_render( l, prim.rays ? primary_rays( l->d_lane_in ) : primary_positions( l->d_lane_in ), cnt, l->d_lane_out, &lane_opts, l->stream );
                 if( st != ACN_OK ) return st;
                 hipLaunchKernelGGL( k_lane_scatter, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
                                     ( const double* )l->d_lane_out, cnt, lanes, k, d_out_rgb );
@@ -1957,6 +2015,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const double* d_pos_xy,
     {
         acn_scene_handle* l = h->lanes[ k ];
         l->budget_div = ( size_t )lanes;
+        l->seeded = prim.rays != nullptr;
         const size_t cnt = lane_count( n, lanes, k );
         if( cnt ) { int st = ensure_workspace( l, cnt ); if( st != ACN_OK ) return st; }
     }
@@ -2011,7 +2070,7 @@ static acn_render_opts opts_of( const acn_render_opts* in )
 #define ACN_OPTS_VIEW const acn_render_opts opts_seen_ = opts_of( opts ); opts = &opts_seen_;
 
 /* one pipeline run on the handle itself, or the concurrent lanes */
-static int render_dispatch( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, double* d_out_rgb,
+static int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, double* d_out_rgb,
                             const acn_render_opts* opts, hipStream_t stream )
 {
     int lanes = lanes_for( h, n );
@@ -2028,7 +2087,7 @@ static int render_dispatch( acn_scene_handle* h, const double* d_pos_xy, size_t 
         if( known )
         {
             double need = 0;
-            for( int q = 0; q < WQ_N; q++ ) need += known->rate[ q ] * ( double )n / 0.7 * ( double )wq_bytes[ q ];
+            for( int q = 0; q < WQ_N; q++ ) need += queue_demand( known->rate, q, prim.rays != nullptr ) * ( double )n / 0.7 * ( double )wq_bytes[ q ];
             /* (sticky by 30 %: rates move a little from call to call, and changing the arrangement re-allocates everything) */
             if( need > ( h->one_lane ? 0.7 : 1.0 ) * ( double )h->workspace_budget ) lanes = 1;
         }
@@ -2048,10 +2107,10 @@ static int render_dispatch( acn_scene_handle* h, const double* d_pos_xy, size_t 
     {
         for( acn_scene_handle* l : h->lanes ) free_workspace( l );   /* the bound is the handle's, whoever uses it */
         if( !h->lanes.empty() ) inherit( h, h->lanes[ 0 ] );
-        return launch_render( h, d_pos_xy, first, n, d_out_rgb, opts, stream );
+        return launch_render( h, prim, n, d_out_rgb, opts, stream );
     }
     free_workspace( h );
-    return render_lanes( h, lanes, d_pos_xy, first, n, d_out_rgb, opts, stream );   /* (makes the lanes it lacks) */
+    return render_lanes( h, lanes, prim, n, d_out_rgb, opts, stream );   /* (makes the lanes it lacks) */
 }
 
 extern "C" int acn_render_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rgb,
@@ -2061,7 +2120,7 @@ extern "C" int acn_render_positions_dev( acn_scene_handle* h, const void* d_pos_
     if( !h || ( n && ( !d_pos_xy || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
     HIP_TRY( hipSetDevice( h->device ) );
     hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    int st = render_dispatch( h, ( const double* )d_pos_xy, 0, n, ( double* )d_out_rgb, opts, stream );
+    int st = render_dispatch( h, primary_positions( ( const double* )d_pos_xy ), n, ( double* )d_out_rgb, opts, stream );
     if( st != ACN_OK ) return st;
     if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
     return ACN_OK;
@@ -2075,10 +2134,28 @@ extern "C" int acn_render_main_pass_dev( acn_scene_handle* h, size_t first, size
     if( first + count > h->dev.prm.image_width * h->dev.prm.image_height ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
     HIP_TRY( hipSetDevice( h->device ) );
     hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    int st = render_dispatch( h, nullptr, first, count, ( double* )d_out_rgb, opts, stream );
+    int st = render_dispatch( h, primary_main_pass( first ), count, ( double* )d_out_rgb, opts, stream );
     if( st != ACN_OK ) return st;
     if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
     return ACN_OK;
+}
+
+/* an entry point on host buffers: n records of in_len doubles copied in, the device-buffer call `dev( d_in, d_out )` (on the
+ * handle's own stream: synchronous), n records of out_len doubles copied out */
+template< class DevCall >
+static int on_host_buffers( acn_scene_handle* h, const double* in, size_t in_len, size_t n, double* out, size_t out_len, DevCall dev )
+{
+    HIP_TRY( hipSetDevice( h->device ) );
+    double* d_in = nullptr; double* d_out = nullptr;
+    HIP_TRY( hipMalloc( &d_in, sizeof( double ) * in_len * n ) );
+    hipError_t e = hipMalloc( &d_out, sizeof( double ) * out_len * n );
+    if( e != hipSuccess ) { hipFree( d_in ); return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) ); }
+    int st = ACN_OK;
+    if( hipMemcpy( d_in, in, sizeof( double ) * in_len * n, hipMemcpyHostToDevice ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "H2D copy failed" );
+    if( st == ACN_OK ) st = dev( d_in, d_out );
+    if( st == ACN_OK && hipMemcpy( out, d_out, sizeof( double ) * out_len * n, hipMemcpyDeviceToHost ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "D2H copy failed" );
+    hipFree( d_in ); hipFree( d_out );
+    return st;
 }
 
 extern "C" int acn_render_positions( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rgb,
@@ -2087,20 +2164,64 @@ extern "C" int acn_render_positions( acn_scene_handle* h, const double* pos_xy, 
     ACN_OPTS_VIEW
     if( !h || ( n && ( !pos_xy || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
     if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    double* d_pos = nullptr; double* d_out = nullptr;
-    HIP_TRY( hipMalloc( &d_pos, sizeof( double ) * 2 * n ) );
-    hipError_t e = hipMalloc( &d_out, sizeof( double ) * 3 * n );
-    if( e != hipSuccess ) { hipFree( d_pos ); return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) ); }
-    int st = ACN_OK;
-    acn_render_opts o{};
-    if( opts ) o = *opts;
+    acn_render_opts o = *opts;
     o.stream = nullptr;
-    if( hipMemcpy( d_pos, pos_xy, sizeof( double ) * 2 * n, hipMemcpyHostToDevice ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "H2D copy failed" );
-    if( st == ACN_OK ) st = acn_render_positions_dev( h, d_pos, n, d_out, &o );
-    if( st == ACN_OK && hipMemcpy( out_rgb, d_out, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "D2H copy failed" );
-    hipFree( d_pos ); hipFree( d_out );
-    return st;
+    return on_host_buffers( h, pos_xy, 2, n, out_rgb, 3, [ & ]( double* d_pos, double* d_out ) { return acn_render_positions_dev( h, d_pos, n, d_out, &o ); } );
+}
+
+/* ---- caller-supplied primary rays (k_rays.hip) ---- */
+extern "C" int acn_render_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, void* d_out_rgb, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !d_rays || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many rays in one call" );
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    /* every ray is checked before anything is rendered: the lowest index of a refused one, one word read back */
+    if( !h->d_ray_check ) HIP_TRY( hipMalloc( &h->d_ray_check, sizeof( unsigned long long ) ) );
+    HIP_TRY( hipMemsetAsync( h->d_ray_check, 0xFF, sizeof( unsigned long long ), stream ) );
+    acn_launch_check_rays( ( const double* )d_rays, n, h->d_ray_check, stream );
+    HIP_TRY( hipGetLastError() );
+    unsigned long long bad = 0;
+    HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check, sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
+    HIP_TRY( hipStreamSynchronize( stream ) );
+    if( bad < n ) return fail( ACN_ERR_ARG, "ray " + std::to_string( bad ) + ": a component is not finite or the direction has no length" );
+    int st = render_dispatch( h, primary_rays( ( const double* )d_rays ), n, ( double* )d_out_rgb, opts, stream );
+    if( st != ACN_OK ) return st;
+    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_render_rays( acn_scene_handle* h, const double* rays, size_t n, double* out_rgb, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !rays || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    return on_host_buffers( h, rays, 6, n, out_rgb, 3, [ & ]( double* d_rays, double* d_out ) { return acn_render_rays_dev( h, d_rays, n, d_out, &o ); } );
+}
+
+extern "C" int acn_camera_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rays, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !d_pos_xy || !d_out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many positions in one call" );
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    acn_launch_camera_rays( h->dev, ( const double* )d_pos_xy, n, ( double* )d_out_rays, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rays )
+{
+    if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    return on_host_buffers( h, pos_xy, 2, n, out_rays, 6, [ & ]( double* d_pos, double* d_out ) { return acn_camera_rays_dev( h, d_pos, n, d_out, nullptr ); } );
 }
 
 /* ---- sharding of whole positions: tiles of ACN_SHARD_TILE, round-robin (plain arithmetic, no GPU) ---- */
@@ -2154,7 +2275,7 @@ extern "C" int acn_render_main_pass_shard_dev( acn_scene_handle* h, size_t first
         hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( mine + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
                             ( const double* )nullptr, first, ( uint64_t )h->dev.prm.image_width, mine, ( int )world, ( int )rank, h->d_shard_pos );
         HIP_TRY( hipGetLastError() );
-        int st = render_dispatch( h, h->d_shard_pos, 0, mine, ( double* )d_part, opts, stream );
+        int st = render_dispatch( h, primary_positions( h->d_shard_pos ), mine, ( double* )d_part, opts, stream );
         if( st != ACN_OK ) return st;
     }
     if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );

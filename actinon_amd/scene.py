@@ -261,6 +261,29 @@ class Handle:
         o = self._opts(linear, stream)
         check(hip.acn_render_main_pass_dev(self.h, first, count, d_out_ptr, C.byref(o)), "acn_render_main_pass_dev")
 
+    def render_rays(self, rays, linear=False):
+        """Radiance of caller-supplied rays (acn_render_rays): rays [n,6] float64 origin, direction -> rgb [n,3] float64."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.empty((r.shape[0], 3), dtype=np.float64)
+        o = self._opts(linear, None)
+        check(hip.acn_render_rays(self.h, r.ctypes.data, r.shape[0], out.ctypes.data, C.byref(o)), "acn_render_rays")
+        return out
+
+    def render_rays_dev(self, d_rays_ptr, n, d_out_ptr, linear=False, stream=None):
+        o = self._opts(linear, stream)
+        check(hip.acn_render_rays_dev(self.h, d_rays_ptr, n, d_out_ptr, C.byref(o)), "acn_render_rays_dev")
+
+    def camera_rays(self, pos_xy):
+        """The rays the pipeline casts for sample positions (acn_camera_rays): pos_xy [n,2] -> [n,6] origin, direction."""
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((pos.shape[0], 6), dtype=np.float64)
+        check(hip.acn_camera_rays(self.h, pos.ctypes.data, pos.shape[0], out.ctypes.data), "acn_camera_rays")
+        return out
+
+    def camera_rays_dev(self, d_pos_ptr, n, d_out_ptr, stream=None):
+        o = self._opts(False, stream)
+        check(hip.acn_camera_rays_dev(self.h, d_pos_ptr, n, d_out_ptr, C.byref(o)), "acn_camera_rays_dev")
+
     def render_main_pass_shard_dev(self, first, count, rank, world, d_part_ptr, linear=True, stream=None):
         """This rank's tiles of the main pass (acn_shard_tile_*), into a part of acn_shard_tile_padded(count, world) rows."""
         o = self._opts(linear, stream)

@@ -222,6 +222,23 @@ int acn_render_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t 
 int acn_render_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, void* d_out_rgb,
                               const acn_render_opts* opts );
 
+/* Radiance of caller-supplied rays (custom cameras, panoramas, lens samples, light probes): the body of lum_machine_s_func
+ * (src/scene.c:956-1013) after its camera ray.  rays: [ n ][ 6 ] f64 origin, direction (the layout of acn_query_rays).
+ * out_rgb[ i ] = cl_s_sat( background_color ) if ray i hits nothing, else cl_s_sat( scene_s_lum( ray, offs, trans,
+ * trace_depth, 1.0 ) ); linear with ACN_OPT_LINEAR_OUT.  Each direction goes through v3d_s_of_length( d, 1 )
+ * (src/vectors.h:148-154), which leaves it unchanged, bit for bit, when |d|^2 is within 1e-8 of 1.  A non-finite component or
+ * a zero direction (|d|^2 not a positive finite number) anywhere fails the call with ACN_ERR_ARG before anything is written;
+ * acn_last_error names the first such ray.  opts: as for the position calls (flags, cancel, stream, ACN_SHARD_SAMPLES).
+ * The scene's image_width, image_height and camera fields are not used; gamma, background_color and every sampling
+ * parameter are.  Streams as for acn_render_positions_dev; the _dev call synchronises the stream once more, before it
+ * renders, to read the check's one word.  Tile sharding is for positions: a caller shards rays by slicing the array. */
+int acn_render_rays( acn_scene_handle* h, const double* rays, size_t n, double* out_rgb, const acn_render_opts* opts );
+int acn_render_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, void* d_out_rgb, const acn_render_opts* opts );
+/* The rays the pipeline casts for sample positions (camera_ray, src/scene.c:980-990), bit for bit: out_rays[ i ] = origin,
+ * direction [ 6 ] f64 of pos_xy[ i ].  The _dev variant follows the stream rules of acn_render_positions_dev. */
+int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rays );
+int acn_camera_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rays, const acn_render_opts* opts );
+
 /* Sharding of whole positions: the n positions of a call (or pixels of a frame) are cut into tiles of ACN_SHARD_TILE
  * consecutive positions dealt round-robin to the ranks -- interleaving balances sky, floor and glass between them.
  * These three are plain arithmetic (no GPU): */
