@@ -7,6 +7,11 @@ ACN_OPT_COUNT_WORK = 2
 ACN_OPT_STAGE_TIMING = 4
 ACN_SHARD_NONE, ACN_SHARD_SAMPLES = 0, 1
 ACN_SHARD_TILE = 256
+# surface records (acn_surface_*): doubles per record, modes, kind bits
+ACN_SURF_STRIDE = 16
+ACN_SURF_FIRST_HIT, ACN_SURF_FOLLOW = 0, 1
+(ACN_SURF_EMITTER, ACN_SURF_DIFFUSE, ACN_SURF_CHROMATIC, ACN_SURF_FRESNEL, ACN_SURF_TRANSPARENT, ACN_SURF_LIGHT_ROOT,
+ ACN_SURF_CUT) = 1, 2, 4, 8, 16, 32, 64
 
 ACN_OK, ACN_ERR_ARG, ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV, ACN_ERR_DEVICE, ACN_ERR_CANCELLED = 0, -1, -2, -3, -4, -5
 

@@ -72,6 +72,12 @@ void acn_launch_seed_rays( const double* rays, uint32_t base, uint32_t cnt, Tile
 void acn_launch_check_rays( const double* rays, size_t n, unsigned long long* first_bad, hipStream_t stream );
 void acn_launch_camera_rays( const DevScene& sc, const double* pos_xy, size_t n, double* out, hipStream_t stream );
 
+/* surface records (k_surface.hip): one ray per lane, no queues.  mode: ACN_SURF_*.  Exactly one of rays ( [ n ][ 6 ] ) and pos_xy
+ * ( [ n ][ 2 ], through camera_ray ) is given; out: [ n ][ ACN_SURF_STRIDE ].  lds_bytes: the staged nodes (lds_nodes) and the
+ * CSG stacks, as the machine kernels get them.  s.dev.flags: the word that takes ACN_FLAG_STACK_OVERFLOW. */
+void acn_launch_surface( uint32_t mode, bool lds_nodes, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
+                         const double* rays, const double* pos_xy, size_t n, double* out );
+
 /* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
 struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
 int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */

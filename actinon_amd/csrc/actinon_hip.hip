@@ -245,6 +245,7 @@ struct acn_scene_handle
     double* d_lane_out = nullptr; size_t lane_out_cap = 0;     /* ... and its results */
     double* d_shard_pos = nullptr; size_t shard_pos_cap = 0;                                /* acn_render_main_pass_shard_dev: the rank's positions */
     unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
+    uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
     bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
     std::string lane_error;
     bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
@@ -1060,6 +1061,7 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( h->d_lane_out ) hipFree( h->d_lane_out );
     if( h->d_shard_pos ) hipFree( h->d_shard_pos );
     if( h->d_ray_check ) hipFree( h->d_ray_check );
+    if( h->d_surface_flags ) hipFree( h->d_surface_flags );
     if( !h->is_lane )   /* a lane borrows the resident scene of its parent */
     {
         if( h->d_nodes ) hipFree( h->d_nodes );
@@ -2222,6 +2224,92 @@ extern "C" int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_
     if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
     if( n == 0 ) return ACN_OK;
     return on_host_buffers( h, pos_xy, 2, n, out_rays, 6, [ & ]( double* d_pos, double* d_out ) { return acn_camera_rays_dev( h, d_pos, n, d_out, nullptr ); } );
+}
+
+/* ---- surface records (k_surface.hip) ---- */
+static int surface_dev( acn_scene_handle* h, const double* d_rays, const double* d_pos_xy, size_t n, uint32_t mode, double* d_out,
+                        const acn_render_opts* opts )
+{
+    if( !h || ( n && ( !( d_rays || d_pos_xy ) || !d_out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
+    if( opts && opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
+    if( n == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    if( !h->d_surface_flags )
+    {
+        HIP_TRY( hipMalloc( &h->d_surface_flags, sizeof( uint32_t ) ) );
+        HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
+    }
+    if( d_rays )
+    {
+        /* every ray is checked before anything is written: the lowest index of a refused one, one word read back */
+        if( !h->d_ray_check ) HIP_TRY( hipMalloc( &h->d_ray_check, sizeof( unsigned long long ) ) );
+        HIP_TRY( hipMemsetAsync( h->d_ray_check, 0xFF, sizeof( unsigned long long ), stream ) );
+        acn_launch_check_rays( d_rays, n, h->d_ray_check, stream );
+        HIP_TRY( hipGetLastError() );
+        unsigned long long bad = 0;
+        HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check, sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
+        HIP_TRY( hipStreamSynchronize( stream ) );
+        if( bad < n ) return fail( ACN_ERR_ARG, "ray " + std::to_string( bad ) + ": a component is not finite or the direction has no length" );
+    }
+    SceneArgs s = scene_args( h );
+    s.dev.flags = h->d_surface_flags;   /* the pipeline's word stays the pipeline's */
+    acn_launch_surface( mode, h->lds_bytes != 0, machine_lds_bytes( h ), stream, s, d_rays, d_pos_xy, n, d_out );
+    HIP_TRY( hipGetLastError() );
+    if( !( opts && opts->stream ) )
+    {
+        uint32_t flags = 0;
+        HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags, sizeof( flags ), hipMemcpyDeviceToHost, stream ) );
+        HIP_TRY( hipStreamSynchronize( stream ) );
+        if( flags )
+        {
+            HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
+            return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow in a surface call" );
+        }
+    }
+    return ACN_OK;
+}
+
+extern "C" int acn_surface_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && !d_rays ) ) return fail( ACN_ERR_ARG, "null argument" );
+    return surface_dev( h, ( const double* )d_rays, nullptr, n, mode, ( double* )d_out, opts );
+}
+
+extern "C" int acn_surface_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && !d_pos_xy ) ) return fail( ACN_ERR_ARG, "null argument" );
+    return surface_dev( h, nullptr, ( const double* )d_pos_xy, n, mode, ( double* )d_out, opts );
+}
+
+/* the host-buffer forms: synchronous, on the handle's own stream */
+static int surface_host( acn_scene_handle* h, const double* in, size_t in_len, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
+{
+    if( !h || ( n && ( !in || !out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
+    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
+    if( n == 0 ) return ACN_OK;
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    return on_host_buffers( h, in, in_len, n, out, ACN_SURF_STRIDE, [ & ]( double* d_in, double* d_out )
+    {
+        return in_len == 6 ? surface_dev( h, d_in, nullptr, n, mode, d_out, &o ) : surface_dev( h, nullptr, d_in, n, mode, d_out, &o );
+    } );
+}
+
+extern "C" int acn_surface_rays( acn_scene_handle* h, const double* rays, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    return surface_host( h, rays, 6, n, mode, out, opts );
+}
+
+extern "C" int acn_surface_positions( acn_scene_handle* h, const double* pos_xy, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    return surface_host( h, pos_xy, 2, n, mode, out, opts );
 }
 
 /* ---- sharding of whole positions: tiles of ACN_SHARD_TILE, round-robin (plain arithmetic, no GPU) ---- */

@@ -344,6 +344,54 @@ class Handle:
         return list(out)
 
 
+    # surface records (acn_surface_*): what a ray meets instead of the radiance it carries
+    def _surface_mode(self, follow):
+        return abi.ACN_SURF_FOLLOW if follow else abi.ACN_SURF_FIRST_HIT
+
+    def surface_rays(self, rays, follow=False):
+        """The surface each ray meets (acn_surface_rays): rays [n,6] float64 origin, direction -> Surface over [n,16].
+        follow=True follows the dominant specular branch to the first diffuse or emitting surface."""
+        r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        out = np.empty((r.shape[0], abi.ACN_SURF_STRIDE), dtype=np.float64)
+        o = self._opts(False, None)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        check(hip.acn_surface_rays(self.h, r.ctypes.data, r.shape[0], self._surface_mode(follow), out.ctypes.data, C.byref(o)),
+              "acn_surface_rays")
+        return Surface(out)
+
+    def surface_positions(self, pos_xy, follow=False):
+        """The same for sample positions, through the camera (acn_surface_positions): pos_xy [n,2] -> Surface."""
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((pos.shape[0], abi.ACN_SURF_STRIDE), dtype=np.float64)
+        o = self._opts(False, None)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        check(hip.acn_surface_positions(self.h, pos.ctypes.data, pos.shape[0], self._surface_mode(follow), out.ctypes.data,
+                                        C.byref(o)), "acn_surface_positions")
+        return Surface(out)
+
+    def surface_rays_dev(self, d_rays_ptr, n, d_out_ptr, follow=False, stream=None):
+        """Device buffers: d_out [n,16] float64, 128-byte aligned; enqueued on `stream` (None: synchronous)."""
+        o = self._opts(False, stream)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        check(hip.acn_surface_rays_dev(self.h, d_rays_ptr, n, self._surface_mode(follow), d_out_ptr, C.byref(o)),
+              "acn_surface_rays_dev")
+
+    def surface_positions_dev(self, d_pos_ptr, n, d_out_ptr, follow=False, stream=None):
+        o = self._opts(False, stream)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        check(hip.acn_surface_positions_dev(self.h, d_pos_ptr, n, self._surface_mode(follow), d_out_ptr, C.byref(o)),
+              "acn_surface_positions_dev")
+
+    def pick(self, x, y):
+        """The object under sample position (x, y): None on a miss, else node (enter object if any, else exit object), its
+        type name, distance and position."""
+        s = self.surface_positions(np.array([[x, y]], dtype=np.float64))
+        if not s.hit[0]:
+            return None
+        node = int(s.enter[0]) if s.enter[0] >= 0 else int(s.exit[0])
+        return {"node": node, "type": abi.NODE_TYPES.get(int(self.flat.node(node).type)), "distance": float(s.distance[0]),
+                "position": s.position[0].copy()}
+
     # test seam acn_query_rays (include/actinon_hip.h): the device's traversal shortcuts one ray per lane
     QUERY_OPS = {"hit_lane": 0, "hit_uni": 1, "element_hit": 2, "side_lane": 3, "side_uni": 4, "prune": 5, "leaf_iv": 6,
                  "trans": 7, "occluded": 8, "cone_cull": 9, "sc_hit": 10, "elements": 11}
@@ -370,6 +418,31 @@ class Handle:
         check(hip.acn_query_rays(self.h, code, int(node), None if r is None else r.ctypes.data, cnt,
                                  None if lim is None else lim.ctypes.data, out.ctypes.data), "acn_query_rays")
         return out[:cnt]
+
+class Surface:
+    """Named views over the [n,16] float64 records of a surface call (include/actinon_hip.h, acn_surface_rays)."""
+
+    def __init__(self, raw):
+        raw = np.asarray(raw, dtype=np.float64)
+        if raw.ndim != 2 or raw.shape[1] != abi.ACN_SURF_STRIDE:
+            raise ValueError(f"surface records are [n,{abi.ACN_SURF_STRIDE}] float64, got {raw.shape}")
+        self.raw = raw
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    distance = property(lambda self: self.raw[:, 0])
+    position = property(lambda self: self.raw[:, 1:4])
+    exit_normal = property(lambda self: self.raw[:, 4:7])
+    normal = property(lambda self: -self.raw[:, 4:7])          # the normal that faces the viewer
+    enter = property(lambda self: self.raw[:, 7].astype(np.int64))
+    exit = property(lambda self: self.raw[:, 8].astype(np.int64))
+    albedo = property(lambda self: self.raw[:, 9:12])
+    kind = property(lambda self: self.raw[:, 12].astype(np.int64))
+    hops = property(lambda self: self.raw[:, 13].astype(np.int64))
+    weight = property(lambda self: self.raw[:, 14])
+    hit = property(lambda self: self.raw[:, 0] < np.inf)
+
 
 def main_pass_positions(width, height, first=0, count=None):
     """Pixel centres of the main pass, row-major (scene.c:1110-1119)."""

@@ -239,6 +239,56 @@ int acn_render_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, void
 int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rays );
 int acn_camera_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rays, const acn_render_opts* opts );
 
+/* The surface a ray meets, one record per ray: what a denoiser takes as guides (depth, normal, albedo), what compositing and
+ * picking need (object ids), none of it sampled.  out[ i ][ 0 .. ACN_SURF_STRIDE ), all f64, integers stored as doubles:
+ *   [ 0 ]       distance: the `a` of scene_s_trans_hit (src/scene.c:362-382: lights first, matter only if strictly nearer);
+ *               ACN_SURF_FOLLOW: the sum of the `a` of every segment, added in hop order.  inf: the (last) ray hit nothing
+ *   [ 1 .. 3 ]  position ray.p + ray.d * a of the reported hit (as scene_s_lum forms pos)
+ *   [ 4 .. 6 ]  trans.exit_nor, bit for bit; the normal that faces the viewer is its negative (src/scene.c:530)
+ *   [ 7 ], [ 8 ] enter_obj, exit_obj: node indices of the media transition, -1 = none
+ *   [ 9 .. 11 ] obj_color( s, position ), s = enter_obj if there is one, else exit_obj (src/objects.c:411-422, textures included)
+ *   [ 12 ]      ACN_SURF_* kind bits: the material rules of scene_s_lum (src/scene.c:432-470) for this hit
+ *   [ 13 ]      hops followed (0 with ACN_SURF_FIRST_HIT)
+ *   [ 14 ]      weight: the product of the shares of the branches followed (1.0 with no hop)
+ *   [ 15 ]      0 (reserved)
+ * A miss has inf, -1, -1 in [ 0 ], [ 7 ], [ 8 ], keeps [ 13 ] and [ 14 ], and is zero elsewhere.
+ * mode ACN_SURF_FIRST_HIT reports the first surface.  ACN_SURF_FOLLOW follows the dominant specular branch to the first
+ * diffuse or emitting surface -- through a glass to the table behind it.  This is a definition of this library, not a function
+ * of the reference; its terms are the intensities scene_s_lum hands its children (src/scene.c:473-653) with trace_min_intensity
+ * left out.  At each hit, in this order:
+ *   EMITTER: stop.
+ *   refl = fresnel_reflectivity > 0 ? fresnel_reflection( d, exit_nor, trix, &refl_d ) * fresnel_reflectivity : 0;  rest = 1 - refl
+ *   w[ 0 ] = refl                                                                   -> ray ( pos, refl_d )
+ *   w[ 1 ] = chromatic_reflectivity * rest;  rest = rest * ( 1 - chromatic_reflectivity )  -> ( pos, v_reflection( d, exit_nor ) )
+ *   w[ 2 ] = diffuse_reflectivity * rest;    rest = rest * ( 1 - diffuse_reflectivity )    -> stop
+ *   w[ 3 ] = transparent ? rest : 0          -> ( ray.p + ray.d * ( a + 2 * f3_eps ), fresnel_refraction( d, exit_nor, trix ) )
+ *   The largest w wins, the lowest index on a tie; if it is not positive or it is w[ 2 ]: stop.  Else weight *= w, hops += 1.
+ * A chain reports at most max( trace_depth, 1 ) hits: a hit of that number that would continue is reported with ACN_SURF_CUT.
+ * A continued ray that hits nothing reports a miss with the hops and the weight so far.
+ * rays: the contract of acn_render_rays (each direction through v3d_s_of_length( d, 1 ); a non-finite component or a zero
+ * direction fails the whole call with ACN_ERR_ARG before anything is written, acn_last_error names the first such ray).
+ * Positions go through camera_ray: acn_surface_positions( pos ) equals acn_surface_rays( acn_camera_rays( pos ) ) bit for bit.
+ * opts: only `stream` is used, by the _dev calls, with the rules of acn_render_positions_dev (the ray call synchronises the
+ * stream once, to read the check's word; the position call never); shard_world > 1 or an unknown mode is ACN_ERR_ARG.
+ * The _dev buffers should be 128-byte aligned: a record is 128 bytes and every lane writes its own line whole.  A surface call
+ * uses no work queue and changes nothing a render call on the same handle sees.  A CSG nesting too deep for the device stacks
+ * fails a call on the handle's own stream with ACN_ERR_UNSUPPORTED; a call on a caller's stream cannot wait for the word, which is then
+ * reported by the handle's next surface call on its own stream. */
+#define ACN_SURF_STRIDE 16          /* doubles per record: 128 bytes */
+#define ACN_SURF_FIRST_HIT 0u
+#define ACN_SURF_FOLLOW    1u       /* follow the dominant specular branch to the first diffuse / emitting surface */
+#define ACN_SURF_EMITTER     1u     /* enter_obj has radiance > 0 */
+#define ACN_SURF_DIFFUSE     2u     /* diffuse_reflectivity > 0 after the exit rule */
+#define ACN_SURF_CHROMATIC   4u     /* chromatic_reflectivity > 0 after the exit rule */
+#define ACN_SURF_FRESNEL     8u     /* fresnel_reflectivity > 0 after the rules (src/scene.c:451, :467) */
+#define ACN_SURF_TRANSPARENT 16u
+#define ACN_SURF_LIGHT_ROOT  32u    /* the hit came from the light compound */
+#define ACN_SURF_CUT         64u    /* ACN_SURF_FOLLOW stopped because of trace_depth */
+int acn_surface_rays( acn_scene_handle* h, const double* rays, size_t n, uint32_t mode, double* out, const acn_render_opts* opts );
+int acn_surface_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts );
+int acn_surface_positions( acn_scene_handle* h, const double* pos_xy, size_t n, uint32_t mode, double* out, const acn_render_opts* opts );
+int acn_surface_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts );
+
 /* Sharding of whole positions: the n positions of a call (or pixels of a frame) are cut into tiles of ACN_SHARD_TILE
  * consecutive positions dealt round-robin to the ranks -- interleaving balances sky, floor and glass between them.
  * These three are plain arithmetic (no GPU): */
