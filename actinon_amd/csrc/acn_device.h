@@ -25,23 +25,9 @@
 
 #define DEV __device__ __forceinline__
 #define DEVN __device__ __noinline__
-/* inlining policy of the two CSG machines (measured on MI355X) */
-#ifndef ACN_SIDE_INLINE
-#define ACN_SIDE_INLINE 1
-#endif
-#ifndef ACN_HIT_INLINE
-#define ACN_HIT_INLINE 1
-#endif
-#if ACN_SIDE_INLINE
+/* inlining policy of the two CSG machines: both in line (measured on MI355X) */
 #define DEV_SIDE __device__ __forceinline__
-#else
-#define DEV_SIDE __device__ __noinline__
-#endif
-#if ACN_HIT_INLINE
 #define DEV_HIT __device__ __forceinline__
-#else
-#define DEV_HIT __device__ __noinline__
-#endif
 
 #define F3_INF ( __builtin_huge_val() )
 #define F3_MAG 1E+30
@@ -99,7 +85,6 @@ struct GMat
 typedef const GNode   ACN_CONST* NodeP;
 typedef const GMat    ACN_CONST* MatP;
 typedef const int32_t ACN_CONST* ElemP;
-typedef const double  ACN_CONST* CDblP;
 typedef const acn_texture ACN_CONST* TexP;
 
 /* node array staged in LDS (per workgroup) for the kernels whose node accesses are per-lane */
@@ -109,39 +94,16 @@ typedef double ACN_LDS* LdsF64P;
 typedef uint32_t ACN_LDS* LdsU32P;
 /* dynamic LDS of the machine kernels: [ staged node array (optional) ][ CSG stacks of the block's 256 lanes ] */
 extern __shared__ __attribute__( ( aligned( 16 ) ) ) double acn_lds_raw[];
-/* ACN_POOLED (acn_pipeline.h; built in round 4, measured slower, OFF): the machine kernels pool the rays of a workgroup's four
- * waves per root element */
-#ifndef ACN_POOLED
-#define ACN_POOLED 0
-#endif
 #ifndef ACN_LDS_DEPTH
-#if ACN_POOLED
-#define ACN_LDS_DEPTH 2                 /* (the third level's 10 KB per workgroup go to the ray pool) */
-#else
 #define ACN_LDS_DEPTH 3                 /* stack levels kept in LDS; deeper nesting continues in scratch */
-#endif
 #endif
 #define ACN_LDS_LANES 256               /* block size of the kernels that provide the stack area */
 /* per level and lane: a 8 B, parked normal 24 B, w 4 B, side 4 B; doubles first (alignment):
  * [ a : D x 256 ][ nx, ny, nz : 3 x D x 256 ][ w : D x 256 ][ side : D x 256 ] */
 #define ACN_LDS_STACK_BYTES ( ACN_LDS_DEPTH * ACN_LDS_LANES * 40 )
 #define ACN_NO_LDS_STACK 0xFFFFFFFFu
-/* behind the stacks: the ray pool of the workgroup (pooled_machine_hit): six planes of 256 doubles (ray in / result out), one
- * plane of 256 words (owners), two sets of the four waves' counts */
-#if ACN_POOLED
-#define ACN_LDS_POOL_BYTES ( 6 * ACN_LDS_LANES * 8 + ACN_LDS_LANES * 4 + 64 )
-#else
-#define ACN_LDS_POOL_BYTES 0
-#endif
-/* behind those: the ray origin of the lock-step machine at hand, one per lane (OrgLds): three planes of 256 doubles */
-#ifndef ACN_PARK_ORIGIN
-#define ACN_PARK_ORIGIN 1
-#endif
-#if ACN_PARK_ORIGIN
+/* behind the stacks: the ray origin of the lock-step machine at hand, one per lane (OrgLds): three planes of 256 doubles */
 #define ACN_LDS_ORG_BYTES ( 3 * ACN_LDS_LANES * 8 )
-#else
-#define ACN_LDS_ORG_BYTES 0
-#endif
 
 /* One entry of a simple compound's pre-order table (simple_compound_hit): everything a visit needs -- the element's
  * envelope, its type and the two links -- in ONE 48-byte record, i.e. one memory round trip per visited node instead
@@ -157,21 +119,6 @@ struct SCEntry
 #define ACN_SC_SPHERE 0x10000u
 #define ACN_SC_ROUGH  0x20000u
 #define ACN_SC_BOUNDING 0x40000u   /* the upload step has verified that the envelope contains every leaf below the entry (all of them spheres) */
-#ifndef ACN_SC_CULL
-#define ACN_SC_CULL 1
-#endif
-#ifndef ACN_SC_TWO_ORDERS
-#define ACN_SC_TWO_ORDERS 1
-#endif
-#ifndef ACN_SC_EARLY_NEXT
-#define ACN_SC_EARLY_NEXT 0
-#endif
-#ifndef ACN_SC_DEFER
-#define ACN_SC_DEFER 0
-#endif
-#ifndef ACN_SC_SPHERE_TABLE
-#define ACN_SC_SPHERE_TABLE 1
-#endif
 
 /* device-resident scene, parameterised by where the node array is read from */
 template< class NP >
@@ -194,7 +141,6 @@ struct DevSceneT
     uint32_t class0_min; /* shading tasks with more samples than this run on 64 lanes (ACN_CLASS0_MIN, acn_pipeline.h: size_class) */
     const SCEntry* sc_table;   /* pre-order tables of the simple compounds */
     const double* sc_spheres;  /* ( pos, radius ) of the sphere leaves of those tables, see SCEntry.flags */
-    CDblP env_tab;             /* per entry of elems[ 0 .. 2 n_elems ): envelope centre and radius of that element ( radius < 0: none ), see root_candidates */
     static constexpr bool prune = false;
     static constexpr bool park = false;   /* the lock-step machines keep the ray origin in LDS (OrgLds): only where the kernel owns the slot */
 };
@@ -211,7 +157,7 @@ __device__ __forceinline__ DevSceneT< NP2 > scene_rebind( const DevScene& sc, NP
     DevSceneT< NP2 > r;
     r.nodes = nodes; r.gnodes = sc.nodes; r.mats = sc.mats; r.elems = sc.elems; r.textures = sc.textures;
     r.light_root = sc.light_root; r.matter_root = sc.matter_root; r.n_nodes = sc.n_nodes; r.n_elems = sc.n_elems;
-    r.prm = sc.prm; r.camera_rotation = sc.camera_rotation; r.unit_f = sc.unit_f; r.flags = sc.flags; r.lds_stack = sc.lds_stack; r.prune_base = sc.prune_base; r.class0_min = sc.class0_min; r.sc_table = sc.sc_table; r.sc_spheres = sc.sc_spheres; r.env_tab = sc.env_tab;
+    r.prm = sc.prm; r.camera_rotation = sc.camera_rotation; r.unit_f = sc.unit_f; r.flags = sc.flags; r.lds_stack = sc.lds_stack; r.prune_base = sc.prune_base; r.class0_min = sc.class0_min; r.sc_table = sc.sc_table; r.sc_spheres = sc.sc_spheres;
     return r;
 }
 
@@ -559,29 +505,9 @@ DEV V3 fresnel_refraction( V3 dir_i, V3 exit_nor, double trix )
 }
 
 /* ---- node access ---- */
-/* A node visit whose index is the same in every lane reads the node through the scalar cache.  Reading field by field,
- * behind the branches that need them (type -> envelope -> position -> axes), makes every visit a chain of three or four
- * DEPENDENT scalar loads of ~150-200 cycles each, which is what the lock-step machines wait for most of their time
- * (profiles/r02/pmc_sq_final.txt: 0.6 of k_walk's wave cycles in s_waitcnt, 6e8 scalar loads per frame).  NodeView copies
- * the whole 192-byte record into SGPRs at once -- three s_load_dwordx16 issued back to back, one wait -- and hands out
- * a pointer to the copy; node arrays in other address spaces (LDS: per-lane indices) are passed through. */
+/* A node that is visited with the same index in every lane is named through these macros.  The view is a pass-through: copying
+ * the whole 192-byte record into SGPRs at once was measured twice and lost both times (DESIGN.md sections 4c, 4d). */
 template< class NP > struct NodeView { NP p; DEV NodeView( NP q ) : p( q ) {} DEV NP ptr() const { return p; } };
-#ifdef ACN_PRELOAD_NODES
-template<> struct NodeView< const GNode ACN_CONST* >
-{
-    GNode v;
-    DEV NodeView( const GNode ACN_CONST* q )
-    {
-        v.type = q->type; v.flags = q->flags; v.child0 = q->child0; v.child1 = q->child1;
-        for( int k = 0; k < 4; k++ ) v.prm[ k ] = q->prm[ k ];
-        for( int k = 0; k < 3; k++ ) { v.pos[ k ] = q->pos[ k ]; v.env_pos[ k ] = q->env_pos[ k ]; }
-        v.env_radius = q->env_radius;
-        for( int k = 0; k < 9; k++ ) v.rax[ k ] = q->rax[ k ];
-        v.surface_roughness = q->surface_roughness; v.sdf_kind = q->sdf_kind; v.cycles = q->cycles;
-    }
-    DEV const GNode* ptr() const { return &v; }
-};
-#endif
 #define ACN_NODE( name, expr ) const auto name##_view_ = NodeView< decltype( expr ) >( expr ); const auto name = name##_view_.ptr();
 #define ACN_NODE_UNIFORM( name, expr ) ACN_NODE( name, expr )
 
@@ -765,16 +691,11 @@ template< class NP, class CT > DEV int distance_side_( NP o, V3 pos, CT* cnt )  
 }
 #define distance_side( ... ) distance_side_( __VA_ARGS__, cnt )
 
-/* objects.c:267-282.  A REAL call (ACN_ROUGH_INLINE restores the in-line form): the perturbation sits behind every one of the
+/* objects.c:267-282.  A REAL call: the perturbation sits behind every one of the
  * ~130 places where a hit returns a normal (leaves, operands, pairs, composites), three logarithms and a seed each -- in line
  * that was 35 - 40 % of k_walk's 1.4 MB of code, in scenes of which most (the wine glass, the diamond, many_spheres) have no rough
  * surface at all: the hot code was spread over twice the instruction-cache lines it needs.  A rough surface pays a call. */
-#ifdef ACN_ROUGH_INLINE
-#define DEV_ROUGH DEV
-#else
-#define DEV_ROUGH DEVN
-#endif
-DEV_ROUGH V3 roughness_apply( double surface_roughness, V3 n, V3 hit_pos )
+DEVN V3 roughness_apply( double surface_roughness, V3 n, V3 hit_pos )
 {
     uint64_t rv = v_random_seed( hit_pos, 1246 );
     double f;
@@ -1441,7 +1362,7 @@ DEV double simple_compound_hit( const SC& sc, int cmp, V3 rp, V3 rd, V3* p_nor, 
      * later children lie, summed over the subtree's compounds) walks the second, meets its near leaves sooner and culls more.  In
      * the reversed table the leaves come in exactly the reverse order, so "first wins" becomes "last visited wins": `<=`. */
     bool rev = false;
-    if( ACN_SC_CULL && ACN_SC_TWO_ORDERS && !CT::counting )
+    if( !CT::counting )
     {
         const int first_rev = sc.elems[ off + 2 ];
         if( first_rev >= 0 )
@@ -1452,44 +1373,26 @@ DEV double simple_compound_hit( const SC& sc, int cmp, V3 rp, V3 rd, V3* p_nor, 
         }
     }
     const int end = i + count;
-    /* The walk does not depend on what the leaves return (an envelope test is a predicate of the ray alone; only the occlusion
-     * form leaves early), and k_shade<64> on many_spheres is short of VALU issue slots, not of memory (PMC, profiles/r04/NOTES.md
-     * section 6: 72 % of the issue slots busy, waves waiting 20 % of their time): one lane in fifty stands on a leaf whose envelope
-     * its ray hits, so three wave iterations in four ran the whole sphere routine for one or two lanes.  DEFER: a lane that finds
-     * such a leaf parks it (one slot) and walks on; only when a lane of the wave finds a SECOND one do all lanes evaluate what they
-     * have parked, behind a wave-uniform branch.  Leaves are evaluated in walk order per lane, so min_a, the strict `<` tie rule
-     * and the first leaf within `limit` are the ones of the plain loop; the occlusion form may walk a few entries further before
-     * it learns that it could have left.  A hit sphere's normal is computed once, behind the loop, from the same expression.
-     * The counting kernels keep the plain loop: their event counts are compared with the oracle's. */
-    constexpr bool DEFER = ACN_SC_DEFER && !CT::counting;
     /* CULL: an entry whose envelope provably contains everything below it (ACN_SC_BOUNDING) and lies wholly behind the best hit so
      * far cannot change the result -- every hit in it is farther, and a farther hit never replaces a nearer one -- so it is treated
      * like a missed envelope.  The reference visits it (compound.c:215-243 has no such test); the counting kernels therefore do,
      * too.  many_spheres, every 16th pixel: see profiles/r04/NOTES.md section 6. */
-    constexpr bool CULL = ACN_SC_CULL && !CT::counting;
-    uint32_t pend_flags = 0; int pend_node = -1, pend_sph = 0;   /* the parked leaf ( flags != 0: one is parked ) */
-    int best_sph = -1; uint32_t best_flags = 0;                   /* DEFER && NOR: the sphere min_a belongs to */
+    constexpr bool CULL = !CT::counting;
     auto leaf = [ & ]( int node, int sph, uint32_t flags ) -> bool   /* true: the occlusion form is done */
     {
         V3 nor = mk( 0, 0, 0 );
         double a;
-        bool table = false;
-#if ACN_SC_SPHERE_TABLE
         if( flags & ACN_SC_SPHERE )   /* the sphere itself from the compact table beside the entries (32 B, L2-resident) instead of its 192-byte node */
         {
             const double* g = sc.sc_spheres + 4 * ( size_t )sph;
-            a = sphere_ray_hit( mk( g[ 0 ], g[ 1 ], g[ 2 ] ), g[ 3 ], rp, rd, NOR && !DEFER, &nor );
-            if( NOR && !DEFER && a < F3_INF && ( flags & ACN_SC_ROUGH ) ) nor = roughness_normal( &sc.nodes[ node ], nor, ray_pos( rp, rd, a ) );
-            table = true;
+            a = sphere_ray_hit( mk( g[ 0 ], g[ 1 ], g[ 2 ] ), g[ 3 ], rp, rd, NOR, &nor );
+            if( NOR && a < F3_INF && ( flags & ACN_SC_ROUGH ) ) nor = roughness_normal( &sc.nodes[ node ], nor, ray_pos( rp, rd, a ) );
         }
-        else
-#endif
-        a = simple_leaf_hit( &sc.nodes[ node ], rp, rd, NOR, &nor );
+        else a = simple_leaf_hit( &sc.nodes[ node ], rp, rd, NOR, &nor );
         if( rev ? ( a <= min_a && a < F3_INF ) : ( a < min_a ) )
         {
             min_a = a;
             if( NOR ) *p_nor = nor;
-            if( NOR && DEFER ) { best_sph = table ? sph : -1; best_flags = flags; }
             *hit_obj = node;
             if( a <= limit ) return true;
         }
@@ -1498,9 +1401,6 @@ DEV double simple_compound_hit( const SC& sc, int cmp, V3 rp, V3 rd, V3* p_nor, 
     SCEntry e = sc.sc_table[ i ];
     while( i < end )
     {
-#ifdef ACN_SC_PREFETCH
-        const SCEntry ahead = sc.sc_table[ i + 1 < end ? i + 1 : i ];
-#endif
         bool miss = ( e.flags & ACN_NODE_HAS_ENVELOPE ) && !env_ray_hits_raw( ld3( e.env_pos ), e.env_radius, rp, rd, cnt );
         if( CULL && !miss && ( e.flags & ACN_SC_BOUNDING ) )
         {
@@ -1509,52 +1409,14 @@ DEV double simple_compound_hit( const SC& sc, int cmp, V3 rp, V3 rd, V3* p_nor, 
         }
         const bool is_leaf = e.type != ACN_COMPOUND;
         const int next = ( !is_leaf && miss ) ? e.skip : i + 1;
-#if ACN_SC_EARLY_NEXT
-        /* the next entry requested BEFORE the leaf is evaluated.  Measured (profiles/r04/ab_c3_table_s20.txt): -4 % alone, +5 % on top
-         * of the sphere table: off */
-        SCEntry e_next = e;
-        if( next < end ) e_next = sc.sc_table[ next ];
-#endif
         if( is_leaf ) cnt->inc( CNT_OBJ_HIT );
         const bool want = is_leaf && !miss;
-        if( DEFER )
-        {
-            if( __ballot( want && pend_flags != 0 ) != 0 )
-            {
-                if( pend_flags != 0 )
-                {
-                    if( leaf( pend_node, pend_sph, pend_flags ) ) return min_a;
-                    pend_flags = 0;
-                }
-            }
-            if( want ) { pend_node = e.node; pend_sph = e.skip; pend_flags = e.flags | 0x80000000u; }
-        }
-        else if( want )
+        if( want )
         {
             if( leaf( e.node, e.skip, e.flags ) ) return min_a;
         }
-#if ACN_SC_EARLY_NEXT
-        e = e_next;
-#elif defined( ACN_SC_PREFETCH )
-        if( next == i + 1 ) e = ahead;
-        else if( next < end ) e = sc.sc_table[ next ];
-#else
         if( next < end ) e = sc.sc_table[ next ];
-#endif
         i = next;
-    }
-    if( DEFER )
-    {
-        if( pend_flags != 0 && leaf( pend_node, pend_sph, pend_flags ) ) return min_a;
-#if ACN_SC_SPHERE_TABLE
-        if( NOR && best_sph >= 0 )   /* sphere_ray_hit's normal (gmath.h:64-83), once, for the hit that won */
-        {
-            const double* g = sc.sc_spheres + 4 * ( size_t )best_sph;
-            V3 nor = v_of_length( v_sub( ray_pos( rp, rd, min_a ), mk( g[ 0 ], g[ 1 ], g[ 2 ] ) ), 1.0 );
-            if( best_flags & ACN_SC_ROUGH ) nor = roughness_normal( &sc.nodes[ *hit_obj ], nor, ray_pos( rp, rd, min_a ) );
-            *p_nor = nor;
-        }
-#endif
     }
     return min_a;
 }
@@ -1585,21 +1447,8 @@ DEV bool surely_outside_n( NP nodes, int node, V3 rp, V3 rd )
     }
     return false;
 }
-#ifndef ACN_PRUNE_CALL
-#define ACN_PRUNE_CALL 0
-#endif
-/* ACN_PRUNE_CALL: ONE copy of the descent per kernel behind a real call instead of one expansion per call site */
-template< int D, class NP >
-__device__ __attribute__( ( noinline ) ) bool surely_outside_call( NP nodes, int node, V3 rp, V3 rd ) { return surely_outside_n< D >( nodes, node, rp, rd ); }
 template< int D, class SC >
-DEV bool surely_outside( const SC& sc, int node, V3 rp, V3 rd )
-{
-#if ACN_PRUNE_CALL
-    return surely_outside_call< D >( sc.nodes, node, rp, rd );
-#else
-    return surely_outside_n< D >( sc.nodes, node, rp, rd );
-#endif
-}
+DEV bool surely_outside( const SC& sc, int node, V3 rp, V3 rd ) { return surely_outside_n< D >( sc.nodes, node, rp, rd ); }
 #ifndef ACN_PRUNE_DEPTH
 #define ACN_PRUNE_DEPTH 3
 #endif
@@ -1819,11 +1668,7 @@ DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj
         ACN_LAP( PH_ROOT_LEAF );
         if( type != ACN_DISTANCE && ( surely_outside< ACN_PRUNE_DEPTH >( sc, e, rp, rd ) || prune_run( sc, e, rp, rd, F3_INF ) ) ) { cnt->inc( CNT_OBJ_HIT ); ACN_LAP( PH_PRUNE ); return F3_INF; }
         ACN_LAP( PH_PRUNE );
-#if ACN_UNI_MACHINE
         return obj_ray_hit_uni< NOR, SC::park >( sref( sc ), e, rp, rd, nor, cnt );   /* the machine redoes the envelope test */
-#else
-        return obj_ray_hit_dev( sref( sc ), e, rp, rd, NOR, nor, cnt );
-#endif
     }
     cnt->inc( CNT_OBJ_HIT );
     double a;
@@ -1843,40 +1688,6 @@ DEVN double light_hit_call( SC sc, int e, V3 rp, V3 rd, CT* cnt )
     return element_hit< false >( sc, e, rp, rd, ( V3* )nullptr, &ho, -F3_INF, cnt );
 }
 
-/* Broad phase of a root loop (ACN_ROOT_CANDIDATES; built, measured, off).  A root compound of a lamp scene has 63 elements, and the loops below visit every one of them for
- * every ray: element index -> node header -> envelope, three dependent scalar loads (~200 cycles each) before the envelope test
- * that rejects the ray for nearly all of them (objects.c:264: a ray that misses an element's envelope gets f3_inf).  The
- * envelopes of the slice elems[ first .. first + count ) lie side by side in env_tab (32 bytes per element, the same order), so
- * this loop is independent loads the compiler overlaps, and its result -- bit i: the ray enters element i's envelope, or the
- * element has none -- lets the loops skip an element NO lane of the wave needs without touching its node, and lets the other
- * lanes sit an element out.  Results do not change: a skipped evaluation is one that returns f3_inf.  Elements from the 65th on
- * are always candidates. */
-template< class SC, class CT >
-DEV uint64_t root_candidates( const SC& sc, int first, int count, V3 rp, V3 rd, CT* cnt )
-{
-    uint64_t m = 0;
-#ifndef ACN_ROOT_CANDIDATES   /* OFF: measured neutral on every workload (hanging_lamp 600x800 305 vs 308 ms, paraffin_lamp 335 - 346 both
-                                 ways, hanging_lamp 2160p every 256th pixel 4 639 vs 4 614 ms: profiles/r04/ab_root_candidates_s15.txt) -- the
-                                 root loop's chain of scalar loads is not what the lamp scenes wait for */
-    return ~0ull;
-#endif
-    const int n = count < 64 ? count : 64;
-    #pragma unroll 4
-    for( int i = 0; i < n; i++ )
-    {
-        const CDblP e = sc.env_tab + 4 * ( size_t )( first + i );
-        const double r = e[ 3 ];
-        bool cand = true;
-        if( r >= 0 )
-        {
-            cand = env_ray_hits_raw( mk( e[ 0 ], e[ 1 ], e[ 2 ] ), r, rp, rd, ACN_NO_CNT );
-            if( !cand ) { cnt->inc( CNT_OBJ_HIT ); cnt->cost( ACN_F_ENV_MISS ); }   /* what element_hit books for such a ray */
-        }
-        if( cand ) m |= 1ull << i;
-    }
-    return m;
-}
-
 /* compound_s_ray_hit on a root compound, any-hit form for occlusion tests: true iff some element hits at <= limit */
 template< class SC, class CT >
 DEV bool root_occluded( const SC& sc, int cmp, V3 rp, V3 rd, double limit, CT* cnt )
@@ -1884,14 +1695,11 @@ DEV bool root_occluded( const SC& sc, int cmp, V3 rp, V3 rd, double limit, CT* c
     auto o = &sc.nodes[ cmp ];
     if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return false;
     int first = o->child0 + ( int )sc.n_elems, count = o->child1;   /* the cost-ordered copy: cheap elements first */
-    const uint64_t cand = root_candidates( sc, first, count, rp, rd, cnt );
     bool occ = false;
     for( int i = 0; i < count; i++ )
     {
-        const bool mine = !occ && ( i >= 64 || ( ( cand >> i ) & 1ull ) );
-        if( __ballot( mine ) == 0ull ) continue;
         int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
-        if( mine )
+        if( !occ )
         {
             int hit_obj;
             double a = element_hit< false >( sc, element, rp, rd, nullptr, &hit_obj, limit, cnt );
@@ -1913,16 +1721,12 @@ DEV double root_trans_hit( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, CT
     if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return F3_INF;
     double min_a = F3_INF;
     int first = o->child0, count = o->child1;
-    const uint64_t cand = root_candidates( sc, first, count, rp, rd, cnt );
     for( int i = 0; i < count; i++ )
     {
-        const bool mine = i >= 64 || ( ( cand >> i ) & 1ull );
-        if( __ballot( mine ) == 0ull ) continue;
         int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
         int hit_obj = -1;
         V3 nor = mk( 0, 0, 0 );
-        double a = F3_INF;
-        if( mine ) a = element_hit< true >( sc, element, rp, rd, &nor, &hit_obj, -F3_INF, cnt );
+        double a = element_hit< true >( sc, element, rp, rd, &nor, &hit_obj, -F3_INF, cnt );
         if( a < F3_INF )
         {
             cnt->cost( ACN_F_TRANS_RESOLVE );
@@ -2148,186 +1952,6 @@ DEV double root_trans_hit_fast( const SC& sc, int cmp, V3 rp, V3 rd, Trans* tran
 }
 
 /* ------------------------------------------------------------------------------------------------------------------ */
-/* Pooled machines (ACN_POOLED=1; built, parity-green, measured SLOWER, off -- see the end of this comment).  A lock-step machine
- * serves the lanes of ONE wave that meet the same root element, and the rays of a wave
- * rarely agree on one: 18 of 64 lanes per entry on the wine glass, 4.4 on hanging_lamp (63 root elements), 7 in its k_hard_path
- * (profiles/r04/phase_ticks_*.txt) -- the machine kernels of the lamp scenes ran at 7 - 10 % of their lanes.  The four waves of a
- * workgroup now POOL the rays that need the same element: every lane with `need` writes its ray into the workgroup's pool in LDS
- * (slots handed out by ballot + the waves' counts), the pooled rays are evaluated in batches of 64 by as few waves as it takes
- * (in turn, so that the work spreads over the SIMDs), and every lane collects its result from its slot: one machine entry with
- * up to 64 lanes instead of four with a quarter each.  A ray's own arithmetic is untouched -- which wave evaluates it is not
- * part of any result.  ALL lanes of the workgroup must call (three barriers); the callers' loops are workgroup-uniform.
- * Measured (profiles/r04/ab_pooled_s17.txt, same box, parity suite green with it): 1080p 49.9 -> 60.4 ms, hanging_lamp 600x800
- * 307 -> 430, paraffin_lamp 340 -> 393, diamond every 16th pixel 2 245 -> 2 659.  Lanes per machine entry were the wrong target:
- * the four waves ran their quarter-full machines SIDE BY SIDE on four SIMDs, and these kernels wait for latency, not for issue
- * slots -- pooling puts the same evaluations one after another on one SIMD while three waves stand at a barrier. */
-struct RayPool
-{
-    LdsF64P v;          /* plane k of entry i: v[ k * 256 + i ]; in: origin 0 - 2, direction 3 - 5; out: a 0, normal 1 - 3 */
-    LdsU32P counts;     /* [ 2 ][ 4 ]: the waves' counts of the call at hand, double-buffered by the parity of `turn` */
-    uint32_t turn;      /* calls so far: parity of the counts, and the rotation of batches over the waves */
-};
-template< class SC > DEV RayPool ray_pool_of( const SC& sc )
-{
-    RayPool pl;
-    pl.v = ( LdsF64P )( ( char ACN_LDS* )acn_lds_raw + sc.lds_stack + ACN_LDS_STACK_BYTES );
-    pl.counts = ( LdsU32P )( pl.v + 6 * ACN_LDS_LANES ) + ACN_LDS_LANES;
-    pl.turn = 0;
-    return pl;
-}
-
-/* obj_ray_hit of root element e (a CSG / SDF object) for every lane of the WORKGROUP with `need`; f3_inf for the others */
-template< bool NOR, class SC, class CT >
-DEV double pooled_machine_hit( const SC& sc, RayPool& pl, int e, bool need, V3 rp, V3 rd, V3* nor, CT* cnt )
-{
-    const uint32_t wave = ( uint32_t )__builtin_amdgcn_readfirstlane( ( int )( threadIdx.x >> 6 ) );
-    const uint32_t lane = threadIdx.x & 63u;
-    const unsigned long long m = __ballot( need );
-    const uint32_t par = ( pl.turn & 1u ) * 4u;
-    const uint32_t turn = pl.turn++;
-    if( lane == 0 ) pl.counts[ par + wave ] = ( uint32_t )__popcll( m );
-    __syncthreads();
-    uint32_t total = 0, off = 0;
-    for( uint32_t w = 0; w < 4u; w++ )
-    {
-        const uint32_t c = ( uint32_t )__builtin_amdgcn_readfirstlane( ( int )pl.counts[ par + w ] );
-        if( w < wave ) off += c;
-        total += c;
-    }
-    if( total == 0 ) return F3_INF;      /* the same in every wave of the workgroup */
-    const uint32_t slot = off + ( uint32_t )__builtin_amdgcn_mbcnt_hi( ( uint32_t )( m >> 32 ), __builtin_amdgcn_mbcnt_lo( ( uint32_t )m, 0u ) );
-    if( need )
-    {
-        pl.v[ slot ] = rp.x; pl.v[ ACN_LDS_LANES + slot ] = rp.y; pl.v[ 2 * ACN_LDS_LANES + slot ] = rp.z;
-        pl.v[ 3 * ACN_LDS_LANES + slot ] = rd.x; pl.v[ 4 * ACN_LDS_LANES + slot ] = rd.y; pl.v[ 5 * ACN_LDS_LANES + slot ] = rd.z;
-    }
-    __syncthreads();
-    for( uint32_t b = 0; b * 64u < total; b++ )
-    {
-        if( ( ( b + turn ) & 3u ) != wave ) continue;      /* batch b is this wave's turn */
-        const uint32_t idx = b * 64u + lane;
-        if( idx < total )
-        {
-            const V3 p = mk( pl.v[ idx ], pl.v[ ACN_LDS_LANES + idx ], pl.v[ 2 * ACN_LDS_LANES + idx ] );
-            const V3 d = mk( pl.v[ 3 * ACN_LDS_LANES + idx ], pl.v[ 4 * ACN_LDS_LANES + idx ], pl.v[ 5 * ACN_LDS_LANES + idx ] );
-            V3 n = mk( 0, 0, 0 );
-            const double a = obj_ray_hit_uni< NOR >( sref( sc ), e, p, d, &n, cnt );
-            pl.v[ idx ] = a;
-            if( NOR ) { pl.v[ ACN_LDS_LANES + idx ] = n.x; pl.v[ 2 * ACN_LDS_LANES + idx ] = n.y; pl.v[ 3 * ACN_LDS_LANES + idx ] = n.z; }
-        }
-    }
-    __syncthreads();
-    double a = F3_INF;
-    if( need )
-    {
-        a = pl.v[ slot ];
-        if( NOR && a < F3_INF ) *nor = mk( pl.v[ ACN_LDS_LANES + slot ], pl.v[ 2 * ACN_LDS_LANES + slot ], pl.v[ 3 * ACN_LDS_LANES + slot ] );
-    }
-    return a;
-}
-
-/* element_hit for the pooled root loops: `live` lanes want the element tested; machine elements go through the pool.  Every lane
- * of the workgroup calls with the same e. */
-template< bool NOR, class SC, class CT >
-DEV double element_hit_pooled( const SC& sc, RayPool& pl, int e, bool live, V3 rp, V3 rd, V3* nor, int* hit_obj, double limit, CT* cnt )
-{
-    ACN_NODE_UNIFORM( n, &sc.nodes[ e ] )
-    const int type = n->type;
-    if( type == ACN_COMPOUND || type <= ACN_SQUAROID )
-    {
-        double a = F3_INF;
-        if( live ) a = element_hit< NOR >( sc, e, rp, rd, nor, hit_obj, limit, cnt );   /* no machine in these branches */
-        return a;
-    }
-    bool need = live;
-    if( need )
-    {
-        *hit_obj = e;
-        if( node_has_env( n ) && !env_ray_hits( n, rp, rd ) ) { cnt->inc( CNT_OBJ_HIT ); need = false; }
-        else if( type != ACN_DISTANCE && ( surely_outside< ACN_PRUNE_DEPTH >( sc, e, rp, rd ) || prune_run( sc, e, rp, rd, limit >= 0 ? limit : F3_INF ) ) ) { cnt->inc( CNT_OBJ_HIT ); need = false; }
-    }
-    return pooled_machine_hit< NOR >( sc, pl, e, need, rp, rd, nor, cnt );
-}
-
-/* root_occluded for the lanes with `want`, pooled */
-template< class SC, class CT >
-DEV bool root_occluded_pooled( const SC& sc, RayPool& pl, int cmp, bool want, V3 rp, V3 rd, double limit, CT* cnt )
-{
-    auto o = &sc.nodes[ cmp ];
-    if( want && node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) want = false;
-    int first = o->child0 + ( int )sc.n_elems, count = o->child1;   /* the cost-ordered copy: cheap elements first */
-    bool occ = false;
-    for( int i = 0; i < count; i++ )
-    {
-        int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
-        int hit_obj;
-        double a = element_hit_pooled< false >( sc, pl, element, want && !occ, rp, rd, ( V3* )nullptr, &hit_obj, limit, cnt );
-        if( a <= limit ) occ = true;
-    }
-    return occ;
-}
-
-/* root_trans_hit for the lanes with `live`, pooled */
-template< class SC, class CT >
-DEV double root_trans_hit_pooled( const SC& sc, RayPool& pl, int cmp, bool live, V3 rp, V3 rd, Trans* trans, CT* cnt )
-{
-    auto o = &sc.nodes[ cmp ];
-    if( live ) cnt->inc( CNT_TRANS_RAY );
-    if( live && node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) live = false;
-    double min_a = F3_INF;
-    int first = o->child0, count = o->child1;
-    for( int i = 0; i < count; i++ )
-    {
-        int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
-        int hit_obj = -1;
-        V3 nor = mk( 0, 0, 0 );
-        double a = element_hit_pooled< true >( sc, pl, element, live, rp, rd, &nor, &hit_obj, -F3_INF, cnt );
-        if( a < F3_INF )
-        {
-            cnt->cost( ACN_F_TRANS_RESOLVE );
-            if( a < min_a - F3_EPS )
-            {
-                min_a = a;
-                if( v_mlv( nor, rd ) > 0 )
-                {
-                    trans->exit_nor = nor; trans->exit_obj = hit_obj; trans->enter_obj = -1;
-                }
-                else
-                {
-                    trans->exit_nor = v_neg( nor ); trans->exit_obj = -1; trans->enter_obj = hit_obj;
-                }
-            }
-            else if( f_abs( a - min_a ) < F3_EPS )
-            {
-                min_a = a < min_a ? a : min_a;
-                if( v_mlv( nor, rd ) > 0 ) trans->exit_obj = hit_obj;
-                else                       trans->enter_obj = hit_obj;
-            }
-        }
-    }
-    return min_a;
-}
-
-/* scene_s_trans_hit (scene.c:362-382) for the lanes with `live`, pooled: every lane of the workgroup calls */
-template< class SC, class CT >
-DEV double scene_trans_hit_pooled( const SC& sc, RayPool& pl, bool live, V3 rp, V3 rd, Trans* trans, CT* cnt )
-{
-    double min_a = F3_INF;
-    double a;
-    Trans trans_l;
-    trans_l.exit_nor = mk( 0, 0, 0 ); trans_l.exit_obj = -1; trans_l.enter_obj = -1;
-    #pragma unroll 1
-    for( int k = 0; k < 2; k++ )
-    {
-        if( ( a = root_trans_hit_pooled( sc, pl, k ? sc.matter_root : sc.light_root, live, rp, rd, &trans_l, cnt ) ) < min_a )
-        {
-            min_a = a;
-            *trans = trans_l;
-        }
-    }
-    return min_a;
-}
-
 template< class SC, class CT >
 DEV double scene_trans_hit_dev( const SC& sc, V3 rp, V3 rd, Trans* trans, CT* cnt )   /* scene.c:362-382 */
 {
@@ -2337,11 +1961,7 @@ DEV double scene_trans_hit_dev( const SC& sc, V3 rp, V3 rd, Trans* trans, CT* cn
     trans_l.exit_nor = mk( 0, 0, 0 ); trans_l.exit_obj = -1; trans_l.enter_obj = -1;
     ACN_LAP( PH_FETCH );
     /* lights, then matter, through ONE in-line copy of the root traversal (and of the CSG machines in it): the root is a scalar */
-#ifdef ACN_ROOT_TWO_COPIES
-    #pragma unroll
-#else
     #pragma unroll 1
-#endif
     for( int k = 0; k < 2; k++ )
     {
         if( ( a = root_trans_hit( sc, k ? sc.matter_root : sc.light_root, rp, rd, &trans_l, cnt ) ) < min_a )

@@ -1,6 +1,7 @@
 /* acn_launch.h -- launch wrappers of the templated pipeline kernels, one translation unit per kernel family
- * (k_shade_*.hip, k_walk_*.hip, k_hard_*.hip) so that `make -j` compiles the families in parallel: the 50-odd kernel
- * instantiations in one file took 8.5 minutes, the families side by side take about 3.  The wrappers pick the
+ * (k_shade_*.hip, k_walk_*.hip, k_hard_*.hip) so that `make -j` compiles the families in parallel: the pipeline's 58 kernel
+ * instantiations (32 of k_shade, 8 each of k_walk, k_hard_shadow and k_hard_path, 2 of k_shade_hits) in one file took 8.5 minutes,
+ * the families side by side take about 3.  The wrappers pick the
  * instantiation from runtime flags; the orchestration stays in actinon_hip.hip. */
 #ifndef ACN_LAUNCH_H
 #define ACN_LAUNCH_H
@@ -34,8 +35,9 @@ struct LevelQ
     uint32_t stack_use;                                     /* slots of a stack every pass but the last uses (< stack_cap: tests) */
     uint32_t* counts;
     const uint32_t* prev_children;
-    unsigned grid;                                          /* workgroups of the persistent kernels */
+    unsigned grid;                                          /* workgroups of k_shade_hits and the hard-ray kernels */
     unsigned shade_grid;                                    /* workgroups of k_shade */
+    unsigned walk_grid;                                     /* workgroups of k_walk */
     uint32_t fetch_walk, fetch_hard;                        /* input items a wave reserves per cursor atomic */
     uint32_t fetch_shade;                                   /* k_shade: steps of 64 / LPT tasks a wave reserves per atomic */
     uint32_t private_limit;                                 /* generations of at most this many rays are finished on private stacks */
@@ -53,11 +55,10 @@ void acn_launch_shade_hits( bool count, const LevelQ& q, hipStream_t stream, con
                             unsigned long long* accum, unsigned long long* counters );
 void acn_launch_shade( int cls, KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s,
                        unsigned long long* accum, unsigned long long* counters );
-/* part: ACN_SHADE_BOTH, or one half of a fissioned launch (ACN_SHADE_DIRECT / ACN_SHADE_PATH) */
-void acn_launch_shade64( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long*, int part );
-void acn_launch_shade16( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long*, int part );
-void acn_launch_shade4( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long*, int part );
-void acn_launch_shade1( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long*, int part );
+void acn_launch_shade64( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
+void acn_launch_shade16( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
+void acn_launch_shade4( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
+void acn_launch_shade1( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
 void acn_launch_hard_shadow( KernelFlags f, const LevelQ& q, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
                              unsigned long long* accum, unsigned long long* counters );
 void acn_launch_hard_path( KernelFlags f, const LevelQ& q, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
@@ -88,27 +89,21 @@ int acn_query_fail( int code, const char* msg );          /* acn_last_error() */
 
 /* k_walk< C, L, R > */
 #define ACN_LW_( C, L, R ) \
-    hipLaunchKernelGGL( ( k_walk< C, L, R > ), dim3( q.grid ), dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), ACN_TASKQ_ARGS_OF( q ), \
+    hipLaunchKernelGGL( ( k_walk< C, L, R > ), dim3( q.walk_grid ), dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), ACN_TASKQ_ARGS_OF( q ), \
         n_cam ? ( const RayTask* )nullptr : ( const RayTask* )q.rays[ pass & 1 ], q.ray_cap, pass, pos_xy, first_pixel, base, n_cam, order, \
         q.rays[ ( pass + 1 ) & 1 ], q.ray_cap, last ? 0xFFFFFFFFu : q.private_limit, \
         q.stacks, q.stack_cap, last ? q.stack_cap : q.stack_use, q.fetch_walk, q.emit_terms, accum, counters )
 
 /* body of acn_launch_shade<LPT>: shared by the four k_shade translation units */
 #define ACN_DEFINE_LAUNCH_SHADE( NAME, LPT, CLS ) \
-template< int PART > static void NAME##_part( KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s, unsigned long long* accum, unsigned long long* counters ) \
+void NAME( KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s, unsigned long long* accum, unsigned long long* counters ) \
 { \
-    if( f.count && f.prune ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, true, true, true, PART );  else ACN_LS_( LPT, CLS, true, false, true, PART ); } \
-    else if( f.count ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, true, true, false, PART );  else ACN_LS_( LPT, CLS, true, false, false, PART ); } \
-    else if( f.prune ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, false, true, true, PART );  else ACN_LS_( LPT, CLS, false, false, true, PART ); } \
-    else               { if( f.leaf_lights ) ACN_LS_( LPT, CLS, false, true, false, PART ); else ACN_LS_( LPT, CLS, false, false, false, PART ); } \
-} \
-void NAME( KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s, unsigned long long* accum, unsigned long long* counters, int part ) \
-{ \
-    if( part == ACN_SHADE_DIRECT )    NAME##_part< ACN_SHADE_DIRECT >( f, q, stream, s, accum, counters ); \
-    else if( part == ACN_SHADE_PATH ) NAME##_part< ACN_SHADE_PATH >( f, q, stream, s, accum, counters ); \
-    else                              NAME##_part< ACN_SHADE_BOTH >( f, q, stream, s, accum, counters ); \
+    if( f.count && f.prune ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, true, true, true );  else ACN_LS_( LPT, CLS, true, false, true ); } \
+    else if( f.count ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, true, true, false );  else ACN_LS_( LPT, CLS, true, false, false ); } \
+    else if( f.prune ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, false, true, true );  else ACN_LS_( LPT, CLS, false, false, true ); } \
+    else               { if( f.leaf_lights ) ACN_LS_( LPT, CLS, false, true, false ); else ACN_LS_( LPT, CLS, false, false, false ); } \
 }
-#define ACN_LS_( LPT, CLS, C, L, P, PART ) hipLaunchKernelGGL( ( k_shade< LPT, C, L, P, PART > ), dim3( q.shade_grid ), dim3( 256 ), 0, stream, ACN_SCENE_ARGS_OF( s ), \
+#define ACN_LS_( LPT, CLS, C, L, P ) hipLaunchKernelGGL( ( k_shade< LPT, C, L, P > ), dim3( q.shade_grid ), dim3( 256 ), 0, stream, ACN_SCENE_ARGS_OF( s ), \
     ( const DTask* )q.tasks, ( const uint32_t* )q.idx[ CLS ], CLS, q.task_cap, q.fetch_shade * ( 64u / LPT ), q.children, q.child_cap, q.hard_shadow, q.hard_path, q.hs_cap, q.hard_cap, q.counts, q.shard_rank, q.shard_world, accum, counters )
 
 #endif

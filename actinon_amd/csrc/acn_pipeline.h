@@ -163,7 +163,7 @@ enum
 {
     QC_TASKS = 0, QC_CLASS0 = 1, QC_CHILDREN = 5, QC_FLAGS = 6, QC_HARD_SHADOW = 7, QC_HARD_PATH = 8,
     QC_CUR_HS = 9, QC_CUR_HP = 10, QC_CUR_HITS = 11, QC_CUR_SHADE0 = 20,   /* .. QC_CUR_SHADE0 + 3: one per size class */
-    QC_CUR_SHADEP0 = 24,   /* .. + 3: the same for the path half of a fissioned k_shade (ACN_SHADE_PATH), which walks the same task lists */
+    /* ( words 24 .. 27 are unused ) */
     /* reserved slots no record was written to (the unused ends of the waves' reservations): mark - dead = records, exactly.
      * Tasks, path-sample hits, deferred path rays, specular rays (all generations of the level together); the deferred-shadow
      * queue has QS_HARD_SHADOW + QS_PROBES.  The dead slots of a chunk do not scale with it -- ~64 per wave, queue and launch --
@@ -201,7 +201,7 @@ DEV int size_class( uint64_t n, uint32_t class0_min )
 #ifndef ACN_QCHUNK_MAX
 #define ACN_QCHUNK_MAX 512u
 #endif
-/* spare: a second reservation taken ahead of need (chunk_prefetch), ACN_INVALID if none */
+/* spare: a second reservation held beside the current one, ACN_INVALID_SLOT if none (nothing takes one at present) */
 struct ChunkState { uint32_t cur, end, spare, size; };   /* size: slots per reservation (ACN_QCHUNK unless the kernel knows better, see chunks_resize) */
 typedef ChunkState ACN_LDS* ChunkP;
 #define ACN_NCHUNKS 8     /* reservation states per wave */
@@ -232,30 +232,6 @@ DEV void chunks_resize( ChunkP cs, uint32_t items_of_launch )
     uint32_t size = ( per_wave / 8u ) & ~63u;
     size = size < ( uint32_t )ACN_QCHUNK ? ( uint32_t )ACN_QCHUNK : size > ACN_QCHUNK_MAX ? ACN_QCHUNK_MAX : size;
     if( ( threadIdx.x & 63 ) < ACN_NCHUNKS ) cs[ threadIdx.x & 63 ].size = size;
-}
-
-/* Reservations ahead of need.  A k_walk wave appends up to 64 records per step to each of its queues, so nearly every
- * step runs a reservation dry and pays the round trip of a returning atomic (1-2 us) per queue in the middle of its
- * shading.  At the start of a step (all lanes active, nothing else in flight) lane q looks at queue q of the wave: if its
- * reservation exists and would not survive one more full step, the lane starts the atomic for the next one; the result
- * is parked in LDS (ChunkState.spare) after the step's traversal, when it has long arrived, and chunk_alloc takes it
- * from there.  One VGPR for all queues; a queue the wave never appended to is never reserved ahead. */
-struct ChunkPrefetch { uint32_t base; bool issued; };
-DEV void chunk_prefetch_issue( ChunkP cs, uint32_t* counter, bool enabled, ChunkPrefetch& pf )   /* lane q: cs = state of queue q */
-{
-    pf.base = 0;
-    const uint32_t cur = cs->cur, end = cs->end, spare = cs->spare;
-#ifndef ACN_RESERVE_AHEAD   /* off by default: measured three times against the same kernels without it, it costs 0.5 - 0.7 ms of the
-                              71 ms wine_glass frame (the extra LDS reads and the compare of every step) and gains nothing where
-                              the steps are long (profiles/r03/NOTES.md) */
-    enabled = false;
-#endif
-    pf.issued = enabled && end != 0u && end - cur < 64u && spare == ACN_INVALID_SLOT;
-    if( pf.issued ) pf.base = atomicAdd( counter, cs->size );
-}
-DEV void chunk_prefetch_park( ChunkP cs, const ChunkPrefetch& pf )
-{
-    if( pf.issued ) cs->spare = pf.base;
 }
 
 /* every lane with `want` gets a distinct slot of the queue counted by *counter.  A request that does not fit the rest
@@ -708,8 +684,6 @@ DEV void wave_add_counters( unsigned long long*, const Cnt< false >& ) {}
 #ifndef ACN_TRACE_WAVES
 #define ACN_TRACE_WAVES ACN_WALK_WAVES
 #endif
-/* ACN_POOLED=1: the machine kernels pool the rays of a workgroup's four waves per root element (acn_device.h: pooled_machine_hit).
- * Measured slower on every workload, off (defined in acn_device.h) */
 #ifndef ACN_HPATH_WAVES
 #define ACN_HPATH_WAVES ACN_WALK_WAVES
 #endif
@@ -787,30 +761,13 @@ void k_walk( ACN_SCENE_PARAMS, ACN_TASKQ_PARAMS, const RayTask* __restrict__ ray
     range_init( fr, true );
     uint32_t traced = 0, steps = 0;
     bool finished = false;
-    RayPool pool = ray_pool_of( sc );
     for( uint32_t step = 0; step < ACN_WALK_MAX_STEPS; step++ )
     {
         /* the step's 64 rays: the top of the private stack, topped up with fresh input */
         uint32_t n_pop = sink.top < 64u ? sink.top : 64u;
         uint32_t n_fresh = 0, fb = 0;
         if( n_pop < 64u ) n_fresh = range_take( fr, cursor, fetch_batch, n_in, 64u - n_pop, &fb );
-#if ACN_POOLED
-        /* the waves of a workgroup step together (they pool their rays per root element): a wave that is out of work keeps
-         * stepping, with no rays, until all four are */
-        const bool have_rays = n_pop + n_fresh != 0;
-        if( !__syncthreads_or( have_rays ? 1 : 0 ) ) { finished = true; break; }
-#else
-        const bool have_rays = true;
         if( n_pop + n_fresh == 0 ) { finished = true; break; }
-#endif
-        /* reservations this step may run dry: their atomics travel while the step's rays are traced (lane q: queue q of the
-         * wave -- 0 tasks, 1 .. 4 the class lists, 5 the next generation's rays, 6 probes) */
-        ChunkPrefetch pf;
-        {
-            const int q = lane < 7 ? lane : 0;
-            uint32_t* ctr = q == 0 ? &tq.counts[ QC_TASKS ] : q <= ACN_NCLASS ? &tq.counts[ QC_CLASS0 + q - 1 ] : q == 5 ? sink.out.counter : &tq.counts[ QC_HARD_SHADOW ];
-            chunk_prefetch_issue( cs + q, ctr, lane < 7 && !( q == 5 && sink.priv ), pf );
-        }
         sink.top -= n_pop;
         const RayTask* src = nullptr;
         bool live = false;
@@ -841,47 +798,23 @@ void k_walk( ACN_SCENE_PARAMS, ACN_TASKQ_PARAMS, const RayTask* __restrict__ ray
         }
         if( src && live ) { rp = src->p; rd = src->d; }
         if( live ) traced++;
-        if( have_rays ) steps++;
+        steps++;
 
         /* scene_s_trans_hit */
         Trans trans;
         trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
         double offs = F3_INF;
-#if ACN_POOLED
-        if constexpr( LDS ) offs = scene_trans_hit_pooled( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), pool, live, rp, rd, &trans, &cnt );
-        else                offs = scene_trans_hit_pooled( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), pool, live, rp, rd, &trans, &cnt );
-#else
         if( live )
         {
-            if constexpr( LDS ) offs = scene_trans_hit_dev( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &cnt );
-            else                offs = scene_trans_hit_dev( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), rp, rd, &trans, &cnt );
+            if constexpr( LDS ) offs = scene_trans_hit_dev( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &cnt );
+            else                offs = scene_trans_hit_dev( scene_view< PRUNE, true >( sc, sc.nodes ), rp, rd, &trans, &cnt );
         }
-#endif
-        chunk_prefetch_park( cs + ( lane < 7 ? lane : 0 ), pf );
         /* what the ray carries is read only now, so that it does not occupy registers across the traversal */
         asm volatile( "" ::: "memory" );
         V3 T = mk( 1, 1, 1 );
         double intensity = 1.0;
         int depth = ( int )sc.prm.trace_depth;
         if( src && live ) { T = src->T; intensity = src->intensity; depth = src->depth; pixel = src->pixel; }
-#ifdef ACN_WALK_REFETCH
-        /* ... and origin and direction are read (camera rays: computed) a second time for the shading: twelve registers less
-         * across the traversal, which copies them anyway */
-        if( src ) { if( live ) { rp = src->p; rd = src->d; } }
-        else
-        {
-            asm volatile( "" : "+v"( pixel ) );
-            double mx, my;
-            if( pos_xy ) { mx = pos_xy[ ( size_t )pixel * 2 ]; my = pos_xy[ ( size_t )pixel * 2 + 1 ]; }
-            else
-            {
-                size_t pix = first_pixel + pixel;
-                mx = ( double )( pix % sc.prm.image_width ) + 0.5;
-                my = ( double )( pix / sc.prm.image_width ) + 0.5;
-            }
-            camera_ray( sc, mx, my, &rp, &rd );
-        }
-#endif
         bool hit = live && offs < F3_INF;
         V3 acc = mk( 0, 0, 0 );
         if( live && !hit ) acc = v_mld( T, v_mlf( ld3( sc.prm.background_color ), intensity ) );
@@ -1024,14 +957,8 @@ template< class F > DEV void frame_set_con( F& f, bool w, const M3& m ) { f.set3
 /* LEAF_LIGHTS: every light is a plane / sphere / squaroid-free leaf, so the kernel contains no call into the CSG
  * machine at all (the usual case); otherwise the light hit goes through the generic element test.
  * The tasks are idx[ 0 .. min( p_counts[ QC_CLASS0 + cls ], task_cap ) ) (dead entries skipped); the persistent waves of
- * the grid fetch them through the cursor of the class.
- * PART: 0 both sample loops of a task (one pixel add per task); 1 the direct-light loops only; 2 the path loop only (its LCG
- * stream starts behind the 2 * direct_samples draws per light of the loops it does not run): the two halves of a fissioned
- * launch, which share nothing but the task record (see render_chunk). */
-#define ACN_SHADE_BOTH   0
-#define ACN_SHADE_DIRECT 1
-#define ACN_SHADE_PATH   2
-template< int LPT, bool COUNT, bool LEAF_LIGHTS, bool PRUNE, int PART = ACN_SHADE_BOTH >
+ * the grid fetch them through the cursor of the class. */
+template< int LPT, bool COUNT, bool LEAF_LIGHTS, bool PRUNE >
 __global__ __launch_bounds__( 256, ACN_SHADE_WAVES )
 void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t* __restrict__ idx, int cls, uint32_t task_cap, uint32_t fetch_batch,
               HitRec* __restrict__ p_children, uint32_t child_cap, HardShadow* __restrict__ p_hard_shadow,
@@ -1073,7 +1000,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
     for( ;; )
     {
         uint32_t base = 0;
-        uint32_t got = range_take( fr, p_counts + ( PART == ACN_SHADE_PATH ? QC_CUR_SHADEP0 : QC_CUR_SHADE0 ) + cls, fetch_batch, n_tasks, ( uint32_t )G, &base );
+        uint32_t got = range_take( fr, p_counts + QC_CUR_SHADE0 + cls, fetch_batch, n_tasks, ( uint32_t )G, &base );
         if( got == 0 ) break;
         uint32_t ti = base + grp;
         if( ( uint32_t )grp >= got ) continue;
@@ -1106,7 +1033,6 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
         const int n_lights = light->child1;
 
         /* ---- direct light, scene.c:542-581 ---- */
-        if constexpr( PART != ACN_SHADE_PATH )
         for( int li = 0; li < n_lights; li++ )
         {
             int light_idx = __builtin_amdgcn_readfirstlane( sc.elems[ light->child0 + li ] );
@@ -1208,10 +1134,8 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
             lum.x += light_color.x * f; lum.y += light_color.y * f; lum.z += light_color.z * f;
             ACN_LAP( PH_SHADE );
         }
-        if constexpr( PART == ACN_SHADE_PATH ) rv = lcg00_jump( rv, 2 * direct_samples * ( uint64_t )n_lights );
 
         /* ---- path tracing, scene.c:584-621 ---- */
-        if constexpr( PART != ACN_SHADE_DIRECT )
         if( sc.prm.path_samples && t.depth > 10 )
         {
             if( sub == 0 ) cnt.cost( ACN_F_FRAME );
@@ -1362,37 +1286,6 @@ void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint3
     fetch_batch = balanced_batch( n, fetch_batch, 64u );
     FetchRange fr;
     range_init( fr, n > 0 );
-#if ACN_POOLED
-    RayPool pool = ray_pool_of( sc );
-    for( ;; )
-    {
-        uint32_t first = 0;
-        uint32_t got = range_take( fr, p_counts + QC_CUR_HS, fetch_batch, n, 64u, &first );
-        if( !__syncthreads_or( got != 0 ? 1 : 0 ) ) break;   /* the four waves of the workgroup pool their rays: they leave together */
-        HardShadow r;
-        r.pos = mk( 0, 0, 0 ); r.d = mk( 0, 0, 1 ); r.limit = 0; r.contrib = mk( 0, 0, 0 ); r.pixel = ACN_INVALID; r.pad = 0;
-        if( ( threadIdx.x & 63 ) < got ) r = recs[ first + ( threadIdx.x & 63 ) ];
-        const bool live = r.pixel != ACN_INVALID;
-        bool occ = false;
-        ACN_LAP( PH_FETCH );
-        /* a probe of a specular ray (probe_push) asks scene_s_trans_hit's question: the lights count as well.
-         * One call site for both roots (the traversal with the CSG machine is in-line code). */
-        #pragma unroll 1
-        for( int k = 0; k < 2; k++ )
-        {
-            const int root = k ? sc.matter_root : sc.light_root;
-            const bool want = live && !occ && ( k == 1 || ( r.pad & 1u ) );
-            if( !__syncthreads_or( want ? 1 : 0 ) ) continue;
-            bool o2;
-            if constexpr( LDS ) o2 = root_occluded_pooled( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), pool, root, want, r.pos, r.d, r.limit, &cnt );
-            else                o2 = root_occluded_pooled( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), pool, root, want, r.pos, r.d, r.limit, &cnt );
-            if( want && o2 ) occ = true;
-        }
-        ACN_LAP( PH_ROOT_LEAF );
-        if( live && !occ ) { cnt.cost( ACN_F_DIRECT_TAIL ); pixel_add( accum, sc.flags, r.pixel, r.contrib ); }
-        ACN_LAP( PH_SHADE );
-    }
-#else
     for( ;; )
     {
         uint32_t first = 0;
@@ -1413,8 +1306,8 @@ void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint3
                     if( __ballot( want ) == 0ull ) continue;
                     if( want )
                     {
-                        if constexpr( LDS ) occ = root_occluded( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), root, r.pos, r.d, r.limit, &cnt );
-                        else                occ = root_occluded( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), root, r.pos, r.d, r.limit, &cnt );
+                        if constexpr( LDS ) occ = root_occluded( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), root, r.pos, r.d, r.limit, &cnt );
+                        else                occ = root_occluded( scene_view< PRUNE, true >( sc, sc.nodes ), root, r.pos, r.d, r.limit, &cnt );
                     }
                 }
                 ACN_LAP( PH_ROOT_LEAF );
@@ -1423,7 +1316,6 @@ void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint3
             }
         }
     }
-#endif
     ACN_LAP( PH_TAIL );
     ACN_PHASE_FLUSH( counters, 1 )
     wave_add_counters( counters, cnt );
@@ -1455,16 +1347,11 @@ void k_hard_path( ACN_SCENE_PARAMS, const HardPath* __restrict__ recs, uint32_t 
     auto kill_ch = [ p_children ]( uint32_t k ) { p_children[ k ].pixel = ACN_INVALID; };
     FetchRange fr;
     range_init( fr, n > 0 );
-    RayPool pool = ray_pool_of( sc );
     for( ;; )
     {
         uint32_t first = 0;
         uint32_t got = range_take( fr, p_counts + QC_CUR_HP, fetch_batch, n, 64u, &first );
-#if ACN_POOLED
-        if( !__syncthreads_or( got != 0 ? 1 : 0 ) ) break;   /* the four waves of the workgroup pool their rays: they leave together */
-#else
         if( got == 0 ) break;
-#endif
         bool hit = false;
         HardPath r;
         r.pos = mk( 0, 0, 0 ); r.d = mk( 0, 0, 1 ); r.T = mk( 0, 0, 0 ); r.intensity = 0; r.depth = 0; r.pixel = ACN_INVALID;
@@ -1472,17 +1359,11 @@ void k_hard_path( ACN_SCENE_PARAMS, const HardPath* __restrict__ recs, uint32_t 
         trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
         double a = F3_INF;
         if( ( threadIdx.x & 63 ) < got ) r = recs[ first + ( threadIdx.x & 63 ) ];
-#if ACN_POOLED
-        if constexpr( LDS ) a = root_trans_hit_pooled( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), pool, sc.matter_root, r.pixel != ACN_INVALID, r.pos, r.d, &trans, &cnt );
-        else                a = root_trans_hit_pooled( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), pool, sc.matter_root, r.pixel != ACN_INVALID, r.pos, r.d, &trans, &cnt );
-#endif
         if( r.pixel != ACN_INVALID )
         {
             ACN_LAP( PH_FETCH );
-#if !ACN_POOLED
-            if constexpr( LDS ) a = root_trans_hit( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), sc.matter_root, r.pos, r.d, &trans, &cnt );
-            else                a = root_trans_hit( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), sc.matter_root, r.pos, r.d, &trans, &cnt );
-#endif
+            if constexpr( LDS ) a = root_trans_hit( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), sc.matter_root, r.pos, r.d, &trans, &cnt );
+            else                a = root_trans_hit( scene_view< PRUNE, true >( sc, sc.nodes ), sc.matter_root, r.pos, r.d, &trans, &cnt );
             ACN_LAP( PH_ROOT_LEAF );
             hit = a < sc.prm.max_path_length;
             if( !hit )

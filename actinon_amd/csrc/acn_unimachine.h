@@ -21,14 +21,7 @@
 #ifndef ACN_UNIMACHINE_H
 #define ACN_UNIMACHINE_H
 
-#ifndef ACN_UNI_MACHINE
-#define ACN_UNI_MACHINE 1
-#endif
-/* which pairs the lock-step machines evaluate in line (pair_hit / pair_side above) instead of through a frame:
- * 0 none, 1 leaf pairs, 2 leaf pairs and level-2 pairs */
-#ifndef ACN_UNI_PAIR_LEVEL
-#define ACN_UNI_PAIR_LEVEL 2
-#endif
+/* The lock-step machines evaluate leaf pairs and level-2 pairs in line (pair_hit / pair_side above) instead of through a frame. */
 
 #define UF_IN         0x1u
 #define UF_MODE( w )  ( ( ( w ) >> 1 ) & 3u )
@@ -92,17 +85,10 @@ DEV_SIDE int obj_side_uni( SR sc, int root, bool act, V3 pos, CT* cnt )
                 else                            { r = distance_side( n, pos ); cnt->inc( CNT_SDF_EVAL ); }
             }
         }
-#if ACN_UNI_PAIR_LEVEL >= 2
         else if( nflags & ( ACN_GFLAG_LEAF_PAIR | ACN_GFLAG_PAIR2 ) )
         {
             if( in ) r = pair_side< 2 >( g, n, pos, cnt );   /* (leaf pairs too: one expansion of the pair code) */
         }
-#elif ACN_UNI_PAIR_LEVEL >= 1
-        else if( nflags & ACN_GFLAG_LEAF_PAIR )
-        {
-            if( in ) r = pair_side< 1 >( g, n, pos, cnt );
-        }
-#endif
         else if( depth >= ACN_CSG_MAX_DEPTH )
         {
             atomicOr( sc.flags, ACN_FLAG_STACK_OVERFLOW );
@@ -180,7 +166,7 @@ DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, C
     const SceneRefT< NodeP > g = uni_view( sc );
     OrgLds org;
     org.p = nullptr;
-    if constexpr( PARK ) org.p = ( volatile double ACN_LDS* )( ( char ACN_LDS* )acn_lds_raw + sc.lds_stack + ACN_LDS_STACK_BYTES + ACN_LDS_POOL_BYTES ) + threadIdx.x;
+    if constexpr( PARK ) org.p = ( volatile double ACN_LDS* )( ( char ACN_LDS* )acn_lds_raw + sc.lds_stack + ACN_LDS_STACK_BYTES ) + threadIdx.x;
     V3 rp = rp_in;
     auto RP = [ & ]() -> V3 { if constexpr( PARK ) return org.get(); else return rp; };
     auto SET_RP = [ & ]( V3 v ) { if constexpr( PARK ) org.set( v ); else rp = v; };
@@ -232,26 +218,19 @@ DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, C
             }
             ACN_LAP( PH_M_LEAF );
         }
-#if ACN_UNI_PAIR_LEVEL >= 1
-        else if( nflags & ( ACN_UNI_PAIR_LEVEL >= 2 ? ( ACN_GFLAG_LEAF_PAIR | ACN_GFLAG_PAIR2 ) : ACN_GFLAG_LEAF_PAIR ) )
+        else if( nflags & ( ACN_GFLAG_LEAF_PAIR | ACN_GFLAG_PAIR2 ) )
         {
             ACN_TALLY( 14, in );
             if( in )
             {
-#if ACN_UNI_PAIR_LEVEL >= 2
                 /* (a leaf pair through the level-2 code as well: its operands are simple, so every step is the level-1 step,
                  * and the kernel carries one expansion of the pair code instead of two) */
                 if constexpr( PARK ) ret_a = pair_hit< 2, true >( g, n, org, rd, NOR, &ret_n, cnt );
                 else                 ret_a = pair_hit< 2, true >( g, n, rp, rd, NOR, &ret_n, cnt );
-#else
-                if constexpr( PARK ) ret_a = pair_hit< 1, true >( g, n, org, rd, NOR, &ret_n, cnt );
-                else                 ret_a = pair_hit< 1, true >( g, n, rp, rd, NOR, &ret_n, cnt );
-#endif
                 if( NOR && ret_a < F3_INF && n->surface_roughness > 0 ) ret_n = roughness_normal( n, ret_n, ray_pos( RP(), rd, ret_a ) );
             }
             ACN_LAP( PH_M_PAIR );
         }
-#endif
         else if( depth >= ACN_CSG_MAX_DEPTH )
         {
             atomicOr( sc.flags, ACN_FLAG_STACK_OVERFLOW );

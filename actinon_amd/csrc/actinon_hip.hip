@@ -93,15 +93,7 @@ struct Tunables
     uint32_t fetch_hard = 256;         /* ACN_FETCH_HARD: records a wave of the hard-ray kernels / k_shade_hits reserves per atomic */
     uint32_t stack_use = 0;            /* ACN_TEST_STACK_USE: slots of a private stack every walk pass but the last uses (tests of the overflow path) */
     bool     debug_chunks = false;     /* ACN_DEBUG_CHUNKS=1: one line per chunk on stderr (size, queue marks, rates, capacities) */
-    bool     ws_uniform = false;       /* ACN_WS_UNIFORM=1: every queue gets the same share of the whole bound at once (round 2's layout; diagnostic) */
-    int      learn_grids = 0;          /* ACN_LEARN_GRIDS: 0 every launch of a chain gets the full persistent grid; 1 the grids follow the input of the
-                                        * last chunk (learned_grid); 2 only launches whose input was empty then get a small grid.  Measured, off: see learned_grid */
-    double   grid_passes = 1.0;        /* ACN_GRID_PASSES: a learned grid gives a workgroup this many workgroup-loads of the input it expects (x 1/2: head room) */
     bool     learn_passes = true;      /* ACN_LEARN_PASSES=0: every level gets ACN_WALK_PASSES launches of k_walk, needed or not */
-    bool     shade_fission = false;    /* ACN_SHADE_FISSION=1: the two sample loops of a shading point run as two launches, the direct-light half and its
-                                          deferred shadow rays on a side stream (render_chunk).  Measured and OFF: 1080p 52.0 -> 56.7 ms, the 1/8 share
-                                          13.7 -> 17 - 20 ms, c2 28.0 -> 31.9, paraffin_lamp 365 -> 400 - 450 (profiles/r04/ab_fission.txt): every lane then
-                                          has two streams of persistent grids, and eight grids of 512 - 1024 workgroups take turns on one chip */
     bool     learn_sample = true;      /* ACN_LEARN_SAMPLE=0: no strided learning pass on a cold handle (learn_rates): the first chunks learn, as in round 3 */
     bool     cold_pipeline = true;     /* ACN_COLD_PIPELINE=0: a cold handle makes its lanes before the learning pass, not beside it (render_lanes) */
     bool     early_lanes = false;      /* ACN_EARLY_LANES=1: the lanes a whole frame of the scene's own raster will use are made during acn_scene_upload (a
@@ -136,14 +128,10 @@ struct Tunables
         if( fetch_hard < 64 ) fetch_hard = 64;
         count_work = getenv( "ACN_COUNT_WORK" ) != nullptr;
         if( const char* e = getenv( "ACN_LEARN_PASSES" ) ) learn_passes = atoi( e ) != 0;
-        if( const char* e = getenv( "ACN_LEARN_GRIDS" ) ) learn_grids = atoi( e );
         if( const char* e = getenv( "ACN_LEARN_SAMPLE" ) ) learn_sample = atoi( e ) != 0;
         if( const char* e = getenv( "ACN_COLD_PIPELINE" ) ) cold_pipeline = atoi( e ) != 0;
         if( const char* e = getenv( "ACN_EARLY_LANES" ) ) early_lanes = atoi( e ) != 0;
-        if( const char* e = getenv( "ACN_SHADE_FISSION" ) ) shade_fission = atoi( e ) != 0;
-        if( const char* e = getenv( "ACN_WS_UNIFORM" ) ) ws_uniform = atoi( e ) != 0;
         debug_chunks = getenv( "ACN_DEBUG_CHUNKS" ) != nullptr;
-        if( const char* e = getenv( "ACN_GRID_PASSES" ) ) { grid_passes = atof( e ); if( !( grid_passes >= 0.25 && grid_passes <= 64.0 ) ) grid_passes = 1.0; }
         stage_timing = getenv( "ACN_STAGE_TIMING" ) != nullptr;
         if( lanes < 1 ) lanes = 1;
         if( lanes > 16 ) lanes = 16;
@@ -184,10 +172,7 @@ struct acn_scene_handle
     acn_texture* d_textures = nullptr;
     SCEntry* d_sc_table = nullptr;
     double* d_sc_spheres = nullptr;            /* ( pos, radius ) of the sphere leaves of d_sc_table */
-    double* d_env_tab = nullptr;               /* envelopes of the compound slices, element by element (acn_device.h: root_candidates) */
     hipStream_t stream = nullptr;
-    hipStream_t side_stream = nullptr;         /* the direct-light half of a fissioned level and its deferred shadow rays (render_chunk) */
-    hipEvent_t ev_fork = nullptr, ev_path = nullptr, ev_join = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
     int cur_stage = 0;
@@ -223,11 +208,6 @@ struct acn_scene_handle
     size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
     uint64_t chunks = 0, retries = 0, levels = 0;
     uint64_t peak_tasks = 0, peak_children = 0;
-    /* learned: the input of every launch of the last chunk's chain and the positions of that chunk ( 0: nothing known ) */
-    uint32_t seen_cnt = 0;
-    uint32_t seen_class[ ACN_MAX_PATH_LEVELS + 1 ][ ACN_NCLASS ] = {};
-    uint32_t seen_hs[ ACN_MAX_PATH_LEVELS + 1 ] = {}, seen_hp[ ACN_MAX_PATH_LEVELS + 1 ] = {}, seen_hits[ ACN_MAX_PATH_LEVELS + 1 ] = {};
-    uint32_t seen_gen[ ACN_MAX_PATH_LEVELS + 1 ][ ACN_MAX_WALK_PASSES + 2 ] = {};
     uint32_t walk_passes_seen[ ACN_MAX_PATH_LEVELS + 1 ] = { 0, 0, 0, 0, 0, 0 };   /* learned: passes of a level that had input in the last chunk (0: not known yet) */
     unsigned long long* d_counters_keep = nullptr;   /* the work counters as they were before the current chunk (restored when it is redone) */
     /* concurrent lanes (render_lanes): clones of this handle that share the resident scene and own a stream and a
@@ -515,7 +495,7 @@ extern "C" int acn_device_count( void )
     return n;
 }
 
-static int lane_objects( int device, bool side_stream, bool debug, acn_scene_handle** out );
+static int lane_objects( int device, bool debug, acn_scene_handle** out );
 static int lanes_for_counts( int tun_lanes, size_t n, uint64_t path_samples );
 
 /* Lanes made during the upload.  A stream that gets its own hardware queue costs ~10 ms of host time, and making one while kernels
@@ -529,13 +509,13 @@ static void early_lanes_begin( acn_scene_handle* h, size_t n, uint64_t path_samp
 {
     const int lanes = lanes_for_counts( h->tun.lanes, n, path_samples );
     if( lanes <= 1 || path_samples >= 256 ) return;
-    const int device = h->device; const bool side = h->tun.shade_fission, debug = h->tun.debug_chunks;
-    h->early_maker = std::thread( [ h, lanes, device, side, debug ]()
+    const int device = h->device; const bool debug = h->tun.debug_chunks;
+    h->early_maker = std::thread( [ h, lanes, device, debug ]()
     {
         for( int k = 0; k < lanes; k++ )
         {
             acn_scene_handle* l = nullptr;
-            if( lane_objects( device, side, debug, &l ) != ACN_OK ) break;
+            if( lane_objects( device, debug, &l ) != ACN_OK ) break;
             h->early_made.push_back( l );
         }
     } );
@@ -595,12 +575,8 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     HIP_TRY_H( hipStreamCreate( &h->stream ) );
     const double t_stream1 = since();   /* (the first stream a process makes: 85 - 100 ms on this runtime; later ones ~10) */
     /* (a stream costs ~10 ms of host time to make: the second one only where it is used) */
-    if( h->tun.shade_fission ) HIP_TRY_H( hipStreamCreateWithFlags( &h->side_stream, hipStreamNonBlocking ) );
     HIP_TRY_H( hipEventCreate( &h->ev0 ) );
     HIP_TRY_H( hipEventCreate( &h->ev1 ) );
-    HIP_TRY_H( hipEventCreateWithFlags( &h->ev_fork, hipEventDisableTiming ) );
-    HIP_TRY_H( hipEventCreateWithFlags( &h->ev_path, hipEventDisableTiming ) );
-    HIP_TRY_H( hipEventCreateWithFlags( &h->ev_join, hipEventDisableTiming ) );
 
     /* ABI layout -> device layout: geometry (GNode) and shading properties (GMat) split */
     std::vector< GNode > nodes( scene->n_nodes );
@@ -697,17 +673,6 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
             if( a.type != ACN_COMPOUND || a.child1 < 2 ) continue;
             int32_t* first = elems2.data() + scene->n_elems + a.child0;
             std::stable_sort( first, first + a.child1, [ & ]( int32_t x, int32_t y ) { return node_cost( x ) < node_cost( y ); } );
-        }
-    }
-    /* the envelope of every entry of elems[ 0 .. 2n ), in the same order: the broad phase of the root loops (root_candidates) */
-    std::vector< double > env_tab( 8 * ( size_t )scene->n_elems + 4, -1.0 );
-    for( size_t k = 0; k < 2 * ( size_t )scene->n_elems; k++ )
-    {
-        const acn_node& a = scene->nodes[ elems2[ k ] ];
-        if( a.flags & ACN_NODE_HAS_ENVELOPE )
-        {
-            for( int c = 0; c < 3; c++ ) env_tab[ 4 * k + c ] = a.env_pos[ c ];
-            env_tab[ 4 * k + 3 ] = a.env_radius;
         }
     }
     /* elems[ 2n .. 2n + n_nodes ): per node the offset of its interval-prune program (acn_device.h: prune_run) or -1,
@@ -938,9 +903,6 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     HIP_TRY_H( hipMalloc( &h->d_sc_spheres, sizeof( double ) * ( sc_spheres.size() ? sc_spheres.size() : 4 ) ) );
     if( sc_spheres.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_spheres, sc_spheres.data(), sizeof( double ) * sc_spheres.size(), hipMemcpyHostToDevice ) );
     h->dev.sc_spheres = h->d_sc_spheres;
-    HIP_TRY_H( hipMalloc( &h->d_env_tab, sizeof( double ) * env_tab.size() ) );
-    HIP_TRY_H( hipMemcpy( h->d_env_tab, env_tab.data(), sizeof( double ) * env_tab.size(), hipMemcpyHostToDevice ) );
-    h->dev.env_tab = ( CDblP )h->d_env_tab;
     /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
      * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
      * and divergent (nested compounds, CSG objects with prune programs: the scenes of the "extras" kernel variants).
@@ -1000,10 +962,10 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
         if( !generic_compound ) lds_max = 0;
         if( const char* e = getenv( "ACN_LDS_MAX" ) ) lds_max = ( size_t )atoll( e );
         size_t need = sizeof( GNode ) * ( size_t )scene->n_nodes;
-        /* every machine kernel owns the stacks AND the ray pool of its workgroup (pooled_machine_hit); nodes are staged in front
-         * of them only if the three fit 40 KB (four workgroups per CU) */
-        h->lds_bytes = need <= lds_max && need + ACN_LDS_STACK_BYTES + ACN_LDS_POOL_BYTES + ACN_LDS_ORG_BYTES <= 40960 ? need : 0;
-        h->lds_stack_bytes = ACN_LDS_STACK_BYTES + ACN_LDS_POOL_BYTES + ACN_LDS_ORG_BYTES;
+        /* every machine kernel owns the stacks and the parked ray origins of its workgroup; nodes are staged in front of them
+         * only if all of it fits 40 KB (four workgroups per CU) */
+        h->lds_bytes = need <= lds_max && need + ACN_LDS_STACK_BYTES + ACN_LDS_ORG_BYTES <= 40960 ? need : 0;
+        h->lds_stack_bytes = ACN_LDS_STACK_BYTES + ACN_LDS_ORG_BYTES;
     }
     h->dev.flags = h->d_counts + QC_FLAGS;
     h->dev.lds_stack = h->lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
@@ -1070,17 +1032,12 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
         if( h->d_textures ) hipFree( h->d_textures );
         if( h->d_sc_table ) hipFree( h->d_sc_table );
         if( h->d_sc_spheres ) hipFree( h->d_sc_spheres );
-        if( h->d_env_tab ) hipFree( h->d_env_tab );
     }
     if( h->d_counters ) hipFree( h->d_counters );
     if( h->d_counters_keep ) hipFree( h->d_counters_keep );
     for( auto& e : h->events ) { hipEventDestroy( e.a ); hipEventDestroy( e.b ); }
     if( h->ev0 ) hipEventDestroy( h->ev0 );
     if( h->ev1 ) hipEventDestroy( h->ev1 );
-    if( h->ev_fork ) hipEventDestroy( h->ev_fork );
-    if( h->ev_path ) hipEventDestroy( h->ev_path );
-    if( h->ev_join ) hipEventDestroy( h->ev_join );
-    if( h->side_stream ) hipStreamDestroy( h->side_stream );
     if( h->stream ) hipStreamDestroy( h->stream );
     delete h;
 }
@@ -1124,16 +1081,7 @@ static int ensure_workspace( acn_scene_handle* h, size_t n )
     const size_t stack_bytes = stack_waves * h->tun.stack_cap * sizeof( RayTask );
     size_t want[ WQ_N ];
     bool trim = false;
-    if( h->tun.ws_uniform )
-    {
-        size_t per_rec = wq_bytes[ WQ_HARD_SHADOW ];
-        for( int q = 0; q < WQ_N; q++ ) per_rec += wq_bytes[ q ];
-        size_t recs = budget > stack_bytes ? ( budget - stack_bytes ) / per_rec : 65536;
-        if( recs > 0x7FFFFF00ull ) recs = 0x7FFFFF00ull;
-        for( int q = 0; q < WQ_N; q++ ) want[ q ] = recs;
-        want[ WQ_HARD_SHADOW ] = 2 * recs;
-    }
-    else if( !rates_known( h ) )
+    if( !rates_known( h ) )
     {
         /* starter set: 2^20 records per queue (the deferred-shadow queue twice that), less for a call of a few positions */
         const size_t s = h->dev.prm.path_samples ? h->dev.prm.path_samples : 1;
@@ -1175,7 +1123,7 @@ static int ensure_workspace( acn_scene_handle* h, size_t n )
      * later and put 100 ms of hipFree + hipMalloc into an arbitrary frame (round 4, session 10: the 1080p bench line read 68.6 ms
      * instead of 51.8 because the trim fell into its ten timed steps) */
     if( rates_known( h ) && h->rate_cnt >= 32768 ) w.sized_calls++;
-    if( fits && rates_known( h ) && !h->tun.ws_uniform && h->rate_cnt >= 32768 && !w.trimmed && w.sized_calls <= 3 )
+    if( fits && rates_known( h ) && h->rate_cnt >= 32768 && !w.trimmed && w.sized_calls <= 3 )
     {
         size_t have = 0, need = 0;
         for( int q = 0; q < WQ_N; q++ ) { have += ( size_t )w.cap[ q ] * wq_bytes[ q ]; need += want[ q ] * wq_bytes[ q ]; }
@@ -1262,7 +1210,7 @@ static LevelQ level_queues( const acn_scene_handle* h, int level )
     q.stacks = w.stacks; q.stack_cap = h->tun.stack_cap; q.stack_use = h->tun.stack_use;
     q.counts = h->d_counts + ( size_t )level * QC_N;
     q.prev_children = h->d_counts + ( size_t )( level > 0 ? level - 1 : 0 ) * QC_N + QC_CHILDREN;
-    q.grid = h->grid; q.shade_grid = h->shade_grid;
+    q.grid = h->grid; q.shade_grid = h->shade_grid; q.walk_grid = h->walk_grid;
     q.fetch_walk = h->tun.fetch_walk; q.fetch_hard = h->tun.fetch_hard; q.private_limit = h->tun.private_limit; q.fetch_shade = h->tun.fetch_shade;
     /* the outermost sample loops are those of level 0 */
     const bool sharded = level == 0 && h->shard_world > 1;
@@ -1285,27 +1233,6 @@ static uint32_t walk_passes_of_level( const acn_scene_handle* h, int level )
     const uint32_t seen = h->tun.learn_passes ? h->walk_passes_seen[ level ] : 0u;
     if( seen && seen + 1 < passes ) passes = seen + 1;
     return passes;
-}
-
-/* Workgroups for a launch whose input had `seen` items in the last chunk of `seen_cnt` positions, scaled to this chunk's `cnt`
- * positions: enough workgroups for twice that input at `per_wg` items each -- what ONE workgroup takes on at a time (256
- * records, 256 / lanes-per-task shading tasks), times ACN_GRID_PASSES -- at least 16, at most the persistent grid.  The
- * kernels are persistent and fetch their work through cursors, so ANY grid finishes ANY input: a guess that is too small
- * costs time, never work.
- * OFF by default since the closing measurements of round 3 (profiles/r03/learned_grids_*.txt, four same-box sessions): the
- * 1080p frame gains 0.2 - 0.7 ms of 70 and C1 0.07 of 1.41 ms, but paraffin_lamp 400x600 loses 15 - 20 % (420 -> 510 ms, in
- * mode 2 as well, i.e. through launches whose input was empty in the chunk before), hanging_lamp 600x800 2 - 5 % and the 1/8
- * share of the 1080p frame 2 - 3 %.  What it buys: most launches of a chain are small (a generation of a few thousand rays, the
- * shading tasks of a size class nothing falls into), and a launch of 512 workgroups that has nothing to do still has to
- * get every one of them onto a chip that the other lanes keep busy -- 0.3 - 1 ms each in the kernel trace of round 2. */
-static unsigned learned_grid( const acn_scene_handle* h, uint32_t seen, uint32_t cnt, uint32_t per_wg, unsigned full )
-{
-    if( !h->tun.learn_grids || h->seen_cnt == 0 ) return full;
-    if( h->tun.learn_grids == 2 ) return seen == 0 ? 16u : full;
-    const double items = 2.0 * ( double )seen * ( double )cnt / ( double )h->seen_cnt + 1.0;
-    double g = items / ( ( double )per_wg * h->tun.grid_passes );
-    if( g < 16.0 ) g = 16.0;
-    return g >= ( double )full ? full : ( unsigned )g;
 }
 
 #define ACN_LAUNCH( h, stage, stream, call ) do { int st_ = stage_begin( h, stage, stream ); if( st_ != ACN_OK ) return st_; call; \
@@ -1351,76 +1278,31 @@ static int render_chunk( acn_scene_handle* h, const Primary& prim, uint32_t base
     const uint32_t n_cam = prim.rays ? 0u : cnt;
     for( int level = 0; level < levels; level++ )
     {
-        const LevelQ q = level_queues( h, level );
+        LevelQ q = level_queues( h, level );
         /* the path-sample hits of the level before are shaded (level >= 1), then the specular rays walked: generation
          * passes while the generations are large, the rest on the waves' private stacks (k_walk); a level has at most as
          * many generations as its hits have depth left */
-        LevelQ qg = q;   /* the level's queues with the grid of the launch at hand (learned_grid) */
         /* a small chunk (<= 2^17 positions) of a frame without path tracing finishes every generation that is no larger than
          * itself on the private stacks: its generations are not worth a launch each (C1, 120 000 pixels on one lane: 1.41 ->
          * 1.15 ms).  With path samples the rule was measured and dropped: the 1/8 share of the 1080p frame 15.2 -> 14.8 ms and
          * hanging_lamp 600x800 -3 %, but paraffin_lamp 400x600 +8 % -- the rays of a CSG scene are worth redistributing
          * (profiles/r03/private_limit_small_frames.txt) */
-        if( !h->tun.private_limit_set && h->dev.prm.path_samples == 0 && cnt <= ( 1u << 17 ) && cnt > qg.private_limit ) qg.private_limit = cnt;
-        if( level > 0 )
-        {
-            qg.grid = learned_grid( h, h->seen_hits[ level ], cnt, 256u, h->grid );
-            ACN_LAUNCH( h, 0, stream, acn_launch_shade_hits( f.count, qg, stream, s, h->d_accum, h->d_counters ) );
-        }
+        if( !h->tun.private_limit_set && h->dev.prm.path_samples == 0 && cnt <= ( 1u << 17 ) && cnt > q.private_limit ) q.private_limit = cnt;
+        if( level > 0 ) ACN_LAUNCH( h, 0, stream, acn_launch_shade_hits( f.count, q, stream, s, h->d_accum, h->d_counters ) );
         const uint32_t passes = walk_passes_of_level( h, level );
         for( uint32_t pass = 0; pass < passes; pass++ )
         {
-            /* the last launch of a level finishes whatever is left on the private stacks: the input of all later generations */
-            uint32_t seen = level == 0 && pass == 0 ? h->seen_cnt : h->seen_gen[ level ][ pass ];
-            if( pass + 1 == passes ) for( uint32_t g = pass + 1; g <= ACN_MAX_WALK_PASSES; g++ ) seen += h->seen_gen[ level ][ g ];
-            /* (k_walk keeps its full grid unless the pass had no input at all: its rays multiply on the private stacks, and
-             * hanging_lamp 600x800 lost 7 % with grids sized to the input) */
-            qg.grid = ( level == 0 && pass == 0 ) || seen != 0 ? h->walk_grid : learned_grid( h, 0, cnt, 512u, h->walk_grid );
-            ACN_LAUNCH( h, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes, qg, lds, stream, s, prim.pos_xy, prim.first, base,
+            /* (the last launch of a level finishes whatever is left on the private stacks: the input of all later generations) */
+            ACN_LAUNCH( h, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes, q, lds, stream, s, prim.pos_xy, prim.first, base,
                                                        level == 0 && pass == 0 ? n_cam : 0u, order, h->d_accum, h->d_counters ) );
         }
-        /* ACN_SHADE_FISSION=1 (off by default: measured slower, see Tunables).  The two sample loops of a shading point share
-         * nothing but the task record, so the level can fork: the direct-light loops and the shadow rays they defer on the side
-         * stream, the path loop and the path rays it defers on the main one.  The critical path of a level is then
-         * walk -> max( direct + hard_shadow, path + hard_path ) instead of their sum.  k_hard_shadow also takes the probes the path
-         * loop appends, so it waits for that launch (ev_path); the queues are the level's, so the next level waits for both.
-         * The last level of a frame casts no path rays (depth <= 10) and a frame without path samples has one level: no fork. */
-        const bool fork = h->tun.shade_fission && level + 1 < levels && h->side_stream != nullptr;
-        hipStream_t direct_stream = fork ? h->side_stream : stream;
-        if( fork )
-        {
-            HIP_TRY( hipEventRecord( h->ev_fork, stream ) );
-            HIP_TRY( hipStreamWaitEvent( h->side_stream, h->ev_fork, 0 ) );
-        }
-        for( int part = fork ? ACN_SHADE_DIRECT : ACN_SHADE_BOTH; part <= ( fork ? ACN_SHADE_PATH : ACN_SHADE_BOTH ); part++ )
-        {
-            hipStream_t part_stream = part == ACN_SHADE_DIRECT ? direct_stream : stream;
-            qg.shade_grid = learned_grid( h, h->seen_class[ level ][ 0 ], cnt, 4u, h->shade_grid );
-            ACN_LAUNCH( h, 1, part_stream, acn_launch_shade64( f, qg, part_stream, s, h->d_accum, h->d_counters, part ) );
-            qg.shade_grid = learned_grid( h, h->seen_class[ level ][ 1 ], cnt, 16u, h->shade_grid );
-            ACN_LAUNCH( h, 1, part_stream, acn_launch_shade16( f, qg, part_stream, s, h->d_accum, h->d_counters, part ) );
-            qg.shade_grid = learned_grid( h, h->seen_class[ level ][ 2 ], cnt, 64u, h->shade_grid );
-            ACN_LAUNCH( h, 1, part_stream, acn_launch_shade4( f, qg, part_stream, s, h->d_accum, h->d_counters, part ) );
-            qg.shade_grid = learned_grid( h, h->seen_class[ level ][ 3 ], cnt, 256u, h->shade_grid );
-            ACN_LAUNCH( h, 1, part_stream, acn_launch_shade1( f, qg, part_stream, s, h->d_accum, h->d_counters, part ) );
-        }
-        if( fork )
-        {
-            HIP_TRY( hipEventRecord( h->ev_path, stream ) );
-            HIP_TRY( hipStreamWaitEvent( h->side_stream, h->ev_path, 0 ) );
-        }
-        qg.grid = learned_grid( h, h->seen_hs[ level ], cnt, 256u, h->grid );
-        ACN_LAUNCH( h, 3, direct_stream, acn_launch_hard_shadow( f, qg, lds, direct_stream, s, h->d_accum, h->d_counters ) );
-        if( level + 1 < levels )   /* the last level casts no path rays (depth <= 10) */
-        {
-            qg.grid = learned_grid( h, h->seen_hp[ level ], cnt, 256u, h->grid );
-            ACN_LAUNCH( h, 3, stream, acn_launch_hard_path( f, qg, lds, stream, s, h->d_accum, h->d_counters ) );
-        }
-        if( fork )
-        {
-            HIP_TRY( hipEventRecord( h->ev_join, h->side_stream ) );
-            HIP_TRY( hipStreamWaitEvent( stream, h->ev_join, 0 ) );
-        }
+        ACN_LAUNCH( h, 1, stream, acn_launch_shade64( f, q, stream, s, h->d_accum, h->d_counters ) );
+        ACN_LAUNCH( h, 1, stream, acn_launch_shade16( f, q, stream, s, h->d_accum, h->d_counters ) );
+        ACN_LAUNCH( h, 1, stream, acn_launch_shade4( f, q, stream, s, h->d_accum, h->d_counters ) );
+        ACN_LAUNCH( h, 1, stream, acn_launch_shade1( f, q, stream, s, h->d_accum, h->d_counters ) );
+        ACN_LAUNCH( h, 3, stream, acn_launch_hard_shadow( f, q, lds, stream, s, h->d_accum, h->d_counters ) );
+        /* the last level casts no path rays (depth <= 10) */
+        if( level + 1 < levels ) ACN_LAUNCH( h, 3, stream, acn_launch_hard_path( f, q, lds, stream, s, h->d_accum, h->d_counters ) );
     }
     HIP_TRY( hipMemcpyAsync( h->h_counts, h->d_counts, sizeof( uint32_t ) * QC_N * levels, hipMemcpyDeviceToHost, stream ) );
     HIP_TRY( hipStreamSynchronize( stream ) );
@@ -1491,15 +1373,6 @@ static int render_chunk( acn_scene_handle* h, const Primary& prim, uint32_t base
             seen[ level ] = ( used == launched && launched > 1 ) ? used + 2 : used;
         }
         for( int level = 0; level < levels; level++ ) h->walk_passes_seen[ level ] = seen[ level ];
-        h->seen_cnt = cnt;
-        for( int level = 0; level < levels; level++ )
-        {
-            const uint32_t* c = h->h_counts + ( size_t )level * QC_N;
-            for( int k = 0; k < ACN_NCLASS; k++ ) h->seen_class[ level ][ k ] = c[ QC_CLASS0 + k ];
-            h->seen_hs[ level ] = c[ QC_HARD_SHADOW ]; h->seen_hp[ level ] = c[ QC_HARD_PATH ];
-            h->seen_hits[ level ] = level > 0 ? h->h_counts[ ( size_t )( level - 1 ) * QC_N + QC_CHILDREN ] : 0u;
-            for( int g = 0; g <= ACN_MAX_WALK_PASSES; g++ ) h->seen_gen[ level ][ g ] = c[ QC_GEN + g ];
-        }
     }
     return ACN_OK;
 }
@@ -1524,7 +1397,7 @@ static void set_rates( acn_scene_handle* h, uint32_t cnt, const uint32_t* fill, 
  * queues are then sized ONCE, while the device is idle (launch_render; render_lanes for all lanes of a call). */
 static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipStream_t stream, size_t plan_positions, unsigned plan_grid )
 {
-    if( rates_known( h ) || !h->tun.learn_sample || h->tun.chunk || h->tun.ws_uniform || n < 16384 ) return ACN_OK;
+    if( rates_known( h ) || !h->tun.learn_sample || h->tun.chunk || n < 16384 ) return ACN_OK;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     int st = ensure_workspace( h, 4096 );   /* the starter set */
@@ -1609,7 +1482,6 @@ static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipS
         break;
     }
     for( int level = 0; level <= ACN_MAX_PATH_LEVELS; level++ ) h->walk_passes_seen[ level ] = 0;
-    h->seen_cnt = 0;
     h->count_work = count_work; h->stage_timing = stage_timing;
     return st;
 }
@@ -1723,7 +1595,6 @@ static int launch_render( acn_scene_handle* h, const Primary& prim, size_t n, do
             /* the marks of an overflowed chunk are lower bounds of its demand */
             for( int q = 0; q < WQ_N; q++ ) { const double r = ( double )fill[ q ] / ( double )cnt; if( r > h->rate[ q ] ) h->rate[ q ] = r; }
             for( int level = 0; level <= ACN_MAX_PATH_LEVELS; level++ ) h->walk_passes_seen[ level ] = 0;   /* the full number of passes again */
-            h->seen_cnt = 0;                                                                                 /* ... and full grids */
             hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, h->d_accum, ( uint32_t )base, cnt, order );
             HIP_TRY( hipGetLastError() );
             continue;
@@ -1827,13 +1698,12 @@ __global__ void k_lane_gather_rays( const double* __restrict__ rays, size_t n_la
     for( int k = 0; k < 6; k++ ) lane_rays[ i * 6 + k ] = rays[ g * 6 + k ];
 }
 
-/* A lane = a clone of the handle that borrows the resident scene and owns two streams, its events, counter blocks and a host
+/* A lane = a clone of the handle that borrows the resident scene and owns a stream, its events, counter blocks and a host
  * thread.  Making a stream takes ~10 ms of host time (tools/bench_alloc: 12 streams 120 - 130 ms, one after the other whatever thread
- * asks; events, pinned memory and hipMalloc of any size are free beside that), so six lanes with two streams each were 60 - 100 ms of
- * a handle's first call, more than its learning pass on the wine glass.  The side stream is made only where it is used
- * (ACN_SHADE_FISSION), and so the HIP objects (lane_objects: nothing in it reads the parent) are made on a helper
- * thread while the learning pass runs on the device (render_lanes), and the parent's fields are copied afterwards (bind_lane). */
-static int lane_objects( int device, bool side_stream, bool debug, acn_scene_handle** out )
+ * asks; events, pinned memory and hipMalloc of any size are free beside that), so six lanes are 60 ms of a handle's first call, more
+ * than its learning pass on the wine glass.  The HIP objects (lane_objects: nothing in it reads the parent) are therefore made on a
+ * helper thread while the learning pass runs on the device (render_lanes), and the parent's fields are copied afterwards (bind_lane). */
+static int lane_objects( int device, bool debug, acn_scene_handle** out )
 {
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
@@ -1846,12 +1716,8 @@ static int lane_objects( int device, bool side_stream, bool debug, acn_scene_han
     t[ 0 ] = since();
     HIP_TRY_L( hipStreamCreateWithFlags( &l->stream, hipStreamNonBlocking ) );
     t[ 1 ] = since();
-    if( side_stream ) HIP_TRY_L( hipStreamCreateWithFlags( &l->side_stream, hipStreamNonBlocking ) );
     HIP_TRY_L( hipEventCreate( &l->ev0 ) );
     HIP_TRY_L( hipEventCreate( &l->ev1 ) );
-    HIP_TRY_L( hipEventCreateWithFlags( &l->ev_fork, hipEventDisableTiming ) );
-    HIP_TRY_L( hipEventCreateWithFlags( &l->ev_path, hipEventDisableTiming ) );
-    HIP_TRY_L( hipEventCreateWithFlags( &l->ev_join, hipEventDisableTiming ) );
     t[ 2 ] = since();
     HIP_TRY_L( hipMalloc( &l->d_counters, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
     HIP_TRY_L( hipMalloc( &l->d_counters_keep, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
@@ -1933,7 +1799,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
         for( int k = 0; k < missing && made_status == ACN_OK; k++ )
         {
             acn_scene_handle* l = nullptr;
-            made_status = lane_objects( h->device, h->tun.shade_fission, h->tun.debug_chunks, &l );
+            made_status = lane_objects( h->device, h->tun.debug_chunks, &l );
             if( made_status == ACN_OK ) made.push_back( l ); else made_message = g_last_error;   /* thread-local where it was set */
         }
     };

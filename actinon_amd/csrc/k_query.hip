@@ -115,12 +115,9 @@ void k_query( ACN_SCENE_PARAMS, int op, int32_t node, const double* __restrict__
     const uint64_t skip = limits ? ( ( const uint64_t* )limits )[ 2 * i + 1 ] : 0ull;
     double* o = out + ACN_Q_STRIDE * i;
     for( int k = 0; k < ACN_Q_STRIDE; k++ ) o[ k ] = 0;
-    if constexpr( LDS ) query_one( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), op, node, rp, rd, limit, skip, o );
-    else                query_one( scene_view< PRUNE, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), op, node, rp, rd, limit, skip, o );
+    if constexpr( LDS ) query_one( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), op, node, rp, rd, limit, skip, o );
+    else                query_one( scene_view< PRUNE, true >( sc, sc.nodes ), op, node, rp, rd, limit, skip, o );
 }
-
-/* root_occluded_pooled is not queried: it exists only in builds with ACN_POOLED=1 (off: measured slower, acn_device.h),
- * and all lanes of a workgroup must call it together, which per-ray queries of a subset of lanes cannot do. */
 
 /* the elements of compound `node` with the device-only bits of their headers; one lane */
 __global__ void k_query_elements( ACN_SCENE_PARAMS, int32_t node, double* __restrict__ out, size_t n )

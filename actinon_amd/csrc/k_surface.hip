@@ -112,8 +112,8 @@ void k_surface( ACN_SCENE_PARAMS, const double* __restrict__ rays, const double*
     {
         if( mine )
         {
-            if constexpr( LDS ) a = surface_trans_hit( scene_view< true, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &light_root );
-            else                a = surface_trans_hit( scene_view< true, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), rp, rd, &trans, &light_root );
+            if constexpr( LDS ) a = surface_trans_hit( scene_view< true, true >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &light_root );
+            else                a = surface_trans_hit( scene_view< true, true >( sc, sc.nodes ), rp, rd, &trans, &light_root );
         }
         dist = a;
         if( a < F3_INF ) kind = surface_kind( sc, surface_material( sc, trans ), trans, light_root );
@@ -128,8 +128,8 @@ void k_surface( ACN_SCENE_PARAMS, const double* __restrict__ rays, const double*
             if( live )
             {
                 trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
-                if constexpr( LDS ) a = surface_trans_hit( scene_view< true, ACN_PARK_ORIGIN != 0 >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &light_root );
-                else                a = surface_trans_hit( scene_view< true, ACN_PARK_ORIGIN != 0 >( sc, sc.nodes ), rp, rd, &trans, &light_root );
+                if constexpr( LDS ) a = surface_trans_hit( scene_view< true, true >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &light_root );
+                else                a = surface_trans_hit( scene_view< true, true >( sc, sc.nodes ), rp, rd, &trans, &light_root );
                 dist += a;
                 live = a < F3_INF;
             }

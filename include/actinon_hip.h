@@ -363,7 +363,6 @@ int acn_detmath_eval( int device, int op, const double* x, const double* y, doub
  *   TRANS              root_trans_hit on compound `node`                a, exit normal[3], exit, enter object;
  *                      root_trans_hit_fast (+ the full redo if hard)    [ 6 .. 11 ] the same, [ 12 ] hard
  *   OCCLUDED           root_occluded, root_occluded_fast( skip ) on compound `node`
- *                      (not root_occluded_pooled: compiled only with ACN_POOLED=1, which production builds leave off)
  *   CONE_CULL          root_cone_cull of the matter root for light `node` seen from the origin: mask, axis[3], cos theta
  *   SC_HIT             simple_compound_hit on `node`: a, normal[3], hit object, any-hit( limit )
  *   ELEMENTS           no rays: per element of compound `node` (n at most): index, ACN_Q_EL_* bits, type; out[ 3 ]:
