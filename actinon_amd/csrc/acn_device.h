@@ -1624,9 +1624,13 @@ DEV bool prune_exec( NP nodes, ElemP elems, int pc, V3 rp, V3 rd, double limit )
 /* Hit test of ROOT element `e` (an index that is the same in every active lane of the wave, so the node is read
  * through the scalar cache into SGPRs and the type dispatch is a scalar branch): obj_ray_hit (objects.c:261-284)
  * for objects -- plane / sphere / squaroid inline, CSG and SDF objects through the hit machine -- and
- * compound_s_ray_hit for nested compounds. */
+ * compound_s_ray_hit for nested compounds.
+ * pre (per lane): run the pre-tests that can only answer "no hit": the element's envelope, surely_outside and the prune
+ * program.  A lane whose ray k_shade has already put through the same tests with the answer "not ruled out" passes false
+ * (resumed records, see the fast-path forms below); what is evaluated then is evaluated as ever.  (A generic nested compound
+ * keeps its envelope test: it belongs to compound_ray_hit_dev, a real call that k_walk shares.) */
 template< bool NOR, class SC, class CT >
-DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj, double limit, CT* cnt )
+DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj, double limit, CT* cnt, bool pre = true )
 {
     ACN_NODE_UNIFORM( n, &sc.nodes[ e ] )
     int type = n->type;
@@ -1636,7 +1640,7 @@ DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj
         {
             if( n->flags & ACN_GFLAG_SIMPLE_COMPOUND )
             {
-                if( node_has_env( n ) && !env_ray_hits( n, rp, rd ) ) return F3_INF;
+                if( pre && node_has_env( n ) && !env_ray_hits( n, rp, rd ) ) return F3_INF;
                 return simple_compound_hit< NOR >( sc, e, rp, rd, nor, hit_obj, limit, cnt );
             }
         }
@@ -1645,14 +1649,14 @@ DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj
          * branch of this function writes too -- are not forced into scratch memory by an escaping pointer */
         V3 cn = mk( 0, 0, 0 );
         int co = *hit_obj;
-        double ac = compound_ray_hit_dev( sref( sc ), e, rp, rd, NOR, &cn, &co, limit, cnt );
+        double ac = compound_ray_hit_dev( sref( sc ), e, rp, rd, NOR, &cn, &co, limit, cnt );   /* (a real call with its own envelope test, whatever pre says) */
         if( ac < F3_INF ) { if constexpr( NOR ) *nor = cn; *hit_obj = co; }
         ACN_LAP( PH_COMPOUND );
         return ac;
     }
     *hit_obj = e;
     bool env = node_has_env( n );
-    if( env && !env_ray_hits( n, rp, rd ) ) { cnt->inc( CNT_OBJ_HIT ); return F3_INF; }
+    if( pre && env && !env_ray_hits( n, rp, rd ) ) { cnt->inc( CNT_OBJ_HIT ); return F3_INF; }
     if( type > ACN_SQUAROID )
     {
 #ifdef ACN_PRUNE_CHECK
@@ -1666,7 +1670,7 @@ DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj
         }
 #endif
         ACN_LAP( PH_ROOT_LEAF );
-        if( type != ACN_DISTANCE && ( surely_outside< ACN_PRUNE_DEPTH >( sc, e, rp, rd ) || prune_run( sc, e, rp, rd, F3_INF ) ) ) { cnt->inc( CNT_OBJ_HIT ); ACN_LAP( PH_PRUNE ); return F3_INF; }
+        if( pre && type != ACN_DISTANCE && ( surely_outside< ACN_PRUNE_DEPTH >( sc, e, rp, rd ) || prune_run( sc, e, rp, rd, F3_INF ) ) ) { cnt->inc( CNT_OBJ_HIT ); ACN_LAP( PH_PRUNE ); return F3_INF; }
         ACN_LAP( PH_PRUNE );
         return obj_ray_hit_uni< NOR, SC::park >( sref( sc ), e, rp, rd, nor, cnt );   /* the machine redoes the envelope test */
     }
@@ -1688,18 +1692,48 @@ DEVN double light_hit_call( SC sc, int e, V3 rp, V3 rd, CT* cnt )
     return element_hit< false >( sc, e, rp, rd, ( V3* )nullptr, &ho, -F3_INF, cnt );
 }
 
-/* compound_s_ray_hit on a root compound, any-hit form for occlusion tests: true iff some element hits at <= limit */
-template< class SC, class CT >
-DEV bool root_occluded( const SC& sc, int cmp, V3 rp, V3 rd, double limit, CT* cnt )
+/* Resume words.  k_shade's in-line passes over the matter root (root_occluded_fast, root_trans_hit_fast below) tell the hard-ray
+ * kernels which root elements are left to do.  A candidate word: bit i, i < ACN_RESUME_POSITIONS: the element at position i of
+ * the root's given order ( elems[ child0 + i ] ) is a candidate; bit ACN_RESUME_POSITIONS: so is some element at a position
+ * beyond.  In a record (HardShadow.pad, HardPath.resume) the word sits two bits up: bit 0 is the record's own ("the light root
+ * counts too"), bit 1 says that the record is resumable at all -- clear: every element is to be done, as for the probes of
+ * k_walk, which nothing has looked at. */
+#define ACN_RESUME_POSITIONS 29
+#define ACN_RESUME_FLAG 2u
+DEV uint32_t resume_bit( int i ) { return 1u << ( i < ACN_RESUME_POSITIONS ? i : ACN_RESUME_POSITIONS ); }
+DEV uint32_t resume_record( uint32_t candidates ) { return ( candidates << 2 ) | ACN_RESUME_FLAG; }
+/* does the record ask for the element at position i ?  (i: wave-uniform) */
+DEV bool resume_wants( uint32_t rec, int i ) { return !( rec & ACN_RESUME_FLAG ) || ( ( rec >> 2 ) & resume_bit( i ) ); }
+/* ... and does that element still need its pre-tests (element_hit) ?  k_shade has run them at the positions it can name */
+DEV bool resume_pre( uint32_t rec, int i ) { return !( rec & ACN_RESUME_FLAG ) || i >= ACN_RESUME_POSITIONS; }
+
+/* compound_s_ray_hit on a root compound, any-hit form for occlusion tests: true iff some element hits at <= limit.
+ * RESUME: rec is a record's resume word (lanes with full and with resumed records share the loop and the one in-line copy
+ * of the machines in it); an element no lane of the wave asks for is skipped.  elems[ pos_base + k ]: the position, in its
+ * compound's given order, of entry k of the cost-ordered copy elems[ n_elems + k ] (written by the upload step). */
+template< bool RESUME, class SC, class CT >
+DEV bool root_occluded_rec( const SC& sc, int cmp, V3 rp, V3 rd, double limit, uint32_t rec, uint32_t pos_base, CT* cnt )
 {
     auto o = &sc.nodes[ cmp ];
-    if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return false;
+    if( ( !RESUME || !( rec & ACN_RESUME_FLAG ) ) && node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return false;   /* (k_shade passed it) */
     int first = o->child0 + ( int )sc.n_elems, count = o->child1;   /* the cost-ordered copy: cheap elements first */
     bool occ = false;
     for( int i = 0; i < count; i++ )
     {
         int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
-        if( !occ )
+        if constexpr( RESUME )
+        {
+            const int at = __builtin_amdgcn_readfirstlane( sc.elems[ pos_base + ( uint32_t )( o->child0 + i ) ] );
+            const bool want = !occ && resume_wants( rec, at );
+            if( __ballot( want ) == 0ull ) continue;   /* (some lane is not occluded yet, or the loop had ended) */
+            if( want )
+            {
+                int hit_obj;
+                double a = element_hit< false >( sc, element, rp, rd, nullptr, &hit_obj, limit, cnt, resume_pre( rec, at ) );
+                if( a <= limit ) occ = true;
+            }
+        }
+        else if( !occ )
         {
             int hit_obj;
             double a = element_hit< false >( sc, element, rp, rd, nullptr, &hit_obj, limit, cnt );
@@ -1709,24 +1743,35 @@ DEV bool root_occluded( const SC& sc, int cmp, V3 rp, V3 rd, double limit, CT* c
     }
     return occ;
 }
+template< class SC, class CT >
+DEV bool root_occluded( const SC& sc, int cmp, V3 rp, V3 rd, double limit, CT* cnt ) { return root_occluded_rec< false >( sc, cmp, rp, rd, limit, 0u, 0u, cnt ); }
 
 struct Trans { V3 exit_nor; int exit_obj; int enter_obj; };
 
-/* compound_s_ray_trans_hit on a root compound (compound.c:246-299) */
-template< class SC, class CT >
-DEV double root_trans_hit( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, CT* cnt )
+/* compound_s_ray_trans_hit on a root compound (compound.c:246-299).
+ * RESUME: rec is a record's resume word.  The loop keeps the given order and only leaves elements out, all of which are
+ * known to miss: the fold below is the full fold without its no-ops. */
+template< bool RESUME, class SC, class CT >
+DEV double root_trans_hit_rec( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, uint32_t rec, CT* cnt )
 {
     auto o = &sc.nodes[ cmp ];
     cnt->inc( CNT_TRANS_RAY );
-    if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return F3_INF;
+    if( ( !RESUME || !( rec & ACN_RESUME_FLAG ) ) && node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return F3_INF;   /* (k_shade passed it) */
     double min_a = F3_INF;
     int first = o->child0, count = o->child1;
     for( int i = 0; i < count; i++ )
     {
+        bool want = true, pre = true;
+        if constexpr( RESUME )
+        {
+            want = resume_wants( rec, i ); pre = resume_pre( rec, i );
+            if( __ballot( want ) == 0ull ) continue;
+        }
         int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
         int hit_obj = -1;
         V3 nor = mk( 0, 0, 0 );
-        double a = element_hit< true >( sc, element, rp, rd, &nor, &hit_obj, -F3_INF, cnt );
+        double a = F3_INF;
+        if( want ) a = element_hit< true >( sc, element, rp, rd, &nor, &hit_obj, -F3_INF, cnt, pre );
         if( a < F3_INF )
         {
             cnt->cost( ACN_F_TRANS_RESOLVE );
@@ -1752,12 +1797,27 @@ DEV double root_trans_hit( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, CT
     }
     return min_a;
 }
+template< class SC, class CT >
+DEV double root_trans_hit( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, CT* cnt ) { return root_trans_hit_rec< false >( sc, cmp, rp, rd, trans, 0u, cnt ); }
 
-/* ---- fast-path forms for k_shade: leaf root elements are tested inline; a ray that gets inside the envelope of a
- * root element that needs the machine (CSG, SDF, nested compound) is reported as `hard` and handed to the hard-ray
- * kernels, which redo the query with the full traversal.  The results are identical: an occlusion test is an OR over
- * the elements, and a transition hit is only computed here when every machine element was missed at its envelope
- * (obj_ray_hit then returns f3_inf for it, objects.c:264). ---- */
+/* ---- fast-path forms for k_shade: leaf root elements are tested inline; a ray that gets past the pre-tests of a root
+ * element that needs the machine (CSG, SDF, nested compound) is reported as hard and handed to the hard-ray kernels,
+ * which RESUME the query where this pass leaves it: the pass returns a candidate word (ACN_RESUME_POSITIONS above) and the
+ * hard-ray kernels visit the named elements only, without the pre-tests this pass has run on them.
+ *   occlusion    an OR over the elements.  The candidates are the machine elements that were not ruled out.  Every other
+ *                element has been evaluated here, or culled for the whole cone, and does not occlude within `limit` -- else
+ *                the pass had answered 1 -- so leaving it out of the OR changes nothing.
+ *   transition   the fold of compound.c:246-299 ignores an element that misses, but depends on the order of those that
+ *                hit within F3_EPS of each other.  The candidates are the machine elements that were not ruled out AND the
+ *                in-line elements that hit here; k_hard_path folds them all again, in the given order: the full fold with
+ *                the misses left out.  (The fold of this pass is only used when there is no candidate machine element.)
+ *   pre-tests    element_hit's envelope test, surely_outside and prune_run( F3_INF ) are what this pass ran on the same
+ *                operands with the answer "not ruled out" (prune_run( limit ) == false implies prune_run( F3_INF ) == false:
+ *                the limit only cuts the hull); an in-line element that hit has passed its envelope.  Skipping them
+ *                skips tests whose outcome is known; what is evaluated is evaluated by the same code as in a full pass.
+ *                Positions the word cannot name (the tail bit) keep their pre-tests.
+ * A transition hit is only final here when every machine element was missed at its pre-tests (obj_ray_hit then returns
+ * f3_inf for it, objects.c:264). ---- */
 DEV bool is_fast_type( int type ) { return type >= ACN_PLANE && type <= ACN_SQUAROID; }
 
 template< bool NOR, class NP, class CT >
@@ -1849,14 +1909,16 @@ DEV uint64_t root_cone_cull( const SC& sc, int cmp, V3 pos, V3 axis, double cos_
     return skip;
 }
 
-/* 0: not occluded, 1: occluded, 2: undecided (hard).  skip: root_cone_cull's bits */
+/* 0: not occluded, 1: occluded, 2: undecided (hard).  skip: root_cone_cull's bits.  *candidates: where the answer is 2, the
+ * machine elements that were not ruled out (a candidate word; it takes the place of a `hard` flag in the loop) */
 template< class SC, class CT >
-DEV int root_occluded_fast( const SC& sc, int cmp, V3 rp, V3 rd, double limit, uint64_t skip, CT* cnt )
+DEV int root_occluded_fast( const SC& sc, int cmp, V3 rp, V3 rd, double limit, uint64_t skip, uint32_t* candidates, CT* cnt )
 {
     auto o = &sc.nodes[ cmp ];
+    *candidates = 0;
     if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return 0;
     int first = o->child0, count = o->child1;
-    bool hard = false;
+    uint32_t hard = 0;
     for( int i = 0; i < count; i++ )
     {
         if( i < 64 && ( ( skip >> i ) & 1ull ) ) continue;
@@ -1883,22 +1945,25 @@ DEV int root_occluded_fast( const SC& sc, int cmp, V3 rp, V3 rd, double limit, u
         else if( type == ACN_COMPOUND || type == ACN_DISTANCE ? ( !node_has_env( n ) || env_ray_hits_( n, rp, rd, ACN_NO_CNT ) )
                                                               : !( surely_outside< ACN_PRUNE_DEPTH >( sc, element, rp, rd ) || ACN_FAST_PRUNE( sc, element, rp, rd, limit ) ) )
         {
-            hard = true;
+            hard |= resume_bit( i );
         }
     }
+    *candidates = hard;
     return hard ? 2 : 0;
 }
 
-/* compound_s_ray_trans_hit on a root compound; *hard is set when the query must be redone by the full traversal */
+/* compound_s_ray_trans_hit on a root compound; *hard is set when the query must be finished by the full traversal.
+ * *machines: the candidate word of the machine elements that were not ruled out ( != 0 iff *hard ); *inline_hits: that of
+ * the in-line elements that hit.  Both together are what k_hard_path folds; an any-hit probe needs the first alone. */
 template< class SC, class CT >
-DEV double root_trans_hit_fast( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, bool* hard, CT* cnt )
+DEV double root_trans_hit_fast( const SC& sc, int cmp, V3 rp, V3 rd, Trans* trans, bool* hard, uint32_t* machines, uint32_t* inline_hits, CT* cnt )
 {
     auto o = &sc.nodes[ cmp ];
-    *hard = false;
+    *hard = false; *machines = 0; *inline_hits = 0;
     if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) { cnt->inc( CNT_TRANS_RAY ); return F3_INF; }
     double min_a = F3_INF;
     int first = o->child0, count = o->child1;
-    bool h = false;
+    uint32_t h = 0, hits = 0;
     for( int i = 0; i < count; i++ )
     {
         int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );
@@ -1907,7 +1972,7 @@ DEV double root_trans_hit_fast( const SC& sc, int cmp, V3 rp, V3 rd, Trans* tran
         if( !is_fast_type( type ) && !( n->flags & ( ACN_GFLAG_LEAF_PAIR | ( SC::prune ? ACN_GFLAG_SIMPLE_COMPOUND : 0u ) ) ) )
         {
             if( type == ACN_COMPOUND || type == ACN_DISTANCE ? ( !node_has_env( n ) || env_ray_hits_( n, rp, rd, ACN_NO_CNT ) )
-                                                             : !( surely_outside< ACN_PRUNE_DEPTH >( sc, element, rp, rd ) || ACN_FAST_PRUNE( sc, element, rp, rd, F3_INF ) ) ) h = true;
+                                                             : !( surely_outside< ACN_PRUNE_DEPTH >( sc, element, rp, rd ) || ACN_FAST_PRUNE( sc, element, rp, rd, F3_INF ) ) ) h |= resume_bit( i );
             continue;
         }
         V3 nor = mk( 0, 0, 0 );
@@ -1925,6 +1990,7 @@ DEV double root_trans_hit_fast( const SC& sc, int cmp, V3 rp, V3 rd, Trans* tran
         }
         if( a < F3_INF )
         {
+            hits |= resume_bit( i );
             cnt->cost( ACN_F_TRANS_RESOLVE );
             if( a < min_a - F3_EPS )
             {
@@ -1946,7 +2012,7 @@ DEV double root_trans_hit_fast( const SC& sc, int cmp, V3 rp, V3 rd, Trans* tran
             }
         }
     }
-    *hard = h;
+    *hard = h != 0; *machines = h; *inline_hits = hits;
     if( !h ) cnt->inc( CNT_TRANS_RAY );
     return min_a;
 }

@@ -16,6 +16,7 @@ struct SceneArgs
     const GMat* mats;
     const int32_t* elems;
     const acn_texture* textures;
+    uint32_t elem_pos_base;   /* elems[ elem_pos_base + k ]: see root_occluded_rec (k_hard_shadow alone reads it: no DevScene field) */
 };
 
 /* variant selection.  The instrumented kernels (count) exist with and without the prune programs / in-line simple

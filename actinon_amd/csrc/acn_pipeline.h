@@ -19,8 +19,9 @@
  *                 draws per sample, scene.c:558,598), casts its cap sample at the light, Oren-Nayar weight, shadow
  *                 ray; then the path samples: hemisphere sample, transition hit against matter; misses take the
  *                 background, hits become HitRecs of the next level; rays that enter the envelope of a CSG / SDF /
- *                 compound root element are deferred to
- *   k_hard_shadow / k_hard_path   persistent waves, one lane per deferred ray, full traversal with the CSG machine.
+ *                 compound root element are deferred, with a word that names those elements, to
+ *   k_hard_shadow / k_hard_path   persistent waves, one lane per deferred ray: the CSG machines of the named elements
+ *                 (records without such a word -- the probes of k_walk -- get the full traversal).
  *   k_shade_hits  first step of levels >= 1: shade_hit on the stored path-sample hits; fills the ray queue of k_walk.
  *
  * Every kernel reads its input count from device memory (the counter block of its level) and fetches work through
@@ -138,7 +139,9 @@ struct HardShadow
     V3 pos, d;
     double limit;        /* distance of the light hit */
     V3 contrib;          /* what the sample adds to the pixel if it is not occluded */
-    uint32_t pixel, pad; /* pixel == ACN_INVALID: dead slot.  pad bit 0: a probe of a specular ray (see probe_push): the light root counts too */
+    uint32_t pixel, pad; /* pixel == ACN_INVALID: dead slot.  pad bit 0: a probe of a specular ray (see probe_push): the light root counts too;
+                            bits 1 .. 31: the resume word of k_shade's in-line pass over the matter root (acn_device.h: ACN_RESUME_FLAG,
+                            resume_record); bit 1 clear: nothing is known, every element is to be tested */
 };
 
 /* a path ray of k_shade that did: k_hard_path finishes the transition hit */
@@ -149,7 +152,10 @@ struct HardPath
     double intensity;
     int depth;
     uint32_t pixel;      /* ACN_INVALID: dead slot */
+    uint32_t resume;     /* bits 1 .. 31: the resume word, as in HardShadow.pad (depth has no bound, so the word has a field of its own) */
+    uint32_t pad;
 };
+static_assert( sizeof( HardShadow ) == 88 && sizeof( HardPath ) == 96, "record sizes: DESIGN.md section 3" );
 
 #define ACN_INVALID 0xFFFFFFFFu
 #define ACN_INVALID_SLOT 0xFFFFFFFFu
@@ -1092,7 +1098,8 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 if( a >= F3_INF ) continue;
                 cnt.inc( CNT_SHADOW_RAY );
                 ACN_LAP( PH_M_FRAME );
-                int occ = root_occluded_fast( scp, sc.matter_root, pos, out_d, a, skip, &cnt );
+                uint32_t cand;   /* occ == 2: the machine elements left for k_hard_shadow */
+                int occ = root_occluded_fast( scp, sc.matter_root, pos, out_d, a, skip, &cand, &cnt );
                 ACN_LAP( PH_M_SIDE );
                 if( occ == 1 ) continue;
                 /* what the sample adds if it is not occluded (scene.c:569-574); the weight of a direct-light sample only scales its
@@ -1108,10 +1115,10 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 double diff_sqr = v_diff_sqr( hit_pos, F.get3( TF_LIGHT_POS ) );
                 double local_intensity = ( diff_sqr > 0 ) ? ( F.get( TF_RADIANCE ) / diff_sqr ) : F3_MAG;
                 double c = local_intensity * weight * F.get( TF_DIFF_I );
-                if( occ == 0 ) { s += c; cnt.cost( ACN_F_DIRECT_TAIL ); }
+                if( cand == 0 ) { s += c; cnt.cost( ACN_F_DIRECT_TAIL ); }
                 /* hard shadow rays: appended to the queue of k_hard_shadow, which adds the contribution itself if unoccluded */
-                uint32_t hs = chunk_alloc( cs + 0, &p_counts[ QC_HARD_SHADOW ], occ == 2 );
-                if( occ == 2 )
+                uint32_t hs = chunk_alloc( cs + 0, &p_counts[ QC_HARD_SHADOW ], cand != 0 );
+                if( cand != 0 )
                 {
                     if( hs < hs_cap )
                     {
@@ -1119,7 +1126,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                         const V3 scale = F.get3( TF_SCALE );
                         h.pos = pos; h.d = out_d; h.limit = a;
                         h.contrib = mk( scale.x * c, scale.y * c, scale.z * c );
-                        h.pixel = t.pixel; h.pad = 0;
+                        h.pixel = t.pixel; h.pad = resume_record( cand );
                         n_hs++;
                     }
                     else
@@ -1174,6 +1181,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 Trans trans;
                 trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
                 bool hard = false;
+                uint32_t machines = 0, inline_hits = 0;   /* candidate words of the in-line pass: what is left for the hard-ray kernels */
                 if( live )
                 {
                     if( oren_nayar )
@@ -1184,7 +1192,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                     }
                     cnt.cost( ACN_F_PATH_TAIL );
                     ACN_LAP( PH_COMPOUND );
-                    a = root_trans_hit_fast( scp, sc.matter_root, pos, out_d, &trans, &hard, &cnt );
+                    a = root_trans_hit_fast( scp, sc.matter_root, pos, out_d, &trans, &hard, &machines, &inline_hits, &cnt );
                     ACN_LAP( PH_TAIL );
                 }
                 const double child_intensity = weight * diffuse_intensity;
@@ -1195,17 +1203,18 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 const bool dark = t.depth - 10 == 0 || child_intensity < sc.prm.trace_min_intensity;
                 if( dark ) hit = false;
                 const bool probe = hard && dark;
-                if( probe ) hard = false;
-                uint32_t ps = chunk_alloc( cs + 0, &p_counts[ QC_HARD_SHADOW ], probe );
-                if( probe )
+                if( probe ) { hard = false; cnt.inc( CNT_TRANS_RAY ); }   /* the compound_s_ray_trans_hit this probe stands for */
+                /* a probe whose in-line elements already hit within the limit is occluded whatever the machines say: not written */
+                const bool probe_open = probe && !( a <= path_limit );
+                uint32_t ps = chunk_alloc( cs + 0, &p_counts[ QC_HARD_SHADOW ], probe_open );
+                if( probe_open )
                 {
-                    cnt.inc( CNT_TRANS_RAY );   /* the compound_s_ray_trans_hit this probe stands for */
                     if( ps < hs_cap )
                     {
                         HardShadow& h = p_hard_shadow[ ps ];
                         h.pos = pos; h.d = out_d; h.limit = path_limit;
                         h.contrib = v_mld( F.get3( TF_SCALE ), v_mlf( bg, child_intensity ) );   /* k_hard_path's term for a miss */
-                        h.pixel = t.pixel; h.pad = 0;
+                        h.pixel = t.pixel; h.pad = resume_record( machines );
                         n_hs++;
                     }
                     else
@@ -1222,6 +1231,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                         HardPath& h = p_hard_path[ hp ];
                         h.pos = pos; h.d = out_d; h.T = F.get3( TF_SCALE ); h.intensity = child_intensity;
                         h.depth = t.depth - 10; h.pixel = t.pixel;
+                        h.resume = resume_record( machines | inline_hits ); h.pad = 0;
                         n_hp++;
                     }
                     else
@@ -1265,10 +1275,11 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
     wave_add_counters( counters, cnt );
 }
 
-/* the shadow rays k_shade could not decide inline: full occlusion test, one lane per ray, persistent waves */
+/* the shadow rays k_shade could not decide inline, one lane per ray, persistent waves: the occlusion test over the elements
+ * the record's resume word names, or over all of them */
 template< bool COUNT, bool LDS, bool PRUNE >
 __global__ __launch_bounds__( 256, ACN_WALK_WAVES )
-void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint32_t cap, uint32_t fetch_batch, uint32_t* __restrict__ p_counts,
+void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint32_t cap, uint32_t fetch_batch, uint32_t pos_base, uint32_t* __restrict__ p_counts,
                     unsigned long long* __restrict__ accum, unsigned long long* __restrict__ counters )
 {
     ACN_CHUNK_FLAGS_LOAD
@@ -1306,8 +1317,9 @@ void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint3
                     if( __ballot( want ) == 0ull ) continue;
                     if( want )
                     {
-                        if constexpr( LDS ) occ = root_occluded( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), root, r.pos, r.d, r.limit, &cnt );
-                        else                occ = root_occluded( scene_view< PRUNE, true >( sc, sc.nodes ), root, r.pos, r.d, r.limit, &cnt );
+                        const uint32_t rec = k ? r.pad : 0u;   /* the word speaks of the matter root */
+                        if constexpr( LDS ) occ = root_occluded_rec< true >( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), root, r.pos, r.d, r.limit, rec, pos_base, &cnt );
+                        else                occ = root_occluded_rec< true >( scene_view< PRUNE, true >( sc, sc.nodes ), root, r.pos, r.d, r.limit, rec, pos_base, &cnt );
                     }
                 }
                 ACN_LAP( PH_ROOT_LEAF );
@@ -1321,7 +1333,8 @@ void k_hard_shadow( ACN_SCENE_PARAMS, const HardShadow* __restrict__ recs, uint3
     wave_add_counters( counters, cnt );
 }
 
-/* the path rays k_shade could not finish inline: full transition hit; hits join the next level's HitRec queue */
+/* the path rays k_shade could not finish inline: the transition hit over the elements the record's resume word names; hits
+ * join the next level's HitRec queue */
 template< bool COUNT, bool LDS, bool PRUNE >
 __global__ __launch_bounds__( 256, ACN_HPATH_WAVES )
 void k_hard_path( ACN_SCENE_PARAMS, const HardPath* __restrict__ recs, uint32_t cap, uint32_t fetch_batch, HitRec* __restrict__ p_children, uint32_t child_cap,
@@ -1354,7 +1367,7 @@ void k_hard_path( ACN_SCENE_PARAMS, const HardPath* __restrict__ recs, uint32_t 
         if( got == 0 ) break;
         bool hit = false;
         HardPath r;
-        r.pos = mk( 0, 0, 0 ); r.d = mk( 0, 0, 1 ); r.T = mk( 0, 0, 0 ); r.intensity = 0; r.depth = 0; r.pixel = ACN_INVALID;
+        r.pos = mk( 0, 0, 0 ); r.d = mk( 0, 0, 1 ); r.T = mk( 0, 0, 0 ); r.intensity = 0; r.depth = 0; r.pixel = ACN_INVALID; r.resume = 0; r.pad = 0;
         Trans trans;
         trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
         double a = F3_INF;
@@ -1362,8 +1375,8 @@ void k_hard_path( ACN_SCENE_PARAMS, const HardPath* __restrict__ recs, uint32_t 
         if( r.pixel != ACN_INVALID )
         {
             ACN_LAP( PH_FETCH );
-            if constexpr( LDS ) a = root_trans_hit( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), sc.matter_root, r.pos, r.d, &trans, &cnt );
-            else                a = root_trans_hit( scene_view< PRUNE, true >( sc, sc.nodes ), sc.matter_root, r.pos, r.d, &trans, &cnt );
+            if constexpr( LDS ) a = root_trans_hit_rec< true >( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), sc.matter_root, r.pos, r.d, &trans, r.resume, &cnt );
+            else                a = root_trans_hit_rec< true >( scene_view< PRUNE, true >( sc, sc.nodes ), sc.matter_root, r.pos, r.d, &trans, r.resume, &cnt );
             ACN_LAP( PH_ROOT_LEAF );
             hit = a < sc.prm.max_path_length;
             if( !hit )

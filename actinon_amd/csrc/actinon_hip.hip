@@ -194,6 +194,7 @@ struct acn_scene_handle
     size_t lds_bytes = 0;                      /* > 0: the node array fits the LDS staging budget */
     size_t lds_stack_bytes = 0;                /* > 0: the machine kernels keep their CSG stacks in LDS */
     bool prune = false;                        /* some root element has an interval-prune program: launch the PRUNE kernel variants */
+    uint32_t elem_pos_base = 0;                /* elems[ elem_pos_base + k ]: given-order position of entry k of the cost-ordered copy (k_hard_shadow: resume words) */
     bool leaf_lights = true;                   /* every light element is a plane / sphere */
     bool count_work = false;                   /* ACN_OPT_COUNT_WORK of the current call */
     uint32_t shard_rank = 0, shard_world = 1;  /* ACN_SHARD_SAMPLES of the current call */
@@ -644,6 +645,9 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
      * test cost (any-hit occlusion queries are an OR over the elements, so their order is free; closest-hit queries
      * keep the given order because ties go to the first element, compound.c:225-243) */
     std::vector< int32_t > elems2( 2 * ( size_t )scene->n_elems + 1, 0 );
+    /* per entry of the cost-ordered copy: its element's position in the compound's given order (the resume words of the hard-ray
+     * kernels speak of those positions, acn_device.h: root_occluded_rec); appended to elems2 behind everything else */
+    std::vector< int32_t > elem_pos( scene->n_elems, 0 );
     std::vector< SCEntry > sc_table;   /* pre-order tables of the simple compounds (acn_device.h: simple_compound_hit) */
     std::vector< double > sc_spheres;
     {
@@ -672,7 +676,10 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
             const acn_node& a = scene->nodes[ i ];
             if( a.type != ACN_COMPOUND || a.child1 < 2 ) continue;
             int32_t* first = elems2.data() + scene->n_elems + a.child0;
-            std::stable_sort( first, first + a.child1, [ & ]( int32_t x, int32_t y ) { return node_cost( x ) < node_cost( y ); } );
+            int32_t* at = elem_pos.data() + a.child0;
+            for( int32_t k = 0; k < a.child1; k++ ) at[ k ] = k;
+            std::stable_sort( at, at + a.child1, [ & ]( int32_t x, int32_t y ) { return node_cost( scene->elems[ a.child0 + x ] ) < node_cost( scene->elems[ a.child0 + y ] ); } );
+            for( int32_t k = 0; k < a.child1; k++ ) first[ k ] = scene->elems[ a.child0 + at[ k ] ];
         }
     }
     /* elems[ 2n .. 2n + n_nodes ): per node the offset of its interval-prune program (acn_device.h: prune_run) or -1,
@@ -894,6 +901,9 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
         }
         elems2.push_back( 0 );
     }
+    h->elem_pos_base = ( uint32_t )elems2.size();
+    elems2.insert( elems2.end(), elem_pos.begin(), elem_pos.end() );
+    elems2.push_back( 0 );
     h->scene_bytes[ 2 ] = sizeof( int32_t ) * elems2.size();
     HIP_TRY_H( hipMalloc( &h->d_elems, sizeof( int32_t ) * elems2.size() ) );
     HIP_TRY_H( hipMalloc( &h->d_sc_table, sizeof( SCEntry ) * ( sc_table.size() ? sc_table.size() : 1 ) ) );
@@ -1188,7 +1198,7 @@ static int stage_end( acn_scene_handle* h, hipStream_t stream )
 static SceneArgs scene_args( const acn_scene_handle* h )
 {
     SceneArgs s;
-    s.dev = h->dev; s.nodes = h->d_nodes; s.mats = h->d_mats; s.elems = h->d_elems; s.textures = h->d_textures;
+    s.dev = h->dev; s.nodes = h->d_nodes; s.mats = h->d_mats; s.elems = h->d_elems; s.textures = h->d_textures; s.elem_pos_base = h->elem_pos_base;
     return s;
 }
 static KernelFlags kernel_flags( const acn_scene_handle* h )
@@ -1756,7 +1766,7 @@ static void bind_lane( const acn_scene_handle* parent, int lanes, acn_scene_hand
     l->scene_bytes[ 0 ] = parent->scene_bytes[ 0 ]; l->scene_bytes[ 1 ] = parent->scene_bytes[ 1 ]; l->scene_bytes[ 2 ] = parent->scene_bytes[ 2 ]; l->scene_bytes[ 3 ] = parent->scene_bytes[ 3 ];
     l->max_csg_depth = parent->max_csg_depth;
     l->lds_bytes = parent->lds_bytes; l->lds_stack_bytes = parent->lds_stack_bytes;
-    l->prune = parent->prune; l->leaf_lights = parent->leaf_lights;
+    l->prune = parent->prune; l->leaf_lights = parent->leaf_lights; l->elem_pos_base = parent->elem_pos_base;
     l->tun = parent->tun; l->cus = parent->cus; l->n_levels = parent->n_levels;
     l->workspace_budget = parent->workspace_budget; l->n_lights = parent->n_lights;
     /* Round 4: six lanes on grids of ONE workgroup per CU (k_shade: one and a half) instead of four lanes on two.  With k_walk at

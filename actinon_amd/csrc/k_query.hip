@@ -12,7 +12,7 @@
 #define ACN_Q_STRIDE ACN_QUERY_STRIDE
 
 template< class SC >
-__device__ void query_one( const SC& scv, int op, int32_t node, V3 rp, V3 rd, double limit, uint64_t skip, double* o )
+__device__ void query_one( const SC& scv, int op, int32_t node, V3 rp, V3 rd, double limit, uint64_t skip, uint32_t pos_base, double* o )
 {
     Cnt< false > cnt_;
     Cnt< false >* cnt = &cnt_;   /* what the leaf routines' macros append */
@@ -60,18 +60,26 @@ __device__ void query_one( const SC& scv, int op, int32_t node, V3 rp, V3 rd, do
         Trans t; t.exit_nor = mk( 0, 0, 0 ); t.exit_obj = -1; t.enter_obj = -1;
         double a = root_trans_hit( scv, node, rp, rd, &t, cnt );
         o[ 0 ] = a; o[ 1 ] = t.exit_nor.x; o[ 2 ] = t.exit_nor.y; o[ 3 ] = t.exit_nor.z; o[ 4 ] = t.exit_obj; o[ 5 ] = t.enter_obj;
-        /* k_shade's form, and k_hard_path's redo where it says hard */
+        /* k_shade's form, and where it says hard k_hard_path's: the fold resumed over the candidates of the in-line pass */
         Trans f; f.exit_nor = mk( 0, 0, 0 ); f.exit_obj = -1; f.enter_obj = -1;
         bool hard = false;
-        double b = root_trans_hit_fast( scv, node, rp, rd, &f, &hard, cnt );
-        if( hard ) { f.exit_nor = mk( 0, 0, 0 ); f.exit_obj = -1; f.enter_obj = -1; b = root_trans_hit( scv, node, rp, rd, &f, cnt ); }
+        uint32_t machines = 0, inline_hits = 0;
+        double b = root_trans_hit_fast( scv, node, rp, rd, &f, &hard, &machines, &inline_hits, cnt );
+        if( hard ) { f.exit_nor = mk( 0, 0, 0 ); f.exit_obj = -1; f.enter_obj = -1; b = root_trans_hit_rec< true >( scv, node, rp, rd, &f, resume_record( machines | inline_hits ), cnt ); }
         o[ 6 ] = b; o[ 7 ] = f.exit_nor.x; o[ 8 ] = f.exit_nor.y; o[ 9 ] = f.exit_nor.z; o[ 10 ] = f.exit_obj; o[ 11 ] = f.enter_obj; o[ 12 ] = hard;
+        o[ 13 ] = ( double )( machines | inline_hits );
     }
     else if( op == ACN_Q_OCCLUDED )
     {
         if( type != ACN_COMPOUND ) { o[ 0 ] = nan; return; }
         o[ 0 ] = root_occluded( scv, node, rp, rd, limit, cnt );
-        o[ 1 ] = root_occluded_fast( scv, node, rp, rd, limit, skip, cnt );
+        uint32_t cand = 0;
+        const int fast = root_occluded_fast( scv, node, rp, rd, limit, skip, &cand, cnt );
+        o[ 1 ] = fast;
+        /* k_hard_shadow's form for what the in-line pass leaves undecided: resumed over its candidates */
+        o[ 2 ] = nan;
+        if( fast == 2 ) o[ 2 ] = root_occluded_rec< true >( scv, node, rp, rd, limit, resume_record( cand ), pos_base, cnt );
+        o[ 3 ] = ( double )cand;
     }
     else if( op == ACN_Q_CONE_CULL )
     {
@@ -103,7 +111,7 @@ __device__ void query_one( const SC& scv, int op, int32_t node, V3 rp, V3 rd, do
 template< bool LDS, bool PRUNE >
 __global__ __launch_bounds__( 256 )
 void k_query( ACN_SCENE_PARAMS, int op, int32_t node, const double* __restrict__ rays, const double* __restrict__ limits, size_t n,
-              double* __restrict__ out )
+              uint32_t pos_base, double* __restrict__ out )
 {
     ACN_SCENE_VIEW
     if( sc_in.lds_stack != ACN_NO_LDS_STACK ) sc.lds_stack = LDS ? sc.n_nodes * ( uint32_t )sizeof( GNode ) : 0u;
@@ -115,8 +123,8 @@ void k_query( ACN_SCENE_PARAMS, int op, int32_t node, const double* __restrict__
     const uint64_t skip = limits ? ( ( const uint64_t* )limits )[ 2 * i + 1 ] : 0ull;
     double* o = out + ACN_Q_STRIDE * i;
     for( int k = 0; k < ACN_Q_STRIDE; k++ ) o[ k ] = 0;
-    if constexpr( LDS ) query_one( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), op, node, rp, rd, limit, skip, o );
-    else                query_one( scene_view< PRUNE, true >( sc, sc.nodes ), op, node, rp, rd, limit, skip, o );
+    if constexpr( LDS ) query_one( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), op, node, rp, rd, limit, skip, pos_base, o );
+    else                query_one( scene_view< PRUNE, true >( sc, sc.nodes ), op, node, rp, rd, limit, skip, pos_base, o );
 }
 
 /* the elements of compound `node` with the device-only bits of their headers; one lane */
@@ -171,10 +179,10 @@ extern "C" int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const 
         {
             const dim3 grid( ( unsigned )( ( nr + 255 ) / 256 ) );
             const size_t lds_total = ( lds ? q.lds_node_bytes : 0 ) + q.lds_stack_bytes;
-            if( lds && prune )  hipLaunchKernelGGL( ( k_query< true, true > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, d_out );
-            else if( lds )      hipLaunchKernelGGL( ( k_query< true, false > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, d_out );
-            else if( prune )    hipLaunchKernelGGL( ( k_query< false, true > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, d_out );
-            else                hipLaunchKernelGGL( ( k_query< false, false > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, d_out );
+            if( lds && prune )  hipLaunchKernelGGL( ( k_query< true, true > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+            else if( lds )      hipLaunchKernelGGL( ( k_query< true, false > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+            else if( prune )    hipLaunchKernelGGL( ( k_query< false, true > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+            else                hipLaunchKernelGGL( ( k_query< false, false > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
         }
         e = hipGetLastError();
     }

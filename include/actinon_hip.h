@@ -361,8 +361,12 @@ int acn_detmath_eval( int device, int op, const double* x, const double* y, doub
  *   PRUNE              surely_outside, prune_run( limit ), prune_run( inf ), has a program
  *   LEAF_IV            iv_ball / iv_squaroid / iv_halfspace of a leaf   lo, hi, envelope chord lo, hi
  *   TRANS              root_trans_hit on compound `node`                a, exit normal[3], exit, enter object;
- *                      root_trans_hit_fast (+ the full redo if hard)    [ 6 .. 11 ] the same, [ 12 ] hard
- *   OCCLUDED           root_occluded, root_occluded_fast( skip ) on compound `node`
+ *                      root_trans_hit_fast, and where that says hard the   [ 6 .. 11 ] the same, [ 12 ] hard,
+ *                      fold resumed over its candidates (k_hard_path)   [ 13 ] the candidate word
+ *   OCCLUDED           root_occluded, root_occluded_fast( skip ) on compound `node`; [ 2 ] where [ 1 ] == 2: the answer of
+ *                      the test resumed over the candidates (k_hard_shadow), else NaN; [ 3 ] the candidate word
+ *                      (candidate word: bit i < 29: the element at position i of the compound is left to do; bit 29: one
+ *                      at a position >= 29 is.  OCCLUDED: machine elements not ruled out; TRANS: also in-line elements that hit)
  *   CONE_CULL          root_cone_cull of the matter root for light `node` seen from the origin: mask, axis[3], cos theta
  *   SC_HIT             simple_compound_hit on `node`: a, normal[3], hit object, any-hit( limit )
  *   ELEMENTS           no rays: per element of compound `node` (n at most): index, ACN_Q_EL_* bits, type; out[ 3 ]:
