@@ -13,6 +13,12 @@ ACN_SURF_FIRST_HIT, ACN_SURF_FOLLOW = 0, 1
 (ACN_SURF_EMITTER, ACN_SURF_DIFFUSE, ACN_SURF_CHROMATIC, ACN_SURF_FRESNEL, ACN_SURF_TRANSPARENT, ACN_SURF_LIGHT_ROOT,
  ACN_SURF_CUT) = 1, 2, 4, 8, 16, 32, 64
 
+# the edge-avoiding filter (acn_denoise): flags, defaults and limits of acn_denoise_params
+ACN_DENOISE_NO_DEMODULATE, ACN_DENOISE_NORMAL_POWER_SET = 1, 2
+ACN_DENOISE_DEFAULT_ITERATIONS, ACN_DENOISE_DEFAULT_NORMAL_POWER_LOG2 = 5, 7
+ACN_DENOISE_DEFAULT_SIGMA_PLANE, ACN_DENOISE_DEFAULT_SIGMA_LUM = 0.1, 4.0
+ACN_DENOISE_MAX_ITERATIONS, ACN_DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 10
+
 ACN_OK, ACN_ERR_ARG, ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV, ACN_ERR_DEVICE, ACN_ERR_CANCELLED = 0, -1, -2, -3, -4, -5
 
 NODE_TYPES = {1: "plane", 2: "sphere", 3: "squaroid", 4: "distance", 5: "pair_inside", 6: "pair_outside",
@@ -58,6 +64,11 @@ class RenderOpts(C.Structure):
                 ("shard_mode", C.c_uint32), ("shard_rank", C.c_uint32), ("shard_world", C.c_uint32), ("reserved2", C.c_uint32)]
 
 
+class DenoiseParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_plane", C.c_double), ("sigma_lum", C.c_double)]
+
+
 class V3(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
 
@@ -74,3 +85,4 @@ class SceneStruct(C.Structure):
 
 
 assert C.sizeof(Node) == 304, C.sizeof(Node)
+assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)

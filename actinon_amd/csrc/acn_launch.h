@@ -80,6 +80,12 @@ void acn_launch_camera_rays( const DevScene& sc, const double* pos_xy, size_t n,
 void acn_launch_surface( uint32_t mode, bool lds_nodes, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
                          const double* rays, const double* pos_xy, size_t n, double* out );
 
+/* the filter of acn_denoise (k_denoise.hip): prepare, variance and one launch per level, the last of which writes out_rgb (which may
+ * be lin).  scratch: ACN_DENOISE_SCRATCH_PER_PIXEL bytes per pixel, 128-byte aligned.  The parameters are final values, no defaults. */
+#define ACN_DENOISE_SCRATCH_PER_PIXEL 128
+void acn_launch_denoise( const double* lin, const double* surf, size_t width, size_t height, uint32_t iterations, uint32_t normal_power_log2,
+                         uint32_t no_demodulate, double sigma_plane, double sigma_lum, void* scratch, double* out_rgb, hipStream_t stream );
+
 /* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
 struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
 int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */

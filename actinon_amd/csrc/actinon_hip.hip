@@ -227,6 +227,7 @@ struct acn_scene_handle
     double* d_shard_pos = nullptr; size_t shard_pos_cap = 0;                                /* acn_render_main_pass_shard_dev: the rank's positions */
     unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
     uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
+    void* d_denoise = nullptr; size_t denoise_bytes = 0;                                    /* acn_denoise: guides and colour buffers, apart from the render workspace */
     bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
     std::string lane_error;
     bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
@@ -1034,6 +1035,7 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( h->d_shard_pos ) hipFree( h->d_shard_pos );
     if( h->d_ray_check ) hipFree( h->d_ray_check );
     if( h->d_surface_flags ) hipFree( h->d_surface_flags );
+    if( h->d_denoise ) hipFree( h->d_denoise );
     if( !h->is_lane )   /* a lane borrows the resident scene of its parent */
     {
         if( h->d_nodes ) hipFree( h->d_nodes );
@@ -2274,6 +2276,85 @@ extern "C" int acn_resolve_dev( acn_scene_handle* h, const void* d_linear_rgb, s
     HIP_TRY( hipGetLastError() );
     if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
     return ACN_OK;
+}
+
+/* ---- the edge-avoiding filter (k_denoise.hip) ---- */
+struct DenoiseSetup { uint32_t iterations, normal_power_log2, no_demodulate; double sigma_plane, sigma_lum; };
+
+/* every check of a denoise call: on the host, before the handle is touched */
+static int denoise_check( const acn_scene_handle* h, const void* lin, const void* surf, size_t width, size_t height,
+                          const acn_denoise_params* prm, const void* out, const acn_render_opts* opts, DenoiseSetup* su )
+{
+    if( !h || !lin || !surf || !out ) return fail( ACN_ERR_ARG, "null argument" );
+    const size_t max_n = ( size_t )1 << 31;
+    if( width == 0 || height == 0 ) return fail( ACN_ERR_ARG, "a frame to denoise needs a width and a height" );
+    if( width > max_n || height > max_n || width * height > max_n ) return fail( ACN_ERR_ARG, "a frame to denoise has at most 2^31 pixels" );
+    acn_denoise_params p{};
+    if( prm )
+    {
+        if( prm->struct_size < sizeof( uint32_t ) ) return fail( ACN_ERR_ARG, "acn_denoise_params.struct_size " + std::to_string( prm->struct_size ) + " is smaller than its first member" );
+        memcpy( &p, prm, prm->struct_size < sizeof( p ) ? prm->struct_size : sizeof( p ) );
+    }
+    if( p.flags & ~( ACN_DENOISE_NO_DEMODULATE | ACN_DENOISE_NORMAL_POWER_SET ) ) return fail( ACN_ERR_ARG, "unknown acn_denoise_params.flags bits" );
+    if( p.iterations > ACN_DENOISE_MAX_ITERATIONS ) return fail( ACN_ERR_ARG, "acn_denoise_params.iterations " + std::to_string( p.iterations ) + " is above 8" );
+    if( p.normal_power_log2 > ACN_DENOISE_MAX_NORMAL_POWER_LOG2 ) return fail( ACN_ERR_ARG, "acn_denoise_params.normal_power_log2 " + std::to_string( p.normal_power_log2 ) + " is above 10" );
+    const double sig[ 2 ] = { p.sigma_plane, p.sigma_lum };
+    for( double s : sig ) if( !( s >= 0 ) || s > 1.7976931348623157e308 ) return fail( ACN_ERR_ARG, "a sigma of acn_denoise_params is negative or not finite" );
+    if( opts && opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a denoise call is not sharded: the filter needs the whole frame" );
+    su->iterations = p.iterations ? p.iterations : ACN_DENOISE_DEFAULT_ITERATIONS;
+    su->normal_power_log2 = ( p.normal_power_log2 || ( p.flags & ACN_DENOISE_NORMAL_POWER_SET ) ) ? p.normal_power_log2 : ACN_DENOISE_DEFAULT_NORMAL_POWER_LOG2;
+    su->no_demodulate = ( p.flags & ACN_DENOISE_NO_DEMODULATE ) ? 1u : 0u;
+    su->sigma_plane = p.sigma_plane != 0 ? p.sigma_plane : ACN_DENOISE_DEFAULT_SIGMA_PLANE;
+    su->sigma_lum = p.sigma_lum != 0 ? p.sigma_lum : ACN_DENOISE_DEFAULT_SIGMA_LUM;
+    return ACN_OK;
+}
+
+extern "C" int acn_denoise_dev( acn_scene_handle* h, const void* d_linear_rgb, const void* d_surface, size_t width, size_t height,
+                                const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    DenoiseSetup su;
+    int st = denoise_check( h, d_linear_rgb, d_surface, width, height, prm, d_out_rgb, opts, &su );
+    if( st != ACN_OK ) return st;
+    if( ( uintptr_t )d_surface % 16 ) return fail( ACN_ERR_ARG, "the surface records of a denoise call are read 16 bytes at a time: align the buffer" );
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    const size_t need = width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL;
+    if( h->denoise_bytes < need )
+    {
+        if( h->d_denoise ) hipFree( h->d_denoise );   /* (waits for whatever still reads it) */
+        h->d_denoise = nullptr; h->denoise_bytes = 0;
+        HIP_TRY( hipMalloc( &h->d_denoise, need ) );
+        h->denoise_bytes = need;
+    }
+    acn_launch_denoise( ( const double* )d_linear_rgb, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2,
+                        su.no_demodulate, su.sigma_plane, su.sigma_lum, h->d_denoise, ( double* )d_out_rgb, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_denoise( acn_scene_handle* h, const double* linear_rgb, const double* surface, size_t width, size_t height,
+                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    DenoiseSetup su;
+    int st = denoise_check( h, linear_rgb, surface, width, height, prm, out_rgb, opts, &su );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t n = width * height;
+    double* d_rgb = nullptr; double* d_surf = nullptr;
+    HIP_TRY( hipMalloc( &d_rgb, sizeof( double ) * 3 * n ) );
+    hipError_t e = hipMalloc( &d_surf, sizeof( double ) * ACN_SURF_STRIDE * n );
+    if( e != hipSuccess ) { hipFree( d_rgb ); return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) ); }
+    if( hipMemcpy( d_rgb, linear_rgb, sizeof( double ) * 3 * n, hipMemcpyHostToDevice ) != hipSuccess ||
+        hipMemcpy( d_surf, surface, sizeof( double ) * ACN_SURF_STRIDE * n, hipMemcpyHostToDevice ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "H2D copy failed" );
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    if( st == ACN_OK ) st = acn_denoise_dev( h, d_rgb, d_surf, width, height, prm, d_rgb, &o );   /* in place */
+    if( st == ACN_OK && hipMemcpy( out_rgb, d_rgb, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "D2H copy failed" );
+    hipFree( d_rgb ); hipFree( d_surf );
+    return st;
 }
 
 extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )

@@ -382,6 +382,48 @@ class Handle:
         check(hip.acn_surface_positions_dev(self.h, d_pos_ptr, n, self._surface_mode(follow), d_out_ptr, C.byref(o)),
               "acn_surface_positions_dev")
 
+    # the edge-avoiding filter (acn_denoise): a low-sample linear frame and its surface records -> a filtered linear frame
+    @staticmethod
+    def denoise_params(iterations=None, normal_power_log2=None, demodulate=True, sigma_plane=None, sigma_lum=None):
+        """acn_denoise_params of keyword arguments; None is the library's default"""
+        p = abi.DenoiseParams()
+        p.struct_size = C.sizeof(abi.DenoiseParams)
+        p.iterations = 0 if iterations is None else int(iterations)
+        if normal_power_log2 is not None:
+            p.normal_power_log2 = int(normal_power_log2)
+            p.flags |= abi.ACN_DENOISE_NORMAL_POWER_SET
+        if not demodulate:
+            p.flags |= abi.ACN_DENOISE_NO_DEMODULATE
+        p.sigma_plane = 0.0 if sigma_plane is None else float(sigma_plane)
+        p.sigma_lum = 0.0 if sigma_lum is None else float(sigma_lum)
+        return p
+
+    def denoise(self, linear, surface, **params):
+        """Filters a linear frame (acn_denoise): linear [h,w,3] float64 as render_*(linear=True) gives it, surface the Surface
+        (or its [h*w,16] records) of the same positions, FOLLOW recommended -> [h,w,3] float64, linear.  params: iterations,
+        normal_power_log2, demodulate, sigma_plane, sigma_lum (Handle.denoise_params)."""
+        lin = np.ascontiguousarray(linear, dtype=np.float64)
+        if lin.ndim != 3 or lin.shape[2] != 3:
+            raise ValueError(f"a frame to denoise is [h,w,3], got {lin.shape}")
+        hh, w = lin.shape[:2]
+        raw = np.ascontiguousarray(surface.raw if isinstance(surface, Surface) else surface, dtype=np.float64)
+        if raw.size != hh * w * abi.ACN_SURF_STRIDE:
+            raise ValueError(f"{hh}x{w} pixels need {hh * w} surface records of {abi.ACN_SURF_STRIDE}, got {raw.shape}")
+        out = np.empty_like(lin)
+        p = self.denoise_params(**params)
+        o = self._opts(False, None)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        check(hip.acn_denoise(self.h, lin.ctypes.data, raw.ctypes.data, w, hh, C.byref(p), out.ctypes.data, C.byref(o)), "acn_denoise")
+        return out
+
+    def denoise_dev(self, d_linear_ptr, d_surface_ptr, width, height, d_out_ptr, stream=None, **params):
+        """Device buffers: d_linear, d_out [h*w,3] float64 (they may be the same), d_surface [h*w,16] float64; enqueued on
+        `stream` without a synchronisation (None: the handle's stream, synchronous)."""
+        p = self.denoise_params(**params)
+        o = self._opts(False, stream)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        check(hip.acn_denoise_dev(self.h, d_linear_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)), "acn_denoise_dev")
+
     def pick(self, x, y):
         """The object under sample position (x, y): None on a miss, else node (enter object if any, else exit object), its
         type name, distance and position."""

@@ -315,6 +315,73 @@ int acn_shard_unpack_dev( acn_scene_handle* h, const void* d_gathered, size_t co
 int acn_resolve_dev( acn_scene_handle* h, const void* d_linear_rgb, size_t n, void* d_out_rgb, void* d_out_rgb8,
                      const acn_render_opts* opts );
 
+/* Edge-avoiding filter for a low-sample LINEAR frame, guided by the frame's surface records (k_denoise.hip).  This filter is a
+ * definition of this library, not a function of the reference, which has no denoiser: an a-trous wavelet filter on the
+ * albedo-demodulated radiance whose stops are the records' object ids, normals and positions and a luminance stop scaled by
+ * a variance estimated from the frame itself.
+ *   linear_rgb [ height * width ][ 3 ]  f64 radiance as ACN_OPT_LINEAR_OUT gives it, one sample position per pixel, row-major
+ *   surface    [ height * width ][ ACN_SURF_STRIDE ]  the records of the same positions or rays, either mode (ACN_SURF_FOLLOW
+ *              is the recommended one: behind glass it guides with the surface that is seen through it)
+ *   out_rgb    [ height * width ][ 3 ]  linear; the caller applies acn_resolve_dev afterwards.  out_rgb == linear_rgb is allowed.
+ * The scene is not consulted: the handle supplies the device, the stream and the scratch memory (two colour buffers of 32 bytes
+ * and one guide of 64 bytes per pixel: 128 bytes per pixel, owned by the handle, grown on demand, freed by acn_scene_free, apart
+ * from the render workspace: render calls before and after compute the same bits and acn_last_stage_ms [ 23 ], [ 24 ] stay).
+ * Work goes to opts->stream; NULL is the handle's own stream, and then the call waits.  On a caller's stream the call never
+ * synchronises: every check is made on the host.  Of opts only `stream` is used; shard_world > 1 is ACN_ERR_ARG.
+ * ACN_ERR_ARG, with acn_last_error set and nothing written: a null handle or buffer; a zero width or height or width * height
+ * above 2^31; iterations > 8; normal_power_log2 > 10; a negative or non-finite sigma; struct_size < 4; unknown flag bits; a
+ * d_surface that is not 16-byte aligned (the records are read 16 bytes at a time; 128-byte alignment, as the surface calls ask, is best).
+ *
+ * Everything is IEEE binary64 without contraction, a / b is IEEE division, exp and sqrt are acn_exp and acn_sqrt of
+ * csrc/acn_detmath.h, a sum a + b + c is ( a + b ) + c, dot( u, v ) is ( u.x * v.x + u.y * v.y ) + u.z * v.z, max( 0, x ) is
+ * x > 0 ? x : 0, and a tap that is skipped adds nothing.  r = record of the pixel, L = its radiance:
+ * 1 demodulate   a.c = r[ 9 + c ] > 0.01 ? r[ 9 + c ] : 1 per channel (1 with ACN_DENOISE_NO_DEMODULATE);  c = L / a.
+ *                A pixel is FILTERABLE iff r[ 0 ] < inf, ( uint32 )r[ 12 ] has no ACN_SURF_EMITTER and c.x, c.y, c.z are finite.
+ *                Any other pixel (a miss, an emitter, non-finite radiance) is copied to the output bit for bit and is never a tap.
+ *                Two filterable pixels MATCH iff r[ 7 ], r[ 8 ] and r[ 13 ] (enter object, exit object, hops), converted to int32,
+ *                are equal.  N = r[ 4 .. 6 ], P = r[ 1 .. 3 ].
+ * 2 variance     lum( c ) = 0.2126 * c.x + 0.7152 * c.y + 0.0722 * c.z.  Over the 7 x 7 window around the pixel, rows outer, left
+ *                to right, the in-image filterable pixels that match it (itself included): n += 1, s1 += l', s2 += l' * l'.
+ *                m = s1 / n;  var = max( 0, s2 / n - m * m ).
+ * 3 levels       i = 0 .. iterations - 1, stride s = 2^i, k = { 1/16, 1/4, 3/8, 1/4, 1/16 }.  The 5 x 5 taps at ( x + ( ti - 2 ) * s,
+ *                y + ( tj - 2 ) * s ), tj outer, ti inner; a tap off the image or not filterable or not matching is skipped.
+ *                  centre tap       w = k[ 2 ] * k[ 2 ]
+ *                  any other tap    w = ( ( k[ tj ] * k[ ti ] ) * w_n ) * exp( -( t_p + t_l ) )
+ *                    w_n = max( 0, dot( N, N' ) ), then normal_power_log2 times w_n = w_n * w_n
+ *                    D = P' - P;  len = sqrt( dot( D, D ) );  t_p = len > 0 ? ( |dot( N, D )| / len ) / sigma_plane : 0
+ *                    t_l = |l' - l| / ( sigma_lum * sqrt( var ) + 1e-8 ),  l = lum( c ), l' = lum( c' ) of the level's input,
+ *                    var the centre's
+ *                  sw += w;  sd += w * ( c' - c );  sv += ( w * w ) * var'
+ *                c_out = c + sd / sw: the weighted mean sum( w c' ) / sum( w ), taken about the centre so that a mean of equal
+ *                numbers is that number;  var_out = sv / ( sw * sw ).  The levels ping-pong between the two colour buffers.
+ * 4 remodulate   out = c * a.
+ * A result does not depend on which pixels share a wavefront.  What the filter is for: main-pass frames of few samples.  It is not
+ * for gradient-cycle refinements (several sample positions per pixel), and it is biased where a texture edge is not in the albedo. */
+#define ACN_DENOISE_NO_DEMODULATE     1u
+#define ACN_DENOISE_NORMAL_POWER_SET  2u   /* normal_power_log2 is taken as it stands: without this flag a 0 there means the default */
+#define ACN_DENOISE_DEFAULT_ITERATIONS        5
+#define ACN_DENOISE_DEFAULT_NORMAL_POWER_LOG2 7
+#define ACN_DENOISE_DEFAULT_SIGMA_PLANE       0.1
+#define ACN_DENOISE_DEFAULT_SIGMA_LUM         4.0
+#define ACN_DENOISE_MAX_ITERATIONS            8
+#define ACN_DENOISE_MAX_NORMAL_POWER_LOG2     10
+typedef struct acn_denoise_params
+{
+    uint32_t struct_size;        /* sizeof( acn_denoise_params ) as the CALLER was compiled; the library reads nothing beyond it,
+                                    and members it does not reach take their defaults */
+    uint32_t iterations;         /* a-trous levels 1 .. 8; 0 = default 5 */
+    uint32_t normal_power_log2;  /* w_n = max( 0, N.N' )^( 2^k ) by k squarings, k 0 .. 10; 0 = default 7, unless flags has
+                                    ACN_DENOISE_NORMAL_POWER_SET: then 0 is k = 0, w_n = max( 0, N.N' ) */
+    uint32_t flags;              /* ACN_DENOISE_* */
+    double   sigma_plane;        /* default 0.1; a member that is 0 takes its default */
+    double   sigma_lum;          /* default 4.0 */
+} acn_denoise_params;
+#define ACN_DENOISE_PARAMS_INIT { ( uint32_t )sizeof( acn_denoise_params ), 0u, 0u, 0u, 0.0, 0.0 }
+int acn_denoise_dev( acn_scene_handle* h, const void* d_linear_rgb, const void* d_surface, size_t width, size_t height,
+                     const acn_denoise_params* prm /* nullable: defaults */, void* d_out_rgb, const acn_render_opts* opts );
+int acn_denoise    ( acn_scene_handle* h, const double* linear_rgb, const double* surface, size_t width, size_t height,
+                     const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
+
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );
 
