@@ -19,6 +19,11 @@ ACN_DENOISE_DEFAULT_ITERATIONS, ACN_DENOISE_DEFAULT_NORMAL_POWER_LOG2 = 5, 7
 ACN_DENOISE_DEFAULT_SIGMA_PLANE, ACN_DENOISE_DEFAULT_SIGMA_LUM = 0.1, 4.0
 ACN_DENOISE_MAX_ITERATIONS, ACN_DENOISE_MAX_NORMAL_POWER_LOG2 = 8, 10
 
+# the thin-lens camera (acn_lens_rays, acn_render_lens): flags, defaults and limits of acn_lens_params
+ACN_LENS_JITTER = 1
+ACN_LENS_DEFAULT_SAMPLES, ACN_LENS_MAX_SAMPLES = 16, 4096
+ACN_LENS_SEED = 2718281828
+
 ACN_OK, ACN_ERR_ARG, ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV, ACN_ERR_DEVICE, ACN_ERR_CANCELLED = 0, -1, -2, -3, -4, -5
 
 NODE_TYPES = {1: "plane", 2: "sphere", 3: "squaroid", 4: "distance", 5: "pair_inside", 6: "pair_outside",
@@ -69,6 +74,11 @@ class DenoiseParams(C.Structure):
                 ("sigma_plane", C.c_double), ("sigma_lum", C.c_double)]
 
 
+class LensParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("samples", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint32),
+                ("aperture_radius", C.c_double), ("focus_distance", C.c_double)]
+
+
 class V3(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
 
@@ -86,3 +96,4 @@ class SceneStruct(C.Structure):
 
 assert C.sizeof(Node) == 304, C.sizeof(Node)
 assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
+assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)

@@ -86,6 +86,15 @@ void acn_launch_surface( uint32_t mode, bool lds_nodes, size_t lds_bytes, hipStr
 void acn_launch_denoise( const double* lin, const double* surf, size_t width, size_t height, uint32_t iterations, uint32_t normal_power_log2,
                          uint32_t no_demodulate, double sigma_plane, double sigma_lum, void* scratch, double* out_rgb, hipStream_t stream );
 
+/* the thin-lens camera (k_lens.hip).  LensSetup: acn_lens_params after the host's checks, final values, no defaults.
+ * rays: out_rays[ i ][ s ][ 6 ] = the ray of position i, sample first_sample + s (s < n_samples); pos_xy [ n ][ 2 ], or null: the pixel
+ * centres first_pixel + i of the scene's raster.  n * n_samples fits a grid of 256-lane workgroups (the host checks).
+ * reduce: out_rgb[ i ] = ( ( ( 0.0 + rad[ i ][ 0 ] ) + rad[ i ][ 1 ] ) + ... ) / samples, through cl_s_sat unless linear; rad [ n ][ samples ][ 3 ]. */
+struct LensSetup { uint64_t seed; uint32_t samples, jitter; double aperture_radius, focus_distance; };
+void acn_launch_lens_rays( const DevScene& sc, const double* pos_xy, size_t first_pixel, size_t n, const LensSetup& ls,
+                           uint32_t first_sample, uint32_t n_samples, double* out_rays, hipStream_t stream );
+void acn_launch_lens_reduce( const double* rad, size_t n, uint32_t samples, double gamma, int linear, double* out_rgb, hipStream_t stream );
+
 /* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
 struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
 int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */

@@ -103,6 +103,7 @@ struct Tunables
                                           20 - 100 (1080p 114 - 174 -> 72 - 75 ms, c2 94 - 135 -> 48 - 49, paraffin_lamp 486 - 504 -> 466 - 479, hanging_lamp
                                           417 - 426 -> 390 - 401); upload + first frame: 1080p 247 - 299 -> 277 - 323 ms, c2 189 - 261 -> 195 - 204, the
                                           lamps +30.  For a host that uploads long before it renders */
+    size_t   lens_slice_rays = ( size_t )1 << 21;   /* ACN_LENS_SLICE_RAYS: rays of one slice of a lens call (acn_render_lens*): floor( this / K ) positions, at least 1 */
     bool     count_work = false;       /* ACN_COUNT_WORK */
     bool     stage_timing = false;     /* ACN_STAGE_TIMING */
     void read()
@@ -122,6 +123,9 @@ struct Tunables
         if( fetch_shade < 1 ) fetch_shade = 1;
         if( const char* e = getenv( "ACN_WALK_PASSES" ) ) walk_passes = ( uint32_t )atoll( e );
         if( const char* e = getenv( "ACN_PRIVATE_LIMIT" ) ) { private_limit = ( uint32_t )atoll( e ); private_limit_set = true; }
+        if( const char* e = getenv( "ACN_LENS_SLICE_RAYS" ) ) lens_slice_rays = ( size_t )atoll( e );
+        if( lens_slice_rays < 1 ) lens_slice_rays = 1;
+        if( lens_slice_rays > ( ( size_t )1 << 28 ) ) lens_slice_rays = ( size_t )1 << 28;
         if( walk_passes < 1 ) walk_passes = 1;
         if( walk_passes > ACN_MAX_WALK_PASSES ) walk_passes = ACN_MAX_WALK_PASSES;
         if( fetch_walk < 64 ) fetch_walk = 64;
@@ -228,6 +232,7 @@ struct acn_scene_handle
     unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
     uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
     void* d_denoise = nullptr; size_t denoise_bytes = 0;                                    /* acn_denoise: guides and colour buffers, apart from the render workspace */
+    double* d_lens_rays = nullptr; double* d_lens_rad = nullptr; size_t lens_cap = 0;       /* acn_render_lens*: the rays [ 6 ] and the radiance [ 3 ] of a slice, lens_cap rays each */
     bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
     std::string lane_error;
     bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
@@ -1036,6 +1041,8 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( h->d_ray_check ) hipFree( h->d_ray_check );
     if( h->d_surface_flags ) hipFree( h->d_surface_flags );
     if( h->d_denoise ) hipFree( h->d_denoise );
+    if( h->d_lens_rays ) hipFree( h->d_lens_rays );
+    if( h->d_lens_rad ) hipFree( h->d_lens_rad );
     if( !h->is_lane )   /* a lane borrows the resident scene of its parent */
     {
         if( h->d_nodes ) hipFree( h->d_nodes );
@@ -2355,6 +2362,157 @@ extern "C" int acn_denoise( acn_scene_handle* h, const double* linear_rgb, const
     if( st == ACN_OK && hipMemcpy( out_rgb, d_rgb, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "D2H copy failed" );
     hipFree( d_rgb ); hipFree( d_surf );
     return st;
+}
+
+/* ---- the thin-lens camera (k_lens.hip) ---- */
+static bool positive_finite( double x ) { return x > 0 && x <= 1.7976931348623157e308; }
+
+/* every check of a lens call's parameters: on the host, before the handle is touched.  window: the samples an acn_lens_rays call asks for */
+static int lens_check( const acn_scene_handle* h, const acn_lens_params* prm, const uint32_t* window, LensSetup* ls )
+{
+    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
+    acn_lens_params p = ACN_LENS_PARAMS_INIT;
+    if( prm )
+    {
+        if( prm->struct_size < sizeof( uint32_t ) ) return fail( ACN_ERR_ARG, "acn_lens_params.struct_size " + std::to_string( prm->struct_size ) + " is smaller than its first member" );
+        p = acn_lens_params{};
+        memcpy( &p, prm, prm->struct_size < sizeof( p ) ? prm->struct_size : sizeof( p ) );
+    }
+    if( p.samples > ACN_LENS_MAX_SAMPLES ) return fail( ACN_ERR_ARG, "acn_lens_params.samples " + std::to_string( p.samples ) + " is above 4096" );
+    if( p.flags & ~ACN_LENS_JITTER ) return fail( ACN_ERR_ARG, "unknown acn_lens_params.flags bits" );
+    if( !( p.aperture_radius >= 0 ) || p.aperture_radius > 1.7976931348623157e308 ) return fail( ACN_ERR_ARG, "acn_lens_params.aperture_radius is negative or not finite" );
+    if( p.aperture_radius > 0 )
+    {
+        if( !positive_finite( p.focus_distance ) ) return fail( ACN_ERR_ARG, "acn_lens_params.focus_distance must be positive and finite when the aperture is open" );
+        if( !( h->dev.prm.camera_focal_length > 0 ) ) return fail( ACN_ERR_ARG, "an open aperture needs a camera_focal_length above 0: the plane in focus lies in front of the camera" );
+    }
+    ls->samples = p.samples ? p.samples : ACN_LENS_DEFAULT_SAMPLES;
+    ls->jitter = ( p.flags & ACN_LENS_JITTER ) ? 1u : 0u;
+    ls->seed = ACN_LENS_SEED + ( uint64_t )p.seed;
+    ls->aperture_radius = p.aperture_radius;
+    ls->focus_distance = p.aperture_radius > 0 ? p.focus_distance : 0.0;
+    if( window )
+    {
+        if( window[ 1 ] == 0 ) return fail( ACN_ERR_ARG, "n_samples is 0" );
+        if( ( uint64_t )window[ 0 ] + window[ 1 ] > ls->samples ) return fail( ACN_ERR_ARG, "first_sample + n_samples is above the " + std::to_string( ls->samples ) + " samples of the lens" );
+    }
+    return ACN_OK;
+}
+
+extern "C" int acn_lens_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                                  uint32_t n_samples, void* d_out_rays, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !d_pos_xy || !d_out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    LensSetup ls;
+    const uint32_t window[ 2 ] = { first_sample, n_samples };
+    int st = lens_check( h, prm, window, &ls );
+    if( st != ACN_OK ) return st;
+    if( n > 0xFFFFFF00ull / n_samples ) return fail( ACN_ERR_ARG, "too many rays in one call" );
+    if( n == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    acn_launch_lens_rays( h->dev, ( const double* )d_pos_xy, 0, n, ls, first_sample, n_samples, ( double* )d_out_rays, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_lens_rays( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                              uint32_t n_samples, double* out_rays )
+{
+    if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    LensSetup ls;
+    const uint32_t window[ 2 ] = { first_sample, n_samples };
+    int st = lens_check( h, prm, window, &ls );
+    if( st != ACN_OK ) return st;
+    if( n > 0xFFFFFF00ull / n_samples ) return fail( ACN_ERR_ARG, "too many rays in one call" );
+    if( n == 0 ) return ACN_OK;
+    return on_host_buffers( h, pos_xy, 2, n, out_rays, ( size_t )6 * n_samples, [ & ]( double* d_pos, double* d_out )
+    {
+        return acn_lens_rays_dev( h, d_pos, n, prm, first_sample, n_samples, d_out, nullptr );
+    } );
+}
+
+/* a lens call after its null checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice: rays, the ray path of
+ * acn_render_rays_dev (linear, its validity kernel left out: the rays are valid by construction), the ordered mean */
+static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, double* d_out_rgb,
+                        const acn_render_opts* opts )
+{
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );
+    if( st != ACN_OK ) return st;
+    const int linear = ( opts->flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0;
+    if( opts->shard_mode > ACN_SHARD_SAMPLES ) return fail( ACN_ERR_ARG, "unknown shard_mode" );
+    if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
+    {
+        if( opts->shard_rank >= opts->shard_world ) return fail( ACN_ERR_ARG, "shard_rank >= shard_world" );
+        if( !linear ) return fail( ACN_ERR_ARG, "a lens call sharded by samples gives partial means: it needs ACN_OPT_LINEAR_OUT" );
+    }
+    if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+    if( n == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
+    const size_t K = ls.samples;
+    size_t slice = h->tun.lens_slice_rays / K;
+    if( slice < 1 ) slice = 1;
+    if( slice > n ) slice = n;
+    if( h->lens_cap < slice * K )
+    {
+        if( h->d_lens_rays ) hipFree( h->d_lens_rays );   /* (waits for whatever still reads them) */
+        if( h->d_lens_rad ) hipFree( h->d_lens_rad );
+        h->d_lens_rays = h->d_lens_rad = nullptr; h->lens_cap = 0;
+        HIP_TRY( hipMalloc( &h->d_lens_rays, sizeof( double ) * 6 * slice * K ) );
+        HIP_TRY( hipMalloc( &h->d_lens_rad, sizeof( double ) * 3 * slice * K ) );
+        h->lens_cap = slice * K;
+    }
+    acn_render_opts ray_opts = *opts;
+    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
+    for( size_t base = 0; base < n; base += slice )
+    {
+        if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+        const size_t cnt = n - base < slice ? n - base : slice;
+        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays, stream );
+        HIP_TRY( hipGetLastError() );
+        st = render_dispatch( h, primary_rays( h->d_lens_rays ), cnt * K, h->d_lens_rad, &ray_opts, stream );
+        if( st != ACN_OK ) return st;
+        acn_launch_lens_reduce( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, stream );
+        HIP_TRY( hipGetLastError() );
+    }
+    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_render_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
+                                    const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !d_pos_xy || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    return render_lens( h, ( const double* )d_pos_xy, 0, n, prm, ( double* )d_out_rgb, opts );
+}
+
+extern "C" int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
+                                              const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( count && !d_out_rgb ) ) return fail( ACN_ERR_ARG, "null argument" );
+    const size_t pixels = h->dev.prm.image_width * h->dev.prm.image_height;
+    if( first > pixels || count > pixels - first ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
+    return render_lens( h, nullptr, first, count, prm, ( double* )d_out_rgb, opts );
+}
+
+extern "C" int acn_render_lens( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
+                                const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !pos_xy || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
+    if( st != ACN_OK ) return st;
+    if( n == 0 ) return ACN_OK;
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    return on_host_buffers( h, pos_xy, 2, n, out_rgb, 3, [ & ]( double* d_pos, double* d_out ) { return acn_render_lens_dev( h, d_pos, n, prm, d_out, &o ); } );
 }
 
 extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )

@@ -424,6 +424,66 @@ class Handle:
         o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
         check(hip.acn_denoise_dev(self.h, d_linear_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)), "acn_denoise_dev")
 
+    # the thin-lens camera (acn_lens_rays, acn_render_lens): K rays per sample position, averaged on the device
+    @staticmethod
+    def lens_params(samples=None, aperture=0.0, focus=0.0, jitter=False, seed=0):
+        """acn_lens_params of keyword arguments; samples=None is the library's default (16)"""
+        p = abi.LensParams()
+        p.struct_size = C.sizeof(abi.LensParams)
+        p.samples = 0 if samples is None else int(samples)
+        p.flags = abi.ACN_LENS_JITTER if jitter else 0
+        p.seed = int(seed)
+        p.aperture_radius = float(aperture)
+        p.focus_distance = float(focus)
+        return p
+
+    @staticmethod
+    def _lens(lens, params):
+        if lens is not None and params:
+            raise ValueError("give either an acn_lens_params or its keyword arguments")
+        return lens if lens is not None else Handle.lens_params(**params)
+
+    def lens_rays(self, pos_xy, first_sample=0, n_samples=None, lens=None, **params):
+        """The lens rays of sample positions (acn_lens_rays): pos_xy [n,2] -> [n, n_samples, 6] origin, direction of the samples
+        first_sample .. first_sample + n_samples - 1 (default: all from first_sample on).  lens: an abi.LensParams, or its
+        keyword arguments (Handle.lens_params)."""
+        p = self._lens(lens, params)
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        if n_samples is None:
+            n_samples = (p.samples or abi.ACN_LENS_DEFAULT_SAMPLES) - first_sample
+        out = np.empty((pos.shape[0], max(int(n_samples), 0), 6), dtype=np.float64)
+        check(hip.acn_lens_rays(self.h, pos.ctypes.data, pos.shape[0], C.byref(p), first_sample, n_samples, out.ctypes.data),
+              "acn_lens_rays")
+        return out
+
+    def lens_rays_dev(self, d_pos_ptr, n, d_out_ptr, first_sample=0, n_samples=None, stream=None, lens=None, **params):
+        p = self._lens(lens, params)
+        if n_samples is None:
+            n_samples = (p.samples or abi.ACN_LENS_DEFAULT_SAMPLES) - first_sample
+        o = self._opts(False, stream)
+        check(hip.acn_lens_rays_dev(self.h, d_pos_ptr, n, C.byref(p), first_sample, n_samples, d_out_ptr, C.byref(o)),
+              "acn_lens_rays_dev")
+
+    def render_lens(self, pos_xy, linear=False, lens=None, **params):
+        """The mean radiance of the lens rays of every position (acn_render_lens): pos_xy [n,2] -> rgb [n,3] float64."""
+        p = self._lens(lens, params)
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((pos.shape[0], 3), dtype=np.float64)
+        o = self._opts(linear, None)
+        check(hip.acn_render_lens(self.h, pos.ctypes.data, pos.shape[0], C.byref(p), out.ctypes.data, C.byref(o)), "acn_render_lens")
+        return out
+
+    def render_lens_dev(self, d_pos_ptr, n, d_out_ptr, linear=False, stream=None, lens=None, **params):
+        p = self._lens(lens, params)
+        o = self._opts(linear, stream)
+        check(hip.acn_render_lens_dev(self.h, d_pos_ptr, n, C.byref(p), d_out_ptr, C.byref(o)), "acn_render_lens_dev")
+
+    def render_lens_main_pass_dev(self, first, count, d_out_ptr, linear=False, stream=None, lens=None, **params):
+        p = self._lens(lens, params)
+        o = self._opts(linear, stream)
+        check(hip.acn_render_lens_main_pass_dev(self.h, first, count, C.byref(p), d_out_ptr, C.byref(o)),
+              "acn_render_lens_main_pass_dev")
+
     def pick(self, x, y):
         """The object under sample position (x, y): None on a miss, else node (enter object if any, else exit object), its
         type name, distance and position."""

@@ -382,6 +382,79 @@ int acn_denoise_dev( acn_scene_handle* h, const void* d_linear_rgb, const void* 
 int acn_denoise    ( acn_scene_handle* h, const double* linear_rgb, const double* surface, size_t width, size_t height,
                      const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
 
+/* Thin-lens camera: depth of field and sub-pixel jitter (k_lens.hip).  The reference has a pinhole only; the lens is a definition
+ * of this library.  Every sample position gets K primary rays from the generator below; the production pipeline renders them as
+ * acn_render_rays does, and the K radiances of a position are averaged on the device in the order of k.
+ *
+ * The ray of position ( px, py ), sample k (0 <= k < K).  Everything is IEEE binary64 without contraction, a / b is IEEE division,
+ * sqrt is acn_sqrt of csrc/acn_detmath.h; f3_rnd0, f3_rnd1 (one step of the LCG each, uniform in [ -1, 1 ] and [ 0, 1 ]),
+ * v_random_seed, v_of_length, camera_ray and m_mlv are those of csrc/acn_device.h; camera_rotation is the matrix camera_ray uses;
+ * dot( a, b ) = ( a.x * b.x + a.y * b.y ) + a.z * b.z; vector sums, differences and products by a number are per component.
+ *   rv = v_random_seed( ( px, py, ( double )( 2 * k + 1 ) ), ACN_LENS_SEED + seed )        (64-bit sum.  v_random_seed reads of a
+ *                     component only its frexp mantissa, which 1, 2, 4, 8 ... share: the odd numbers 2 k + 1 all differ in it,
+ *                     as the pixel centres i + 0.5 do, so the K samples of a position are K different samples)
+ *   ACN_LENS_JITTER:  jx = f3_rnd1( &rv ) - 0.5;  jy = f3_rnd1( &rv ) - 0.5;  qx = px + jx;  qy = py + jy
+ *   else              qx = px;  qy = py;  nothing is drawn
+ *   ( o, d ) = camera_ray( qx, qy )
+ *   aperture_radius == 0:  the ray is ( o, d ), bit for bit, and nothing more is drawn.  Else
+ *     at most 32 rounds:  u = f3_rnd0( &rv );  v = f3_rnd0( &rv );  the first pair with u * u + v * v <= 1.0 is taken and ends the
+ *                         rounds; if none is, u = v = 0
+ *     R = m_mlv( camera_rotation, ( 1, 0, 0 ) );  V = m_mlv( camera_rotation, ( 0, 1, 0 ) );  T = m_mlv( camera_rotation, ( 0, 0, 1 ) )
+ *                         (right, view and top direction of the camera)
+ *     t  = focus_distance / dot( d, V )
+ *     F  = o + d * t                                  the point of the plane in focus that the pinhole ray meets
+ *     o' = o + ( R * ( aperture_radius * u ) + T * ( aperture_radius * v ) )
+ *     the ray is ( o', v_of_length( F - o', 1 ) )
+ * The mean.  L( ray ) is what acn_render_rays returns for that ray with ACN_OPT_LINEAR_OUT (a miss gives background_color);
+ * sum = ( ( 0.0 + L0 ) + L1 ) + ... in the order of k;  mean = sum / ( double )K;  the output is cl_s_sat( mean ), or mean itself
+ * with ACN_OPT_LINEAR_OUT.  So K = 1 without jitter and with aperture 0 is acn_render_positions, bit for bit.  A result does not
+ * depend on which positions or samples share a wavefront, nor on how the call is cut into slices.
+ *
+ * acn_lens_rays writes the rays of samples [ first_sample, first_sample + n_samples ) of every position: out [ n ][ n_samples ][ 6 ].
+ * The _dev form uses of opts only `stream` and never synchronises a caller's stream (NULL: the handle's own, and then it waits).
+ * acn_render_lens*: opts as for acn_render_rays_dev: flags, cancel (polled at least between slices), stream, ACN_SHARD_SAMPLES --
+ * which needs ACN_OPT_LINEAR_OUT; the mean of partial sums is then a partial mean, and the caller sum-reduces the ranks' buffers.
+ * A call is cut into slices of floor( S / K ) positions, at least 1 (S: ACN_LENS_SLICE_RAYS, default 2^21, read at
+ * acn_scene_upload; it changes no pixel).  Per slice the rays are made, rendered by the ray path of acn_render_rays_dev as it
+ * stands (its validity check left out: the rays are valid by construction) and reduced into the caller's buffer.  The handle owns
+ * one rays buffer and one radiance buffer of a slice (72 bytes per ray), apart from the render workspace and the denoiser's
+ * scratch, grown on demand, freed by acn_scene_free.  acn_last_stage_ms, acn_last_counters and acn_last_kernel_ms describe the
+ * render of the LAST slice.
+ * ACN_ERR_ARG, checked on the host before anything is written, acn_last_error set: a null handle or (with n > 0) a null buffer;
+ * samples > 4096; unknown flag bits; struct_size < 4; an aperture_radius that is negative or not finite; aperture_radius > 0 with a
+ * focus_distance that is not positive and finite, or with camera_focal_length <= 0; n_samples == 0 or first_sample + n_samples > K;
+ * more than 2^32 - 256 rays in one acn_lens_rays call; a pixel range outside the image; ACN_SHARD_SAMPLES without
+ * ACN_OPT_LINEAR_OUT.  A null acn_lens_params is ACN_LENS_PARAMS_INIT. */
+#define ACN_LENS_JITTER 1u              /* each sample's position is moved uniformly inside its pixel-sized square */
+#define ACN_LENS_DEFAULT_SAMPLES 16
+#define ACN_LENS_MAX_SAMPLES     4096
+#define ACN_LENS_SEED            2718281828ull
+typedef struct acn_lens_params
+{
+    uint32_t struct_size;      /* sizeof as the CALLER was compiled; nothing beyond it is read; < 4 is ACN_ERR_ARG */
+    uint32_t samples;          /* K: rays per position, 1 .. 4096; 0 = default 16 */
+    uint32_t flags;            /* ACN_LENS_*; unknown bits are ACN_ERR_ARG */
+    uint32_t seed;             /* added to ACN_LENS_SEED: another seed, another sample set */
+    double   aperture_radius;  /* lens radius in scene units, >= 0, finite; 0 = pinhole */
+    double   focus_distance;   /* distance of the plane in focus from the camera position, measured ALONG the view
+                                  direction; > 0 and finite whenever aperture_radius > 0, otherwise not read */
+} acn_lens_params;
+#define ACN_LENS_PARAMS_INIT { ( uint32_t )sizeof( acn_lens_params ), 0u, 0u, 0u, 0.0, 0.0 }
+
+/* the rays of samples [ first_sample, first_sample + n_samples ) of every position: out [ n ][ n_samples ][ 6 ] f64 */
+int acn_lens_rays    ( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                       uint32_t n_samples, double* out_rays );
+int acn_lens_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                       uint32_t n_samples, void* d_out_rays, const acn_render_opts* opts );
+/* out_rgb[ i ] = cl_s_sat( mean over k of L( ray( i, k ) ) ); linear with ACN_OPT_LINEAR_OUT */
+int acn_render_lens    ( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
+                         const acn_render_opts* opts );
+int acn_render_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
+                         const acn_render_opts* opts );
+/* the same for the pixel centres [ first, first + count ) of the scene's raster (positions of acn_render_main_pass_dev) */
+int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
+                                   const acn_render_opts* opts );
+
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );
 
