@@ -34,9 +34,13 @@ $(BUILD)/k_walk_lds.o $(BUILD)/k_walk_glb.o: HIPFLAGS += $(WALK_SCHED)
 $(BUILD)/%.o: actinon_amd/csrc/%.hip $(wildcard actinon_amd/csrc/*.h) include/actinon_hip.h
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(LIBDIR)/libactinon_hip.so: $(HIP_OBJS)
+# the scene tables of the upload: host-only C++, no HIP (tests/test_tables_cpu.py compiles the same unit on its own)
+$(BUILD)/acn_tables.o: actinon_amd/csrc/acn_tables.cpp actinon_amd/csrc/acn_tables.h include/actinon_hip.h
+	@mkdir -p $(BUILD)
+	$(CXX) -O2 -fPIC -std=c++17 -Wall -ffp-contract=off -fno-fast-math -Iinclude -Iactinon_amd/csrc -c -o $@ $<
+$(LIBDIR)/libactinon_hip.so: $(HIP_OBJS) $(BUILD)/acn_tables.o
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(HIP_OBJS)
+	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(HIP_OBJS) $(BUILD)/acn_tables.o
 
 $(LIBDIR)/libactinon_host.so: actinon_amd/host/acn_scene.c actinon_amd/host/acn_driver.c actinon_amd/host/acn_scenes.c actinon_amd/host/acn_interp.c include/acn_scene.h include/acn_interp.h include/actinon_hip.h $(LIBDIR)/libactinon_hip.so
 	$(CC) $(CFLAGS) -shared -o $@ actinon_amd/host/acn_scene.c actinon_amd/host/acn_driver.c actinon_amd/host/acn_scenes.c actinon_amd/host/acn_interp.c -L$(LIBDIR) -lactinon_hip -lm -Wl,-rpath,'$$ORIGIN'

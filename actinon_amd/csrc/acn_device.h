@@ -18,6 +18,7 @@
 
 #include <hip/hip_runtime.h>
 #include "actinon_hip.h"
+#include "acn_tables.h"   /* GNode, GMat, SCEntry, the flag / opcode constants and the depth and LDS limits: shared with the host-only table builder */
 #include "acn_detmath.h"
 #include "acn_costs.h"
 
@@ -34,48 +35,11 @@
 #define F3_EPS 1E-6
 #define ACN_PI 3.14159265358979323846
 
-#ifndef ACN_CSG_MAX_DEPTH
-#define ACN_CSG_MAX_DEPTH   24   /* nesting of pair / neg / scale wrappers */
-#endif
-#ifndef ACN_CMP_MAX_DEPTH
-#define ACN_CMP_MAX_DEPTH   12   /* nesting of compounds */
-#endif
 #define ACN_TASK_STACK      64   /* pending rays per lane */
-#define ACN_MAX_PATH_LEVELS 5    /* suspended path loops: trace_depth <= 10 * 5 + 10 */
 
 struct V3 { double x, y, z; };
 struct M3 { V3 x, y, z; };
 struct Ray { V3 p, d; };
-
-/* Device layout of a node: geometry only (192 B); shading properties live in GMat (96 B, read once per shading
- * point).  Built from the ABI's acn_node by acn_scene_upload. */
-struct GNode
-{
-    int32_t  type;
-    uint32_t flags;
-    int32_t  child0, child1;
-    double   prm[ 4 ];
-    double   pos[ 3 ];
-    double   env_pos[ 3 ];
-    double   env_radius;
-    double   rax[ 9 ];
-    double   surface_roughness;
-    int32_t  sdf_kind, cycles;
-};
-
-struct GMat
-{
-    double color[ 3 ];
-    double radiance;
-    double refractive_index;
-    double fresnel_reflectivity;
-    double chromatic_reflectivity;
-    double diffuse_reflectivity;
-    double sigma;
-    double transparency[ 3 ];
-    int32_t texture;     /* index into the texture table, -1 = none */
-    int32_t pad_;
-};
 
 /* The scene arrays are read through the CONSTANT address space: they never change while a kernel runs, so a load
  * whose address is the same in every lane (root-compound loops, a wave's shading task) is issued as a scalar load
@@ -94,31 +58,8 @@ typedef double ACN_LDS* LdsF64P;
 typedef uint32_t ACN_LDS* LdsU32P;
 /* dynamic LDS of the machine kernels: [ staged node array (optional) ][ CSG stacks of the block's 256 lanes ] */
 extern __shared__ __attribute__( ( aligned( 16 ) ) ) double acn_lds_raw[];
-#ifndef ACN_LDS_DEPTH
-#define ACN_LDS_DEPTH 3                 /* stack levels kept in LDS; deeper nesting continues in scratch */
-#endif
-#define ACN_LDS_LANES 256               /* block size of the kernels that provide the stack area */
-/* per level and lane: a 8 B, parked normal 24 B, w 4 B, side 4 B; doubles first (alignment):
- * [ a : D x 256 ][ nx, ny, nz : 3 x D x 256 ][ w : D x 256 ][ side : D x 256 ] */
-#define ACN_LDS_STACK_BYTES ( ACN_LDS_DEPTH * ACN_LDS_LANES * 40 )
+/* the stacks ( ACN_LDS_STACK_BYTES ) and behind them the parked ray origins ( ACN_LDS_ORG_BYTES ): acn_tables.h */
 #define ACN_NO_LDS_STACK 0xFFFFFFFFu
-/* behind the stacks: the ray origin of the lock-step machine at hand, one per lane (OrgLds): three planes of 256 doubles */
-#define ACN_LDS_ORG_BYTES ( 3 * ACN_LDS_LANES * 8 )
-
-/* One entry of a simple compound's pre-order table (simple_compound_hit): everything a visit needs -- the element's
- * envelope, its type and the two links -- in ONE 48-byte record, i.e. one memory round trip per visited node instead
- * of three dependent ones (element index -> node header -> envelope). */
-struct SCEntry
-{
-    double  env_pos[ 3 ], env_radius;
-    int32_t node;        /* node index (leaves: the object that is hit) */
-    int32_t skip;        /* entry behind this element's subtree */
-    int32_t type;        /* acn_node_type */
-    uint32_t flags;      /* ACN_NODE_HAS_ENVELOPE | ACN_SC_SPHERE ( skip = index into sc_spheres ) | ACN_SC_ROUGH */
-};
-#define ACN_SC_SPHERE 0x10000u
-#define ACN_SC_ROUGH  0x20000u
-#define ACN_SC_BOUNDING 0x40000u   /* the upload step has verified that the envelope contains every leaf below the entry (all of them spheres) */
 
 /* device-resident scene, parameterised by where the node array is read from */
 template< class NP >
@@ -720,9 +661,6 @@ template< class NP, class CT > DEV V3 roughness_normal_( NP hdr, V3 n, V3 hit_po
  * step marks such pairs (ACN_GFLAG_LEAF_PAIR) and both machines evaluate them in line: the same sequence of child
  * evaluations, side tests and walk steps as the general frames (objects.c:1052-1094 / 1209-1251, 1096-1099 / 1253-1256),
  * without frame, stack or nested loops. */
-#define ACN_GFLAG_LEAF_PAIR 0x100u      /* device-only bits of GNode.flags: a level-1 pair ... */
-#define ACN_GFLAG_PAIR2     0x400u      /* ... a level-2 pair: at least one operand is a level-1 pair (machines only) */
-#define ACN_GFLAG_PRUNE_LEVELS_SHIFT 12  /* bits 12 - 14: see surely_outside */
 
 template< class NP, class CT > DEV int simple_leaf_side_( NP g, V3 pos, CT* cnt )
 {
@@ -1346,7 +1284,6 @@ DEV bool env_behind( V3 env_pos, double r, V3 rp, V3 rd, double bound )
  * entry count); compound_s_ray_hit (compound.c:215-243) then is a stackless loop: an enveloped compound that the
  * ray misses is skipped by its link, everything else advances by one.  Same element order as the recursion, so ties
  * between equal distances resolve identically.  No stack, no machine: k_shade runs it in line. */
-#define ACN_GFLAG_SIMPLE_COMPOUND 0x200u   /* device-only bit of GNode.flags */
 
 template< bool NOR, class SC, class CT >
 DEV double simple_compound_hit( const SC& sc, int cmp, V3 rp, V3 rd, V3* p_nor, int* hit_obj, double limit, CT* cnt )
@@ -1449,13 +1386,10 @@ DEV bool surely_outside_n( NP nodes, int node, V3 rp, V3 rd )
 }
 template< int D, class SC >
 DEV bool surely_outside( const SC& sc, int node, V3 rp, V3 rd ) { return surely_outside_n< D >( sc.nodes, node, rp, rd ); }
-#ifndef ACN_PRUNE_DEPTH
-#define ACN_PRUNE_DEPTH 3
-#endif
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* Interval pruning of big CSG objects.  For a root element with many nodes the upload step compiles a small postfix
- * program (actinon_hip.hip: build_prune_programs) that computes a conservative parameter interval [ lo, hi ] of the
+ * program (acn_tables.cpp: build_prune_programs) that computes a conservative parameter interval [ lo, hi ] of the
  * ray: every t at which rp + t * rd could be classified "inside the object" by obj_side, or be reported as a hit,
  * lies in it.  An empty interval means the reference returns f3_inf for the object and +1 for obj_side at every point
  * it would look at (the argument of surely_outside, made sharper), so the object is skipped with results unchanged:
@@ -1544,14 +1478,11 @@ template< class NP > DEV Iv iv_squaroid( NP o, V3 rp, V3 rd )
  *   pair_outside    H = hull( H(A) u H(B) )                 S = hull( S(A) u S(B) )
  *   envelope E      ray misses E: H = S = empty; else S = S n chord( E ), H unchanged
  * The object is skipped iff H( root ) has no point in [ -W, limit + W ]. */
-enum { ACN_PO_END = 0, ACN_PO_PLANE, ACN_PO_SPHERE, ACN_PO_QUAD, ACN_PO_ALL, ACN_PO_NEG, ACN_PO_AND, ACN_PO_OR, ACN_PO_ENV };
-#define ACN_PO( op, node ) ( ( uint32_t )( op ) | ( ( uint32_t )( node ) << 4 ) )
 #ifdef ACN_PRUNE_CHECK
 #define ACN_FAST_PRUNE( ... ) false
 #else
 #define ACN_FAST_PRUNE( ... ) prune_run( __VA_ARGS__ )
 #endif
-#define ACN_PRUNE_STACK 5
 
 /* true: `node` (a wave-uniform index) cannot report a hit at any t <= limit.  false also when it has no program. */
 template< class NP >

@@ -15,6 +15,7 @@
 #include <condition_variable>
 
 #include "acn_launch.h"
+#include "acn_tables.h"
 #include "acn_chunkplan.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -106,8 +107,18 @@ struct Tunables
     size_t   lens_slice_rays = ( size_t )1 << 21;   /* ACN_LENS_SLICE_RAYS: rays of one slice of a lens call (acn_render_lens*): floor( this / K ) positions, at least 1 */
     bool     count_work = false;       /* ACN_COUNT_WORK */
     bool     stage_timing = false;     /* ACN_STAGE_TIMING */
+    acn_table_opts tables;             /* the switches of the scene tables (acn_tables.h) */
     void read()
     {
+        tables.no_leaf_pairs = getenv( "ACN_NO_LEAF_PAIRS" ) != nullptr;
+        tables.no_pair2 = getenv( "ACN_NO_PAIR2" ) != nullptr;
+        tables.no_prune_levels = getenv( "ACN_NO_PRUNE_LEVELS" ) != nullptr;
+        tables.no_simple_compounds = getenv( "ACN_NO_SIMPLE_COMPOUNDS" ) != nullptr;
+        tables.no_sc_cull = getenv( "ACN_NO_SC_CULL" ) != nullptr;
+        tables.no_sc_reversed = getenv( "ACN_NO_SC_REVERSED" ) != nullptr;
+        tables.verbose = getenv( "ACN_VERBOSE" ) != nullptr;
+        if( const char* e = getenv( "ACN_PRUNE_MIN" ) ) tables.prune_min = ( size_t )atoll( e );
+        if( const char* e = getenv( "ACN_LDS_MAX" ) ) { tables.lds_max = ( size_t )atoll( e ); tables.lds_max_set = true; }
         if( const char* e = getenv( "ACN_WORKSPACE_MB" ) ) workspace_mb = ( size_t )atoll( e );
         if( const char* e = getenv( "ACN_CHUNK" ) ) chunk = ( size_t )atoll( e );
         if( const char* e = getenv( "ACN_LANES" ) ) lanes = atoi( e );
@@ -170,10 +181,23 @@ struct acn_scene_handle
 {
     int device = 0;
     DevScene dev{};
-    GNode*   d_nodes = nullptr;
-    GMat*    d_mats = nullptr;
-    int32_t* d_elems = nullptr;
-    acn_texture* d_textures = nullptr;
+    /* the resident scene and what the tables say about it: a lane borrows all of it from its parent (bind_lane) */
+    struct Resident
+    {
+        GNode*   d_nodes = nullptr;
+        GMat*    d_mats = nullptr;
+        int32_t* d_elems = nullptr;
+        acn_texture* d_textures = nullptr;
+        size_t scene_bytes[ 4 ] = { 0, 0, 0, 0 };
+        int max_csg_depth = 0;
+        size_t lds_bytes = 0;                      /* > 0: the node array fits the LDS staging budget */
+        size_t lds_stack_bytes = 0;                /* > 0: the machine kernels keep their CSG stacks in LDS */
+        bool prune = false;                        /* some root element has an interval-prune program: launch the PRUNE kernel variants */
+        bool leaf_lights = true;                   /* every light element is a plane / sphere */
+        uint32_t elem_pos_base = 0;                /* elems[ elem_pos_base + k ]: given-order position of entry k of the cost-ordered copy (k_hard_shadow: resume words) */
+        int n_levels = 1;                          /* path levels of the scene's trace_depth */
+        size_t n_lights = 1;                       /* elements of the light root */
+    } scene;
     SCEntry* d_sc_table = nullptr;
     double* d_sc_spheres = nullptr;            /* ( pos, radius ) of the sphere leaves of d_sc_table */
     hipStream_t stream = nullptr;
@@ -181,13 +205,10 @@ struct acn_scene_handle
     bool timed = false;
     int cur_stage = 0;
     bool stage_timing = false;                 /* ACN_OPT_STAGE_TIMING of the current call */
-    int max_csg_depth = 0;
     Tunables tun;
     unsigned cus = 256;                        /* compute units of the device */
     unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
     unsigned walk_grid = 1024;                 /* ... of k_walk */
-    int n_levels = 1;                          /* path levels of the scene's trace_depth */
-    size_t n_lights = 1;                       /* elements of the light root */
     /* workspace of the wavefront pipeline */
     Workspace ws;
     uint32_t* d_counts = nullptr;              /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
@@ -195,11 +216,6 @@ struct acn_scene_handle
     unsigned long long* d_accum = nullptr;  size_t accum_cap = 0;
     unsigned long long* d_counters = nullptr;
     std::vector< StageEvents > events;  size_t events_used = 0;
-    size_t lds_bytes = 0;                      /* > 0: the node array fits the LDS staging budget */
-    size_t lds_stack_bytes = 0;                /* > 0: the machine kernels keep their CSG stacks in LDS */
-    bool prune = false;                        /* some root element has an interval-prune program: launch the PRUNE kernel variants */
-    uint32_t elem_pos_base = 0;                /* elems[ elem_pos_base + k ]: given-order position of entry k of the cost-ordered copy (k_hard_shadow: resume words) */
-    bool leaf_lights = true;                   /* every light element is a plane / sphere */
     bool count_work = false;                   /* ACN_OPT_COUNT_WORK of the current call */
     uint32_t shard_rank = 0, shard_world = 1;  /* ACN_SHARD_SAMPLES of the current call */
     uint64_t launches[ 4 ] = { 0, 0, 0, 0 };   /* walk, shade, finalize, hard-ray kernels */
@@ -225,7 +241,6 @@ struct acn_scene_handle
     std::vector< acn_scene_handle* > early_made;
     int early_status = 0; std::string early_message;
     LaneWorker* worker = nullptr;              /* of a lane */
-    size_t scene_bytes[ 4 ] = { 0, 0, 0, 0 };
     double* d_lane_in = nullptr; size_t lane_in_cap = 0;       /* a lane's gathered positions or rays (doubles) */
     double* d_lane_out = nullptr; size_t lane_out_cap = 0;     /* ... and its results */
     double* d_shard_pos = nullptr; size_t shard_pos_cap = 0;                                /* acn_render_main_pass_shard_dev: the rank's positions */
@@ -379,121 +394,6 @@ __global__ void k_detmath( int op, const double* x, const double* y, double* out
 }
 
 /* ------------------------------------------------------------------------------------------------------------------ */
-/* validation: what the reference would abort on, plus the device limits */
-static int csg_depth( const acn_flat_scene* sc, int node, int d, std::string& err )
-{
-    if( d > 4096 ) { err = "cyclic node graph"; return -1; }
-    const acn_node* n = &sc->nodes[ node ];
-    int m = 0;
-    switch( n->type )
-    {
-        case ACN_PAIR_INSIDE: case ACN_PAIR_OUTSIDE:
-        {
-            int a = csg_depth( sc, n->child0, d + 1, err ), b = csg_depth( sc, n->child1, d + 1, err );
-            if( a < 0 || b < 0 ) return -1;
-            m = 1 + ( a > b ? a : b );
-            break;
-        }
-        case ACN_NEG: case ACN_SCALE:
-        {
-            int a = csg_depth( sc, n->child0, d + 1, err );
-            if( a < 0 ) return -1;
-            m = 1 + a;
-            break;
-        }
-        default: break;
-    }
-    return m;
-}
-
-static int compound_depth( const acn_flat_scene* sc, int node, int d, int* max_csg, std::string& err )
-{
-    if( d > 256 ) { err = "compound nesting too deep / cyclic"; return -1; }
-    const acn_node* n = &sc->nodes[ node ];
-    int m = 1;
-    for( int k = 0; k < n->child1; k++ )
-    {
-        int e = sc->elems[ n->child0 + k ];
-        if( sc->nodes[ e ].type == ACN_COMPOUND )
-        {
-            int c = compound_depth( sc, e, d + 1, max_csg, err );
-            if( c < 0 ) return -1;
-            if( c + 1 > m ) m = c + 1;
-        }
-        else
-        {
-            int c = csg_depth( sc, e, 0, err );
-            if( c < 0 ) return -1;
-            if( c > *max_csg ) *max_csg = c;
-        }
-    }
-    return m;
-}
-
-static int validate( const acn_flat_scene* sc, int* max_csg )
-{
-    if( !sc || !sc->nodes ) return fail( ACN_ERR_ARG, "null scene" );
-    if( sc->abi_version != ACN_ABI_VERSION ) return fail( ACN_ERR_ARG, "abi_version mismatch" );
-    if( sc->n_nodes == 0 || sc->light_root < 0 || sc->matter_root < 0 || ( uint32_t )sc->light_root >= sc->n_nodes ||
-        ( uint32_t )sc->matter_root >= sc->n_nodes ) return fail( ACN_ERR_ARG, "bad root index" );
-    if( sc->n_elems && !sc->elems ) return fail( ACN_ERR_ARG, "null elems" );
-    if( sc->params.experimental_level != 0 ) return fail( ACN_ERR_UNSUPPORTED, "Unsupported experimental level" );   /* scene.c:1004-1007 */
-    if( sc->params.image_height < 2 || sc->params.image_width < 1 ) return fail( ACN_ERR_ARG, "image size" );
-    if( sc->params.trace_depth > 10 * ACN_MAX_PATH_LEVELS + 10 ) return fail( ACN_ERR_UNSUPPORTED, "trace_depth exceeds device path-level limit" );
-    for( uint32_t i = 0; i < sc->n_nodes; i++ )
-    {
-        const acn_node* n = &sc->nodes[ i ];
-        if( n->texture != -1 )
-        {
-            if( n->texture < 0 || ( uint32_t )n->texture >= sc->n_textures || !sc->textures ) return fail( ACN_ERR_ARG, "bad texture index" );
-            const acn_texture* t = &sc->textures[ n->texture ];
-            if( t->kind != ACN_TXM_PLAIN && t->kind != ACN_TXM_CHESS ) return fail( ACN_ERR_ARG, "unknown texture kind" );
-            if( t->kind == ACN_TXM_CHESS && n->type != ACN_PLANE && n->type != ACN_SPHERE && n->type != ACN_DISTANCE )
-                return fail( ACN_ERR_UNSUPPORTED, "object has no projection-function for a chess texture (objects.c:240-245)" );
-        }
-        switch( n->type )
-        {
-            case ACN_PLANE: case ACN_SPHERE: case ACN_SQUAROID: break;
-            case ACN_DISTANCE:
-                if( n->sdf_kind != ACN_SDF_SPHERE && n->sdf_kind != ACN_SDF_TORUS ) return fail( ACN_ERR_UNSUPPORTED, "unknown distance function" );
-                break;
-            case ACN_PAIR_INSIDE: case ACN_PAIR_OUTSIDE:
-                if( n->child1 < 0 || ( uint32_t )n->child1 >= sc->n_nodes || sc->nodes[ n->child1 ].type == ACN_COMPOUND ) return fail( ACN_ERR_ARG, "bad pair child" );
-                /* fallthrough */
-            case ACN_NEG: case ACN_SCALE:
-                if( n->child0 < 0 || ( uint32_t )n->child0 >= sc->n_nodes || sc->nodes[ n->child0 ].type == ACN_COMPOUND ) return fail( ACN_ERR_ARG, "bad child" );
-                break;
-            case ACN_COMPOUND:
-                if( n->child1 < 0 || n->child0 < 0 || ( uint64_t )n->child0 + ( uint64_t )n->child1 > sc->n_elems ) return fail( ACN_ERR_ARG, "bad compound slice" );
-                for( int k = 0; k < n->child1; k++ )
-                {
-                    int e = sc->elems[ n->child0 + k ];
-                    if( e < 0 || ( uint32_t )e >= sc->n_nodes ) return fail( ACN_ERR_ARG, "bad element index" );
-                }
-                break;
-            default: return fail( ACN_ERR_ARG, "unknown node type" );
-        }
-    }
-    const acn_node* light = &sc->nodes[ sc->light_root ];
-    if( light->type != ACN_COMPOUND || sc->nodes[ sc->matter_root ].type != ACN_COMPOUND ) return fail( ACN_ERR_ARG, "roots must be compounds" );
-    for( int k = 0; k < light->child1; k++ )
-    {
-        int t = sc->nodes[ sc->elems[ light->child0 + k ] ].type;
-        if( t == ACN_COMPOUND ) return fail( ACN_ERR_ARG, "light elements must be objects (scene.c:547)" );
-        if( t != ACN_PLANE && t != ACN_SPHERE && t != ACN_PAIR_INSIDE && t != ACN_PAIR_OUTSIDE )
-            return fail( ACN_ERR_NO_FOV, "light object has no fov-function (objects.c:254-258)" );
-    }
-    std::string err;
-    *max_csg = 0;
-    int dl = compound_depth( sc, sc->light_root, 0, max_csg, err );
-    int dm = dl < 0 ? -1 : compound_depth( sc, sc->matter_root, 0, max_csg, err );
-    if( dl < 0 || dm < 0 ) return fail( ACN_ERR_ARG, err );
-    if( dm > ACN_CMP_MAX_DEPTH || dl > ACN_CMP_MAX_DEPTH ) return fail( ACN_ERR_UNSUPPORTED, "compound nesting exceeds device limit" );
-    if( *max_csg > ACN_CSG_MAX_DEPTH ) return fail( ACN_ERR_UNSUPPORTED, "CSG nesting exceeds device limit" );
-    return ACN_OK;
-}
-
-/* ------------------------------------------------------------------------------------------------------------------ */
 /* ABI */
 extern "C" int acn_device_count( void )
 {
@@ -534,8 +434,9 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     if( !out ) return fail( ACN_ERR_ARG, "null out" );
     *out = nullptr;
     int max_csg = 0;
-    int st = validate( scene, &max_csg );
-    if( st != ACN_OK ) return st;
+    std::string err;
+    int st = acn_tables_validate( scene, &max_csg, &err );
+    if( st != ACN_OK ) return fail( st, err );
     int ndev = acn_device_count();
     if( ndev <= 0 ) return fail( ACN_ERR_DEVICE, "no HIP device (libactinon_hip has no CPU fallback)" );
     if( device < 0 || device >= ndev ) return fail( ACN_ERR_ARG, "bad device index" );
@@ -544,7 +445,6 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     acn_scene_handle* h = new acn_scene_handle();
     h->device = device;
-    h->max_csg_depth = max_csg;
     h->tun.read();
     if( h->tun.early_lanes ) early_lanes_begin( h, ( size_t )scene->params.image_width * ( size_t )scene->params.image_height, scene->params.path_samples );
     double t_up[ 4 ] = { 0, 0, 0, 0 };   /* ACN_DEBUG_CHUNKS: stream + events, host-side tables, device copies, the camera kernel */
@@ -571,9 +471,6 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
         h->grid = h->tun.grid ? h->tun.grid : ( unsigned )cus * 4u;
         h->shade_grid = h->tun.shade_grid ? h->tun.shade_grid : ( unsigned )cus * 4u;
         h->walk_grid = h->tun.walk_grid ? h->tun.walk_grid : h->grid;
-        /* path levels: level L shades hits at depth trace_depth - 10 L and spawns the next one while that is > 10 (scene.c:584) */
-        uint64_t td = scene->params.trace_depth;
-        h->n_levels = scene->params.path_samples && td > 10 ? 1 + ( int )( ( td - 10 + 9 ) / 10 ) : 1;
     }
     auto bail = [ & ]( int code ) { acn_scene_free( h ); return code; };
 #define HIP_TRY_H( expr ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) \
@@ -584,408 +481,56 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     /* (a stream costs ~10 ms of host time to make: the second one only where it is used) */
     HIP_TRY_H( hipEventCreate( &h->ev0 ) );
     HIP_TRY_H( hipEventCreate( &h->ev1 ) );
-
-    /* ABI layout -> device layout: geometry (GNode) and shading properties (GMat) split */
-    std::vector< GNode > nodes( scene->n_nodes );
-    std::vector< GMat > mats( scene->n_nodes );
-    for( uint32_t i = 0; i < scene->n_nodes; i++ )
-    {
-        const acn_node& a = scene->nodes[ i ];
-        GNode& g = nodes[ i ];
-        memset( &g, 0, sizeof( g ) );
-        g.type = a.type; g.flags = a.flags; g.child0 = a.child0; g.child1 = a.child1;
-        if( ( a.type == ACN_PAIR_INSIDE || a.type == ACN_PAIR_OUTSIDE ) && !getenv( "ACN_NO_LEAF_PAIRS" ) )
-        {
-            auto simple = [ & ]( int32_t c )
-            {
-                const acn_node* x = &scene->nodes[ c ];
-                if( x->type == ACN_NEG ) x = &scene->nodes[ x->child0 ];
-                return x->type == ACN_PLANE || x->type == ACN_SPHERE || x->type == ACN_SQUAROID;
-            };
-            auto level1 = [ & ]( int32_t c )
-            {
-                const acn_node& x = scene->nodes[ c ];
-                return ( x.type == ACN_PAIR_INSIDE || x.type == ACN_PAIR_OUTSIDE ) && simple( x.child0 ) && simple( x.child1 );
-            };
-            if( simple( a.child0 ) && simple( a.child1 ) ) g.flags |= ACN_GFLAG_LEAF_PAIR;
-            else if( ( simple( a.child0 ) || level1( a.child0 ) ) && ( simple( a.child1 ) || level1( a.child1 ) ) && !getenv( "ACN_NO_PAIR2" ) ) g.flags |= ACN_GFLAG_PAIR2;
-        }
-        memcpy( g.prm, a.prm, sizeof( g.prm ) );
-        memcpy( g.pos, a.pos, sizeof( g.pos ) );
-        memcpy( g.env_pos, a.env_pos, sizeof( g.env_pos ) );
-        g.env_radius = a.env_radius;
-        memcpy( g.rax, a.rax, sizeof( g.rax ) );
-        g.surface_roughness = a.surface_roughness;
-        g.sdf_kind = a.sdf_kind; g.cycles = a.cycles;
-        GMat& m = mats[ i ];
-        memcpy( m.color, a.color, sizeof( m.color ) );
-        m.radiance = a.radiance; m.refractive_index = a.refractive_index;
-        m.fresnel_reflectivity = a.fresnel_reflectivity; m.chromatic_reflectivity = a.chromatic_reflectivity;
-        m.diffuse_reflectivity = a.diffuse_reflectivity; m.sigma = a.sigma;
-        memcpy( m.transparency, a.transparency, sizeof( m.transparency ) );
-        m.texture = a.texture; m.pad_ = 0;
-    }
-    /* surely_outside (acn_device.h) descends a pair tree up to ACN_PRUNE_DEPTH levels to test the envelopes it finds.  How many
-     * levels of a node are worth reading is known here: ACN_GFLAG_PRUNE_LEVELS( flags ) = 0 if neither the node nor any pair
-     * operand within three levels below it has an envelope, else 1 + the depth of the deepest such envelope -- the descent stops
-     * where nothing is left to test instead of reading operands for nothing (a chain of dependent scalar loads per level). */
-    if( !getenv( "ACN_NO_PRUNE_LEVELS" ) )
-    {
-        std::function< int( int32_t, int ) > deepest = [ & ]( int32_t i, int left ) -> int   /* depth of the deepest envelope within `left` levels, -1: none */
-        {
-            const acn_node& a = scene->nodes[ i ];
-            int best = ( a.flags & ACN_NODE_HAS_ENVELOPE ) ? 0 : -1;
-            if( left > 0 && ( a.type == ACN_PAIR_INSIDE || a.type == ACN_PAIR_OUTSIDE ) )
-                for( int32_t c : { a.child0, a.child1 } ) { int d = deepest( c, left - 1 ); if( d >= 0 && d + 1 > best ) best = d + 1; }
-            return best;
-        };
-        for( uint32_t i = 0; i < scene->n_nodes; i++ ) nodes[ i ].flags |= ( uint32_t )( deepest( ( int32_t )i, 3 ) + 1 ) << ACN_GFLAG_PRUNE_LEVELS_SHIFT;
-    }
-    else for( uint32_t i = 0; i < scene->n_nodes; i++ ) nodes[ i ].flags |= 4u << ACN_GFLAG_PRUNE_LEVELS_SHIFT;
-    h->scene_bytes[ 0 ] = sizeof( GNode ) * scene->n_nodes; h->scene_bytes[ 1 ] = sizeof( GMat ) * scene->n_nodes;
-    h->scene_bytes[ 3 ] = sizeof( acn_texture ) * ( scene->n_textures ? scene->n_textures : 1 );
     t_up[ 0 ] = since();
-    HIP_TRY_H( hipMalloc( &h->d_nodes, sizeof( GNode ) * scene->n_nodes ) );
-    HIP_TRY_H( hipMalloc( &h->d_mats, sizeof( GMat ) * scene->n_nodes ) );
-    /* elems[ 0 .. n ) as given; elems[ n .. 2n ) the same slices with each compound's elements ordered by estimated
-     * test cost (any-hit occlusion queries are an OR over the elements, so their order is free; closest-hit queries
-     * keep the given order because ties go to the first element, compound.c:225-243) */
-    std::vector< int32_t > elems2( 2 * ( size_t )scene->n_elems + 1, 0 );
-    /* per entry of the cost-ordered copy: its element's position in the compound's given order (the resume words of the hard-ray
-     * kernels speak of those positions, acn_device.h: root_occluded_rec); appended to elems2 behind everything else */
-    std::vector< int32_t > elem_pos( scene->n_elems, 0 );
-    std::vector< SCEntry > sc_table;   /* pre-order tables of the simple compounds (acn_device.h: simple_compound_hit) */
-    std::vector< double > sc_spheres;
-    {
-        std::vector< double > cost( scene->n_nodes, -1.0 );
-        std::function< double( int32_t ) > node_cost = [ & ]( int32_t i ) -> double
-        {
-            if( cost[ i ] >= 0 ) return cost[ i ];
-            const acn_node& a = scene->nodes[ i ];
-            double c = 1;
-            switch( a.type )
-            {
-                case ACN_PLANE: c = 0.5; break;
-                case ACN_SPHERE: c = 1; break;
-                case ACN_SQUAROID: c = 1.5; break;
-                case ACN_DISTANCE: c = 60; break;            /* sphere tracing, up to `cycles` evaluations */
-                case ACN_NEG: case ACN_SCALE: c = 1 + node_cost( a.child0 ); break;
-                case ACN_PAIR_INSIDE: case ACN_PAIR_OUTSIDE: c = 2 + 1.5 * ( node_cost( a.child0 ) + node_cost( a.child1 ) ); break;
-                case ACN_COMPOUND: c = 1; for( int32_t k = 0; k < a.child1; k++ ) c += node_cost( scene->elems[ a.child0 + k ] ); break;
-                default: break;
-            }
-            return cost[ i ] = c;
-        };
-        for( uint32_t k = 0; k < scene->n_elems; k++ ) elems2[ k ] = elems2[ scene->n_elems + k ] = scene->elems[ k ];
-        for( uint32_t i = 0; i < scene->n_nodes; i++ )
-        {
-            const acn_node& a = scene->nodes[ i ];
-            if( a.type != ACN_COMPOUND || a.child1 < 2 ) continue;
-            int32_t* first = elems2.data() + scene->n_elems + a.child0;
-            int32_t* at = elem_pos.data() + a.child0;
-            for( int32_t k = 0; k < a.child1; k++ ) at[ k ] = k;
-            std::stable_sort( at, at + a.child1, [ & ]( int32_t x, int32_t y ) { return node_cost( scene->elems[ a.child0 + x ] ) < node_cost( scene->elems[ a.child0 + y ] ); } );
-            for( int32_t k = 0; k < a.child1; k++ ) first[ k ] = scene->elems[ a.child0 + at[ k ] ];
-        }
-    }
-    /* elems[ 2n .. 2n + n_nodes ): per node the offset of its interval-prune program (acn_device.h: prune_run) or -1,
-     * followed by the programs.  Only root elements of compounds that are CSG composites with at least
-     * ACN_PRUNE_MIN nodes get one (small trees are cheaper to walk than to pre-test). */
-    h->dev.prune_base = 2 * scene->n_elems;
-    {
-        size_t min_nodes = 32;
-        if( const char* e = getenv( "ACN_PRUNE_MIN" ) ) min_nodes = ( size_t )atoll( e );
-        elems2.resize( 2 * ( size_t )scene->n_elems );
-        elems2.resize( 2 * ( size_t )scene->n_elems + scene->n_nodes, -1 );
-        std::vector< int32_t > size( scene->n_nodes, -1 );
-        std::function< int32_t( int32_t ) > subtree = [ & ]( int32_t i ) -> int32_t
-        {
-            if( size[ i ] >= 0 ) return size[ i ];
-            const acn_node& a = scene->nodes[ i ];
-            int32_t c = 1;
-            if( a.type == ACN_NEG || a.type == ACN_SCALE ) c += subtree( a.child0 );
-            else if( a.type == ACN_PAIR_INSIDE || a.type == ACN_PAIR_OUTSIDE ) c += subtree( a.child0 ) + subtree( a.child1 );
-            return size[ i ] = c;
-        };
-        std::vector< uint32_t > prog;
-        int max_depth = 0;
-        /* postfix code for node i; returns the interval-stack depth it needs.  The child that needs the deeper
-         * stack is emitted first (the combining ops are symmetric), which keeps balanced trees within the budget. */
-        std::function< int( int32_t, int ) > gen = [ & ]( int32_t i, int depth ) -> int
-        {
-            const acn_node& a = scene->nodes[ i ];
-            int need = 1;
-            switch( a.type )
-            {
-                case ACN_PLANE:    prog.push_back( ACN_PO( ACN_PO_PLANE, i ) ); break;
-                case ACN_SPHERE:   prog.push_back( ACN_PO( ACN_PO_SPHERE, i ) ); break;
-                case ACN_SQUAROID: prog.push_back( ACN_PO( ACN_PO_QUAD, i ) ); break;
-                case ACN_NEG:
-                {
-                    const acn_node& c = scene->nodes[ a.child0 ];
-                    need = gen( a.child0, depth );
-                    bool bare_plane = c.type == ACN_PLANE && !( c.flags & ACN_NODE_HAS_ENVELOPE ) && a.child0 != 0;
-                    prog.push_back( ACN_PO( ACN_PO_NEG, bare_plane ? a.child0 : 0 ) );
-                }
-                break;
-                case ACN_PAIR_INSIDE: case ACN_PAIR_OUTSIDE:
-                {
-                    if( depth >= max_depth ) { prog.push_back( ACN_PO( ACN_PO_ALL, 0 ) ); break; }
-                    /* n-ary view: chains of the same pair type without envelopes in between are one intersection /
-                     * union (the sets H and S do not depend on how the reference's tree is balanced); operands are
-                     * combined one after the other, the one needing the deepest stack first */
-                    std::vector< int32_t > items, todo{ a.child1, a.child0 };
-                    while( !todo.empty() )
-                    {
-                        int32_t c = todo.back(); todo.pop_back();
-                        const acn_node& cn = scene->nodes[ c ];
-                        if( cn.type == a.type && !( cn.flags & ACN_NODE_HAS_ENVELOPE ) ) { todo.push_back( cn.child1 ); todo.push_back( cn.child0 ); }
-                        else items.push_back( c );
-                    }
-                    size_t mark = prog.size();
-                    std::vector< std::pair< int, std::vector< uint32_t > > > code;
-                    for( int32_t c : items )
-                    {
-                        int d = gen( c, depth + 1 );
-                        code.emplace_back( d, std::vector< uint32_t >( prog.begin() + mark, prog.end() ) );
-                        prog.resize( mark );
-                    }
-                    std::stable_sort( code.begin(), code.end(), []( const std::pair< int, std::vector< uint32_t > >& x, const std::pair< int, std::vector< uint32_t > >& y ) { return x.first > y.first; } );
-                    need = code[ 0 ].first;
-                    for( size_t k = 0; k < code.size(); k++ )
-                    {
-                        prog.insert( prog.end(), code[ k ].second.begin(), code[ k ].second.end() );
-                        if( k > 0 )
-                        {
-                            prog.push_back( ACN_PO( a.type == ACN_PAIR_INSIDE ? ACN_PO_AND : ACN_PO_OR, 0 ) );
-                            if( 1 + code[ k ].first > need ) need = 1 + code[ k ].first;
-                        }
-                    }
-                    if( need > ACN_PRUNE_STACK ) { prog.resize( mark ); prog.push_back( ACN_PO( ACN_PO_ALL, 0 ) ); need = 1; }
-                }
-                break;
-                default: prog.push_back( ACN_PO( ACN_PO_ALL, 0 ) ); break;
-            }
-            if( a.flags & ACN_NODE_HAS_ENVELOPE ) prog.push_back( ACN_PO( ACN_PO_ENV, i ) );
-            return need;
-        };
-        const size_t max_ops = 256;
-        for( uint32_t i = 0; i < scene->n_nodes; i++ )
-        {
-            const acn_node& c = scene->nodes[ i ];
-            if( c.type != ACN_COMPOUND ) continue;
-            for( int32_t k = 0; k < c.child1; k++ )
-            {
-                int32_t e = scene->elems[ c.child0 + k ];
-                const acn_node& a = scene->nodes[ e ];
-                if( !( a.type == ACN_PAIR_INSIDE || a.type == ACN_PAIR_OUTSIDE ) ) continue;
-                if( ( size_t )subtree( e ) < min_nodes || elems2[ h->dev.prune_base + e ] >= 0 ) continue;
-                for( max_depth = 12; max_depth >= 1; max_depth-- )   /* the deepest expansion that fits the budget */
-                {
-                    prog.clear();
-                    gen( e, 0 );
-                    if( prog.size() < max_ops ) break;
-                }
-                if( max_depth < 1 ) continue;
-                prog.push_back( ACN_PO( ACN_PO_END, 0 ) );
-                elems2[ h->dev.prune_base + e ] = ( int32_t )elems2.size();
-                h->prune = true;
-                for( uint32_t w : prog ) elems2.push_back( ( int32_t )w );
-            }
-        }
-        /* simple compounds (acn_device.h: simple_compound_hit): pre-order ( node, skip ) tables for root elements that
-         * are compounds over nothing but compounds and simple leaves; the same per-node offset table locates them */
-        if( !getenv( "ACN_NO_SIMPLE_COMPOUNDS" ) )
-        {
-            std::vector< SCEntry >& sct = sc_table;
-            std::vector< int8_t > simple( scene->n_nodes, -1 );
-            std::function< bool( int32_t ) > is_simple = [ & ]( int32_t i ) -> bool
-            {
-                if( simple[ i ] >= 0 ) return simple[ i ] != 0;
-                const acn_node& a = scene->nodes[ i ];
-                bool ok = a.type == ACN_PLANE || a.type == ACN_SPHERE || a.type == ACN_SQUAROID;
-                if( a.type == ACN_COMPOUND )
-                {
-                    ok = true;
-                    for( int32_t k = 0; k < a.child1 && ok; k++ ) ok = is_simple( scene->elems[ a.child0 + k ] );
-                }
-                simple[ i ] = ok ? 1 : 0;
-                return ok;
-            };
-            const bool no_cull = getenv( "ACN_NO_SC_CULL" ) != nullptr;
-            size_t n_bounding = 0, n_reversed = 0;
-            const bool no_rev = getenv( "ACN_NO_SC_REVERSED" ) != nullptr;
-            std::vector< int32_t > sph_of( scene->n_nodes, -1 );      /* sphere record of a leaf, flags of an entry: the reversed table reuses them */
-            std::vector< uint32_t > flags_of( scene->n_nodes, 0u );
-            double order_dir[ 3 ] = { 0, 0, 0 };                      /* along which the children of the compounds at hand come later, summed over the compounds */
-            auto centre = [ & ]( const acn_node& x, int c ) { return ( x.flags & ACN_NODE_HAS_ENVELOPE ) ? x.env_pos[ c ] : x.pos[ c ]; };
-            std::function< void( int32_t, bool ) > emit = [ & ]( int32_t c, bool reversed )   /* children of compound c, depth first */
-            {
-                const acn_node& a = scene->nodes[ c ];
-                if( !reversed && a.child1 > 1 )
-                {
-                    double mean[ 3 ] = { 0, 0, 0 };
-                    for( int32_t k = 0; k < a.child1; k++ ) for( int x = 0; x < 3; x++ ) mean[ x ] += centre( scene->nodes[ scene->elems[ a.child0 + k ] ], x ) / a.child1;
-                    for( int32_t k = 0; k < a.child1; k++ ) for( int x = 0; x < 3; x++ )
-                        order_dir[ x ] += ( k - 0.5 * ( a.child1 - 1 ) ) * ( centre( scene->nodes[ scene->elems[ a.child0 + k ] ], x ) - mean[ x ] );
-                }
-                for( int32_t kk = 0; kk < a.child1; kk++ )
-                {
-                    const int32_t k = reversed ? a.child1 - 1 - kk : kk;
-                    int32_t e = scene->elems[ a.child0 + k ];
-                    const acn_node& en = scene->nodes[ e ];
-                    size_t at = sct.size();
-                    SCEntry rec;
-                    memcpy( rec.env_pos, en.env_pos, sizeof( rec.env_pos ) );
-                    rec.env_radius = en.env_radius; rec.node = e; rec.skip = 0; rec.type = en.type; rec.flags = en.flags & ACN_NODE_HAS_ENVELOPE;
-                    sct.push_back( rec );
-                    if( en.type == ACN_COMPOUND ) emit( e, reversed );
-                    sct[ at ].skip = ( int32_t )sct.size();   /* the entry behind e's subtree */
-                    if( reversed )
-                    {
-                        sct[ at ].flags = flags_of[ e ];
-                        if( en.type == ACN_SPHERE ) sct[ at ].skip = sph_of[ e ];
-                        continue;
-                    }
-                    if( ( rec.flags & ACN_NODE_HAS_ENVELOPE ) && !no_cull )   /* does the envelope contain every leaf below? (simple_compound_hit: CULL) */
-                    {
-                        bool inside = true;
-                        for( size_t j = at; j < sct.size() && inside; j++ )
-                        {
-                            const acn_node& ln = scene->nodes[ sct[ j ].node ];
-                            if( ln.type == ACN_COMPOUND ) continue;
-                            if( ln.type != ACN_SPHERE ) { inside = false; break; }
-                            double d2 = 0;
-                            for( int x = 0; x < 3; x++ ) d2 += ( ln.pos[ x ] - en.env_pos[ x ] ) * ( ln.pos[ x ] - en.env_pos[ x ] );
-                            inside = sqrt( d2 ) + fabs( ln.prm[ 0 ] ) <= fabs( en.env_radius ) * ( 1.0 - 1E-9 );
-                        }
-                        if( inside ) { sct[ at ].flags |= ACN_SC_BOUNDING; n_bounding++; }
-                    }
-                    if( en.type == ACN_SPHERE )   /* a leaf never follows its link: it names the sphere's record instead */
-                    {
-                        sph_of[ e ] = ( int32_t )( sc_spheres.size() / 4 );
-                        sct[ at ].skip = sph_of[ e ];
-                        sct[ at ].flags |= ACN_SC_SPHERE | ( en.surface_roughness > 0 ? ACN_SC_ROUGH : 0u );
-                        for( int x = 0; x < 3; x++ ) sc_spheres.push_back( en.pos[ x ] );
-                        sc_spheres.push_back( en.prm[ 0 ] );
-                    }
-                    flags_of[ e ] = sct[ at ].flags;
-                }
-            };
-            for( int root : { scene->light_root, scene->matter_root } )
-            {
-                const acn_node& r = scene->nodes[ root ];
-                for( int32_t k = 0; k < r.child1; k++ )
-                {
-                    int32_t e = scene->elems[ r.child0 + k ];
-                    if( scene->nodes[ e ].type != ACN_COMPOUND || !is_simple( e ) || elems2[ h->dev.prune_base + e ] >= 0 ) continue;
-                    elems2[ h->dev.prune_base + e ] = ( int32_t )elems2.size();
-                    elems2.push_back( ( int32_t )sct.size() );     /* first entry */
-                    size_t first = sct.size();
-                    order_dir[ 0 ] = order_dir[ 1 ] = order_dir[ 2 ] = 0;
-                    emit( e, false );
-                    const size_t count = sct.size() - first;
-                    elems2.push_back( ( int32_t )count );          /* entry count */
-                    /* the same subtree with the children of every compound in reverse order, for rays that run against the order of the
-                     * first (simple_compound_hit: the walk culls more the sooner it meets the near leaves); -1: none */
-                    const double len = sqrt( order_dir[ 0 ] * order_dir[ 0 ] + order_dir[ 1 ] * order_dir[ 1 ] + order_dir[ 2 ] * order_dir[ 2 ] );
-                    if( !no_rev && !no_cull && count >= 64 && len > 0 )
-                    {
-                        elems2.push_back( ( int32_t )sct.size() );
-                        elems2.push_back( ( int32_t )( sc_spheres.size() / 4 ) );
-                        for( int x = 0; x < 3; x++ ) sc_spheres.push_back( order_dir[ x ] / len );
-                        sc_spheres.push_back( 0.0 );
-                        emit( e, true );
-                        n_reversed += count;
-                    }
-                    else { elems2.push_back( -1 ); elems2.push_back( 0 ); }
-                    nodes[ e ].flags |= ACN_GFLAG_SIMPLE_COMPOUND;
-                    h->prune = true;   /* the extras kernel variants */
-                }
-            }
-            if( getenv( "ACN_VERBOSE" ) && sct.size() ) fprintf( stderr, "actinon_hip: simple compounds: %zu entries, %zu with a verified bounding envelope, %zu again in reversed order\n", sct.size() - n_reversed, n_bounding, n_reversed );
-        }
-        elems2.push_back( 0 );
-    }
-    h->elem_pos_base = ( uint32_t )elems2.size();
-    elems2.insert( elems2.end(), elem_pos.begin(), elem_pos.end() );
-    elems2.push_back( 0 );
-    h->scene_bytes[ 2 ] = sizeof( int32_t ) * elems2.size();
-    HIP_TRY_H( hipMalloc( &h->d_elems, sizeof( int32_t ) * elems2.size() ) );
-    HIP_TRY_H( hipMalloc( &h->d_sc_table, sizeof( SCEntry ) * ( sc_table.size() ? sc_table.size() : 1 ) ) );
+    acn_scene_tables t;   /* everything the traversal shortcuts read, built on the host alone (acn_tables.cpp) */
+    acn_tables_build( scene, h->tun.tables, &t );
     t_up[ 1 ] = since();
-    if( sc_table.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_table, sc_table.data(), sizeof( SCEntry ) * sc_table.size(), hipMemcpyHostToDevice ) );
-    h->dev.sc_table = h->d_sc_table;
-    HIP_TRY_H( hipMalloc( &h->d_sc_spheres, sizeof( double ) * ( sc_spheres.size() ? sc_spheres.size() : 4 ) ) );
-    if( sc_spheres.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_spheres, sc_spheres.data(), sizeof( double ) * sc_spheres.size(), hipMemcpyHostToDevice ) );
-    h->dev.sc_spheres = h->d_sc_spheres;
-    /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
-     * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
-     * and divergent (nested compounds, CSG objects with prune programs: the scenes of the "extras" kernel variants).
-     * Measured, 4 lanes: wine_glass 1080p (200 / 64 samples) 79.8 ms narrow, 85.2 wide from 33 samples; many_spheres
-     * 1080p p256 every 16th pixel 3.94 s narrow, 2.90 s wide; diamond 1080p p512 4.58 s narrow, 4.05 s wide. */
-    h->dev.class0_min = h->tun.class0_min ? h->tun.class0_min : ( h->prune ? 32u : 255u );
-    HIP_TRY_H( hipMalloc( &h->d_textures, sizeof( acn_texture ) * ( scene->n_textures ? scene->n_textures : 1 ) ) );
-    if( scene->n_textures ) HIP_TRY_H( hipMemcpy( h->d_textures, scene->textures, sizeof( acn_texture ) * scene->n_textures, hipMemcpyHostToDevice ) );
+    acn_scene_handle::Resident& r = h->scene;
+    r.max_csg_depth = max_csg;
+    r.lds_bytes = t.lds_bytes; r.lds_stack_bytes = t.lds_stack_bytes;
+    r.prune = t.prune; r.leaf_lights = t.leaf_lights; r.elem_pos_base = t.elem_pos_base;
+    r.n_levels = t.n_levels; r.n_lights = t.n_lights;
+    const size_t n_tex = scene->n_textures ? scene->n_textures : 1, n_sc = t.sc_table.size() ? t.sc_table.size() : 1, n_sph = t.sc_spheres.size() ? t.sc_spheres.size() : 4;
+    r.scene_bytes[ 0 ] = sizeof( GNode ) * t.nodes.size(); r.scene_bytes[ 1 ] = sizeof( GMat ) * t.mats.size();
+    r.scene_bytes[ 2 ] = sizeof( int32_t ) * t.elems.size(); r.scene_bytes[ 3 ] = sizeof( acn_texture ) * n_tex;
+    HIP_TRY_H( hipMalloc( &r.d_nodes, r.scene_bytes[ 0 ] ) );
+    HIP_TRY_H( hipMalloc( &r.d_mats, r.scene_bytes[ 1 ] ) );
+    HIP_TRY_H( hipMalloc( &r.d_elems, r.scene_bytes[ 2 ] ) );
+    HIP_TRY_H( hipMalloc( &h->d_sc_table, sizeof( SCEntry ) * n_sc ) );
+    if( t.sc_table.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_table, t.sc_table.data(), sizeof( SCEntry ) * t.sc_table.size(), hipMemcpyHostToDevice ) );
+    HIP_TRY_H( hipMalloc( &h->d_sc_spheres, sizeof( double ) * n_sph ) );
+    if( t.sc_spheres.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_spheres, t.sc_spheres.data(), sizeof( double ) * t.sc_spheres.size(), hipMemcpyHostToDevice ) );
+    HIP_TRY_H( hipMalloc( &r.d_textures, r.scene_bytes[ 3 ] ) );
+    if( scene->n_textures ) HIP_TRY_H( hipMemcpy( r.d_textures, scene->textures, sizeof( acn_texture ) * scene->n_textures, hipMemcpyHostToDevice ) );
     HIP_TRY_H( hipMalloc( &h->d_counters, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
     HIP_TRY_H( hipMemset( h->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
     HIP_TRY_H( hipMalloc( &h->d_counters_keep, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
     HIP_TRY_H( hipMalloc( &h->d_counts, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
     HIP_TRY_H( hipHostMalloc( &h->h_counts, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
-    HIP_TRY_H( hipMemcpy( h->d_nodes, nodes.data(), sizeof( GNode ) * scene->n_nodes, hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMemcpy( h->d_mats, mats.data(), sizeof( GMat ) * scene->n_nodes, hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMemcpy( h->d_elems, elems2.data(), sizeof( int32_t ) * elems2.size(), hipMemcpyHostToDevice ) );
-    h->dev.nodes = ( NodeP )h->d_nodes; h->dev.gnodes = ( NodeP )h->d_nodes;
-    h->dev.mats = ( MatP )h->d_mats;
-    h->dev.elems = ( ElemP )h->d_elems;
-    h->dev.textures = ( TexP )h->d_textures;
+    HIP_TRY_H( hipMemcpy( r.d_nodes, t.nodes.data(), r.scene_bytes[ 0 ], hipMemcpyHostToDevice ) );
+    HIP_TRY_H( hipMemcpy( r.d_mats, t.mats.data(), r.scene_bytes[ 1 ], hipMemcpyHostToDevice ) );
+    HIP_TRY_H( hipMemcpy( r.d_elems, t.elems.data(), r.scene_bytes[ 2 ], hipMemcpyHostToDevice ) );
+    HIP_TRY_H( hipMemset( h->d_counts, 0, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
+    h->dev.nodes = ( NodeP )r.d_nodes; h->dev.gnodes = ( NodeP )r.d_nodes;
+    h->dev.mats = ( MatP )r.d_mats;
+    h->dev.elems = ( ElemP )r.d_elems;
+    h->dev.textures = ( TexP )r.d_textures;
+    h->dev.sc_table = h->d_sc_table;
+    h->dev.sc_spheres = h->d_sc_spheres;
+    h->dev.prune_base = t.prune_base;
     h->dev.light_root = scene->light_root;
     h->dev.matter_root = scene->matter_root;
     h->dev.n_nodes = scene->n_nodes;
     h->dev.n_elems = scene->n_elems;
     h->dev.prm = scene->params;
-    {
-        const acn_node& lr = scene->nodes[ scene->light_root ];
-        h->n_lights = lr.child1 > 0 ? ( size_t )lr.child1 : 1;
-        for( int k = 0; k < lr.child1; k++ )
-        {
-            int t = scene->nodes[ scene->elems[ lr.child0 + k ] ].type;
-            if( t != ACN_PLANE && t != ACN_SPHERE ) h->leaf_lights = false;
-        }
-    }
-    {
-        /* LDS plan of the machine kernels (160 KB per CU, 4 blocks of 256 lanes wanted per CU => 40 KB per block):
-         *   nodes + stacks   when the node array is small (<= 8 KB: wine_glass 6 KB);
-         *   nodes only       up to 40 KB (diamond): staging the per-lane node reads pays more than the stacks;
-         *   stacks only      beyond (the node array stays in global memory / L2).
-         * ACN_LDS_MAX (bytes of nodes that may be staged) and ACN_LDS_STACK=0|1 override. */
-        size_t lds_max = 40960;
-        /* Round 4: nodes are staged only for scenes whose roots hold GENERIC nested compounds (hanging_lamps_in_row: compounds of
-         * CSG objects) -- the one traversal left that reads nodes per lane (compound_ray_hit_dev).  The lock-step machines read
-         * every node through scalar loads from global memory whatever is staged, and the leaves a root loop tests in line are
-         * better off with scalar loads too: a staged node comes back through ds_read into VGPRs (1080p wine_glass 51.8 -> 50.6 ms
-         * without staging, profiles/r04); the diamond's 40 KB of nodes had cost it the LDS stacks of its CSG machines. */
-        bool generic_compound = false;
-        for( int root : { scene->light_root, scene->matter_root } )
-        {
-            const acn_node& r = scene->nodes[ root ];
-            for( int32_t k = 0; k < r.child1; k++ )
-            {
-                const int32_t e = scene->elems[ r.child0 + k ];
-                if( scene->nodes[ e ].type == ACN_COMPOUND && !( nodes[ e ].flags & ACN_GFLAG_SIMPLE_COMPOUND ) ) generic_compound = true;
-            }
-        }
-        if( !generic_compound ) lds_max = 0;
-        if( const char* e = getenv( "ACN_LDS_MAX" ) ) lds_max = ( size_t )atoll( e );
-        size_t need = sizeof( GNode ) * ( size_t )scene->n_nodes;
-        /* every machine kernel owns the stacks and the parked ray origins of its workgroup; nodes are staged in front of them
-         * only if all of it fits 40 KB (four workgroups per CU) */
-        h->lds_bytes = need <= lds_max && need + ACN_LDS_STACK_BYTES + ACN_LDS_ORG_BYTES <= 40960 ? need : 0;
-        h->lds_stack_bytes = ACN_LDS_STACK_BYTES + ACN_LDS_ORG_BYTES;
-    }
     h->dev.flags = h->d_counts + QC_FLAGS;
-    h->dev.lds_stack = h->lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
-    HIP_TRY_H( hipMemset( h->d_counts, 0, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
+    h->dev.lds_stack = r.lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
+    /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
+     * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
+     * and divergent (nested compounds, CSG objects with prune programs: the scenes of the "extras" kernel variants).
+     * Measured, 4 lanes: wine_glass 1080p (200 / 64 samples) 79.8 ms narrow, 85.2 wide from 33 samples; many_spheres
+     * 1080p p256 every 16th pixel 3.94 s narrow, 2.90 s wide; diamond 1080p p512 4.58 s narrow, 4.05 s wide. */
+    h->dev.class0_min = h->tun.class0_min ? h->tun.class0_min : ( r.prune ? 32u : 255u );
     /* camera basis on the device so that it shares the device's arithmetic */
     {
         M3* d_rot = nullptr; double* d_uf = nullptr;
@@ -1045,10 +590,10 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( h->d_lens_rad ) hipFree( h->d_lens_rad );
     if( !h->is_lane )   /* a lane borrows the resident scene of its parent */
     {
-        if( h->d_nodes ) hipFree( h->d_nodes );
-        if( h->d_mats ) hipFree( h->d_mats );
-        if( h->d_elems ) hipFree( h->d_elems );
-        if( h->d_textures ) hipFree( h->d_textures );
+        if( h->scene.d_nodes ) hipFree( h->scene.d_nodes );
+        if( h->scene.d_mats ) hipFree( h->scene.d_mats );
+        if( h->scene.d_elems ) hipFree( h->scene.d_elems );
+        if( h->scene.d_textures ) hipFree( h->scene.d_textures );
         if( h->d_sc_table ) hipFree( h->d_sc_table );
         if( h->d_sc_spheres ) hipFree( h->d_sc_spheres );
     }
@@ -1104,7 +649,7 @@ static int ensure_workspace( acn_scene_handle* h, size_t n )
     {
         /* starter set: 2^20 records per queue (the deferred-shadow queue twice that), less for a call of a few positions */
         const size_t s = h->dev.prm.path_samples ? h->dev.prm.path_samples : 1;
-        const size_t per_pos = ( s + 2 ) * ( s > 16 ? s / 16 : 1 ) + ( size_t )h->dev.prm.direct_samples * h->n_lights;
+        const size_t per_pos = ( s + 2 ) * ( s > 16 ? s / 16 : 1 ) + ( size_t )h->dev.prm.direct_samples * h->scene.n_lights;
         size_t recs = n * per_pos + 65536;
         if( recs > ACN_STARTER_RECORDS ) recs = ACN_STARTER_RECORDS;
         size_t per_rec = wq_bytes[ WQ_HARD_SHADOW ];
@@ -1207,13 +752,13 @@ static int stage_end( acn_scene_handle* h, hipStream_t stream )
 static SceneArgs scene_args( const acn_scene_handle* h )
 {
     SceneArgs s;
-    s.dev = h->dev; s.nodes = h->d_nodes; s.mats = h->d_mats; s.elems = h->d_elems; s.textures = h->d_textures; s.elem_pos_base = h->elem_pos_base;
+    s.dev = h->dev; s.nodes = h->scene.d_nodes; s.mats = h->scene.d_mats; s.elems = h->scene.d_elems; s.textures = h->scene.d_textures; s.elem_pos_base = h->scene.elem_pos_base;
     return s;
 }
 static KernelFlags kernel_flags( const acn_scene_handle* h )
 {
     KernelFlags f;
-    f.count = h->count_work; f.leaf_lights = h->leaf_lights; f.lds_nodes = h->lds_bytes != 0; f.prune = h->prune;
+    f.count = h->count_work; f.leaf_lights = h->scene.leaf_lights; f.lds_nodes = h->scene.lds_bytes != 0; f.prune = h->scene.prune;
     return f;
 }
 /* the workspace as the kernels of path level `level` see it */
@@ -1237,7 +782,7 @@ static LevelQ level_queues( const acn_scene_handle* h, int level )
     q.emit_terms = sharded && h->shard_rank != 0 ? 0u : 1u;
     return q;
 }
-static size_t machine_lds_bytes( const acn_scene_handle* h ) { return h->lds_bytes + h->lds_stack_bytes; }
+static size_t machine_lds_bytes( const acn_scene_handle* h ) { return h->scene.lds_bytes + h->scene.lds_stack_bytes; }
 
 /* launches of k_walk for path level `level`: ACN_WALK_PASSES, but no more than the hits of the level have depth left */
 static uint32_t walk_passes_of_level( const acn_scene_handle* h, int level )
@@ -1282,7 +827,7 @@ static int render_chunk( acn_scene_handle* h, const Primary& prim, uint32_t base
     *overflow = 0;
     *dead_share = 0;
     for( int q = 0; q < WQ_N; q++ ) fill[ q ] = 0;
-    const int levels = h->n_levels;
+    const int levels = h->scene.n_levels;
     const KernelFlags f = kernel_flags( h );
     const SceneArgs s = scene_args( h );
     const size_t lds = machine_lds_bytes( h );
@@ -1432,7 +977,7 @@ static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipS
     /* as many positions as the starter queues hold by the guess launch_render makes for a first chunk, 4096 at most */
     const size_t s = h->dev.prm.path_samples ? h->dev.prm.path_samples : 1;
     size_t want = ( size_t )( ( double )h->ws.cap[ WQ_CHILDREN ] / ( ( double )( s + 2 ) * ( s > 64 ? ( double )s / 64.0 : 1.0 ) ) );
-    const size_t by_shadow = ( size_t )( ( double )h->ws.cap[ WQ_HARD_SHADOW ] / ( 0.25 * ( double )( h->dev.prm.direct_samples * h->n_lights + s ) + 4.0 ) );
+    const size_t by_shadow = ( size_t )( ( double )h->ws.cap[ WQ_HARD_SHADOW ] / ( 0.25 * ( double )( h->dev.prm.direct_samples * h->scene.n_lights + s ) + 4.0 ) );
     if( want > by_shadow ) want = by_shadow;
     if( want > 4096 ) want = 4096;
     /* (the guess is ten times what the lamp scenes need at path_samples 1024, where it allowed 63 positions: no sample at all, and
@@ -1465,7 +1010,7 @@ static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipS
         /* the records the sample left in each queue, exactly (marks minus dead slots; the fullest level counts, the queues are
          * the levels' in turn), plus a quarter for what a sample of a few thousand positions does not see */
         double live[ WQ_N ] = { 0, 0, 0, 0, 0 };
-        for( int level = 0; level < h->n_levels; level++ )
+        for( int level = 0; level < h->scene.n_levels; level++ )
         {
             const uint32_t* c = h->h_counts + ( size_t )level * QC_N;
             auto up = [ & ]( int q, double v ) { if( v > live[ q ] ) live[ q ] = v; };
@@ -1559,7 +1104,7 @@ static int launch_render( acn_scene_handle* h, const Primary& prim, size_t n, do
          * side by factors, not orders of magnitude (an overflow costs one small chunk): path-sample hits ~ path_samples per
          * position, squared from 64 samples on (two nested levels); a quarter of the direct-light samples deferred */
         chunk = ( size_t )( ( double )h->ws.cap[ WQ_CHILDREN ] / ( ( double )( s + 2 ) * ( s > 64 ? ( double )s / 64.0 : 1.0 ) ) );
-        const size_t by_shadow = ( size_t )( ( double )h->ws.cap[ WQ_HARD_SHADOW ] / ( 0.25 * ( double )( h->dev.prm.direct_samples * h->n_lights + s ) + 4.0 ) );
+        const size_t by_shadow = ( size_t )( ( double )h->ws.cap[ WQ_HARD_SHADOW ] / ( 0.25 * ( double )( h->dev.prm.direct_samples * h->scene.n_lights + s ) + 4.0 ) );
         if( chunk > by_shadow ) chunk = by_shadow;
         if( chunk > 32768 ) chunk = 32768;
     }
@@ -1771,13 +1316,9 @@ static void bind_lane( const acn_scene_handle* parent, int lanes, acn_scene_hand
 {
     l->budget_div = ( size_t )lanes;
     l->dev = parent->dev;
-    l->d_nodes = parent->d_nodes; l->d_mats = parent->d_mats; l->d_elems = parent->d_elems; l->d_textures = parent->d_textures;
-    l->scene_bytes[ 0 ] = parent->scene_bytes[ 0 ]; l->scene_bytes[ 1 ] = parent->scene_bytes[ 1 ]; l->scene_bytes[ 2 ] = parent->scene_bytes[ 2 ]; l->scene_bytes[ 3 ] = parent->scene_bytes[ 3 ];
-    l->max_csg_depth = parent->max_csg_depth;
-    l->lds_bytes = parent->lds_bytes; l->lds_stack_bytes = parent->lds_stack_bytes;
-    l->prune = parent->prune; l->leaf_lights = parent->leaf_lights; l->elem_pos_base = parent->elem_pos_base;
-    l->tun = parent->tun; l->cus = parent->cus; l->n_levels = parent->n_levels;
-    l->workspace_budget = parent->workspace_budget; l->n_lights = parent->n_lights;
+    l->scene = parent->scene;
+    l->tun = parent->tun; l->cus = parent->cus;
+    l->workspace_budget = parent->workspace_budget;
     /* Round 4: six lanes on grids of ONE workgroup per CU (k_shade: one and a half) instead of four lanes on two.  With k_walk at
      * four waves per SIMD a grid of 256 workgroups is resident at once, and six shorter chains fill each other's tails better than
      * four: 1080p 50.2 -> 49.1 ms, c2 26.4 -> 25.0, and the share one of 8 GPUs gets 12.25 -> 11.4 ms (profiles/r04/ab_lanes6_*).
@@ -2140,7 +1681,7 @@ static int surface_dev( acn_scene_handle* h, const double* d_rays, const double*
     }
     SceneArgs s = scene_args( h );
     s.dev.flags = h->d_surface_flags;   /* the pipeline's word stays the pipeline's */
-    acn_launch_surface( mode, h->lds_bytes != 0, machine_lds_bytes( h ), stream, s, d_rays, d_pos_xy, n, d_out );
+    acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h ), stream, s, d_rays, d_pos_xy, n, d_out );
     HIP_TRY( hipGetLastError() );
     if( !( opts && opts->stream ) )
     {
@@ -2596,7 +2137,7 @@ int acn_query_env( acn_scene_handle* h, QueryEnv* q )
 {
     if( !h || !q ) return fail( ACN_ERR_ARG, "null argument" );
     HIP_TRY( hipSetDevice( h->device ) );
-    q->s = scene_args( h ); q->lds_node_bytes = h->lds_bytes; q->lds_stack_bytes = h->lds_stack_bytes; q->stream = h->stream;
+    q->s = scene_args( h ); q->lds_node_bytes = h->scene.lds_bytes; q->lds_stack_bytes = h->scene.lds_stack_bytes; q->stream = h->stream;
     return ACN_OK;
 }
 int acn_query_fail( int code, const char* msg ) { return fail( code, msg ); }
