@@ -29,7 +29,9 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_re
                "acn_render_rays", "acn_render_rays_dev", "acn_camera_rays", "acn_camera_rays_dev",
                "acn_surface_rays", "acn_surface_rays_dev", "acn_surface_positions", "acn_surface_positions_dev",
                "acn_denoise", "acn_denoise_dev",
-               "acn_lens_rays", "acn_lens_rays_dev", "acn_render_lens", "acn_render_lens_dev", "acn_render_lens_main_pass_dev"]
+               "acn_lens_rays", "acn_lens_rays_dev", "acn_render_lens", "acn_render_lens_dev", "acn_render_lens_main_pass_dev",
+               "acn_render_lens_stats", "acn_render_lens_stats_dev", "acn_render_lens_stats_main_pass_dev", "acn_lens_stats_merge",
+               "acn_lens_stats_merge_dev", "acn_lens_stats_resolve_dev", "acn_denoise_stats", "acn_denoise_stats_dev"]
 # symbols declared by include/acn_scene.h
 HOST_SYMBOLS = ["acn_rotx", "acn_roty", "acn_rotz", "acn_obj_plane_s_create", "acn_obj_sphere_s_create",
                 "acn_obj_squaroid_s_create_squaroid", "acn_obj_squaroid_s_create_ellipsoid",
@@ -77,6 +79,14 @@ hip.acn_lens_rays_dev.argtypes = [vp, vp, C.c_size_t, P(abi.LensParams), C.c_uin
 hip.acn_render_lens.argtypes = [vp, vp, C.c_size_t, P(abi.LensParams), vp, P(abi.RenderOpts)]
 hip.acn_render_lens_dev.argtypes = [vp, vp, C.c_size_t, P(abi.LensParams), vp, P(abi.RenderOpts)]
 hip.acn_render_lens_main_pass_dev.argtypes = [vp, C.c_size_t, C.c_size_t, P(abi.LensParams), vp, P(abi.RenderOpts)]
+hip.acn_render_lens_stats.argtypes = [vp, vp, C.c_size_t, P(abi.LensParams), vp, vp, P(abi.RenderOpts)]
+hip.acn_render_lens_stats_dev.argtypes = [vp, vp, C.c_size_t, P(abi.LensParams), vp, vp, P(abi.RenderOpts)]
+hip.acn_render_lens_stats_main_pass_dev.argtypes = [vp, C.c_size_t, C.c_size_t, P(abi.LensParams), vp, vp, P(abi.RenderOpts)]
+for _n in ["acn_lens_stats_merge", "acn_lens_stats_merge_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, vp, P(abi.RenderOpts)]
+hip.acn_lens_stats_resolve_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, P(abi.RenderOpts)]
+for _n in ["acn_denoise_stats", "acn_denoise_stats_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, P(abi.DenoiseParams), vp, P(abi.RenderOpts)]
 hip.acn_resolve_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, P(abi.RenderOpts)]
 hip.acn_last_kernel_ms.argtypes = [vp, P(C.c_double)]
 hip.acn_last_stage_ms.argtypes = [vp, P(C.c_double), C.c_int]

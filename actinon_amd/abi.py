@@ -24,6 +24,10 @@ ACN_LENS_JITTER = 1
 ACN_LENS_DEFAULT_SAMPLES, ACN_LENS_MAX_SAMPLES = 16, 4096
 ACN_LENS_SEED = 2718281828
 
+# lens sample statistics (acn_render_lens_stats, acn_lens_stats_*, acn_denoise_stats): doubles per record, the floor of `noise`
+ACN_STATS_STRIDE = 8
+ACN_STATS_NOISE_FLOOR = 0.01
+
 ACN_OK, ACN_ERR_ARG, ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV, ACN_ERR_DEVICE, ACN_ERR_CANCELLED = 0, -1, -2, -3, -4, -5
 
 NODE_TYPES = {1: "plane", 2: "sphere", 3: "squaroid", 4: "distance", 5: "pair_inside", 6: "pair_outside",

@@ -86,6 +86,12 @@ void acn_launch_surface( uint32_t mode, bool lds_nodes, size_t lds_bytes, hipStr
 void acn_launch_denoise( const double* lin, const double* surf, size_t width, size_t height, uint32_t iterations, uint32_t normal_power_log2,
                          uint32_t no_demodulate, double sigma_plane, double sigma_lum, void* scratch, double* out_rgb, hipStream_t stream );
 
+/* the filter of acn_denoise_stats: steps 1 and 2 from the statistics records [ n ][ ACN_STATS_STRIDE ] (16-byte aligned), the levels of
+ * acn_launch_denoise.  background: the linear value of an EMPTY record's pixel.  out_rgb is written by the first launch already */
+void acn_launch_denoise_stats( const double* stats, const double* surf, size_t width, size_t height, uint32_t iterations, uint32_t normal_power_log2,
+                               uint32_t no_demodulate, double sigma_plane, double sigma_lum, const double* background, void* scratch,
+                               double* out_rgb, hipStream_t stream );
+
 /* the thin-lens camera (k_lens.hip).  LensSetup: acn_lens_params after the host's checks, final values, no defaults.
  * rays: out_rays[ i ][ s ][ 6 ] = the ray of position i, sample first_sample + s (s < n_samples); pos_xy [ n ][ 2 ], or null: the pixel
  * centres first_pixel + i of the scene's raster.  n * n_samples fits a grid of 256-lane workgroups (the host checks).
@@ -94,6 +100,14 @@ struct LensSetup { uint64_t seed; uint32_t samples, jitter; double aperture_radi
 void acn_launch_lens_rays( const DevScene& sc, const double* pos_xy, size_t first_pixel, size_t n, const LensSetup& ls,
                            uint32_t first_sample, uint32_t n_samples, double* out_rays, hipStream_t stream );
 void acn_launch_lens_reduce( const double* rad, size_t n, uint32_t samples, double gamma, int linear, double* out_rgb, hipStream_t stream );
+/* reduce_stats: the same out_rgb (nullable) and stats[ i ] = { samples, mean, m2, 0 }, always linear; stats 16-byte aligned.
+ * merge: acc[ index ? index[ j ] : j ] <- part[ j ], j < n_part; indices outside [ 0, n_acc ) are skipped.
+ * resolve: out_rgb (nullable) the mean or, of an EMPTY record, background; out_noise (nullable) [ n ]. */
+void acn_launch_lens_reduce_stats( const double* rad, size_t n, uint32_t samples, double gamma, int linear, double* out_rgb, double* stats,
+                                   hipStream_t stream );
+void acn_launch_stats_merge( double* acc, size_t n_acc, const double* part, size_t n_part, const int64_t* index, hipStream_t stream );
+void acn_launch_stats_resolve( const double* stats, size_t n, const double* background, double gamma, int linear, double* out_rgb,
+                               double* out_noise, hipStream_t stream );
 
 /* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
 struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };

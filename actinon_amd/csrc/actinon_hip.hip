@@ -17,6 +17,7 @@
 #include "acn_launch.h"
 #include "acn_tables.h"
 #include "acn_chunkplan.h"
+#include "acn_stats_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* error plumbing */
@@ -1906,27 +1907,15 @@ extern "C" int acn_denoise( acn_scene_handle* h, const double* linear_rgb, const
 }
 
 /* ---- the thin-lens camera (k_lens.hip) ---- */
-static bool positive_finite( double x ) { return x > 0 && x <= 1.7976931348623157e308; }
 
 /* every check of a lens call's parameters: on the host, before the handle is touched.  window: the samples an acn_lens_rays call asks for */
 static int lens_check( const acn_scene_handle* h, const acn_lens_params* prm, const uint32_t* window, LensSetup* ls )
 {
     if( !h ) return fail( ACN_ERR_ARG, "null argument" );
-    acn_lens_params p = ACN_LENS_PARAMS_INIT;
-    if( prm )
-    {
-        if( prm->struct_size < sizeof( uint32_t ) ) return fail( ACN_ERR_ARG, "acn_lens_params.struct_size " + std::to_string( prm->struct_size ) + " is smaller than its first member" );
-        p = acn_lens_params{};
-        memcpy( &p, prm, prm->struct_size < sizeof( p ) ? prm->struct_size : sizeof( p ) );
-    }
-    if( p.samples > ACN_LENS_MAX_SAMPLES ) return fail( ACN_ERR_ARG, "acn_lens_params.samples " + std::to_string( p.samples ) + " is above 4096" );
-    if( p.flags & ~ACN_LENS_JITTER ) return fail( ACN_ERR_ARG, "unknown acn_lens_params.flags bits" );
-    if( !( p.aperture_radius >= 0 ) || p.aperture_radius > 1.7976931348623157e308 ) return fail( ACN_ERR_ARG, "acn_lens_params.aperture_radius is negative or not finite" );
-    if( p.aperture_radius > 0 )
-    {
-        if( !positive_finite( p.focus_distance ) ) return fail( ACN_ERR_ARG, "acn_lens_params.focus_distance must be positive and finite when the aperture is open" );
-        if( !( h->dev.prm.camera_focal_length > 0 ) ) return fail( ACN_ERR_ARG, "an open aperture needs a camera_focal_length above 0: the plane in focus lies in front of the camera" );
-    }
+    acn_lens_params p;
+    std::string msg;
+    if( acn_lens_params_read( prm, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );   /* (acn_stats_host.h: the members alone) */
+    if( p.aperture_radius > 0 && !( h->dev.prm.camera_focal_length > 0 ) ) return fail( ACN_ERR_ARG, "an open aperture needs a camera_focal_length above 0: the plane in focus lies in front of the camera" );
     ls->samples = p.samples ? p.samples : ACN_LENS_DEFAULT_SAMPLES;
     ls->jitter = ( p.flags & ACN_LENS_JITTER ) ? 1u : 0u;
     ls->seed = ACN_LENS_SEED + ( uint64_t )p.seed;
@@ -1978,7 +1967,7 @@ extern "C" int acn_lens_rays( acn_scene_handle* h, const double* pos_xy, size_t 
 /* a lens call after its null checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice: rays, the ray path of
  * acn_render_rays_dev (linear, its validity kernel left out: the rays are valid by construction), the ordered mean */
 static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, double* d_out_rgb,
-                        const acn_render_opts* opts )
+                        const acn_render_opts* opts, double* d_stats = nullptr, bool with_stats = false )
 {
     LensSetup ls;
     int st = lens_check( h, prm, nullptr, &ls );
@@ -1988,6 +1977,7 @@ static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t firs
     if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
     {
         if( opts->shard_rank >= opts->shard_world ) return fail( ACN_ERR_ARG, "shard_rank >= shard_world" );
+        if( with_stats ) return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
         if( !linear ) return fail( ACN_ERR_ARG, "a lens call sharded by samples gives partial means: it needs ACN_OPT_LINEAR_OUT" );
     }
     if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
@@ -2017,7 +2007,11 @@ static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t firs
         HIP_TRY( hipGetLastError() );
         st = render_dispatch( h, primary_rays( h->d_lens_rays ), cnt * K, h->d_lens_rad, &ray_opts, stream );
         if( st != ACN_OK ) return st;
-        acn_launch_lens_reduce( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, stream );
+        if( with_stats )
+            acn_launch_lens_reduce_stats( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
+                                          d_stats + ( size_t )ACN_STATS_STRIDE * base, stream );
+        else
+            acn_launch_lens_reduce( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, stream );
         HIP_TRY( hipGetLastError() );
     }
     if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
@@ -2054,6 +2048,182 @@ extern "C" int acn_render_lens( acn_scene_handle* h, const double* pos_xy, size_
     acn_render_opts o = *opts;
     o.stream = nullptr;
     return on_host_buffers( h, pos_xy, 2, n, out_rgb, 3, [ & ]( double* d_pos, double* d_out ) { return acn_render_lens_dev( h, d_pos, n, prm, d_out, &o ); } );
+}
+
+/* ---- lens sample statistics (k_lens.hip, k_denoise.hip; the checks that need no handle: acn_stats_host.h) ---- */
+static int stats_buffer( const void* stats, size_t n, const char* what )
+{
+    std::string msg;
+    return acn_stats_buffer_check( stats, n, what, &msg ) == ACN_OK ? ACN_OK : fail( ACN_ERR_ARG, msg );
+}
+
+extern "C" int acn_render_lens_stats_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
+                                          void* d_stats, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !d_pos_xy || !d_stats ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( stats_buffer( d_stats, n, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    return render_lens( h, ( const double* )d_pos_xy, 0, n, prm, ( double* )d_out_rgb, opts, ( double* )d_stats, true );
+}
+
+extern "C" int acn_render_lens_stats_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
+                                                    void* d_stats, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( count && !d_stats ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( stats_buffer( d_stats, count, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    const size_t pixels = h->dev.prm.image_width * h->dev.prm.image_height;
+    if( first > pixels || count > pixels - first ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
+    return render_lens( h, nullptr, first, count, prm, ( double* )d_out_rgb, opts, ( double* )d_stats, true );
+}
+
+/* device copies of host arrays for one call; everything is freed when it goes */
+struct DevCopies
+{
+    std::vector< void* > held;
+    ~DevCopies() { for( void* p : held ) hipFree( p ); }
+    /* null on failure; src (nullable) is copied in */
+    void* make( const void* src, size_t bytes )
+    {
+        void* d = nullptr;
+        if( hipMalloc( &d, bytes ? bytes : 1 ) != hipSuccess ) return nullptr;
+        held.push_back( d );
+        if( src && bytes && hipMemcpy( d, src, bytes, hipMemcpyHostToDevice ) != hipSuccess ) return nullptr;
+        return d;
+    }
+};
+
+extern "C" int acn_render_lens_stats( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
+                                      double* stats, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && ( !pos_xy || !stats ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
+    if( st != ACN_OK ) return st;
+    if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
+        return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
+    if( n == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    DevCopies dc;
+    void* d_pos = dc.make( pos_xy, sizeof( double ) * 2 * n );
+    void* d_out = out_rgb ? dc.make( nullptr, sizeof( double ) * 3 * n ) : nullptr;
+    void* d_st = dc.make( nullptr, sizeof( double ) * ACN_STATS_STRIDE * n );
+    if( !d_pos || !d_st || ( out_rgb && !d_out ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    st = acn_render_lens_stats_dev( h, d_pos, n, prm, d_out, d_st, &o );
+    if( st != ACN_OK ) return st;
+    if( out_rgb ) HIP_TRY( hipMemcpy( out_rgb, d_out, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) );
+    HIP_TRY( hipMemcpy( stats, d_st, sizeof( double ) * ACN_STATS_STRIDE * n, hipMemcpyDeviceToHost ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_lens_stats_merge_dev( acn_scene_handle* h, void* d_acc, size_t n_acc, const void* d_part, size_t n_part,
+                                         const int64_t* d_index, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
+    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a merge of lens statistics is not sharded" );
+    if( stats_buffer( d_acc, n_acc, "d_acc" ) != ACN_OK || stats_buffer( d_part, n_part, "d_part" ) != ACN_OK ) return ACN_ERR_ARG;
+    if( !d_index && n_part > n_acc ) return fail( ACN_ERR_ARG, "a merge without an index needs n_part <= n_acc" );
+    if( ( uintptr_t )d_index % 8 ) return fail( ACN_ERR_ARG, "d_index is an array of int64_t: align the buffer" );
+    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
+    acn_launch_stats_merge( ( double* )d_acc, n_acc, ( const double* )d_part, n_part, d_index, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_lens_stats_merge( acn_scene_handle* h, double* acc, size_t n_acc, const double* part, size_t n_part,
+                                     const int64_t* index, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n_acc && !acc ) || ( n_part && !part ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a merge of lens statistics is not sharded" );
+    std::string msg;
+    if( acn_stats_index_check( index, n_part, n_acc, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    DevCopies dc;
+    const size_t rec = sizeof( double ) * ACN_STATS_STRIDE;
+    void* d_acc = dc.make( acc, rec * n_acc );
+    void* d_part = dc.make( part, rec * n_part );
+    void* d_index = index ? dc.make( index, sizeof( int64_t ) * n_part ) : nullptr;
+    if( !d_acc || !d_part || ( index && !d_index ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    int st = acn_lens_stats_merge_dev( h, d_acc, n_acc, d_part, n_part, ( const int64_t* )d_index, &o );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipMemcpy( acc, d_acc, rec * n_acc, hipMemcpyDeviceToHost ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_lens_stats_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb, void* d_out_noise,
+                                           const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    if( !h || ( n && !d_stats ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a resolve of lens statistics is not sharded" );
+    if( stats_buffer( d_stats, n, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    if( n == 0 || ( !d_out_rgb && !d_out_noise ) ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
+    acn_launch_stats_resolve( ( const double* )d_stats, n, h->dev.prm.background_color, h->dev.prm.gamma, ( opts->flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0,
+                              ( double* )d_out_rgb, ( double* )d_out_noise, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                                      const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    DenoiseSetup su;
+    int st = denoise_check( h, d_stats, d_surface, width, height, prm, d_out_rgb, opts, &su );
+    if( st != ACN_OK ) return st;
+    if( ( uintptr_t )d_surface % 16 ) return fail( ACN_ERR_ARG, "the surface records of a denoise call are read 16 bytes at a time: align the buffer" );
+    if( stats_buffer( d_stats, width * height, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    const size_t need = width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL;
+    if( h->denoise_bytes < need )
+    {
+        if( h->d_denoise ) hipFree( h->d_denoise );   /* (waits for whatever still reads it) */
+        h->d_denoise = nullptr; h->denoise_bytes = 0;
+        HIP_TRY( hipMalloc( &h->d_denoise, need ) );
+        h->denoise_bytes = need;
+    }
+    acn_launch_denoise_stats( ( const double* )d_stats, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2,
+                              su.no_demodulate, su.sigma_plane, su.sigma_lum, h->dev.prm.background_color, h->d_denoise, ( double* )d_out_rgb, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_denoise_stats( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                                  const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    DenoiseSetup su;
+    int st = denoise_check( h, stats, surface, width, height, prm, out_rgb, opts, &su );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t n = width * height;
+    DevCopies dc;
+    void* d_st = dc.make( stats, sizeof( double ) * ACN_STATS_STRIDE * n );
+    void* d_surf = dc.make( surface, sizeof( double ) * ACN_SURF_STRIDE * n );
+    void* d_rgb = dc.make( nullptr, sizeof( double ) * 3 * n );
+    if( !d_st || !d_surf || !d_rgb ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    acn_render_opts o = *opts;
+    o.stream = nullptr;
+    st = acn_denoise_stats_dev( h, d_st, d_surf, width, height, prm, d_rgb, &o );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipMemcpy( out_rgb, d_rgb, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) );
+    return ACN_OK;
 }
 
 extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )

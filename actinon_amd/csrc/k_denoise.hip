@@ -11,7 +11,13 @@
  * 2^31 high has more rows of tiles than a grid has in y).  A tap that is skipped is predicated: its address is clamped to the
  * centre, it is loaded, and a select drops its terms -- sums start at +0 and never become -0, so adding the +0 of a dropped term
  * is adding nothing.  The one branch is wave-level: a tap that no lane of the wave takes (most of them at stride 64 near a border)
- * is not loaded, which for the same reason changes no bit.  No lane reads another lane's registers. */
+ * is not loaded, which for the same reason changes no bit.  No lane reads another lane's registers.
+ *
+ * acn_denoise_stats (frames of acn_render_lens_stats*) launches k_dn_prepare_stats, k_dn_prefilter and the same k_dn_level:
+ *   prepare_stats  also reads the lane's 64-byte statistics record with 16-byte loads; the colour piece is { c.xyz, var_raw }, a
+ *                  negative var_raw standing for "none", and the pixel's mean (the background for an EMPTY record) goes to the
+ *                  frame, where the last level finds the pixels it copies.
+ *   prefilter      3 x 3 window on the guide keys and var_raw, in the arrangement of `variance`. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
 
@@ -112,6 +118,77 @@ void k_dn_variance( const double2* __restrict__ guide, const double2* __restrict
     out[ 2 * p + 1 ] = make_double2( c1.x, var );
 }
 
+/* steps 1 and 2 of acn_denoise_stats: L is the mean of the record, var_raw the measured variance of the demodulated mean */
+__global__ __launch_bounds__( 256 )
+void k_dn_prepare_stats( const double2* __restrict__ stats, const double* __restrict__ surf, size_t n, uint32_t no_demodulate,
+                         double bg_x, double bg_y, double bg_z, double2* __restrict__ guide, double2* __restrict__ pix, double* __restrict__ frame )
+{
+    const size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
+    if( i >= n ) return;
+    const double2 s0 = stats[ 4 * i ], s1 = stats[ 4 * i + 1 ], s2 = stats[ 4 * i + 2 ], s3 = stats[ 4 * i + 3 ];
+    const double2* r = ( const double2* )( surf + ( size_t )ACN_SURF_STRIDE * i );
+    const double2 r0 = r[ 0 ], r1 = r[ 1 ], r2 = r[ 2 ], r3 = r[ 3 ], r4 = r[ 4 ], r5 = r[ 5 ], r6 = r[ 6 ];
+    const double cnt = s0.x;
+    const bool empty = !( cnt >= 1.0 && cnt < __builtin_inf() );
+    const double lx = empty ? bg_x : s0.y, ly = empty ? bg_y : s1.x, lz = empty ? bg_z : s1.y;
+    const double ax = dn_albedo( r4.y, no_demodulate ), ay = dn_albedo( r5.x, no_demodulate ), az = dn_albedo( r5.y, no_demodulate );
+    const double cx = lx / ax, cy = ly / ay, cz = lz / az;
+    DnKey key;
+    key.enter = ( int32_t )r3.y; key.exit = ( int32_t )r4.x; key.hops = ( int32_t )r6.y;
+    key.ok = !empty && r0.x < __builtin_inf() && !( ( uint32_t )( int32_t )r6.x & ACN_SURF_EMITTER ) && dn_finite( cx ) && dn_finite( cy ) && dn_finite( cz );
+    double var_raw = -1.0;
+    if( !empty && cnt > 1.0 )
+    {
+        const double vx = ( s2.x / ( cnt - 1.0 ) ) / cnt, vy = ( s2.y / ( cnt - 1.0 ) ) / cnt, vz = ( s3.x / ( cnt - 1.0 ) ) / cnt;
+        var_raw = ( ( 0.2126 * 0.2126 ) * ( vx / ( ax * ax ) ) + ( 0.7152 * 0.7152 ) * ( vy / ( ay * ay ) ) ) + ( 0.0722 * 0.0722 ) * ( vz / ( az * az ) );
+    }
+    union { DnKey k; double2 d; } kv; kv.k = key;
+    double2* g = guide + 4 * i;
+    g[ 0 ] = make_double2( r2.x, r2.y );   /* N */
+    g[ 1 ] = make_double2( r3.x, r0.y );   /* N.z, P.x */
+    g[ 2 ] = make_double2( r1.x, r1.y );   /* P.y, P.z */
+    g[ 3 ] = kv.d;
+    pix[ 2 * i ]     = make_double2( cx, cy );
+    pix[ 2 * i + 1 ] = make_double2( cz, var_raw );
+    frame[ 3 * i ] = lx; frame[ 3 * i + 1 ] = ly; frame[ 3 * i + 2 ] = lz;
+}
+
+/* var = the ( 1/4, 1/2, 1/4 )^2 mean of the var_raw that the matching pixels of the 3 x 3 window have; 0 where none has one */
+__global__ __launch_bounds__( 256 )
+void k_dn_prefilter( const double2* __restrict__ guide, const double2* __restrict__ in, size_t width, size_t height, size_t tiles_x,
+                     double2* __restrict__ out )
+{
+    size_t x, y;
+    if( !dn_pixel( width, height, tiles_x, &x, &y ) ) return;
+    const size_t p = y * width + x;
+    const DnKey key = dn_key( guide, p );
+    const double2 c0 = in[ 2 * p ], c1 = in[ 2 * p + 1 ];
+    double var = 0.0;
+    if( key.ok )
+    {
+        double sw = 0.0, sv = 0.0;
+        #pragma unroll
+        for( int dy = -1; dy <= 1; dy++ )
+        {
+            #pragma unroll
+            for( int dx = -1; dx <= 1; dx++ )
+            {
+                bool inside;
+                const size_t q = dn_tap( x, y, dx, dy, width, height, p, &inside );
+                const DnKey k2 = dn_key( guide, q );
+                const double vr = in[ 2 * q + 1 ].y;
+                const bool ok = inside && k2.ok && k2.enter == key.enter && k2.exit == key.exit && k2.hops == key.hops && !( vr < 0.0 );
+                const double g = ( dy ? 0.25 : 0.5 ) * ( dx ? 0.25 : 0.5 );
+                sw += ok ? g : 0.0;
+                sv += ok ? g * vr : 0.0;
+            }
+        }
+        var = sw > 0 ? sv / sw : 0.0;
+    }
+    out[ 2 * p ]     = c0;
+    out[ 2 * p + 1 ] = make_double2( c1.x, var );
+}
+
 /* one a-trous level.  LAST: the result is remodulated and written to the frame, pixels that are not filterable are copied there */
 template< bool LAST >
 __global__ __launch_bounds__( 256 )
@@ -205,5 +282,32 @@ void acn_launch_denoise( const double* lin, const double* surf, size_t width, si
         else
             hipLaunchKernelGGL( ( k_dn_level< true > ), tiles, dim3( 256 ), 0, stream, guide, buf[ src ], width, height, tiles_x, stride,
                                 normal_power_log2, sigma_plane, sigma_lum, ( double2* )nullptr, lin, surf, no_demodulate, out_rgb );
+    }
+}
+
+/* acn_denoise_stats: the same scratch; the frame itself holds the per-pixel means from prepare on, which is where the last level reads
+ * the pixels it copies (in place: a lane touches its own pixel alone) */
+void acn_launch_denoise_stats( const double* stats, const double* surf, size_t width, size_t height, uint32_t iterations, uint32_t normal_power_log2,
+                               uint32_t no_demodulate, double sigma_plane, double sigma_lum, const double* background, void* scratch,
+                               double* out_rgb, hipStream_t stream )
+{
+    const size_t n = width * height;
+    double2* guide = ( double2* )scratch;
+    double2* buf[ 2 ] = { guide + 4 * n, guide + 6 * n };
+    const size_t tiles_x = ( width + DN_TILE - 1 ) / DN_TILE, tiles_y = ( height + DN_TILE - 1 ) / DN_TILE;
+    const dim3 tiles( ( unsigned )( tiles_x * tiles_y ) );
+    hipLaunchKernelGGL( k_dn_prepare_stats, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, stream, ( const double2* )stats, surf, n,
+                        no_demodulate, background[ 0 ], background[ 1 ], background[ 2 ], guide, buf[ 0 ], out_rgb );
+    hipLaunchKernelGGL( k_dn_prefilter, tiles, dim3( 256 ), 0, stream, guide, buf[ 0 ], width, height, tiles_x, buf[ 1 ] );
+    int src = 1;
+    for( uint32_t i = 0; i < iterations; i++, src ^= 1 )
+    {
+        const long long stride = 1ll << i;
+        if( i + 1 < iterations )
+            hipLaunchKernelGGL( ( k_dn_level< false > ), tiles, dim3( 256 ), 0, stream, guide, buf[ src ], width, height, tiles_x, stride,
+                                normal_power_log2, sigma_plane, sigma_lum, buf[ src ^ 1 ], ( const double* )nullptr, ( const double* )nullptr, 0u, ( double* )nullptr );
+        else
+            hipLaunchKernelGGL( ( k_dn_level< true > ), tiles, dim3( 256 ), 0, stream, guide, buf[ src ], width, height, tiles_x, stride,
+                                normal_power_log2, sigma_plane, sigma_lum, ( double2* )nullptr, ( const double* )out_rgb, surf, no_demodulate, out_rgb );
     }
 }

@@ -12,7 +12,12 @@
  *                  lanes on consecutive doubles (the whole tile is one contiguous run when K <= LENS_TILE_K, else runs of
  *                  LENS_TILE_K * 24 bytes), and lane t < 3 * positions then adds channel t % 3 of position t / 3 from LDS, alone
  *                  and in the order of k: ( ( 0.0 + L0 ) + L1 ) + ...  No lane reads another lane's registers and no sum is
- *                  split, so a result does not depend on which positions share a wavefront or a workgroup. */
+ *                  split, so a result does not depend on which positions share a wavefront or a workgroup.
+ *   k_lens_reduce_stats  the sibling of k_lens_reduce behind acn_render_lens_stats*, on the same tiling: pass 1 is that sum, pass 2
+ *                  stages the tiles again (not when K <= LENS_TILE_K: the one tile is still in LDS) and the same lane adds the
+ *                  squared deviations from its mean in the order of k.  The 64-byte records of the workgroup are put together in
+ *                  LDS and leave as 16-byte pieces, consecutive lanes on consecutive pieces: 64 positions are one run of 4 KiB.
+ *   k_stats_merge, k_stats_resolve  one record per lane, read and written as four 16-byte pieces. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
 
@@ -97,6 +102,125 @@ void k_lens_reduce( const double* __restrict__ rad, size_t n, uint32_t K, double
     out_rgb[ p0 * 3 + tid ] = mean;
 }
 
+/* k_lens_reduce plus the record of every position (include/actinon_hip.h, ACN_STATS_STRIDE): n = K, the mean, and
+ * m2 = ( ( 0.0 + d0 * d0 ) + d1 * d1 ) + ..., dk = Lk - mean, a second pass over the samples.  out_rgb may be null */
+__global__ __launch_bounds__( 256 )
+void k_lens_reduce_stats( const double* __restrict__ rad, size_t n, uint32_t K, double gamma, int linear, double* __restrict__ out_rgb,
+                          double2* __restrict__ stats )
+{
+    __shared__ double tile[ LENS_TILE_POS * LENS_TILE_K * 3 ];
+    __shared__ double2 rec[ LENS_TILE_POS * 4 ];
+    const size_t p0 = ( size_t )blockIdx.x * LENS_TILE_POS;
+    const uint32_t np = n - p0 < LENS_TILE_POS ? ( uint32_t )( n - p0 ) : LENS_TILE_POS;
+    const uint32_t tid = threadIdx.x;
+    const bool adds = tid < np * 3;
+    const uint32_t my_p = tid / 3, my_c = tid - my_p * 3;
+    double sum = 0.0;
+    for( uint32_t k0 = 0; k0 < K; k0 += LENS_TILE_K )
+    {
+        const uint32_t kc = K - k0 < LENS_TILE_K ? K - k0 : LENS_TILE_K, row = kc * 3;
+        if( k0 ) __syncthreads();   /* (the adds of the tile before) */
+        for( uint32_t idx = tid; idx < np * row; idx += 256 )
+        {
+            const uint32_t p = idx / row, r = idx - p * row;
+            tile[ idx ] = rad[ ( ( p0 + p ) * K + k0 ) * 3 + r ];
+        }
+        __syncthreads();
+        if( adds ) for( uint32_t k = 0; k < kc; k++ ) sum = sum + tile[ my_p * row + k * 3 + my_c ];
+    }
+    const double mean = sum / ( double )K;
+    double m2 = 0.0;
+    for( uint32_t k0 = 0; k0 < K; k0 += LENS_TILE_K )
+    {
+        const uint32_t kc = K - k0 < LENS_TILE_K ? K - k0 : LENS_TILE_K, row = kc * 3;
+        if( K > LENS_TILE_K )   /* else the one tile of pass 1 is still there */
+        {
+            __syncthreads();
+            for( uint32_t idx = tid; idx < np * row; idx += 256 )
+            {
+                const uint32_t p = idx / row, r = idx - p * row;
+                tile[ idx ] = rad[ ( ( p0 + p ) * K + k0 ) * 3 + r ];
+            }
+            __syncthreads();
+        }
+        if( adds ) for( uint32_t k = 0; k < kc; k++ )
+        {
+            const double d = tile[ my_p * row + k * 3 + my_c ] - mean;
+            m2 = m2 + d * d;
+        }
+    }
+    if( adds )
+    {
+        double* r = ( double* )rec + my_p * ACN_STATS_STRIDE;
+        r[ 1 + my_c ] = mean;
+        r[ 4 + my_c ] = m2;
+        if( my_c == 0 ) { r[ 0 ] = ( double )K; r[ 7 ] = 0.0; }
+        if( out_rgb ) out_rgb[ p0 * 3 + tid ] = linear ? mean : cl_sat( mk( mean, mean, mean ), gamma ).x;   /* (as k_lens_reduce) */
+    }
+    __syncthreads();
+    if( tid < np * 4 ) stats[ p0 * 4 + tid ] = rec[ tid ];
+}
+
+/* a record whose [ 0 ] is not a finite number >= 1 is EMPTY (a NaN fails both comparisons) */
+__device__ static inline bool stats_empty( double n ) { return !( n >= 1.0 && n < __builtin_inf() ); }
+
+/* acc[ i ] <- merge( acc[ i ], part[ j ] ), i = index ? index[ j ] : j; an i outside [ 0, n_acc ) is skipped: nothing is read or written */
+__global__ __launch_bounds__( 256 )
+void k_stats_merge( double2* acc, size_t n_acc, const double2* __restrict__ part, size_t n_part, const long long* __restrict__ index )
+{
+    const size_t j = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
+    if( j >= n_part ) return;
+    long long i = ( long long )j;
+    if( index )
+    {
+        i = index[ j ];
+        if( i < 0 ) return;
+    }
+    if( ( size_t )i >= n_acc ) return;
+    const double2 b0 = part[ 4 * j ], b1 = part[ 4 * j + 1 ], b2 = part[ 4 * j + 2 ], b3 = part[ 4 * j + 3 ];
+    if( stats_empty( b0.x ) ) return;
+    double2* a = acc + 4 * ( size_t )i;
+    const double2 a0 = a[ 0 ], a1 = a[ 1 ], a2 = a[ 2 ], a3 = a[ 3 ];
+    if( stats_empty( a0.x ) ) { a[ 0 ] = b0; a[ 1 ] = b1; a[ 2 ] = b2; a[ 3 ] = b3; return; }
+    const double na = a0.x, nb = b0.x, nn = na + nb;
+    const double fb = nb / nn, fab = ( na * nb ) / nn;
+    const double dx = b0.y - a0.y, dy = b1.x - a1.x, dz = b1.y - a1.y;
+    const double mx = a0.y + dx * fb, my = a1.x + dy * fb, mz = a1.y + dz * fb;
+    const double sx = ( a2.x + b2.x ) + ( dx * dx ) * fab;
+    const double sy = ( a2.y + b2.y ) + ( dy * dy ) * fab;
+    const double sz = ( a3.x + b3.x ) + ( dz * dz ) * fab;
+    a[ 0 ] = make_double2( nn, mx ); a[ 1 ] = make_double2( my, mz ); a[ 2 ] = make_double2( sx, sy ); a[ 3 ] = make_double2( sz, 0.0 );
+}
+
+/* out_rgb (nullable): the mean, or the background of an EMPTY record, through cl_s_sat unless linear; out_noise (nullable): `noise` */
+__global__ __launch_bounds__( 256 )
+void k_stats_resolve( const double2* __restrict__ stats, size_t n, double bg_x, double bg_y, double bg_z, double gamma, int linear,
+                      double* __restrict__ out_rgb, double* __restrict__ out_noise )
+{
+    const size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
+    if( i >= n ) return;
+    const double2 r0 = stats[ 4 * i ], r1 = stats[ 4 * i + 1 ], r2 = stats[ 4 * i + 2 ], r3 = stats[ 4 * i + 3 ];
+    const bool empty = stats_empty( r0.x );
+    const double cnt = r0.x;
+    if( out_rgb )
+    {
+        V3 c = empty ? mk( bg_x, bg_y, bg_z ) : mk( r0.y, r1.x, r1.y );
+        if( !linear ) c = cl_sat( c, gamma );
+        out_rgb[ 3 * i ] = c.x; out_rgb[ 3 * i + 1 ] = c.y; out_rgb[ 3 * i + 2 ] = c.z;
+    }
+    if( out_noise )
+    {
+        double noise = __builtin_inf();
+        if( !empty && cnt > 1.0 )
+        {
+            const double vx = ( r2.x / ( cnt - 1.0 ) ) / cnt, vy = ( r2.y / ( cnt - 1.0 ) ) / cnt, vz = ( r3.x / ( cnt - 1.0 ) ) / cnt;
+            const double lum = ( 0.2126 * r0.y + 0.7152 * r1.x ) + 0.0722 * r1.y;
+            noise = acn_sqrt( ( ( 0.2126 * 0.2126 ) * vx + ( 0.7152 * 0.7152 ) * vy ) + ( 0.0722 * 0.0722 ) * vz ) / ( acn_fabs( lum ) + ACN_STATS_NOISE_FLOOR );
+        }
+        out_noise[ i ] = noise;
+    }
+}
+
 void acn_launch_lens_rays( const DevScene& sc, const double* pos_xy, size_t first_pixel, size_t n, const LensSetup& ls,
                            uint32_t first_sample, uint32_t n_samples, double* out_rays, hipStream_t stream )
 {
@@ -109,4 +233,24 @@ void acn_launch_lens_reduce( const double* rad, size_t n, uint32_t samples, doub
 {
     hipLaunchKernelGGL( k_lens_reduce, dim3( ( unsigned )( ( n + LENS_TILE_POS - 1 ) / LENS_TILE_POS ) ), dim3( 256 ), 0, stream,
                         rad, n, samples, gamma, linear, out_rgb );
+}
+
+void acn_launch_lens_reduce_stats( const double* rad, size_t n, uint32_t samples, double gamma, int linear, double* out_rgb, double* stats,
+                                   hipStream_t stream )
+{
+    hipLaunchKernelGGL( k_lens_reduce_stats, dim3( ( unsigned )( ( n + LENS_TILE_POS - 1 ) / LENS_TILE_POS ) ), dim3( 256 ), 0, stream,
+                        rad, n, samples, gamma, linear, out_rgb, ( double2* )stats );
+}
+
+void acn_launch_stats_merge( double* acc, size_t n_acc, const double* part, size_t n_part, const int64_t* index, hipStream_t stream )
+{
+    hipLaunchKernelGGL( k_stats_merge, dim3( ( unsigned )( ( n_part + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
+                        ( double2* )acc, n_acc, ( const double2* )part, n_part, ( const long long* )index );
+}
+
+void acn_launch_stats_resolve( const double* stats, size_t n, const double* background, double gamma, int linear, double* out_rgb,
+                               double* out_noise, hipStream_t stream )
+{
+    hipLaunchKernelGGL( k_stats_resolve, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
+                        ( const double2* )stats, n, background[ 0 ], background[ 1 ], background[ 2 ], gamma, linear, out_rgb, out_noise );
 }

@@ -484,6 +484,98 @@ class Handle:
         check(hip.acn_render_lens_main_pass_dev(self.h, first, count, C.byref(p), d_out_ptr, C.byref(o)),
               "acn_render_lens_main_pass_dev")
 
+    # lens sample statistics (acn_render_lens_stats, acn_lens_stats_*, acn_denoise_stats): one [8] float64 record per position
+    def _plain_opts(self, linear, stream):
+        o = self._opts(linear, stream)
+        o.shard_mode, o.shard_rank, o.shard_world = abi.ACN_SHARD_NONE, 0, 0
+        return o
+
+    def render_lens_stats(self, pos_xy, linear=False, lens=None, **params):
+        """render_lens and the sample statistics of every position (acn_render_lens_stats): pos_xy [n,2] -> ( rgb [n,3] float64,
+        saturated or linear as render_lens gives it, LensStats over [n,8] )."""
+        p = self._lens(lens, params)
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((pos.shape[0], 3), dtype=np.float64)
+        raw = np.empty((pos.shape[0], abi.ACN_STATS_STRIDE), dtype=np.float64)
+        o = self._opts(linear, None)
+        check(hip.acn_render_lens_stats(self.h, pos.ctypes.data, pos.shape[0], C.byref(p), out.ctypes.data, raw.ctypes.data, C.byref(o)),
+              "acn_render_lens_stats")
+        return out, LensStats(raw, self)
+
+    def render_lens_stats_dev(self, d_pos_ptr, n, d_out_ptr, d_stats_ptr, linear=False, stream=None, lens=None, **params):
+        """Device buffers: d_out [n,3] float64 or None, d_stats [n,8] float64, 16-byte aligned."""
+        p = self._lens(lens, params)
+        o = self._opts(linear, stream)
+        check(hip.acn_render_lens_stats_dev(self.h, d_pos_ptr, n, C.byref(p), d_out_ptr, d_stats_ptr, C.byref(o)),
+              "acn_render_lens_stats_dev")
+
+    def render_lens_stats_main_pass_dev(self, first, count, d_out_ptr, d_stats_ptr, linear=False, stream=None, lens=None, **params):
+        p = self._lens(lens, params)
+        o = self._opts(linear, stream)
+        check(hip.acn_render_lens_stats_main_pass_dev(self.h, first, count, C.byref(p), d_out_ptr, d_stats_ptr, C.byref(o)),
+              "acn_render_lens_stats_main_pass_dev")
+
+    def lens_stats_merge(self, acc, part, index=None):
+        """Merges the records `part` into a copy of `acc` (acn_lens_stats_merge), part[j] into acc[index[j]] (index None: acc[j]);
+        LensStats or [n,8] arrays -> LensStats.  Indices out of range or given twice are refused."""
+        a = np.array(acc.raw if isinstance(acc, LensStats) else acc, dtype=np.float64).reshape(-1, abi.ACN_STATS_STRIDE)
+        b = np.ascontiguousarray(part.raw if isinstance(part, LensStats) else part, dtype=np.float64).reshape(-1, abi.ACN_STATS_STRIDE)
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+        if idx is not None and len(idx) != len(b):
+            raise ValueError(f"{len(b)} records need {len(b)} indices, got {len(idx)}")
+        o = self._plain_opts(False, None)
+        check(hip.acn_lens_stats_merge(self.h, a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0],
+                                       None if idx is None else idx.ctypes.data, C.byref(o)), "acn_lens_stats_merge")
+        return LensStats(a, self)
+
+    def lens_stats_merge_dev(self, d_acc_ptr, n_acc, d_part_ptr, n_part, d_index_ptr=None, stream=None):
+        """Device buffers; d_index int64 [n_part] or None.  An index outside [0, n_acc) is skipped."""
+        o = self._plain_opts(False, stream)
+        check(hip.acn_lens_stats_merge_dev(self.h, d_acc_ptr, n_acc, d_part_ptr, n_part, d_index_ptr, C.byref(o)),
+              "acn_lens_stats_merge_dev")
+
+    def lens_stats_resolve_dev(self, d_stats_ptr, n, d_out_rgb_ptr=None, d_out_noise_ptr=None, linear=False, stream=None):
+        """The colour [n,3] (saturated unless linear; the background for an EMPTY record) and the noise [n] of device records."""
+        o = self._plain_opts(linear, stream)
+        check(hip.acn_lens_stats_resolve_dev(self.h, d_stats_ptr, n, d_out_rgb_ptr, d_out_noise_ptr, C.byref(o)),
+              "acn_lens_stats_resolve_dev")
+
+    def lens_stats_resolve(self, stats, linear=False):
+        """acn_lens_stats_resolve_dev on host records (LensStats or [n,8]) -> ( rgb [n,3], noise [n] ); the copies go through torch."""
+        import torch
+        raw = np.ascontiguousarray(stats.raw if isinstance(stats, LensStats) else stats, dtype=np.float64).reshape(-1, abi.ACN_STATS_STRIDE)
+        n = raw.shape[0]
+        dev = torch.device("cuda", self.device)
+        d = torch.from_numpy(raw).to(dev)
+        rgb = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        noise = torch.empty((n,), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.lens_stats_resolve_dev(d.data_ptr(), n, rgb.data_ptr(), noise.data_ptr(), linear=linear)
+        return rgb.cpu().numpy(), noise.cpu().numpy()
+
+    def denoise_stats(self, stats, surface, width, height, **params):
+        """acn_denoise with the measured variance (acn_denoise_stats): stats the LensStats (or [h*w,8] records) of a frame's pixels,
+        surface the Surface of the same positions -> [h,w,3] float64, linear.  params: as for denoise."""
+        raw = np.ascontiguousarray(stats.raw if isinstance(stats, LensStats) else stats, dtype=np.float64)
+        srf = np.ascontiguousarray(surface.raw if isinstance(surface, Surface) else surface, dtype=np.float64)
+        n = int(width) * int(height)
+        if raw.size != n * abi.ACN_STATS_STRIDE or srf.size != n * abi.ACN_SURF_STRIDE:
+            raise ValueError(f"{height}x{width} pixels need {n} statistics and surface records, got {raw.shape} and {srf.shape}")
+        out = np.empty((int(height), int(width), 3), dtype=np.float64)
+        p = self.denoise_params(**params)
+        o = self._plain_opts(False, None)
+        check(hip.acn_denoise_stats(self.h, raw.ctypes.data, srf.ctypes.data, width, height, C.byref(p), out.ctypes.data, C.byref(o)),
+              "acn_denoise_stats")
+        return out
+
+    def denoise_stats_dev(self, d_stats_ptr, d_surface_ptr, width, height, d_out_ptr, stream=None, **params):
+        """Device buffers: d_stats [h*w,8], d_surface [h*w,16], d_out [h*w,3] float64; enqueued on `stream` without a
+        synchronisation (None: the handle's stream, synchronous)."""
+        p = self.denoise_params(**params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_denoise_stats_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)),
+              "acn_denoise_stats_dev")
+
     def pick(self, x, y):
         """The object under sample position (x, y): None on a miss, else node (enter object if any, else exit object), its
         type name, distance and position."""
@@ -544,6 +636,40 @@ class Surface:
     hops = property(lambda self: self.raw[:, 13].astype(np.int64))
     weight = property(lambda self: self.raw[:, 14])
     hit = property(lambda self: self.raw[:, 0] < np.inf)
+
+
+class LensStats:
+    """Named views over the [n,8] float64 records of a lens statistics call (include/actinon_hip.h, ACN_STATS_STRIDE).  `handle`
+    (optional) is the Handle that resolves them: .noise is computed by acn_lens_stats_resolve_dev on the device."""
+
+    def __init__(self, raw, handle=None):
+        raw = np.asarray(raw, dtype=np.float64)
+        if raw.ndim != 2 or raw.shape[1] != abi.ACN_STATS_STRIDE:
+            raise ValueError(f"lens statistics are [n,{abi.ACN_STATS_STRIDE}] float64, got {raw.shape}")
+        self.raw = raw
+        self.handle = handle
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    n = property(lambda self: self.raw[:, 0])
+    mean = property(lambda self: self.raw[:, 1:4])
+    m2 = property(lambda self: self.raw[:, 4:7])
+    empty = property(lambda self: ~(np.isfinite(self.raw[:, 0]) & (self.raw[:, 0] >= 1)))
+
+    @property
+    def variance_of_mean(self):
+        """( m2 / ( n - 1 ) ) / n per channel; NaN where n <= 1 or the record is EMPTY"""
+        n = self.raw[:, 0:1]
+        with np.errstate(all="ignore"):
+            vm = (self.raw[:, 4:7] / (n - 1.0)) / n
+        return np.where((n > 1) & ~self.empty[:, None], vm, np.nan)
+
+    @property
+    def noise(self):
+        if self.handle is None:
+            raise AcnError(abi.ACN_ERR_ARG, "LensStats.noise is resolved on the device: construct it with a Handle")
+        return self.handle.lens_stats_resolve(self.raw, linear=True)[1]
 
 
 def main_pass_positions(width, height, first=0, count=None):

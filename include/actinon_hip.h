@@ -455,6 +455,86 @@ int acn_render_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, co
 int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
                                    const acn_render_opts* opts );
 
+/* Lens sample statistics: how noisy each position of a lens call still is (k_lens.hip, k_denoise.hip).  A lens call sees all K
+ * radiances of a position; these calls keep, beside their mean, the sum of their squared deviations, as one record per position
+ * that stays on the device, can be merged with the records of another call (another seed: 2 K independent samples) and resolved
+ * to a colour and a noise figure.  A sampling policy -- refine where the noise is high, stop when converged -- is the caller's
+ * (tools/render_progressive.py is one): the library supplies the statistics, not the policy.
+ *
+ * The record, ACN_STATS_STRIDE doubles, 64 bytes; buffers of records must be 16-byte aligned (they are moved 16 bytes at a time):
+ *   [ 0 ]       n     samples behind the record, stored as a double.  A record whose [ 0 ] is not a finite number >= 1 is EMPTY
+ *                     (a zero-filled buffer is all EMPTY records)
+ *   [ 1 .. 3 ]  mean  linear radiance per channel
+ *   [ 4 .. 6 ]  m2    sum over the samples of ( L_k.c - mean.c )^2 per channel
+ *   [ 7 ]       0     reserved
+ * Everything is IEEE binary64 without contraction, a / b is IEEE division, sqrt is acn_sqrt of csrc/acn_detmath.h, a sum a + b + c is
+ * ( a + b ) + c, lum( c ) = ( 0.2126 * c.x + 0.7152 * c.y ) + 0.0722 * c.z.  Derived from a record:
+ *   vm.c  = n > 1 ? ( m2.c / ( n - 1 ) ) / n : none                      the variance of the mean
+ *   noise = n > 1 ? acn_sqrt( ( ( 0.2126 * 0.2126 ) * vm.x + ( 0.7152 * 0.7152 ) * vm.y ) + ( 0.0722 * 0.0722 ) * vm.z )
+ *                   / ( |lum( mean )| + ACN_STATS_NOISE_FLOOR ) : +inf       the standard error of the luminance, relative
+ *
+ * acn_render_lens_stats* behave exactly as acn_render_lens* do -- slices, buffers, streams, cancel, stage counters, out_rgb saturated
+ * or linear by ACN_OPT_LINEAR_OUT and bit for bit what acn_render_lens* writes -- except that out_rgb may be null and that every
+ * position also gets its record, which is always linear:
+ *   n      = K
+ *   mean.c = ( ( ( 0.0 + L0.c ) + L1.c ) + ... ) / ( double )K               the bits of acn_render_lens with ACN_OPT_LINEAR_OUT
+ *   m2.c   = ( ( 0.0 + d0 * d0 ) + d1 * d1 ) + ...,  dk = Lk.c - mean.c      in the order of k: a second pass over the K samples,
+ *                                                                            not the s2 / n - m * m form
+ * A slice holds all K samples of each of its positions; a record does not depend on which positions share a wavefront, a workgroup
+ * or a slice.  ACN_ERR_ARG, on the host before anything is written, acn_last_error set: everything acn_render_lens* refuses; a null
+ * stats buffer with n > 0; a stats buffer that is not 16-byte aligned; ACN_SHARD_SAMPLES with shard_world > 1 (deviations of partial
+ * radiances mean nothing).
+ *
+ * acn_lens_stats_merge*: for j in [ 0, n_part ), i = index ? index[ j ] : j, a = acc[ i ], b = part[ j ]:
+ *   b EMPTY:  acc[ i ] is untouched.     a EMPTY:  acc[ i ] = b, bit for bit (a zero-filled accumulator is a valid start).     Else
+ *   n      = na + nb
+ *   dl.c   = mean_b.c - mean_a.c
+ *   mean.c = mean_a.c + dl.c * ( nb / n )
+ *   m2.c   = ( m2_a.c + m2_b.c ) + ( dl.c * dl.c ) * ( ( na * nb ) / n )
+ *   [ 7 ]  = 0
+ * A merged mean is NOT the bits of one call with na + nb samples: it equals that call to rounding (and the samples of two seeds are
+ * other samples than those of one seed anyway).  A null index requires n_part <= n_acc.  In the _dev form an index outside
+ * [ 0, n_acc ) is skipped -- nothing is read or written for it -- so the call never faults and never synchronises a caller's stream;
+ * duplicate indices leave the records at those indices, and only those, unspecified.  The host form checks the indices first and
+ * refuses any that is out of range or comes twice with ACN_ERR_ARG, nothing written.  d_index: int64_t [ n_part ] on the device.
+ * acn_lens_stats_resolve_dev: out_rgb (nullable) [ n ][ 3 ] = mean, through cl_s_sat unless ACN_OPT_LINEAR_OUT; an EMPTY record gives
+ * the scene's background_color the same way.  out_noise (nullable) [ n ] = noise as above; EMPTY or n == 1 gives +inf.
+ * Of opts, merge and resolve use `stream` (NULL: the handle's own, and then the call waits; a caller's stream is never synchronised)
+ * and resolve `flags`; shard_world > 1 is ACN_ERR_ARG, as are a null handle or buffer and a buffer that is not 16-byte aligned.
+ *
+ * acn_denoise_stats*: the filter of acn_denoise with the measured variance in place of the spatial guess -- steps 1 and 2 change,
+ * steps 3 and 4, the parameters, the scratch memory (128 bytes per pixel) and the stream rules are those of acn_denoise.
+ * 1 demodulate   L of a pixel is its record's mean.  An EMPTY record makes the pixel not FILTERABLE, and its output is the linear
+ *                resolve above: background_color.  Else as in acn_denoise: a, c = L / a, FILTERABLE, MATCH, N, P.
+ * 2 variance     var_raw = n > 1 ? ( ( 0.2126 * 0.2126 ) * ( vm.x / ( a.x * a.x ) ) + ( 0.7152 * 0.7152 ) * ( vm.y / ( a.y * a.y ) ) )
+ *                                  + ( 0.0722 * 0.0722 ) * ( vm.z / ( a.z * a.z ) ) : none          (a negative var_raw counts as none)
+ *                Over the 3 x 3 window around the pixel, rows outer, left to right, g = { 1/4, 1/2, 1/4 }: the in-image filterable
+ *                pixels that match it and have a var_raw, itself included if it has one:
+ *                sw += g[ j ] * g[ i ];  sv += ( g[ j ] * g[ i ] ) * var_raw'.     var = sw > 0 ? sv / sw : 0.
+ *                So a pixel with one sample borrows the variance of its neighbours, and a pixel with no measured neighbour has
+ *                var = 0: it is not smoothed across luminance.
+ * ACN_ERR_ARG: what acn_denoise_dev refuses, and a d_stats that is not 16-byte aligned.  out_rgb is [ height * width ][ 3 ], linear.
+ * What the call is for: frames of acn_render_lens_stats* with ACN_LENS_JITTER and a closed or small aperture.  With a wide aperture
+ * the pinhole surface records do not describe the blurred frame; like acn_denoise it is biased where a texture edge is not in the albedo. */
+#define ACN_STATS_STRIDE 8      /* doubles per record: 64 bytes */
+#define ACN_STATS_NOISE_FLOOR 0.01
+int acn_render_lens_stats_dev          ( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm,
+                                         void* d_out_rgb /* nullable */, void* d_stats, const acn_render_opts* opts );
+int acn_render_lens_stats_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm,
+                                         void* d_out_rgb /* nullable */, void* d_stats, const acn_render_opts* opts );
+int acn_render_lens_stats              ( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm,
+                                         double* out_rgb /* nullable */, double* stats, const acn_render_opts* opts );
+int acn_lens_stats_merge_dev  ( acn_scene_handle* h, void* d_acc, size_t n_acc, const void* d_part, size_t n_part,
+                                const int64_t* d_index /* nullable */, const acn_render_opts* opts );
+int acn_lens_stats_merge      ( acn_scene_handle* h, double* acc, size_t n_acc, const double* part, size_t n_part,
+                                const int64_t* index /* nullable */, const acn_render_opts* opts );
+int acn_lens_stats_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb /* nullable */,
+                                void* d_out_noise /* nullable, [ n ] f64 */, const acn_render_opts* opts );
+int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                           const acn_denoise_params* prm /* nullable: defaults */, void* d_out_rgb, const acn_render_opts* opts );
+int acn_denoise_stats    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                           const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
+
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );
 

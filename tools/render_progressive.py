@@ -1,0 +1,158 @@
+#!/usr/bin/env python3
+"""A frame of an Actinon scene rendered in passes that go where the frame is still noisy (acn_render_lens_stats, acn_lens_stats_*).
+
+    python tools/render_progressive.py SCENE OUT.pnm --samples K --passes P --target-noise T [--denoise] [--noise-map FILE]
+                                       [--aperture A --focus D --width W --height H --path-samples P --direct-samples D]
+
+SCENE is an .acn script (the scene of its first create_image) or a flattened scene .npz, as for tools/render_panorama.py.
+Pass 0 renders every pixel with K jittered lens samples, seed 0, into an accumulator of per-pixel sample statistics on the device.
+Pass p > 0 takes the pixels whose resolved noise -- the standard error of the mean's luminance, relative to that luminance
+(include/actinon_hip.h) -- exceeds T, renders only those with seed p and merges their records into the accumulator by index.  The
+tool stops after P passes or when no pixel is left, resolves the accumulator (--denoise: acn_denoise_stats first, guided by the
+frame's surface records and the measured variance), and writes a P6 PNM.  --noise-map writes the final noise per pixel as a [H,W]
+float64 .npy.  Ray counts are printed pass by pass.
+
+Stopping on the samples' own variance is slightly biased toward dark estimates: a pixel whose first samples happen to come out
+dark and alike looks converged and keeps its dark mean, while one whose samples come out bright is refined.  That is why the
+policy lives here, in a tool a caller can read and change, and not in the library, which supplies the statistics alone."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from render_panorama import load_scene  # noqa: E402,F401  (the scene of a script or an .npz)
+
+
+def select(d_noise, target):
+    """the pixels of the next pass: int64 indices, ascending, of the entries of d_noise above target (on d_noise's device)"""
+    import torch
+    return torch.nonzero(d_noise > target).reshape(-1)
+
+
+def centres(idx, width):
+    """pixel centres [m,2] float64 of pixel indices idx of a raster `width` wide (on idx's device)"""
+    import torch
+    return torch.stack([(idx % width).to(torch.float64) + 0.5, torch.div(idx, width, rounding_mode="floor").to(torch.float64) + 0.5], dim=1).contiguous()
+
+
+def sync(dev):
+    import torch
+    if dev.type == "cuda":
+        torch.cuda.synchronize(dev)
+
+
+def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=print):
+    """-> the accumulator [n,8] and the noise [n] as tensors on dev, and the rays of every pass.  h: an actinon_amd.Handle"""
+    import torch
+    lens = dict(lens or {})
+    n = width * height
+    d_acc = torch.zeros((n, 8), dtype=torch.float64, device=dev)
+    d_noise = torch.empty((n,), dtype=torch.float64, device=dev)
+    sync(dev)
+    h.render_lens_stats_main_pass_dev(0, n, None, d_acc.data_ptr(), linear=True, samples=samples, seed=0, **lens)
+    rays = [n * samples]
+    log(f"pass 0: {n} pixels, {rays[0]} rays")
+    for p in range(1, passes):
+        h.lens_stats_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), linear=True)
+        idx = select(d_noise, target)
+        m = int(idx.numel())
+        if m == 0:
+            log(f"pass {p}: no pixel above {target}")
+            break
+        d_pos = centres(idx, width)
+        d_part = torch.empty((m, 8), dtype=torch.float64, device=dev)
+        sync(dev)
+        h.render_lens_stats_dev(d_pos.data_ptr(), m, None, d_part.data_ptr(), linear=True, samples=samples, seed=p, **lens)
+        h.lens_stats_merge_dev(d_acc.data_ptr(), n, d_part.data_ptr(), m, idx.data_ptr())
+        rays.append(m * samples)
+        log(f"pass {p}: {m} pixels, {rays[-1]} rays")
+    h.lens_stats_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), linear=True)
+    return d_acc, d_noise, rays
+
+
+def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0, log=print):
+    """-> the frame [H,W,3] uint8, the records [n,8], the noise [H,W] and the rays of every pass"""
+    import torch
+    import actinon_amd as A
+    w, hh = int(flat.params.image_width), int(flat.params.image_height)
+    n = w * hh
+    h = A.Handle(flat)
+    dev = torch.device("cuda", h.device)
+    d_acc, d_noise, rays = run_passes(h, w, hh, samples, passes, target, dev, lens=dict(jitter=True, aperture=aperture, focus=focus), log=log)
+    d_lin = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+    sync(dev)
+    if denoise:
+        d_pos = torch.from_numpy(A.main_pass_positions(w, hh)).to(dev)
+        d_surf = torch.empty((n, A.abi.ACN_SURF_STRIDE), dtype=torch.float64, device=dev)
+        sync(dev)
+        h.surface_positions_dev(d_pos.data_ptr(), n, d_surf.data_ptr(), follow=True)
+        h.denoise_stats_dev(d_acc.data_ptr(), d_surf.data_ptr(), w, hh, d_lin.data_ptr())
+    else:
+        h.lens_stats_resolve_dev(d_acc.data_ptr(), n, d_lin.data_ptr(), None, linear=True)
+    h.resolve_dev(d_lin.data_ptr(), n, None, d_rgb8.data_ptr())
+    out = d_rgb8.cpu().numpy().reshape(hh, w, 3), d_acc.cpu().numpy(), d_noise.cpu().numpy().reshape(hh, w), rays
+    h.close()
+    return out
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="A frame rendered in passes that go where it is still noisy (acn_render_lens_stats)")
+    ap.add_argument("scene", help=".acn script or flattened scene .npz")
+    ap.add_argument("out", help="output image, P6 PNM")
+    ap.add_argument("--samples", type=int, required=True, help="K: jittered lens samples per pixel and pass, 1 .. 4096")
+    ap.add_argument("--passes", type=int, required=True, help="P: passes at most, the first over the whole raster")
+    ap.add_argument("--target-noise", type=float, required=True, help="T: a pixel whose noise exceeds it is sampled again")
+    ap.add_argument("--denoise", action="store_true", help="filter the result with acn_denoise_stats before it is resolved")
+    ap.add_argument("--noise-map", default=None, metavar="FILE", help="write the final noise per pixel, [H,W] float64 .npy")
+    ap.add_argument("--aperture", type=float, default=0.0, help="lens radius in scene units (default 0: a pinhole with jitter)")
+    ap.add_argument("--focus", type=float, default=0.0, help="distance of the plane in focus, for an open aperture")
+    ap.add_argument("--width", type=int, default=None)
+    ap.add_argument("--height", type=int, default=None)
+    ap.add_argument("--path-samples", type=int, default=None)
+    ap.add_argument("--direct-samples", type=int, default=None)
+    args = ap.parse_args(argv)
+    if not 1 <= args.samples <= 4096:
+        ap.error("--samples is 1 .. 4096")
+    if args.passes < 1:
+        ap.error("--passes is at least 1")
+    if not args.target_noise >= 0:
+        ap.error("--target-noise is not negative")
+    if args.aperture < 0 or (args.aperture > 0 and not args.focus > 0):
+        ap.error("the aperture is not negative and the focus distance of an open aperture is positive")
+    for value in (args.width, args.height, args.path_samples, args.direct_samples):
+        if value is not None and value < 0:
+            ap.error("sample counts and sizes are not negative")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from render_aovs import write_pnm
+    flat = load_scene(args.scene)
+    prm = flat.params
+    for name, value in (("path_samples", args.path_samples), ("direct_samples", args.direct_samples),
+                        ("image_width", args.width), ("image_height", args.height)):
+        if value is not None:
+            setattr(prm, name, value)
+    if prm.image_width < 1 or prm.image_height < 2:
+        sys.exit("the image needs a width of at least 1 and a height of at least 2")
+    out8, records, noise, rays = render(flat, args.samples, args.passes, args.target_noise, denoise=args.denoise,
+                                        aperture=args.aperture, focus=args.focus)
+    write_pnm(args.out, np.ascontiguousarray(out8))
+    if args.noise_map:
+        with open(args.noise_map, "wb") as f:
+            np.save(f, noise)
+    pixels = int(prm.image_width) * int(prm.image_height)
+    print(f"{args.out}: {prm.image_width}x{prm.image_height}, {len(rays)} passes of {args.samples} samples, {sum(rays)} rays "
+          f"({sum(rays) / (args.passes * args.samples * pixels):.3f} of {args.passes} full passes), "
+          f"{int((noise > args.target_noise).sum())} pixels still above {args.target_noise}")
+
+
+if __name__ == "__main__":
+    main()
