@@ -28,6 +28,9 @@ ACN_LENS_SEED = 2718281828
 ACN_STATS_STRIDE = 8
 ACN_STATS_NOISE_FLOOR = 0.01
 
+# selecting positions by a key (acn_select_above, acn_key_histogram): bins of the histogram, its words (the last counts NaN keys)
+ACN_KEY_HIST_BINS, ACN_KEY_HIST_WORDS = 256, 257
+
 ACN_OK, ACN_ERR_ARG, ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV, ACN_ERR_DEVICE, ACN_ERR_CANCELLED = 0, -1, -2, -3, -4, -5
 
 NODE_TYPES = {1: "plane", 2: "sphere", 3: "squaroid", 4: "distance", 5: "pair_inside", 6: "pair_outside",
@@ -83,6 +86,11 @@ class LensParams(C.Structure):
                 ("aperture_radius", C.c_double), ("focus_distance", C.c_double)]
 
 
+class SelectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_double), ("capacity", C.c_uint64),
+                ("raster_width", C.c_uint64), ("raster_first", C.c_uint64)]
+
+
 class V3(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
 
@@ -101,3 +109,4 @@ class SceneStruct(C.Structure):
 assert C.sizeof(Node) == 304, C.sizeof(Node)
 assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
 assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)
+assert C.sizeof(SelectParams) == 40, C.sizeof(SelectParams)

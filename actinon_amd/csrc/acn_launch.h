@@ -109,6 +109,16 @@ void acn_launch_stats_merge( double* acc, size_t n_acc, const double* part, size
 void acn_launch_stats_resolve( const double* stats, size_t n, const double* background, double gamma, int linear, double* out_rgb,
                                double* out_noise, hipStream_t stream );
 
+/* acn_select_above* and acn_key_histogram* (k_select.hip), after the host's checks (acn_select_host.h); n >= 1.
+ * select: three launches -- the count per tile of ACN_SELECT_TILE entries, the exclusive scan of the counts, the scatter (left out
+ * when capacity is 0 or both out buffers are null).  tiles: acn_select_tiles( n ) + 1 words of the handle; the last one and
+ * *out_count (nullable, device) receive the total.  raster_width > 0 whenever src_pos_xy is null and out_pos_xy is not.
+ * key_hist: adds the bins of the keys to out_hist [ ACN_KEY_HIST_WORDS ], which the caller has zeroed on the same stream. */
+void acn_launch_select( const double* key, size_t n, double threshold, unsigned long long* tiles, unsigned long long capacity,
+                        const double* src_pos_xy, unsigned long long raster_width, unsigned long long raster_first, int64_t* out_index,
+                        double* out_pos_xy, unsigned long long* out_count, hipStream_t stream );
+void acn_launch_key_hist( const double* key, size_t n, unsigned long long* out_hist, hipStream_t stream );
+
 /* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
 struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
 int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */

@@ -18,6 +18,7 @@
 #include "acn_tables.h"
 #include "acn_chunkplan.h"
 #include "acn_stats_host.h"
+#include "acn_select_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* error plumbing */
@@ -249,6 +250,7 @@ struct acn_scene_handle
     uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
     void* d_denoise = nullptr; size_t denoise_bytes = 0;                                    /* acn_denoise: guides and colour buffers, apart from the render workspace */
     double* d_lens_rays = nullptr; double* d_lens_rad = nullptr; size_t lens_cap = 0;       /* acn_render_lens*: the rays [ 6 ] and the radiance [ 3 ] of a slice, lens_cap rays each */
+    unsigned long long* d_select_tiles = nullptr; size_t select_tiles_cap = 0;              /* acn_select_above*: the counts per tile and their total, select_tiles_cap words */
     bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
     std::string lane_error;
     bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
@@ -589,6 +591,7 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( h->d_denoise ) hipFree( h->d_denoise );
     if( h->d_lens_rays ) hipFree( h->d_lens_rays );
     if( h->d_lens_rad ) hipFree( h->d_lens_rad );
+    if( h->d_select_tiles ) hipFree( h->d_select_tiles );
     if( !h->is_lane )   /* a lane borrows the resident scene of its parent */
     {
         if( h->scene.d_nodes ) hipFree( h->scene.d_nodes );
@@ -2225,6 +2228,108 @@ extern "C" int acn_denoise_stats( acn_scene_handle* h, const double* stats, cons
     HIP_TRY( hipMemcpy( out_rgb, d_rgb, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) );
     return ACN_OK;
 }
+
+/* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */
+extern "C" int acn_select_above_dev( acn_scene_handle* h, const void* d_key, size_t n, const acn_select_params* prm, const void* d_src_pos_xy,
+                                     void* d_out_index, void* d_out_pos_xy, void* d_out_count, uint64_t* out_count, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    std::string msg;
+    acn_select_params p;
+    if( acn_select_args_check( h != nullptr, d_key, n, prm, d_src_pos_xy, d_out_index, d_out_pos_xy, opts->shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( ( uintptr_t )d_out_count % 8 ) return fail( ACN_ERR_ARG, "d_out_count is a uint64_t: align it" );
+    const uint64_t width = p.raster_width ? p.raster_width : h->dev.prm.image_width;
+    if( !d_src_pos_xy && d_out_pos_xy && width == 0 ) return fail( ACN_ERR_ARG, "raster positions need a raster_width or a scene with an image_width" );
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
+    if( n == 0 )   /* no launch */
+    {
+        if( d_out_count ) HIP_TRY( hipMemsetAsync( d_out_count, 0, sizeof( uint64_t ), stream ) );
+        if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
+        if( out_count ) *out_count = 0;
+        return ACN_OK;
+    }
+    const size_t words = ( size_t )acn_select_tiles( n ) + 1;
+    if( h->select_tiles_cap < words )
+    {
+        if( h->d_select_tiles ) hipFree( h->d_select_tiles );   /* (waits for whatever still reads them) */
+        h->d_select_tiles = nullptr; h->select_tiles_cap = 0;
+        HIP_TRY( hipMalloc( &h->d_select_tiles, sizeof( unsigned long long ) * words ) );
+        h->select_tiles_cap = words;
+    }
+    acn_launch_select( ( const double* )d_key, n, p.threshold, h->d_select_tiles, p.capacity, ( const double* )d_src_pos_xy, width, p.raster_first,
+                       ( int64_t* )d_out_index, ( double* )d_out_pos_xy, ( unsigned long long* )d_out_count, stream );
+    HIP_TRY( hipGetLastError() );
+    if( out_count )   /* the one synchronisation of a caller's stream */
+    {
+        unsigned long long total = 0;
+        HIP_TRY( hipMemcpyAsync( &total, h->d_select_tiles + ( words - 1 ), sizeof( total ), hipMemcpyDeviceToHost, stream ) );
+        HIP_TRY( hipStreamSynchronize( stream ) );
+        *out_count = total;
+    }
+    else if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_select_above( acn_scene_handle* h, const double* key, size_t n, const acn_select_params* prm, const double* src_pos_xy,
+                                 int64_t* out_index, double* out_pos_xy, uint64_t* out_count )
+{
+    std::string msg;
+    acn_select_params p;
+    if( acn_select_args_check( h != nullptr, key, n, prm, src_pos_xy, out_index, out_pos_xy, 0, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) { if( out_count ) *out_count = 0; return ACN_OK; }
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t cap = ( size_t )( p.capacity < n ? p.capacity : n );   /* (no more than n are ever selected) */
+    DevCopies dc;
+    void* d_key = dc.make( key, sizeof( double ) * n );
+    void* d_src = src_pos_xy ? dc.make( src_pos_xy, sizeof( double ) * 2 * n ) : nullptr;
+    void* d_index = out_index && cap ? dc.make( nullptr, sizeof( int64_t ) * cap ) : nullptr;
+    void* d_pos = out_pos_xy && cap ? dc.make( nullptr, sizeof( double ) * 2 * cap ) : nullptr;
+    if( !d_key || ( src_pos_xy && !d_src ) || ( out_index && cap && !d_index ) || ( out_pos_xy && cap && !d_pos ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    acn_select_params q = p;
+    q.struct_size = ( uint32_t )sizeof( q );
+    q.capacity = ( d_index || d_pos ) ? cap : 0;
+    uint64_t total = 0;
+    int st = acn_select_above_dev( h, d_key, n, &q, d_src, d_index, d_pos, nullptr, &total, nullptr );
+    if( st != ACN_OK ) return st;
+    const size_t wrote = ( size_t )( total < q.capacity ? total : q.capacity );
+    if( d_index && wrote ) HIP_TRY( hipMemcpy( out_index, d_index, sizeof( int64_t ) * wrote, hipMemcpyDeviceToHost ) );
+    if( d_pos && wrote ) HIP_TRY( hipMemcpy( out_pos_xy, d_pos, sizeof( double ) * 2 * wrote, hipMemcpyDeviceToHost ) );
+    if( out_count ) *out_count = total;
+    return ACN_OK;
+}
+
+extern "C" int acn_key_histogram_dev( acn_scene_handle* h, const void* d_key, size_t n, void* d_out_hist, const acn_render_opts* opts )
+{
+    ACN_OPTS_VIEW
+    std::string msg;
+    if( acn_key_hist_args_check( h != nullptr, d_key, n, d_out_hist, opts->shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    HIP_TRY( hipSetDevice( h->device ) );
+    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
+    HIP_TRY( hipMemsetAsync( d_out_hist, 0, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS, stream ) );
+    if( n ) acn_launch_key_hist( ( const double* )d_key, n, ( unsigned long long* )d_out_hist, stream );
+    HIP_TRY( hipGetLastError() );
+    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_key_histogram( acn_scene_handle* h, const double* key, size_t n, uint64_t* out_hist )
+{
+    std::string msg;
+    if( acn_key_hist_args_check( h != nullptr, key, n, out_hist, 0, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    HIP_TRY( hipSetDevice( h->device ) );
+    DevCopies dc;
+    void* d_key = dc.make( key, sizeof( double ) * n );
+    void* d_hist = dc.make( nullptr, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS );
+    if( !d_key || !d_hist ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    int st = acn_key_histogram_dev( h, d_key, n, d_hist, nullptr );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipMemcpy( out_hist, d_hist, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS, hipMemcpyDeviceToHost ) );
+    return ACN_OK;
+}
+
+extern "C" double acn_key_hist_edge( uint32_t bin ) { return acn_select_hist_edge( bin ); }
+extern "C" double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget ) { return acn_select_hist_threshold( hist, budget ); }
 
 extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )
 {

@@ -576,6 +576,58 @@ class Handle:
         check(hip.acn_denoise_stats_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)),
               "acn_denoise_stats_dev")
 
+    # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
+    @staticmethod
+    def select_params(threshold, capacity=0, raster_width=0, raster_first=0):
+        p = abi.SelectParams()
+        p.struct_size = C.sizeof(abi.SelectParams)
+        p.threshold, p.capacity, p.raster_width, p.raster_first = threshold, capacity, raster_width, raster_first
+        return p
+
+    def select_above_dev(self, d_key_ptr, n, threshold, capacity, d_index_ptr=None, d_pos_ptr=None, d_src_pos_ptr=None, raster_width=0,
+                         raster_first=0, d_count_ptr=None, want_count=True, stream=None):
+        """The entries of the device keys [n] float64 above threshold, in ascending order (acn_select_above_dev): their indices into
+        d_index int64 [capacity] and their positions into d_pos [capacity,2] float64 (either may be None) -- gathered from d_src_pos
+        [n,2], or the pixel centres raster_first + i of a raster raster_width wide (0: the scene's).  The total goes to d_count
+        (uint64 on the device, or None) and, with want_count, is returned, which synchronises `stream` once; else None is returned."""
+        p = self.select_params(threshold, capacity, raster_width, raster_first)
+        o = self._plain_opts(False, stream)
+        count = C.c_uint64(0)
+        check(hip.acn_select_above_dev(self.h, d_key_ptr, n, C.byref(p), d_src_pos_ptr, d_index_ptr, d_pos_ptr, d_count_ptr,
+                                       C.byref(count) if want_count else None, C.byref(o)), "acn_select_above_dev")
+        return int(count.value) if want_count else None
+
+    def select_above(self, key, threshold, src_pos=None, raster_width=0, raster_first=0, capacity=None):
+        """acn_select_above on host arrays: key [n] float64 -> ( index int64 [m], pos [m,2] float64, count ), m = min( count, capacity );
+        capacity None: n.  count is the total selected, also beyond the capacity."""
+        k = np.ascontiguousarray(key, dtype=np.float64).reshape(-1)
+        n = k.shape[0]
+        cap = n if capacity is None else int(capacity)
+        src = None if src_pos is None else np.ascontiguousarray(src_pos, dtype=np.float64).reshape(-1, 2)
+        if src is not None and src.shape[0] != n:
+            raise ValueError(f"{n} keys need {n} positions, got {src.shape[0]}")
+        room = min(cap, n)
+        index = np.empty((room,), dtype=np.int64)
+        pos = np.empty((room, 2), dtype=np.float64)
+        p = self.select_params(threshold, cap, raster_width, raster_first)
+        count = C.c_uint64(0)
+        check(hip.acn_select_above(self.h, k.ctypes.data, n, C.byref(p), None if src is None else src.ctypes.data,
+                                   index.ctypes.data if room else None, pos.ctypes.data if room else None, C.byref(count)), "acn_select_above")
+        m = min(int(count.value), room)
+        return index[:m], pos[:m], int(count.value)
+
+    def key_histogram_dev(self, d_key_ptr, n, d_hist_ptr, stream=None):
+        """The exact histogram of device keys [n] float64 into d_hist uint64 [257], overwritten (acn_key_histogram_dev)."""
+        o = self._plain_opts(False, stream)
+        check(hip.acn_key_histogram_dev(self.h, d_key_ptr, n, d_hist_ptr, C.byref(o)), "acn_key_histogram_dev")
+
+    def key_histogram(self, key):
+        """acn_key_histogram on a host array: key [n] float64 -> uint64 [257]; word 256 counts the NaN keys."""
+        k = np.ascontiguousarray(key, dtype=np.float64).reshape(-1)
+        hist = np.empty((abi.ACN_KEY_HIST_WORDS,), dtype=np.uint64)
+        check(hip.acn_key_histogram(self.h, k.ctypes.data, k.shape[0], hist.ctypes.data), "acn_key_histogram")
+        return hist
+
     def pick(self, x, y):
         """The object under sample position (x, y): None on a miss, else node (enter object if any, else exit object), its
         type name, distance and position."""
@@ -680,6 +732,20 @@ def main_pass_positions(width, height, first=0, count=None):
     pos[:, 0] = (idx % width) + 0.5
     pos[:, 1] = (idx // width) + 0.5
     return pos
+
+
+def key_hist_edge(bin):
+    """The lower edge of bin `bin` of acn_key_histogram (acn_key_hist_edge): -inf for bin 0, NaN above 255.  No GPU."""
+    return float(hip.acn_key_hist_edge(int(bin)))
+
+
+def key_hist_threshold(hist, budget):
+    """The threshold above which at most `budget` of the keys behind `hist` (uint64 [257]) lie (acn_key_hist_threshold): the edge
+    of the lowest bin from which upward the counts fit the budget, +inf if none does.  No GPU."""
+    hh = np.ascontiguousarray(hist, dtype=np.uint64).reshape(-1)
+    if hh.shape[0] != abi.ACN_KEY_HIST_WORDS:
+        raise ValueError(f"a key histogram has {abi.ACN_KEY_HIST_WORDS} words, got {hh.shape[0]}")
+    return float(hip.acn_key_hist_threshold(hh.ctypes.data, int(budget)))
 
 
 def cps_from_cl(rgb):

@@ -535,6 +535,83 @@ int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void*
 int acn_denoise_stats    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
 
+/* Selecting positions by a key on the device (k_select.hip): the step between acn_lens_stats_resolve_dev, which leaves a noise
+ * figure per pixel in d_out_noise, and acn_render_lens_stats_dev / acn_lens_stats_merge_dev, which take an ordered index list and
+ * a position list.  The library supplies the two primitives every refinement policy needs and decides nothing itself: an ordered
+ * selection of the entries above a threshold, and an exact histogram of the keys from which a caller derives a threshold that
+ * fits a ray budget without a sort.
+ *
+ * acn_select_above*: entry i of key [ n ] f64 is SELECTED iff key[ i ] > threshold, an IEEE comparison of doubles: a NaN key is
+ * never selected, a +inf key is whenever threshold < +inf, -0.0 is not above 0.0.
+ *   Ranks      with s_0 < s_1 < ... the selected indices in ascending order, out_index[ r ] = s_r for r < min( count, capacity )
+ *   Positions  with src_pos_xy [ n ][ 2 ]:  out_pos_xy[ r ] = src_pos_xy[ s_r ], bit for bit.  Without it, W = raster_width, or the
+ *              scene's image_width when that is 0, and p = raster_first + s_r:
+ *                out_pos_xy[ r ] = ( ( double )( p % W ) + 0.5, ( double )( p / W ) + 0.5 )
+ *              both exact in binary64 (raster_first + n <= 2^52), and with raster_width 0 the bits of the positions of pixel p in
+ *              acn_render_main_pass_dev and acn_render_lens_stats_main_pass_dev
+ *   Counts     d_out_count (device) and out_count (host), each nullable, receive the TOTAL number selected, also when it exceeds
+ *              capacity: the caller sees that the list was cut.  Nothing is written at or beyond entry `capacity` of an out
+ *              buffer, nor at or beyond entry `count`.  capacity == 0 with null out buffers is a pure count; either out buffer
+ *              alone may be null
+ *   Independence  a result depends on the keys, the threshold and the capacity alone: not on which entries share a wavefront, a
+ *              workgroup or a tile, nor on the order in which workgroups run
+ *   Streams    the work goes to opts->stream; NULL: the handle's own stream, and the call waits.  On a caller's stream the call
+ *              synchronises that stream exactly once, and only when out_count is given (as acn_render_rays_dev does for its check
+ *              word); with out_count == NULL it never synchronises.  Of opts only `stream` is used; shard_world > 1 is ACN_ERR_ARG
+ *   Errors     ACN_ERR_ARG, checked on the host before anything is written, acn_last_error set: a null handle; a null key with
+ *              n > 0; n > 2^31; a null prm (the threshold has no default); struct_size < 16; any flags bit; a NaN threshold;
+ *              capacity > 0 with both out buffers null; shard_world > 1; a buffer that is not 8-byte aligned; raster positions
+ *              asked for with raster_first + n > 2^52.  n == 0 is ACN_OK with count 0 and no launch
+ *   Isolation  a select call uses no work queue and changes nothing a render call sees: acn_last_stage_ms, acn_last_counters and
+ *              acn_last_kernel_ms stay what they were, [ 23 ] and [ 24 ] included
+ * Three launches: a count per tile of 2048 entries, an exclusive scan of the tile counts by one workgroup, a scatter that recomputes
+ * the predicate.  The handle owns the tile counts (8 bytes per tile), apart from the render workspace, the denoiser's scratch and
+ * the lens buffers, grown on demand, freed by acn_scene_free; select calls on one handle must therefore not overlap each other.
+ * Indices and counts are 64-bit.  The host form copies min( count, capacity ) entries back and nothing beyond them.
+ *
+ * acn_key_histogram*: out_hist [ ACN_KEY_HIST_WORDS ] uint64, overwritten (the call zeroes it itself, on the stream).  The word of
+ * a key from its raw bits u, with LO = ( 1023 - 40 ) * 4:
+ *   NaN (either sign)             word 256
+ *   the sign bit set              bin 0 (-0.0 and -inf included)
+ *   else, e = u >> 50             (the exponent and the two top mantissa bits: monotone in the key)
+ *                                 bin = e < LO ? 0 : min( e - LO + 1, 255 )
+ * Four bins per octave from 2^-40 upward; bin 0 is everything below 2^-40, bin 255 everything from its edge upward, +inf included.
+ * The counts are exact integers and sum to n.  Streams as for acn_select_above_dev, except that this call never synchronises a
+ * caller's stream.  ACN_ERR_ARG: a null handle, key (n > 0) or out_hist; n > 2^31; shard_world > 1; a buffer not 8-byte aligned.
+ * n == 0 gives 257 zeros.
+ * acn_key_hist_edge( j ): the lower edge of bin j, the double whose bits are ( uint64_t )( LO + j - 1 ) << 50 for j in 1 .. 255;
+ * -inf for j = 0; NaN for j > 255.  No GPU, no error state.
+ * acn_key_hist_threshold( hist, budget ): edge( j ) of the smallest j >= 1 with hist[ j ] + ... + hist[ 255 ] <= budget, +inf if
+ * there is none (NaN for a null hist).  No GPU, no error state.  By construction acn_select_above with that threshold selects at
+ * most `budget` entries: those of bins j .. 255 except the keys equal to edge( j ), which fall out (strict >).  With +inf nothing is
+ * selected.  Records with one sample have noise +inf and sit in bin 255, so a budget that is to reach any pixel must be at least as
+ * large as their number. */
+typedef struct acn_select_params
+{
+    uint32_t struct_size;    /* sizeof as the CALLER was compiled; nothing beyond it is read; < 16 is ACN_ERR_ARG */
+    uint32_t flags;          /* none defined: any set bit is ACN_ERR_ARG */
+    double   threshold;      /* entry i is SELECTED iff key[ i ] > threshold (IEEE: a NaN key is never selected; +inf is,
+                                whenever threshold < +inf).  A NaN threshold is ACN_ERR_ARG */
+    uint64_t capacity;       /* entries the out buffers hold; results of rank >= capacity are not written */
+    uint64_t raster_width;   /* positions without src_pos_xy: pixel centres of a raster this wide; 0 = the scene's image_width */
+    uint64_t raster_first;   /* ... whose pixel `raster_first + i` is entry i */
+} acn_select_params;
+#define ACN_SELECT_PARAMS_INIT { ( uint32_t )sizeof( acn_select_params ), 0u, 0.0, 0u, 0u, 0u }
+#define ACN_KEY_HIST_BINS 256
+#define ACN_KEY_HIST_WORDS 257      /* [ 256 ]: NaN keys */
+int acn_select_above_dev( acn_scene_handle* h, const void* d_key /* [ n ] f64 */, size_t n, const acn_select_params* prm,
+                          const void* d_src_pos_xy /* nullable [ n ][ 2 ] */, void* d_out_index /* nullable int64 [ capacity ] */,
+                          void* d_out_pos_xy /* nullable [ capacity ][ 2 ] f64 */, void* d_out_count /* nullable uint64 on the device */,
+                          uint64_t* out_count /* nullable, host */, const acn_render_opts* opts );
+int acn_select_above    ( acn_scene_handle* h, const double* key, size_t n, const acn_select_params* prm,
+                          const double* src_pos_xy /* nullable */, int64_t* out_index /* nullable */, double* out_pos_xy /* nullable */,
+                          uint64_t* out_count /* nullable */ );
+int acn_key_histogram_dev( acn_scene_handle* h, const void* d_key, size_t n, void* d_out_hist /* uint64 [ 257 ], overwritten */,
+                           const acn_render_opts* opts );
+int acn_key_histogram    ( acn_scene_handle* h, const double* key, size_t n, uint64_t* out_hist );
+double acn_key_hist_edge( uint32_t bin );                                  /* no GPU */
+double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget );   /* no GPU */
+
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );
 

@@ -2,6 +2,7 @@
 """A frame of an Actinon scene rendered in passes that go where the frame is still noisy (acn_render_lens_stats, acn_lens_stats_*).
 
     python tools/render_progressive.py SCENE OUT.pnm --samples K --passes P --target-noise T [--denoise] [--noise-map FILE]
+                                       [--select torch|library] [--rays-per-pass B]
                                        [--aperture A --focus D --width W --height H --path-samples P --direct-samples D]
 
 SCENE is an .acn script (the scene of its first create_image) or a flattened scene .npz, as for tools/render_panorama.py.
@@ -11,6 +12,12 @@ Pass p > 0 takes the pixels whose resolved noise -- the standard error of the me
 tool stops after P passes or when no pixel is left, resolves the accumulator (--denoise: acn_denoise_stats first, guided by the
 frame's surface records and the measured variance), and writes a P6 PNM.  --noise-map writes the final noise per pixel as a [H,W]
 float64 .npy.  Ray counts are printed pass by pass.
+
+--select library takes the pixels of a pass with acn_select_above_dev -- the indices and the pixel centres in one call, as a C host
+would -- instead of torch.nonzero and a torch.stack; the passes are the same, bit for bit.  --rays-per-pass B bounds every pass after
+the first: the pass takes the histogram of the noise (acn_key_histogram_dev), T_B = acn_key_hist_threshold( hist, B // K ) and selects
+above max( T, T_B ), so it casts at most B rays, on the noisiest pixels.  Pixels with one sample have noise +inf and are taken only
+by a budget at least as large as their number.
 
 Stopping on the samples' own variance is slightly biased toward dark estimates: a pixel whose first samples happen to come out
 dark and alike looks converged and keeps its dark mean, while one whose samples come out bright is refined.  That is why the
@@ -46,25 +53,49 @@ def sync(dev):
         torch.cuda.synchronize(dev)
 
 
-def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=print):
-    """-> the accumulator [n,8] and the noise [n] as tensors on dev, and the rays of every pass.  h: an actinon_amd.Handle"""
+def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=print, *, select_mode="torch", rays_per_pass=None, on_pass=None):
+    """-> the accumulator [n,8] and the noise [n] as tensors on dev, and the rays of every pass.  h: an actinon_amd.Handle.
+    select_mode "library": the pixels of a pass come from h.select_above_dev, not from select and centres.  rays_per_pass B: a pass
+    after the first selects above max( target, key_hist_threshold( histogram of the noise, B // samples ) ).
+    on_pass( p, threshold, idx, d_noise ): called for every pass after the first with its threshold, the selected indices and the noise
+    they were selected from (tensors on dev)"""
     import torch
     lens = dict(lens or {})
     n = width * height
     d_acc = torch.zeros((n, 8), dtype=torch.float64, device=dev)
     d_noise = torch.empty((n,), dtype=torch.float64, device=dev)
+    budget = None if rays_per_pass is None else int(rays_per_pass) // samples
+    if budget is not None:
+        import actinon_amd as A
+        d_hist = torch.zeros((A.abi.ACN_KEY_HIST_WORDS,), dtype=torch.int64, device=dev)
+    if select_mode == "library":
+        room = n if budget is None else min(n, budget)
+        d_idx_all = torch.empty((max(room, 1),), dtype=torch.int64, device=dev)
+        d_pos_all = torch.empty((max(room, 1), 2), dtype=torch.float64, device=dev)
     sync(dev)
     h.render_lens_stats_main_pass_dev(0, n, None, d_acc.data_ptr(), linear=True, samples=samples, seed=0, **lens)
     rays = [n * samples]
     log(f"pass 0: {n} pixels, {rays[0]} rays")
     for p in range(1, passes):
         h.lens_stats_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), linear=True)
-        idx = select(d_noise, target)
-        m = int(idx.numel())
+        above = target
+        if budget is not None:
+            h.key_histogram_dev(d_noise.data_ptr(), n, d_hist.data_ptr())
+            above = max(target, A.key_hist_threshold(d_hist.cpu().numpy().view(np.uint64), budget))
+        if select_mode == "library":
+            m = min(h.select_above_dev(d_noise.data_ptr(), n, above, room, d_index_ptr=d_idx_all.data_ptr(), d_pos_ptr=d_pos_all.data_ptr(),
+                                       raster_width=width, raster_first=0), room)
+            idx, d_pos = d_idx_all[:m], d_pos_all[:m]
+        else:
+            idx = select(d_noise, above)
+            m = int(idx.numel())
+        if on_pass is not None:
+            on_pass(p, above, idx, d_noise)
         if m == 0:
-            log(f"pass {p}: no pixel above {target}")
+            log(f"pass {p}: no pixel above {above}")
             break
-        d_pos = centres(idx, width)
+        if select_mode != "library":
+            d_pos = centres(idx, width)
         d_part = torch.empty((m, 8), dtype=torch.float64, device=dev)
         sync(dev)
         h.render_lens_stats_dev(d_pos.data_ptr(), m, None, d_part.data_ptr(), linear=True, samples=samples, seed=p, **lens)
@@ -75,7 +106,8 @@ def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=pr
     return d_acc, d_noise, rays
 
 
-def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0, log=print):
+def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0, log=print, *, select_mode="torch", rays_per_pass=None,
+           on_pass=None):
     """-> the frame [H,W,3] uint8, the records [n,8], the noise [H,W] and the rays of every pass"""
     import torch
     import actinon_amd as A
@@ -83,7 +115,8 @@ def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0
     n = w * hh
     h = A.Handle(flat)
     dev = torch.device("cuda", h.device)
-    d_acc, d_noise, rays = run_passes(h, w, hh, samples, passes, target, dev, lens=dict(jitter=True, aperture=aperture, focus=focus), log=log)
+    d_acc, d_noise, rays = run_passes(h, w, hh, samples, passes, target, dev, lens=dict(jitter=True, aperture=aperture, focus=focus), log=log,
+                                     select_mode=select_mode, rays_per_pass=rays_per_pass, on_pass=on_pass)
     d_lin = torch.empty((n, 3), dtype=torch.float64, device=dev)
     d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
     sync(dev)
@@ -110,6 +143,10 @@ def parse_args(argv=None):
     ap.add_argument("--target-noise", type=float, required=True, help="T: a pixel whose noise exceeds it is sampled again")
     ap.add_argument("--denoise", action="store_true", help="filter the result with acn_denoise_stats before it is resolved")
     ap.add_argument("--noise-map", default=None, metavar="FILE", help="write the final noise per pixel, [H,W] float64 .npy")
+    ap.add_argument("--select", choices=("torch", "library"), default="torch",
+                    help="how the pixels of a pass are taken: torch.nonzero, or the library's acn_select_above_dev")
+    ap.add_argument("--rays-per-pass", type=int, default=None, metavar="B",
+                    help="a pass after the first casts at most B rays, on the noisiest pixels (acn_key_histogram_dev)")
     ap.add_argument("--aperture", type=float, default=0.0, help="lens radius in scene units (default 0: a pinhole with jitter)")
     ap.add_argument("--focus", type=float, default=0.0, help="distance of the plane in focus, for an open aperture")
     ap.add_argument("--width", type=int, default=None)
@@ -123,6 +160,8 @@ def parse_args(argv=None):
         ap.error("--passes is at least 1")
     if not args.target_noise >= 0:
         ap.error("--target-noise is not negative")
+    if args.rays_per_pass is not None and args.rays_per_pass < 0:
+        ap.error("--rays-per-pass is not negative")
     if args.aperture < 0 or (args.aperture > 0 and not args.focus > 0):
         ap.error("the aperture is not negative and the focus distance of an open aperture is positive")
     for value in (args.width, args.height, args.path_samples, args.direct_samples):
@@ -143,7 +182,7 @@ def main(argv=None):
     if prm.image_width < 1 or prm.image_height < 2:
         sys.exit("the image needs a width of at least 1 and a height of at least 2")
     out8, records, noise, rays = render(flat, args.samples, args.passes, args.target_noise, denoise=args.denoise,
-                                        aperture=args.aperture, focus=args.focus)
+                                        aperture=args.aperture, focus=args.focus, select_mode=args.select, rays_per_pass=args.rays_per_pass)
     write_pnm(args.out, np.ascontiguousarray(out8))
     if args.noise_map:
         with open(args.noise_map, "wb") as f:
