@@ -1,0 +1,678 @@
+/* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
+ * denoise, the thin-lens camera and its sample statistics, select and key histogram, and the two test seams acn_estimate_envelope
+ * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
+ * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points. */
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <string>
+
+#include "acn_handle.h"
+#include "acn_stats_host.h"
+#include "acn_select_host.h"
+
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* kernels */
+
+/* cl_s_sat + cps_from_cl after the (cross-GPU) accumulation */
+__global__ void k_resolve( const double* __restrict__ lin, size_t n, double gamma, double* __restrict__ out_rgb,
+                           unsigned char* __restrict__ out_rgb8 )
+{
+    size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
+    if( i >= n ) return;
+    V3 c = cl_sat( mk( lin[ i * 3 ], lin[ i * 3 + 1 ], lin[ i * 3 + 2 ] ), gamma );
+    if( out_rgb ) { out_rgb[ i * 3 ] = c.x; out_rgb[ i * 3 + 1 ] = c.y; out_rgb[ i * 3 + 2 ] = c.z; }
+    if( out_rgb8 )
+    {
+        out_rgb8[ i * 3 + 0 ] = c.x > 0.0 ? c.x < 1.0 ? ( unsigned char )( c.x * 256 ) : 255 : 0;
+        out_rgb8[ i * 3 + 1 ] = c.y > 0.0 ? c.y < 1.0 ? ( unsigned char )( c.y * 256 ) : 255 : 0;
+        out_rgb8[ i * 3 + 2 ] = c.z > 0.0 ? c.z < 1.0 ? ( unsigned char )( c.z * 256 ) : 255 : 0;
+    }
+}
+
+/* obj_ray_exit + obj_estimate_envelope (objects.c:286-363), one lane */
+__global__ void k_estimate_envelope( DevScene sc, int node, uint64_t samples, uint32_t rseed, double radius_factor,
+                                     V3* scratch, double* out )
+{
+    Cnt< false > cnt;
+    NodeP hdr = &sc.nodes[ node ];
+    uint64_t size = 0;
+    V3 sum = mk( 0, 0, 0 );
+    uint64_t rv = rseed;
+    V3 rp = ld3( hdr->pos );
+    for( uint64_t i = 0; i < samples; i++ )
+    {
+        V3 rd = v_random_sphere_belt( &rv, 1.0 );
+        /* obj_ray_exit */
+        double exit_a = F3_INF;
+        {
+            V3 nor = mk( 0, 0, 0 );
+            double a = obj_ray_hit_dev( sref( sc ), node, rp, rd, true, &nor, &cnt );
+            if( a < F3_INF )
+            {
+                V3 lp = rp;
+                double s = 0;
+                while( a < F3_INF )
+                {
+                    a += F3_EPS * 2;
+                    s += a;
+                    lp = ray_pos( lp, rd, a );
+                    a = obj_ray_hit_dev( sref( sc ), node, lp, rd, true, &nor, &cnt );
+                }
+                if( v_mlv( nor, rd ) > 0 ) exit_a = s;
+            }
+        }
+        if( exit_a < F3_INF )
+        {
+            V3 pos = ray_pos( rp, rd, exit_a );
+            scratch[ size++ ] = pos;
+            sum = v_add( sum, ray_pos( rp, rd, exit_a ) );
+            rp = v_mlf( sum, ( 1.0 / size ) );
+            rp.x += F3_EPS * f3_rnd0( &rv );
+            rp.y += F3_EPS * f3_rnd0( &rv );
+            rp.z += F3_EPS * f3_rnd0( &rv );
+        }
+    }
+    double radius = F3_MAG;
+    if( size > 0 )
+    {
+        double max_r2 = 0;
+        for( uint64_t i = 0; i < size; i++ )
+        {
+            double r = v_diff_sqr( rp, scratch[ i ] );
+            max_r2 = r > max_r2 ? r : max_r2;
+        }
+        radius = acn_sqrt( max_r2 ) * radius_factor;
+    }
+    out[ 0 ] = rp.x; out[ 1 ] = rp.y; out[ 2 ] = rp.z; out[ 3 ] = radius;
+}
+
+__global__ void k_detmath( int op, const double* x, const double* y, double* out, size_t n )
+{
+    size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
+    if( i >= n ) return;
+    double a = x[ i ], b = y ? y[ i ] : 0.0, r = 0;
+    switch( op )
+    {
+        case 0: r = acn_sin( a ); break;
+        case 1: r = acn_cos( a ); break;
+        case 2: r = acn_tan( a ); break;
+        case 3: r = acn_acos( a ); break;
+        case 4: r = acn_log( a ); break;
+        case 5: r = acn_exp( a ); break;
+        case 6: r = acn_pow( a, b ); break;
+        case 7: r = acn_sqrt( a ); break;
+        case 8: r = a / b; break;
+        case 9: r = ( double )acn_f64_bits( a ); break;
+        case 10: r = acn_frexp_mant( a ); break;
+        default: break;
+    }
+    out[ i ] = r;
+}
+
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* ABI */
+extern "C" int acn_camera_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rays, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !d_pos_xy || !d_out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many positions in one call" );
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_camera_rays( h->dev, ( const double* )d_pos_xy, n, ( double* )d_out_rays, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rays )
+{
+    if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    return host_in_out( h, pos_xy, sizeof( double ) * 2 * n, out_rays, sizeof( double ) * 6 * n,
+                        [ & ]( void* d_pos, void* d_out ) { return acn_camera_rays_dev( h, d_pos, n, d_out, nullptr ); } );
+}
+
+/* ---- surface records (k_surface.hip) ---- */
+static int surface_dev( acn_scene_handle* h, const double* d_rays, const double* d_pos_xy, size_t n, uint32_t mode, double* d_out, Call& c )
+{
+    if( !h || ( n && ( !( d_rays || d_pos_xy ) || !d_out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
+    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
+    if( n == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    if( !h->d_surface_flags )
+    {
+        HIP_TRY( hipMalloc( &h->d_surface_flags, sizeof( uint32_t ) ) );
+        HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
+    }
+    if( d_rays && ( st = check_rays( h, d_rays, n, c.stream ) ) != ACN_OK ) return st;
+    SceneArgs s = scene_args( h );
+    s.dev.flags = h->d_surface_flags;   /* the pipeline's word stays the pipeline's */
+    acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h ), c.stream, s, d_rays, d_pos_xy, n, d_out );
+    HIP_TRY( hipGetLastError() );
+    if( !c.own ) return ACN_OK;   /* (a caller's stream is not synchronised for the flags) */
+    uint32_t flags = 0;
+    HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags, sizeof( flags ), hipMemcpyDeviceToHost, c.stream ) );
+    if( ( st = call_end( c ) ) != ACN_OK ) return st;
+    if( flags )
+    {
+        HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
+        return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow in a surface call" );
+    }
+    return ACN_OK;
+}
+
+extern "C" int acn_surface_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && !d_rays ) ) return fail( ACN_ERR_ARG, "null argument" );
+    return surface_dev( h, ( const double* )d_rays, nullptr, n, mode, ( double* )d_out, c );
+}
+
+extern "C" int acn_surface_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && !d_pos_xy ) ) return fail( ACN_ERR_ARG, "null argument" );
+    return surface_dev( h, nullptr, ( const double* )d_pos_xy, n, mode, ( double* )d_out, c );
+}
+
+/* the host-buffer forms: synchronous, on the handle's own stream */
+static int surface_host( acn_scene_handle* h, const double* in, size_t in_len, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !in || !out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
+    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
+    if( n == 0 ) return ACN_OK;
+    c.opts.stream = nullptr;
+    return host_in_out( h, in, sizeof( double ) * in_len * n, out, sizeof( double ) * ACN_SURF_STRIDE * n, [ & ]( void* d_in, void* d_out )
+    {
+        return surface_dev( h, in_len == 6 ? ( const double* )d_in : nullptr, in_len == 6 ? nullptr : ( const double* )d_in, n, mode, ( double* )d_out, c );
+    } );
+}
+
+extern "C" int acn_surface_rays( acn_scene_handle* h, const double* rays, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
+{
+    return surface_host( h, rays, 6, n, mode, out, opts );
+}
+
+extern "C" int acn_surface_positions( acn_scene_handle* h, const double* pos_xy, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
+{
+    return surface_host( h, pos_xy, 2, n, mode, out, opts );
+}
+
+extern "C" int acn_resolve_dev( acn_scene_handle* h, const void* d_linear_rgb, size_t n, void* d_out_rgb, void* d_out_rgb8,
+                                const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && !d_linear_rgb ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    hipLaunchKernelGGL( k_resolve, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, c.stream,
+                        ( const double* )d_linear_rgb, n, h->dev.prm.gamma, ( double* )d_out_rgb, ( unsigned char* )d_out_rgb8 );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+/* ---- the edge-avoiding filter (k_denoise.hip) ---- */
+struct DenoiseSetup { uint32_t iterations, normal_power_log2, no_demodulate; double sigma_plane, sigma_lum; };
+
+/* every check of a denoise call: on the host, before the handle is touched */
+static int denoise_check( const acn_scene_handle* h, const void* lin, const void* surf, size_t width, size_t height,
+                          const acn_denoise_params* prm, const void* out, const acn_render_opts& opts, DenoiseSetup* su )
+{
+    if( !h || !lin || !surf || !out ) return fail( ACN_ERR_ARG, "null argument" );
+    const size_t max_n = ( size_t )1 << 31;
+    if( width == 0 || height == 0 ) return fail( ACN_ERR_ARG, "a frame to denoise needs a width and a height" );
+    if( width > max_n || height > max_n || width * height > max_n ) return fail( ACN_ERR_ARG, "a frame to denoise has at most 2^31 pixels" );
+    acn_denoise_params p{};
+    if( prm )
+    {
+        if( prm->struct_size < sizeof( uint32_t ) ) return fail( ACN_ERR_ARG, "acn_denoise_params.struct_size " + std::to_string( prm->struct_size ) + " is smaller than its first member" );
+        memcpy( &p, prm, prm->struct_size < sizeof( p ) ? prm->struct_size : sizeof( p ) );
+    }
+    if( p.flags & ~( ACN_DENOISE_NO_DEMODULATE | ACN_DENOISE_NORMAL_POWER_SET ) ) return fail( ACN_ERR_ARG, "unknown acn_denoise_params.flags bits" );
+    if( p.iterations > ACN_DENOISE_MAX_ITERATIONS ) return fail( ACN_ERR_ARG, "acn_denoise_params.iterations " + std::to_string( p.iterations ) + " is above 8" );
+    if( p.normal_power_log2 > ACN_DENOISE_MAX_NORMAL_POWER_LOG2 ) return fail( ACN_ERR_ARG, "acn_denoise_params.normal_power_log2 " + std::to_string( p.normal_power_log2 ) + " is above 10" );
+    const double sig[ 2 ] = { p.sigma_plane, p.sigma_lum };
+    for( double s : sig ) if( !( s >= 0 ) || s > 1.7976931348623157e308 ) return fail( ACN_ERR_ARG, "a sigma of acn_denoise_params is negative or not finite" );
+    if( opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a denoise call is not sharded: the filter needs the whole frame" );
+    su->iterations = p.iterations ? p.iterations : ACN_DENOISE_DEFAULT_ITERATIONS;
+    su->normal_power_log2 = ( p.normal_power_log2 || ( p.flags & ACN_DENOISE_NORMAL_POWER_SET ) ) ? p.normal_power_log2 : ACN_DENOISE_DEFAULT_NORMAL_POWER_LOG2;
+    su->no_demodulate = ( p.flags & ACN_DENOISE_NO_DEMODULATE ) ? 1u : 0u;
+    su->sigma_plane = p.sigma_plane != 0 ? p.sigma_plane : ACN_DENOISE_DEFAULT_SIGMA_PLANE;
+    su->sigma_lum = p.sigma_lum != 0 ? p.sigma_lum : ACN_DENOISE_DEFAULT_SIGMA_LUM;
+    return ACN_OK;
+}
+
+/* ---- lens sample statistics: the checks that need no handle (acn_stats_host.h) ---- */
+static int stats_buffer( const void* stats, size_t n, const char* what )
+{
+    std::string msg;
+    return acn_stats_buffer_check( stats, n, what, &msg ) == ACN_OK ? ACN_OK : fail( ACN_ERR_ARG, msg );
+}
+
+/* acn_denoise_dev, and acn_denoise_stats_dev (from_stats): d_in is the linear frame, or the statistics records the filter takes
+ * its colour and variance from */
+static int denoise_dev( acn_scene_handle* h, const void* d_in, const void* d_surface, size_t width, size_t height, const acn_denoise_params* prm,
+                        void* d_out_rgb, Call& c, bool from_stats )
+{
+    DenoiseSetup su;
+    int st = denoise_check( h, d_in, d_surface, width, height, prm, d_out_rgb, c.opts, &su );
+    if( st != ACN_OK ) return st;
+    if( ( uintptr_t )d_surface % 16 ) return fail( ACN_ERR_ARG, "the surface records of a denoise call are read 16 bytes at a time: align the buffer" );
+    if( from_stats && stats_buffer( d_in, width * height, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    if( ( st = grow_device( &h->d_denoise, &h->denoise_bytes, width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL ) ) != ACN_OK ) return st;
+    if( from_stats )
+        acn_launch_denoise_stats( ( const double* )d_in, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2, su.no_demodulate,
+                                  su.sigma_plane, su.sigma_lum, h->dev.prm.background_color, h->d_denoise, ( double* )d_out_rgb, c.stream );
+    else
+        acn_launch_denoise( ( const double* )d_in, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2, su.no_demodulate,
+                            su.sigma_plane, su.sigma_lum, h->d_denoise, ( double* )d_out_rgb, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+/* the two host forms.  The plain filter works in place on the copy of the frame; the statistics need a frame beside them */
+static int denoise_host( acn_scene_handle* h, const double* in, const double* surface, size_t width, size_t height, const acn_denoise_params* prm,
+                         double* out_rgb, const acn_render_opts* opts, bool from_stats )
+{
+    Call c( opts );
+    DenoiseSetup su;
+    int st = denoise_check( h, in, surface, width, height, prm, out_rgb, c.opts, &su );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t n = width * height, rgb_bytes = sizeof( double ) * 3 * n;
+    DevCopies dc;
+    void* d_in = dc.make( in, from_stats ? sizeof( double ) * ACN_STATS_STRIDE * n : rgb_bytes );
+    void* d_surf = dc.make( surface, sizeof( double ) * ACN_SURF_STRIDE * n );
+    void* d_rgb = from_stats ? dc.make( nullptr, rgb_bytes ) : d_in;
+    if( !d_in || !d_surf || !d_rgb ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    c.opts.stream = nullptr;
+    st = denoise_dev( h, d_in, d_surf, width, height, prm, d_rgb, c, from_stats );
+    return st != ACN_OK ? st : DevCopies::fetch( out_rgb, d_rgb, rgb_bytes );
+}
+
+extern "C" int acn_denoise_dev( acn_scene_handle* h, const void* d_linear_rgb, const void* d_surface, size_t width, size_t height,
+                                const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
+{
+    Call c( opts );
+    return denoise_dev( h, d_linear_rgb, d_surface, width, height, prm, d_out_rgb, c, false );
+}
+
+extern "C" int acn_denoise( acn_scene_handle* h, const double* linear_rgb, const double* surface, size_t width, size_t height,
+                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
+{
+    return denoise_host( h, linear_rgb, surface, width, height, prm, out_rgb, opts, false );
+}
+
+extern "C" int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                                      const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
+{
+    Call c( opts );
+    return denoise_dev( h, d_stats, d_surface, width, height, prm, d_out_rgb, c, true );
+}
+
+extern "C" int acn_denoise_stats( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                                  const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
+{
+    return denoise_host( h, stats, surface, width, height, prm, out_rgb, opts, true );
+}
+
+/* ---- the thin-lens camera (k_lens.hip) ---- */
+
+/* every check of a lens call's parameters: on the host, before the handle is touched.  window: the samples an acn_lens_rays call asks for */
+static int lens_check( const acn_scene_handle* h, const acn_lens_params* prm, const uint32_t* window, LensSetup* ls )
+{
+    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
+    acn_lens_params p;
+    std::string msg;
+    if( acn_lens_params_read( prm, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );   /* (acn_stats_host.h: the members alone) */
+    if( p.aperture_radius > 0 && !( h->dev.prm.camera_focal_length > 0 ) ) return fail( ACN_ERR_ARG, "an open aperture needs a camera_focal_length above 0: the plane in focus lies in front of the camera" );
+    ls->samples = p.samples ? p.samples : ACN_LENS_DEFAULT_SAMPLES;
+    ls->jitter = ( p.flags & ACN_LENS_JITTER ) ? 1u : 0u;
+    ls->seed = ACN_LENS_SEED + ( uint64_t )p.seed;
+    ls->aperture_radius = p.aperture_radius;
+    ls->focus_distance = p.aperture_radius > 0 ? p.focus_distance : 0.0;
+    if( window )
+    {
+        if( window[ 1 ] == 0 ) return fail( ACN_ERR_ARG, "n_samples is 0" );
+        if( ( uint64_t )window[ 0 ] + window[ 1 ] > ls->samples ) return fail( ACN_ERR_ARG, "first_sample + n_samples is above the " + std::to_string( ls->samples ) + " samples of the lens" );
+    }
+    return ACN_OK;
+}
+
+/* the checks an acn_lens_rays call makes before its n == 0 return, in either form */
+static int lens_rays_check( const acn_scene_handle* h, const void* pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                            uint32_t n_samples, const void* out_rays, LensSetup* ls )
+{
+    if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    const uint32_t window[ 2 ] = { first_sample, n_samples };
+    int st = lens_check( h, prm, window, ls );
+    if( st != ACN_OK ) return st;
+    if( n > 0xFFFFFF00ull / n_samples ) return fail( ACN_ERR_ARG, "too many rays in one call" );
+    return ACN_OK;
+}
+
+extern "C" int acn_lens_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                                  uint32_t n_samples, void* d_out_rays, const acn_render_opts* opts )
+{
+    Call c( opts );
+    LensSetup ls;
+    int st = lens_rays_check( h, d_pos_xy, n, prm, first_sample, n_samples, d_out_rays, &ls );
+    if( st != ACN_OK || n == 0 ) return st;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    acn_launch_lens_rays( h->dev, ( const double* )d_pos_xy, 0, n, ls, first_sample, n_samples, ( double* )d_out_rays, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_lens_rays( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
+                              uint32_t n_samples, double* out_rays )
+{
+    LensSetup ls;
+    int st = lens_rays_check( h, pos_xy, n, prm, first_sample, n_samples, out_rays, &ls );
+    if( st != ACN_OK || n == 0 ) return st;
+    return host_in_out( h, pos_xy, sizeof( double ) * 2 * n, out_rays, sizeof( double ) * 6 * n_samples * n, [ & ]( void* d_pos, void* d_out )
+    {
+        return acn_lens_rays_dev( h, d_pos, n, prm, first_sample, n_samples, d_out, nullptr );
+    } );
+}
+
+/* a lens call after its null checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice: rays, the ray path of
+ * acn_render_rays_dev (linear, its validity kernel left out: the rays are valid by construction), the ordered mean */
+static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, double* d_out_rgb,
+                        Call& c, double* d_stats = nullptr, bool with_stats = false )
+{
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );
+    if( st != ACN_OK ) return st;
+    const acn_render_opts& o = c.opts;
+    const int linear = ( o.flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0;
+    if( o.shard_mode > ACN_SHARD_SAMPLES ) return fail( ACN_ERR_ARG, "unknown shard_mode" );
+    if( o.shard_mode == ACN_SHARD_SAMPLES && o.shard_world > 1 )
+    {
+        if( o.shard_rank >= o.shard_world ) return fail( ACN_ERR_ARG, "shard_rank >= shard_world" );
+        if( with_stats ) return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
+        if( !linear ) return fail( ACN_ERR_ARG, "a lens call sharded by samples gives partial means: it needs ACN_OPT_LINEAR_OUT" );
+    }
+    if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+    if( n == 0 ) return ACN_OK;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    const size_t K = ls.samples;
+    size_t slice = h->tun.lens_slice_rays / K;
+    if( slice < 1 ) slice = 1;
+    if( slice > n ) slice = n;
+    if( ( st = grow_device( ( void** )&h->d_lens_rays, &h->lens_rays_bytes, sizeof( double ) * 6 * slice * K ) ) != ACN_OK ) return st;
+    if( ( st = grow_device( ( void** )&h->d_lens_rad, &h->lens_rad_bytes, sizeof( double ) * 3 * slice * K ) ) != ACN_OK ) return st;
+    acn_render_opts ray_opts = o;
+    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
+    for( size_t base = 0; base < n; base += slice )
+    {
+        if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+        const size_t cnt = n - base < slice ? n - base : slice;
+        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays, c.stream );
+        HIP_TRY( hipGetLastError() );
+        st = render_dispatch( h, primary_rays( h->d_lens_rays ), cnt * K, h->d_lens_rad, &ray_opts, c.stream );
+        if( st != ACN_OK ) return st;
+        if( with_stats )
+            acn_launch_lens_reduce_stats( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
+                                          d_stats + ( size_t )ACN_STATS_STRIDE * base, c.stream );
+        else
+            acn_launch_lens_reduce( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
+        HIP_TRY( hipGetLastError() );
+    }
+    return call_end( c );
+}
+
+extern "C" int acn_render_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
+                                    const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !d_pos_xy || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    return render_lens( h, ( const double* )d_pos_xy, 0, n, prm, ( double* )d_out_rgb, c );
+}
+
+extern "C" int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
+                                              const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( count && !d_out_rgb ) ) return fail( ACN_ERR_ARG, "null argument" );
+    int st = pixel_range_check( h, first, count );
+    return st != ACN_OK ? st : render_lens( h, nullptr, first, count, prm, ( double* )d_out_rgb, c );
+}
+
+extern "C" int acn_render_lens( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
+                                const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !pos_xy || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
+    if( st != ACN_OK || n == 0 ) return st;
+    c.opts.stream = nullptr;
+    return host_in_out( h, pos_xy, sizeof( double ) * 2 * n, out_rgb, sizeof( double ) * 3 * n,
+                        [ & ]( void* d_pos, void* d_out ) { return acn_render_lens_dev( h, d_pos, n, prm, d_out, &c.opts ); } );
+}
+
+/* ---- lens sample statistics (k_lens.hip, k_denoise.hip) ---- */
+extern "C" int acn_render_lens_stats_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
+                                          void* d_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !d_pos_xy || !d_stats ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( stats_buffer( d_stats, n, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    return render_lens( h, ( const double* )d_pos_xy, 0, n, prm, ( double* )d_out_rgb, c, ( double* )d_stats, true );
+}
+
+extern "C" int acn_render_lens_stats_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
+                                                    void* d_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( count && !d_stats ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( stats_buffer( d_stats, count, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    int st = pixel_range_check( h, first, count );
+    return st != ACN_OK ? st : render_lens( h, nullptr, first, count, prm, ( double* )d_out_rgb, c, ( double* )d_stats, true );
+}
+
+extern "C" int acn_render_lens_stats( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
+                                      double* stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !pos_xy || !stats ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
+    if( st != ACN_OK ) return st;
+    if( c.opts.shard_mode == ACN_SHARD_SAMPLES && c.opts.shard_world > 1 )
+        return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
+    if( n == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    DevCopies dc;
+    void* d_pos = dc.make( pos_xy, sizeof( double ) * 2 * n );
+    void* d_out = out_rgb ? dc.make( nullptr, sizeof( double ) * 3 * n ) : nullptr;
+    void* d_st = dc.make( nullptr, sizeof( double ) * ACN_STATS_STRIDE * n );
+    if( !d_pos || !d_st || ( out_rgb && !d_out ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    c.opts.stream = nullptr;
+    st = acn_render_lens_stats_dev( h, d_pos, n, prm, d_out, d_st, &c.opts );
+    if( st == ACN_OK && out_rgb ) st = DevCopies::fetch( out_rgb, d_out, sizeof( double ) * 3 * n );
+    return st != ACN_OK ? st : DevCopies::fetch( stats, d_st, sizeof( double ) * ACN_STATS_STRIDE * n );
+}
+
+extern "C" int acn_lens_stats_merge_dev( acn_scene_handle* h, void* d_acc, size_t n_acc, const void* d_part, size_t n_part,
+                                         const int64_t* d_index, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
+    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a merge of lens statistics is not sharded" );
+    if( stats_buffer( d_acc, n_acc, "d_acc" ) != ACN_OK || stats_buffer( d_part, n_part, "d_part" ) != ACN_OK ) return ACN_ERR_ARG;
+    if( !d_index && n_part > n_acc ) return fail( ACN_ERR_ARG, "a merge without an index needs n_part <= n_acc" );
+    if( ( uintptr_t )d_index % 8 ) return fail( ACN_ERR_ARG, "d_index is an array of int64_t: align the buffer" );
+    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_stats_merge( ( double* )d_acc, n_acc, ( const double* )d_part, n_part, d_index, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_lens_stats_merge( acn_scene_handle* h, double* acc, size_t n_acc, const double* part, size_t n_part,
+                                     const int64_t* index, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n_acc && !acc ) || ( n_part && !part ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a merge of lens statistics is not sharded" );
+    std::string msg;
+    if( acn_stats_index_check( index, n_part, n_acc, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    DevCopies dc;
+    const size_t rec = sizeof( double ) * ACN_STATS_STRIDE;
+    void* d_acc = dc.make( acc, rec * n_acc );
+    void* d_part = dc.make( part, rec * n_part );
+    void* d_index = index ? dc.make( index, sizeof( int64_t ) * n_part ) : nullptr;
+    if( !d_acc || !d_part || ( index && !d_index ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    c.opts.stream = nullptr;
+    int st = acn_lens_stats_merge_dev( h, d_acc, n_acc, d_part, n_part, ( const int64_t* )d_index, &c.opts );
+    return st != ACN_OK ? st : DevCopies::fetch( acc, d_acc, rec * n_acc );
+}
+
+extern "C" int acn_lens_stats_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb, void* d_out_noise,
+                                           const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && !d_stats ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a resolve of lens statistics is not sharded" );
+    if( stats_buffer( d_stats, n, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
+    if( n == 0 || ( !d_out_rgb && !d_out_noise ) ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_stats_resolve( ( const double* )d_stats, n, h->dev.prm.background_color, h->dev.prm.gamma, ( c.opts.flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0,
+                              ( double* )d_out_rgb, ( double* )d_out_noise, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+/* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */
+extern "C" int acn_select_above_dev( acn_scene_handle* h, const void* d_key, size_t n, const acn_select_params* prm, const void* d_src_pos_xy,
+                                     void* d_out_index, void* d_out_pos_xy, void* d_out_count, uint64_t* out_count, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_select_params p;
+    if( acn_select_args_check( h != nullptr, d_key, n, prm, d_src_pos_xy, d_out_index, d_out_pos_xy, c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( ( uintptr_t )d_out_count % 8 ) return fail( ACN_ERR_ARG, "d_out_count is a uint64_t: align it" );
+    const uint64_t width = p.raster_width ? p.raster_width : h->dev.prm.image_width;
+    if( !d_src_pos_xy && d_out_pos_xy && width == 0 ) return fail( ACN_ERR_ARG, "raster positions need a raster_width or a scene with an image_width" );
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    if( n == 0 )   /* no launch */
+    {
+        if( d_out_count ) HIP_TRY( hipMemsetAsync( d_out_count, 0, sizeof( uint64_t ), c.stream ) );
+        if( ( st = call_end( c ) ) != ACN_OK ) return st;
+        if( out_count ) *out_count = 0;
+        return ACN_OK;
+    }
+    const size_t words = ( size_t )acn_select_tiles( n ) + 1;
+    if( ( st = grow_device( ( void** )&h->d_select_tiles, &h->select_tiles_bytes, sizeof( unsigned long long ) * words ) ) != ACN_OK ) return st;
+    acn_launch_select( ( const double* )d_key, n, p.threshold, h->d_select_tiles, p.capacity, ( const double* )d_src_pos_xy, width, p.raster_first,
+                       ( int64_t* )d_out_index, ( double* )d_out_pos_xy, ( unsigned long long* )d_out_count, c.stream );
+    HIP_TRY( hipGetLastError() );
+    if( !out_count ) return call_end( c );
+    /* the one synchronisation of a caller's stream */
+    unsigned long long total = 0;
+    HIP_TRY( hipMemcpyAsync( &total, h->d_select_tiles + ( words - 1 ), sizeof( total ), hipMemcpyDeviceToHost, c.stream ) );
+    HIP_TRY( hipStreamSynchronize( c.stream ) );
+    *out_count = total;
+    return ACN_OK;
+}
+
+extern "C" int acn_select_above( acn_scene_handle* h, const double* key, size_t n, const acn_select_params* prm, const double* src_pos_xy,
+                                 int64_t* out_index, double* out_pos_xy, uint64_t* out_count )
+{
+    std::string msg;
+    acn_select_params p;
+    if( acn_select_args_check( h != nullptr, key, n, prm, src_pos_xy, out_index, out_pos_xy, 0, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) { if( out_count ) *out_count = 0; return ACN_OK; }
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t cap = ( size_t )( p.capacity < n ? p.capacity : n );   /* (no more than n are ever selected) */
+    DevCopies dc;
+    void* d_key = dc.make( key, sizeof( double ) * n );
+    void* d_src = src_pos_xy ? dc.make( src_pos_xy, sizeof( double ) * 2 * n ) : nullptr;
+    void* d_index = out_index && cap ? dc.make( nullptr, sizeof( int64_t ) * cap ) : nullptr;
+    void* d_pos = out_pos_xy && cap ? dc.make( nullptr, sizeof( double ) * 2 * cap ) : nullptr;
+    if( !d_key || ( src_pos_xy && !d_src ) || ( out_index && cap && !d_index ) || ( out_pos_xy && cap && !d_pos ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    acn_select_params q = p;
+    q.struct_size = ( uint32_t )sizeof( q );
+    q.capacity = ( d_index || d_pos ) ? cap : 0;
+    uint64_t total = 0;
+    int st = acn_select_above_dev( h, d_key, n, &q, d_src, d_index, d_pos, nullptr, &total, nullptr );
+    const size_t wrote = ( size_t )( total < q.capacity ? total : q.capacity );
+    if( st == ACN_OK && d_index && wrote ) st = DevCopies::fetch( out_index, d_index, sizeof( int64_t ) * wrote );
+    if( st == ACN_OK && d_pos && wrote ) st = DevCopies::fetch( out_pos_xy, d_pos, sizeof( double ) * 2 * wrote );
+    if( st == ACN_OK && out_count ) *out_count = total;
+    return st;
+}
+
+extern "C" int acn_key_histogram_dev( acn_scene_handle* h, const void* d_key, size_t n, void* d_out_hist, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_key_hist_args_check( h != nullptr, d_key, n, d_out_hist, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipMemsetAsync( d_out_hist, 0, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS, c.stream ) );
+    if( n ) acn_launch_key_hist( ( const double* )d_key, n, ( unsigned long long* )d_out_hist, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_key_histogram( acn_scene_handle* h, const double* key, size_t n, uint64_t* out_hist )
+{
+    std::string msg;
+    if( acn_key_hist_args_check( h != nullptr, key, n, out_hist, 0, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    const size_t hist_bytes = sizeof( uint64_t ) * ACN_KEY_HIST_WORDS;
+    return host_in_out( h, key, sizeof( double ) * n, out_hist, hist_bytes,
+                        [ & ]( void* d_key, void* d_hist ) { return acn_key_histogram_dev( h, d_key, n, d_hist, nullptr ); } );
+}
+
+extern "C" double acn_key_hist_edge( uint32_t bin ) { return acn_select_hist_edge( bin ); }
+extern "C" double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget ) { return acn_select_hist_threshold( hist, budget ); }
+
+/* ---- test seams: the envelope estimate and the deterministic math library, on the device's arithmetic ---- */
+extern "C" int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_t samples, uint32_t rseed,
+                                      double radius_factor, double* out )
+{
+    Call c( nullptr );
+    if( !h || !out || node < 0 || ( uint32_t )node >= h->dev.n_nodes ) return fail( ACN_ERR_ARG, "bad argument" );
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    DevCopies dc;
+    void* d_scratch = dc.make( nullptr, sizeof( V3 ) * ( samples ? samples : 1 ) );
+    void* d_out = dc.make( nullptr, sizeof( double ) * 4 );
+    if( !d_scratch || !d_out ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    DevScene est_scene = h->dev;
+    est_scene.lds_stack = ACN_NO_LDS_STACK;   /* one lane, no dynamic LDS: the machine keeps its stacks in scratch */
+    hipLaunchKernelGGL( k_estimate_envelope, dim3( 1 ), dim3( 1 ), 0, c.stream, est_scene, node, samples, rseed, radius_factor, ( V3* )d_scratch, ( double* )d_out );
+    HIP_TRY( hipGetLastError() );
+    st = call_end( c );
+    return st != ACN_OK ? st : DevCopies::fetch( out, d_out, sizeof( double ) * 4 );
+}
+
+extern "C" int acn_detmath_eval( int device, int op, const double* x, const double* y, double* out, size_t n )
+{
+    if( !x || !out ) return fail( ACN_ERR_ARG, "null argument" );
+    if( acn_device_count() <= 0 ) return fail( ACN_ERR_DEVICE, "no HIP device" );
+    HIP_TRY( hipSetDevice( device ) );
+    DevCopies dc;
+    void* dx = dc.make( x, sizeof( double ) * n );
+    void* dout = dc.make( nullptr, sizeof( double ) * n );
+    void* dy = y ? dc.make( y, sizeof( double ) * n ) : nullptr;
+    if( !dx || !dout || ( y && !dy ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    hipLaunchKernelGGL( k_detmath, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, 0, op, ( const double* )dx, ( const double* )dy, ( double* )dout, n );
+    HIP_TRY( hipGetLastError() );
+    HIP_TRY( hipDeviceSynchronize() );
+    return DevCopies::fetch( out, dout, sizeof( double ) * n );
+}

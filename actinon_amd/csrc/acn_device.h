@@ -1,4 +1,5 @@
-/* acn_device.h -- gfx950 device code of the trace / radiance path (included only by actinon_hip.hip).
+/* acn_device.h -- gfx950 device code of the trace / radiance path (every .hip unit includes it through
+ * acn_pipeline.h and acn_launch.h).
  *
  * What the reference does with recursion over heap objects and vtables (src/objects.c, src/compound.c,
  * src/scene.c:420-667) is done here with index-linked POD nodes, explicit per-lane stacks and state machines:

@@ -1,0 +1,393 @@
+/* acn_handle.h -- what the host units of libactinon_hip.so share: the scene handle, the error plumbing, the frame of one C ABI
+ * call and the few functions that cross between actinon_hip.hip (life cycle, workspace, pipeline, lanes and the pipeline's own
+ * entry points), acn_calls.hip (every other entry point) and k_query.hip (the test seam). */
+#ifndef ACN_HANDLE_H
+#define ACN_HANDLE_H
+
+#include <hip/hip_runtime.h>
+#include <cstdlib>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <vector>
+#include <functional>
+#include <thread>
+#include <condition_variable>
+
+#include "acn_launch.h"
+#include "acn_tables.h"
+#include "acn_chunkplan.h"
+
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* error plumbing */
+extern thread_local std::string g_last_error;   /* one object, defined in actinon_hip.hip: what acn_last_error() returns */
+static inline int fail( int code, const std::string& msg ) { g_last_error = msg; return code; }
+
+#define HIP_TRY( expr ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) \
+    return fail( ACN_ERR_DEVICE, std::string( #expr ) + ": " + hipGetErrorString( e_ ) ); } while( 0 )
+
+struct StageEvents { hipEvent_t a, b; int stage; };
+
+/* a persistent host thread per lane (creating a thread per call costs a HIP per-thread initialisation each time) */
+struct LaneWorker
+{
+    std::thread thread;
+    std::mutex m;
+    std::condition_variable cv;
+    std::function< void() > job;
+    bool has_job = false, done = true, quit = false;
+    void start()
+    {
+        thread = std::thread( [ this ]()
+        {
+            for( ;; )
+            {
+                std::function< void() > j;
+                {
+                    std::unique_lock< std::mutex > lk( m );
+                    cv.wait( lk, [ this ] { return has_job || quit; } );
+                    if( quit ) return;
+                    j = job; has_job = false;
+                }
+                j();
+                { std::lock_guard< std::mutex > lk( m ); done = true; }
+                cv.notify_all();
+            }
+        } );
+    }
+    void post( std::function< void() > j )
+    {
+        { std::lock_guard< std::mutex > lk( m ); job = std::move( j ); has_job = true; done = false; }
+        cv.notify_all();
+    }
+    void wait() { std::unique_lock< std::mutex > lk( m ); cv.wait( lk, [ this ] { return done; } ); }
+    void stop()
+    {
+        if( !thread.joinable() ) return;
+        { std::lock_guard< std::mutex > lk( m ); quit = true; }
+        cv.notify_all();
+        thread.join();
+    }
+};
+
+/* Tunables, read from the environment ONCE per acn_scene_upload (never from the render path: getenv there would race a
+ * host that changes its environment, and would let a value change between the concurrent lanes of one call) */
+struct Tunables
+{
+    size_t   workspace_mb = 0;         /* ACN_WORKSPACE_MB: upper bound of the queue workspace of one handle (all its lanes); 0: 64 GiB or a
+                                          quarter of the device memory that is free at upload, whichever is less */
+    size_t   chunk = 0;                /* ACN_CHUNK: sample positions per pipeline run, 0 = derived from the queue capacity */
+    int      lanes = 6;                /* ACN_LANES: concurrent pipeline runs of a large call (4 until round 4, each on grids twice the size: create_lane) */
+    unsigned grid = 0;                 /* ACN_GRID: workgroups of the persistent kernels, 0 = 4 per compute unit */
+    unsigned shade_grid = 0;           /* ACN_SHADE_GRID: workgroups of k_shade, 0 = 4 per compute unit */
+    unsigned walk_grid = 0;            /* ACN_WALK_GRID: workgroups of k_walk (256 VGPRs: two of its waves fill a SIMD's register file), 0 = as ACN_GRID */
+    uint32_t stack_cap = 512;          /* ACN_STACK_CAP: private ray slots per k_walk wave */
+    uint32_t fetch_walk = 64;          /* ACN_FETCH_WALK: fresh rays a k_walk wave reserves per cursor atomic */
+    uint32_t walk_passes = 4;          /* ACN_WALK_PASSES: launches of k_walk per path level (the last one finishes whatever is left on the waves' private
+                                          stacks).  12 until round 4: with k_walk at 4 waves per SIMD the private tail is cheap and the launches are not --
+                                          1080p 52.0 -> 50.3 ms, the 1/8 share 13.7 -> 12.1, c2 28.2 -> 26.3, paraffin_lamp 367 -> 339 (profiles/r04/ab_walk_passes_*) */
+    uint32_t private_limit = 32768;    /* ACN_PRIVATE_LIMIT: a generation of at most this many rays is finished on private stacks */
+    bool     private_limit_set = false; /* ... given by the environment: then it holds for chunks of every size (render_chunk) */
+    uint32_t class0_min = 0;           /* ACN_CLASS0_MIN: shading tasks with more samples than this take the 64-lane kernel, the others 16 / 4 / 1 lanes; 0: chosen per scene (acn_scene_upload) */
+    uint32_t fetch_shade = 16;         /* ACN_FETCH_SHADE: steps ( of 64 / lanes-per-task tasks ) a k_shade wave reserves per cursor atomic */
+    uint32_t fetch_hard = 256;         /* ACN_FETCH_HARD: records a wave of the hard-ray kernels / k_shade_hits reserves per atomic */
+    uint32_t stack_use = 0;            /* ACN_TEST_STACK_USE: slots of a private stack every walk pass but the last uses (tests of the overflow path) */
+    bool     debug_chunks = false;     /* ACN_DEBUG_CHUNKS=1: one line per chunk on stderr (size, queue marks, rates, capacities) */
+    bool     learn_passes = true;      /* ACN_LEARN_PASSES=0: every level gets ACN_WALK_PASSES launches of k_walk, needed or not */
+    bool     learn_sample = true;      /* ACN_LEARN_SAMPLE=0: no strided learning pass on a cold handle (learn_rates): the first chunks learn, as in round 3 */
+    bool     cold_pipeline = true;     /* ACN_COLD_PIPELINE=0: a cold handle makes its lanes before the learning pass, not beside it (render_lanes) */
+    bool     early_lanes = false;      /* ACN_EARLY_LANES=1: the lanes a whole frame of the scene's own raster will use are made during acn_scene_upload (a
+                                          helper thread beside the upload's own work, while the device is idle), not by the first call that needs them.
+                                          Measured and OFF (profiles/r04/ab_early_lanes_s42.txt): the streams cost the same ~10 ms each wherever they are made
+                                          and do not overlap the handle's own first stream, so the upload grows by 50 - 90 ms while the first frame loses
+                                          20 - 100 (1080p 114 - 174 -> 72 - 75 ms, c2 94 - 135 -> 48 - 49, paraffin_lamp 486 - 504 -> 466 - 479, hanging_lamp
+                                          417 - 426 -> 390 - 401); upload + first frame: 1080p 247 - 299 -> 277 - 323 ms, c2 189 - 261 -> 195 - 204, the
+                                          lamps +30.  For a host that uploads long before it renders */
+    size_t   lens_slice_rays = ( size_t )1 << 21;   /* ACN_LENS_SLICE_RAYS: rays of one slice of a lens call (acn_render_lens*): floor( this / K ) positions, at least 1 */
+    bool     count_work = false;       /* ACN_COUNT_WORK */
+    bool     stage_timing = false;     /* ACN_STAGE_TIMING */
+    acn_table_opts tables;             /* the switches of the scene tables (acn_tables.h) */
+    void read()
+    {
+        tables.no_leaf_pairs = getenv( "ACN_NO_LEAF_PAIRS" ) != nullptr;
+        tables.no_pair2 = getenv( "ACN_NO_PAIR2" ) != nullptr;
+        tables.no_prune_levels = getenv( "ACN_NO_PRUNE_LEVELS" ) != nullptr;
+        tables.no_simple_compounds = getenv( "ACN_NO_SIMPLE_COMPOUNDS" ) != nullptr;
+        tables.no_sc_cull = getenv( "ACN_NO_SC_CULL" ) != nullptr;
+        tables.no_sc_reversed = getenv( "ACN_NO_SC_REVERSED" ) != nullptr;
+        tables.verbose = getenv( "ACN_VERBOSE" ) != nullptr;
+        if( const char* e = getenv( "ACN_PRUNE_MIN" ) ) tables.prune_min = ( size_t )atoll( e );
+        if( const char* e = getenv( "ACN_LDS_MAX" ) ) { tables.lds_max = ( size_t )atoll( e ); tables.lds_max_set = true; }
+        if( const char* e = getenv( "ACN_WORKSPACE_MB" ) ) workspace_mb = ( size_t )atoll( e );
+        if( const char* e = getenv( "ACN_CHUNK" ) ) chunk = ( size_t )atoll( e );
+        if( const char* e = getenv( "ACN_LANES" ) ) lanes = atoi( e );
+        if( const char* e = getenv( "ACN_GRID" ) ) grid = ( unsigned )atoi( e );
+        if( const char* e = getenv( "ACN_SHADE_GRID" ) ) shade_grid = ( unsigned )atoi( e );
+        if( const char* e = getenv( "ACN_WALK_GRID" ) ) walk_grid = ( unsigned )atoi( e );
+        if( const char* e = getenv( "ACN_STACK_CAP" ) ) stack_cap = ( uint32_t )atoll( e );
+        if( const char* e = getenv( "ACN_TEST_STACK_USE" ) ) stack_use = ( uint32_t )atoll( e );
+        if( const char* e = getenv( "ACN_FETCH_WALK" ) ) fetch_walk = ( uint32_t )atoll( e );
+        if( const char* e = getenv( "ACN_FETCH_HARD" ) ) fetch_hard = ( uint32_t )atoll( e );
+        if( const char* e = getenv( "ACN_FETCH_SHADE" ) ) fetch_shade = ( uint32_t )atoll( e );
+        if( const char* e = getenv( "ACN_CLASS0_MIN" ) ) class0_min = ( uint32_t )atoll( e );
+        if( fetch_shade < 1 ) fetch_shade = 1;
+        if( const char* e = getenv( "ACN_WALK_PASSES" ) ) walk_passes = ( uint32_t )atoll( e );
+        if( const char* e = getenv( "ACN_PRIVATE_LIMIT" ) ) { private_limit = ( uint32_t )atoll( e ); private_limit_set = true; }
+        if( const char* e = getenv( "ACN_LENS_SLICE_RAYS" ) ) lens_slice_rays = ( size_t )atoll( e );
+        if( lens_slice_rays < 1 ) lens_slice_rays = 1;
+        if( lens_slice_rays > ( ( size_t )1 << 28 ) ) lens_slice_rays = ( size_t )1 << 28;
+        if( walk_passes < 1 ) walk_passes = 1;
+        if( walk_passes > ACN_MAX_WALK_PASSES ) walk_passes = ACN_MAX_WALK_PASSES;
+        if( fetch_walk < 64 ) fetch_walk = 64;
+        if( fetch_hard < 64 ) fetch_hard = 64;
+        count_work = getenv( "ACN_COUNT_WORK" ) != nullptr;
+        if( const char* e = getenv( "ACN_LEARN_PASSES" ) ) learn_passes = atoi( e ) != 0;
+        if( const char* e = getenv( "ACN_LEARN_SAMPLE" ) ) learn_sample = atoi( e ) != 0;
+        if( const char* e = getenv( "ACN_COLD_PIPELINE" ) ) cold_pipeline = atoi( e ) != 0;
+        if( const char* e = getenv( "ACN_EARLY_LANES" ) ) early_lanes = atoi( e ) != 0;
+        debug_chunks = getenv( "ACN_DEBUG_CHUNKS" ) != nullptr;
+        stage_timing = getenv( "ACN_STAGE_TIMING" ) != nullptr;
+        if( lanes < 1 ) lanes = 1;
+        if( lanes > 16 ) lanes = 16;
+        if( stack_cap < 256 ) stack_cap = 256;
+        if( stack_use == 0 || stack_use > stack_cap ) stack_use = stack_cap;
+    }
+};
+
+/* the queue workspace of one pipeline run */
+struct Workspace
+{
+    DTask*      tasks = nullptr;
+    uint32_t*   idx[ ACN_NCLASS ] = { nullptr, nullptr, nullptr, nullptr };
+    HitRec*     children = nullptr;
+    HardShadow* hard_shadow = nullptr;
+    HardPath*   hard_path = nullptr;
+    RayTask*    rays[ 2 ] = { nullptr, nullptr };
+    RayTask*    stacks = nullptr;   size_t stack_waves = 0;
+    uint32_t    cap[ 5 ] = { 0, 0, 0, 0, 0 };   /* records per queue, WQ_* */
+    size_t      bytes = 0;          /* device memory of the queues and stacks */
+    uint64_t    allocs = 0;         /* times this workspace was (re)allocated */
+    bool        trimmed = false;    /* it was already re-allocated smaller once */
+    uint32_t    sized_calls = 0;    /* calls of ensure_workspace with learned rates (the trim window, see there) */
+};
+/* the queues of a pipeline run.  Each is sized from its OWN demand per sample position (learned, below): on the wine glass a
+ * position leaves 15 deferred shadow rays but 2 shading points, and one common capacity -- the former layout -- made every
+ * queue as large as the fullest one needs (64 GiB for a 1080p frame of which 7 % were used). */
+enum { WQ_TASKS = 0, WQ_CHILDREN, WQ_HARD_SHADOW, WQ_HARD_PATH, WQ_RAYS, WQ_N };
+
+struct acn_scene_handle
+{
+    int device = 0;
+    DevScene dev{};
+    /* the resident scene and what the tables say about it: a lane borrows all of it from its parent (bind_lane) */
+    struct Resident
+    {
+        GNode*   d_nodes = nullptr;
+        GMat*    d_mats = nullptr;
+        int32_t* d_elems = nullptr;
+        acn_texture* d_textures = nullptr;
+        size_t scene_bytes[ 4 ] = { 0, 0, 0, 0 };
+        int max_csg_depth = 0;
+        size_t lds_bytes = 0;                      /* > 0: the node array fits the LDS staging budget */
+        size_t lds_stack_bytes = 0;                /* > 0: the machine kernels keep their CSG stacks in LDS */
+        bool prune = false;                        /* some root element has an interval-prune program: launch the PRUNE kernel variants */
+        bool leaf_lights = true;                   /* every light element is a plane / sphere */
+        uint32_t elem_pos_base = 0;                /* elems[ elem_pos_base + k ]: given-order position of entry k of the cost-ordered copy (k_hard_shadow: resume words) */
+        int n_levels = 1;                          /* path levels of the scene's trace_depth */
+        size_t n_lights = 1;                       /* elements of the light root */
+    } scene;
+    SCEntry* d_sc_table = nullptr;
+    double* d_sc_spheres = nullptr;            /* ( pos, radius ) of the sphere leaves of d_sc_table */
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
+    int cur_stage = 0;
+    bool stage_timing = false;                 /* ACN_OPT_STAGE_TIMING of the current call */
+    Tunables tun;
+    unsigned cus = 256;                        /* compute units of the device */
+    unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
+    unsigned walk_grid = 1024;                 /* ... of k_walk */
+    /* workspace of the wavefront pipeline */
+    Workspace ws;
+    uint32_t* d_counts = nullptr;              /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
+    uint32_t* h_counts = nullptr;              /* pinned copy */
+    unsigned long long* d_accum = nullptr;  size_t accum_bytes = 0;
+    unsigned long long* d_counters = nullptr;
+    std::vector< StageEvents > events;  size_t events_used = 0;
+    bool count_work = false;                   /* ACN_OPT_COUNT_WORK of the current call */
+    uint32_t shard_rank = 0, shard_world = 1;  /* ACN_SHARD_SAMPLES of the current call */
+    uint64_t launches[ 4 ] = { 0, 0, 0, 0 };   /* walk, shade, finalize, hard-ray kernels */
+    uint64_t hard_rays = 0, walk_steps = 0, walk_rays = 0, shade_hit_recs = 0, host_syncs = 0, private_rays = 0, probe_rays = 0;
+    uint32_t flags_seen = 0;                   /* ACN_FLAG_* bits of the last call */
+    uint32_t rate_cnt = 0;                     /* positions of the chunk the rates were taken from */
+    acn_chunk_ctl ctl = { 0.7, 0, 0 };         /* acn_chunkplan.h.  fill_target: fraction of its capacity the fullest queue of a chunk is
+                                                  planned to reach: lowered by every overflow (a redone chunk is lost work), raised slowly
+                                                  by chunks that fit */
+    double rate[ 5 ] = { 0, 0, 0, 0, 0 };      /* learned: records per sample position a chunk leaves in each queue (WQ_*); 0: not known yet */
+    size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
+    uint64_t chunks = 0, retries = 0, levels = 0;
+    uint64_t peak_tasks = 0, peak_children = 0;
+    uint32_t walk_passes_seen[ ACN_MAX_PATH_LEVELS + 1 ] = { 0, 0, 0, 0, 0, 0 };   /* learned: passes of a level that had input in the last chunk (0: not known yet) */
+    unsigned long long* d_counters_keep = nullptr;   /* the work counters as they were before the current chunk (restored when it is redone) */
+    /* concurrent lanes (render_lanes): clones of this handle that share the resident scene and own a stream and a
+     * workspace each */
+    bool is_lane = false;
+    size_t budget_div = 1;                     /* workspace budget of a lane = the handle's budget / lanes */
+    std::vector< acn_scene_handle* > lanes;
+    /* lanes made during acn_scene_upload on a helper thread (early_lanes_begin), taken over by the first call that runs on lanes */
+    std::thread early_maker;
+    std::vector< acn_scene_handle* > early_made;
+    int early_status = 0; std::string early_message;
+    LaneWorker* worker = nullptr;              /* of a lane */
+    double* d_lane_in = nullptr; size_t lane_in_bytes = 0;     /* a lane's gathered positions or rays (grow_device, as every *_bytes below) */
+    double* d_lane_out = nullptr; size_t lane_out_bytes = 0;   /* ... and its results */
+    double* d_shard_pos = nullptr; size_t shard_pos_bytes = 0;                              /* acn_render_main_pass_shard_dev: the rank's positions */
+    unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
+    uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
+    void* d_denoise = nullptr; size_t denoise_bytes = 0;                                    /* acn_denoise: guides and colour buffers, apart from the render workspace */
+    double* d_lens_rays = nullptr; size_t lens_rays_bytes = 0;                              /* acn_render_lens*: the rays [ 6 ] of a slice */
+    double* d_lens_rad = nullptr; size_t lens_rad_bytes = 0;                                /* ... and their radiance [ 3 ] */
+    unsigned long long* d_select_tiles = nullptr; size_t select_tiles_bytes = 0;            /* acn_select_above*: the counts per tile and their total */
+    bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
+    std::string lane_error;
+    bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
+    int  lanes_used = 0;                       /* ... the first lanes_used of them */
+    bool one_lane = false;                     /* the last call would have used lanes but did not fit the workspace bound that way */
+};
+
+static SceneArgs scene_args( const acn_scene_handle* h )
+{
+    SceneArgs s;
+    s.dev = h->dev; s.nodes = h->scene.d_nodes; s.mats = h->scene.d_mats; s.elems = h->scene.d_elems; s.textures = h->scene.d_textures; s.elem_pos_base = h->scene.elem_pos_base;
+    return s;
+}
+static size_t machine_lds_bytes( const acn_scene_handle* h ) { return h->scene.lds_bytes + h->scene.lds_stack_bytes; }
+
+/* What the primary rays of a call come from, handed down the whole chain (render_dispatch -> launch_render / render_lanes ->
+ * learn_rates -> render_chunk -> acn_launch_walk): sample positions [ n ][ 2 ], the pixel centres of the main pass from pixel
+ * `first` on (pos_xy == nullptr), or the caller's rays [ n ][ 6 ] -- seeded into the level-0 ray queue (k_rays.hip), where the
+ * first walk pass reads them instead of making camera rays. */
+struct Primary
+{
+    const double* pos_xy = nullptr;
+    size_t first = 0;
+    const double* rays = nullptr;
+};
+static Primary primary_positions( const double* pos_xy ) { Primary p; p.pos_xy = pos_xy; return p; }
+static Primary primary_main_pass( size_t first ) { Primary p; p.first = first; return p; }
+static Primary primary_rays( const double* rays ) { Primary p; p.rays = rays; return p; }
+
+/* the caller's options as far as the caller's header knew them (acn_render_opts.struct_size), the rest zero */
+static acn_render_opts opts_of( const acn_render_opts* in )
+{
+    acn_render_opts o{};
+    if( in )
+    {
+        /* 0: a caller that zero-initialises the struct (the memset idiom) and never heard of struct_size -- the word was a
+         * reserved zero in the first published layout, which already had the shard members: the 40-byte base layout */
+        size_t n = in->struct_size ? in->struct_size : ( size_t )ACN_RENDER_OPTS_BASE_SIZE;
+        if( n > sizeof( o ) ) n = sizeof( o );
+        memcpy( &o, in, n );
+    }
+    o.struct_size = ( uint32_t )sizeof( o );
+    return o;
+}
+
+/* one pipeline run on the handle itself, or the concurrent lanes (actinon_hip.hip).  opts: never null */
+int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, double* d_out_rgb, const acn_render_opts* opts, hipStream_t stream );
+
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* The frame of one C ABI call.  The options are viewed when the frame is made, so every argument check reads them before the
+ * device is touched; call_begin sets the device and picks the stream, call_end synchronises the stream iff it is the handle's own.
+ * A host-buffer form sets opts.stream = nullptr before it hands the frame (or its opts) on: it is synchronous. */
+struct Call
+{
+    acn_render_opts opts;           /* the caller's options as opts_of views them: there is no null to test for */
+    hipStream_t stream = nullptr;   /* opts.stream, or the handle's own */
+    bool own = true;                /* ... the handle's own */
+    explicit Call( const acn_render_opts* in ) : opts( opts_of( in ) ) {}
+};
+static inline int call_begin( acn_scene_handle* h, Call* c )
+{
+    HIP_TRY( hipSetDevice( h->device ) );
+    c->own = c->opts.stream == nullptr;
+    c->stream = c->own ? h->stream : ( hipStream_t )c->opts.stream;
+    return ACN_OK;
+}
+static inline int call_end( const Call& c )
+{
+    if( c.own ) HIP_TRY( hipStreamSynchronize( c.stream ) );
+    return ACN_OK;
+}
+
+/* a device buffer of at least `want` bytes: grown, never shrunk, its contents not kept; *cap is 0 after a hipMalloc that failed */
+static inline int grow_device( void** p, size_t* cap, size_t want )
+{
+    if( *cap >= want ) return ACN_OK;
+    if( *p ) hipFree( *p );   /* (waits for whatever still reads it) */
+    *p = nullptr; *cap = 0;
+    HIP_TRY( hipMalloc( p, want ) );
+    *cap = want;
+    return ACN_OK;
+}
+
+/* every ray of a call is checked before anything is rendered or written: the lowest index of a refused one, one word read back
+ * (this synchronises `stream`, a caller's too) */
+static inline int check_rays( acn_scene_handle* h, const double* d_rays, size_t n, hipStream_t stream )
+{
+    if( !h->d_ray_check ) HIP_TRY( hipMalloc( &h->d_ray_check, sizeof( unsigned long long ) ) );
+    HIP_TRY( hipMemsetAsync( h->d_ray_check, 0xFF, sizeof( unsigned long long ), stream ) );
+    acn_launch_check_rays( d_rays, n, h->d_ray_check, stream );
+    HIP_TRY( hipGetLastError() );
+    unsigned long long bad = 0;
+    HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check, sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
+    HIP_TRY( hipStreamSynchronize( stream ) );
+    if( bad < n ) return fail( ACN_ERR_ARG, "ray " + std::to_string( bad ) + ": a component is not finite or the direction has no length" );
+    return ACN_OK;
+}
+
+/* pixels [ first, first + count ) of a main pass lie in the scene's raster (first + count may not wrap either) */
+static inline int pixel_range_check( const acn_scene_handle* h, size_t first, size_t count )
+{
+    const size_t pixels = h->dev.prm.image_width * h->dev.prm.image_height;
+    if( first > pixels || count > pixels - first ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
+    return ACN_OK;
+}
+
+/* device copies of host arrays for one call; everything is freed when it goes */
+struct DevCopies
+{
+    std::vector< void* > held;
+    ~DevCopies() { for( void* p : held ) hipFree( p ); }
+    /* null on failure; src (nullable) is copied in */
+    void* make( const void* src, size_t bytes )
+    {
+        void* d = nullptr;
+        if( hipMalloc( &d, bytes ? bytes : 1 ) != hipSuccess ) return nullptr;
+        held.push_back( d );
+        if( src && bytes && hipMemcpy( d, src, bytes, hipMemcpyHostToDevice ) != hipSuccess ) return nullptr;
+        return d;
+    }
+    /* a result back to the host, after the call has synchronised */
+    static int fetch( void* dst, const void* d, size_t bytes )
+    {
+        HIP_TRY( hipMemcpy( dst, d, bytes, hipMemcpyDeviceToHost ) );
+        return ACN_OK;
+    }
+};
+
+/* the plainest host-buffer form: one array copied in, the device-buffer call `dev( d_in, d_out )` on the handle's own stream, one
+ * array copied out */
+template< class DevCall >
+static int host_in_out( acn_scene_handle* h, const void* in, size_t in_bytes, void* out, size_t out_bytes, DevCall dev )
+{
+    HIP_TRY( hipSetDevice( h->device ) );
+    DevCopies dc;
+    void* d_in = dc.make( in, in_bytes );
+    void* d_out = dc.make( nullptr, out_bytes );
+    if( !d_in || !d_out ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    const int st = dev( d_in, d_out );
+    return st != ACN_OK ? st : DevCopies::fetch( out, d_out, out_bytes );
+}
+
+#endif

@@ -2,7 +2,8 @@
  * (k_shade_*.hip, k_walk_*.hip, k_hard_*.hip) so that `make -j` compiles the families in parallel: the pipeline's 58 kernel
  * instantiations (32 of k_shade, 8 each of k_walk, k_hard_shadow and k_hard_path, 2 of k_shade_hits) in one file took 8.5 minutes,
  * the families side by side take about 3.  The wrappers pick the
- * instantiation from runtime flags; the orchestration stays in actinon_hip.hip. */
+ * instantiation from runtime flags; the orchestration stays in actinon_hip.hip (the pipeline) and acn_calls.hip (the entry points
+ * beside it). */
 #ifndef ACN_LAUNCH_H
 #define ACN_LAUNCH_H
 
@@ -118,11 +119,6 @@ void acn_launch_select( const double* key, size_t n, double threshold, unsigned 
                         const double* src_pos_xy, unsigned long long raster_width, unsigned long long raster_first, int64_t* out_index,
                         double* out_pos_xy, unsigned long long* out_count, hipStream_t stream );
 void acn_launch_key_hist( const double* key, size_t n, unsigned long long* out_hist, hipStream_t stream );
-
-/* what the test seam acn_query_rays (k_query.hip) needs of a handle: its scene as the machine kernels get it */
-struct QueryEnv { SceneArgs s; size_t lds_node_bytes, lds_stack_bytes; hipStream_t stream; };
-int acn_query_env( acn_scene_handle* h, QueryEnv* q );   /* hipSetDevice included */
-int acn_query_fail( int code, const char* msg );          /* acn_last_error() */
 
 #define ACN_SCENE_ARGS_OF( s ) ( s ).dev, ( s ).nodes, ( s ).mats, ( s ).elems, ( s ).textures
 #define ACN_TASKQ_ARGS_OF( q ) ( q ).tasks, ( q ).idx[ 0 ], ( q ).idx[ 1 ], ( q ).idx[ 2 ], ( q ).idx[ 3 ], ( q ).counts, ( q ).task_cap, ( q ).hard_shadow, ( q ).hs_cap, ( q ).emit_terms

@@ -1,6 +1,6 @@
 /* acn_select_host.h -- what acn_select_above* and acn_key_histogram* do without a handle and without the GPU: the reading of
  * acn_select_params, every argument check of the two calls, the bin of a key, acn_key_hist_edge and acn_key_hist_threshold.  Plain
- * C++, no HIP header: actinon_hip.hip calls these before it touches a handle, k_select.hip compiles the bin function for the device
+ * C++, no HIP header: acn_calls.hip calls these before it touches a handle, k_select.hip compiles the bin function for the device
  * as well (the one expression both sides use), and tests/csrc/select_cpu.cpp compiles the header on its own, as a shim for the
  * CPU tests and as a program that runs under the address and undefined-behaviour sanitizers.  A check returns an acn_status and, on
  * a refusal, the message acn_last_error will carry. */

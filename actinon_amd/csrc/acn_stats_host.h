@@ -1,5 +1,5 @@
 /* acn_stats_host.h -- the host-side checks of the lens and lens-statistics entry points that need neither a handle nor the GPU:
- * plain C++, no HIP.  actinon_hip.hip calls them before it touches a handle; tests/csrc/stats_cpu.cpp compiles them on their own
+ * plain C++, no HIP.  acn_calls.hip calls them before it touches a handle; tests/csrc/stats_cpu.cpp compiles them on their own
  * into a program that runs under the address and undefined-behaviour sanitizers.  Each returns an acn_status and, on a refusal, the
  * message acn_last_error will carry. */
 #ifndef ACN_STATS_HOST_H

@@ -1,4 +1,5 @@
-/* actinon_hip.hip -- libactinon_hip.so: kernels + the C ABI of include/actinon_hip.h (gfx950 only). */
+/* actinon_hip.hip -- libactinon_hip.so (gfx950 only): the handle's life cycle, the workspace, the wavefront pipeline with its concurrent
+ * lanes, and the entry points of include/actinon_hip.h that are the pipeline's own.  Every other entry point: acn_calls.hip. */
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
@@ -14,249 +15,16 @@
 #include <atomic>
 #include <condition_variable>
 
-#include "acn_launch.h"
-#include "acn_tables.h"
-#include "acn_chunkplan.h"
-#include "acn_stats_host.h"
-#include "acn_select_host.h"
+
+#include "acn_handle.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
-/* error plumbing */
-static thread_local std::string g_last_error;
-static int fail( int code, const std::string& msg ) { g_last_error = msg; return code; }
+/* error plumbing (fail and HIP_TRY: acn_handle.h) */
+thread_local std::string g_last_error;
 extern "C" const char* acn_last_error( void ) { return g_last_error.c_str(); }
 
-#define HIP_TRY( expr ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) \
-    return fail( ACN_ERR_DEVICE, std::string( #expr ) + ": " + hipGetErrorString( e_ ) ); } while( 0 )
-
-struct StageEvents { hipEvent_t a, b; int stage; };
-
-/* a persistent host thread per lane (creating a thread per call costs a HIP per-thread initialisation each time) */
-struct LaneWorker
-{
-    std::thread thread;
-    std::mutex m;
-    std::condition_variable cv;
-    std::function< void() > job;
-    bool has_job = false, done = true, quit = false;
-    void start()
-    {
-        thread = std::thread( [ this ]()
-        {
-            for( ;; )
-            {
-                std::function< void() > j;
-                {
-                    std::unique_lock< std::mutex > lk( m );
-                    cv.wait( lk, [ this ] { return has_job || quit; } );
-                    if( quit ) return;
-                    j = job; has_job = false;
-                }
-                j();
-                { std::lock_guard< std::mutex > lk( m ); done = true; }
-                cv.notify_all();
-            }
-        } );
-    }
-    void post( std::function< void() > j )
-    {
-        { std::lock_guard< std::mutex > lk( m ); job = std::move( j ); has_job = true; done = false; }
-        cv.notify_all();
-    }
-    void wait() { std::unique_lock< std::mutex > lk( m ); cv.wait( lk, [ this ] { return done; } ); }
-    void stop()
-    {
-        if( !thread.joinable() ) return;
-        { std::lock_guard< std::mutex > lk( m ); quit = true; }
-        cv.notify_all();
-        thread.join();
-    }
-};
-
-/* Tunables, read from the environment ONCE per acn_scene_upload (never from the render path: getenv there would race a
- * host that changes its environment, and would let a value change between the concurrent lanes of one call) */
-struct Tunables
-{
-    size_t   workspace_mb = 0;         /* ACN_WORKSPACE_MB: upper bound of the queue workspace of one handle (all its lanes); 0: 64 GiB or a
-                                          quarter of the device memory that is free at upload, whichever is less */
-    size_t   chunk = 0;                /* ACN_CHUNK: sample positions per pipeline run, 0 = derived from the queue capacity */
-    int      lanes = 6;                /* ACN_LANES: concurrent pipeline runs of a large call (4 until round 4, each on grids twice the size: create_lane) */
-    unsigned grid = 0;                 /* ACN_GRID: workgroups of the persistent kernels, 0 = 4 per compute unit */
-    unsigned shade_grid = 0;           /* ACN_SHADE_GRID: workgroups of k_shade, 0 = 4 per compute unit */
-    unsigned walk_grid = 0;            /* ACN_WALK_GRID: workgroups of k_walk (256 VGPRs: two of its waves fill a SIMD's register file), 0 = as ACN_GRID */
-    uint32_t stack_cap = 512;          /* ACN_STACK_CAP: private ray slots per k_walk wave */
-    uint32_t fetch_walk = 64;          /* ACN_FETCH_WALK: fresh rays a k_walk wave reserves per cursor atomic */
-    uint32_t walk_passes = 4;          /* ACN_WALK_PASSES: launches of k_walk per path level (the last one finishes whatever is left on the waves' private
-                                          stacks).  12 until round 4: with k_walk at 4 waves per SIMD the private tail is cheap and the launches are not --
-                                          1080p 52.0 -> 50.3 ms, the 1/8 share 13.7 -> 12.1, c2 28.2 -> 26.3, paraffin_lamp 367 -> 339 (profiles/r04/ab_walk_passes_*) */
-    uint32_t private_limit = 32768;    /* ACN_PRIVATE_LIMIT: a generation of at most this many rays is finished on private stacks */
-    bool     private_limit_set = false; /* ... given by the environment: then it holds for chunks of every size (render_chunk) */
-    uint32_t class0_min = 0;           /* ACN_CLASS0_MIN: shading tasks with more samples than this take the 64-lane kernel, the others 16 / 4 / 1 lanes; 0: chosen per scene (acn_scene_upload) */
-    uint32_t fetch_shade = 16;         /* ACN_FETCH_SHADE: steps ( of 64 / lanes-per-task tasks ) a k_shade wave reserves per cursor atomic */
-    uint32_t fetch_hard = 256;         /* ACN_FETCH_HARD: records a wave of the hard-ray kernels / k_shade_hits reserves per atomic */
-    uint32_t stack_use = 0;            /* ACN_TEST_STACK_USE: slots of a private stack every walk pass but the last uses (tests of the overflow path) */
-    bool     debug_chunks = false;     /* ACN_DEBUG_CHUNKS=1: one line per chunk on stderr (size, queue marks, rates, capacities) */
-    bool     learn_passes = true;      /* ACN_LEARN_PASSES=0: every level gets ACN_WALK_PASSES launches of k_walk, needed or not */
-    bool     learn_sample = true;      /* ACN_LEARN_SAMPLE=0: no strided learning pass on a cold handle (learn_rates): the first chunks learn, as in round 3 */
-    bool     cold_pipeline = true;     /* ACN_COLD_PIPELINE=0: a cold handle makes its lanes before the learning pass, not beside it (render_lanes) */
-    bool     early_lanes = false;      /* ACN_EARLY_LANES=1: the lanes a whole frame of the scene's own raster will use are made during acn_scene_upload (a
-                                          helper thread beside the upload's own work, while the device is idle), not by the first call that needs them.
-                                          Measured and OFF (profiles/r04/ab_early_lanes_s42.txt): the streams cost the same ~10 ms each wherever they are made
-                                          and do not overlap the handle's own first stream, so the upload grows by 50 - 90 ms while the first frame loses
-                                          20 - 100 (1080p 114 - 174 -> 72 - 75 ms, c2 94 - 135 -> 48 - 49, paraffin_lamp 486 - 504 -> 466 - 479, hanging_lamp
-                                          417 - 426 -> 390 - 401); upload + first frame: 1080p 247 - 299 -> 277 - 323 ms, c2 189 - 261 -> 195 - 204, the
-                                          lamps +30.  For a host that uploads long before it renders */
-    size_t   lens_slice_rays = ( size_t )1 << 21;   /* ACN_LENS_SLICE_RAYS: rays of one slice of a lens call (acn_render_lens*): floor( this / K ) positions, at least 1 */
-    bool     count_work = false;       /* ACN_COUNT_WORK */
-    bool     stage_timing = false;     /* ACN_STAGE_TIMING */
-    acn_table_opts tables;             /* the switches of the scene tables (acn_tables.h) */
-    void read()
-    {
-        tables.no_leaf_pairs = getenv( "ACN_NO_LEAF_PAIRS" ) != nullptr;
-        tables.no_pair2 = getenv( "ACN_NO_PAIR2" ) != nullptr;
-        tables.no_prune_levels = getenv( "ACN_NO_PRUNE_LEVELS" ) != nullptr;
-        tables.no_simple_compounds = getenv( "ACN_NO_SIMPLE_COMPOUNDS" ) != nullptr;
-        tables.no_sc_cull = getenv( "ACN_NO_SC_CULL" ) != nullptr;
-        tables.no_sc_reversed = getenv( "ACN_NO_SC_REVERSED" ) != nullptr;
-        tables.verbose = getenv( "ACN_VERBOSE" ) != nullptr;
-        if( const char* e = getenv( "ACN_PRUNE_MIN" ) ) tables.prune_min = ( size_t )atoll( e );
-        if( const char* e = getenv( "ACN_LDS_MAX" ) ) { tables.lds_max = ( size_t )atoll( e ); tables.lds_max_set = true; }
-        if( const char* e = getenv( "ACN_WORKSPACE_MB" ) ) workspace_mb = ( size_t )atoll( e );
-        if( const char* e = getenv( "ACN_CHUNK" ) ) chunk = ( size_t )atoll( e );
-        if( const char* e = getenv( "ACN_LANES" ) ) lanes = atoi( e );
-        if( const char* e = getenv( "ACN_GRID" ) ) grid = ( unsigned )atoi( e );
-        if( const char* e = getenv( "ACN_SHADE_GRID" ) ) shade_grid = ( unsigned )atoi( e );
-        if( const char* e = getenv( "ACN_WALK_GRID" ) ) walk_grid = ( unsigned )atoi( e );
-        if( const char* e = getenv( "ACN_STACK_CAP" ) ) stack_cap = ( uint32_t )atoll( e );
-        if( const char* e = getenv( "ACN_TEST_STACK_USE" ) ) stack_use = ( uint32_t )atoll( e );
-        if( const char* e = getenv( "ACN_FETCH_WALK" ) ) fetch_walk = ( uint32_t )atoll( e );
-        if( const char* e = getenv( "ACN_FETCH_HARD" ) ) fetch_hard = ( uint32_t )atoll( e );
-        if( const char* e = getenv( "ACN_FETCH_SHADE" ) ) fetch_shade = ( uint32_t )atoll( e );
-        if( const char* e = getenv( "ACN_CLASS0_MIN" ) ) class0_min = ( uint32_t )atoll( e );
-        if( fetch_shade < 1 ) fetch_shade = 1;
-        if( const char* e = getenv( "ACN_WALK_PASSES" ) ) walk_passes = ( uint32_t )atoll( e );
-        if( const char* e = getenv( "ACN_PRIVATE_LIMIT" ) ) { private_limit = ( uint32_t )atoll( e ); private_limit_set = true; }
-        if( const char* e = getenv( "ACN_LENS_SLICE_RAYS" ) ) lens_slice_rays = ( size_t )atoll( e );
-        if( lens_slice_rays < 1 ) lens_slice_rays = 1;
-        if( lens_slice_rays > ( ( size_t )1 << 28 ) ) lens_slice_rays = ( size_t )1 << 28;
-        if( walk_passes < 1 ) walk_passes = 1;
-        if( walk_passes > ACN_MAX_WALK_PASSES ) walk_passes = ACN_MAX_WALK_PASSES;
-        if( fetch_walk < 64 ) fetch_walk = 64;
-        if( fetch_hard < 64 ) fetch_hard = 64;
-        count_work = getenv( "ACN_COUNT_WORK" ) != nullptr;
-        if( const char* e = getenv( "ACN_LEARN_PASSES" ) ) learn_passes = atoi( e ) != 0;
-        if( const char* e = getenv( "ACN_LEARN_SAMPLE" ) ) learn_sample = atoi( e ) != 0;
-        if( const char* e = getenv( "ACN_COLD_PIPELINE" ) ) cold_pipeline = atoi( e ) != 0;
-        if( const char* e = getenv( "ACN_EARLY_LANES" ) ) early_lanes = atoi( e ) != 0;
-        debug_chunks = getenv( "ACN_DEBUG_CHUNKS" ) != nullptr;
-        stage_timing = getenv( "ACN_STAGE_TIMING" ) != nullptr;
-        if( lanes < 1 ) lanes = 1;
-        if( lanes > 16 ) lanes = 16;
-        if( stack_cap < 256 ) stack_cap = 256;
-        if( stack_use == 0 || stack_use > stack_cap ) stack_use = stack_cap;
-    }
-};
-
-/* the queue workspace of one pipeline run */
-struct Workspace
-{
-    DTask*      tasks = nullptr;
-    uint32_t*   idx[ ACN_NCLASS ] = { nullptr, nullptr, nullptr, nullptr };
-    HitRec*     children = nullptr;
-    HardShadow* hard_shadow = nullptr;
-    HardPath*   hard_path = nullptr;
-    RayTask*    rays[ 2 ] = { nullptr, nullptr };
-    RayTask*    stacks = nullptr;   size_t stack_waves = 0;
-    uint32_t    cap[ 5 ] = { 0, 0, 0, 0, 0 };   /* records per queue, WQ_* */
-    size_t      bytes = 0;          /* device memory of the queues and stacks */
-    uint64_t    allocs = 0;         /* times this workspace was (re)allocated */
-    bool        trimmed = false;    /* it was already re-allocated smaller once */
-    uint32_t    sized_calls = 0;    /* calls of ensure_workspace with learned rates (the trim window, see there) */
-};
-/* the queues of a pipeline run.  Each is sized from its OWN demand per sample position (learned, below): on the wine glass a
- * position leaves 15 deferred shadow rays but 2 shading points, and one common capacity -- the former layout -- made every
- * queue as large as the fullest one needs (64 GiB for a 1080p frame of which 7 % were used). */
-enum { WQ_TASKS = 0, WQ_CHILDREN, WQ_HARD_SHADOW, WQ_HARD_PATH, WQ_RAYS, WQ_N };
+/* bytes per record of each queue (WQ_*) */
 static const size_t wq_bytes[ WQ_N ] = { sizeof( DTask ) + ACN_NCLASS * sizeof( uint32_t ), sizeof( HitRec ), sizeof( HardShadow ), sizeof( HardPath ), 2 * sizeof( RayTask ) };
-
-struct acn_scene_handle
-{
-    int device = 0;
-    DevScene dev{};
-    /* the resident scene and what the tables say about it: a lane borrows all of it from its parent (bind_lane) */
-    struct Resident
-    {
-        GNode*   d_nodes = nullptr;
-        GMat*    d_mats = nullptr;
-        int32_t* d_elems = nullptr;
-        acn_texture* d_textures = nullptr;
-        size_t scene_bytes[ 4 ] = { 0, 0, 0, 0 };
-        int max_csg_depth = 0;
-        size_t lds_bytes = 0;                      /* > 0: the node array fits the LDS staging budget */
-        size_t lds_stack_bytes = 0;                /* > 0: the machine kernels keep their CSG stacks in LDS */
-        bool prune = false;                        /* some root element has an interval-prune program: launch the PRUNE kernel variants */
-        bool leaf_lights = true;                   /* every light element is a plane / sphere */
-        uint32_t elem_pos_base = 0;                /* elems[ elem_pos_base + k ]: given-order position of entry k of the cost-ordered copy (k_hard_shadow: resume words) */
-        int n_levels = 1;                          /* path levels of the scene's trace_depth */
-        size_t n_lights = 1;                       /* elements of the light root */
-    } scene;
-    SCEntry* d_sc_table = nullptr;
-    double* d_sc_spheres = nullptr;            /* ( pos, radius ) of the sphere leaves of d_sc_table */
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    int cur_stage = 0;
-    bool stage_timing = false;                 /* ACN_OPT_STAGE_TIMING of the current call */
-    Tunables tun;
-    unsigned cus = 256;                        /* compute units of the device */
-    unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
-    unsigned walk_grid = 1024;                 /* ... of k_walk */
-    /* workspace of the wavefront pipeline */
-    Workspace ws;
-    uint32_t* d_counts = nullptr;              /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
-    uint32_t* h_counts = nullptr;              /* pinned copy */
-    unsigned long long* d_accum = nullptr;  size_t accum_cap = 0;
-    unsigned long long* d_counters = nullptr;
-    std::vector< StageEvents > events;  size_t events_used = 0;
-    bool count_work = false;                   /* ACN_OPT_COUNT_WORK of the current call */
-    uint32_t shard_rank = 0, shard_world = 1;  /* ACN_SHARD_SAMPLES of the current call */
-    uint64_t launches[ 4 ] = { 0, 0, 0, 0 };   /* walk, shade, finalize, hard-ray kernels */
-    uint64_t hard_rays = 0, walk_steps = 0, walk_rays = 0, shade_hit_recs = 0, host_syncs = 0, private_rays = 0, probe_rays = 0;
-    uint32_t flags_seen = 0;                   /* ACN_FLAG_* bits of the last call */
-    uint32_t rate_cnt = 0;                     /* positions of the chunk the rates were taken from */
-    acn_chunk_ctl ctl = { 0.7, 0, 0 };         /* acn_chunkplan.h.  fill_target: fraction of its capacity the fullest queue of a chunk is
-                                                  planned to reach: lowered by every overflow (a redone chunk is lost work), raised slowly
-                                                  by chunks that fit */
-    double rate[ 5 ] = { 0, 0, 0, 0, 0 };      /* learned: records per sample position a chunk leaves in each queue (WQ_*); 0: not known yet */
-    size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
-    uint64_t chunks = 0, retries = 0, levels = 0;
-    uint64_t peak_tasks = 0, peak_children = 0;
-    uint32_t walk_passes_seen[ ACN_MAX_PATH_LEVELS + 1 ] = { 0, 0, 0, 0, 0, 0 };   /* learned: passes of a level that had input in the last chunk (0: not known yet) */
-    unsigned long long* d_counters_keep = nullptr;   /* the work counters as they were before the current chunk (restored when it is redone) */
-    /* concurrent lanes (render_lanes): clones of this handle that share the resident scene and own a stream and a
-     * workspace each */
-    bool is_lane = false;
-    size_t budget_div = 1;                     /* workspace budget of a lane = the handle's budget / lanes */
-    std::vector< acn_scene_handle* > lanes;
-    /* lanes made during acn_scene_upload on a helper thread (early_lanes_begin), taken over by the first call that runs on lanes */
-    std::thread early_maker;
-    std::vector< acn_scene_handle* > early_made;
-    int early_status = 0; std::string early_message;
-    LaneWorker* worker = nullptr;              /* of a lane */
-    double* d_lane_in = nullptr; size_t lane_in_cap = 0;       /* a lane's gathered positions or rays (doubles) */
-    double* d_lane_out = nullptr; size_t lane_out_cap = 0;     /* ... and its results */
-    double* d_shard_pos = nullptr; size_t shard_pos_cap = 0;                                /* acn_render_main_pass_shard_dev: the rank's positions */
-    unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
-    uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
-    void* d_denoise = nullptr; size_t denoise_bytes = 0;                                    /* acn_denoise: guides and colour buffers, apart from the render workspace */
-    double* d_lens_rays = nullptr; double* d_lens_rad = nullptr; size_t lens_cap = 0;       /* acn_render_lens*: the rays [ 6 ] and the radiance [ 3 ] of a slice, lens_cap rays each */
-    unsigned long long* d_select_tiles = nullptr; size_t select_tiles_cap = 0;              /* acn_select_above*: the counts per tile and their total, select_tiles_cap words */
-    bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
-    std::string lane_error;
-    bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
-    int  lanes_used = 0;                       /* ... the first lanes_used of them */
-    bool one_lane = false;                     /* the last call would have used lanes but did not fit the workspace bound that way */
-};
 #define ACN_LEVEL_BLOCKS ( ACN_MAX_PATH_LEVELS + 1 )
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -298,102 +66,6 @@ __global__ void k_clear_slots( unsigned long long* __restrict__ accum, uint32_t 
     uint32_t p = order.position( base + i );
     if( p >= order.n ) return;
     accum[ ( size_t )p * 3 + 0 ] = 0; accum[ ( size_t )p * 3 + 1 ] = 0; accum[ ( size_t )p * 3 + 2 ] = 0;
-}
-
-/* cl_s_sat + cps_from_cl after the (cross-GPU) accumulation */
-__global__ void k_resolve( const double* __restrict__ lin, size_t n, double gamma, double* __restrict__ out_rgb,
-                           unsigned char* __restrict__ out_rgb8 )
-{
-    size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
-    if( i >= n ) return;
-    V3 c = cl_sat( mk( lin[ i * 3 ], lin[ i * 3 + 1 ], lin[ i * 3 + 2 ] ), gamma );
-    if( out_rgb ) { out_rgb[ i * 3 ] = c.x; out_rgb[ i * 3 + 1 ] = c.y; out_rgb[ i * 3 + 2 ] = c.z; }
-    if( out_rgb8 )
-    {
-        out_rgb8[ i * 3 + 0 ] = c.x > 0.0 ? c.x < 1.0 ? ( unsigned char )( c.x * 256 ) : 255 : 0;
-        out_rgb8[ i * 3 + 1 ] = c.y > 0.0 ? c.y < 1.0 ? ( unsigned char )( c.y * 256 ) : 255 : 0;
-        out_rgb8[ i * 3 + 2 ] = c.z > 0.0 ? c.z < 1.0 ? ( unsigned char )( c.z * 256 ) : 255 : 0;
-    }
-}
-
-/* obj_ray_exit + obj_estimate_envelope (objects.c:286-363), one lane */
-__global__ void k_estimate_envelope( DevScene sc, int node, uint64_t samples, uint32_t rseed, double radius_factor,
-                                     V3* scratch, double* out )
-{
-    Cnt< false > cnt;
-    NodeP hdr = &sc.nodes[ node ];
-    uint64_t size = 0;
-    V3 sum = mk( 0, 0, 0 );
-    uint64_t rv = rseed;
-    V3 rp = ld3( hdr->pos );
-    for( uint64_t i = 0; i < samples; i++ )
-    {
-        V3 rd = v_random_sphere_belt( &rv, 1.0 );
-        /* obj_ray_exit */
-        double exit_a = F3_INF;
-        {
-            V3 nor = mk( 0, 0, 0 );
-            double a = obj_ray_hit_dev( sref( sc ), node, rp, rd, true, &nor, &cnt );
-            if( a < F3_INF )
-            {
-                V3 lp = rp;
-                double s = 0;
-                while( a < F3_INF )
-                {
-                    a += F3_EPS * 2;
-                    s += a;
-                    lp = ray_pos( lp, rd, a );
-                    a = obj_ray_hit_dev( sref( sc ), node, lp, rd, true, &nor, &cnt );
-                }
-                if( v_mlv( nor, rd ) > 0 ) exit_a = s;
-            }
-        }
-        if( exit_a < F3_INF )
-        {
-            V3 pos = ray_pos( rp, rd, exit_a );
-            scratch[ size++ ] = pos;
-            sum = v_add( sum, ray_pos( rp, rd, exit_a ) );
-            rp = v_mlf( sum, ( 1.0 / size ) );
-            rp.x += F3_EPS * f3_rnd0( &rv );
-            rp.y += F3_EPS * f3_rnd0( &rv );
-            rp.z += F3_EPS * f3_rnd0( &rv );
-        }
-    }
-    double radius = F3_MAG;
-    if( size > 0 )
-    {
-        double max_r2 = 0;
-        for( uint64_t i = 0; i < size; i++ )
-        {
-            double r = v_diff_sqr( rp, scratch[ i ] );
-            max_r2 = r > max_r2 ? r : max_r2;
-        }
-        radius = acn_sqrt( max_r2 ) * radius_factor;
-    }
-    out[ 0 ] = rp.x; out[ 1 ] = rp.y; out[ 2 ] = rp.z; out[ 3 ] = radius;
-}
-
-__global__ void k_detmath( int op, const double* x, const double* y, double* out, size_t n )
-{
-    size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
-    if( i >= n ) return;
-    double a = x[ i ], b = y ? y[ i ] : 0.0, r = 0;
-    switch( op )
-    {
-        case 0: r = acn_sin( a ); break;
-        case 1: r = acn_cos( a ); break;
-        case 2: r = acn_tan( a ); break;
-        case 3: r = acn_acos( a ); break;
-        case 4: r = acn_log( a ); break;
-        case 5: r = acn_exp( a ); break;
-        case 6: r = acn_pow( a, b ); break;
-        case 7: r = acn_sqrt( a ); break;
-        case 8: r = a / b; break;
-        case 9: r = ( double )acn_f64_bits( a ); break;
-        case 10: r = acn_frexp_mant( a ); break;
-        default: break;
-    }
-    out[ i ] = r;
 }
 
 /* ------------------------------------------------------------------------------------------------------------------ */
@@ -753,12 +425,7 @@ static int stage_end( acn_scene_handle* h, hipStream_t stream )
     return ACN_OK;
 }
 
-static SceneArgs scene_args( const acn_scene_handle* h )
-{
-    SceneArgs s;
-    s.dev = h->dev; s.nodes = h->scene.d_nodes; s.mats = h->scene.d_mats; s.elems = h->scene.d_elems; s.textures = h->scene.d_textures; s.elem_pos_base = h->scene.elem_pos_base;
-    return s;
-}
+
 static KernelFlags kernel_flags( const acn_scene_handle* h )
 {
     KernelFlags f;
@@ -786,7 +453,6 @@ static LevelQ level_queues( const acn_scene_handle* h, int level )
     q.emit_terms = sharded && h->shard_rank != 0 ? 0u : 1u;
     return q;
 }
-static size_t machine_lds_bytes( const acn_scene_handle* h ) { return h->scene.lds_bytes + h->scene.lds_stack_bytes; }
 
 /* launches of k_walk for path level `level`: ACN_WALK_PASSES, but no more than the hits of the level have depth left */
 static uint32_t walk_passes_of_level( const acn_scene_handle* h, int level )
@@ -805,20 +471,6 @@ static uint32_t walk_passes_of_level( const acn_scene_handle* h, int level )
 
 #define ACN_LAUNCH( h, stage, stream, call ) do { int st_ = stage_begin( h, stage, stream ); if( st_ != ACN_OK ) return st_; call; \
     HIP_TRY( hipGetLastError() ); if( ( st_ = stage_end( h, stream ) ) != ACN_OK ) return st_; } while( 0 )
-
-/* What the primary rays of a call come from, handed down the whole chain (render_dispatch -> launch_render / render_lanes ->
- * learn_rates -> render_chunk -> acn_launch_walk): sample positions [ n ][ 2 ], the pixel centres of the main pass from pixel
- * `first` on (pos_xy == nullptr), or the caller's rays [ n ][ 6 ] -- seeded into the level-0 ray queue (k_rays.hip), where the
- * first walk pass reads them instead of making camera rays. */
-struct Primary
-{
-    const double* pos_xy = nullptr;
-    size_t first = 0;
-    const double* rays = nullptr;
-};
-static Primary primary_positions( const double* pos_xy ) { Primary p; p.pos_xy = pos_xy; return p; }
-static Primary primary_main_pass( size_t first ) { Primary p; p.first = first; return p; }
-static Primary primary_rays( const double* rays ) { Primary p; p.rays = rays; return p; }
 
 /* One chunk of positions [ base, base + cnt ).  The whole chain -- per path level: ( k_shade_hits -> ) the passes of
  * k_walk -> k_shade x 4 size classes -> k_hard_shadow -> k_hard_path -- is enqueued blind: every kernel takes
@@ -970,13 +622,7 @@ static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipS
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     int st = ensure_workspace( h, 4096 );   /* the starter set */
     if( st != ACN_OK ) return st;
-    if( h->accum_cap < n )
-    {
-        if( h->d_accum ) hipFree( h->d_accum );
-        h->d_accum = nullptr; h->accum_cap = 0;
-        HIP_TRY( hipMalloc( &h->d_accum, sizeof( unsigned long long ) * 3 * n ) );
-        h->accum_cap = n;
-    }
+    if( ( st = grow_device( ( void** )&h->d_accum, &h->accum_bytes, sizeof( unsigned long long ) * 3 * n ) ) != ACN_OK ) return st;
     if( h->tun.debug_chunks ) fprintf( stderr, "[acn sample] starter queues (%.2f GB) after %.2f ms\n", ( double )h->ws.bytes / 1e9, since() );
     /* as many positions as the starter queues hold by the guess launch_render makes for a first chunk, 4096 at most */
     const size_t s = h->dev.prm.path_samples ? h->dev.prm.path_samples : 1;
@@ -1057,33 +703,27 @@ static int learn_rates( acn_scene_handle* h, const Primary& prim, size_t n, hipS
 static int launch_render( acn_scene_handle* h, const Primary& prim, size_t n, double* d_out_rgb,
                           const acn_render_opts* opts, hipStream_t stream )
 {
-    if( opts && opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+    if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
     if( n == 0 ) return ACN_OK;
     if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many positions in one call" );
     h->seeded = prim.rays != nullptr;
-    int linear = ( opts && ( opts->flags & ACN_OPT_LINEAR_OUT ) ) ? 1 : 0;
-    h->count_work = ( opts && ( opts->flags & ACN_OPT_COUNT_WORK ) ) || h->tun.count_work;
+    int linear = ( opts->flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0;
+    h->count_work = ( opts->flags & ACN_OPT_COUNT_WORK ) || h->tun.count_work;
     h->shard_rank = 0; h->shard_world = 1;
-    if( opts && opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
+    if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
     {
         if( opts->shard_rank >= opts->shard_world ) return fail( ACN_ERR_ARG, "shard_rank >= shard_world" );
         h->shard_rank = opts->shard_rank; h->shard_world = opts->shard_world;
     }
-    else if( opts && opts->shard_mode > ACN_SHARD_SAMPLES ) return fail( ACN_ERR_ARG, "unknown shard_mode" );
-    h->stage_timing = ( opts && ( opts->flags & ACN_OPT_STAGE_TIMING ) ) || h->tun.stage_timing;
+    else if( opts->shard_mode > ACN_SHARD_SAMPLES ) return fail( ACN_ERR_ARG, "unknown shard_mode" );
+    h->stage_timing = ( opts->flags & ACN_OPT_STAGE_TIMING ) || h->tun.stage_timing;
     int st = learn_rates( h, prim, n, stream, n, h->walk_grid > h->grid ? h->walk_grid : h->grid );
     if( st != ACN_OK ) return st;
     /* (shard fields again: the learning pass renders unsharded) */
-    if( opts && opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 ) { h->shard_rank = opts->shard_rank; h->shard_world = opts->shard_world; }
+    if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 ) { h->shard_rank = opts->shard_rank; h->shard_world = opts->shard_world; }
     st = ensure_workspace( h, n );
     if( st != ACN_OK ) return st;
-    if( h->accum_cap < n )
-    {
-        if( h->d_accum ) hipFree( h->d_accum );
-        h->d_accum = nullptr; h->accum_cap = 0;
-        HIP_TRY( hipMalloc( &h->d_accum, sizeof( unsigned long long ) * 3 * n ) );
-        h->accum_cap = n;
-    }
+    if( ( st = grow_device( ( void** )&h->d_accum, &h->accum_bytes, sizeof( unsigned long long ) * 3 * n ) ) != ACN_OK ) return st;
     h->events_used = 0;
     h->launches[ 0 ] = h->launches[ 1 ] = h->launches[ 2 ] = h->launches[ 3 ] = 0;
     h->hard_rays = 0; h->walk_steps = 0; h->walk_rays = 0; h->shade_hit_recs = 0; h->host_syncs = 0; h->flags_seen = 0; h->private_rays = 0; h->probe_rays = 0;
@@ -1131,7 +771,7 @@ static int launch_render( acn_scene_handle* h, const Primary& prim, size_t n, do
     size_t base = 0;
     while( base < n_slots )
     {
-        if( opts && opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+        if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
         /* the planned chunk; a rest that is predicted to fill no queue beyond 85 % is taken whole (a second chunk would be
          * another whole chain of launches for a few positions); a retry is at most half of the chunk that overflowed
          * (acn_chunkplan.h) */
@@ -1304,17 +944,6 @@ static int lane_objects( int device, bool debug, acn_scene_handle** out )
     return ACN_OK;
 }
 
-/* a device buffer of at least `want` doubles: grown, never shrunk */
-static int grow_buffer( double** p, size_t* cap, size_t want )
-{
-    if( *cap >= want ) return ACN_OK;
-    if( *p ) hipFree( *p );
-    *p = nullptr; *cap = 0;
-    HIP_TRY( hipMalloc( p, sizeof( double ) * want ) );
-    *cap = want;
-    return ACN_OK;
-}
-
 static unsigned lane_grid( const acn_scene_handle* parent ) { return parent->tun.grid ? parent->tun.grid : parent->cus * 1u; }
 static void bind_lane( const acn_scene_handle* parent, int lanes, acn_scene_handle* l )
 {
@@ -1405,8 +1034,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
      * hipMalloc itself is not what a first call pays: 22 GB of queues take 1 - 5 ms (tools/bench_alloc: 0.02 ms per GB; a lane that
      * started as soon as its own queues existed gained nothing, profiles/r04/first_frames_s36_s38.txt). */
     mark( 1 );
-    acn_render_opts lane_opts{};
-    if( opts ) lane_opts = *opts;
+    acn_render_opts lane_opts = *opts;
     std::vector< int > status( lanes, ACN_OK );
     std::vector< std::string > message( lanes );
     auto post_lane = [ & ]( int k )
@@ -1421,8 +1049,8 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
                 HIP_TRY( hipSetDevice( h->device ) );
                 if( cnt == 0 ) { l->events_used = 0; HIP_TRY( hipMemset( l->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) ); return ACN_OK; }
                 /* the lane's share of the input: positions (2 doubles each) or rays (6) */
-                int st = grow_buffer( &l->d_lane_in, &l->lane_in_cap, ( prim.rays ? 6 : 2 ) * cnt );
-                if( st == ACN_OK ) st = grow_buffer( &l->d_lane_out, &l->lane_out_cap, 3 * cnt );
+                int st = grow_device( ( void** )&l->d_lane_in, &l->lane_in_bytes, sizeof( double ) * ( prim.rays ? 6 : 2 ) * cnt );
+                if( st == ACN_OK ) st = grow_device( ( void** )&l->d_lane_out, &l->lane_out_bytes, sizeof( double ) * 3 * cnt );
                 if( st != ACN_OK ) return st;
                 if( prim.rays )
                     hipLaunchKernelGGL( k_lane_gather_rays, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
@@ -1484,26 +1112,8 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     return ACN_OK;
 }
 
-/* the caller's options as far as the caller's header knew them (acn_render_opts.struct_size), the rest zero */
-static acn_render_opts opts_of( const acn_render_opts* in )
-{
-    acn_render_opts o{};
-    if( in )
-    {
-        /* 0: a caller that zero-initialises the struct (the memset idiom) and never heard of struct_size -- the word was a
-         * reserved zero in the first published layout, which already had the shard members: the 40-byte base layout */
-        size_t n = in->struct_size ? in->struct_size : ( size_t )ACN_RENDER_OPTS_BASE_SIZE;
-        if( n > sizeof( o ) ) n = sizeof( o );
-        memcpy( &o, in, n );
-    }
-    o.struct_size = ( uint32_t )sizeof( o );
-    return o;
-}
-#define ACN_OPTS_VIEW const acn_render_opts opts_seen_ = opts_of( opts ); opts = &opts_seen_;
-
 /* one pipeline run on the handle itself, or the concurrent lanes */
-static int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, double* d_out_rgb,
-                            const acn_render_opts* opts, hipStream_t stream )
+int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, double* d_out_rgb, const acn_render_opts* opts, hipStream_t stream )
 {
     int lanes = lanes_for( h, n );
     /* Lanes pay when a lane's share is ONE chunk: their chains overlap.  A call whose queues cannot hold it in one chunk
@@ -1545,201 +1155,61 @@ static int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, 
     return render_lanes( h, lanes, prim, n, d_out_rgb, opts, stream );   /* (makes the lanes it lacks) */
 }
 
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* the pipeline's own entry points (every other one: acn_calls.hip) */
 extern "C" int acn_render_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rgb,
                                          const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( n && ( !d_pos_xy || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    int st = render_dispatch( h, primary_positions( ( const double* )d_pos_xy ), n, ( double* )d_out_rgb, opts, stream );
-    if( st != ACN_OK ) return st;
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st == ACN_OK ) st = render_dispatch( h, primary_positions( ( const double* )d_pos_xy ), n, ( double* )d_out_rgb, &c.opts, c.stream );
+    return st != ACN_OK ? st : call_end( c );
 }
 
 extern "C" int acn_render_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, void* d_out_rgb,
                                          const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( count && !d_out_rgb ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( first + count > h->dev.prm.image_width * h->dev.prm.image_height ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    int st = render_dispatch( h, primary_main_pass( first ), count, ( double* )d_out_rgb, opts, stream );
-    if( st != ACN_OK ) return st;
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-/* an entry point on host buffers: n records of in_len doubles copied in, the device-buffer call `dev( d_in, d_out )` (on the
- * handle's own stream: synchronous), n records of out_len doubles copied out */
-template< class DevCall >
-static int on_host_buffers( acn_scene_handle* h, const double* in, size_t in_len, size_t n, double* out, size_t out_len, DevCall dev )
-{
-    HIP_TRY( hipSetDevice( h->device ) );
-    double* d_in = nullptr; double* d_out = nullptr;
-    HIP_TRY( hipMalloc( &d_in, sizeof( double ) * in_len * n ) );
-    hipError_t e = hipMalloc( &d_out, sizeof( double ) * out_len * n );
-    if( e != hipSuccess ) { hipFree( d_in ); return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) ); }
-    int st = ACN_OK;
-    if( hipMemcpy( d_in, in, sizeof( double ) * in_len * n, hipMemcpyHostToDevice ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "H2D copy failed" );
-    if( st == ACN_OK ) st = dev( d_in, d_out );
-    if( st == ACN_OK && hipMemcpy( out, d_out, sizeof( double ) * out_len * n, hipMemcpyDeviceToHost ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "D2H copy failed" );
-    hipFree( d_in ); hipFree( d_out );
-    return st;
+    int st = pixel_range_check( h, first, count );
+    if( st == ACN_OK ) st = call_begin( h, &c );
+    if( st == ACN_OK ) st = render_dispatch( h, primary_main_pass( first ), count, ( double* )d_out_rgb, &c.opts, c.stream );
+    return st != ACN_OK ? st : call_end( c );
 }
 
 extern "C" int acn_render_positions( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rgb,
                                      const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( n && ( !pos_xy || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
     if( n == 0 ) return ACN_OK;
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    return on_host_buffers( h, pos_xy, 2, n, out_rgb, 3, [ & ]( double* d_pos, double* d_out ) { return acn_render_positions_dev( h, d_pos, n, d_out, &o ); } );
+    c.opts.stream = nullptr;
+    return host_in_out( h, pos_xy, sizeof( double ) * 2 * n, out_rgb, sizeof( double ) * 3 * n,
+                        [ & ]( void* d_pos, void* d_out ) { return acn_render_positions_dev( h, d_pos, n, d_out, &c.opts ); } );
 }
 
 /* ---- caller-supplied primary rays (k_rays.hip) ---- */
 extern "C" int acn_render_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, void* d_out_rgb, const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( n && ( !d_rays || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
     if( n == 0 ) return ACN_OK;
     if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many rays in one call" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    /* every ray is checked before anything is rendered: the lowest index of a refused one, one word read back */
-    if( !h->d_ray_check ) HIP_TRY( hipMalloc( &h->d_ray_check, sizeof( unsigned long long ) ) );
-    HIP_TRY( hipMemsetAsync( h->d_ray_check, 0xFF, sizeof( unsigned long long ), stream ) );
-    acn_launch_check_rays( ( const double* )d_rays, n, h->d_ray_check, stream );
-    HIP_TRY( hipGetLastError() );
-    unsigned long long bad = 0;
-    HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check, sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
-    HIP_TRY( hipStreamSynchronize( stream ) );
-    if( bad < n ) return fail( ACN_ERR_ARG, "ray " + std::to_string( bad ) + ": a component is not finite or the direction has no length" );
-    int st = render_dispatch( h, primary_rays( ( const double* )d_rays ), n, ( double* )d_out_rgb, opts, stream );
-    if( st != ACN_OK ) return st;
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st == ACN_OK ) st = check_rays( h, ( const double* )d_rays, n, c.stream );
+    if( st == ACN_OK ) st = render_dispatch( h, primary_rays( ( const double* )d_rays ), n, ( double* )d_out_rgb, &c.opts, c.stream );
+    return st != ACN_OK ? st : call_end( c );
 }
 
 extern "C" int acn_render_rays( acn_scene_handle* h, const double* rays, size_t n, double* out_rgb, const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( n && ( !rays || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
     if( n == 0 ) return ACN_OK;
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    return on_host_buffers( h, rays, 6, n, out_rgb, 3, [ & ]( double* d_rays, double* d_out ) { return acn_render_rays_dev( h, d_rays, n, d_out, &o ); } );
-}
-
-extern "C" int acn_camera_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, void* d_out_rays, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && ( !d_pos_xy || !d_out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( n == 0 ) return ACN_OK;
-    if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many positions in one call" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    acn_launch_camera_rays( h->dev, ( const double* )d_pos_xy, n, ( double* )d_out_rays, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rays )
-{
-    if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( n == 0 ) return ACN_OK;
-    return on_host_buffers( h, pos_xy, 2, n, out_rays, 6, [ & ]( double* d_pos, double* d_out ) { return acn_camera_rays_dev( h, d_pos, n, d_out, nullptr ); } );
-}
-
-/* ---- surface records (k_surface.hip) ---- */
-static int surface_dev( acn_scene_handle* h, const double* d_rays, const double* d_pos_xy, size_t n, uint32_t mode, double* d_out,
-                        const acn_render_opts* opts )
-{
-    if( !h || ( n && ( !( d_rays || d_pos_xy ) || !d_out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
-    if( opts && opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
-    if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    if( !h->d_surface_flags )
-    {
-        HIP_TRY( hipMalloc( &h->d_surface_flags, sizeof( uint32_t ) ) );
-        HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
-    }
-    if( d_rays )
-    {
-        /* every ray is checked before anything is written: the lowest index of a refused one, one word read back */
-        if( !h->d_ray_check ) HIP_TRY( hipMalloc( &h->d_ray_check, sizeof( unsigned long long ) ) );
-        HIP_TRY( hipMemsetAsync( h->d_ray_check, 0xFF, sizeof( unsigned long long ), stream ) );
-        acn_launch_check_rays( d_rays, n, h->d_ray_check, stream );
-        HIP_TRY( hipGetLastError() );
-        unsigned long long bad = 0;
-        HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check, sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
-        HIP_TRY( hipStreamSynchronize( stream ) );
-        if( bad < n ) return fail( ACN_ERR_ARG, "ray " + std::to_string( bad ) + ": a component is not finite or the direction has no length" );
-    }
-    SceneArgs s = scene_args( h );
-    s.dev.flags = h->d_surface_flags;   /* the pipeline's word stays the pipeline's */
-    acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h ), stream, s, d_rays, d_pos_xy, n, d_out );
-    HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) )
-    {
-        uint32_t flags = 0;
-        HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags, sizeof( flags ), hipMemcpyDeviceToHost, stream ) );
-        HIP_TRY( hipStreamSynchronize( stream ) );
-        if( flags )
-        {
-            HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
-            return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow in a surface call" );
-        }
-    }
-    return ACN_OK;
-}
-
-extern "C" int acn_surface_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && !d_rays ) ) return fail( ACN_ERR_ARG, "null argument" );
-    return surface_dev( h, ( const double* )d_rays, nullptr, n, mode, ( double* )d_out, opts );
-}
-
-extern "C" int acn_surface_positions_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && !d_pos_xy ) ) return fail( ACN_ERR_ARG, "null argument" );
-    return surface_dev( h, nullptr, ( const double* )d_pos_xy, n, mode, ( double* )d_out, opts );
-}
-
-/* the host-buffer forms: synchronous, on the handle's own stream */
-static int surface_host( acn_scene_handle* h, const double* in, size_t in_len, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
-{
-    if( !h || ( n && ( !in || !out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
-    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
-    if( n == 0 ) return ACN_OK;
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    return on_host_buffers( h, in, in_len, n, out, ACN_SURF_STRIDE, [ & ]( double* d_in, double* d_out )
-    {
-        return in_len == 6 ? surface_dev( h, d_in, nullptr, n, mode, d_out, &o ) : surface_dev( h, nullptr, d_in, n, mode, d_out, &o );
-    } );
-}
-
-extern "C" int acn_surface_rays( acn_scene_handle* h, const double* rays, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    return surface_host( h, rays, 6, n, mode, out, opts );
-}
-
-extern "C" int acn_surface_positions( acn_scene_handle* h, const double* pos_xy, size_t n, uint32_t mode, double* out, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    return surface_host( h, pos_xy, 2, n, mode, out, opts );
+    c.opts.stream = nullptr;
+    return host_in_out( h, rays, sizeof( double ) * 6 * n, out_rgb, sizeof( double ) * 3 * n,
+                        [ & ]( void* d_rays, void* d_out ) { return acn_render_rays_dev( h, d_rays, n, d_out, &c.opts ); } );
 }
 
 /* ---- sharding of whole positions: tiles of ACN_SHARD_TILE, round-robin (plain arithmetic, no GPU) ---- */
@@ -1774,562 +1244,37 @@ __global__ void k_shard_unpack( const double* __restrict__ gathered, size_t n, u
 extern "C" int acn_render_main_pass_shard_dev( acn_scene_handle* h, size_t first, size_t count, uint32_t rank, uint32_t world,
                                                void* d_part, const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( count && !d_part ) || world == 0 || rank >= world ) return fail( ACN_ERR_ARG, "bad argument" );
-    if( first + count > h->dev.prm.image_width * h->dev.prm.image_height ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
+    int st = pixel_range_check( h, first, count );
+    if( st == ACN_OK ) st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
     const size_t mine = acn_shard_tile_count( count, rank, world ), padded = acn_shard_tile_padded( count, world );
-    if( padded > mine ) HIP_TRY( hipMemsetAsync( ( double* )d_part + 3 * mine, 0, sizeof( double ) * 3 * ( padded - mine ), stream ) );
+    if( padded > mine ) HIP_TRY( hipMemsetAsync( ( double* )d_part + 3 * mine, 0, sizeof( double ) * 3 * ( padded - mine ), c.stream ) );
     if( mine )
     {
-        if( h->shard_pos_cap < mine )
-        {
-            if( h->d_shard_pos ) hipFree( h->d_shard_pos );
-            h->d_shard_pos = nullptr; h->shard_pos_cap = 0;
-            HIP_TRY( hipMalloc( &h->d_shard_pos, sizeof( double ) * 2 * mine ) );
-            h->shard_pos_cap = mine;
-        }
-        hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( mine + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
+        if( ( st = grow_device( ( void** )&h->d_shard_pos, &h->shard_pos_bytes, sizeof( double ) * 2 * mine ) ) != ACN_OK ) return st;
+        hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( mine + 255 ) / 256 ) ), dim3( 256 ), 0, c.stream,
                             ( const double* )nullptr, first, ( uint64_t )h->dev.prm.image_width, mine, ( int )world, ( int )rank, h->d_shard_pos );
         HIP_TRY( hipGetLastError() );
-        int st = render_dispatch( h, primary_positions( h->d_shard_pos ), mine, ( double* )d_part, opts, stream );
-        if( st != ACN_OK ) return st;
+        if( ( st = render_dispatch( h, primary_positions( h->d_shard_pos ), mine, ( double* )d_part, &c.opts, c.stream ) ) != ACN_OK ) return st;
     }
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
+    return call_end( c );
 }
 
 extern "C" int acn_shard_unpack_dev( acn_scene_handle* h, const void* d_gathered, size_t count, uint32_t world, void* d_frame,
                                      const acn_render_opts* opts )
 {
-    ACN_OPTS_VIEW
+    Call c( opts );
     if( !h || ( count && ( !d_gathered || !d_frame ) ) || world == 0 ) return fail( ACN_ERR_ARG, "bad argument" );
     if( count == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    hipLaunchKernelGGL( k_shard_unpack, dim3( ( unsigned )( ( count + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    hipLaunchKernelGGL( k_shard_unpack, dim3( ( unsigned )( ( count + 255 ) / 256 ) ), dim3( 256 ), 0, c.stream,
                         ( const double* )d_gathered, count, world, acn_shard_tile_padded( count, world ), ( double* )d_frame );
     HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
+    return call_end( c );
 }
-
-extern "C" int acn_resolve_dev( acn_scene_handle* h, const void* d_linear_rgb, size_t n, void* d_out_rgb, void* d_out_rgb8,
-                                const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && !d_linear_rgb ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    hipLaunchKernelGGL( k_resolve, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
-                        ( const double* )d_linear_rgb, n, h->dev.prm.gamma, ( double* )d_out_rgb, ( unsigned char* )d_out_rgb8 );
-    HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-/* ---- the edge-avoiding filter (k_denoise.hip) ---- */
-struct DenoiseSetup { uint32_t iterations, normal_power_log2, no_demodulate; double sigma_plane, sigma_lum; };
-
-/* every check of a denoise call: on the host, before the handle is touched */
-static int denoise_check( const acn_scene_handle* h, const void* lin, const void* surf, size_t width, size_t height,
-                          const acn_denoise_params* prm, const void* out, const acn_render_opts* opts, DenoiseSetup* su )
-{
-    if( !h || !lin || !surf || !out ) return fail( ACN_ERR_ARG, "null argument" );
-    const size_t max_n = ( size_t )1 << 31;
-    if( width == 0 || height == 0 ) return fail( ACN_ERR_ARG, "a frame to denoise needs a width and a height" );
-    if( width > max_n || height > max_n || width * height > max_n ) return fail( ACN_ERR_ARG, "a frame to denoise has at most 2^31 pixels" );
-    acn_denoise_params p{};
-    if( prm )
-    {
-        if( prm->struct_size < sizeof( uint32_t ) ) return fail( ACN_ERR_ARG, "acn_denoise_params.struct_size " + std::to_string( prm->struct_size ) + " is smaller than its first member" );
-        memcpy( &p, prm, prm->struct_size < sizeof( p ) ? prm->struct_size : sizeof( p ) );
-    }
-    if( p.flags & ~( ACN_DENOISE_NO_DEMODULATE | ACN_DENOISE_NORMAL_POWER_SET ) ) return fail( ACN_ERR_ARG, "unknown acn_denoise_params.flags bits" );
-    if( p.iterations > ACN_DENOISE_MAX_ITERATIONS ) return fail( ACN_ERR_ARG, "acn_denoise_params.iterations " + std::to_string( p.iterations ) + " is above 8" );
-    if( p.normal_power_log2 > ACN_DENOISE_MAX_NORMAL_POWER_LOG2 ) return fail( ACN_ERR_ARG, "acn_denoise_params.normal_power_log2 " + std::to_string( p.normal_power_log2 ) + " is above 10" );
-    const double sig[ 2 ] = { p.sigma_plane, p.sigma_lum };
-    for( double s : sig ) if( !( s >= 0 ) || s > 1.7976931348623157e308 ) return fail( ACN_ERR_ARG, "a sigma of acn_denoise_params is negative or not finite" );
-    if( opts && opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a denoise call is not sharded: the filter needs the whole frame" );
-    su->iterations = p.iterations ? p.iterations : ACN_DENOISE_DEFAULT_ITERATIONS;
-    su->normal_power_log2 = ( p.normal_power_log2 || ( p.flags & ACN_DENOISE_NORMAL_POWER_SET ) ) ? p.normal_power_log2 : ACN_DENOISE_DEFAULT_NORMAL_POWER_LOG2;
-    su->no_demodulate = ( p.flags & ACN_DENOISE_NO_DEMODULATE ) ? 1u : 0u;
-    su->sigma_plane = p.sigma_plane != 0 ? p.sigma_plane : ACN_DENOISE_DEFAULT_SIGMA_PLANE;
-    su->sigma_lum = p.sigma_lum != 0 ? p.sigma_lum : ACN_DENOISE_DEFAULT_SIGMA_LUM;
-    return ACN_OK;
-}
-
-extern "C" int acn_denoise_dev( acn_scene_handle* h, const void* d_linear_rgb, const void* d_surface, size_t width, size_t height,
-                                const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    DenoiseSetup su;
-    int st = denoise_check( h, d_linear_rgb, d_surface, width, height, prm, d_out_rgb, opts, &su );
-    if( st != ACN_OK ) return st;
-    if( ( uintptr_t )d_surface % 16 ) return fail( ACN_ERR_ARG, "the surface records of a denoise call are read 16 bytes at a time: align the buffer" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    const size_t need = width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL;
-    if( h->denoise_bytes < need )
-    {
-        if( h->d_denoise ) hipFree( h->d_denoise );   /* (waits for whatever still reads it) */
-        h->d_denoise = nullptr; h->denoise_bytes = 0;
-        HIP_TRY( hipMalloc( &h->d_denoise, need ) );
-        h->denoise_bytes = need;
-    }
-    acn_launch_denoise( ( const double* )d_linear_rgb, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2,
-                        su.no_demodulate, su.sigma_plane, su.sigma_lum, h->d_denoise, ( double* )d_out_rgb, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_denoise( acn_scene_handle* h, const double* linear_rgb, const double* surface, size_t width, size_t height,
-                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    DenoiseSetup su;
-    int st = denoise_check( h, linear_rgb, surface, width, height, prm, out_rgb, opts, &su );
-    if( st != ACN_OK ) return st;
-    HIP_TRY( hipSetDevice( h->device ) );
-    const size_t n = width * height;
-    double* d_rgb = nullptr; double* d_surf = nullptr;
-    HIP_TRY( hipMalloc( &d_rgb, sizeof( double ) * 3 * n ) );
-    hipError_t e = hipMalloc( &d_surf, sizeof( double ) * ACN_SURF_STRIDE * n );
-    if( e != hipSuccess ) { hipFree( d_rgb ); return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) ); }
-    if( hipMemcpy( d_rgb, linear_rgb, sizeof( double ) * 3 * n, hipMemcpyHostToDevice ) != hipSuccess ||
-        hipMemcpy( d_surf, surface, sizeof( double ) * ACN_SURF_STRIDE * n, hipMemcpyHostToDevice ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "H2D copy failed" );
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    if( st == ACN_OK ) st = acn_denoise_dev( h, d_rgb, d_surf, width, height, prm, d_rgb, &o );   /* in place */
-    if( st == ACN_OK && hipMemcpy( out_rgb, d_rgb, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) != hipSuccess ) st = fail( ACN_ERR_DEVICE, "D2H copy failed" );
-    hipFree( d_rgb ); hipFree( d_surf );
-    return st;
-}
-
-/* ---- the thin-lens camera (k_lens.hip) ---- */
-
-/* every check of a lens call's parameters: on the host, before the handle is touched.  window: the samples an acn_lens_rays call asks for */
-static int lens_check( const acn_scene_handle* h, const acn_lens_params* prm, const uint32_t* window, LensSetup* ls )
-{
-    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
-    acn_lens_params p;
-    std::string msg;
-    if( acn_lens_params_read( prm, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );   /* (acn_stats_host.h: the members alone) */
-    if( p.aperture_radius > 0 && !( h->dev.prm.camera_focal_length > 0 ) ) return fail( ACN_ERR_ARG, "an open aperture needs a camera_focal_length above 0: the plane in focus lies in front of the camera" );
-    ls->samples = p.samples ? p.samples : ACN_LENS_DEFAULT_SAMPLES;
-    ls->jitter = ( p.flags & ACN_LENS_JITTER ) ? 1u : 0u;
-    ls->seed = ACN_LENS_SEED + ( uint64_t )p.seed;
-    ls->aperture_radius = p.aperture_radius;
-    ls->focus_distance = p.aperture_radius > 0 ? p.focus_distance : 0.0;
-    if( window )
-    {
-        if( window[ 1 ] == 0 ) return fail( ACN_ERR_ARG, "n_samples is 0" );
-        if( ( uint64_t )window[ 0 ] + window[ 1 ] > ls->samples ) return fail( ACN_ERR_ARG, "first_sample + n_samples is above the " + std::to_string( ls->samples ) + " samples of the lens" );
-    }
-    return ACN_OK;
-}
-
-extern "C" int acn_lens_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
-                                  uint32_t n_samples, void* d_out_rays, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && ( !d_pos_xy || !d_out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    LensSetup ls;
-    const uint32_t window[ 2 ] = { first_sample, n_samples };
-    int st = lens_check( h, prm, window, &ls );
-    if( st != ACN_OK ) return st;
-    if( n > 0xFFFFFF00ull / n_samples ) return fail( ACN_ERR_ARG, "too many rays in one call" );
-    if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    acn_launch_lens_rays( h->dev, ( const double* )d_pos_xy, 0, n, ls, first_sample, n_samples, ( double* )d_out_rays, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_lens_rays( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t first_sample,
-                              uint32_t n_samples, double* out_rays )
-{
-    if( !h || ( n && ( !pos_xy || !out_rays ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    LensSetup ls;
-    const uint32_t window[ 2 ] = { first_sample, n_samples };
-    int st = lens_check( h, prm, window, &ls );
-    if( st != ACN_OK ) return st;
-    if( n > 0xFFFFFF00ull / n_samples ) return fail( ACN_ERR_ARG, "too many rays in one call" );
-    if( n == 0 ) return ACN_OK;
-    return on_host_buffers( h, pos_xy, 2, n, out_rays, ( size_t )6 * n_samples, [ & ]( double* d_pos, double* d_out )
-    {
-        return acn_lens_rays_dev( h, d_pos, n, prm, first_sample, n_samples, d_out, nullptr );
-    } );
-}
-
-/* a lens call after its null checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice: rays, the ray path of
- * acn_render_rays_dev (linear, its validity kernel left out: the rays are valid by construction), the ordered mean */
-static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, double* d_out_rgb,
-                        const acn_render_opts* opts, double* d_stats = nullptr, bool with_stats = false )
-{
-    LensSetup ls;
-    int st = lens_check( h, prm, nullptr, &ls );
-    if( st != ACN_OK ) return st;
-    const int linear = ( opts->flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0;
-    if( opts->shard_mode > ACN_SHARD_SAMPLES ) return fail( ACN_ERR_ARG, "unknown shard_mode" );
-    if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
-    {
-        if( opts->shard_rank >= opts->shard_world ) return fail( ACN_ERR_ARG, "shard_rank >= shard_world" );
-        if( with_stats ) return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
-        if( !linear ) return fail( ACN_ERR_ARG, "a lens call sharded by samples gives partial means: it needs ACN_OPT_LINEAR_OUT" );
-    }
-    if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
-    if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
-    const size_t K = ls.samples;
-    size_t slice = h->tun.lens_slice_rays / K;
-    if( slice < 1 ) slice = 1;
-    if( slice > n ) slice = n;
-    if( h->lens_cap < slice * K )
-    {
-        if( h->d_lens_rays ) hipFree( h->d_lens_rays );   /* (waits for whatever still reads them) */
-        if( h->d_lens_rad ) hipFree( h->d_lens_rad );
-        h->d_lens_rays = h->d_lens_rad = nullptr; h->lens_cap = 0;
-        HIP_TRY( hipMalloc( &h->d_lens_rays, sizeof( double ) * 6 * slice * K ) );
-        HIP_TRY( hipMalloc( &h->d_lens_rad, sizeof( double ) * 3 * slice * K ) );
-        h->lens_cap = slice * K;
-    }
-    acn_render_opts ray_opts = *opts;
-    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
-    for( size_t base = 0; base < n; base += slice )
-    {
-        if( opts->cancel && *opts->cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
-        const size_t cnt = n - base < slice ? n - base : slice;
-        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays, stream );
-        HIP_TRY( hipGetLastError() );
-        st = render_dispatch( h, primary_rays( h->d_lens_rays ), cnt * K, h->d_lens_rad, &ray_opts, stream );
-        if( st != ACN_OK ) return st;
-        if( with_stats )
-            acn_launch_lens_reduce_stats( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
-                                          d_stats + ( size_t )ACN_STATS_STRIDE * base, stream );
-        else
-            acn_launch_lens_reduce( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, stream );
-        HIP_TRY( hipGetLastError() );
-    }
-    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_render_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
-                                    const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && ( !d_pos_xy || !d_out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    return render_lens( h, ( const double* )d_pos_xy, 0, n, prm, ( double* )d_out_rgb, opts );
-}
-
-extern "C" int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
-                                              const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( count && !d_out_rgb ) ) return fail( ACN_ERR_ARG, "null argument" );
-    const size_t pixels = h->dev.prm.image_width * h->dev.prm.image_height;
-    if( first > pixels || count > pixels - first ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
-    return render_lens( h, nullptr, first, count, prm, ( double* )d_out_rgb, opts );
-}
-
-extern "C" int acn_render_lens( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
-                                const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && ( !pos_xy || !out_rgb ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    LensSetup ls;
-    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
-    if( st != ACN_OK ) return st;
-    if( n == 0 ) return ACN_OK;
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    return on_host_buffers( h, pos_xy, 2, n, out_rgb, 3, [ & ]( double* d_pos, double* d_out ) { return acn_render_lens_dev( h, d_pos, n, prm, d_out, &o ); } );
-}
-
-/* ---- lens sample statistics (k_lens.hip, k_denoise.hip; the checks that need no handle: acn_stats_host.h) ---- */
-static int stats_buffer( const void* stats, size_t n, const char* what )
-{
-    std::string msg;
-    return acn_stats_buffer_check( stats, n, what, &msg ) == ACN_OK ? ACN_OK : fail( ACN_ERR_ARG, msg );
-}
-
-extern "C" int acn_render_lens_stats_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
-                                          void* d_stats, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && ( !d_pos_xy || !d_stats ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( stats_buffer( d_stats, n, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
-    return render_lens( h, ( const double* )d_pos_xy, 0, n, prm, ( double* )d_out_rgb, opts, ( double* )d_stats, true );
-}
-
-extern "C" int acn_render_lens_stats_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, void* d_out_rgb,
-                                                    void* d_stats, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( count && !d_stats ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( stats_buffer( d_stats, count, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
-    const size_t pixels = h->dev.prm.image_width * h->dev.prm.image_height;
-    if( first > pixels || count > pixels - first ) return fail( ACN_ERR_ARG, "pixel range outside the image" );
-    return render_lens( h, nullptr, first, count, prm, ( double* )d_out_rgb, opts, ( double* )d_stats, true );
-}
-
-/* device copies of host arrays for one call; everything is freed when it goes */
-struct DevCopies
-{
-    std::vector< void* > held;
-    ~DevCopies() { for( void* p : held ) hipFree( p ); }
-    /* null on failure; src (nullable) is copied in */
-    void* make( const void* src, size_t bytes )
-    {
-        void* d = nullptr;
-        if( hipMalloc( &d, bytes ? bytes : 1 ) != hipSuccess ) return nullptr;
-        held.push_back( d );
-        if( src && bytes && hipMemcpy( d, src, bytes, hipMemcpyHostToDevice ) != hipSuccess ) return nullptr;
-        return d;
-    }
-};
-
-extern "C" int acn_render_lens_stats( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, double* out_rgb,
-                                      double* stats, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && ( !pos_xy || !stats ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    LensSetup ls;
-    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
-    if( st != ACN_OK ) return st;
-    if( opts->shard_mode == ACN_SHARD_SAMPLES && opts->shard_world > 1 )
-        return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
-    if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    DevCopies dc;
-    void* d_pos = dc.make( pos_xy, sizeof( double ) * 2 * n );
-    void* d_out = out_rgb ? dc.make( nullptr, sizeof( double ) * 3 * n ) : nullptr;
-    void* d_st = dc.make( nullptr, sizeof( double ) * ACN_STATS_STRIDE * n );
-    if( !d_pos || !d_st || ( out_rgb && !d_out ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    st = acn_render_lens_stats_dev( h, d_pos, n, prm, d_out, d_st, &o );
-    if( st != ACN_OK ) return st;
-    if( out_rgb ) HIP_TRY( hipMemcpy( out_rgb, d_out, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) );
-    HIP_TRY( hipMemcpy( stats, d_st, sizeof( double ) * ACN_STATS_STRIDE * n, hipMemcpyDeviceToHost ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_lens_stats_merge_dev( acn_scene_handle* h, void* d_acc, size_t n_acc, const void* d_part, size_t n_part,
-                                         const int64_t* d_index, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
-    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a merge of lens statistics is not sharded" );
-    if( stats_buffer( d_acc, n_acc, "d_acc" ) != ACN_OK || stats_buffer( d_part, n_part, "d_part" ) != ACN_OK ) return ACN_ERR_ARG;
-    if( !d_index && n_part > n_acc ) return fail( ACN_ERR_ARG, "a merge without an index needs n_part <= n_acc" );
-    if( ( uintptr_t )d_index % 8 ) return fail( ACN_ERR_ARG, "d_index is an array of int64_t: align the buffer" );
-    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
-    acn_launch_stats_merge( ( double* )d_acc, n_acc, ( const double* )d_part, n_part, d_index, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_lens_stats_merge( acn_scene_handle* h, double* acc, size_t n_acc, const double* part, size_t n_part,
-                                     const int64_t* index, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n_acc && !acc ) || ( n_part && !part ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a merge of lens statistics is not sharded" );
-    std::string msg;
-    if( acn_stats_index_check( index, n_part, n_acc, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
-    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    DevCopies dc;
-    const size_t rec = sizeof( double ) * ACN_STATS_STRIDE;
-    void* d_acc = dc.make( acc, rec * n_acc );
-    void* d_part = dc.make( part, rec * n_part );
-    void* d_index = index ? dc.make( index, sizeof( int64_t ) * n_part ) : nullptr;
-    if( !d_acc || !d_part || ( index && !d_index ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    int st = acn_lens_stats_merge_dev( h, d_acc, n_acc, d_part, n_part, ( const int64_t* )d_index, &o );
-    if( st != ACN_OK ) return st;
-    HIP_TRY( hipMemcpy( acc, d_acc, rec * n_acc, hipMemcpyDeviceToHost ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_lens_stats_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb, void* d_out_noise,
-                                           const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    if( !h || ( n && !d_stats ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( opts->shard_world > 1 ) return fail( ACN_ERR_ARG, "a resolve of lens statistics is not sharded" );
-    if( stats_buffer( d_stats, n, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
-    if( n == 0 || ( !d_out_rgb && !d_out_noise ) ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
-    acn_launch_stats_resolve( ( const double* )d_stats, n, h->dev.prm.background_color, h->dev.prm.gamma, ( opts->flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0,
-                              ( double* )d_out_rgb, ( double* )d_out_noise, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
-                                      const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    DenoiseSetup su;
-    int st = denoise_check( h, d_stats, d_surface, width, height, prm, d_out_rgb, opts, &su );
-    if( st != ACN_OK ) return st;
-    if( ( uintptr_t )d_surface % 16 ) return fail( ACN_ERR_ARG, "the surface records of a denoise call are read 16 bytes at a time: align the buffer" );
-    if( stats_buffer( d_stats, width * height, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = ( opts && opts->stream ) ? ( hipStream_t )opts->stream : h->stream;
-    const size_t need = width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL;
-    if( h->denoise_bytes < need )
-    {
-        if( h->d_denoise ) hipFree( h->d_denoise );   /* (waits for whatever still reads it) */
-        h->d_denoise = nullptr; h->denoise_bytes = 0;
-        HIP_TRY( hipMalloc( &h->d_denoise, need ) );
-        h->denoise_bytes = need;
-    }
-    acn_launch_denoise_stats( ( const double* )d_stats, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2,
-                              su.no_demodulate, su.sigma_plane, su.sigma_lum, h->dev.prm.background_color, h->d_denoise, ( double* )d_out_rgb, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !( opts && opts->stream ) ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_denoise_stats( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
-                                  const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    DenoiseSetup su;
-    int st = denoise_check( h, stats, surface, width, height, prm, out_rgb, opts, &su );
-    if( st != ACN_OK ) return st;
-    HIP_TRY( hipSetDevice( h->device ) );
-    const size_t n = width * height;
-    DevCopies dc;
-    void* d_st = dc.make( stats, sizeof( double ) * ACN_STATS_STRIDE * n );
-    void* d_surf = dc.make( surface, sizeof( double ) * ACN_SURF_STRIDE * n );
-    void* d_rgb = dc.make( nullptr, sizeof( double ) * 3 * n );
-    if( !d_st || !d_surf || !d_rgb ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    acn_render_opts o = *opts;
-    o.stream = nullptr;
-    st = acn_denoise_stats_dev( h, d_st, d_surf, width, height, prm, d_rgb, &o );
-    if( st != ACN_OK ) return st;
-    HIP_TRY( hipMemcpy( out_rgb, d_rgb, sizeof( double ) * 3 * n, hipMemcpyDeviceToHost ) );
-    return ACN_OK;
-}
-
-/* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */
-extern "C" int acn_select_above_dev( acn_scene_handle* h, const void* d_key, size_t n, const acn_select_params* prm, const void* d_src_pos_xy,
-                                     void* d_out_index, void* d_out_pos_xy, void* d_out_count, uint64_t* out_count, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    std::string msg;
-    acn_select_params p;
-    if( acn_select_args_check( h != nullptr, d_key, n, prm, d_src_pos_xy, d_out_index, d_out_pos_xy, opts->shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
-    if( ( uintptr_t )d_out_count % 8 ) return fail( ACN_ERR_ARG, "d_out_count is a uint64_t: align it" );
-    const uint64_t width = p.raster_width ? p.raster_width : h->dev.prm.image_width;
-    if( !d_src_pos_xy && d_out_pos_xy && width == 0 ) return fail( ACN_ERR_ARG, "raster positions need a raster_width or a scene with an image_width" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
-    if( n == 0 )   /* no launch */
-    {
-        if( d_out_count ) HIP_TRY( hipMemsetAsync( d_out_count, 0, sizeof( uint64_t ), stream ) );
-        if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
-        if( out_count ) *out_count = 0;
-        return ACN_OK;
-    }
-    const size_t words = ( size_t )acn_select_tiles( n ) + 1;
-    if( h->select_tiles_cap < words )
-    {
-        if( h->d_select_tiles ) hipFree( h->d_select_tiles );   /* (waits for whatever still reads them) */
-        h->d_select_tiles = nullptr; h->select_tiles_cap = 0;
-        HIP_TRY( hipMalloc( &h->d_select_tiles, sizeof( unsigned long long ) * words ) );
-        h->select_tiles_cap = words;
-    }
-    acn_launch_select( ( const double* )d_key, n, p.threshold, h->d_select_tiles, p.capacity, ( const double* )d_src_pos_xy, width, p.raster_first,
-                       ( int64_t* )d_out_index, ( double* )d_out_pos_xy, ( unsigned long long* )d_out_count, stream );
-    HIP_TRY( hipGetLastError() );
-    if( out_count )   /* the one synchronisation of a caller's stream */
-    {
-        unsigned long long total = 0;
-        HIP_TRY( hipMemcpyAsync( &total, h->d_select_tiles + ( words - 1 ), sizeof( total ), hipMemcpyDeviceToHost, stream ) );
-        HIP_TRY( hipStreamSynchronize( stream ) );
-        *out_count = total;
-    }
-    else if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_select_above( acn_scene_handle* h, const double* key, size_t n, const acn_select_params* prm, const double* src_pos_xy,
-                                 int64_t* out_index, double* out_pos_xy, uint64_t* out_count )
-{
-    std::string msg;
-    acn_select_params p;
-    if( acn_select_args_check( h != nullptr, key, n, prm, src_pos_xy, out_index, out_pos_xy, 0, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
-    if( n == 0 ) { if( out_count ) *out_count = 0; return ACN_OK; }
-    HIP_TRY( hipSetDevice( h->device ) );
-    const size_t cap = ( size_t )( p.capacity < n ? p.capacity : n );   /* (no more than n are ever selected) */
-    DevCopies dc;
-    void* d_key = dc.make( key, sizeof( double ) * n );
-    void* d_src = src_pos_xy ? dc.make( src_pos_xy, sizeof( double ) * 2 * n ) : nullptr;
-    void* d_index = out_index && cap ? dc.make( nullptr, sizeof( int64_t ) * cap ) : nullptr;
-    void* d_pos = out_pos_xy && cap ? dc.make( nullptr, sizeof( double ) * 2 * cap ) : nullptr;
-    if( !d_key || ( src_pos_xy && !d_src ) || ( out_index && cap && !d_index ) || ( out_pos_xy && cap && !d_pos ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    acn_select_params q = p;
-    q.struct_size = ( uint32_t )sizeof( q );
-    q.capacity = ( d_index || d_pos ) ? cap : 0;
-    uint64_t total = 0;
-    int st = acn_select_above_dev( h, d_key, n, &q, d_src, d_index, d_pos, nullptr, &total, nullptr );
-    if( st != ACN_OK ) return st;
-    const size_t wrote = ( size_t )( total < q.capacity ? total : q.capacity );
-    if( d_index && wrote ) HIP_TRY( hipMemcpy( out_index, d_index, sizeof( int64_t ) * wrote, hipMemcpyDeviceToHost ) );
-    if( d_pos && wrote ) HIP_TRY( hipMemcpy( out_pos_xy, d_pos, sizeof( double ) * 2 * wrote, hipMemcpyDeviceToHost ) );
-    if( out_count ) *out_count = total;
-    return ACN_OK;
-}
-
-extern "C" int acn_key_histogram_dev( acn_scene_handle* h, const void* d_key, size_t n, void* d_out_hist, const acn_render_opts* opts )
-{
-    ACN_OPTS_VIEW
-    std::string msg;
-    if( acn_key_hist_args_check( h != nullptr, d_key, n, d_out_hist, opts->shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
-    HIP_TRY( hipSetDevice( h->device ) );
-    hipStream_t stream = opts->stream ? ( hipStream_t )opts->stream : h->stream;
-    HIP_TRY( hipMemsetAsync( d_out_hist, 0, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS, stream ) );
-    if( n ) acn_launch_key_hist( ( const double* )d_key, n, ( unsigned long long* )d_out_hist, stream );
-    HIP_TRY( hipGetLastError() );
-    if( !opts->stream ) HIP_TRY( hipStreamSynchronize( stream ) );
-    return ACN_OK;
-}
-
-extern "C" int acn_key_histogram( acn_scene_handle* h, const double* key, size_t n, uint64_t* out_hist )
-{
-    std::string msg;
-    if( acn_key_hist_args_check( h != nullptr, key, n, out_hist, 0, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
-    HIP_TRY( hipSetDevice( h->device ) );
-    DevCopies dc;
-    void* d_key = dc.make( key, sizeof( double ) * n );
-    void* d_hist = dc.make( nullptr, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS );
-    if( !d_key || !d_hist ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    int st = acn_key_histogram_dev( h, d_key, n, d_hist, nullptr );
-    if( st != ACN_OK ) return st;
-    HIP_TRY( hipMemcpy( out_hist, d_hist, sizeof( uint64_t ) * ACN_KEY_HIST_WORDS, hipMemcpyDeviceToHost ) );
-    return ACN_OK;
-}
-
-extern "C" double acn_key_hist_edge( uint32_t bin ) { return acn_select_hist_edge( bin ); }
-extern "C" double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget ) { return acn_select_hist_threshold( hist, budget ); }
 
 extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )
 {
@@ -2386,55 +1331,5 @@ extern "C" int acn_last_counters( acn_scene_handle* h, uint64_t* out, int n )
         for( int k = 0; k < ACN_CNT_SLOTS; k++ ) sum[ k ] += c[ k ];
     }
     for( int k = 0; k < n; k++ ) out[ k ] = k < ACN_CNT_SLOTS ? sum[ k ] : 0;
-    return ACN_OK;
-}
-
-extern "C" int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_t samples, uint32_t rseed,
-                                      double radius_factor, double* out )
-{
-    if( !h || !out || node < 0 || ( uint32_t )node >= h->dev.n_nodes ) return fail( ACN_ERR_ARG, "bad argument" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    V3* d_scratch = nullptr; double* d_out = nullptr;
-    HIP_TRY( hipMalloc( &d_scratch, sizeof( V3 ) * ( samples ? samples : 1 ) ) );
-    HIP_TRY( hipMalloc( &d_out, sizeof( double ) * 4 ) );
-    DevScene est_scene = h->dev;
-    est_scene.lds_stack = ACN_NO_LDS_STACK;   /* one lane, no dynamic LDS: the machine keeps its stacks in scratch */
-    hipLaunchKernelGGL( k_estimate_envelope, dim3( 1 ), dim3( 1 ), 0, h->stream, est_scene, node, samples, rseed, radius_factor, d_scratch, d_out );
-    hipError_t e = hipGetLastError();
-    if( e == hipSuccess ) e = hipStreamSynchronize( h->stream );
-    if( e == hipSuccess ) e = hipMemcpy( out, d_out, sizeof( double ) * 4, hipMemcpyDeviceToHost );
-    hipFree( d_scratch ); hipFree( d_out );
-    if( e != hipSuccess ) return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) );
-    return ACN_OK;
-}
-
-int acn_query_env( acn_scene_handle* h, QueryEnv* q )
-{
-    if( !h || !q ) return fail( ACN_ERR_ARG, "null argument" );
-    HIP_TRY( hipSetDevice( h->device ) );
-    q->s = scene_args( h ); q->lds_node_bytes = h->scene.lds_bytes; q->lds_stack_bytes = h->scene.lds_stack_bytes; q->stream = h->stream;
-    return ACN_OK;
-}
-int acn_query_fail( int code, const char* msg ) { return fail( code, msg ); }
-
-extern "C" int acn_detmath_eval( int device, int op, const double* x, const double* y, double* out, size_t n )
-{
-    if( !x || !out ) return fail( ACN_ERR_ARG, "null argument" );
-    if( acn_device_count() <= 0 ) return fail( ACN_ERR_DEVICE, "no HIP device" );
-    HIP_TRY( hipSetDevice( device ) );
-    double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    HIP_TRY( hipMalloc( &dx, sizeof( double ) * n ) );
-    HIP_TRY( hipMalloc( &dout, sizeof( double ) * n ) );
-    HIP_TRY( hipMemcpy( dx, x, sizeof( double ) * n, hipMemcpyHostToDevice ) );
-    if( y )
-    {
-        HIP_TRY( hipMalloc( &dy, sizeof( double ) * n ) );
-        HIP_TRY( hipMemcpy( dy, y, sizeof( double ) * n, hipMemcpyHostToDevice ) );
-    }
-    hipLaunchKernelGGL( k_detmath, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, 0, op, dx, dy, dout, n );
-    HIP_TRY( hipGetLastError() );
-    HIP_TRY( hipDeviceSynchronize() );
-    HIP_TRY( hipMemcpy( out, dout, sizeof( double ) * n, hipMemcpyDeviceToHost ) );
-    hipFree( dx ); hipFree( dout ); if( dy ) hipFree( dy );
     return ACN_OK;
 }

@@ -6,7 +6,7 @@
  * (DevScenePT).  Ray i runs on lane i % 64 of wave i / 64, so the caller decides which rays share a wave.  The production
  * kernels are untouched: this unit only instantiates the same templates once more. */
 #include <hip/hip_runtime.h>
-#include "acn_launch.h"
+#include "acn_handle.h"
 
 /* results per ray: ACN_Q_STRIDE doubles; integers are stored as doubles, skip masks as their 64 raw bits */
 #define ACN_Q_STRIDE ACN_QUERY_STRIDE
@@ -154,44 +154,36 @@ extern "C" int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const 
 {
     const uint32_t flags = ( uint32_t )op & ~0xFFu;
     op &= 0xFF;
-    QueryEnv q;
-    int st = acn_query_env( h, &q );
+    Call c( nullptr );
+    if( !h ) return fail( ACN_ERR_ARG, "null argument" );
+    int st = call_begin( h, &c );
     if( st != ACN_OK ) return st;
-    if( !out || node < 0 || ( uint32_t )node >= q.s.dev.n_nodes || op < 0 || op >= ACN_Q_N ) return acn_query_fail( ACN_ERR_ARG, "acn_query_rays: bad argument" );
-    if( op != ACN_Q_ELEMENTS && n && !rays ) return acn_query_fail( ACN_ERR_ARG, "acn_query_rays: no rays" );
-    const bool lds = !( flags & ACN_QUERY_GLOBAL_NODES ) && q.lds_node_bytes != 0;
+    const SceneArgs s = scene_args( h );
+    if( !out || node < 0 || ( uint32_t )node >= s.dev.n_nodes || op < 0 || op >= ACN_Q_N ) return fail( ACN_ERR_ARG, "acn_query_rays: bad argument" );
+    if( op != ACN_Q_ELEMENTS && n && !rays ) return fail( ACN_ERR_ARG, "acn_query_rays: no rays" );
+    const bool lds = !( flags & ACN_QUERY_GLOBAL_NODES ) && h->scene.lds_bytes != 0;
     const bool prune = !( flags & ACN_QUERY_PLAIN_SCENE );
-    double *d_rays = nullptr, *d_lim = nullptr, *d_out = nullptr;
-    hipError_t e = hipSuccess;
     const size_t nr = op == ACN_Q_ELEMENTS ? 0 : n;
     const size_t out_bytes = sizeof( double ) * ACN_Q_STRIDE * ( n ? n : 1 );
-    e = hipMalloc( &d_out, out_bytes );
-    if( e == hipSuccess && nr ) e = hipMalloc( &d_rays, sizeof( double ) * 6 * nr );
-    if( e == hipSuccess && nr && limits ) e = hipMalloc( &d_lim, sizeof( double ) * 2 * nr );
-    if( e == hipSuccess && nr ) e = hipMemcpy( d_rays, rays, sizeof( double ) * 6 * nr, hipMemcpyHostToDevice );
-    if( e == hipSuccess && d_lim ) e = hipMemcpy( d_lim, limits, sizeof( double ) * 2 * nr, hipMemcpyHostToDevice );
-    if( e == hipSuccess ) e = hipMemsetAsync( d_out, 0, out_bytes, q.stream );
-    if( e == hipSuccess )
+    DevCopies dc;
+    double* d_out = ( double* )dc.make( nullptr, out_bytes );
+    const double* d_rays = nr ? ( const double* )dc.make( rays, sizeof( double ) * 6 * nr ) : nullptr;
+    const double* d_lim = nr && limits ? ( const double* )dc.make( limits, sizeof( double ) * 2 * nr ) : nullptr;
+    if( !d_out || ( nr && !d_rays ) || ( nr && limits && !d_lim ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    HIP_TRY( hipMemsetAsync( d_out, 0, out_bytes, c.stream ) );
+    if( op == ACN_Q_ELEMENTS ) hipLaunchKernelGGL( k_query_elements, dim3( 1 ), dim3( 1 ), 0, c.stream, ACN_SCENE_ARGS_OF( s ), node, d_out, n );
+    else if( nr )
     {
-        const SceneArgs& s = q.s;
-        if( op == ACN_Q_ELEMENTS ) hipLaunchKernelGGL( k_query_elements, dim3( 1 ), dim3( 1 ), 0, q.stream, ACN_SCENE_ARGS_OF( s ), node, d_out, n );
-        else if( nr )
-        {
-            const dim3 grid( ( unsigned )( ( nr + 255 ) / 256 ) );
-            const size_t lds_total = ( lds ? q.lds_node_bytes : 0 ) + q.lds_stack_bytes;
-            if( lds && prune )  hipLaunchKernelGGL( ( k_query< true, true > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-            else if( lds )      hipLaunchKernelGGL( ( k_query< true, false > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-            else if( prune )    hipLaunchKernelGGL( ( k_query< false, true > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-            else                hipLaunchKernelGGL( ( k_query< false, false > ), grid, dim3( 256 ), lds_total, q.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-        }
-        e = hipGetLastError();
+        const dim3 grid( ( unsigned )( ( nr + 255 ) / 256 ) );
+        const size_t lds_total = ( lds ? h->scene.lds_bytes : 0 ) + h->scene.lds_stack_bytes;
+        if( lds && prune )  hipLaunchKernelGGL( ( k_query< true, true > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+        else if( lds )      hipLaunchKernelGGL( ( k_query< true, false > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+        else if( prune )    hipLaunchKernelGGL( ( k_query< false, true > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+        else                hipLaunchKernelGGL( ( k_query< false, false > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
     }
-    if( e == hipSuccess ) e = hipStreamSynchronize( q.stream );
-    if( e == hipSuccess && n ) e = hipMemcpy( out, d_out, out_bytes, hipMemcpyDeviceToHost );   /* out holds n rows: none for n == 0 */
-    if( e == hipSuccess && op == ACN_Q_ELEMENTS && n ) ( ( double* )out )[ 3 ] = ( double )q.lds_node_bytes;   /* 0: nodes are never staged */
-    if( d_rays ) hipFree( d_rays );
-    if( d_lim ) hipFree( d_lim );
-    if( d_out ) hipFree( d_out );
-    if( e != hipSuccess ) return acn_query_fail( ACN_ERR_DEVICE, hipGetErrorString( e ) );
+    HIP_TRY( hipGetLastError() );
+    if( ( st = call_end( c ) ) != ACN_OK ) return st;
+    if( n && ( st = DevCopies::fetch( out, d_out, out_bytes ) ) != ACN_OK ) return st;   /* out holds n rows: none for n == 0 */
+    if( op == ACN_Q_ELEMENTS && n ) ( ( double* )out )[ 3 ] = ( double )h->scene.lds_bytes;   /* 0: nodes are never staged */
     return ACN_OK;
 }
