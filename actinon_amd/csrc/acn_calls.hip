@@ -147,9 +147,9 @@ static int surface_dev( acn_scene_handle* h, const double* d_rays, const double*
         HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
     }
     if( d_rays && ( st = check_rays( h, d_rays, n, c.stream ) ) != ACN_OK ) return st;
-    SceneArgs s = scene_args( h );
+    SceneArgs s = scene_args( h->dev, h->scene );
     s.dev.flags = h->d_surface_flags;   /* the pipeline's word stays the pipeline's */
-    acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h ), c.stream, s, d_rays, d_pos_xy, n, d_out );
+    acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, d_rays, d_pos_xy, n, d_out );
     HIP_TRY( hipGetLastError() );
     if( !c.own ) return ACN_OK;   /* (a caller's stream is not synchronised for the flags) */
     uint32_t flags = 0;

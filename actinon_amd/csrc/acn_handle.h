@@ -1,5 +1,5 @@
-/* acn_handle.h -- what the host units of libactinon_hip.so share: the scene handle, the error plumbing, the frame of one C ABI
- * call and the few functions that cross between actinon_hip.hip (life cycle, workspace, pipeline, lanes and the pipeline's own
+/* acn_handle.h -- what the host units of libactinon_hip.so share: the scene handle, the pipeline runner (PipeRun), the error
+ * plumbing, the frame of one C ABI call and the few functions that cross between actinon_hip.hip (life cycle, workspace, pipeline, lanes and the pipeline's own
  * entry points), acn_calls.hip (every other entry point) and k_query.hip (the test seam). */
 #ifndef ACN_HANDLE_H
 #define ACN_HANDLE_H
@@ -17,6 +17,7 @@
 #include "acn_launch.h"
 #include "acn_tables.h"
 #include "acn_chunkplan.h"
+#include "acn_queueplan.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* error plumbing */
@@ -154,7 +155,7 @@ struct Tunables
     }
 };
 
-/* the queue workspace of one pipeline run */
+/* the queue workspace of one pipeline run (WQ_*: acn_queueplan.h) */
 struct Workspace
 {
     DTask*      tasks = nullptr;
@@ -168,18 +169,96 @@ struct Workspace
     size_t      bytes = 0;          /* device memory of the queues and stacks */
     uint64_t    allocs = 0;         /* times this workspace was (re)allocated */
     bool        trimmed = false;    /* it was already re-allocated smaller once */
-    uint32_t    sized_calls = 0;    /* calls of ensure_workspace with learned rates (the trim window, see there) */
+    uint32_t    sized_calls = 0;    /* calls of ensure_workspace with learned rates (the trim window: acn_keep_caps) */
 };
-/* the queues of a pipeline run.  Each is sized from its OWN demand per sample position (learned, below): on the wine glass a
- * position leaves 15 deferred shadow rays but 2 shading points, and one common capacity -- the former layout -- made every
- * queue as large as the fullest one needs (64 GiB for a 1080p frame of which 7 % were used). */
-enum { WQ_TASKS = 0, WQ_CHILDREN, WQ_HARD_SHADOW, WQ_HARD_PATH, WQ_RAYS, WQ_N };
+
+/* the statistics of one call (acn_last_stage_ms) */
+struct RunStats
+{
+    uint64_t launches[ 4 ] = { 0, 0, 0, 0 };   /* walk, shade, finalize, hard-ray kernels */
+    uint64_t hard_rays = 0, walk_steps = 0, walk_rays = 0, shade_hit_recs = 0, host_syncs = 0, private_rays = 0, probe_rays = 0;
+    uint32_t flags_seen = 0;                   /* ACN_FLAG_* bits of the last call */
+    uint64_t chunks = 0, retries = 0, levels = 0;
+    uint64_t peak_tasks = 0, peak_children = 0;
+    void reset() { *this = RunStats(); }
+    /* a lane's into its call's: sums, but the flags' union and the deepest level (the peaks of concurrent lanes add up) */
+    void add( const RunStats& l )
+    {
+        for( int i = 0; i < 4; i++ ) launches[ i ] += l.launches[ i ];
+        hard_rays += l.hard_rays; walk_steps += l.walk_steps; walk_rays += l.walk_rays; shade_hit_recs += l.shade_hit_recs;
+        host_syncs += l.host_syncs; flags_seen |= l.flags_seen; private_rays += l.private_rays; probe_rays += l.probe_rays;
+        chunks += l.chunks; retries += l.retries;
+        if( l.levels > levels ) levels = l.levels;
+        peak_tasks += l.peak_tasks; peak_children += l.peak_children;
+    }
+};
+
+/* what a pipeline run has learned about the scene; it stays with the run for its next call */
+struct Learned
+{
+    double rate[ 5 ] = { 0, 0, 0, 0, 0 };      /* records per sample position a chunk leaves in each queue (WQ_*); 0: not known yet */
+    uint32_t rate_cnt = 0;                     /* positions of the chunk the rates were taken from */
+    acn_chunk_ctl ctl = { 0.7, 0, 0 };         /* acn_chunkplan.h.  fill_target: fraction of its capacity the fullest queue of a chunk is
+                                                  planned to reach: lowered by every overflow (a redone chunk is lost work), raised slowly
+                                                  by chunks that fit */
+    uint32_t walk_passes_seen[ ACN_MAX_PATH_LEVELS + 1 ] = { 0, 0, 0, 0, 0, 0 };   /* passes of a level that had input in the last chunk (0: not known yet) */
+    bool known() const { return acn_rates_known( rate ) != 0; }
+    void forget_passes() { for( uint32_t& seen : walk_passes_seen ) seen = 0; }   /* the full number of passes again */
+    /* what one arrangement (the handle's own run, its lanes) learned about the scene (records per position) holds for the
+     * other: only if `to` knows nothing and `from` does; the walk passes start over */
+    static void inherit( Learned* to, const Learned& from )
+    {
+        if( to->known() || !from.known() ) return;
+        for( int q = 0; q < WQ_N; q++ ) to->rate[ q ] = from.rate[ q ];
+        to->rate_cnt = from.rate_cnt; to->ctl.fill_target = from.ctl.fill_target;
+        to->forget_passes();
+    }
+};
+
+/* the per-call switches of a pipeline run */
+struct Switches
+{
+    bool count_work = false;                   /* ACN_OPT_COUNT_WORK */
+    bool stage_timing = false;                 /* ACN_OPT_STAGE_TIMING */
+    uint32_t shard_rank = 0, shard_world = 1;  /* ACN_SHARD_SAMPLES */
+    bool seeded = false;                       /* the call renders the caller's rays (Primary): its ray queue has a known demand (acn_queue_demand) */
+};
+
+struct acn_scene_handle;
+
+/* One pipeline runner: what launch_render needs to work a call off on one stream.  A handle has its own, for a call that runs
+ * alone, and one per concurrent lane (render_lanes); all of them read the scene, the tunables and the budget of the handle. */
+struct PipeRun
+{
+    const acn_scene_handle* h = nullptr;       /* the handle it serves (a lane: from bind_lane on) */
+    DevScene dev{};                            /* the handle's, with flags -> the run's own counter block */
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
+    unsigned walk_grid = 1024;                 /* ... of k_walk */
+    Workspace ws;
+    uint32_t* d_counts = nullptr;              /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
+    uint32_t* h_counts = nullptr;              /* pinned copy */
+    unsigned long long* d_accum = nullptr;  size_t accum_bytes = 0;
+    unsigned long long* d_counters = nullptr;
+    unsigned long long* d_counters_keep = nullptr;   /* the work counters as they were before the current chunk (restored when it is redone) */
+    std::vector< StageEvents > events;  size_t events_used = 0;
+    int cur_stage = 0;
+    size_t budget_div = 1;                     /* workspace budget of a lane = the handle's budget / lanes */
+    Switches sw;                               /* of the current call */
+    Learned learned;
+    RunStats stats;                            /* of the last call */
+    /* of a lane */
+    LaneWorker* worker = nullptr;
+    double* d_lane_in = nullptr; size_t lane_in_bytes = 0;     /* its gathered positions or rays (grow_device, as every *_bytes below) */
+    double* d_lane_out = nullptr; size_t lane_out_bytes = 0;   /* ... and its results */
+};
 
 struct acn_scene_handle
 {
     int device = 0;
-    DevScene dev{};
-    /* the resident scene and what the tables say about it: a lane borrows all of it from its parent (bind_lane) */
+    DevScene dev{};                            /* the template of every run's copy (flags: the own run's) */
+    /* the resident scene and what the tables say about it */
     struct Resident
     {
         GNode*   d_nodes = nullptr;
@@ -198,49 +277,20 @@ struct acn_scene_handle
     } scene;
     SCEntry* d_sc_table = nullptr;
     double* d_sc_spheres = nullptr;            /* ( pos, radius ) of the sphere leaves of d_sc_table */
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    bool timed = false;
-    int cur_stage = 0;
-    bool stage_timing = false;                 /* ACN_OPT_STAGE_TIMING of the current call */
     Tunables tun;
     unsigned cus = 256;                        /* compute units of the device */
-    unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
-    unsigned walk_grid = 1024;                 /* ... of k_walk */
-    /* workspace of the wavefront pipeline */
-    Workspace ws;
-    uint32_t* d_counts = nullptr;              /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
-    uint32_t* h_counts = nullptr;              /* pinned copy */
-    unsigned long long* d_accum = nullptr;  size_t accum_bytes = 0;
-    unsigned long long* d_counters = nullptr;
-    std::vector< StageEvents > events;  size_t events_used = 0;
-    bool count_work = false;                   /* ACN_OPT_COUNT_WORK of the current call */
-    uint32_t shard_rank = 0, shard_world = 1;  /* ACN_SHARD_SAMPLES of the current call */
-    uint64_t launches[ 4 ] = { 0, 0, 0, 0 };   /* walk, shade, finalize, hard-ray kernels */
-    uint64_t hard_rays = 0, walk_steps = 0, walk_rays = 0, shade_hit_recs = 0, host_syncs = 0, private_rays = 0, probe_rays = 0;
-    uint32_t flags_seen = 0;                   /* ACN_FLAG_* bits of the last call */
-    uint32_t rate_cnt = 0;                     /* positions of the chunk the rates were taken from */
-    acn_chunk_ctl ctl = { 0.7, 0, 0 };         /* acn_chunkplan.h.  fill_target: fraction of its capacity the fullest queue of a chunk is
-                                                  planned to reach: lowered by every overflow (a redone chunk is lost work), raised slowly
-                                                  by chunks that fit */
-    double rate[ 5 ] = { 0, 0, 0, 0, 0 };      /* learned: records per sample position a chunk leaves in each queue (WQ_*); 0: not known yet */
     size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
-    uint64_t chunks = 0, retries = 0, levels = 0;
-    uint64_t peak_tasks = 0, peak_children = 0;
-    uint32_t walk_passes_seen[ ACN_MAX_PATH_LEVELS + 1 ] = { 0, 0, 0, 0, 0, 0 };   /* learned: passes of a level that had input in the last chunk (0: not known yet) */
-    unsigned long long* d_counters_keep = nullptr;   /* the work counters as they were before the current chunk (restored when it is redone) */
-    /* concurrent lanes (render_lanes): clones of this handle that share the resident scene and own a stream and a
-     * workspace each */
-    bool is_lane = false;
-    size_t budget_div = 1;                     /* workspace budget of a lane = the handle's budget / lanes */
-    std::vector< acn_scene_handle* > lanes;
+    PipeRun run;                               /* a call that runs alone; its stream is the handle's own, its statistics the last call's */
+    /* concurrent lanes (render_lanes): runners that own a stream, a workspace and a host thread each */
+    std::vector< PipeRun* > lanes;
     /* lanes made during acn_scene_upload on a helper thread (early_lanes_begin), taken over by the first call that runs on lanes */
     std::thread early_maker;
-    std::vector< acn_scene_handle* > early_made;
-    int early_status = 0; std::string early_message;
-    LaneWorker* worker = nullptr;              /* of a lane */
-    double* d_lane_in = nullptr; size_t lane_in_bytes = 0;     /* a lane's gathered positions or rays (grow_device, as every *_bytes below) */
-    double* d_lane_out = nullptr; size_t lane_out_bytes = 0;   /* ... and its results */
+    std::vector< PipeRun* > early_made;
+    bool timed = false;
+    bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
+    int  lanes_used = 0;                       /* ... the first lanes_used of them */
+    bool one_lane = false;                     /* the last call would have used lanes but did not fit the workspace bound that way */
+    /* scratch of the entry points that are not the pipeline's */
     double* d_shard_pos = nullptr; size_t shard_pos_bytes = 0;                              /* acn_render_main_pass_shard_dev: the rank's positions */
     unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
     uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
@@ -248,20 +298,15 @@ struct acn_scene_handle
     double* d_lens_rays = nullptr; size_t lens_rays_bytes = 0;                              /* acn_render_lens*: the rays [ 6 ] of a slice */
     double* d_lens_rad = nullptr; size_t lens_rad_bytes = 0;                                /* ... and their radiance [ 3 ] */
     unsigned long long* d_select_tiles = nullptr; size_t select_tiles_bytes = 0;            /* acn_select_above*: the counts per tile and their total */
-    bool seeded = false;                       /* the current call renders the caller's rays (Primary): its ray queue has a known demand (demand) */
-    std::string lane_error;
-    bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
-    int  lanes_used = 0;                       /* ... the first lanes_used of them */
-    bool one_lane = false;                     /* the last call would have used lanes but did not fit the workspace bound that way */
 };
 
-static SceneArgs scene_args( const acn_scene_handle* h )
+static SceneArgs scene_args( const DevScene& dev, const acn_scene_handle::Resident& r )
 {
     SceneArgs s;
-    s.dev = h->dev; s.nodes = h->scene.d_nodes; s.mats = h->scene.d_mats; s.elems = h->scene.d_elems; s.textures = h->scene.d_textures; s.elem_pos_base = h->scene.elem_pos_base;
+    s.dev = dev; s.nodes = r.d_nodes; s.mats = r.d_mats; s.elems = r.d_elems; s.textures = r.d_textures; s.elem_pos_base = r.elem_pos_base;
     return s;
 }
-static size_t machine_lds_bytes( const acn_scene_handle* h ) { return h->scene.lds_bytes + h->scene.lds_stack_bytes; }
+static size_t machine_lds_bytes( const acn_scene_handle::Resident& r ) { return r.lds_bytes + r.lds_stack_bytes; }
 
 /* What the primary rays of a call come from, handed down the whole chain (render_dispatch -> launch_render / render_lanes ->
  * learn_rates -> render_chunk -> acn_launch_walk): sample positions [ n ][ 2 ], the pixel centres of the main pass from pixel
@@ -311,7 +356,7 @@ static inline int call_begin( acn_scene_handle* h, Call* c )
 {
     HIP_TRY( hipSetDevice( h->device ) );
     c->own = c->opts.stream == nullptr;
-    c->stream = c->own ? h->stream : ( hipStream_t )c->opts.stream;
+    c->stream = c->own ? h->run.stream : ( hipStream_t )c->opts.stream;
     return ACN_OK;
 }
 static inline int call_end( const Call& c )

@@ -158,7 +158,7 @@ extern "C" int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const 
     if( !h ) return fail( ACN_ERR_ARG, "null argument" );
     int st = call_begin( h, &c );
     if( st != ACN_OK ) return st;
-    const SceneArgs s = scene_args( h );
+    const SceneArgs s = scene_args( h->dev, h->scene );
     if( !out || node < 0 || ( uint32_t )node >= s.dev.n_nodes || op < 0 || op >= ACN_Q_N ) return fail( ACN_ERR_ARG, "acn_query_rays: bad argument" );
     if( op != ACN_Q_ELEMENTS && n && !rays ) return fail( ACN_ERR_ARG, "acn_query_rays: no rays" );
     const bool lds = !( flags & ACN_QUERY_GLOBAL_NODES ) && h->scene.lds_bytes != 0;

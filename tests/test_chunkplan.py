@@ -20,12 +20,14 @@ class Ctl(C.Structure):
 @pytest.fixture(scope="module")
 def plan():
     src = os.path.join(ROOT, "tests", "csrc", "chunkplan_cpu.c")
-    hdr = os.path.join(ROOT, "actinon_amd", "csrc", "acn_chunkplan.h")
+    hdrs = [os.path.join(ROOT, "actinon_amd", "csrc", h) for h in ("acn_chunkplan.h", "acn_queueplan.h")]
     out = os.path.join(ROOT, "build", "libchunkplan_cpu.so")
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-I", os.path.join(ROOT, "actinon_amd", "csrc"), src, "-o", out])
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in [src] + hdrs):
+        subprocess.check_call(["gcc", "-O2", "-fPIC", "-shared", "-Wall", "-ffp-contract=off", "-I", os.path.join(ROOT, "actinon_amd", "csrc"), src, "-o", out])
     lib = C.CDLL(out)
+    lib.plan_chunk_for_caps.argtypes = [C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_uint32)]
+    lib.plan_chunk_for_caps.restype = C.c_size_t
     lib.plan_init.argtypes = [C.POINTER(Ctl), C.c_double]
     lib.plan_next.argtypes = [C.POINTER(Ctl), C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     lib.plan_next.restype = C.c_uint32
@@ -45,7 +47,7 @@ def run_call(lib, n_slots, demand, cap, fill_target, rate0, fixed=0, max_iters=1
     known = any(r > 0 for r in rate0)
 
     def chunk_for_caps():
-        return max(64, int(min(ctl.fill_target * caps[q] / max(rate[q], 1e-3) for q in range(5))))
+        return lib.plan_chunk_for_caps(rate, ctl.fill_target, caps)           # launch_render's own (acn_queueplan.h)
 
     chunk = chunk_for_caps() if known else 1024
     base, log, chunks, retries = 0, [], 0, 0

@@ -390,3 +390,42 @@ def test_cold_handle_learns_from_a_sample_and_renders_the_same_bits(oracle, monk
     sample = np.arange(0, len(pos), stride)[:512]
     cpu = oracle.render_positions(flat, pos[sample], linear=True)
     assert np.abs(first[sample] - cpu).max() <= TOL
+
+
+def test_one_handle_moves_between_its_lanes_and_its_own_run(monkeypatch):
+    """What a handle learned holds for its lanes and for its own run, in both directions (Learned::inherit), the side not in use
+    gives its queues back, and the statistics of a call on lanes are the lanes' together (RunStats::add).  One handle, ACN_LANES=3,
+    wine_glass 320 x 180 p64 d50 -- the smallest shape at which three lanes run (tests/test_queueplan_cpu.py): all positions on lanes
+    (cold), the first 4096 on the handle's own run, all positions on lanes again (warm), all positions as rays.  Every result has the
+    bits of a fresh one-lane handle; no warm call redoes a chunk; one host synchronisation per chunk and lane."""
+    sc = A.Scene.build("wine_glass", image_width=320, image_height=180, path_samples=64, direct_samples=50)
+    flat = sc.flatten()
+    pos = S.positions(flat)
+    monkeypatch.setenv("ACN_LANES", "1")
+    one = A.Handle(flat)
+    monkeypatch.setenv("ACN_LANES", "3")
+    h = A.Handle(flat)                                            # (tunables are read at the upload)
+    rays = one.camera_rays(pos)
+    want = {"cold": one.render_positions(pos, linear=True)}
+    st_one = one.last_stages()
+    got, st = {}, {}
+    for label, call in (("cold", lambda: h.render_positions(pos, linear=True)), ("small", lambda: h.render_positions(pos[:4096], linear=True)),
+                        ("warm", lambda: h.render_positions(pos, linear=True)), ("rays", lambda: h.render_rays(rays, linear=True))):
+        got[label] = call()
+        st[label] = h.last_stages()
+    h.close()
+    one.close()
+    monkeypatch.setenv("ACN_LANES", "1")
+    for label, call in (("small", lambda f: f.render_positions(pos[:4096], linear=True)), ("warm", lambda f: f.render_positions(pos, linear=True)),
+                        ("rays", lambda f: f.render_rays(rays, linear=True))):
+        fresh = A.Handle(flat)
+        want[label] = call(fresh)
+        fresh.close()
+    for label in ("cold", "small", "warm", "rays"):
+        assert np.array_equal(got[label], want[label]), label
+        assert st[label]["host_syncs"] == st[label]["chunks"], (label, st[label])
+        assert st[label]["finalize_launches"] == (1 if label == "small" else 3), (label, st[label])
+    for label in ("small", "warm", "rays"):
+        assert st[label]["retries"] == 0, (label, st[label])
+    for label in ("cold", "warm"):
+        assert st[label]["walk_rays"] == st_one["walk_rays"] and st[label]["hard_rays"] == st_one["hard_rays"], (label, st[label], st_one)
