@@ -141,23 +141,23 @@ static int surface_dev( acn_scene_handle* h, const double* d_rays, const double*
     if( n == 0 ) return ACN_OK;
     int st = call_begin( h, &c );
     if( st != ACN_OK ) return st;
-    if( !h->d_surface_flags )
+    if( !h->d_surface_flags.get() )
     {
-        HIP_TRY( hipMalloc( &h->d_surface_flags, sizeof( uint32_t ) ) );
-        HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
+        if( h->d_surface_flags.grow( sizeof( uint32_t ) ) ) return ACN_ERR_DEVICE;
+        HIP_TRY( hipMemset( h->d_surface_flags.get(), 0, sizeof( uint32_t ) ) );
     }
     if( d_rays && ( st = check_rays( h, d_rays, n, c.stream ) ) != ACN_OK ) return st;
     SceneArgs s = scene_args( h->dev, h->scene );
-    s.dev.flags = h->d_surface_flags;   /* the pipeline's word stays the pipeline's */
+    s.dev.flags = h->d_surface_flags.get();   /* the pipeline's word stays the pipeline's */
     acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, d_rays, d_pos_xy, n, d_out );
     HIP_TRY( hipGetLastError() );
     if( !c.own ) return ACN_OK;   /* (a caller's stream is not synchronised for the flags) */
     uint32_t flags = 0;
-    HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags, sizeof( flags ), hipMemcpyDeviceToHost, c.stream ) );
+    HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags.get(), sizeof( flags ), hipMemcpyDeviceToHost, c.stream ) );
     if( ( st = call_end( c ) ) != ACN_OK ) return st;
     if( flags )
     {
-        HIP_TRY( hipMemset( h->d_surface_flags, 0, sizeof( uint32_t ) ) );
+        HIP_TRY( hipMemset( h->d_surface_flags.get(), 0, sizeof( uint32_t ) ) );
         return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow in a surface call" );
     }
     return ACN_OK;
@@ -265,13 +265,13 @@ static int denoise_dev( acn_scene_handle* h, const void* d_in, const void* d_sur
     if( ( uintptr_t )d_surface % 16 ) return fail( ACN_ERR_ARG, "the surface records of a denoise call are read 16 bytes at a time: align the buffer" );
     if( from_stats && stats_buffer( d_in, width * height, "d_stats" ) != ACN_OK ) return ACN_ERR_ARG;
     if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
-    if( ( st = grow_device( &h->d_denoise, &h->denoise_bytes, width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL ) ) != ACN_OK ) return st;
+    if( h->d_denoise.grow( width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL ) ) return ACN_ERR_DEVICE;
     if( from_stats )
         acn_launch_denoise_stats( ( const double* )d_in, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2, su.no_demodulate,
-                                  su.sigma_plane, su.sigma_lum, h->dev.prm.background_color, h->d_denoise, ( double* )d_out_rgb, c.stream );
+                                  su.sigma_plane, su.sigma_lum, h->dev.prm.background_color, h->d_denoise.get(), ( double* )d_out_rgb, c.stream );
     else
         acn_launch_denoise( ( const double* )d_in, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2, su.no_demodulate,
-                            su.sigma_plane, su.sigma_lum, h->d_denoise, ( double* )d_out_rgb, c.stream );
+                            su.sigma_plane, su.sigma_lum, h->d_denoise.get(), ( double* )d_out_rgb, c.stream );
     HIP_TRY( hipGetLastError() );
     return call_end( c );
 }
@@ -406,23 +406,22 @@ static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t firs
     size_t slice = h->tun.lens_slice_rays / K;
     if( slice < 1 ) slice = 1;
     if( slice > n ) slice = n;
-    if( ( st = grow_device( ( void** )&h->d_lens_rays, &h->lens_rays_bytes, sizeof( double ) * 6 * slice * K ) ) != ACN_OK ) return st;
-    if( ( st = grow_device( ( void** )&h->d_lens_rad, &h->lens_rad_bytes, sizeof( double ) * 3 * slice * K ) ) != ACN_OK ) return st;
+    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || h->d_lens_rad.grow( sizeof( double ) * 3 * slice * K ) ) return ACN_ERR_DEVICE;
     acn_render_opts ray_opts = o;
     ray_opts.flags |= ACN_OPT_LINEAR_OUT;
     for( size_t base = 0; base < n; base += slice )
     {
         if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
         const size_t cnt = n - base < slice ? n - base : slice;
-        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays, c.stream );
+        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays.get(), c.stream );
         HIP_TRY( hipGetLastError() );
-        st = render_dispatch( h, primary_rays( h->d_lens_rays ), cnt * K, h->d_lens_rad, &ray_opts, c.stream );
+        st = render_dispatch( h, primary_rays( h->d_lens_rays.get() ), cnt * K, h->d_lens_rad.get(), &ray_opts, c.stream );
         if( st != ACN_OK ) return st;
         if( with_stats )
-            acn_launch_lens_reduce_stats( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
+            acn_launch_lens_reduce_stats( h->d_lens_rad.get(), cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
                                           d_stats + ( size_t )ACN_STATS_STRIDE * base, c.stream );
         else
-            acn_launch_lens_reduce( h->d_lens_rad, cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
+            acn_launch_lens_reduce( h->d_lens_rad.get(), cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
         HIP_TRY( hipGetLastError() );
     }
     return call_end( c );
@@ -576,14 +575,14 @@ extern "C" int acn_select_above_dev( acn_scene_handle* h, const void* d_key, siz
         return ACN_OK;
     }
     const size_t words = ( size_t )acn_select_tiles( n ) + 1;
-    if( ( st = grow_device( ( void** )&h->d_select_tiles, &h->select_tiles_bytes, sizeof( unsigned long long ) * words ) ) != ACN_OK ) return st;
-    acn_launch_select( ( const double* )d_key, n, p.threshold, h->d_select_tiles, p.capacity, ( const double* )d_src_pos_xy, width, p.raster_first,
+    if( h->d_select_tiles.grow( sizeof( unsigned long long ) * words ) ) return ACN_ERR_DEVICE;
+    acn_launch_select( ( const double* )d_key, n, p.threshold, h->d_select_tiles.get(), p.capacity, ( const double* )d_src_pos_xy, width, p.raster_first,
                        ( int64_t* )d_out_index, ( double* )d_out_pos_xy, ( unsigned long long* )d_out_count, c.stream );
     HIP_TRY( hipGetLastError() );
     if( !out_count ) return call_end( c );
     /* the one synchronisation of a caller's stream */
     unsigned long long total = 0;
-    HIP_TRY( hipMemcpyAsync( &total, h->d_select_tiles + ( words - 1 ), sizeof( total ), hipMemcpyDeviceToHost, c.stream ) );
+    HIP_TRY( hipMemcpyAsync( &total, h->d_select_tiles.get() + ( words - 1 ), sizeof( total ), hipMemcpyDeviceToHost, c.stream ) );
     HIP_TRY( hipStreamSynchronize( c.stream ) );
     *out_count = total;
     return ACN_OK;

@@ -1,12 +1,15 @@
 /* acn_handle.h -- what the host units of libactinon_hip.so share: the scene handle, the pipeline runner (PipeRun), the error
  * plumbing, the frame of one C ABI call and the few functions that cross between actinon_hip.hip (life cycle, workspace, pipeline, lanes and the pipeline's own
- * entry points), acn_calls.hip (every other entry point) and k_query.hip (the test seam). */
+ * entry points), acn_calls.hip (every other entry point) and k_query.hip (the test seam).
+ * Ownership: what a handle or a runner holds on the device (memory, events, streams) is a member of an owning type of acn_devbuf.h, a lane
+ * or a worker thread a std::unique_ptr: nothing is freed by a list, an early return cannot leak; kernels get plain pointers (.get()). */
 #ifndef ACN_HANDLE_H
 #define ACN_HANDLE_H
 
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -18,6 +21,7 @@
 #include "acn_tables.h"
 #include "acn_chunkplan.h"
 #include "acn_queueplan.h"
+#include "acn_devbuf.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* error plumbing */
@@ -27,7 +31,20 @@ static inline int fail( int code, const std::string& msg ) { g_last_error = msg;
 #define HIP_TRY( expr ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) \
     return fail( ACN_ERR_DEVICE, std::string( #expr ) + ": " + hipGetErrorString( e_ ) ); } while( 0 )
 
-struct StageEvents { hipEvent_t a, b; int stage; };
+/* The HIP policies of acn_devbuf.h: device memory, pinned host memory, events, streams.  alloc returns the hipError_t (0: done) and
+ * leaves a failure worded for acn_last_error(), so `if( buf.grow( bytes ) ) return ACN_ERR_DEVICE;` is a whole call site. */
+static inline int alloc_status( hipError_t e, const char* call ) { if( e != hipSuccess ) fail( ACN_ERR_DEVICE, std::string( call ) + ": " + hipGetErrorString( e ) ); return ( int )e; }
+struct HipDevice { static int alloc( void** p, size_t want ) { return alloc_status( hipMalloc( p, want ), "hipMalloc( p, want )" ); }
+                   static void release( void* p ) { hipFree( p ); } };   /* (hipFree waits for whatever still reads the block) */
+struct HipPinned { static int alloc( void** p, size_t want ) { return alloc_status( hipHostMalloc( p, want ), "hipHostMalloc( p, want )" ); }
+                   static void release( void* p ) { hipHostFree( p ); } };
+struct HipEventDel { static void destroy( hipEvent_t e ) { hipEventDestroy( e ); } };
+struct HipStreamDel { static void destroy( hipStream_t s ) { hipStreamDestroy( s ); } };
+template< class T > using DevBuf = Buf< T, HipDevice >;
+using Event = Owned< hipEvent_t, HipEventDel >;
+using Stream = Owned< hipStream_t, HipStreamDel >;
+
+struct StageEvents { Event a, b; int stage = 0; };
 
 /* a persistent host thread per lane (creating a thread per call costs a HIP per-thread initialisation each time) */
 struct LaneWorker
@@ -37,6 +54,7 @@ struct LaneWorker
     std::condition_variable cv;
     std::function< void() > job;
     bool has_job = false, done = true, quit = false;
+    ~LaneWorker() { stop(); }
     void start()
     {
         thread = std::thread( [ this ]()
@@ -158,18 +176,28 @@ struct Tunables
 /* the queue workspace of one pipeline run (WQ_*: acn_queueplan.h) */
 struct Workspace
 {
-    DTask*      tasks = nullptr;
-    uint32_t*   idx[ ACN_NCLASS ] = { nullptr, nullptr, nullptr, nullptr };
-    HitRec*     children = nullptr;
-    HardShadow* hard_shadow = nullptr;
-    HardPath*   hard_path = nullptr;
-    RayTask*    rays[ 2 ] = { nullptr, nullptr };
-    RayTask*    stacks = nullptr;   size_t stack_waves = 0;
+    DevBuf< DTask >      tasks;
+    DevBuf< uint32_t >   idx[ ACN_NCLASS ];
+    DevBuf< HitRec >     children;
+    DevBuf< HardShadow > hard_shadow;
+    DevBuf< HardPath >   hard_path;
+    DevBuf< RayTask >    rays[ 2 ];
+    DevBuf< RayTask >    stacks;   size_t stack_waves = 0;
     uint32_t    cap[ 5 ] = { 0, 0, 0, 0, 0 };   /* records per queue, WQ_* */
     size_t      bytes = 0;          /* device memory of the queues and stacks */
     uint64_t    allocs = 0;         /* times this workspace was (re)allocated */
     bool        trimmed = false;    /* it was already re-allocated smaller once */
     uint32_t    sized_calls = 0;    /* calls of ensure_workspace with learned rates (the trim window: acn_keep_caps) */
+    /* The queues and stacks go back to the device; cap, bytes and stack_waves are zero.  The bookkeeping: trimmed and sized_calls start
+     * over with EVERY release, also the one ensure_workspace makes to allocate anew (it sets trimmed again when it is done).  allocs
+     * survives only there (keep_allocs): a runner that gives its queues back to the handle's bound (render_dispatch, render_lanes) counts from zero. */
+    void release( bool keep_allocs = false )
+    {
+        tasks.reset(); for( auto& b : idx ) b.reset();
+        children.reset(); hard_shadow.reset(); hard_path.reset(); for( auto& b : rays ) b.reset();
+        stacks.reset(); stack_waves = 0; bytes = 0; for( uint32_t& c : cap ) c = 0;
+        trimmed = false; sized_calls = 0; if( !keep_allocs ) allocs = 0;
+    }
 };
 
 /* the statistics of one call (acn_last_stage_ms) */
@@ -232,16 +260,16 @@ struct PipeRun
 {
     const acn_scene_handle* h = nullptr;       /* the handle it serves (a lane: from bind_lane on) */
     DevScene dev{};                            /* the handle's, with flags -> the run's own counter block */
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stream stream;
+    Event ev0, ev1;
     unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
     unsigned walk_grid = 1024;                 /* ... of k_walk */
     Workspace ws;
-    uint32_t* d_counts = nullptr;              /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
-    uint32_t* h_counts = nullptr;              /* pinned copy */
-    unsigned long long* d_accum = nullptr;  size_t accum_bytes = 0;
-    unsigned long long* d_counters = nullptr;
-    unsigned long long* d_counters_keep = nullptr;   /* the work counters as they were before the current chunk (restored when it is redone) */
+    DevBuf< uint32_t > d_counts;               /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
+    Buf< uint32_t, HipPinned > h_counts;       /* pinned copy */
+    DevBuf< unsigned long long > d_accum;
+    DevBuf< unsigned long long > d_counters;
+    DevBuf< unsigned long long > d_counters_keep;   /* the work counters as they were before the current chunk (restored when it is redone) */
     std::vector< StageEvents > events;  size_t events_used = 0;
     int cur_stage = 0;
     size_t budget_div = 1;                     /* workspace budget of a lane = the handle's budget / lanes */
@@ -249,9 +277,10 @@ struct PipeRun
     Learned learned;
     RunStats stats;                            /* of the last call */
     /* of a lane */
-    LaneWorker* worker = nullptr;
-    double* d_lane_in = nullptr; size_t lane_in_bytes = 0;     /* its gathered positions or rays (grow_device, as every *_bytes below) */
-    double* d_lane_out = nullptr; size_t lane_out_bytes = 0;   /* ... and its results */
+    std::unique_ptr< LaneWorker > worker;
+    DevBuf< double > d_lane_in;                /* its gathered positions or rays */
+    DevBuf< double > d_lane_out;               /* ... and its results */
+    ~PipeRun() { worker.reset(); }             /* the thread is stopped and joined before anything it may touch goes (the members, last to first) */
 };
 
 struct acn_scene_handle
@@ -261,11 +290,10 @@ struct acn_scene_handle
     /* the resident scene and what the tables say about it */
     struct Resident
     {
-        GNode*   d_nodes = nullptr;
-        GMat*    d_mats = nullptr;
-        int32_t* d_elems = nullptr;
-        acn_texture* d_textures = nullptr;
-        size_t scene_bytes[ 4 ] = { 0, 0, 0, 0 };
+        DevBuf< GNode >   d_nodes;
+        DevBuf< GMat >    d_mats;
+        DevBuf< int32_t > d_elems;
+        DevBuf< acn_texture > d_textures;
         int max_csg_depth = 0;
         size_t lds_bytes = 0;                      /* > 0: the node array fits the LDS staging budget */
         size_t lds_stack_bytes = 0;                /* > 0: the machine kernels keep their CSG stacks in LDS */
@@ -275,35 +303,35 @@ struct acn_scene_handle
         int n_levels = 1;                          /* path levels of the scene's trace_depth */
         size_t n_lights = 1;                       /* elements of the light root */
     } scene;
-    SCEntry* d_sc_table = nullptr;
-    double* d_sc_spheres = nullptr;            /* ( pos, radius ) of the sphere leaves of d_sc_table */
+    DevBuf< SCEntry > d_sc_table;
+    DevBuf< double > d_sc_spheres;             /* ( pos, radius ) of the sphere leaves of d_sc_table */
     Tunables tun;
     unsigned cus = 256;                        /* compute units of the device */
     size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
     PipeRun run;                               /* a call that runs alone; its stream is the handle's own, its statistics the last call's */
     /* concurrent lanes (render_lanes): runners that own a stream, a workspace and a host thread each */
-    std::vector< PipeRun* > lanes;
+    std::vector< std::unique_ptr< PipeRun > > lanes;
     /* lanes made during acn_scene_upload on a helper thread (early_lanes_begin), taken over by the first call that runs on lanes */
     std::thread early_maker;
-    std::vector< PipeRun* > early_made;
+    std::vector< std::unique_ptr< PipeRun > > early_made;
     bool timed = false;
     bool used_lanes = false;                   /* the last render call ran through the lanes: statistics are their sums */
     int  lanes_used = 0;                       /* ... the first lanes_used of them */
     bool one_lane = false;                     /* the last call would have used lanes but did not fit the workspace bound that way */
     /* scratch of the entry points that are not the pipeline's */
-    double* d_shard_pos = nullptr; size_t shard_pos_bytes = 0;                              /* acn_render_main_pass_shard_dev: the rank's positions */
-    unsigned long long* d_ray_check = nullptr;                                              /* acn_render_rays_dev: the lowest index of a refused ray */
-    uint32_t* d_surface_flags = nullptr;                                                    /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
-    void* d_denoise = nullptr; size_t denoise_bytes = 0;                                    /* acn_denoise: guides and colour buffers, apart from the render workspace */
-    double* d_lens_rays = nullptr; size_t lens_rays_bytes = 0;                              /* acn_render_lens*: the rays [ 6 ] of a slice */
-    double* d_lens_rad = nullptr; size_t lens_rad_bytes = 0;                                /* ... and their radiance [ 3 ] */
-    unsigned long long* d_select_tiles = nullptr; size_t select_tiles_bytes = 0;            /* acn_select_above*: the counts per tile and their total */
+    DevBuf< double > d_shard_pos;                   /* acn_render_main_pass_shard_dev: the rank's positions */
+    DevBuf< unsigned long long > d_ray_check;       /* acn_render_rays_dev: the lowest index of a refused ray */
+    DevBuf< uint32_t > d_surface_flags;             /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
+    DevBuf< void > d_denoise;                       /* acn_denoise: guides and colour buffers, apart from the render workspace */
+    DevBuf< double > d_lens_rays;                   /* acn_render_lens*: the rays [ 6 ] of a slice */
+    DevBuf< double > d_lens_rad;                    /* ... and their radiance [ 3 ] */
+    DevBuf< unsigned long long > d_select_tiles;    /* acn_select_above*: the counts per tile and their total */
 };
 
 static SceneArgs scene_args( const DevScene& dev, const acn_scene_handle::Resident& r )
 {
     SceneArgs s;
-    s.dev = dev; s.nodes = r.d_nodes; s.mats = r.d_mats; s.elems = r.d_elems; s.textures = r.d_textures; s.elem_pos_base = r.elem_pos_base;
+    s.dev = dev; s.nodes = r.d_nodes.get(); s.mats = r.d_mats.get(); s.elems = r.d_elems.get(); s.textures = r.d_textures.get(); s.elem_pos_base = r.elem_pos_base;
     return s;
 }
 static size_t machine_lds_bytes( const acn_scene_handle::Resident& r ) { return r.lds_bytes + r.lds_stack_bytes; }
@@ -356,7 +384,7 @@ static inline int call_begin( acn_scene_handle* h, Call* c )
 {
     HIP_TRY( hipSetDevice( h->device ) );
     c->own = c->opts.stream == nullptr;
-    c->stream = c->own ? h->run.stream : ( hipStream_t )c->opts.stream;
+    c->stream = c->own ? h->run.stream.get() : ( hipStream_t )c->opts.stream;
     return ACN_OK;
 }
 static inline int call_end( const Call& c )
@@ -365,27 +393,16 @@ static inline int call_end( const Call& c )
     return ACN_OK;
 }
 
-/* a device buffer of at least `want` bytes: grown, never shrunk, its contents not kept; *cap is 0 after a hipMalloc that failed */
-static inline int grow_device( void** p, size_t* cap, size_t want )
-{
-    if( *cap >= want ) return ACN_OK;
-    if( *p ) hipFree( *p );   /* (waits for whatever still reads it) */
-    *p = nullptr; *cap = 0;
-    HIP_TRY( hipMalloc( p, want ) );
-    *cap = want;
-    return ACN_OK;
-}
-
 /* every ray of a call is checked before anything is rendered or written: the lowest index of a refused one, one word read back
  * (this synchronises `stream`, a caller's too) */
 static inline int check_rays( acn_scene_handle* h, const double* d_rays, size_t n, hipStream_t stream )
 {
-    if( !h->d_ray_check ) HIP_TRY( hipMalloc( &h->d_ray_check, sizeof( unsigned long long ) ) );
-    HIP_TRY( hipMemsetAsync( h->d_ray_check, 0xFF, sizeof( unsigned long long ), stream ) );
-    acn_launch_check_rays( d_rays, n, h->d_ray_check, stream );
+    if( h->d_ray_check.grow( sizeof( unsigned long long ) ) ) return ACN_ERR_DEVICE;
+    HIP_TRY( hipMemsetAsync( h->d_ray_check.get(), 0xFF, sizeof( unsigned long long ), stream ) );
+    acn_launch_check_rays( d_rays, n, h->d_ray_check.get(), stream );
     HIP_TRY( hipGetLastError() );
     unsigned long long bad = 0;
-    HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check, sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
+    HIP_TRY( hipMemcpyAsync( &bad, h->d_ray_check.get(), sizeof( bad ), hipMemcpyDeviceToHost, stream ) );
     HIP_TRY( hipStreamSynchronize( stream ) );
     if( bad < n ) return fail( ACN_ERR_ARG, "ray " + std::to_string( bad ) + ": a component is not finite or the direction has no length" );
     return ACN_OK;
@@ -402,14 +419,14 @@ static inline int pixel_range_check( const acn_scene_handle* h, size_t first, si
 /* device copies of host arrays for one call; everything is freed when it goes */
 struct DevCopies
 {
-    std::vector< void* > held;
-    ~DevCopies() { for( void* p : held ) hipFree( p ); }
+    std::vector< DevBuf< void > > held;
     /* null on failure; src (nullable) is copied in */
     void* make( const void* src, size_t bytes )
     {
-        void* d = nullptr;
-        if( hipMalloc( &d, bytes ? bytes : 1 ) != hipSuccess ) return nullptr;
-        held.push_back( d );
+        DevBuf< void > b;
+        if( b.grow( bytes ? bytes : 1 ) ) return nullptr;
+        void* d = b.get();
+        held.push_back( std::move( b ) );
         if( src && bytes && hipMemcpy( d, src, bytes, hipMemcpyHostToDevice ) != hipSuccess ) return nullptr;
         return d;
     }

@@ -3,20 +3,10 @@
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <cstddef>
-#include <mutex>
-#include <string>
-#include <vector>
-#include <functional>
 #include <algorithm>
-#include <thread>
-#include <atomic>
-#include <condition_variable>
 
-
-#include "acn_handle.h"
+#include "acn_handle.h"   /* (and the standard headers its types need) */
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* error plumbing (fail and HIP_TRY: acn_handle.h) */
@@ -77,7 +67,27 @@ extern "C" int acn_device_count( void )
     return n;
 }
 
-static int lane_objects( int device, bool debug, PipeRun** out );
+static int lane_objects( int device, bool debug, std::unique_ptr< PipeRun >* out );
+
+/* What every runner has beside its stream, which the caller has made: two events, the counter blocks, their pinned copy, and the blocks the
+ * kernels add to zeroed -- synchronously for the handle's own run, on its stream for a lane (where everything that uses them follows; the
+ * null stream would wait for the caller's).  mark( i ): the events (0), the blocks and memsets (1), the pinned block (2) are done. */
+template< class Mark >
+static hipError_t run_objects( PipeRun* r, bool on_stream, Mark mark )
+{
+    const size_t counters = sizeof( unsigned long long ) * ACN_CNT_SLOTS, counts = sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS;
+    hipError_t e = hipEventCreate( r->ev0.put() );
+    if( e == hipSuccess ) e = hipEventCreate( r->ev1.put() );
+    mark( 0 );
+    for( auto* b : { &r->d_counters, &r->d_counters_keep } ) if( e == hipSuccess ) e = ( hipError_t )b->grow( counters );
+    if( e == hipSuccess ) e = ( hipError_t )r->d_counts.grow( counts );
+    if( e == hipSuccess ) e = on_stream ? hipMemsetAsync( r->d_counters.get(), 0, counters, r->stream.get() ) : hipMemset( r->d_counters.get(), 0, counters );
+    if( e == hipSuccess ) e = on_stream ? hipMemsetAsync( r->d_counts.get(), 0, counts, r->stream.get() ) : hipMemset( r->d_counts.get(), 0, counts );
+    mark( 1 );
+    if( e == hipSuccess ) e = ( hipError_t )r->h_counts.grow( counts );
+    mark( 2 );
+    return e;
+}
 
 /* Lanes made during the upload.  A stream that gets its own hardware queue costs ~10 ms of host time, and making one while kernels
  * run stretches those kernels too (the learning pass of a cold handle: 19 ms alone, 56 - 150 ms beside six streams being made,
@@ -95,9 +105,9 @@ static void early_lanes_begin( acn_scene_handle* h, size_t n, uint64_t path_samp
     {
         for( int k = 0; k < lanes; k++ )
         {
-            PipeRun* l = nullptr;
+            std::unique_ptr< PipeRun > l;
             if( lane_objects( device, debug, &l ) != ACN_OK ) break;
-            h->early_made.push_back( l );
+            h->early_made.push_back( std::move( l ) );
         }
     } );
 }
@@ -117,13 +127,14 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     HIP_TRY( hipSetDevice( device ) );
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
-    acn_scene_handle* h = new acn_scene_handle();
+    /* (whatever returns early from here on frees what exists by then: acn_scene_free joins the helper thread first) */
+    std::unique_ptr< acn_scene_handle, void ( * )( acn_scene_handle* ) > h( new acn_scene_handle(), acn_scene_free );
     PipeRun* own = &h->run;
-    own->h = h;
+    own->h = h.get();
     h->device = device;
     h->tun.read();
-    if( h->tun.early_lanes ) early_lanes_begin( h, ( size_t )scene->params.image_width * ( size_t )scene->params.image_height, scene->params.path_samples );
-    double t_up[ 4 ] = { 0, 0, 0, 0 };   /* ACN_DEBUG_CHUNKS: stream + events, host-side tables, device copies, the camera kernel */
+    if( h->tun.early_lanes ) early_lanes_begin( h.get(), ( size_t )scene->params.image_width * ( size_t )scene->params.image_height, scene->params.path_samples );
+    double t_events = 0, t_up[ 4 ] = { 0, 0, 0, 0 };   /* ACN_DEBUG_CHUNKS: stream + events, host-side tables, device copies, the camera kernel */
     {
         /* Workspace BOUND of the handle: ACN_WORKSPACE_MB, or 64 GiB / a quarter of the free device memory (288 GB per
          * MI355X).  It is a bound, not an allocation: the queues are sized from measured demand (ensure_workspace) and take
@@ -148,16 +159,13 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
         own->shade_grid = h->tun.shade_grid ? h->tun.shade_grid : ( unsigned )cus * 4u;
         own->walk_grid = h->tun.walk_grid ? h->tun.walk_grid : own->grid;
     }
-    auto bail = [ & ]( int code ) { acn_scene_free( h ); return code; };
-#define HIP_TRY_H( expr ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) \
-    return bail( fail( ACN_ERR_DEVICE, std::string( #expr ) + ": " + hipGetErrorString( e_ ) ) ); } while( 0 )
     const double t_stream0 = since();
-    HIP_TRY_H( hipStreamCreate( &own->stream ) );
+    HIP_TRY( hipStreamCreate( own->stream.put() ) );
     const double t_stream1 = since();   /* (the first stream a process makes: 85 - 100 ms on this runtime; later ones ~10) */
     /* (a stream costs ~10 ms of host time to make: the second one only where it is used) */
-    HIP_TRY_H( hipEventCreate( &own->ev0 ) );
-    HIP_TRY_H( hipEventCreate( &own->ev1 ) );
-    t_up[ 0 ] = since();
+    const hipError_t made = run_objects( own, false, [ & ]( int i ) { if( i == 0 ) t_events = since(); } );
+    if( made != hipSuccess ) return fail( ACN_ERR_DEVICE, std::string( "events and counter blocks of the handle's run: " ) + hipGetErrorString( made ) );
+    t_up[ 0 ] = since();   /* (the counter blocks, made between t_events and here, are counted with the device copies below) */
     acn_scene_tables t;   /* everything the traversal shortcuts read, built on the host alone (acn_tables.cpp) */
     acn_tables_build( scene, h->tun.tables, &t );
     t_up[ 1 ] = since();
@@ -167,39 +175,29 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     r.prune = t.prune; r.leaf_lights = t.leaf_lights; r.elem_pos_base = t.elem_pos_base;
     r.n_levels = t.n_levels; r.n_lights = t.n_lights;
     const size_t n_tex = scene->n_textures ? scene->n_textures : 1, n_sc = t.sc_table.size() ? t.sc_table.size() : 1, n_sph = t.sc_spheres.size() ? t.sc_spheres.size() : 4;
-    r.scene_bytes[ 0 ] = sizeof( GNode ) * t.nodes.size(); r.scene_bytes[ 1 ] = sizeof( GMat ) * t.mats.size();
-    r.scene_bytes[ 2 ] = sizeof( int32_t ) * t.elems.size(); r.scene_bytes[ 3 ] = sizeof( acn_texture ) * n_tex;
-    HIP_TRY_H( hipMalloc( &r.d_nodes, r.scene_bytes[ 0 ] ) );
-    HIP_TRY_H( hipMalloc( &r.d_mats, r.scene_bytes[ 1 ] ) );
-    HIP_TRY_H( hipMalloc( &r.d_elems, r.scene_bytes[ 2 ] ) );
-    HIP_TRY_H( hipMalloc( &h->d_sc_table, sizeof( SCEntry ) * n_sc ) );
-    if( t.sc_table.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_table, t.sc_table.data(), sizeof( SCEntry ) * t.sc_table.size(), hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMalloc( &h->d_sc_spheres, sizeof( double ) * n_sph ) );
-    if( t.sc_spheres.size() ) HIP_TRY_H( hipMemcpy( h->d_sc_spheres, t.sc_spheres.data(), sizeof( double ) * t.sc_spheres.size(), hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMalloc( &r.d_textures, r.scene_bytes[ 3 ] ) );
-    if( scene->n_textures ) HIP_TRY_H( hipMemcpy( r.d_textures, scene->textures, sizeof( acn_texture ) * scene->n_textures, hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMalloc( &own->d_counters, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
-    HIP_TRY_H( hipMemset( own->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
-    HIP_TRY_H( hipMalloc( &own->d_counters_keep, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
-    HIP_TRY_H( hipMalloc( &own->d_counts, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
-    HIP_TRY_H( hipHostMalloc( &own->h_counts, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
-    HIP_TRY_H( hipMemcpy( r.d_nodes, t.nodes.data(), r.scene_bytes[ 0 ], hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMemcpy( r.d_mats, t.mats.data(), r.scene_bytes[ 1 ], hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMemcpy( r.d_elems, t.elems.data(), r.scene_bytes[ 2 ], hipMemcpyHostToDevice ) );
-    HIP_TRY_H( hipMemset( own->d_counts, 0, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
-    h->dev.nodes = ( NodeP )r.d_nodes; h->dev.gnodes = ( NodeP )r.d_nodes;
-    h->dev.mats = ( MatP )r.d_mats;
-    h->dev.elems = ( ElemP )r.d_elems;
-    h->dev.textures = ( TexP )r.d_textures;
-    h->dev.sc_table = h->d_sc_table;
-    h->dev.sc_spheres = h->d_sc_spheres;
+    if( r.d_nodes.grow( sizeof( GNode ) * t.nodes.size() ) || r.d_mats.grow( sizeof( GMat ) * t.mats.size() ) || r.d_elems.grow( sizeof( int32_t ) * t.elems.size() ) ) return ACN_ERR_DEVICE;
+    if( h->d_sc_table.grow( sizeof( SCEntry ) * n_sc ) ) return ACN_ERR_DEVICE;
+    if( t.sc_table.size() ) HIP_TRY( hipMemcpy( h->d_sc_table.get(), t.sc_table.data(), sizeof( SCEntry ) * t.sc_table.size(), hipMemcpyHostToDevice ) );
+    if( h->d_sc_spheres.grow( sizeof( double ) * n_sph ) ) return ACN_ERR_DEVICE;
+    if( t.sc_spheres.size() ) HIP_TRY( hipMemcpy( h->d_sc_spheres.get(), t.sc_spheres.data(), sizeof( double ) * t.sc_spheres.size(), hipMemcpyHostToDevice ) );
+    if( r.d_textures.grow( sizeof( acn_texture ) * n_tex ) ) return ACN_ERR_DEVICE;
+    if( scene->n_textures ) HIP_TRY( hipMemcpy( r.d_textures.get(), scene->textures, sizeof( acn_texture ) * scene->n_textures, hipMemcpyHostToDevice ) );
+    HIP_TRY( hipMemcpy( r.d_nodes.get(), t.nodes.data(), r.d_nodes.bytes(), hipMemcpyHostToDevice ) );
+    HIP_TRY( hipMemcpy( r.d_mats.get(), t.mats.data(), r.d_mats.bytes(), hipMemcpyHostToDevice ) );
+    HIP_TRY( hipMemcpy( r.d_elems.get(), t.elems.data(), r.d_elems.bytes(), hipMemcpyHostToDevice ) );
+    h->dev.nodes = ( NodeP )r.d_nodes.get(); h->dev.gnodes = ( NodeP )r.d_nodes.get();
+    h->dev.mats = ( MatP )r.d_mats.get();
+    h->dev.elems = ( ElemP )r.d_elems.get();
+    h->dev.textures = ( TexP )r.d_textures.get();
+    h->dev.sc_table = h->d_sc_table.get();
+    h->dev.sc_spheres = h->d_sc_spheres.get();
     h->dev.prune_base = t.prune_base;
     h->dev.light_root = scene->light_root;
     h->dev.matter_root = scene->matter_root;
     h->dev.n_nodes = scene->n_nodes;
     h->dev.n_elems = scene->n_elems;
     h->dev.prm = scene->params;
-    h->dev.flags = own->d_counts + QC_FLAGS;
+    h->dev.flags = own->d_counts.get() + QC_FLAGS;
     h->dev.lds_stack = r.lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
     /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
      * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
@@ -209,56 +207,23 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     h->dev.class0_min = h->tun.class0_min ? h->tun.class0_min : ( r.prune ? 32u : 255u );
     /* camera basis on the device so that it shares the device's arithmetic */
     {
-        M3* d_rot = nullptr; double* d_uf = nullptr;
-        HIP_TRY_H( hipMalloc( &d_rot, sizeof( M3 ) ) );
-        HIP_TRY_H( hipMalloc( &d_uf, sizeof( double ) ) );
+        DevBuf< M3 > d_rot; DevBuf< double > d_uf;
+        if( d_rot.grow( sizeof( M3 ) ) || d_uf.grow( sizeof( double ) ) ) return ACN_ERR_DEVICE;
         t_up[ 2 ] = since();
-        early_lanes_join( h );   /* before the first kernel: nothing of this handle runs while hardware queues are being made */
+        early_lanes_join( h.get() );   /* before the first kernel: nothing of this handle runs while hardware queues are being made */
         t_up[ 3 ] = since();
-        hipLaunchKernelGGL( k_camera_setup, dim3( 1 ), dim3( 1 ), 0, own->stream, h->dev, d_rot, d_uf );
-        HIP_TRY_H( hipGetLastError() );
-        HIP_TRY_H( hipStreamSynchronize( own->stream ) );
-        HIP_TRY_H( hipMemcpy( &h->dev.camera_rotation, d_rot, sizeof( M3 ), hipMemcpyDeviceToHost ) );
-        HIP_TRY_H( hipMemcpy( &h->dev.unit_f, d_uf, sizeof( double ), hipMemcpyDeviceToHost ) );
-        hipFree( d_rot ); hipFree( d_uf );
+        hipLaunchKernelGGL( k_camera_setup, dim3( 1 ), dim3( 1 ), 0, own->stream.get(), h->dev, d_rot.get(), d_uf.get() );
+        HIP_TRY( hipGetLastError() );
+        HIP_TRY( hipStreamSynchronize( own->stream.get() ) );
+        HIP_TRY( hipMemcpy( &h->dev.camera_rotation, d_rot.get(), sizeof( M3 ), hipMemcpyDeviceToHost ) );
+        HIP_TRY( hipMemcpy( &h->dev.unit_f, d_uf.get(), sizeof( double ), hipMemcpyDeviceToHost ) );
     }
     own->dev = h->dev;
     if( h->tun.debug_chunks )
         fprintf( stderr, "[acn upload] %u nodes: the handle's stream %.2f ms, events %.2f, tables on the host %.2f, device copies %.2f, waited for %d early lanes %.2f, first kernel of the library (camera set-up) %.2f\n",
-                 ( unsigned )scene->n_nodes, t_stream1 - t_stream0, t_up[ 0 ] - t_stream1 + t_stream0, t_up[ 1 ] - t_up[ 0 ], t_up[ 2 ] - t_up[ 1 ], ( int )h->early_made.size(), t_up[ 3 ] - t_up[ 2 ], since() - t_up[ 3 ] );
-    *out = h;
+                 ( unsigned )scene->n_nodes, t_stream1 - t_stream0, t_events - t_stream1 + t_stream0, t_up[ 1 ] - t_up[ 0 ], t_up[ 2 ] - t_up[ 1 ] + t_up[ 0 ] - t_events, ( int )h->early_made.size(), t_up[ 3 ] - t_up[ 2 ], since() - t_up[ 3 ] );
+    *out = h.release();
     return ACN_OK;
-}
-
-static void free_workspace( PipeRun* r )
-{
-    Workspace& w = r->ws;
-    if( w.tasks ) hipFree( w.tasks );
-    for( int k = 0; k < ACN_NCLASS; k++ ) if( w.idx[ k ] ) hipFree( w.idx[ k ] );
-    if( w.children ) hipFree( w.children );
-    if( w.hard_shadow ) hipFree( w.hard_shadow );
-    if( w.hard_path ) hipFree( w.hard_path );
-    for( int k = 0; k < 2; k++ ) if( w.rays[ k ] ) hipFree( w.rays[ k ] );
-    if( w.stacks ) hipFree( w.stacks );
-    w = Workspace();
-}
-
-/* everything a runner owns (the handle's own run is a member of the handle; a lane is deleted by who calls) */
-static void pipe_free( PipeRun* r )
-{
-    if( r->worker ) { r->worker->stop(); delete r->worker; r->worker = nullptr; }
-    free_workspace( r );
-    if( r->d_counts ) hipFree( r->d_counts );
-    if( r->h_counts ) hipHostFree( r->h_counts );
-    if( r->d_accum ) hipFree( r->d_accum );
-    if( r->d_lane_in ) hipFree( r->d_lane_in );
-    if( r->d_lane_out ) hipFree( r->d_lane_out );
-    if( r->d_counters ) hipFree( r->d_counters );
-    if( r->d_counters_keep ) hipFree( r->d_counters_keep );
-    for( auto& e : r->events ) { hipEventDestroy( e.a ); hipEventDestroy( e.b ); }
-    if( r->ev0 ) hipEventDestroy( r->ev0 );
-    if( r->ev1 ) hipEventDestroy( r->ev1 );
-    if( r->stream ) hipStreamDestroy( r->stream );
 }
 
 extern "C" void acn_scene_free( acn_scene_handle* h )
@@ -266,23 +231,7 @@ extern "C" void acn_scene_free( acn_scene_handle* h )
     if( !h ) return;
     hipSetDevice( h->device );
     early_lanes_join( h );
-    for( PipeRun* l : h->early_made ) { pipe_free( l ); delete l; }
-    for( PipeRun* l : h->lanes ) { pipe_free( l ); delete l; }
-    if( h->d_shard_pos ) hipFree( h->d_shard_pos );
-    if( h->d_ray_check ) hipFree( h->d_ray_check );
-    if( h->d_surface_flags ) hipFree( h->d_surface_flags );
-    if( h->d_denoise ) hipFree( h->d_denoise );
-    if( h->d_lens_rays ) hipFree( h->d_lens_rays );
-    if( h->d_lens_rad ) hipFree( h->d_lens_rad );
-    if( h->d_select_tiles ) hipFree( h->d_select_tiles );
-    if( h->scene.d_nodes ) hipFree( h->scene.d_nodes );
-    if( h->scene.d_mats ) hipFree( h->scene.d_mats );
-    if( h->scene.d_elems ) hipFree( h->scene.d_elems );
-    if( h->scene.d_textures ) hipFree( h->scene.d_textures );
-    if( h->d_sc_table ) hipFree( h->d_sc_table );
-    if( h->d_sc_spheres ) hipFree( h->d_sc_spheres );
-    pipe_free( &h->run );
-    delete h;
+    delete h;   /* (its members and its runners free themselves: acn_handle.h) */
 }
 
 /* the queues of a run hold what acn_wanted_caps (acn_queueplan.h) asks for, for a call of n positions: kept, or allocated anew */
@@ -296,25 +245,22 @@ static int ensure_workspace( PipeRun* r, size_t n )
     acn_wanted_caps( r->learned.rate, r->sw.seeded, n, r->dev.prm.path_samples, r->dev.prm.direct_samples, r->h->scene.n_lights, budget, stack_bytes, wq_bytes, want );
     int trim = 0;
     if( acn_keep_caps( w.cap, w.stack_waves, stack_waves, want, wq_bytes, r->learned.known(), r->learned.rate_cnt, w.trimmed, &w.sized_calls, &trim ) ) return ACN_OK;
-    const uint64_t allocs_before = w.allocs;
-    free_workspace( r );
-    w.allocs = allocs_before + 1;
+    w.release( true ); w.allocs++;
     for( ;; )
     {
         hipError_t e = hipSuccess;
         size_t total = 0;
-        auto grab = [ & ]( void** p, size_t bytes ) { if( e == hipSuccess ) { e = hipMalloc( p, bytes ); total += bytes; } };
-        grab( ( void** )&w.children, sizeof( HitRec ) * want[ WQ_CHILDREN ] );
-        grab( ( void** )&w.tasks, sizeof( DTask ) * want[ WQ_TASKS ] );
-        for( int k = 0; k < ACN_NCLASS; k++ ) grab( ( void** )&w.idx[ k ], sizeof( uint32_t ) * want[ WQ_TASKS ] );
-        grab( ( void** )&w.hard_shadow, sizeof( HardShadow ) * want[ WQ_HARD_SHADOW ] );
-        grab( ( void** )&w.hard_path, sizeof( HardPath ) * want[ WQ_HARD_PATH ] );
-        for( int k = 0; k < 2; k++ ) grab( ( void** )&w.rays[ k ], sizeof( RayTask ) * want[ WQ_RAYS ] );
-        grab( ( void** )&w.stacks, stack_bytes );
+        auto grab = [ & ]( auto& buf, size_t bytes ) { if( e == hipSuccess ) { e = ( hipError_t )buf.grow( bytes ); total += bytes; } };
+        grab( w.children, sizeof( HitRec ) * want[ WQ_CHILDREN ] );
+        grab( w.tasks, sizeof( DTask ) * want[ WQ_TASKS ] );
+        for( int k = 0; k < ACN_NCLASS; k++ ) grab( w.idx[ k ], sizeof( uint32_t ) * want[ WQ_TASKS ] );
+        grab( w.hard_shadow, sizeof( HardShadow ) * want[ WQ_HARD_SHADOW ] );
+        grab( w.hard_path, sizeof( HardPath ) * want[ WQ_HARD_PATH ] );
+        for( int k = 0; k < 2; k++ ) grab( w.rays[ k ], sizeof( RayTask ) * want[ WQ_RAYS ] );
+        grab( w.stacks, stack_bytes );
         if( e == hipSuccess ) { w.bytes = total; break; }
         ( void )hipGetLastError();
-        free_workspace( r );
-        w.allocs = allocs_before + 1;
+        w.release( true );
         if( acn_halve_caps( want ) ) return fail( ACN_ERR_DEVICE, std::string( "queue workspace: " ) + hipGetErrorString( e ) );
     }
     for( int q = 0; q < WQ_N; q++ ) w.cap[ q ] = ( uint32_t )want[ q ];
@@ -331,25 +277,24 @@ static int stage_begin( PipeRun* r, const Switches& sw, int stage, hipStream_t s
     if( !sw.stage_timing ) { r->cur_stage = stage; return ACN_OK; }
     if( r->events_used == r->events.size() )
     {
-        StageEvents e{};
-        HIP_TRY( hipEventCreate( &e.a ) );
-        HIP_TRY( hipEventCreate( &e.b ) );
-        r->events.push_back( e );
+        StageEvents e;
+        HIP_TRY( hipEventCreate( e.a.put() ) );
+        HIP_TRY( hipEventCreate( e.b.put() ) );
+        r->events.push_back( std::move( e ) );
     }
     r->events[ r->events_used ].stage = stage;
-    HIP_TRY( hipEventRecord( r->events[ r->events_used ].a, stream ) );
+    HIP_TRY( hipEventRecord( r->events[ r->events_used ].a.get(), stream ) );
     return ACN_OK;
 }
 
 static int stage_end( PipeRun* r, const Switches& sw, hipStream_t stream )
 {
     if( !sw.stage_timing ) { r->stats.launches[ r->cur_stage ]++; return ACN_OK; }
-    HIP_TRY( hipEventRecord( r->events[ r->events_used ].b, stream ) );
+    HIP_TRY( hipEventRecord( r->events[ r->events_used ].b.get(), stream ) );
     r->stats.launches[ r->events[ r->events_used ].stage ]++;
     r->events_used++;
     return ACN_OK;
 }
-
 
 static KernelFlags kernel_flags( const PipeRun* r, const Switches& sw )
 {
@@ -364,14 +309,14 @@ static LevelQ level_queues( const PipeRun* r, const Switches& sw, int level )
     const Workspace& w = r->ws;
     const Tunables& tun = r->h->tun;
     LevelQ q;
-    q.tasks = w.tasks; for( int k = 0; k < ACN_NCLASS; k++ ) q.idx[ k ] = w.idx[ k ];
+    q.tasks = w.tasks.get(); for( int k = 0; k < ACN_NCLASS; k++ ) q.idx[ k ] = w.idx[ k ].get();
     q.task_cap = w.cap[ WQ_TASKS ]; q.child_cap = w.cap[ WQ_CHILDREN ]; q.hs_cap = w.cap[ WQ_HARD_SHADOW ]; q.hard_cap = w.cap[ WQ_HARD_PATH ];
     q.ray_cap = w.cap[ WQ_RAYS ];
-    q.children = w.children; q.hard_shadow = w.hard_shadow; q.hard_path = w.hard_path;
-    q.rays[ 0 ] = w.rays[ 0 ]; q.rays[ 1 ] = w.rays[ 1 ];
-    q.stacks = w.stacks; q.stack_cap = tun.stack_cap; q.stack_use = tun.stack_use;
-    q.counts = r->d_counts + ( size_t )level * QC_N;
-    q.prev_children = r->d_counts + ( size_t )( level > 0 ? level - 1 : 0 ) * QC_N + QC_CHILDREN;
+    q.children = w.children.get(); q.hard_shadow = w.hard_shadow.get(); q.hard_path = w.hard_path.get();
+    q.rays[ 0 ] = w.rays[ 0 ].get(); q.rays[ 1 ] = w.rays[ 1 ].get();
+    q.stacks = w.stacks.get(); q.stack_cap = tun.stack_cap; q.stack_use = tun.stack_use;
+    q.counts = r->d_counts.get() + ( size_t )level * QC_N;
+    q.prev_children = r->d_counts.get() + ( size_t )( level > 0 ? level - 1 : 0 ) * QC_N + QC_CHILDREN;
     q.grid = r->grid; q.shade_grid = r->shade_grid; q.walk_grid = r->walk_grid;
     q.fetch_walk = tun.fetch_walk; q.fetch_hard = tun.fetch_hard; q.private_limit = tun.private_limit; q.fetch_shade = tun.fetch_shade;
     /* the outermost sample loops are those of level 0 */
@@ -407,7 +352,8 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
     const KernelFlags f = kernel_flags( r, sw );
     const SceneArgs s = scene_args( r->dev, r->h->scene );
     const size_t lds = machine_lds_bytes( r->h->scene );
-    HIP_TRY( hipMemsetAsync( r->d_counts, 0, sizeof( uint32_t ) * QC_N * levels, stream ) );
+    unsigned long long* const accum = r->d_accum.get(); unsigned long long* const counters = r->d_counters.get(); uint32_t* const h_counts = r->h_counts.get();
+    HIP_TRY( hipMemsetAsync( r->d_counts.get(), 0, sizeof( uint32_t ) * QC_N * levels, stream ) );
     if( prim.rays )
     {
         /* the caller's rays are generation 0 of level 0, one slot each (launch_render keeps a chunk within the ray queue) */
@@ -428,32 +374,32 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
          * hanging_lamp 600x800 -3 %, but paraffin_lamp 400x600 +8 % -- the rays of a CSG scene are worth redistributing
          * (profiles/r03/private_limit_small_frames.txt) */
         if( !tun.private_limit_set && r->dev.prm.path_samples == 0 && cnt <= ( 1u << 17 ) && cnt > q.private_limit ) q.private_limit = cnt;
-        if( level > 0 ) ACN_LAUNCH( r, sw, 0, stream, acn_launch_shade_hits( f.count, q, stream, s, r->d_accum, r->d_counters ) );
+        if( level > 0 ) ACN_LAUNCH( r, sw, 0, stream, acn_launch_shade_hits( f.count, q, stream, s, accum, counters ) );
         const uint32_t passes = walk_passes_of_level( r, level );
         for( uint32_t pass = 0; pass < passes; pass++ )
         {
             /* (the last launch of a level finishes whatever is left on the private stacks: the input of all later generations) */
             ACN_LAUNCH( r, sw, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes, q, lds, stream, s, prim.pos_xy, prim.first, base,
-                                                           level == 0 && pass == 0 ? n_cam : 0u, order, r->d_accum, r->d_counters ) );
+                                                           level == 0 && pass == 0 ? n_cam : 0u, order, accum, counters ) );
         }
-        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade64( f, q, stream, s, r->d_accum, r->d_counters ) );
-        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade16( f, q, stream, s, r->d_accum, r->d_counters ) );
-        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade4( f, q, stream, s, r->d_accum, r->d_counters ) );
-        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade1( f, q, stream, s, r->d_accum, r->d_counters ) );
-        ACN_LAUNCH( r, sw, 3, stream, acn_launch_hard_shadow( f, q, lds, stream, s, r->d_accum, r->d_counters ) );
+        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade64( f, q, stream, s, accum, counters ) );
+        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade16( f, q, stream, s, accum, counters ) );
+        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade4( f, q, stream, s, accum, counters ) );
+        ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade1( f, q, stream, s, accum, counters ) );
+        ACN_LAUNCH( r, sw, 3, stream, acn_launch_hard_shadow( f, q, lds, stream, s, accum, counters ) );
         /* the last level casts no path rays (depth <= 10) */
-        if( level + 1 < levels ) ACN_LAUNCH( r, sw, 3, stream, acn_launch_hard_path( f, q, lds, stream, s, r->d_accum, r->d_counters ) );
+        if( level + 1 < levels ) ACN_LAUNCH( r, sw, 3, stream, acn_launch_hard_path( f, q, lds, stream, s, accum, counters ) );
     }
-    HIP_TRY( hipMemcpyAsync( r->h_counts, r->d_counts, sizeof( uint32_t ) * QC_N * levels, hipMemcpyDeviceToHost, stream ) );
+    HIP_TRY( hipMemcpyAsync( h_counts, r->d_counts.get(), sizeof( uint32_t ) * QC_N * levels, hipMemcpyDeviceToHost, stream ) );
     HIP_TRY( hipStreamSynchronize( stream ) );
     stats.host_syncs++;
     /* the seeded generation of a ray call is a known demand (acn_queue_demand), not a learned one: with its word cleared the queue
      * marks, the learned passes and learn_rates see the counts of a position call, where level 0 has no generation 0 */
-    if( prim.rays ) r->h_counts[ QC_GEN + 0 ] = 0;
+    if( prim.rays ) h_counts[ QC_GEN + 0 ] = 0;
     uint32_t flags = 0;
     for( int level = 0; level < levels; level++ )
     {
-        const uint32_t* c = r->h_counts + ( size_t )level * QC_N;
+        const uint32_t* c = h_counts + ( size_t )level * QC_N;
         flags |= c[ QC_FLAGS ];
         if( c[ QC_GEN + walk_passes_of_level( r, level ) ] ) flags |= ACN_FLAG_CHILD_OVERFLOW;   /* rays left over by the last pass */
     }
@@ -462,7 +408,7 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
      * overflowed: at least this much): the next chunk's size and the queue capacities are derived from it */
     for( int level = 0; level < levels; level++ )
     {
-        const uint32_t* c = r->h_counts + ( size_t )level * QC_N;
+        const uint32_t* c = h_counts + ( size_t )level * QC_N;
         auto up = [ & ]( int q, uint32_t v ) { if( v > fill[ q ] ) fill[ q ] = v; };
         up( WQ_TASKS, c[ QC_TASKS ] );
         for( int k = 0; k < ACN_NCLASS; k++ ) up( WQ_TASKS, c[ QC_CLASS0 + k ] );
@@ -478,7 +424,7 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
         uint32_t mark = 0, recs = 0;
         for( int level = 0; level < levels; level++ )
         {
-            const uint32_t* c = r->h_counts + ( size_t )level * QC_N;
+            const uint32_t* c = h_counts + ( size_t )level * QC_N;
             if( c[ QC_HARD_SHADOW ] > mark ) { mark = c[ QC_HARD_SHADOW ]; recs = c[ QS_HARD_SHADOW ] + c[ QS_PROBES ]; }
         }
         if( mark > 0 && recs < mark ) *dead_share = ( double )( mark - recs ) / ( double )mark;
@@ -488,7 +434,7 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
     if( flags & ACN_FLAG_STACK_OVERFLOW ) return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow (or a walk that did not end)" );
     for( int level = 0; level < levels; level++ )
     {
-        const uint32_t* c = r->h_counts + ( size_t )level * QC_N;
+        const uint32_t* c = h_counts + ( size_t )level * QC_N;
         if( c[ QC_TASKS ] == 0 && c[ QS_WALK_RAYS ] == 0 ) break;
         stats.levels++;
         stats.walk_rays += c[ QS_WALK_RAYS ];
@@ -503,7 +449,7 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
     if( cnt >= 4096 )   /* a chunk large enough to stand for the next one */
     {
         uint32_t seen[ ACN_MAX_PATH_LEVELS + 1 ];
-        for( int level = 0; level < levels; level++ ) seen[ level ] = acn_walk_passes_seen( r->h_counts + ( size_t )level * QC_N + QC_GEN, walk_passes_of_level( r, level ) );
+        for( int level = 0; level < levels; level++ ) seen[ level ] = acn_walk_passes_seen( h_counts + ( size_t )level * QC_N + QC_GEN, walk_passes_of_level( r, level ) );
         for( int level = 0; level < levels; level++ ) r->learned.walk_passes_seen[ level ] = seen[ level ];
     }
     return ACN_OK;
@@ -529,7 +475,7 @@ static int learn_rates( PipeRun* r, const Primary& prim, size_t n, hipStream_t s
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     int st = ensure_workspace( r, 4096 );   /* the starter set */
     if( st != ACN_OK ) return st;
-    if( ( st = grow_device( ( void** )&r->d_accum, &r->accum_bytes, sizeof( unsigned long long ) * 3 * n ) ) != ACN_OK ) return st;
+    if( r->d_accum.grow( sizeof( unsigned long long ) * 3 * n ) ) return ACN_ERR_DEVICE;
     if( tun.debug_chunks ) fprintf( stderr, "[acn sample] starter queues (%.2f GB) after %.2f ms\n", ( double )r->ws.bytes / 1e9, since() );
     size_t want = acn_sample_positions( r->ws.cap[ WQ_CHILDREN ], r->ws.cap[ WQ_HARD_SHADOW ], r->dev.prm.path_samples, r->dev.prm.direct_samples, r->h->scene.n_lights, n );
     /* the sample renders unsharded, counts no work and records no stage events */
@@ -542,7 +488,7 @@ static int learn_rates( PipeRun* r, const Primary& prim, size_t n, hipStream_t s
         order.n = ( uint32_t )n; order.n_tiles = 1; order.mul = 1;
         order.sample_stride = ( uint32_t )( n / want );
         const uint32_t cnt = ( uint32_t )want;
-        hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, r->d_accum, 0u, cnt, order );
+        hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, r->d_accum.get(), 0u, cnt, order );
         HIP_TRY( hipGetLastError() );
         int overflow = 0;
         uint32_t fill[ WQ_N ];
@@ -555,7 +501,7 @@ static int learn_rates( PipeRun* r, const Primary& prim, size_t n, hipStream_t s
             fprintf( stderr, "[acn sample] %u positions (every %u-th) %s dead %.2f | per pos T %.1f C %.1f HS %.1f HP %.1f R %.1f\n", cnt, order.sample_stride, overflow ? "OVERFLOW" : "ok",
                      dead_share, fill[ 0 ] / ( double )cnt, fill[ 1 ] / ( double )cnt, fill[ 2 ] / ( double )cnt, fill[ 3 ] / ( double )cnt, fill[ 4 ] / ( double )cnt );
         if( overflow ) continue;
-        acn_sample_rates( r->h_counts, r->h->scene.n_levels, &count_index, cnt, plan_positions, plan_grid, L.rate );
+        acn_sample_rates( r->h_counts.get(), r->h->scene.n_levels, &count_index, cnt, plan_positions, plan_grid, L.rate );
         if( tun.debug_chunks ) fprintf( stderr, "[acn sample] rates T %.1f C %.1f HS %.1f HP %.1f R %.1f\n", L.rate[ 0 ], L.rate[ 1 ], L.rate[ 2 ], L.rate[ 3 ], L.rate[ 4 ] );
         L.rate_cnt = 8192;   /* a sample of the whole frame: trusted like a chunk that size (launch_render re-sizes for the whole rest at once) */
         break;
@@ -588,13 +534,13 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
     if( st != ACN_OK ) return st;
     st = ensure_workspace( r, n );
     if( st != ACN_OK ) return st;
-    if( ( st = grow_device( ( void** )&r->d_accum, &r->accum_bytes, sizeof( unsigned long long ) * 3 * n ) ) != ACN_OK ) return st;
+    if( r->d_accum.grow( sizeof( unsigned long long ) * 3 * n ) ) return ACN_ERR_DEVICE;
     r->events_used = 0;
     r->stats.reset();
     L.ctl.retry_bound = 0;   /* (a call that ended in the middle of a retry) */
-    HIP_TRY( hipMemsetAsync( r->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS, stream ) );
-    HIP_TRY( hipEventRecord( r->ev0, stream ) );
-    HIP_TRY( hipMemsetAsync( r->d_accum, 0, sizeof( unsigned long long ) * 3 * n, stream ) );
+    HIP_TRY( hipMemsetAsync( r->d_counters.get(), 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS, stream ) );
+    HIP_TRY( hipEventRecord( r->ev0.get(), stream ) );
+    HIP_TRY( hipMemsetAsync( r->d_accum.get(), 0, sizeof( unsigned long long ) * 3 * n, stream ) );
 
     /* Positions per pipeline run.  How many records a position leaves in each queue differs by orders of magnitude between
      * scenes (wine_glass: 15 deferred shadow rays per pixel; a closed room at path_samples 1024: 260 000 second-level hits),
@@ -626,7 +572,7 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
         uint32_t fill[ WQ_N ];
         double dead_share = 0;
         /* the work counters of a chunk that has to be redone must not count twice */
-        if( sw.count_work ) HIP_TRY( hipMemcpyAsync( r->d_counters_keep, r->d_counters, sizeof( unsigned long long ) * ACN_CNT_SLOTS, hipMemcpyDeviceToDevice, stream ) );
+        if( sw.count_work ) HIP_TRY( hipMemcpyAsync( r->d_counters_keep.get(), r->d_counters.get(), sizeof( unsigned long long ) * ACN_CNT_SLOTS, hipMemcpyDeviceToDevice, stream ) );
         st = render_chunk( r, sw, prim, ( uint32_t )base, cnt, order, stream, &overflow, fill, &dead_share );
         if( st != ACN_OK ) return st;
         if( tun.debug_chunks )
@@ -637,14 +583,14 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
         if( overflow )
         {
             if( cnt <= 1 ) return fail( ACN_ERR_DEVICE, "work queues overflow for a single position: raise ACN_WORKSPACE_MB" );
-            if( sw.count_work ) HIP_TRY( hipMemcpyAsync( r->d_counters, r->d_counters_keep, sizeof( unsigned long long ) * ACN_CNT_SLOTS, hipMemcpyDeviceToDevice, stream ) );
+            if( sw.count_work ) HIP_TRY( hipMemcpyAsync( r->d_counters.get(), r->d_counters_keep.get(), sizeof( unsigned long long ) * ACN_CNT_SLOTS, hipMemcpyDeviceToDevice, stream ) );
             r->stats.retries++;
             /* scenes whose demand per position varies much between chunks (many_spheres p256: 49 of 220 chunks were redone at
              * a fixed 70 %) plan with more head room */
             chunk = acn_ctl_overflow( &L.ctl, cnt );
             acn_overflow_rates( L.rate, cnt, fill );
             L.forget_passes();
-            hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, r->d_accum, ( uint32_t )base, cnt, order );
+            hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, r->d_accum.get(), ( uint32_t )base, cnt, order );
             HIP_TRY( hipGetLastError() );
             continue;
         }
@@ -665,10 +611,10 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
     }
     if( ( st = stage_begin( r, sw, 2, stream ) ) != ACN_OK ) return st;
     hipLaunchKernelGGL( k_finalize, dim3( ( unsigned )( ( n + 255 ) / 256 ) ), dim3( 256 ), 0, stream,
-                        ( const unsigned long long* )r->d_accum, ( uint32_t )n, r->dev.prm.gamma, linear, d_out_rgb );
+                        ( const unsigned long long* )r->d_accum.get(), ( uint32_t )n, r->dev.prm.gamma, linear, d_out_rgb );
     HIP_TRY( hipGetLastError() );
     if( ( st = stage_end( r, sw, stream ) ) != ACN_OK ) return st;
-    HIP_TRY( hipEventRecord( r->ev1, stream ) );
+    HIP_TRY( hipEventRecord( r->ev1.get(), stream ) );
     return ACN_OK;
 }
 
@@ -725,34 +671,21 @@ __global__ void k_lane_gather_rays( const double* __restrict__ rays, size_t n_la
  * of any size are free beside that), so six lanes are 60 ms of a handle's first call, more than its learning pass on the wine
  * glass.  The HIP objects (lane_objects: nothing in it reads the handle) are therefore made on a helper thread while the learning
  * pass runs on the device (render_lanes), and the lane is tied to its handle afterwards (bind_lane). */
-static int lane_objects( int device, bool debug, PipeRun** out )
+static int lane_objects( int device, bool debug, std::unique_ptr< PipeRun >* out )
 {
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     double t[ 5 ] = { 0, 0, 0, 0, 0 };
-    PipeRun* l = new PipeRun();
-#define HIP_TRY_L( expr ) do { hipError_t e_ = ( expr ); if( e_ != hipSuccess ) { pipe_free( l ); delete l; return fail( ACN_ERR_DEVICE, hipGetErrorString( e_ ) ); } } while( 0 )
-    HIP_TRY_L( hipSetDevice( device ) );
+    std::unique_ptr< PipeRun > l( new PipeRun() );
+    hipError_t e = hipSetDevice( device );
     t[ 0 ] = since();
-    HIP_TRY_L( hipStreamCreateWithFlags( &l->stream, hipStreamNonBlocking ) );
+    if( e == hipSuccess ) e = hipStreamCreateWithFlags( l->stream.put(), hipStreamNonBlocking );
     t[ 1 ] = since();
-    HIP_TRY_L( hipEventCreate( &l->ev0 ) );
-    HIP_TRY_L( hipEventCreate( &l->ev1 ) );
-    t[ 2 ] = since();
-    HIP_TRY_L( hipMalloc( &l->d_counters, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
-    HIP_TRY_L( hipMalloc( &l->d_counters_keep, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) );
-    HIP_TRY_L( hipMalloc( &l->d_counts, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
-    /* on the lane's own stream, where everything that uses them follows (the null stream would wait for the caller's) */
-    HIP_TRY_L( hipMemsetAsync( l->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS, l->stream ) );
-    HIP_TRY_L( hipMemsetAsync( l->d_counts, 0, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS, l->stream ) );
-    t[ 3 ] = since();
-    HIP_TRY_L( hipHostMalloc( &l->h_counts, sizeof( uint32_t ) * QC_N * ACN_LEVEL_BLOCKS ) );
-    t[ 4 ] = since();
-#undef HIP_TRY_L
-    l->worker = new LaneWorker();
-    l->worker->start();
+    if( e == hipSuccess ) e = run_objects( l.get(), true, [ & ]( int i ) { t[ 2 + i ] = since(); } );
+    if( e != hipSuccess ) return fail( ACN_ERR_DEVICE, hipGetErrorString( e ) );
+    l->worker.reset( new LaneWorker() ); l->worker->start();
     if( debug ) fprintf( stderr, "[acn lane] set device %.2f ms, stream %.2f, events %.2f, counter blocks + memsets %.2f, pinned block %.2f, thread %.2f\n", t[ 0 ], t[ 1 ] - t[ 0 ], t[ 2 ] - t[ 1 ], t[ 3 ] - t[ 2 ], t[ 4 ] - t[ 3 ], since() - t[ 4 ] );
-    *out = l;
+    *out = std::move( l );
     return ACN_OK;
 }
 
@@ -762,7 +695,7 @@ static void bind_lane( const acn_scene_handle* h, int lanes, PipeRun* l )
     l->h = h;
     l->budget_div = ( size_t )lanes;
     l->dev = h->dev;
-    l->dev.flags = l->d_counts + QC_FLAGS;
+    l->dev.flags = l->d_counts.get() + QC_FLAGS;
     /* Round 4: six lanes on grids of ONE workgroup per CU (k_shade: one and a half) instead of four lanes on two.  With k_walk at
      * four waves per SIMD a grid of 256 workgroups is resident at once, and six shorter chains fill each other's tails better than
      * four: 1080p 50.2 -> 49.1 ms, c2 26.4 -> 25.0, and the share one of 8 GPUs gets 12.25 -> 11.4 ms (profiles/r04/ab_lanes6_*).
@@ -784,18 +717,18 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     auto mark = [ & ]( int i ) { t_mark[ i ] = std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     /* the lanes this call lacks: made on a helper thread while the learning pass of a cold handle runs (see lane_objects) */
     early_lanes_join( h );
-    for( PipeRun* l : h->early_made ) { bind_lane( h, lanes, l ); h->lanes.push_back( l ); }   /* made during the upload */
+    for( auto& l : h->early_made ) { bind_lane( h, lanes, l.get() ); h->lanes.push_back( std::move( l ) ); }   /* made during the upload */
     h->early_made.clear();
     const int missing = lanes - ( int )h->lanes.size();
-    std::vector< PipeRun* > made;
+    std::vector< std::unique_ptr< PipeRun > > made;
     int made_status = ACN_OK; std::string made_message;
     auto make_missing = [ & ]()
     {
         for( int k = 0; k < missing && made_status == ACN_OK; k++ )
         {
-            PipeRun* l = nullptr;
+            std::unique_ptr< PipeRun > l;
             made_status = lane_objects( h->device, h->tun.debug_chunks, &l );
-            if( made_status == ACN_OK ) made.push_back( l ); else made_message = g_last_error;   /* thread-local where it was set */
+            if( made_status == ACN_OK ) made.push_back( std::move( l ) ); else made_message = g_last_error;   /* thread-local where it was set */
         }
     };
     std::thread maker;
@@ -803,8 +736,8 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     const bool maker_used = missing > 0 && learn && h->tun.cold_pipeline;
     if( missing > 0 ) { if( maker_used ) maker = std::thread( make_missing ); else make_missing(); }
     /* what the caller queued on `stream` before this call must be done before the lanes read the positions */
-    hipError_t drained = hipEventRecord( own->ev0, stream );
-    if( drained == hipSuccess ) drained = hipEventSynchronize( own->ev0 );
+    hipError_t drained = hipEventRecord( own->ev0.get(), stream );
+    if( drained == hipSuccess ) drained = hipEventSynchronize( own->ev0.get() );
     mark( 0 );
     /* a cold handle learns the scene's queue demand once, for all lanes, from a sample of the call (learn_rates) */
     int learned = ACN_OK;
@@ -815,12 +748,12 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
         if( learned == ACN_OK ) drained = hipStreamSynchronize( stream );
     }
     if( maker.joinable() ) maker.join();
-    for( PipeRun* l : made ) { bind_lane( h, lanes, l ); h->lanes.push_back( l ); }
+    for( auto& l : made ) { bind_lane( h, lanes, l.get() ); h->lanes.push_back( std::move( l ) ); }
     if( drained != hipSuccess ) return fail( ACN_ERR_DEVICE, hipGetErrorString( drained ) );
     if( learned != ACN_OK ) return learned;
     if( made_status != ACN_OK ) return fail( made_status, made_message );
     for( int k = 0; k < lanes; k++ ) Learned::inherit( &h->lanes[ k ]->learned, own->learned.known() ? own->learned : h->lanes[ 0 ]->learned );
-    if( learn && own->learned.known() ) free_workspace( own );   /* the bound is the handle's, whoever uses it */
+    if( learn && own->learned.known() ) own->ws.release();   /* the bound is the handle's, whoever uses it */
     /* The lanes' queues are (re-)sized here, while the device is idle: hipFree synchronises the device, so lanes that
      * re-size at the start of their chains wait for each other's chunks (second frame of paraffin_lamp 400x600, whose
      * queues are trimmed to the rates the first frame learned: 2.1 s instead of 0.45, profiles/r03/frames_paraffin_*.txt).
@@ -834,30 +767,30 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     {
         h->lanes[ k ]->worker->post( [ &, k ]()
         {
-            PipeRun* l = h->lanes[ k ];
+            PipeRun* l = h->lanes[ k ].get();
             l->budget_div = ( size_t )lanes;
             size_t cnt = acn_lane_count( n, lanes, k );
             auto run = [ & ]() -> int
             {
                 HIP_TRY( hipSetDevice( h->device ) );
-                if( cnt == 0 ) { l->events_used = 0; HIP_TRY( hipMemset( l->d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) ); return ACN_OK; }
+                if( cnt == 0 ) { l->events_used = 0; HIP_TRY( hipMemset( l->d_counters.get(), 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS ) ); return ACN_OK; }
                 /* the lane's share of the input: positions (2 doubles each) or rays (6) */
-                int st = grow_device( ( void** )&l->d_lane_in, &l->lane_in_bytes, sizeof( double ) * ( prim.rays ? 6 : 2 ) * cnt );
-                if( st == ACN_OK ) st = grow_device( ( void** )&l->d_lane_out, &l->lane_out_bytes, sizeof( double ) * 3 * cnt );
-                if( st != ACN_OK ) return st;
+                if( l->d_lane_in.grow( sizeof( double ) * ( prim.rays ? 6 : 2 ) * cnt ) || l->d_lane_out.grow( sizeof( double ) * 3 * cnt ) ) return ACN_ERR_DEVICE;
+                double* const d_in = l->d_lane_in.get(); double* const d_out = l->d_lane_out.get();
+                hipStream_t const ls = l->stream.get();
                 if( prim.rays )
-                    hipLaunchKernelGGL( k_lane_gather_rays, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
-                                        prim.rays, cnt, lanes, k, l->d_lane_in );
+                    hipLaunchKernelGGL( k_lane_gather_rays, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
+                                        prim.rays, cnt, lanes, k, d_in );
                 else
-                    hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
-                                        prim.pos_xy, prim.first, ( uint64_t )h->dev.prm.image_width, cnt, lanes, k, l->d_lane_in );
+                    hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
+                                        prim.pos_xy, prim.first, ( uint64_t )h->dev.prm.image_width, cnt, lanes, k, d_in );
                 HIP_TRY( hipGetLastError() );
-                st = launch_render( l, prim.rays ? primary_rays( l->d_lane_in ) : primary_positions( l->d_lane_in ), cnt, l->d_lane_out, &lane_opts, l->stream );
+                const int st = launch_render( l, prim.rays ? primary_rays( d_in ) : primary_positions( d_in ), cnt, d_out, &lane_opts, ls );
                 if( st != ACN_OK ) return st;
-                hipLaunchKernelGGL( k_lane_scatter, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, l->stream,
-                                    ( const double* )l->d_lane_out, cnt, lanes, k, d_out_rgb );
+                hipLaunchKernelGGL( k_lane_scatter, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
+                                    ( const double* )d_out, cnt, lanes, k, d_out_rgb );
                 HIP_TRY( hipGetLastError() );
-                HIP_TRY( hipStreamSynchronize( l->stream ) );
+                HIP_TRY( hipStreamSynchronize( ls ) );
                 return ACN_OK;
             };
             status[ k ] = run();
@@ -866,7 +799,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     };
     for( int k = 0; k < lanes; k++ )
     {
-        PipeRun* l = h->lanes[ k ];
+        PipeRun* l = h->lanes[ k ].get();
         l->budget_div = ( size_t )lanes;
         l->sw.seeded = prim.rays != nullptr;
         const size_t cnt = acn_lane_count( n, lanes, k );
@@ -880,7 +813,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
         fprintf( stderr, "[acn call] %zu positions on %d lanes: %d lanes made%s, caller's stream drained after %.2f ms, learning pass %.2f, queues sized %.2f, lanes done %.2f\n",
                  n, lanes, missing > 0 ? missing : 0, maker_used ? " beside the learning pass" : "", t_mark[ 0 ], t_mark[ 1 ] - t_mark[ 0 ], t_mark[ 2 ] - t_mark[ 1 ], t_mark[ 3 ] - t_mark[ 2 ] );
     for( int k = 0; k < lanes; k++ ) if( status[ k ] != ACN_OK ) return fail( status[ k ], message[ k ] );
-    HIP_TRY( hipEventRecord( own->ev1, stream ) );
+    HIP_TRY( hipEventRecord( own->ev1.get(), stream ) );
     /* statistics of the call: the lanes' together (RunStats::add), without those that had no positions */
     own->stats.reset();
     for( int k = 0; k < lanes; k++ ) if( acn_lane_count( n, lanes, k ) ) own->stats.add( h->lanes[ k ]->stats );
@@ -912,13 +845,13 @@ int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, double*
     int st;
     if( lanes <= 1 )
     {
-        for( PipeRun* l : h->lanes ) free_workspace( l );   /* the bound is the handle's, whoever uses it */
+        for( auto& l : h->lanes ) l->ws.release();   /* the bound is the handle's, whoever uses it */
         if( !h->lanes.empty() ) Learned::inherit( &own->learned, h->lanes[ 0 ]->learned );
         st = launch_render( own, prim, n, d_out_rgb, opts, stream );
     }
     else
     {
-        free_workspace( own );
+        own->ws.release();
         st = render_lanes( h, lanes, prim, n, d_out_rgb, opts, stream );   /* (makes the lanes it lacks) */
     }
     if( st == ACN_OK && n ) h->timed = true;
@@ -1023,11 +956,11 @@ extern "C" int acn_render_main_pass_shard_dev( acn_scene_handle* h, size_t first
     if( padded > mine ) HIP_TRY( hipMemsetAsync( ( double* )d_part + 3 * mine, 0, sizeof( double ) * 3 * ( padded - mine ), c.stream ) );
     if( mine )
     {
-        if( ( st = grow_device( ( void** )&h->d_shard_pos, &h->shard_pos_bytes, sizeof( double ) * 2 * mine ) ) != ACN_OK ) return st;
+        if( h->d_shard_pos.grow( sizeof( double ) * 2 * mine ) ) return ACN_ERR_DEVICE;
         hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( mine + 255 ) / 256 ) ), dim3( 256 ), 0, c.stream,
-                            ( const double* )nullptr, first, ( uint64_t )h->dev.prm.image_width, mine, ( int )world, ( int )rank, h->d_shard_pos );
+                            ( const double* )nullptr, first, ( uint64_t )h->dev.prm.image_width, mine, ( int )world, ( int )rank, h->d_shard_pos.get() );
         HIP_TRY( hipGetLastError() );
-        if( ( st = render_dispatch( h, primary_positions( h->d_shard_pos ), mine, ( double* )d_part, &c.opts, c.stream ) ) != ACN_OK ) return st;
+        if( ( st = render_dispatch( h, primary_positions( h->d_shard_pos.get() ), mine, ( double* )d_part, &c.opts, c.stream ) ) != ACN_OK ) return st;
     }
     return call_end( c );
 }
@@ -1050,9 +983,9 @@ extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )
 {
     if( !h || !trace_ms || !h->timed ) return fail( ACN_ERR_ARG, "no timed launch" );
     HIP_TRY( hipSetDevice( h->device ) );
-    HIP_TRY( hipEventSynchronize( h->run.ev1 ) );
+    HIP_TRY( hipEventSynchronize( h->run.ev1.get() ) );
     float ms = 0;
-    HIP_TRY( hipEventElapsedTime( &ms, h->run.ev0, h->run.ev1 ) );
+    HIP_TRY( hipEventElapsedTime( &ms, h->run.ev0.get(), h->run.ev1.get() ) );
     *trace_ms = ms;
     return ACN_OK;
 }
@@ -1060,15 +993,16 @@ extern "C" int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms )
 /* the runners of the last call: the lanes it ran on, or the handle's own */
 static std::vector< const PipeRun* > last_runs( const acn_scene_handle* h )
 {
-    if( h->used_lanes ) return std::vector< const PipeRun* >( h->lanes.begin(), h->lanes.begin() + h->lanes_used );
-    return { &h->run };
+    std::vector< const PipeRun* > runs;
+    for( int k = 0; h->used_lanes && k < h->lanes_used; k++ ) runs.push_back( h->lanes[ k ].get() );
+    return h->used_lanes ? runs : std::vector< const PipeRun* >{ &h->run };
 }
 
 extern "C" int acn_last_stage_ms( acn_scene_handle* h, double* out, int n )
 {
     if( !h || !out || n < 0 || n > 25 || !h->timed ) return fail( ACN_ERR_ARG, "no timed launch" );
     HIP_TRY( hipSetDevice( h->device ) );
-    HIP_TRY( hipEventSynchronize( h->run.ev1 ) );
+    HIP_TRY( hipEventSynchronize( h->run.ev1.get() ) );
     double ms[ 4 ] = { 0, 0, 0, 0 };
     size_t queue_cap = 0, ws_bytes = 0, ws_allocs = 0;
     for( const PipeRun* l : last_runs( h ) )   /* stage times: summed over the concurrent lanes of the call */
@@ -1077,12 +1011,12 @@ extern "C" int acn_last_stage_ms( acn_scene_handle* h, double* out, int n )
         for( size_t i = 0; i < l->events_used; i++ )
         {
             float t = 0;
-            HIP_TRY( hipEventElapsedTime( &t, l->events[ i ].a, l->events[ i ].b ) );
+            HIP_TRY( hipEventElapsedTime( &t, l->events[ i ].a.get(), l->events[ i ].b.get() ) );
             ms[ l->events[ i ].stage ] += t;
         }
     }
     float total = 0;
-    HIP_TRY( hipEventElapsedTime( &total, h->run.ev0, h->run.ev1 ) );
+    HIP_TRY( hipEventElapsedTime( &total, h->run.ev0.get(), h->run.ev1.get() ) );
     const RunStats& s = h->run.stats;
     double v[ 25 ] = { ms[ 0 ], ms[ 1 ], ms[ 2 ], total, ( double )s.launches[ 0 ], ( double )s.launches[ 1 ], ( double )s.launches[ 2 ],
                        ( double )s.chunks, ( double )s.retries, ( double )s.levels, ( double )s.peak_tasks, ( double )s.peak_children,
@@ -1101,7 +1035,7 @@ extern "C" int acn_last_counters( acn_scene_handle* h, uint64_t* out, int n )
     for( int k = 0; k < ACN_CNT_SLOTS; k++ ) sum[ k ] = 0;
     for( const PipeRun* l : last_runs( h ) )
     {
-        HIP_TRY( hipMemcpy( c, l->d_counters, sizeof( c ), hipMemcpyDeviceToHost ) );
+        HIP_TRY( hipMemcpy( c, l->d_counters.get(), sizeof( c ), hipMemcpyDeviceToHost ) );
         for( int k = 0; k < ACN_CNT_SLOTS; k++ ) sum[ k ] += c[ k ];
     }
     for( int k = 0; k < n; k++ ) out[ k ] = k < ACN_CNT_SLOTS ? sum[ k ] : 0;
