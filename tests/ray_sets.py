@@ -115,13 +115,18 @@ def make_leaf(kind, rng):
     return _place(o, rng)
 
 
-def random_csg(rng, depth):
+def random_csg(rng, depth, leaf=None, visit=None):
     """A random CSG tree of the given depth over every primitive constructor, with complements, scale wrappers,
-    rotations, moves and explicit envelopes on the way."""
+    rotations, moves and explicit envelopes on the way.  leaf( kind, rng ) replaces make_leaf; visit( o ) sees every leaf
+    and every pair before its parent clones it (neither may draw from rng: the tree stays the same)."""
+    leaf = leaf or make_leaf
+    visit = visit or (lambda o: None)
     if depth == 0:
-        return make_leaf(LEAF_KINDS[int(rng.integers(0, len(LEAF_KINDS)))], rng)
-    a = random_csg(rng, depth - 1)
-    b = random_csg(rng, int(rng.integers(0, depth)))
+        o = leaf(LEAF_KINDS[int(rng.integers(0, len(LEAF_KINDS)))], rng)
+        visit(o)
+        return o
+    a = random_csg(rng, depth - 1, leaf, visit)
+    b = random_csg(rng, int(rng.integers(0, depth)), leaf, visit)
     # a bounded operand keeps the infinite quadrics and half-spaces from filling the scene
     if rng.random() < 0.5:
         ball = host.acn_obj_sphere_s_create(float(rng.uniform(0.8, 1.4)))
@@ -136,6 +141,7 @@ def random_csg(rng, depth):
     inside = rng.random() < 0.6
     o = (host.acn_obj_pair_inside_s_create_pair if inside else host.acn_obj_pair_outside_s_create_pair)(a, b)
     host.acn_obj_discard(a); host.acn_obj_discard(b)
+    visit(o)
     if rng.random() < 0.15:
         t = host.acn_obj_scale_s_create_scale(o, A.v3(*rng.uniform(0.6, 1.5, 3)))
         host.acn_obj_discard(o)
@@ -154,15 +160,17 @@ def plane_normal(p):
     return rax(f.node(f.elems_of(f.c.matter_root)[0]))[2].copy()
 
 
-def balanced_polytope(rng, n=24):
+def balanced_polytope(rng, n=24, visit=None):
     """acn_create_inside_composite of n half-spaces tangent to a unit-ish sphere (a diamond-like polytope, 2n - 1 nodes:
-    the upload step compiles an interval-prune program for it)."""
+    the upload step compiles an interval-prune program for it).  visit( k, plane ) sees plane k before the composite clones it."""
     planes = []
     for k in range(n):
         p = host.acn_obj_plane_s_create()
         for m in _rot(rng):
             host.acn_obj_rotate(p, C.byref(m))
         host.acn_obj_move(p, A.v3(*plane_normal(p)))   # the plane at distance 1 from the origin, the origin inside
+        if visit:
+            visit(k, p)
         planes.append(p)
     arr = (C.c_void_p * n)(*planes)
     o = host.acn_create_inside_composite(arr, n)
@@ -190,18 +198,19 @@ def balanced_blob(rng, n=20):
     return o
 
 
-def tie_compound(rng, groups=8, per=8, shift=0.0):
+def tie_compound(rng, groups=8, per=8, shift=0.0, visit=None):
     """(h) A compound of `groups` enveloped sub-compounds of `per` spheres each (>= 64 table entries: the upload step lays
     it out a second time in reverse order), in which sub-compound g + groups / 2 holds exactly the spheres of sub-compound g:
     every leaf exists twice under different parents, so distances tie bit for bit and only the tie rule picks the hit.
     shift > 0: the twins are moved by `shift` along z instead and get envelopes as tight as culling allows -- along z the later
-    twin in the table is nearer by less than f3_eps, the case env_behind's margin is for."""
+    twin in the table is nearer by less than f3_eps, the case env_behind's margin is for.
+    visit( g, k, sphere ) sees sphere k of sub-compound g before it is pushed."""
     half = groups // 2
     spheres = [[(rng.uniform(-1.5, 1.5, 3), float(rng.uniform(0.15, 0.4))) for _ in range(per)] for _ in range(half)]
     top = host.acn_compound_s_create()
     for g in range(groups):
         sub = host.acn_compound_s_create()
-        for pos, r in spheres[g % half]:
+        for k, (pos, r) in enumerate(spheres[g % half]):
             s = host.acn_obj_sphere_s_create(r)
             host.acn_obj_set_material(s, b"diffuse")
             if shift and g >= half:
@@ -209,6 +218,8 @@ def tie_compound(rng, groups=8, per=8, shift=0.0):
             host.acn_obj_move(s, A.v3(*pos))
             if shift:   # just wide enough for the upload step to call it bounding (culling on, simple_compound_hit)
                 host.acn_obj_set_envelope(s, A.v3(*pos), r * (1 + 4e-9))
+            if visit:
+                visit(g, k, s)
             host.acn_compound_s_push(sub, s)
             host.acn_obj_discard(s)
         c = np.mean([p for p, _ in spheres[g % half]], axis=0)
@@ -607,3 +618,361 @@ def cone_parallel_plane(rng, light_c, light_r, nor, n=6, backs=(0.5, 2.0), digit
                 p = T - g * mp.mpf(back)
                 out.append((np.array([float(x) for x in p]), unit(np.array([float(x) for x in g]))))
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# distance objects and rough surfaces (tests/test_rough_distance_cpu.py, tests/test_gpu_rough_distance.py)
+
+ACN_SDF_SPHERE, ACN_SDF_TORUS = 0, 1
+ROUGHNESS = (0.002, 0.02, 0.1)   # the values of the lamp scripts
+TORUS_ROLES = ("torus", "torus_bare", "torus_short", "rough_torus")   # root elements that are one torus node
+DISTANCE_ROLES = ("torus", "torus_bare", "torus_short", "sdf_sphere", "sdf_default")
+
+
+def _pair_inside(a, b):
+    o = host.acn_obj_pair_inside_s_create_pair(a, b)
+    host.acn_obj_discard(a); host.acn_obj_discard(b)
+    return o
+
+
+def _neg(a):
+    o = host.acn_obj_neg_s_create_neg(a)
+    host.acn_obj_discard(a)
+    return o
+
+
+def _scale(a, v):
+    o = host.acn_obj_scale_s_create_scale(a, A.v3(*v))
+    host.acn_obj_discard(a)
+    return o
+
+
+def _torus(rng, r1=0.5, r2=0.18):
+    o = host.acn_obj_torus_create(r1, r2)
+    host.acn_obj_set_material(o, b"diffuse")
+    return _place(o, rng, spread=0.2)
+
+
+def rough_distance_scene(seed=2, rough=True):
+    """The second query scene: one light sphere; as matter root elements distance objects (tori with and without an envelope,
+    with 3 cycles, the sphere function under a scale, the default function; tori as operands of pairs, under NEG and under a
+    scale wrapper, in a random tree) and rough surfaces at every place a normal is perturbed (leaves, both operands of a leaf
+    pair and the pair, the pair alone, a complemented operand, under a scale wrapper, a random tree, a balanced composite, a
+    simple compound with ties between a rough and a smooth twin), and a sphere of negative roughness.  rough=False builds the
+    SMOOTH TWIN: the same objects, the same draws and the same node indices, no acn_obj_set_surface_roughness call.
+    Returns (scene, roles): roles[k] names root element k of the matter root."""
+    rng = np.random.default_rng(seed)
+    sc = A.Scene()
+    sc.set(image_width=64, image_height=48, gamma=1.0, trace_depth=10, trace_min_intensity=0.03, direct_samples=8,
+           path_samples=4, max_path_length=4.0, camera_position=(0, -8, 2), camera_view_direction=(0, 8, -2),
+           camera_top_direction=(0, 0, 1), camera_focal_length=3, background_color=(0.3, 0.35, 0.4))
+    light = host.acn_obj_sphere_s_create(0.7)
+    host.acn_obj_set_radiance(light, 25.0)
+    host.acn_obj_move(light, A.v3(-1, -2, 9))
+    sc.push(light)
+    host.acn_obj_discard(light)
+    objs, roles = [], []
+
+    def rgh(o, v):
+        if rough:
+            host.acn_obj_set_surface_roughness(o, float(v))
+        return o
+
+    def add(role, o):
+        objs.append(o); roles.append(role)
+
+    def ball(r, at=(0, 0, 0)):
+        o = host.acn_obj_sphere_s_create(float(r))
+        host.acn_obj_set_material(o, b"diffuse")
+        host.acn_obj_move(o, A.v3(*at))
+        return o
+
+    # -- distance objects
+    add("torus", _torus(rng))
+    o = host.acn_obj_distance_s_create()   # assembled by hand: no envelope, not rotated (rays along its axis meet f == 0 exactly)
+    assert host.acn_obj_set_distance_function(o, ACN_SDF_TORUS, 0.18 / 0.5) == 0
+    host.acn_obj_scale(o, 0.5)
+    host.acn_obj_set_material(o, b"diffuse")
+    add("torus_bare", _place(o, rng, spread=0.2, rotate=False))
+    o = _torus(rng)
+    assert host.acn_obj_set_field(o, b"cycles", 3.0) == 1
+    add("torus_short", o)
+    o = host.acn_obj_distance_s_create()
+    assert host.acn_obj_set_distance_function(o, ACN_SDF_SPHERE, 0.0) == 0
+    host.acn_obj_scale(o, 0.37)
+    host.acn_obj_set_material(o, b"diffuse")
+    add("sdf_sphere", _place(o, rng, spread=0.2))
+    o = host.acn_obj_distance_s_create()
+    host.acn_obj_set_material(o, b"diffuse")
+    add("sdf_default", _place(o, rng, spread=0.2))
+    add("torus_and_ball", _pair_inside(_torus(rng), ball(0.5, (0.35, 0.1, 0.05))))
+    p = host.acn_obj_plane_s_create()
+    host.acn_obj_set_material(p, b"diffuse")
+    add("torus_minus_half", _pair_inside(_torus(rng), _neg(_place(p, rng, spread=0.1))))
+    add("torus_scaled", _scale(_torus(rng), (1.3, 0.7, 1.1)))
+    add("torus_hole", _pair_inside(ball(0.6), _neg(_torus(rng))))
+    first = [True]
+
+    def torus_leaf(kind, r):
+        o = make_leaf(kind, r)   # the draws of the leaf it replaces are made
+        if first[0]:
+            first[0] = False
+            host.acn_obj_discard(o)
+            o = host.acn_obj_torus_create(0.5, 0.18)
+            host.acn_obj_set_material(o, b"diffuse")
+        return o
+    add("torus_deep", random_csg(rng, 3, leaf=torus_leaf))
+
+    # -- rough surfaces
+    for role, kind, v in (("rough_sphere", "sphere", 0.02), ("rough_plane", "plane", 0.1), ("rough_ellipsoid", "ellipsoid", 0.002),
+                          ("rough_cone", "cone", 0.02)):
+        add(role, rgh(make_leaf(kind, rng), v))
+    add("rough_torus", rgh(_torus(rng), 0.1))
+    add("rough_leaf_pair", rgh(_pair_inside(rgh(make_leaf("sphere", rng), 0.1), rgh(make_leaf("plane", rng), 0.002)), 0.02))
+    add("rough_pair_only", rgh(_pair_inside(make_leaf("sphere", rng), make_leaf("plane", rng)), 0.1))
+    o = host.acn_obj_squaroid_s_create_ellipsoid(1.0, 0.9, 0.8)   # a wide bite out of the ball: its rough wall is what rays see
+    host.acn_obj_set_material(o, b"diffuse")
+    for m in _rot(rng):
+        host.acn_obj_rotate(o, C.byref(m))
+    host.acn_obj_move(o, A.v3(0.4, 0.2, 0.1))
+    add("rough_neg", _pair_inside(ball(1.0), _neg(rgh(o, 0.02))))
+    add("rough_scaled", _scale(rgh(_pair_inside(rgh(make_leaf("sphere", rng), 0.02), rgh(make_leaf("plane", rng), 0.1)), 0.002),
+                               (1.3, 0.7, 1.1)))
+    # the roughness of the tree's nodes comes from a stream of its own, seeded after the geometry draws above: whatever the tree
+    # draws, both twins make the same draws in the same order
+    rrng = np.random.default_rng(int(rng.integers(0, 2 ** 62)))
+
+    def every_third(o):
+        pick, v = rrng.random() < 1 / 3, ROUGHNESS[int(rrng.integers(0, 3))]
+        if pick:
+            rgh(o, v)
+    add("rough_tree", rgh(random_csg(rng, 4, visit=every_third), 0.02))
+    add("rough_polytope", rgh(balanced_polytope(rng, visit=lambda k, p: rgh(p, ROUGHNESS[k % 3]) if k % 3 == 0 else None), 0.02))
+    # sphere k of sub-compound g is rough where its bit-identical twin in sub-compound g + groups / 2 is smooth
+    add("rough_compound", tie_compound(rng, visit=lambda g, k, s: rgh(s, ROUGHNESS[k % 3]) if (k + (g >= 4)) % 2 else None))
+    o = make_leaf("sphere", rng)
+    if rough:
+        host.acn_obj_set_surface_roughness(o, -0.01)   # the guard is > 0: no perturbation
+    add("not_rough", o)
+
+    cols = 6
+    for k, o in enumerate(objs):   # a grid, a few units apart
+        host.acn_obj_move(o, A.v3(5.0 * (k % cols) - 12.5, 5.0 * (k // cols) - 7.5, 0.0))
+        sc.push(o)
+        host.acn_obj_discard(o)
+    return sc, roles
+
+
+def nodes_of(flat, i, out=None, scaled=True):
+    """indices of every node in the subtree of node i (i first); scaled=False: not those under a scale wrapper"""
+    out = [] if out is None else out
+    out.append(i)
+    n = flat.node(i)
+    if n.type in (ACN_PAIR_INSIDE, ACN_PAIR_OUTSIDE):
+        nodes_of(flat, n.child0, out, scaled); nodes_of(flat, n.child1, out, scaled)
+    elif n.type == ACN_NEG or (n.type == ACN_SCALE and scaled):
+        nodes_of(flat, n.child0, out, scaled)
+    elif n.type == ACN_COMPOUND:
+        for e in flat.elems_of(i):
+            nodes_of(flat, e, out, scaled)
+    return out
+
+
+def tori_of(flat, i, scaled=True):
+    return [k for k in nodes_of(flat, i, scaled=scaled) if flat.node(k).type == ACN_DISTANCE and flat.node(k).sdf_kind == ACN_SDF_TORUS]
+
+
+def _torus_frame(node):
+    """(pos, rax, inv_scale, r) in longdouble: local = rax ( p - pos ) inv_scale; the local torus has radii 1 and r"""
+    L = np.longdouble
+    return np.array(node.pos[:], dtype=L), rax(node).astype(L), L(node.prm[0]), L(node.prm[1])
+
+
+def _torus_world(node, local):
+    pos, M, inv, r = _torus_frame(node)
+    return pos + (np.asarray(local, dtype=np.longdouble) / inv) @ M
+
+
+def _rays(o, d, label):
+    o = np.asarray(o, dtype=np.float64)
+    d = unit(np.asarray(d, dtype=np.float64))
+    return RaySet().add(np.concatenate([o, d], axis=1), label)
+
+
+def torus_tangent(rng, node, n):
+    """tangent lines of the exact torus (points, normals and tangent directions in longdouble), shifted along the exact
+    normal by k 2^-52 of the torus' size (k in TANGENT_K) and by +-f3_eps and +-10 f3_eps; origins one unit before the tangent
+    point and on it"""
+    L = np.longdouble
+    pos, M, inv, r = _torus_frame(node)
+    rs = RaySet()
+    size = float((1 + r) / inv)
+    for shift in [k * ULP * size for k in TANGENT_K] + [F3_EPS, -F3_EPS, 10 * F3_EPS, -10 * F3_EPS]:
+        u, v = rng.uniform(0, 2 * np.pi, n).astype(L), rng.uniform(0, 2 * np.pi, n).astype(L)
+        P = np.stack([(1 + r * np.cos(v)) * np.cos(u), (1 + r * np.cos(v)) * np.sin(u), r * np.sin(v)], axis=1)
+        N = np.stack([np.cos(v) * np.cos(u), np.cos(v) * np.sin(u), np.sin(v)], axis=1)
+        Tu = np.stack([-np.sin(u), np.cos(u), np.zeros(n, dtype=L)], axis=1)
+        Tv = np.stack([-np.sin(v) * np.cos(u), -np.sin(v) * np.sin(u), np.cos(v)], axis=1)
+        w = rng.uniform(0, 2 * np.pi, n).astype(L)
+        T = Tu * np.cos(w)[:, None] + Tv * np.sin(w)[:, None]
+        Pw, Nw, Tw = _torus_world(node, P), N @ M, T @ M
+        foot = Pw + Nw * L(shift)
+        for t0 in (1.0, 0.0):
+            rs.extend(_rays(foot - Tw * L(t0), Tw, "torus_tangent"))
+    return rs
+
+
+def torus_axis(node):
+    """rays along the local z axis through the centre, both ways and from the centre itself (the f == 0 branch of the torus
+    function); through the centre in the equatorial plane; parallel to the axis through the tube's centre circle"""
+    L = np.longdouble
+    pos, M, inv, r = _torus_frame(node)
+    z = np.array([0, 0, 1], dtype=L)
+    o, d = [], []
+    for s in (1, -1):
+        for t in (3.0, 1.0, 0.25, 0.0, -0.25):
+            o.append(-s * t * z); d.append(s * z)
+    for phi in np.linspace(0, 2 * np.pi, 16, endpoint=False):
+        e = np.array([np.cos(phi), np.sin(phi), 0], dtype=L)
+        for t in (3.0, 0.5, 0.0):
+            o.append(e * t); d.append(-e)
+        for s in (1, -1):
+            o.append(e + s * 3 * z); d.append(-s * z)
+            o.append(e); d.append(s * z)
+    return _rays(_torus_world(node, np.array(o)), np.array(d) @ M, "torus_axis")
+
+
+def torus_inside(rng, node, n):
+    """origins on the tube's centre circle and at random depths inside the tube, random directions: the inside-out branch"""
+    L = np.longdouble
+    pos, M, inv, r = _torus_frame(node)
+    u, v = rng.uniform(0, 2 * np.pi, n).astype(L), rng.uniform(0, 2 * np.pi, n).astype(L)
+    depth = np.where(np.arange(n) % 4 == 0, 0.0, rng.random(n) ** 0.5 * 0.999).astype(L) * r
+    P = np.stack([(1 + depth * np.cos(v)) * np.cos(u), (1 + depth * np.cos(v)) * np.sin(u), depth * np.sin(v)], axis=1)
+    return _rays(_torus_world(node, P), random_dirs(rng, n), "torus_inside")
+
+
+def torus_in_hole(rng, node, n):
+    """origins outside the tube and inside the envelope of the constructor: in the hole, and off the surface along the exact
+    normal by +-f3_eps and +-2 f3_eps (the negative ones just inside); random directions"""
+    L = np.longdouble
+    pos, M, inv, r = _torus_frame(node)
+    h = n // 2
+    rad = (rng.random(h) ** 0.5).astype(L) * (1 - r)
+    phi = rng.uniform(0, 2 * np.pi, h).astype(L)
+    P = np.stack([rad * np.cos(phi), rad * np.sin(phi), rng.uniform(-1, 1, h).astype(L) * r], axis=1)
+    rs = _rays(_torus_world(node, P), random_dirs(rng, h), "torus_in_hole")
+    m = n - h
+    u, v = rng.uniform(0, 2 * np.pi, m).astype(L), rng.uniform(0, 2 * np.pi, m).astype(L)
+    off = np.array([F3_EPS, -F3_EPS, 2 * F3_EPS, -2 * F3_EPS], dtype=L)[np.arange(m) % 4] * inv
+    q = r + off
+    P = np.stack([(1 + q * np.cos(v)) * np.cos(u), (1 + q * np.cos(v)) * np.sin(u), q * np.sin(v)], axis=1)
+    return rs.extend(_rays(_torus_world(node, P), random_dirs(rng, m), "torus_in_hole"))
+
+
+def rough_distance_rays(rng, oracle, flat, e, n=400):
+    """the ray set of root element e of rough_distance_scene (about 1500 rays): uniform, secondary, tangents of the bounding
+    ball and the envelopes, far and envelope origins, and the four torus classes for every torus under e"""
+    node = flat.node(e)
+    c, rad = node_ball(flat, e)
+    if node.type != ACN_SPHERE and not (node.flags & 1):
+        est = oracle.estimate_envelope(flat, e, samples=2000)
+        if np.all(np.isfinite(est)) and 0 < est[3] < 10:
+            c, rad = np.array(est[:3]), est[3]
+    rs = uniform(rng, c, rad, n)
+    a, nor, _ = element_hits(oracle, flat, e, rs.rays)
+    pick = np.flatnonzero(np.isfinite(a))[:60]
+    rs.extend(secondary(rng, oracle, flat, rs.rays[pick], a[pick], nor[pick], n_refract=30))
+    rs.extend(tangent_ball(rng, c, rad, 5))
+    rs.extend(far(rng, c, rad, 60))
+    for ec, er in envelopes_of(flat, e)[:3]:
+        rs.extend(envelope_boundary(rng, ec, er, 5))
+        rs.extend(tangent_ball(rng, ec, er, 3))
+    for t in tori_of(flat, e, scaled=False)[:1]:   # (under a scale wrapper the torus' frame is not the element's)
+        tn = flat.node(t)
+        rs.extend(torus_tangent(rng, tn, 8))
+        rs.extend(torus_axis(tn))
+        rs.extend(torus_inside(rng, tn, 120))
+        rs.extend(torus_in_hole(rng, tn, 120))
+    if node.type == ACN_COMPOUND:   # through leaf centres: the bit-identical twins tie exactly
+        cen = np.array([flat.node(l).pos[:] for l in leaves_of(flat, e)[:64]])
+        d = random_dirs(rng, len(cen))
+        rs.add(np.concatenate([cen - 4 * d, d], axis=1), "ties")
+        rs.add(np.concatenate([cen + 4 * d, -d], axis=1), "ties")
+    return rs
+
+
+def element_hits(oracle, flat, e, rays):
+    """( a, nor, hit object ) of root element e: compound_s_ray_hit for a compound, obj_ray_hit otherwise"""
+    if flat.node(e).type == ACN_COMPOUND:
+        return oracle.compound_ray_hits(flat, e, rays)
+    a, nor = oracle.obj_ray_hits(flat, e, rays)
+    return a, nor, np.full(len(a), e, dtype=np.int64)
+
+
+class RoughDistanceSets:
+    """both scenes flattened, and per role the ray set with the oracle's answers in the rough scene (a, nor, ho) and in the
+    smooth twin (ta, tnor).  Built once per test module; nothing in it is written to afterwards."""
+
+    def __init__(self, oracle, seed=2):
+        self.scene, self.roles = rough_distance_scene(seed, rough=True)
+        self.twin_scene, roles = rough_distance_scene(seed, rough=False)
+        assert roles == self.roles
+        self.flat, self.twin = self.scene.flatten(), self.twin_scene.flatten()
+        self.root = self.flat.c.matter_root
+        self.elems = dict(zip(self.roles, self.flat.elems_of(self.root)))
+        assert len(self.elems) == len(self.roles) and self.flat.c.n_nodes == self.twin.c.n_nodes
+        rng = np.random.default_rng(12)
+        self.sets = {}
+        for role, e in self.elems.items():
+            rs = rough_distance_rays(rng, oracle, self.flat, e)
+            a, nor, ho = element_hits(oracle, self.flat, e, rs.rays)
+            ta, tnor, _ = element_hits(oracle, self.twin, e, rs.rays)
+            for v in (a, nor, ho, ta, tnor, rs.rays):
+                v.setflags(write=False)
+            self.sets[role] = (rs, a, nor, ho, ta, tnor)
+
+    def rough_nodes(self, role):
+        return [k for k in nodes_of(self.flat, self.elems[role]) if self.flat.node(k).surface_roughness > 0]
+
+    def counts(self, a_of=None):
+        """per role: rays, finite hits, and hits and misses of the torus_tangent and torus_inside classes, from distances
+        a_of[ role ] (default: the oracle's)"""
+        out = {}
+        for role, (rs, a, nor, ho, ta, tnor) in self.sets.items():
+            a = a if a_of is None else a_of[role]
+            fin = np.isfinite(a)
+            out[role] = {"rays": len(rs), "hits": int(fin.sum())}
+            for c in ("torus_tangent", "torus_inside"):
+                if (rs.cls == c).any():
+                    out[role][c + "_hits"] = int((fin & (rs.cls == c)).sum())
+                    out[role][c + "_misses"] = int((~fin & (rs.cls == c)).sum())
+        return out
+
+    def check_counts(self, cnt):
+        """the tests are not vacuous: >= 100 finite hits per role (torus_short: >= 10); on the tori that are root elements with
+        200 cycles >= 10 hits and >= 10 misses of torus_tangent rays and >= 100 torus_inside hits; >= 50 rays leave torus_bare
+        with a miss"""
+        for role, c in cnt.items():
+            print("counts", role, c)
+            assert c["hits"] >= (10 if role == "torus_short" else 100), (role, c)
+        for role in ("torus", "torus_bare", "rough_torus"):
+            assert cnt[role]["torus_tangent_hits"] >= 10 and cnt[role]["torus_tangent_misses"] >= 10, (role, cnt[role])
+            assert cnt[role]["torus_inside_hits"] >= 100, (role, cnt[role])
+        assert cnt["torus_bare"]["rays"] - cnt["torus_bare"]["hits"] >= 50
+
+
+def rough_distance_scene_rays(rng, oracle, flat, per=80):
+    """rays for the scene-level queries of rough_distance_scene: around every root element, secondary rays of their hits on
+    the whole root, tangents of the elements' balls, far origins"""
+    root = flat.c.matter_root
+    rs = RaySet()
+    for e in flat.elems_of(root):
+        c, r = node_ball(flat, e, default_r=1.0)
+        rs.extend(uniform(rng, c, 1.5 * min(r, 2.0), per))
+        rs.extend(tangent_ball(rng, c, min(r, 2.0), 2))
+    a, nor, ho = oracle.compound_ray_hits(flat, root, rs.rays)
+    pick = np.flatnonzero(np.isfinite(a))[::3]
+    rs.extend(secondary(rng, oracle, flat, rs.rays[pick], a[pick], nor[pick], n_refract=60))
+    rs.extend(far(rng, np.zeros(3), 8.0, 200))
+    return rs
