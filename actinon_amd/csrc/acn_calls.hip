@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera and its sample statistics, select and key histogram, and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics and its surface records, select and key histogram, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points. */
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include "acn_handle.h"
 #include "acn_stats_host.h"
 #include "acn_select_host.h"
+#include "acn_lenssurf_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* kernels */
@@ -133,6 +134,36 @@ extern "C" int acn_camera_rays( acn_scene_handle* h, const double* pos_xy, size_
 }
 
 /* ---- surface records (k_surface.hip) ---- */
+/* the word that takes ACN_FLAG_STACK_OVERFLOW of the surface kernels (the pipeline's word stays the pipeline's): made on first use */
+static int surface_flags_begin( acn_scene_handle* h, SceneArgs* s )
+{
+    if( !h->d_surface_flags.get() )
+    {
+        if( h->d_surface_flags.grow( sizeof( uint32_t ) ) ) return ACN_ERR_DEVICE;
+        HIP_TRY( hipMemset( h->d_surface_flags.get(), 0, sizeof( uint32_t ) ) );
+    }
+    *s = scene_args( h->dev, h->scene );
+    s->dev.flags = h->d_surface_flags.get();
+    return ACN_OK;
+}
+
+/* the end of a call that launched surface kernels: on the handle's own stream the call waits and reads the word; a caller's stream is
+ * not synchronised for it */
+static int surface_flags_end( acn_scene_handle* h, const Call& c )
+{
+    if( !c.own ) return ACN_OK;
+    uint32_t flags = 0;
+    HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags.get(), sizeof( flags ), hipMemcpyDeviceToHost, c.stream ) );
+    int st = call_end( c );
+    if( st != ACN_OK ) return st;
+    if( flags )
+    {
+        HIP_TRY( hipMemset( h->d_surface_flags.get(), 0, sizeof( uint32_t ) ) );
+        return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow in a surface call" );
+    }
+    return ACN_OK;
+}
+
 static int surface_dev( acn_scene_handle* h, const double* d_rays, const double* d_pos_xy, size_t n, uint32_t mode, double* d_out, Call& c )
 {
     if( !h || ( n && ( !( d_rays || d_pos_xy ) || !d_out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
@@ -141,26 +172,12 @@ static int surface_dev( acn_scene_handle* h, const double* d_rays, const double*
     if( n == 0 ) return ACN_OK;
     int st = call_begin( h, &c );
     if( st != ACN_OK ) return st;
-    if( !h->d_surface_flags.get() )
-    {
-        if( h->d_surface_flags.grow( sizeof( uint32_t ) ) ) return ACN_ERR_DEVICE;
-        HIP_TRY( hipMemset( h->d_surface_flags.get(), 0, sizeof( uint32_t ) ) );
-    }
+    SceneArgs s;
+    if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
     if( d_rays && ( st = check_rays( h, d_rays, n, c.stream ) ) != ACN_OK ) return st;
-    SceneArgs s = scene_args( h->dev, h->scene );
-    s.dev.flags = h->d_surface_flags.get();   /* the pipeline's word stays the pipeline's */
     acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, d_rays, d_pos_xy, n, d_out );
     HIP_TRY( hipGetLastError() );
-    if( !c.own ) return ACN_OK;   /* (a caller's stream is not synchronised for the flags) */
-    uint32_t flags = 0;
-    HIP_TRY( hipMemcpyAsync( &flags, h->d_surface_flags.get(), sizeof( flags ), hipMemcpyDeviceToHost, c.stream ) );
-    if( ( st = call_end( c ) ) != ACN_OK ) return st;
-    if( flags )
-    {
-        HIP_TRY( hipMemset( h->d_surface_flags.get(), 0, sizeof( uint32_t ) ) );
-        return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow in a surface call" );
-    }
-    return ACN_OK;
+    return surface_flags_end( h, c );
 }
 
 extern "C" int acn_surface_rays_dev( acn_scene_handle* h, const void* d_rays, size_t n, uint32_t mode, void* d_out, const acn_render_opts* opts )
@@ -552,6 +569,92 @@ extern "C" int acn_lens_stats_resolve_dev( acn_scene_handle* h, const void* d_st
                               ( double* )d_out_rgb, ( double* )d_out_noise, c.stream );
     HIP_TRY( hipGetLastError() );
     return call_end( c );
+}
+
+/* ---- lens surface records (k_lens_surface.hip; the checks that need no handle: acn_lenssurf_host.h) ---- */
+extern "C" int acn_surface_reduce_dev( acn_scene_handle* h, const void* d_records, size_t n, uint32_t K, void* d_out, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_lenssurf_reduce_check( h != nullptr, d_records, n, K, d_out, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_surface_reduce( ( const double* )d_records, n, K, ( double* )d_out, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_surface_reduce( acn_scene_handle* h, const double* records, size_t n, uint32_t K, double* out, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_lenssurf_reduce_check( h != nullptr, records, n, K, out, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    const size_t rec = sizeof( double ) * ACN_SURF_STRIDE;
+    return host_in_out( h, records, rec * K * n, out, rec * n,
+                        [ & ]( void* d_in, void* d_out ) { return acn_surface_reduce_dev( h, d_in, n, K, d_out, nullptr ); } );
+}
+
+/* a lens surface call after its checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice, cut as render_lens
+ * cuts: rays, the surface kernel of acn_surface_rays (its validity kernel left out: the rays are valid by construction), the reduction */
+static int surface_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, uint32_t mode, double* d_out, Call& c )
+{
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (the members again, and the one check that needs the scene: the focal length) */
+    if( st != ACN_OK || n == 0 ) return st;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    const size_t K = ls.samples;
+    const size_t slice = acn_lenssurf_slice( h->tun.lens_slice_rays, ( uint32_t )K, n );
+    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || h->d_lens_surf.grow( sizeof( double ) * ACN_SURF_STRIDE * slice * K ) ) return ACN_ERR_DEVICE;
+    SceneArgs s;
+    if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
+    for( size_t base = 0; base < n; base += slice )
+    {
+        const size_t cnt = n - base < slice ? n - base : slice;
+        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays.get(), c.stream );
+        HIP_TRY( hipGetLastError() );
+        acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, h->d_lens_rays.get(), nullptr, cnt * K, h->d_lens_surf.get() );
+        HIP_TRY( hipGetLastError() );
+        acn_launch_surface_reduce( h->d_lens_surf.get(), cnt, ( uint32_t )K, d_out + ( size_t )ACN_SURF_STRIDE * base, c.stream );
+        HIP_TRY( hipGetLastError() );
+    }
+    return surface_flags_end( h, c );
+}
+
+extern "C" int acn_surface_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode, void* d_out,
+                                     const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_lens_params p;
+    if( acn_lenssurf_lens_check( h != nullptr, true, d_pos_xy, n, prm, mode, d_out, c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    return surface_lens( h, ( const double* )d_pos_xy, 0, n, prm, mode, ( double* )d_out, c );
+}
+
+extern "C" int acn_surface_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, uint32_t mode, void* d_out,
+                                               const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_lens_params p;
+    if( acn_lenssurf_lens_check( h != nullptr, false, nullptr, count, prm, mode, d_out, c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    int st = pixel_range_check( h, first, count );
+    return st != ACN_OK ? st : surface_lens( h, nullptr, first, count, prm, mode, ( double* )d_out, c );
+}
+
+extern "C" int acn_surface_lens( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode, double* out,
+                                 const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_lens_params p;
+    if( acn_lenssurf_lens_check( h != nullptr, true, pos_xy, n, prm, mode, out, c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made) */
+    if( st != ACN_OK || n == 0 ) return st;
+    return host_in_out( h, pos_xy, sizeof( double ) * 2 * n, out, sizeof( double ) * ACN_SURF_STRIDE * n,
+                        [ & ]( void* d_pos, void* d_out ) { return acn_surface_lens_dev( h, d_pos, n, prm, mode, d_out, nullptr ); } );
 }
 
 /* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */

@@ -326,6 +326,7 @@ struct acn_scene_handle
     DevBuf< double > d_lens_rays;                   /* acn_render_lens*: the rays [ 6 ] of a slice */
     DevBuf< double > d_lens_rad;                    /* ... and their radiance [ 3 ] */
     DevBuf< unsigned long long > d_select_tiles;    /* acn_select_above*: the counts per tile and their total */
+    DevBuf< double > d_lens_surf;                   /* acn_surface_lens*: the surface records [ 16 ] of a slice's rays */
 };
 
 static SceneArgs scene_args( const DevScene& dev, const acn_scene_handle::Resident& r )

@@ -110,6 +110,10 @@ void acn_launch_stats_merge( double* acc, size_t n_acc, const double* part, size
 void acn_launch_stats_resolve( const double* stats, size_t n, const double* background, double gamma, int linear, double* out_rgb,
                                double* out_noise, hipStream_t stream );
 
+/* the aggregate surface record (k_lens_surface.hip; include/actinon_hip.h states it): records [ n ][ samples ][ ACN_SURF_STRIDE ] ->
+ * out [ n ][ ACN_SURF_STRIDE ], both 16-byte aligned, samples 1 .. ACN_LENS_MAX_SAMPLES */
+void acn_launch_surface_reduce( const double* records, size_t n, uint32_t samples, double* out, hipStream_t stream );
+
 /* acn_select_above* and acn_key_histogram* (k_select.hip), after the host's checks (acn_select_host.h); n >= 1.
  * select: three launches -- the count per tile of ACN_SELECT_TILE entries, the exclusive scan of the counts, the scatter (left out
  * when capacity is 0 or both out buffers are null).  tiles: acn_select_tiles( n ) + 1 words of the handle; the last one and

@@ -576,6 +576,49 @@ class Handle:
         check(hip.acn_denoise_stats_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)),
               "acn_denoise_stats_dev")
 
+    # lens surface records (acn_surface_reduce, acn_surface_lens): the K records of a position reduced to one aggregate record
+    def surface_reduce(self, records):
+        """The aggregate record of every position (acn_surface_reduce): records [n,K,16] float64, the surface records of the K rays
+        of each position -> Surface over [n,16]; .coverage is the share of the K samples in the dominant class."""
+        r = np.ascontiguousarray(records, dtype=np.float64)
+        if r.ndim != 3 or r.shape[2] != abi.ACN_SURF_STRIDE:
+            raise ValueError(f"records to reduce are [n,K,{abi.ACN_SURF_STRIDE}] float64, got {r.shape}")
+        out = np.empty((r.shape[0], abi.ACN_SURF_STRIDE), dtype=np.float64)
+        o = self._plain_opts(False, None)
+        check(hip.acn_surface_reduce(self.h, r.ctypes.data, r.shape[0], r.shape[1], out.ctypes.data, C.byref(o)), "acn_surface_reduce")
+        return Surface(out)
+
+    def surface_reduce_dev(self, d_records_ptr, n, samples, d_out_ptr, stream=None):
+        """Device buffers: d_records [n,samples,16], d_out [n,16] float64, 16-byte aligned; enqueued on `stream` without a
+        synchronisation (None: the handle's stream, synchronous)."""
+        o = self._plain_opts(False, stream)
+        check(hip.acn_surface_reduce_dev(self.h, d_records_ptr, n, samples, d_out_ptr, C.byref(o)), "acn_surface_reduce_dev")
+
+    def surface_lens(self, pos_xy, follow=False, lens=None, **params):
+        """The aggregate surface record of the lens rays of every position (acn_surface_lens): pos_xy [n,2] -> Surface.  lens: an
+        abi.LensParams, or its keyword arguments samples, aperture, focus, jitter, seed (Handle.lens_params): with those of a
+        render_lens_stats call the records describe the samples behind its statistics."""
+        p = self._lens(lens, params)
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        out = np.empty((pos.shape[0], abi.ACN_SURF_STRIDE), dtype=np.float64)
+        o = self._plain_opts(False, None)
+        check(hip.acn_surface_lens(self.h, pos.ctypes.data, pos.shape[0], C.byref(p), self._surface_mode(follow), out.ctypes.data,
+                                   C.byref(o)), "acn_surface_lens")
+        return Surface(out)
+
+    def surface_lens_dev(self, d_pos_ptr, n, d_out_ptr, follow=False, stream=None, lens=None, **params):
+        """Device buffers: d_pos [n,2], d_out [n,16] float64, 16-byte aligned."""
+        p = self._lens(lens, params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_surface_lens_dev(self.h, d_pos_ptr, n, C.byref(p), self._surface_mode(follow), d_out_ptr, C.byref(o)),
+              "acn_surface_lens_dev")
+
+    def surface_lens_main_pass_dev(self, first, count, d_out_ptr, follow=False, stream=None, lens=None, **params):
+        p = self._lens(lens, params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_surface_lens_main_pass_dev(self.h, first, count, C.byref(p), self._surface_mode(follow), d_out_ptr, C.byref(o)),
+              "acn_surface_lens_main_pass_dev")
+
     # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
     @staticmethod
     def select_params(threshold, capacity=0, raster_width=0, raster_first=0):
@@ -687,6 +730,7 @@ class Surface:
     kind = property(lambda self: self.raw[:, 12].astype(np.int64))
     hops = property(lambda self: self.raw[:, 13].astype(np.int64))
     weight = property(lambda self: self.raw[:, 14])
+    coverage = property(lambda self: self.raw[:, 15])          # 0 in a pinhole record; the dominant class's share in an aggregate
     hit = property(lambda self: self.raw[:, 0] < np.inf)
 
 

@@ -250,7 +250,7 @@ int acn_camera_rays_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, vo
  *   [ 12 ]      ACN_SURF_* kind bits: the material rules of scene_s_lum (src/scene.c:432-470) for this hit
  *   [ 13 ]      hops followed (0 with ACN_SURF_FIRST_HIT)
  *   [ 14 ]      weight: the product of the shares of the branches followed (1.0 with no hop)
- *   [ 15 ]      0 (reserved)
+ *   [ 15 ]      0; an aggregate record (acn_surface_reduce*, acn_surface_lens*) carries its coverage here, which is > 0
  * A miss has inf, -1, -1 in [ 0 ], [ 7 ], [ 8 ], keeps [ 13 ] and [ 14 ], and is zero elsewhere.
  * mode ACN_SURF_FIRST_HIT reports the first surface.  ACN_SURF_FOLLOW follows the dominant specular branch to the first
  * diffuse or emitting surface -- through a glass to the table behind it.  This is a definition of this library, not a function
@@ -355,8 +355,10 @@ int acn_resolve_dev( acn_scene_handle* h, const void* d_linear_rgb, size_t n, vo
  *                c_out = c + sd / sw: the weighted mean sum( w c' ) / sum( w ), taken about the centre so that a mean of equal
  *                numbers is that number;  var_out = sv / ( sw * sw ).  The levels ping-pong between the two colour buffers.
  * 4 remodulate   out = c * a.
- * A result does not depend on which pixels share a wavefront.  What the filter is for: main-pass frames of few samples.  It is not
- * for gradient-cycle refinements (several sample positions per pixel), and it is biased where a texture edge is not in the albedo. */
+ * A result does not depend on which pixels share a wavefront.  What the filter is for: main-pass frames of few samples.  A pixel
+ * that stands for several rays (lens samples, the positions of a gradient-cycle refinement) has no single pinhole record: reduce the
+ * records of its rays with acn_surface_reduce* (acn_surface_lens* for the lens) and guide with the aggregate.  The filter is biased
+ * where a texture edge is not in the albedo. */
 #define ACN_DENOISE_NO_DEMODULATE     1u
 #define ACN_DENOISE_NORMAL_POWER_SET  2u   /* normal_power_log2 is taken as it stands: without this flag a 0 there means the default */
 #define ACN_DENOISE_DEFAULT_ITERATIONS        5
@@ -514,8 +516,10 @@ int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t cou
  *                So a pixel with one sample borrows the variance of its neighbours, and a pixel with no measured neighbour has
  *                var = 0: it is not smoothed across luminance.
  * ACN_ERR_ARG: what acn_denoise_dev refuses, and a d_stats that is not 16-byte aligned.  out_rgb is [ height * width ][ 3 ], linear.
- * What the call is for: frames of acn_render_lens_stats* with ACN_LENS_JITTER and a closed or small aperture.  With a wide aperture
- * the pinhole surface records do not describe the blurred frame; like acn_denoise it is biased where a texture edge is not in the albedo. */
+ * What the call is for: frames of acn_render_lens_stats*.  With a closed or small aperture the pinhole records of the pixel centres
+ * guide it; with a wide aperture or at anti-aliased silhouettes they do not describe the blurred frame: guide with the aggregate
+ * records of acn_surface_lens* for the same acn_lens_params.  A pixel of coverage 0.55 still carries 45 % of another surface's radiance
+ * and is matched to its dominant class only; like acn_denoise the filter is biased where a texture edge is not in the albedo. */
 #define ACN_STATS_STRIDE 8      /* doubles per record: 64 bytes */
 #define ACN_STATS_NOISE_FLOOR 0.01
 int acn_render_lens_stats_dev          ( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm,
@@ -534,6 +538,62 @@ int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void*
                            const acn_denoise_params* prm /* nullable: defaults */, void* d_out_rgb, const acn_render_opts* opts );
 int acn_denoise_stats    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
+
+/* Lens surface records: the guides of a depth-of-field frame (k_lens_surface.hip).  A pinhole record describes the one ray through
+ * the sample position; at a defocused edge or an anti-aliased silhouette most of the K lens rays of the position meet something
+ * else.  These calls reduce the K surface records of a position to one AGGREGATE record of the same layout (ACN_SURF_STRIDE doubles),
+ * which acn_denoise*, acn_denoise_stats* and every reader of surface records take as it is (the filter reads doubles 0 .. 13 only).
+ * The aggregate is a definition of this library.
+ *
+ * Input: for one position the records r_0 .. r_{K-1}; r_k is what acn_surface_rays writes, in the given mode, for the ray of sample k.
+ * Class of a sample: ( hit, e, x, h ) with hit = r_k[ 0 ] < inf and e, x, h = r_k[ 7 ], r_k[ 8 ], r_k[ 13 ] converted to int32 -- the
+ *   three numbers the filter's MATCH rule compares.  Two samples are of one class iff all four are equal.
+ * Dominant class: the class with the most members; among classes with equally many, the one whose first member has the smallest k.
+ *   Its members are k_1 < k_2 < ... < k_m.
+ * Ordered mean of a quantity q over the members: s = q_{k_1}; s = s + q_{k_2}; ...; mean = s / ( double )m.  IEEE binary64 without
+ *   contraction, IEEE division.  The sum starts at the first member, not at +0.0: with m == 1 the mean is that sample's bits, a -0.0
+ *   included.
+ * The dominant class is a hit:
+ *   [ 0 ]              mean distance
+ *   [ 1 .. 3 ]         mean position, per component
+ *   [ 4 .. 6 ]         m == 1: the sample's exit_nor, bit for bit.  Else g = mean exit_nor per component,
+ *                      q = ( g.x * g.x + g.y * g.y ) + g.z * g.z, and the normal is q > 0 ? g / acn_sqrt( q ) per component : ( 0, 0, 0 )
+ *   [ 7 ], [ 8 ], [ 13 ] e, x, h as doubles
+ *   [ 9 .. 11 ]        mean albedo, per component
+ *   [ 12 ]             the bitwise OR of the members' kind bits ( ( uint32 )r_k[ 12 ] ), as a double
+ *   [ 14 ]             mean weight
+ *   [ 15 ]             coverage ( double )m / ( double )K
+ * The dominant class is a miss: the miss record of acn_surface_rays -- inf, zeros, -1, -1, zeros, kind 0 -- with [ 13 ] = h,
+ *   [ 14 ] = the mean weight of the members and [ 15 ] = the coverage.
+ * So a pinhole record has [ 15 ] == 0 and an aggregate has [ 15 ] > 0; K = 1 without jitter and with aperture 0 is
+ * acn_surface_positions bit for bit in doubles 0 .. 14; and a record depends on its K input records alone, not on which positions
+ * share a wavefront, a workgroup or a slice.  The dominant class is exact for any K and any number of classes.
+ *
+ * acn_surface_reduce*: records [ n ][ K ][ ACN_SURF_STRIDE ] -> out [ n ][ ACN_SURF_STRIDE ], K 1 .. ACN_LENS_MAX_SAMPLES: the reduction
+ * alone, for callers with cameras of their own (acn_surface_rays of stereo, panorama or custom lens rays).
+ * acn_surface_lens*: the K rays of acn_lens_rays for every position (same acn_lens_params: with the same members, seed included, they
+ * are bit for bit the rays acn_render_lens_stats* renders, so the guides describe the samples behind the statistics record), traced as
+ * acn_surface_rays does in `mode`, reduced.  A call is cut into slices of floor( S / K ) positions, at least 1, exactly as
+ * acn_render_lens* (S: ACN_LENS_SLICE_RAYS; it changes no record).  Per slice: the rays into the handle's lens rays buffer, the surface
+ * kernel as it stands into a slice buffer of records, the reduction into the caller's buffer.  The rays are valid by construction: no
+ * validity kernel runs and nothing is read back for one.  The slice buffer of records (128 bytes per ray: 268 MB at the default S) is
+ * the handle's, apart from the render workspace, the denoiser's scratch, the lens buffers and the select counts, grown on demand,
+ * freed by acn_scene_free.  acn_surface_lens_main_pass_dev: the pixel centres [ first, first + count ) of the scene's raster.
+ * Work goes to opts->stream; NULL is the handle's own stream, and then the call waits.  A caller's stream is never synchronised (a
+ * CSG stack overflow is reported as the surface calls report it).  Of opts only `stream` is used.  These calls touch no work queue,
+ * counter or learned rate: renders before and after them are bit-identical and allocate nothing; acn_last_stage_ms,
+ * acn_last_counters and acn_last_kernel_ms do not move, [ 23 ] and [ 24 ] included.
+ * ACN_ERR_ARG, on the host before any launch, acn_last_error set, nothing written: a null handle, or a null buffer with n > 0; K == 0 or
+ * K > 4096 (reduce); everything acn_render_lens* refuses of an acn_lens_params; an unknown mode; shard_world > 1; an in / out buffer
+ * that is not 16-byte aligned; a pixel range outside the image.  n == 0 is ACN_OK with no launch. */
+int acn_surface_reduce_dev( acn_scene_handle* h, const void* d_records, size_t n, uint32_t K, void* d_out, const acn_render_opts* opts );
+int acn_surface_reduce    ( acn_scene_handle* h, const double* records, size_t n, uint32_t K, double* out, const acn_render_opts* opts );
+int acn_surface_lens_dev          ( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
+                                    void* d_out, const acn_render_opts* opts );
+int acn_surface_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, uint32_t mode,
+                                    void* d_out, const acn_render_opts* opts );
+int acn_surface_lens              ( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
+                                    double* out, const acn_render_opts* opts );
 
 /* Selecting positions by a key on the device (k_select.hip): the step between acn_lens_stats_resolve_dev, which leaves a noise
  * figure per pixel in d_out_noise, and acn_render_lens_stats_dev / acn_lens_stats_merge_dev, which take an ordered index list and

@@ -2,7 +2,7 @@
 """A frame of an Actinon scene rendered in passes that go where the frame is still noisy (acn_render_lens_stats, acn_lens_stats_*).
 
     python tools/render_progressive.py SCENE OUT.pnm --samples K --passes P --target-noise T [--denoise] [--noise-map FILE]
-                                       [--select torch|library] [--rays-per-pass B]
+                                       [--select torch|library] [--rays-per-pass B] [--guides pinhole|lens] [--min-coverage C]
                                        [--aperture A --focus D --width W --height H --path-samples P --direct-samples D]
 
 SCENE is an .acn script (the scene of its first create_image) or a flattened scene .npz, as for tools/render_panorama.py.
@@ -21,7 +21,14 @@ by a budget at least as large as their number.
 
 Stopping on the samples' own variance is slightly biased toward dark estimates: a pixel whose first samples happen to come out
 dark and alike looks converged and keeps its dark mean, while one whose samples come out bright is refined.  That is why the
-policy lives here, in a tool a caller can read and change, and not in the library, which supplies the statistics alone."""
+policy lives here, in a tool a caller can read and change, and not in the library, which supplies the statistics alone.
+
+--guides says which surface records guide --denoise.  pinhole (the default): the FOLLOW record of the ray through each pixel centre
+(acn_surface_positions).  lens: the aggregate FOLLOW record of the K lens rays of pass 0 (acn_surface_lens_main_pass_dev with the
+tool's --samples, --aperture, --focus, jitter and seed 0), which at a defocused edge or an anti-aliased silhouette names the surface
+most of the pixel's samples met.  --min-coverage C (with lens guides): a pixel whose dominant class holds less than C of its K
+samples gets distance inf in its record before the filter, so it is copied through and is never a tap; a pixel of coverage 0.55
+still carries 45 % of another surface's radiance, and how much of that a frame tolerates is the caller's decision, like the rest."""
 import argparse
 import os
 import sys
@@ -107,7 +114,7 @@ def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=pr
 
 
 def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0, log=print, *, select_mode="torch", rays_per_pass=None,
-           on_pass=None):
+           on_pass=None, guides="pinhole", min_coverage=0.0):
     """-> the frame [H,W,3] uint8, the records [n,8], the noise [H,W] and the rays of every pass"""
     import torch
     import actinon_amd as A
@@ -121,10 +128,17 @@ def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0
     d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
     sync(dev)
     if denoise:
-        d_pos = torch.from_numpy(A.main_pass_positions(w, hh)).to(dev)
         d_surf = torch.empty((n, A.abi.ACN_SURF_STRIDE), dtype=torch.float64, device=dev)
-        sync(dev)
-        h.surface_positions_dev(d_pos.data_ptr(), n, d_surf.data_ptr(), follow=True)
+        if guides == "lens":
+            sync(dev)
+            h.surface_lens_main_pass_dev(0, n, d_surf.data_ptr(), follow=True, samples=samples, seed=0, jitter=True, aperture=aperture, focus=focus)
+            if min_coverage > 0:
+                d_surf[:, 0] = torch.where(d_surf[:, 15] < min_coverage, torch.full_like(d_surf[:, 0], float("inf")), d_surf[:, 0])
+                sync(dev)
+        else:
+            d_pos = torch.from_numpy(A.main_pass_positions(w, hh)).to(dev)
+            sync(dev)
+            h.surface_positions_dev(d_pos.data_ptr(), n, d_surf.data_ptr(), follow=True)
         h.denoise_stats_dev(d_acc.data_ptr(), d_surf.data_ptr(), w, hh, d_lin.data_ptr())
     else:
         h.lens_stats_resolve_dev(d_acc.data_ptr(), n, d_lin.data_ptr(), None, linear=True)
@@ -147,6 +161,10 @@ def parse_args(argv=None):
                     help="how the pixels of a pass are taken: torch.nonzero, or the library's acn_select_above_dev")
     ap.add_argument("--rays-per-pass", type=int, default=None, metavar="B",
                     help="a pass after the first casts at most B rays, on the noisiest pixels (acn_key_histogram_dev)")
+    ap.add_argument("--guides", choices=("pinhole", "lens"), default="pinhole",
+                    help="the surface records that guide --denoise: of the pixel centres, or the aggregate of the K lens rays (acn_surface_lens)")
+    ap.add_argument("--min-coverage", type=float, default=0.0, metavar="C",
+                    help="with lens guides: a pixel whose coverage is below C is copied through the filter and is never a tap")
     ap.add_argument("--aperture", type=float, default=0.0, help="lens radius in scene units (default 0: a pinhole with jitter)")
     ap.add_argument("--focus", type=float, default=0.0, help="distance of the plane in focus, for an open aperture")
     ap.add_argument("--width", type=int, default=None)
@@ -162,6 +180,8 @@ def parse_args(argv=None):
         ap.error("--target-noise is not negative")
     if args.rays_per_pass is not None and args.rays_per_pass < 0:
         ap.error("--rays-per-pass is not negative")
+    if not 0 <= args.min_coverage <= 1:
+        ap.error("--min-coverage is 0 .. 1")
     if args.aperture < 0 or (args.aperture > 0 and not args.focus > 0):
         ap.error("the aperture is not negative and the focus distance of an open aperture is positive")
     for value in (args.width, args.height, args.path_samples, args.direct_samples):
@@ -182,7 +202,8 @@ def main(argv=None):
     if prm.image_width < 1 or prm.image_height < 2:
         sys.exit("the image needs a width of at least 1 and a height of at least 2")
     out8, records, noise, rays = render(flat, args.samples, args.passes, args.target_noise, denoise=args.denoise,
-                                        aperture=args.aperture, focus=args.focus, select_mode=args.select, rays_per_pass=args.rays_per_pass)
+                                        aperture=args.aperture, focus=args.focus, select_mode=args.select, rays_per_pass=args.rays_per_pass,
+                                        guides=args.guides, min_coverage=args.min_coverage)
     write_pnm(args.out, np.ascontiguousarray(out8))
     if args.noise_map:
         with open(args.noise_map, "wb") as f:
