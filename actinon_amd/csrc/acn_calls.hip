@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera, its sample statistics and its surface records, select and key histogram, and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points. */
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include "acn_stats_host.h"
 #include "acn_select_host.h"
 #include "acn_lenssurf_host.h"
+#include "acn_layers_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* kernels */
@@ -655,6 +656,165 @@ extern "C" int acn_surface_lens( acn_scene_handle* h, const double* pos_xy, size
     if( st != ACN_OK || n == 0 ) return st;
     return host_in_out( h, pos_xy, sizeof( double ) * 2 * n, out, sizeof( double ) * ACN_SURF_STRIDE * n,
                         [ & ]( void* d_pos, void* d_out ) { return acn_surface_lens_dev( h, d_pos, n, prm, mode, d_out, nullptr ); } );
+}
+
+/* ---- layered lens records and their filter (k_lens_layers.hip, k_denoise_layers.hip; the checks that need no handle: acn_layers_host.h) ---- */
+extern "C" int acn_lens_layers_reduce_dev( acn_scene_handle* h, const void* d_records, const void* d_radiance, size_t n, uint32_t K, void* d_out_surface,
+                                           void* d_out_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_layers_reduce_check( h != nullptr, d_records, d_radiance, n, K, d_out_surface, d_out_stats, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_lens_layers( ( const double* )d_records, ( const double* )d_radiance, n, K, ( double* )d_out_surface, n, ( double* )d_out_stats, n, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_lens_layers_reduce( acn_scene_handle* h, const double* records, const double* radiance, size_t n, uint32_t K, double* out_surface,
+                                       double* out_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_layers_reduce_check( h != nullptr, records, radiance, n, K, out_surface, out_stats, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t surf_bytes = sizeof( double ) * ACN_SURF_STRIDE * 2 * n, stats_bytes = sizeof( double ) * ACN_STATS_STRIDE * 3 * n;
+    DevCopies dc;
+    void* d_rec = dc.make( records, sizeof( double ) * ACN_SURF_STRIDE * K * n );
+    void* d_rad = dc.make( radiance, sizeof( double ) * 3 * K * n );
+    void* d_surf = dc.make( nullptr, surf_bytes );
+    void* d_st = dc.make( nullptr, stats_bytes );
+    if( !d_rec || !d_rad || !d_surf || !d_st ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    int st = acn_lens_layers_reduce_dev( h, d_rec, d_rad, n, K, d_surf, d_st, nullptr );
+    if( st == ACN_OK ) st = DevCopies::fetch( out_surface, d_surf, surf_bytes );
+    return st != ACN_OK ? st : DevCopies::fetch( out_stats, d_st, stats_bytes );
+}
+
+/* a layered lens call after its checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice, cut as render_lens
+ * cuts: the rays once, the ray path of render_lens, the surface kernel of surface_lens, the split into the caller's planes [ . ][ n ] */
+static int render_lens_layers( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, uint32_t mode,
+                               double* d_out_rgb, double* d_out_surface, double* d_out_stats, Call& c )
+{
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (the members again, and the one check that needs the scene: the focal length) */
+    if( st != ACN_OK ) return st;
+    const acn_render_opts& o = c.opts;
+    const int linear = ( o.flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0;
+    if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+    if( n == 0 ) return ACN_OK;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    const size_t K = ls.samples;
+    const size_t slice = acn_lenssurf_slice( h->tun.lens_slice_rays, ( uint32_t )K, n );
+    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || h->d_lens_rad.grow( sizeof( double ) * 3 * slice * K ) ||
+        h->d_lens_surf.grow( sizeof( double ) * ACN_SURF_STRIDE * slice * K ) ) return ACN_ERR_DEVICE;
+    SceneArgs s;
+    if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
+    acn_render_opts ray_opts = o;
+    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
+    for( size_t base = 0; base < n; base += slice )
+    {
+        if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+        const size_t cnt = n - base < slice ? n - base : slice;
+        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays.get(), c.stream );
+        HIP_TRY( hipGetLastError() );
+        st = render_dispatch( h, primary_rays( h->d_lens_rays.get() ), cnt * K, h->d_lens_rad.get(), &ray_opts, c.stream );
+        if( st != ACN_OK ) return st;
+        acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, h->d_lens_rays.get(), nullptr, cnt * K, h->d_lens_surf.get() );
+        HIP_TRY( hipGetLastError() );
+        if( d_out_rgb ) acn_launch_lens_reduce( h->d_lens_rad.get(), cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
+        acn_launch_lens_layers( h->d_lens_surf.get(), h->d_lens_rad.get(), cnt, ( uint32_t )K, d_out_surface + ( size_t )ACN_SURF_STRIDE * base, n,
+                                d_out_stats + ( size_t )ACN_STATS_STRIDE * base, n, c.stream );
+        HIP_TRY( hipGetLastError() );
+    }
+    return surface_flags_end( h, c );
+}
+
+extern "C" int acn_render_lens_layers_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
+                                           void* d_out_rgb, void* d_out_surface, void* d_out_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_lens_params p;
+    if( acn_layers_lens_check( h != nullptr, true, d_pos_xy, n, prm, mode, d_out_surface, d_out_stats, c.opts.shard_mode, c.opts.shard_rank,
+                               c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    return render_lens_layers( h, ( const double* )d_pos_xy, 0, n, prm, mode, ( double* )d_out_rgb, ( double* )d_out_surface, ( double* )d_out_stats, c );
+}
+
+extern "C" int acn_render_lens_layers_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, uint32_t mode,
+                                                     void* d_out_rgb, void* d_out_surface, void* d_out_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_lens_params p;
+    if( acn_layers_lens_check( h != nullptr, false, nullptr, count, prm, mode, d_out_surface, d_out_stats, c.opts.shard_mode, c.opts.shard_rank,
+                               c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    int st = pixel_range_check( h, first, count );
+    return st != ACN_OK ? st : render_lens_layers( h, nullptr, first, count, prm, mode, ( double* )d_out_rgb, ( double* )d_out_surface, ( double* )d_out_stats, c );
+}
+
+extern "C" int acn_render_lens_layers( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode, double* out_rgb,
+                                       double* out_surface, double* out_stats, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_lens_params p;
+    if( acn_layers_lens_check( h != nullptr, true, pos_xy, n, prm, mode, out_surface, out_stats, c.opts.shard_mode, c.opts.shard_rank, c.opts.shard_world,
+                               &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    LensSetup ls;
+    int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made) */
+    if( st != ACN_OK || n == 0 ) return st;
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t surf_bytes = sizeof( double ) * ACN_SURF_STRIDE * 2 * n, stats_bytes = sizeof( double ) * ACN_STATS_STRIDE * 3 * n;
+    DevCopies dc;
+    void* d_pos = dc.make( pos_xy, sizeof( double ) * 2 * n );
+    void* d_rgb = out_rgb ? dc.make( nullptr, sizeof( double ) * 3 * n ) : nullptr;
+    void* d_surf = dc.make( nullptr, surf_bytes );
+    void* d_st = dc.make( nullptr, stats_bytes );
+    if( !d_pos || !d_surf || !d_st || ( out_rgb && !d_rgb ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    c.opts.stream = nullptr;
+    st = acn_render_lens_layers_dev( h, d_pos, n, prm, mode, d_rgb, d_surf, d_st, &c.opts );
+    if( st == ACN_OK && out_rgb ) st = DevCopies::fetch( out_rgb, d_rgb, sizeof( double ) * 3 * n );
+    if( st == ACN_OK ) st = DevCopies::fetch( out_surface, d_surf, surf_bytes );
+    return st != ACN_OK ? st : DevCopies::fetch( out_stats, d_st, stats_bytes );
+}
+
+extern "C" int acn_denoise_layers_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                                       const acn_denoise_params* prm, void* d_out_rgb, const acn_render_opts* opts )
+{
+    Call c( opts );
+    DenoiseSetup su;
+    int st = denoise_check( h, d_stats, d_surface, width, height, prm, d_out_rgb, c.opts, &su );
+    if( st != ACN_OK ) return st;
+    std::string msg;
+    if( acn_layers_denoise_check( d_stats, d_surface, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    if( h->d_denoise.grow( width * height * ( size_t )ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL ) ) return ACN_ERR_DEVICE;
+    acn_launch_denoise_layers( ( const double* )d_stats, ( const double* )d_surface, width, height, su.iterations, su.normal_power_log2, su.no_demodulate,
+                               su.sigma_plane, su.sigma_lum, h->dev.prm.background_color, h->d_denoise.get(), ( double* )d_out_rgb, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_denoise_layers( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                                   const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
+{
+    Call c( opts );
+    DenoiseSetup su;
+    int st = denoise_check( h, stats, surface, width, height, prm, out_rgb, c.opts, &su );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipSetDevice( h->device ) );
+    const size_t n = width * height, rgb_bytes = sizeof( double ) * 3 * n;
+    DevCopies dc;
+    void* d_st = dc.make( stats, sizeof( double ) * ACN_STATS_STRIDE * 3 * n );
+    void* d_surf = dc.make( surface, sizeof( double ) * ACN_SURF_STRIDE * 2 * n );
+    void* d_rgb = dc.make( nullptr, rgb_bytes );
+    if( !d_st || !d_surf || !d_rgb ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    c.opts.stream = nullptr;
+    st = acn_denoise_layers_dev( h, d_st, d_surf, width, height, prm, d_rgb, &c.opts );
+    return st != ACN_OK ? st : DevCopies::fetch( out_rgb, d_rgb, rgb_bytes );
 }
 
 /* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */

@@ -322,7 +322,7 @@ struct acn_scene_handle
     DevBuf< double > d_shard_pos;                   /* acn_render_main_pass_shard_dev: the rank's positions */
     DevBuf< unsigned long long > d_ray_check;       /* acn_render_rays_dev: the lowest index of a refused ray */
     DevBuf< uint32_t > d_surface_flags;             /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
-    DevBuf< void > d_denoise;                       /* acn_denoise: guides and colour buffers, apart from the render workspace */
+    DevBuf< void > d_denoise;                       /* acn_denoise*, acn_denoise_layers*: guides and colour buffers, apart from the render workspace */
     DevBuf< double > d_lens_rays;                   /* acn_render_lens*: the rays [ 6 ] of a slice */
     DevBuf< double > d_lens_rad;                    /* ... and their radiance [ 3 ] */
     DevBuf< unsigned long long > d_select_tiles;    /* acn_select_above*: the counts per tile and their total */

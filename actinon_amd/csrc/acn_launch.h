@@ -114,6 +114,20 @@ void acn_launch_stats_resolve( const double* stats, size_t n, const double* back
  * out [ n ][ ACN_SURF_STRIDE ], both 16-byte aligned, samples 1 .. ACN_LENS_MAX_SAMPLES */
 void acn_launch_surface_reduce( const double* records, size_t n, uint32_t samples, double* out, hipStream_t stream );
 
+/* the layered records (k_lens_layers.hip; include/actinon_hip.h states them): records [ n ][ samples ][ ACN_SURF_STRIDE ] and rad
+ * [ n ][ samples ][ 3 ] -> plane l of out_surface at out_surface + l * surface_plane * ACN_SURF_STRIDE (l = 0, 1) and plane l of
+ * out_stats at out_stats + l * stats_plane * ACN_STATS_STRIDE (l = 0, 1, 2: layer 0, layer 1, rest); the planes are counted in
+ * positions, so a slice of a larger call writes into the caller's planes.  records and both outputs 16-byte aligned */
+void acn_launch_lens_layers( const double* records, const double* rad, size_t n, uint32_t samples, double* out_surface, size_t surface_plane,
+                             double* out_stats, size_t stats_plane, hipStream_t stream );
+
+/* the filter of acn_denoise_layers (k_denoise_layers.hip): stats [ 3 ][ n ][ ACN_STATS_STRIDE ], surf [ 2 ][ n ][ ACN_SURF_STRIDE ], both 16-byte
+ * aligned; the parameters are final values; scratch: ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL bytes per pixel, 128-byte aligned */
+#define ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL 256
+void acn_launch_denoise_layers( const double* stats, const double* surf, size_t width, size_t height, uint32_t iterations, uint32_t normal_power_log2,
+                                uint32_t no_demodulate, double sigma_plane, double sigma_lum, const double* background, void* scratch,
+                                double* out_rgb, hipStream_t stream );
+
 /* acn_select_above* and acn_key_histogram* (k_select.hip), after the host's checks (acn_select_host.h); n >= 1.
  * select: three launches -- the count per tile of ACN_SELECT_TILE entries, the exclusive scan of the counts, the scatter (left out
  * when capacity is 0 or both out buffers are null).  tiles: acn_select_tiles( n ) + 1 words of the handle; the last one and

@@ -20,26 +20,7 @@
  *   prefilter      3 x 3 window on the guide keys and var_raw, in the arrangement of `variance`. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
-
-#define DN_TILE 16
-
-struct DnKey { int32_t enter, exit, hops, ok; };   /* ok: the pixel is filterable */
-
-__device__ static inline bool dn_finite( double x ) { return ( acn_f64_bits( x ) & 0x7FF0000000000000ull ) != 0x7FF0000000000000ull; }
-__device__ static inline double dn_lum( double x, double y, double z ) { return ( 0.2126 * x + 0.7152 * y ) + 0.0722 * z; }
-__device__ static inline double dn_dot( double ax, double ay, double az, double bx, double by, double bz ) { return ( ax * bx + ay * by ) + az * bz; }
-__device__ static inline double dn_k( int t ) { return t == 2 ? 0.375 : ( ( t & 1 ) ? 0.25 : 0.0625 ); }
-__device__ static inline double dn_albedo( double v, uint32_t no_demodulate ) { return ( !no_demodulate && v > 0.01 ) ? v : 1.0; }
-
-/* the pixel of this lane; false: outside the image */
-__device__ static inline bool dn_pixel( size_t width, size_t height, size_t tiles_x, size_t* x, size_t* y )
-{
-    const size_t tile = blockIdx.x;
-    const size_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
-    *x = tx * DN_TILE + ( threadIdx.x & ( DN_TILE - 1 ) );
-    *y = ty * DN_TILE + ( threadIdx.x / DN_TILE );
-    return *x < width && *y < height;
-}
+#include "acn_denoise_dev.h"
 
 __global__ __launch_bounds__( 256 )
 void k_dn_prepare( const double* __restrict__ lin, const double* __restrict__ surf, size_t n, uint32_t no_demodulate,
@@ -63,20 +44,6 @@ void k_dn_prepare( const double* __restrict__ lin, const double* __restrict__ su
     g[ 3 ] = kv.d;
     pix[ 2 * i ]     = make_double2( cx, cy );
     pix[ 2 * i + 1 ] = make_double2( cz, 0.0 );
-}
-
-__device__ static inline DnKey dn_key( const double2* __restrict__ guide, size_t p )
-{
-    union { DnKey k; double2 d; } kv; kv.d = guide[ 4 * p + 3 ];
-    return kv.k;
-}
-
-/* the in-image pixel ( x + dx, y + dy ), or the centre p with *in = false */
-__device__ static inline size_t dn_tap( size_t x, size_t y, long long dx, long long dy, size_t width, size_t height, size_t p, bool* in )
-{
-    const long long qx = ( long long )x + dx, qy = ( long long )y + dy;
-    *in = qx >= 0 && qx < ( long long )width && qy >= 0 && qy < ( long long )height;
-    return *in ? ( size_t )qy * width + ( size_t )qx : p;
 }
 
 __global__ __launch_bounds__( 256 )

@@ -23,6 +23,7 @@
  * four workgroups per compute unit; the kernel runs no CSG machine and takes no dynamic LDS. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
+#include "acn_surfclass.h"
 
 #define SURF_TILE_POS 16
 #define SURF_TILE_K   16
@@ -32,18 +33,6 @@
 
 /* positions of one launch: a multiple of the tile, far below the grid limit of 2^31 - 1 workgroups */
 #define SURF_REDUCE_LAUNCH_POS ( ( size_t )1 << 30 )
-
-/* the class of a sample as two words: ( e, x ) and ( h, hit ) */
-struct SurfKey { uint64_t ex, hh; };
-
-__device__ static inline SurfKey surf_key( const double* r )
-{
-    SurfKey key;
-    const uint32_t e = ( uint32_t )( int32_t )r[ 7 ], x = ( uint32_t )( int32_t )r[ 8 ], h = ( uint32_t )( int32_t )r[ 13 ];
-    key.ex = ( ( uint64_t )e << 32 ) | x;
-    key.hh = ( ( uint64_t )h << 1 ) | ( r[ 0 ] < __builtin_inf() ? 1u : 0u );
-    return key;
-}
 
 __global__ __launch_bounds__( 256 )
 void k_surface_reduce( const double2* __restrict__ records, size_t n, uint32_t K, double2* __restrict__ out )

@@ -619,6 +619,93 @@ class Handle:
         check(hip.acn_surface_lens_main_pass_dev(self.h, first, count, C.byref(p), self._surface_mode(follow), d_out_ptr, C.byref(o)),
               "acn_surface_lens_main_pass_dev")
 
+    # layered lens records (acn_lens_layers_reduce, acn_render_lens_layers, acn_denoise_layers): the two largest classes of a
+    # position's samples as records of their own, planar: surface [2,n,16] (layer 0, layer 1), statistics [3,n,8] (layer 0, layer 1, rest)
+    def lens_layers_reduce(self, records, radiance):
+        """The split alone (acn_lens_layers_reduce): records [n,K,16] and linear radiance [n,K,3] of the K rays of each position ->
+        ( [Surface, Surface], [LensStats, LensStats, LensStats] ): layer 0, layer 1 and, of the statistics, the rest."""
+        r = np.ascontiguousarray(records, dtype=np.float64)
+        L = np.ascontiguousarray(radiance, dtype=np.float64)
+        if r.ndim != 3 or r.shape[2] != abi.ACN_SURF_STRIDE or L.shape != r.shape[:2] + (3,):
+            raise ValueError(f"layers are split from records [n,K,{abi.ACN_SURF_STRIDE}] and radiance [n,K,3], got {r.shape} and {L.shape}")
+        n = r.shape[0]
+        surf = np.empty((abi.ACN_LAYERS_SURFACE_PLANES, n, abi.ACN_SURF_STRIDE), dtype=np.float64)
+        st = np.empty((abi.ACN_LAYERS_STATS_PLANES, n, abi.ACN_STATS_STRIDE), dtype=np.float64)
+        o = self._plain_opts(False, None)
+        check(hip.acn_lens_layers_reduce(self.h, r.ctypes.data, L.ctypes.data, n, r.shape[1], surf.ctypes.data, st.ctypes.data, C.byref(o)),
+              "acn_lens_layers_reduce")
+        return [Surface(p) for p in surf], [LensStats(p, self) for p in st]
+
+    def lens_layers_reduce_dev(self, d_records_ptr, d_radiance_ptr, n, samples, d_out_surface_ptr, d_out_stats_ptr, stream=None):
+        """Device buffers: d_records [n,samples,16], d_radiance [n,samples,3], d_out_surface [2,n,16], d_out_stats [3,n,8] float64,
+        the records 16-byte aligned; enqueued on `stream` without a synchronisation (None: the handle's stream, synchronous)."""
+        o = self._plain_opts(False, stream)
+        check(hip.acn_lens_layers_reduce_dev(self.h, d_records_ptr, d_radiance_ptr, n, samples, d_out_surface_ptr, d_out_stats_ptr, C.byref(o)),
+              "acn_lens_layers_reduce_dev")
+
+    def render_lens_layers(self, pos_xy, follow=False, linear=False, lens=None, **params):
+        """render_lens and the layered records of every position (acn_render_lens_layers): pos_xy [n,2] -> ( rgb [n,3] float64 as
+        render_lens gives it, [Surface, Surface], [LensStats, LensStats, LensStats] ).  lens: an abi.LensParams, or its keyword
+        arguments samples, aperture, focus, jitter, seed (Handle.lens_params)."""
+        p = self._lens(lens, params)
+        pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+        n = pos.shape[0]
+        out = np.empty((n, 3), dtype=np.float64)
+        surf = np.empty((abi.ACN_LAYERS_SURFACE_PLANES, n, abi.ACN_SURF_STRIDE), dtype=np.float64)
+        st = np.empty((abi.ACN_LAYERS_STATS_PLANES, n, abi.ACN_STATS_STRIDE), dtype=np.float64)
+        o = self._opts(linear, None)
+        check(hip.acn_render_lens_layers(self.h, pos.ctypes.data, n, C.byref(p), self._surface_mode(follow), out.ctypes.data, surf.ctypes.data,
+                                         st.ctypes.data, C.byref(o)), "acn_render_lens_layers")
+        return out, [Surface(q) for q in surf], [LensStats(q, self) for q in st]
+
+    def render_lens_layers_dev(self, d_pos_ptr, n, d_out_ptr, d_out_surface_ptr, d_out_stats_ptr, follow=False, linear=False, stream=None,
+                               lens=None, **params):
+        """Device buffers: d_pos [n,2], d_out [n,3] or None, d_out_surface [2,n,16], d_out_stats [3,n,8] float64, 16-byte aligned."""
+        p = self._lens(lens, params)
+        o = self._opts(linear, stream)
+        check(hip.acn_render_lens_layers_dev(self.h, d_pos_ptr, n, C.byref(p), self._surface_mode(follow), d_out_ptr, d_out_surface_ptr,
+                                             d_out_stats_ptr, C.byref(o)), "acn_render_lens_layers_dev")
+
+    def render_lens_layers_main_pass_dev(self, first, count, d_out_ptr, d_out_surface_ptr, d_out_stats_ptr, follow=False, linear=False,
+                                         stream=None, lens=None, **params):
+        p = self._lens(lens, params)
+        o = self._opts(linear, stream)
+        check(hip.acn_render_lens_layers_main_pass_dev(self.h, first, count, C.byref(p), self._surface_mode(follow), d_out_ptr,
+                                                       d_out_surface_ptr, d_out_stats_ptr, C.byref(o)), "acn_render_lens_layers_main_pass_dev")
+
+    @staticmethod
+    def _planes(records, cls, planes, stride):
+        """[planes,n,stride] float64 of a list of Surface / LensStats or of an array"""
+        if isinstance(records, (list, tuple)):
+            records = [r.raw if isinstance(r, cls) else r for r in records]
+        raw = np.ascontiguousarray(records, dtype=np.float64)
+        if raw.ndim != 3 or raw.shape[0] != planes or raw.shape[2] != stride:
+            raise ValueError(f"layered records are [{planes},n,{stride}] float64, got {raw.shape}")
+        return raw
+
+    def denoise_layers(self, stats, surface, width, height, **params):
+        """The layered filter (acn_denoise_layers): stats the three LensStats (or [3,h*w,8]) and surface the two Surface (or
+        [2,h*w,16]) of a frame's pixels, as render_lens_layers gives them -> [h,w,3] float64, linear.  params: as for denoise."""
+        raw = self._planes(stats, LensStats, abi.ACN_LAYERS_STATS_PLANES, abi.ACN_STATS_STRIDE)
+        srf = self._planes(surface, Surface, abi.ACN_LAYERS_SURFACE_PLANES, abi.ACN_SURF_STRIDE)
+        n = int(width) * int(height)
+        if raw.shape[1] != n or srf.shape[1] != n:
+            raise ValueError(f"{height}x{width} pixels need {n} records per plane, got {raw.shape} and {srf.shape}")
+        out = np.empty((int(height), int(width), 3), dtype=np.float64)
+        p = self.denoise_params(**params)
+        o = self._plain_opts(False, None)
+        check(hip.acn_denoise_layers(self.h, raw.ctypes.data, srf.ctypes.data, width, height, C.byref(p), out.ctypes.data, C.byref(o)),
+              "acn_denoise_layers")
+        return out
+
+    def denoise_layers_dev(self, d_stats_ptr, d_surface_ptr, width, height, d_out_ptr, stream=None, **params):
+        """Device buffers: d_stats [3,h*w,8], d_surface [2,h*w,16], d_out [h*w,3] float64; enqueued on `stream` without a
+        synchronisation (None: the handle's stream, synchronous)."""
+        p = self.denoise_params(**params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_denoise_layers_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)),
+              "acn_denoise_layers_dev")
+
     # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
     @staticmethod
     def select_params(threshold, capacity=0, raster_width=0, raster_first=0):

@@ -519,7 +519,8 @@ int acn_render_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t cou
  * What the call is for: frames of acn_render_lens_stats*.  With a closed or small aperture the pinhole records of the pixel centres
  * guide it; with a wide aperture or at anti-aliased silhouettes they do not describe the blurred frame: guide with the aggregate
  * records of acn_surface_lens* for the same acn_lens_params.  A pixel of coverage 0.55 still carries 45 % of another surface's radiance
- * and is matched to its dominant class only; like acn_denoise the filter is biased where a texture edge is not in the albedo. */
+ * and is matched to its dominant class only (acn_render_lens_layers* and acn_denoise_layers*, below, keep the two surfaces apart); like
+ * acn_denoise the filter is biased where a texture edge is not in the albedo. */
 #define ACN_STATS_STRIDE 8      /* doubles per record: 64 bytes */
 #define ACN_STATS_NOISE_FLOOR 0.01
 int acn_render_lens_stats_dev          ( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm,
@@ -594,6 +595,93 @@ int acn_surface_lens_main_pass_dev( acn_scene_handle* h, size_t first, size_t co
                                     void* d_out, const acn_render_opts* opts );
 int acn_surface_lens              ( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
                                     double* out, const acn_render_opts* opts );
+
+/* Layered lens records: the two largest surfaces of a position kept apart (k_lens_layers.hip), and the filter that takes each as a
+ * sample of the picture of its own (k_denoise_layers.hip).  An aggregate record describes the dominant class of the K lens samples
+ * only, and the statistics record beside it mixes the radiances of all classes: at a defocused edge the filter then carries the
+ * minority surface's radiance into the dominant surface's neighbours.  These calls split the K samples of a position by class, give
+ * every part its own statistics record and the two largest parts their own surface record, filter the two layers as
+ * acn_denoise_stats filters a frame and put the pixel together again.  All of it is a definition of this library.
+ * Everything is IEEE binary64 without contraction, a / b is IEEE division, a sum a + b + c is ( a + b ) + c, sqrt and exp are acn_sqrt
+ * and acn_exp of csrc/acn_detmath.h.  Where a result is a NaN, which NaN it is (sign, payload) is not defined.
+ *
+ * The split.  Input, for one position: the surface records r_0 .. r_{K-1} as acn_surface_rays writes them in `mode` and the linear
+ * radiances L_0 .. L_{K-1} as acn_render_rays returns them with ACN_OPT_LINEAR_OUT, both for the ray of sample k.
+ *   Class of a sample: ( hit, e, x, h ), the class of acn_surface_reduce*.
+ *   LAYER 0: the dominant class over all K samples by the rule of acn_surface_reduce*: the most members, among classes with equally
+ *     many the one whose first member has the smallest k.
+ *   LAYER 1: the dominant class, by the same rule, over the samples that are not in layer 0; absent if there are none.
+ *   REST: every other sample.  The member counts m0 + m1 + mr = K.  The split is exact for any K <= 4096 and any number of classes.
+ *   Surface record of a layer (ACN_SURF_STRIDE doubles): the aggregate record of acn_surface_reduce* taken over the layer's members
+ *     alone -- every ordered mean over its members k_1 < k_2 < ..., starting at the first -- with [ 15 ] = ( double )m_l / ( double )K.
+ *     Plane 0 is therefore acn_surface_reduce* of the same records bit for bit, in all 16 doubles.  An absent layer 1 is the miss
+ *     record (inf in [ 0 ], -1 in [ 7 ] and [ 8 ], zeros elsewhere) with [ 13 ] = [ 14 ] = [ 15 ] = 0: its coverage 0 tells it from a layer.
+ *   Statistics record of a layer or of the rest (ACN_STATS_STRIDE doubles), over its m members k_1 < k_2 < ...:
+ *     n      = m
+ *     mean.c = ( ( ( 0.0 + L_{k_1}.c ) + L_{k_2}.c ) + ... ) / ( double )m
+ *     m2.c   = ( ( 0.0 + d * d ) + ... ),  d = L_k.c - mean.c, a second pass over the members in the order of k
+ *     [ 7 ]  = 0.         No members: eight zeros, an EMPTY record.
+ *     A position whose K samples are of one class has, in plane 0, the bits of the record acn_render_lens_stats* writes.
+ *   Layout, planar -- every plane is a frame the existing calls take as it is (acn_denoise_stats of plane 0 of both, for one):
+ *     out_surface [ ACN_LAYERS_SURFACE_PLANES = 2 ][ n ][ ACN_SURF_STRIDE ]    layer 0, layer 1
+ *     out_stats   [ ACN_LAYERS_STATS_PLANES = 3 ][ n ][ ACN_STATS_STRIDE ]     layer 0, layer 1, rest
+ *   A record depends on the K records and radiances of its position alone: not on which positions share a wavefront, a workgroup or
+ *   a slice.  No sum is split across lanes.
+ * acn_lens_layers_reduce*: records [ n ][ K ][ ACN_SURF_STRIDE ], radiance [ n ][ K ][ 3 ] -> the planes: the split alone, for callers with
+ *   cameras of their own.  Of opts only `stream` is used (NULL: the handle's own, and then the call waits; a caller's stream is never
+ *   synchronised).  ACN_ERR_ARG, on the host before any launch, acn_last_error set, nothing written: a null handle, or a null buffer
+ *   with n > 0; K == 0 or K > 4096; shard_world > 1; records or an out buffer not 16-byte aligned, radiance not 8-byte aligned.
+ *   n == 0 is ACN_OK with no launch.
+ * acn_render_lens_layers*: per slice of floor( S / K ) positions, cut exactly as acn_render_lens* cut (S: ACN_LENS_SLICE_RAYS): the rays
+ *   of acn_lens_rays once into the handle's lens rays buffer; rendered by the ray path of acn_render_lens_stats* into the handle's
+ *   radiance buffer; traced by the surface kernel as acn_surface_lens* does, in `mode`, into the handle's slice buffer of records;
+ *   split into the caller's planes.  No buffer is added to the handle.  d_out_rgb (nullable) is bit for bit what acn_render_lens*
+ *   writes (saturated, or linear with ACN_OPT_LINEAR_OUT); the records are always linear.  acn_render_lens_layers_main_pass_dev: the
+ *   pixel centres [ first, first + count ) of the scene's raster.  Streams, cancel, flags, acn_last_stage_ms, acn_last_counters and
+ *   acn_last_kernel_ms (the render of the LAST slice) are those of acn_render_lens_stats*; a CSG stack overflow of the surface kernel
+ *   is reported as acn_surface_lens* report it.  ACN_ERR_ARG, on the host before anything is written, acn_last_error set: everything
+ *   acn_render_lens_stats* and acn_surface_lens* refuse -- a null handle or (n > 0) a null pos_xy, out_surface or out_stats; the
+ *   acn_lens_params; an unknown mode; an unknown shard_mode; ACN_SHARD_SAMPLES with shard_world > 1; pos_xy or an out plane buffer not
+ *   16-byte aligned; a pixel range outside the image.
+ *
+ * acn_denoise_layers*: stats [ 3 ][ width * height ][ ACN_STATS_STRIDE ], surface [ 2 ][ width * height ][ ACN_SURF_STRIDE ] as above ->
+ *   out_rgb [ width * height ][ 3 ], linear.  The parameters, the stream rules and the argument checks are those of acn_denoise_stats*
+ *   (both input buffers 16-byte aligned).  The scratch is 256 bytes per pixel (per layer a guide of 64 bytes and two colour buffers of
+ *   32): the handle's denoise scratch, grown on demand, apart from everything a render sees.  For each pixel p and layer l in { 0, 1 }:
+ *   1, 2        as in acn_denoise_stats on ( stats[ l ][ p ], surface[ l ][ p ] ): a, c = mean / a, FILTERABLE (an EMPTY record is
+ *               not), the MATCH key, N, P and var_raw.
+ *   CANDIDATE   of tap pixel q for the centre ( p, l ): at q == p layer l itself; else the lowest l' in { 0, 1 } for which ( q, l' ) is
+ *               FILTERABLE and MATCHes ( p, l ); if there is none the tap is skipped.  So the surface a pixel sees as its minority
+ *               finds the neighbours that see it as their majority.
+ *   2, 3        the 3 x 3 variance prefilter and the a-trous levels of acn_denoise_stats, unchanged in every expression, with "pixel
+ *               q" read as the candidate of q: its c', var', N', P' and var_raw' come from that layer's buffers of the same level.
+ *               Both layers advance level by level together.
+ *   4           a filterable layer gives F_l = c * a; a layer that is not filterable and not EMPTY gives F_l = mean, bit for bit.
+ *   COMPOSITE   n_l = [ 0 ] of a record, 0 for an EMPTY one;  K_p = ( n0 + n1 ) + nr.  The terms, in the order layer 0, layer 1, rest:
+ *               ( n0 / K_p ) * F_0.c,  ( n1 / K_p ) * F_1.c,  ( nr / K_p ) * mean_r.c.  An EMPTY record contributes no term; the sum
+ *               starts at the first term present and adds the others in order; three EMPTY records give the scene's
+ *               background_color, linear.  The rest is never filtered: it has no single guide.
+ *   With plane 1 and the rest EMPTY everywhere the call is therefore acn_denoise_stats( stats plane 0, surface plane 0 ) bit for bit.
+ * acn_lens_layers_reduce* and acn_denoise_layers* touch no work queue, counter or learned rate: renders before and after them are
+ * bit-identical, acn_last_stage_ms ([ 23 ], [ 24 ] included), acn_last_counters and acn_last_kernel_ms do not move.
+ * Out of scope: merging layered records across passes -- acn_lens_stats_merge* has no notion of which class a layer of either pass
+ * is -- and with it tools/render_progressive.py on layers; acn_denoise_stats of a single plane stays what that tool uses. */
+#define ACN_LAYERS_SURFACE_PLANES 2   /* out_surface: layer 0, layer 1 */
+#define ACN_LAYERS_STATS_PLANES   3   /* out_stats: layer 0, layer 1, rest */
+int acn_lens_layers_reduce_dev( acn_scene_handle* h, const void* d_records, const void* d_radiance, size_t n, uint32_t K, void* d_out_surface,
+                                void* d_out_stats, const acn_render_opts* opts );
+int acn_lens_layers_reduce    ( acn_scene_handle* h, const double* records, const double* radiance, size_t n, uint32_t K, double* out_surface,
+                                double* out_stats, const acn_render_opts* opts );
+int acn_render_lens_layers_dev          ( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
+                                          void* d_out_rgb /* nullable */, void* d_out_surface, void* d_out_stats, const acn_render_opts* opts );
+int acn_render_lens_layers_main_pass_dev( acn_scene_handle* h, size_t first, size_t count, const acn_lens_params* prm, uint32_t mode,
+                                          void* d_out_rgb /* nullable */, void* d_out_surface, void* d_out_stats, const acn_render_opts* opts );
+int acn_render_lens_layers              ( acn_scene_handle* h, const double* pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
+                                          double* out_rgb /* nullable */, double* out_surface, double* out_stats, const acn_render_opts* opts );
+int acn_denoise_layers_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                            const acn_denoise_params* prm /* nullable: defaults */, void* d_out_rgb, const acn_render_opts* opts );
+int acn_denoise_layers    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
 
 /* Selecting positions by a key on the device (k_select.hip): the step between acn_lens_stats_resolve_dev, which leaves a noise
  * figure per pixel in d_out_noise, and acn_render_lens_stats_dev / acn_lens_stats_merge_dev, which take an ordered index list and
