@@ -1,7 +1,8 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
  * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
- * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points. */
+ * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points.
+ * The lens calls that cut their positions into slices share one loop, lens_slices; a host-buffer form is a HostCall (acn_handle.h). */
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
@@ -165,14 +166,19 @@ static int surface_flags_end( acn_scene_handle* h, const Call& c )
     return ACN_OK;
 }
 
+static int surface_mode_check( uint32_t mode, const acn_render_opts& opts )
+{
+    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
+    if( opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
+    return ACN_OK;
+}
+
 static int surface_dev( acn_scene_handle* h, const double* d_rays, const double* d_pos_xy, size_t n, uint32_t mode, double* d_out, Call& c )
 {
     if( !h || ( n && ( !( d_rays || d_pos_xy ) || !d_out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
-    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
-    if( n == 0 ) return ACN_OK;
-    int st = call_begin( h, &c );
-    if( st != ACN_OK ) return st;
+    int st = surface_mode_check( mode, c.opts );
+    if( st != ACN_OK || n == 0 ) return st;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
     SceneArgs s;
     if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
     if( d_rays && ( st = check_rays( h, d_rays, n, c.stream ) ) != ACN_OK ) return st;
@@ -200,9 +206,8 @@ static int surface_host( acn_scene_handle* h, const double* in, size_t in_len, s
 {
     Call c( opts );
     if( !h || ( n && ( !in || !out ) ) ) return fail( ACN_ERR_ARG, "null argument" );
-    if( mode != ACN_SURF_FIRST_HIT && mode != ACN_SURF_FOLLOW ) return fail( ACN_ERR_ARG, "unknown surface mode " + std::to_string( mode ) );
-    if( c.opts.shard_world > 1 ) return fail( ACN_ERR_ARG, "a surface call is not sharded: slice the array" );
-    if( n == 0 ) return ACN_OK;
+    const int st = surface_mode_check( mode, c.opts );
+    if( st != ACN_OK || n == 0 ) return st;
     c.opts.stream = nullptr;
     return host_in_out( h, in, sizeof( double ) * in_len * n, out, sizeof( double ) * ACN_SURF_STRIDE * n, [ & ]( void* d_in, void* d_out )
     {
@@ -302,16 +307,13 @@ static int denoise_host( acn_scene_handle* h, const double* in, const double* su
     DenoiseSetup su;
     int st = denoise_check( h, in, surface, width, height, prm, out_rgb, c.opts, &su );
     if( st != ACN_OK ) return st;
-    HIP_TRY( hipSetDevice( h->device ) );
     const size_t n = width * height, rgb_bytes = sizeof( double ) * 3 * n;
-    DevCopies dc;
-    void* d_in = dc.make( in, from_stats ? sizeof( double ) * ACN_STATS_STRIDE * n : rgb_bytes );
-    void* d_surf = dc.make( surface, sizeof( double ) * ACN_SURF_STRIDE * n );
-    void* d_rgb = from_stats ? dc.make( nullptr, rgb_bytes ) : d_in;
-    if( !d_in || !d_surf || !d_rgb ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    HostCall hc( h );
+    void* d_in = from_stats ? hc.in( in, sizeof( double ) * ACN_STATS_STRIDE * n ) : hc.inout( in, out_rgb, rgb_bytes );
+    void* d_surf = hc.in( surface, sizeof( double ) * ACN_SURF_STRIDE * n );
+    void* d_rgb = from_stats ? hc.out( out_rgb, rgb_bytes ) : d_in;
     c.opts.stream = nullptr;
-    st = denoise_dev( h, d_in, d_surf, width, height, prm, d_rgb, c, from_stats );
-    return st != ACN_OK ? st : DevCopies::fetch( out_rgb, d_rgb, rgb_bytes );
+    return hc.run( [ & ] { return denoise_dev( h, d_in, d_surf, width, height, prm, d_rgb, c, from_stats ); } );
 }
 
 extern "C" int acn_denoise_dev( acn_scene_handle* h, const void* d_linear_rgb, const void* d_surface, size_t width, size_t height,
@@ -400,8 +402,51 @@ extern "C" int acn_lens_rays( acn_scene_handle* h, const double* pos_xy, size_t 
     } );
 }
 
-/* a lens call after its null checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice: rays, the ray path of
- * acn_render_rays_dev (linear, its validity kernel left out: the rays are valid by construction), the ordered mean */
+/* The slice loop of every lens call, after the call's checks and with n > 0: d_pos_xy, or null for the pixel centres from `first` on.
+ * A slice is acn_lenssurf_slice positions; its rays go into the handle's slice buffers once, and from them come the per-ray products
+ * the call wants: the radiance, by the ray path of acn_render_rays_dev (linear; its validity kernel left out: the rays are valid by
+ * construction), the surface records, by the surface kernel of acn_surface_rays (likewise), or both.  reduce( base, cnt, d_rad, d_surf )
+ * launches the call's reduction(s) of positions [ base, base + cnt ) on c.stream; a product not wanted is null.  Cancel is polled iff
+ * the slice renders: a call for records alone reads only `stream` of its options. */
+struct LensProducts { bool radiance, surface; uint32_t mode; };   /* mode: of the surface records */
+
+template< class Reduce >
+static int lens_slices( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const LensSetup& ls, Call& c, LensProducts want, Reduce reduce )
+{
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    const uint32_t K = ls.samples;
+    const size_t slice = acn_lenssurf_slice( h->tun.lens_slice_rays, K, n );
+    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || ( want.radiance && h->d_lens_rad.grow( sizeof( double ) * 3 * slice * K ) ) ||
+        ( want.surface && h->d_lens_surf.grow( sizeof( double ) * ACN_SURF_STRIDE * slice * K ) ) ) return ACN_ERR_DEVICE;
+    double* const d_rays = h->d_lens_rays.get();
+    double* const d_rad = want.radiance ? h->d_lens_rad.get() : nullptr;
+    double* const d_surf = want.surface ? h->d_lens_surf.get() : nullptr;
+    SceneArgs s;
+    if( want.surface && ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
+    acn_render_opts ray_opts = c.opts;
+    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
+    for( size_t base = 0; base < n; base += slice )
+    {
+        if( want.radiance && c.opts.cancel && *c.opts.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
+        const size_t cnt = n - base < slice ? n - base : slice;
+        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, K, d_rays, c.stream );
+        HIP_TRY( hipGetLastError() );
+        if( want.radiance && ( st = render_dispatch( h, primary_rays( d_rays ), cnt * K, d_rad, &ray_opts, c.stream ) ) != ACN_OK ) return st;
+        if( want.surface )
+        {
+            acn_launch_surface( want.mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, d_rays, nullptr, cnt * K, d_surf );
+            HIP_TRY( hipGetLastError() );
+        }
+        reduce( base, cnt, d_rad, d_surf );
+        HIP_TRY( hipGetLastError() );
+    }
+    return want.surface ? surface_flags_end( h, c ) : call_end( c );
+}
+
+static int lens_stats_by_samples() { return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" ); }
+
+/* a lens call after its null checks: the ordered mean of each position's radiances, with_stats their statistics records beside it */
 static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, double* d_out_rgb,
                         Call& c, double* d_stats = nullptr, bool with_stats = false )
 {
@@ -414,35 +459,19 @@ static int render_lens( acn_scene_handle* h, const double* d_pos_xy, size_t firs
     if( o.shard_mode == ACN_SHARD_SAMPLES && o.shard_world > 1 )
     {
         if( o.shard_rank >= o.shard_world ) return fail( ACN_ERR_ARG, "shard_rank >= shard_world" );
-        if( with_stats ) return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
+        if( with_stats ) return lens_stats_by_samples();
         if( !linear ) return fail( ACN_ERR_ARG, "a lens call sharded by samples gives partial means: it needs ACN_OPT_LINEAR_OUT" );
     }
     if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
     if( n == 0 ) return ACN_OK;
-    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
-    const size_t K = ls.samples;
-    size_t slice = h->tun.lens_slice_rays / K;
-    if( slice < 1 ) slice = 1;
-    if( slice > n ) slice = n;
-    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || h->d_lens_rad.grow( sizeof( double ) * 3 * slice * K ) ) return ACN_ERR_DEVICE;
-    acn_render_opts ray_opts = o;
-    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
-    for( size_t base = 0; base < n; base += slice )
+    return lens_slices( h, d_pos_xy, first, n, ls, c, { true, false, 0 }, [ & ]( size_t base, size_t cnt, const double* d_rad, const double* )
     {
-        if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
-        const size_t cnt = n - base < slice ? n - base : slice;
-        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays.get(), c.stream );
-        HIP_TRY( hipGetLastError() );
-        st = render_dispatch( h, primary_rays( h->d_lens_rays.get() ), cnt * K, h->d_lens_rad.get(), &ray_opts, c.stream );
-        if( st != ACN_OK ) return st;
         if( with_stats )
-            acn_launch_lens_reduce_stats( h->d_lens_rad.get(), cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
+            acn_launch_lens_reduce_stats( d_rad, cnt, ls.samples, h->dev.prm.gamma, linear, d_out_rgb ? d_out_rgb + 3 * base : nullptr,
                                           d_stats + ( size_t )ACN_STATS_STRIDE * base, c.stream );
         else
-            acn_launch_lens_reduce( h->d_lens_rad.get(), cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
-        HIP_TRY( hipGetLastError() );
-    }
-    return call_end( c );
+            acn_launch_lens_reduce( d_rad, cnt, ls.samples, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
+    } );
 }
 
 extern "C" int acn_render_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, void* d_out_rgb,
@@ -503,19 +532,14 @@ extern "C" int acn_render_lens_stats( acn_scene_handle* h, const double* pos_xy,
     LensSetup ls;
     int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made; the device call checks the rest before it writes) */
     if( st != ACN_OK ) return st;
-    if( c.opts.shard_mode == ACN_SHARD_SAMPLES && c.opts.shard_world > 1 )
-        return fail( ACN_ERR_ARG, "lens statistics are not sharded by samples (ACN_SHARD_SAMPLES): deviations of partial radiances mean nothing" );
+    if( c.opts.shard_mode == ACN_SHARD_SAMPLES && c.opts.shard_world > 1 ) return lens_stats_by_samples();
     if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    DevCopies dc;
-    void* d_pos = dc.make( pos_xy, sizeof( double ) * 2 * n );
-    void* d_out = out_rgb ? dc.make( nullptr, sizeof( double ) * 3 * n ) : nullptr;
-    void* d_st = dc.make( nullptr, sizeof( double ) * ACN_STATS_STRIDE * n );
-    if( !d_pos || !d_st || ( out_rgb && !d_out ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    HostCall hc( h );
+    void* d_pos = hc.in( pos_xy, sizeof( double ) * 2 * n );
+    void* d_out = hc.out( out_rgb, sizeof( double ) * 3 * n );
+    void* d_st = hc.out( stats, sizeof( double ) * ACN_STATS_STRIDE * n );
     c.opts.stream = nullptr;
-    st = acn_render_lens_stats_dev( h, d_pos, n, prm, d_out, d_st, &c.opts );
-    if( st == ACN_OK && out_rgb ) st = DevCopies::fetch( out_rgb, d_out, sizeof( double ) * 3 * n );
-    return st != ACN_OK ? st : DevCopies::fetch( stats, d_st, sizeof( double ) * ACN_STATS_STRIDE * n );
+    return hc.run( [ & ] { return acn_render_lens_stats_dev( h, d_pos, n, prm, d_out, d_st, &c.opts ); } );
 }
 
 extern "C" int acn_lens_stats_merge_dev( acn_scene_handle* h, void* d_acc, size_t n_acc, const void* d_part, size_t n_part,
@@ -544,16 +568,13 @@ extern "C" int acn_lens_stats_merge( acn_scene_handle* h, double* acc, size_t n_
     std::string msg;
     if( acn_stats_index_check( index, n_part, n_acc, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
     if( n_part == 0 || n_acc == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    DevCopies dc;
     const size_t rec = sizeof( double ) * ACN_STATS_STRIDE;
-    void* d_acc = dc.make( acc, rec * n_acc );
-    void* d_part = dc.make( part, rec * n_part );
-    void* d_index = index ? dc.make( index, sizeof( int64_t ) * n_part ) : nullptr;
-    if( !d_acc || !d_part || ( index && !d_index ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    HostCall hc( h );
+    void* d_acc = hc.inout( acc, acc, rec * n_acc );
+    void* d_part = hc.in( part, rec * n_part );
+    void* d_index = index ? hc.in( index, sizeof( int64_t ) * n_part ) : nullptr;
     c.opts.stream = nullptr;
-    int st = acn_lens_stats_merge_dev( h, d_acc, n_acc, d_part, n_part, ( const int64_t* )d_index, &c.opts );
-    return st != ACN_OK ? st : DevCopies::fetch( acc, d_acc, rec * n_acc );
+    return hc.run( [ & ] { return acn_lens_stats_merge_dev( h, d_acc, n_acc, d_part, n_part, ( const int64_t* )d_index, &c.opts ); } );
 }
 
 extern "C" int acn_lens_stats_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb, void* d_out_noise,
@@ -597,30 +618,16 @@ extern "C" int acn_surface_reduce( acn_scene_handle* h, const double* records, s
                         [ & ]( void* d_in, void* d_out ) { return acn_surface_reduce_dev( h, d_in, n, K, d_out, nullptr ); } );
 }
 
-/* a lens surface call after its checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice, cut as render_lens
- * cuts: rays, the surface kernel of acn_surface_rays (its validity kernel left out: the rays are valid by construction), the reduction */
+/* a lens surface call after its checks: the aggregate record of each position's records */
 static int surface_lens( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, uint32_t mode, double* d_out, Call& c )
 {
     LensSetup ls;
     int st = lens_check( h, prm, nullptr, &ls );   /* (the members again, and the one check that needs the scene: the focal length) */
     if( st != ACN_OK || n == 0 ) return st;
-    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
-    const size_t K = ls.samples;
-    const size_t slice = acn_lenssurf_slice( h->tun.lens_slice_rays, ( uint32_t )K, n );
-    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || h->d_lens_surf.grow( sizeof( double ) * ACN_SURF_STRIDE * slice * K ) ) return ACN_ERR_DEVICE;
-    SceneArgs s;
-    if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
-    for( size_t base = 0; base < n; base += slice )
+    return lens_slices( h, d_pos_xy, first, n, ls, c, { false, true, mode }, [ & ]( size_t base, size_t cnt, const double*, const double* d_surf )
     {
-        const size_t cnt = n - base < slice ? n - base : slice;
-        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays.get(), c.stream );
-        HIP_TRY( hipGetLastError() );
-        acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, h->d_lens_rays.get(), nullptr, cnt * K, h->d_lens_surf.get() );
-        HIP_TRY( hipGetLastError() );
-        acn_launch_surface_reduce( h->d_lens_surf.get(), cnt, ( uint32_t )K, d_out + ( size_t )ACN_SURF_STRIDE * base, c.stream );
-        HIP_TRY( hipGetLastError() );
-    }
-    return surface_flags_end( h, c );
+        acn_launch_surface_reduce( d_surf, cnt, ls.samples, d_out + ( size_t )ACN_SURF_STRIDE * base, c.stream );
+    } );
 }
 
 extern "C" int acn_surface_lens_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode, void* d_out,
@@ -680,21 +687,16 @@ extern "C" int acn_lens_layers_reduce( acn_scene_handle* h, const double* record
     std::string msg;
     if( acn_layers_reduce_check( h != nullptr, records, radiance, n, K, out_surface, out_stats, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
     if( n == 0 ) return ACN_OK;
-    HIP_TRY( hipSetDevice( h->device ) );
-    const size_t surf_bytes = sizeof( double ) * ACN_SURF_STRIDE * 2 * n, stats_bytes = sizeof( double ) * ACN_STATS_STRIDE * 3 * n;
-    DevCopies dc;
-    void* d_rec = dc.make( records, sizeof( double ) * ACN_SURF_STRIDE * K * n );
-    void* d_rad = dc.make( radiance, sizeof( double ) * 3 * K * n );
-    void* d_surf = dc.make( nullptr, surf_bytes );
-    void* d_st = dc.make( nullptr, stats_bytes );
-    if( !d_rec || !d_rad || !d_surf || !d_st ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    int st = acn_lens_layers_reduce_dev( h, d_rec, d_rad, n, K, d_surf, d_st, nullptr );
-    if( st == ACN_OK ) st = DevCopies::fetch( out_surface, d_surf, surf_bytes );
-    return st != ACN_OK ? st : DevCopies::fetch( out_stats, d_st, stats_bytes );
+    HostCall hc( h );
+    void* d_rec = hc.in( records, sizeof( double ) * ACN_SURF_STRIDE * K * n );
+    void* d_rad = hc.in( radiance, sizeof( double ) * 3 * K * n );
+    void* d_surf = hc.out( out_surface, sizeof( double ) * ACN_SURF_STRIDE * 2 * n );
+    void* d_st = hc.out( out_stats, sizeof( double ) * ACN_STATS_STRIDE * 3 * n );
+    return hc.run( [ & ] { return acn_lens_layers_reduce_dev( h, d_rec, d_rad, n, K, d_surf, d_st, nullptr ); } );
 }
 
-/* a layered lens call after its checks: d_pos_xy, or null for the pixel centres from `first` on.  Slice by slice, cut as render_lens
- * cuts: the rays once, the ray path of render_lens, the surface kernel of surface_lens, the split into the caller's planes [ . ][ n ] */
+/* a layered lens call after its checks: the ordered mean of render_lens (if d_out_rgb) and the split of each position's records and
+ * radiances into the caller's planes [ . ][ n ] */
 static int render_lens_layers( acn_scene_handle* h, const double* d_pos_xy, size_t first, size_t n, const acn_lens_params* prm, uint32_t mode,
                                double* d_out_rgb, double* d_out_surface, double* d_out_stats, Call& c )
 {
@@ -705,31 +707,12 @@ static int render_lens_layers( acn_scene_handle* h, const double* d_pos_xy, size
     const int linear = ( o.flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0;
     if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
     if( n == 0 ) return ACN_OK;
-    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
-    const size_t K = ls.samples;
-    const size_t slice = acn_lenssurf_slice( h->tun.lens_slice_rays, ( uint32_t )K, n );
-    if( h->d_lens_rays.grow( sizeof( double ) * 6 * slice * K ) || h->d_lens_rad.grow( sizeof( double ) * 3 * slice * K ) ||
-        h->d_lens_surf.grow( sizeof( double ) * ACN_SURF_STRIDE * slice * K ) ) return ACN_ERR_DEVICE;
-    SceneArgs s;
-    if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
-    acn_render_opts ray_opts = o;
-    ray_opts.flags |= ACN_OPT_LINEAR_OUT;
-    for( size_t base = 0; base < n; base += slice )
+    return lens_slices( h, d_pos_xy, first, n, ls, c, { true, true, mode }, [ & ]( size_t base, size_t cnt, const double* d_rad, const double* d_surf )
     {
-        if( o.cancel && *o.cancel ) return fail( ACN_ERR_CANCELLED, "cancelled" );
-        const size_t cnt = n - base < slice ? n - base : slice;
-        acn_launch_lens_rays( h->dev, d_pos_xy ? d_pos_xy + 2 * base : nullptr, first + base, cnt, ls, 0, ( uint32_t )K, h->d_lens_rays.get(), c.stream );
-        HIP_TRY( hipGetLastError() );
-        st = render_dispatch( h, primary_rays( h->d_lens_rays.get() ), cnt * K, h->d_lens_rad.get(), &ray_opts, c.stream );
-        if( st != ACN_OK ) return st;
-        acn_launch_surface( mode, h->scene.lds_bytes != 0, machine_lds_bytes( h->scene ), c.stream, s, h->d_lens_rays.get(), nullptr, cnt * K, h->d_lens_surf.get() );
-        HIP_TRY( hipGetLastError() );
-        if( d_out_rgb ) acn_launch_lens_reduce( h->d_lens_rad.get(), cnt, ( uint32_t )K, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
-        acn_launch_lens_layers( h->d_lens_surf.get(), h->d_lens_rad.get(), cnt, ( uint32_t )K, d_out_surface + ( size_t )ACN_SURF_STRIDE * base, n,
+        if( d_out_rgb ) acn_launch_lens_reduce( d_rad, cnt, ls.samples, h->dev.prm.gamma, linear, d_out_rgb + 3 * base, c.stream );
+        acn_launch_lens_layers( d_surf, d_rad, cnt, ls.samples, d_out_surface + ( size_t )ACN_SURF_STRIDE * base, n,
                                 d_out_stats + ( size_t )ACN_STATS_STRIDE * base, n, c.stream );
-        HIP_TRY( hipGetLastError() );
-    }
-    return surface_flags_end( h, c );
+    } );
 }
 
 extern "C" int acn_render_lens_layers_dev( acn_scene_handle* h, const void* d_pos_xy, size_t n, const acn_lens_params* prm, uint32_t mode,
@@ -766,19 +749,13 @@ extern "C" int acn_render_lens_layers( acn_scene_handle* h, const double* pos_xy
     LensSetup ls;
     int st = lens_check( h, prm, nullptr, &ls );   /* (before the buffers are made) */
     if( st != ACN_OK || n == 0 ) return st;
-    HIP_TRY( hipSetDevice( h->device ) );
-    const size_t surf_bytes = sizeof( double ) * ACN_SURF_STRIDE * 2 * n, stats_bytes = sizeof( double ) * ACN_STATS_STRIDE * 3 * n;
-    DevCopies dc;
-    void* d_pos = dc.make( pos_xy, sizeof( double ) * 2 * n );
-    void* d_rgb = out_rgb ? dc.make( nullptr, sizeof( double ) * 3 * n ) : nullptr;
-    void* d_surf = dc.make( nullptr, surf_bytes );
-    void* d_st = dc.make( nullptr, stats_bytes );
-    if( !d_pos || !d_surf || !d_st || ( out_rgb && !d_rgb ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    HostCall hc( h );
+    void* d_pos = hc.in( pos_xy, sizeof( double ) * 2 * n );
+    void* d_rgb = hc.out( out_rgb, sizeof( double ) * 3 * n );
+    void* d_surf = hc.out( out_surface, sizeof( double ) * ACN_SURF_STRIDE * 2 * n );
+    void* d_st = hc.out( out_stats, sizeof( double ) * ACN_STATS_STRIDE * 3 * n );
     c.opts.stream = nullptr;
-    st = acn_render_lens_layers_dev( h, d_pos, n, prm, mode, d_rgb, d_surf, d_st, &c.opts );
-    if( st == ACN_OK && out_rgb ) st = DevCopies::fetch( out_rgb, d_rgb, sizeof( double ) * 3 * n );
-    if( st == ACN_OK ) st = DevCopies::fetch( out_surface, d_surf, surf_bytes );
-    return st != ACN_OK ? st : DevCopies::fetch( out_stats, d_st, stats_bytes );
+    return hc.run( [ & ] { return acn_render_lens_layers_dev( h, d_pos, n, prm, mode, d_rgb, d_surf, d_st, &c.opts ); } );
 }
 
 extern "C" int acn_denoise_layers_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
@@ -805,16 +782,13 @@ extern "C" int acn_denoise_layers( acn_scene_handle* h, const double* stats, con
     DenoiseSetup su;
     int st = denoise_check( h, stats, surface, width, height, prm, out_rgb, c.opts, &su );
     if( st != ACN_OK ) return st;
-    HIP_TRY( hipSetDevice( h->device ) );
-    const size_t n = width * height, rgb_bytes = sizeof( double ) * 3 * n;
-    DevCopies dc;
-    void* d_st = dc.make( stats, sizeof( double ) * ACN_STATS_STRIDE * 3 * n );
-    void* d_surf = dc.make( surface, sizeof( double ) * ACN_SURF_STRIDE * 2 * n );
-    void* d_rgb = dc.make( nullptr, rgb_bytes );
-    if( !d_st || !d_surf || !d_rgb ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    const size_t n = width * height;
+    HostCall hc( h );
+    void* d_st = hc.in( stats, sizeof( double ) * ACN_STATS_STRIDE * 3 * n );
+    void* d_surf = hc.in( surface, sizeof( double ) * ACN_SURF_STRIDE * 2 * n );
+    void* d_rgb = hc.out( out_rgb, sizeof( double ) * 3 * n );
     c.opts.stream = nullptr;
-    st = acn_denoise_layers_dev( h, d_st, d_surf, width, height, prm, d_rgb, &c.opts );
-    return st != ACN_OK ? st : DevCopies::fetch( out_rgb, d_rgb, rgb_bytes );
+    return hc.run( [ & ] { return acn_denoise_layers_dev( h, d_st, d_surf, width, height, prm, d_rgb, &c.opts ); } );
 }
 
 /* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */

@@ -323,10 +323,10 @@ struct acn_scene_handle
     DevBuf< unsigned long long > d_ray_check;       /* acn_render_rays_dev: the lowest index of a refused ray */
     DevBuf< uint32_t > d_surface_flags;             /* acn_surface_*: the ACN_FLAG_* word of the surface kernels (not the pipeline's) */
     DevBuf< void > d_denoise;                       /* acn_denoise*, acn_denoise_layers*: guides and colour buffers, apart from the render workspace */
-    DevBuf< double > d_lens_rays;                   /* acn_render_lens*: the rays [ 6 ] of a slice */
-    DevBuf< double > d_lens_rad;                    /* ... and their radiance [ 3 ] */
+    DevBuf< double > d_lens_rays;                   /* the slice buffers of the lens driver (lens_slices, acn_calls.hip): the rays [ 6 ] of a slice, */
+    DevBuf< double > d_lens_rad;                    /* ... their radiance [ 3 ], grown by the calls that render, */
+    DevBuf< double > d_lens_surf;                   /* ... and their surface records [ 16 ], grown by the calls that take records */
     DevBuf< unsigned long long > d_select_tiles;    /* acn_select_above*: the counts per tile and their total */
-    DevBuf< double > d_lens_surf;                   /* acn_surface_lens*: the surface records [ 16 ] of a slice's rays */
 };
 
 static SceneArgs scene_args( const DevScene& dev, const acn_scene_handle::Resident& r )
@@ -373,7 +373,7 @@ int render_dispatch( acn_scene_handle* h, const Primary& prim, size_t n, double*
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* The frame of one C ABI call.  The options are viewed when the frame is made, so every argument check reads them before the
  * device is touched; call_begin sets the device and picks the stream, call_end synchronises the stream iff it is the handle's own.
- * A host-buffer form sets opts.stream = nullptr before it hands the frame (or its opts) on: it is synchronous. */
+ * A host-buffer form (HostCall, below) sets opts.stream = nullptr before it hands the frame (or its opts) on: it is synchronous. */
 struct Call
 {
     acn_render_opts opts;           /* the caller's options as opts_of views them: there is no null to test for */
@@ -439,18 +439,42 @@ struct DevCopies
     }
 };
 
-/* the plainest host-buffer form: one array copied in, the device-buffer call `dev( d_in, d_out )` on the handle's own stream, one
- * array copied out */
+/* The host-buffer form of a call: after its checks an entry point declares its arrays here, takes the device pointers and runs its
+ * device-buffer form on the handle's own stream (opts.stream = nullptr: synchronous).  The device is set before the first allocation; a
+ * buffer that cannot be made fails the form once, before anything is launched; the outputs come back in declaration order, after ACN_OK */
+struct HostCall
+{
+    struct Out { void* dst; const void* d; size_t bytes; };
+    DevCopies dc;
+    std::vector< Out > outs;
+    int st;
+    explicit HostCall( const acn_scene_handle* h ) : st( [ h ]() -> int { HIP_TRY( hipSetDevice( h->device ) ); return ACN_OK; }() ) {}
+    /* a buffer that src (nullable) is copied into and dst (nullable) takes the content of; in and out are the two halves */
+    void* inout( const void* src, void* dst, size_t bytes )
+    {
+        void* d = st == ACN_OK ? dc.make( src, bytes ) : nullptr;
+        if( d && dst ) outs.push_back( { dst, d, bytes } );
+        if( !d && st == ACN_OK ) st = fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+        return d;
+    }
+    void* in( const void* src, size_t bytes ) { return inout( src, nullptr, bytes ); }
+    void* out( void* dst, size_t bytes ) { return dst ? inout( nullptr, dst, bytes ) : nullptr; }   /* a null dst: nothing made, nothing fetched */
+    template< class DevCall > int run( DevCall dev )
+    {
+        if( st != ACN_OK || ( st = dev() ) != ACN_OK ) return st;
+        for( const Out& o : outs ) if( ( st = DevCopies::fetch( o.dst, o.d, o.bytes ) ) != ACN_OK ) return st;
+        return ACN_OK;
+    }
+};
+
+/* the plainest of them: one array copied in, the device-buffer call `dev( d_in, d_out )`, one array copied out */
 template< class DevCall >
 static int host_in_out( acn_scene_handle* h, const void* in, size_t in_bytes, void* out, size_t out_bytes, DevCall dev )
 {
-    HIP_TRY( hipSetDevice( h->device ) );
-    DevCopies dc;
-    void* d_in = dc.make( in, in_bytes );
-    void* d_out = dc.make( nullptr, out_bytes );
-    if( !d_in || !d_out ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-    const int st = dev( d_in, d_out );
-    return st != ACN_OK ? st : DevCopies::fetch( out, d_out, out_bytes );
+    HostCall hc( h );
+    void* d_in = hc.in( in, in_bytes );
+    void* d_out = hc.out( out, out_bytes );
+    return hc.run( [ & ] { return dev( d_in, d_out ); } );
 }
 
 #endif

@@ -6,7 +6,9 @@
    frame to the bits it gave before.
 2. A host-buffer form gives the bits of its device-buffer form, at sizes that are no round number.  acn_select_above and
    acn_key_histogram are left to test_gpu_select.py::test_a_callers_stream_and_the_host_form, which holds both forms of both calls
-   against one model at n = one tile + 1 already."""
+   against one model at n = one tile + 1 already.
+3. The lens calls share one slice loop (lens_slices in csrc/acn_calls.hip): cut into slices of 13, 13 and 11 positions, or of one
+   position each, every family gives the bits of the uncut call, and the families agree where their contracts say they do."""
 import ctypes as C
 
 import numpy as np
@@ -35,8 +37,12 @@ def torch():
 
 
 @pytest.fixture(scope="module")
-def h():
-    flat = A.Scene.build("wine_glass", image_width=W, image_height=H, path_samples=16, direct_samples=50).flatten()
+def flat():
+    return A.Scene.build("wine_glass", image_width=W, image_height=H, path_samples=16, direct_samples=50).flatten()
+
+
+@pytest.fixture(scope="module")
+def h(flat):
     handle = A.Handle(flat)
     yield handle
     handle.close()
@@ -170,3 +176,92 @@ def test_merge_forms_with_an_index(h, torch, pos):
     assert same_bits(got, d_acc.cpu().numpy())
     rest = np.setdiff1d(np.arange(N), idx)
     assert same_bits(got[rest], acc[rest]) and (got[idx, 0] == 6).all()     # five records took two samples more, the others none
+
+
+def planes(records):
+    return np.stack([r.raw for r in records])
+
+
+def test_lens_record_forms(h, torch, pos):
+    """surface_reduce, surface_lens, lens_layers_reduce, render_lens_layers: host form against device form"""
+    K = LENS["samples"]
+    rays = h.lens_rays(pos, **LENS).reshape(-1, 6)
+    rec = h.surface_rays(rays, follow=True).raw.reshape(N, K, abi.ACN_SURF_STRIDE)
+    rad = h.render_rays(rays, linear=True).reshape(N, K, 3)
+    d_pos, d_rec, d_rad = on_device(torch, h, pos), on_device(torch, h, rec), on_device(torch, h, rad)
+    d_one = empty(torch, h, N, abi.ACN_SURF_STRIDE)
+    h.surface_reduce_dev(d_rec.data_ptr(), N, K, d_one.data_ptr())
+    assert same_bits(h.surface_reduce(rec).raw, d_one.cpu().numpy())
+    for follow in (False, True):
+        d_one.fill_(-7.25)
+        h.surface_lens_dev(d_pos.data_ptr(), N, d_one.data_ptr(), follow=follow, **LENS)
+        assert same_bits(h.surface_lens(pos, follow=follow, **LENS).raw, d_one.cpu().numpy()), follow
+    d_rgb = empty(torch, h, N, 3)
+    d_surf = empty(torch, h, abi.ACN_LAYERS_SURFACE_PLANES, N, abi.ACN_SURF_STRIDE)
+    d_st = empty(torch, h, abi.ACN_LAYERS_STATS_PLANES, N, abi.ACN_STATS_STRIDE)
+    h.lens_layers_reduce_dev(d_rec.data_ptr(), d_rad.data_ptr(), N, K, d_surf.data_ptr(), d_st.data_ptr())
+    surf, st = h.lens_layers_reduce(rec, rad)
+    assert same_bits(planes(surf), d_surf.cpu().numpy()) and same_bits(planes(st), d_st.cpu().numpy())
+    d_surf.fill_(-7.25), d_st.fill_(-7.25)
+    h.render_lens_layers_dev(d_pos.data_ptr(), N, d_rgb.data_ptr(), d_surf.data_ptr(), d_st.data_ptr(), follow=True, **LENS)
+    rgb, surf, st = h.render_lens_layers(pos, follow=True, **LENS)
+    want_surf, want_st = d_surf.cpu().numpy(), d_st.cpu().numpy()
+    assert same_bits(rgb, d_rgb.cpu().numpy()) and same_bits(planes(surf), want_surf) and same_bits(planes(st), want_st)
+    # out_rgb = NULL in both forms: the planes alone, the same ones
+    d_surf.fill_(-7.25), d_st.fill_(-7.25)
+    h.render_lens_layers_dev(d_pos.data_ptr(), N, None, d_surf.data_ptr(), d_st.data_ptr(), follow=True, **LENS)
+    raw_surf, raw_st = np.full(want_surf.shape, -7.25), np.full(want_st.shape, -7.25)
+    p, o = h.lens_params(**LENS), h._opts(False, None)
+    A.check(hip.acn_render_lens_layers(h.h, pos.ctypes.data, N, C.byref(p), abi.ACN_SURF_FOLLOW, None, raw_surf.ctypes.data, raw_st.ctypes.data,
+                                       C.byref(o)), "acn_render_lens_layers")
+    assert same_bits(raw_surf, d_surf.cpu().numpy()) and same_bits(raw_st, d_st.cpu().numpy())
+    assert same_bits(raw_surf, want_surf) and same_bits(raw_st, want_st)
+
+
+def test_denoise_layers_forms_on_a_9_by_5_frame(h, torch):
+    w, hh = 9, 5
+    frame_pos = A.main_pass_positions(W, H).reshape(H, W, 2)[7:7 + hh, 20:20 + w].reshape(-1, 2)     # across the glass
+    _, surf, st = h.render_lens_layers(frame_pos, follow=True, linear=True, samples=4, jitter=True)
+    d_surf, d_st = on_device(torch, h, planes(surf)), on_device(torch, h, planes(st))
+    d_out = empty(torch, h, hh * w, 3)
+    h.denoise_layers_dev(d_st.data_ptr(), d_surf.data_ptr(), w, hh, d_out.data_ptr(), iterations=3)
+    assert same_bits(h.denoise_layers(st, surf, w, hh, iterations=3).reshape(-1, 3), d_out.cpu().numpy())
+
+
+def same_bits_or_nan(a, b):
+    """bit for bit, and a NaN matches a NaN"""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def lens_families(handle, pos):
+    """the four families that cut their positions into slices, on one handle"""
+    rgb = handle.render_lens(pos, linear=True, **LENS)
+    stats_rgb, stats = handle.render_lens_stats(pos, linear=True, **LENS)
+    surface = handle.surface_lens(pos, follow=True, **LENS).raw
+    layers_rgb, layers_surf, layers_st = handle.render_lens_layers(pos, follow=True, linear=True, **LENS)
+    return {"render_lens": rgb, "render_lens_stats rgb": stats_rgb, "render_lens_stats": stats.raw, "surface_lens": surface,
+            "render_lens_layers rgb": layers_rgb, "render_lens_layers surface": planes(layers_surf), "render_lens_layers stats": planes(layers_st)}
+
+
+@pytest.fixture(scope="module")
+def uncut(h, pos):
+    """the families at the default slice size: the 37 positions are one slice"""
+    return lens_families(h, pos)
+
+
+@pytest.mark.parametrize("slice_rays", [40, 2])
+def test_all_lens_families_cut_alike(flat, pos, uncut, slice_rays):
+    """K = 3: 40 rays are slices of 13, 13 and 11 of the 37 positions; 2 rays are less than one position's, so every slice is one"""
+    mp = pytest.MonkeyPatch()
+    mp.setenv("ACN_LENS_SLICE_RAYS", str(slice_rays))
+    cut = A.Handle(flat)                                                      # (tunables are read at the upload)
+    mp.undo()
+    try:
+        got = lens_families(cut, pos)
+    finally:
+        cut.close()
+    for name, want in uncut.items():
+        assert same_bits_or_nan(got[name], want), (slice_rays, name)
+    assert same_bits_or_nan(got["render_lens_layers surface"][0], got["surface_lens"]), slice_rays
+    assert same_bits_or_nan(got["render_lens_layers rgb"], got["render_lens"]), slice_rays
