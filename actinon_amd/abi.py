@@ -94,6 +94,28 @@ class SelectParams(C.Structure):
                 ("raster_width", C.c_uint64), ("raster_first", C.c_uint64)]
 
 
+# the stage-runner test seam (acn_run_stage): stages, option bits, limits
+ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE = 0, 1
+ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_LEAF_LIGHTS, ACN_STAGE_NO_EMIT_TERMS = 1, 2, 4
+ACN_STAGE_MAX_RECORDS, ACN_STAGE_MAX_SAMPLES, ACN_STAGE_MAX_DEPTH = 1 << 20, 1 << 16, 1 << 20
+ACN_STAGE_INFO_WORDS = 10
+
+
+class StageArgs(C.Structure):
+    _fields_ = [("stage", C.c_uint32), ("flags", C.c_uint32), ("cls", C.c_uint32), ("shard_rank", C.c_uint32), ("shard_world", C.c_uint32),
+                ("n", C.c_uint32), ("n_index", C.c_uint32), ("pad", C.c_uint32), ("input", C.c_void_p), ("index", C.c_void_p)]
+
+
+class StageCaps(C.Structure):
+    _fields_ = [("cap_tasks", C.c_uint32), ("cap_rays", C.c_uint32), ("cap_children", C.c_uint32), ("cap_hard_shadow", C.c_uint32),
+                ("cap_hard_path", C.c_uint32), ("grid", C.c_uint32), ("chunk", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class StageOut(C.Structure):
+    _fields_ = [("tasks", C.c_void_p), ("idx", C.c_void_p * 4), ("rays", C.c_void_p), ("children", C.c_void_p), ("hard_shadow", C.c_void_p),
+                ("hard_path", C.c_void_p), ("counts", C.c_void_p), ("accum", C.c_void_p)]
+
+
 class V3(C.Structure):
     _fields_ = [("x", C.c_double), ("y", C.c_double), ("z", C.c_double)]
 

@@ -2042,10 +2042,12 @@ DEV double oren_nayar_weight_pre( double weight, double theta_i, double sin_i, d
  * hence  max( cos_phi, 0 ) * sin( max ) * tan( min )  =  theta_i >= theta_r:  ( m+ / sr ) * sin_i * ( sr / w ) = m+ * sin_i / w
  *                                                        theta_i <  theta_r:  ( m+ / sr ) * sr * tan_i       = m+ * tan_i
  * and the weight is  w * on_a + on_b * m+ * ( cos_i <= w ? sin_i : w * tan_i ):  eleven multiply-adds and a select instead of
- * acos + sincos + sqrt + two divisions (16 % of k_shade's time, profiles/r03/NOTES.md section 2).  Agrees with
- * oren_nayar_weight to ~1e-15 relative (5e-9 relative where w < 1e-4, the range in which v_of_length returns its argument
- * unscaled, vectors.h:151: a sample whose weight is below 1e-4 to begin with); the path loop keeps the exact form because its
- * weight becomes the child's intensity (scene.c:596-617).  tan_i is used only where cos_i > w > 0. */
+ * acos + sincos + sqrt + two divisions (16 % of k_shade's time, profiles/r03/NOTES.md section 2).  Agreement with
+ * oren_nayar_weight, measured (tests/test_stages_cpu.py): |closed - exact| <= K 2^-53 on_b / min( sr, cos_i, 1 )
+ * with K < 9 -- 6e-14 relative in general, but 7e-10 where out_d lies within 1e-3 rad of the normal (sr < 1e-3, w ~ 1: acos( w )
+ * loses the digits of sr) and 3e-13 where theta_i is within 1e-3 of pi / 2; and 5e-9 relative where w < 1e-4, the range in which
+ * v_of_length returns its argument unscaled (vectors.h:151), which is the exact form's deviation, not this one's.  The path loop
+ * keeps the exact form because its weight becomes the child's intensity (scene.c:596-617).  tan_i is used only where cos_i > w > 0. */
 DEV double oren_nayar_weight_direct( double w, double sin_i, double cos_i, double tan_i, double on_a, double on_b, V3 out_d, V3 nor, V3 ray_prj )
 {
     double m = -v_mlv( v_orthogonal_projection( out_d, nor ), ray_prj );

@@ -1,0 +1,126 @@
+/* acn_stage_host.h -- what acn_stage_plan / acn_run_stage (include/actinon_hip.h, the stage-runner test seam) do without the GPU: every
+ * argument check, and the capacities of the output queues.  Plain C++, no HIP header: k_stage.hip calls acn_stage_check before it
+ * launches anything, and tests/csrc/stage_cpu.cpp compiles the header on its own into a program that runs under the address and
+ * undefined-behaviour sanitizers.  The two input records are restated here as plain structs; k_stage.hip asserts that they are the
+ * pipeline's (sizes and offsets). */
+#ifndef ACN_STAGE_HOST_H
+#define ACN_STAGE_HOST_H
+
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <string>
+
+#include "actinon_hip.h"
+
+struct acn_stage_v3 { double x, y, z; };
+/* HitRec of acn_pipeline.h */
+struct acn_stage_hitrec
+{
+    acn_stage_v3 p, d; double offs; acn_stage_v3 exit_nor, T; double intensity;
+    int32_t exit_obj, enter_obj, depth; uint32_t pixel;
+};
+/* DTask of acn_pipeline.h */
+struct acn_stage_dtask
+{
+    acn_stage_v3 pos, surface_d, ray_projection; double theta_i, on_a, on_b, diffuse_intensity; acn_stage_v3 Tc;
+    uint64_t rv; int32_t depth; uint32_t pixel;
+};
+
+/* what the checks read of the uploaded scene */
+struct acn_stage_scene
+{
+    uint32_t n_nodes, n_lights;
+    uint64_t direct_samples, path_samples;
+};
+
+#define ACN_STAGE_DEAD 0xFFFFFFFFu
+#define ACN_STAGE_MAX_GRID 64u          /* workgroups of a stage launch: 256 waves at most */
+#define ACN_STAGE_MAX_CAP ( 1u << 26 )  /* records of one output queue */
+
+/* samples of a loop as shade_hit and k_shade count them: ( uint64_t )( samples * diffuse_intensity ), at least 1.  *ok: the product is
+ * finite, not negative and within ACN_STAGE_MAX_SAMPLES (so the conversion is defined) */
+static inline uint64_t acn_stage_samples( uint64_t samples, double diffuse_intensity, bool* ok )
+{
+    const double v = ( double )samples * diffuse_intensity;
+    if( !( v >= 0.0 ) || !( v < ( double )ACN_STAGE_MAX_SAMPLES + 1.0 ) ) { *ok = false; return 0; }
+    const uint64_t n = ( uint64_t )v;
+    return n == 0 ? 1 : n;
+}
+
+/* slots a wave reserves at a time: ACN_QCHUNK of k_shade, chunks_resize( n ) of k_shade_hits (acn_pipeline.h) */
+static inline uint32_t acn_stage_chunk( uint32_t stage, uint32_t n, uint32_t grid )
+{
+    if( stage != ACN_STAGE_SHADE_HITS ) return 64u;
+    uint32_t size = ( ( n / ( grid * 4u ) ) / 8u ) & ~63u;
+    return size < 64u ? 64u : size > 512u ? 512u : size;
+}
+
+/* every check of a stage call, then the capacities: the records the input can produce at most plus one reservation per wave (a wave
+ * leaves the unused end of at most one reservation per queue behind).  have_handle: the caller holds one. */
+static inline int acn_stage_check( bool have_handle, const acn_stage_args* a, const acn_stage_scene& sc, acn_stage_caps* caps, std::string* msg )
+{
+    if( !have_handle ) { *msg = "null argument: handle"; return ACN_ERR_ARG; }
+    if( !a || !caps ) { *msg = "null argument: acn_stage_args / acn_stage_caps"; return ACN_ERR_ARG; }
+    if( a->stage >= ACN_STAGE_N ) { *msg = "unknown stage " + std::to_string( a->stage ); return ACN_ERR_ARG; }
+    if( a->flags & ~( ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_LEAF_LIGHTS | ACN_STAGE_NO_EMIT_TERMS ) ) { *msg = "unknown acn_stage_args.flags bits"; return ACN_ERR_ARG; }
+    if( !a->in ) { *msg = "null argument: in"; return ACN_ERR_ARG; }
+    if( a->n == 0 || a->n > ACN_STAGE_MAX_RECORDS ) { *msg = "n " + std::to_string( a->n ) + " is outside 1 .. 2^20 records"; return ACN_ERR_ARG; }
+    const bool shade = a->stage == ACN_STAGE_SHADE;
+    uint64_t sum_direct = 0, sum_path = 0;
+    if( !shade )
+    {
+        const acn_stage_hitrec* r = ( const acn_stage_hitrec* )a->in;
+        for( uint32_t i = 0; i < a->n; i++ )
+        {
+            const std::string who = "hit record " + std::to_string( i );
+            if( r[ i ].pixel == ACN_STAGE_DEAD ) continue;
+            if( r[ i ].pixel >= a->n ) { *msg = who + ": pixel " + std::to_string( r[ i ].pixel ) + " is not below n"; return ACN_ERR_ARG; }
+            if( r[ i ].depth < 0 || r[ i ].depth > ACN_STAGE_MAX_DEPTH ) { *msg = who + ": depth " + std::to_string( r[ i ].depth ) + " is outside 0 .. 2^20"; return ACN_ERR_ARG; }
+            for( int32_t o : { r[ i ].exit_obj, r[ i ].enter_obj } )
+                if( o < -1 || ( o >= 0 && ( uint32_t )o >= sc.n_nodes ) ) { *msg = who + ": object " + std::to_string( o ) + " is no node of the scene"; return ACN_ERR_ARG; }
+        }
+    }
+    else
+    {
+        if( a->cls > 3 ) { *msg = "size class " + std::to_string( a->cls ) + " is above 3"; return ACN_ERR_ARG; }
+        const uint32_t world = a->shard_world ? a->shard_world : 1u;
+        if( a->shard_rank >= world ) { *msg = "shard_rank " + std::to_string( a->shard_rank ) + " is not below shard_world"; return ACN_ERR_ARG; }
+        if( !a->index ) { *msg = "null argument: index"; return ACN_ERR_ARG; }
+        if( a->n_index == 0 || a->n_index > ACN_STAGE_MAX_RECORDS ) { *msg = "n_index " + std::to_string( a->n_index ) + " is outside 1 .. 2^20 entries"; return ACN_ERR_ARG; }
+        const acn_stage_dtask* t = ( const acn_stage_dtask* )a->in;
+        for( uint32_t k = 0; k < a->n_index; k++ )
+        {
+            const uint32_t i = a->index[ k ];
+            if( i == ACN_STAGE_DEAD ) continue;
+            if( i >= a->n ) { *msg = "index entry " + std::to_string( k ) + ": task " + std::to_string( i ) + " is not below n"; return ACN_ERR_ARG; }
+            const std::string who = "task " + std::to_string( i );
+            if( t[ i ].pixel >= a->n ) { *msg = who + ": pixel " + std::to_string( t[ i ].pixel ) + " is not below n"; return ACN_ERR_ARG; }
+            if( t[ i ].depth < 0 || t[ i ].depth > ACN_STAGE_MAX_DEPTH ) { *msg = who + ": depth " + std::to_string( t[ i ].depth ) + " is outside 0 .. 2^20"; return ACN_ERR_ARG; }
+            bool ok = true;
+            const uint64_t nd = sc.n_lights ? acn_stage_samples( sc.direct_samples, t[ i ].diffuse_intensity, &ok ) : 0;
+            const uint64_t np = sc.path_samples && t[ i ].depth > 10 ? acn_stage_samples( sc.path_samples, t[ i ].diffuse_intensity, &ok ) : 0;
+            if( !ok ) { *msg = who + ": diffuse_intensity asks for a sample count that is not within 0 .. 2^16"; return ACN_ERR_ARG; }
+            sum_direct += nd * sc.n_lights;
+            sum_path += np;
+        }
+    }
+    acn_stage_caps c;
+    memset( &c, 0, sizeof( c ) );
+    const uint32_t items = shade ? a->n_index : a->n;
+    c.grid = ( items + 3u ) / 4u;
+    c.grid = c.grid > ACN_STAGE_MAX_GRID ? ACN_STAGE_MAX_GRID : c.grid;
+    c.chunk = acn_stage_chunk( a->stage, a->n, c.grid );
+    const uint64_t slack = ( uint64_t )c.grid * 4u * c.chunk;
+    uint64_t tasks, rays, children, hs, hp;
+    if( shade ) { tasks = a->n_index; rays = 0; children = sum_path + slack; hp = sum_path + slack; hs = sum_direct + sum_path + slack; }
+    else        { tasks = ( uint64_t )a->n + slack; rays = 3ull * a->n + slack; children = a->n; hp = 0; hs = 3ull * a->n + slack; }
+    for( uint64_t v : { tasks, rays, children, hs, hp } )
+        if( v > ACN_STAGE_MAX_CAP ) { *msg = "the input can produce " + std::to_string( v ) + " records of one queue: above 2^26"; return ACN_ERR_ARG; }
+    c.cap_tasks = ( uint32_t )tasks; c.cap_rays = ( uint32_t )rays; c.cap_children = ( uint32_t )children;
+    c.cap_hard_shadow = ( uint32_t )hs; c.cap_hard_path = ( uint32_t )hp;
+    *caps = c;
+    return ACN_OK;
+}
+
+#endif

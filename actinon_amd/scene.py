@@ -795,6 +795,88 @@ class Handle:
                                  None if lim is None else lim.ctypes.data, out.ctypes.data), "acn_query_rays")
         return out[:cnt]
 
+    # test seam acn_run_stage (include/actinon_hip.h): one shading kernel alone.  The records of csrc/acn_pipeline.h as numpy dtypes;
+    # run_stage asserts their sizes against the library's
+    _V = (np.float64, 3)
+    STAGE_RECORDS = {
+        "ray": np.dtype([("p", *_V), ("d", *_V), ("T", *_V), ("intensity", "f8"), ("depth", "i4"), ("pixel", "u4")]),
+        "task": np.dtype([("pos", *_V), ("surface_d", *_V), ("ray_projection", *_V), ("theta_i", "f8"), ("on_a", "f8"), ("on_b", "f8"),
+                          ("diffuse_intensity", "f8"), ("Tc", *_V), ("rv", "u8"), ("depth", "i4"), ("pixel", "u4")]),
+        "hit": np.dtype([("p", *_V), ("d", *_V), ("offs", "f8"), ("exit_nor", *_V), ("T", *_V), ("intensity", "f8"), ("exit_obj", "i4"),
+                         ("enter_obj", "i4"), ("depth", "i4"), ("pixel", "u4")]),
+        "hard_shadow": np.dtype([("pos", *_V), ("d", *_V), ("limit", "f8"), ("contrib", *_V), ("pixel", "u4"), ("pad", "u4")]),
+        "hard_path": np.dtype([("pos", *_V), ("d", *_V), ("T", *_V), ("intensity", "f8"), ("depth", "i4"), ("pixel", "u4"), ("resume", "u4"),
+                               ("pad", "u4")]),
+    }
+    del _V
+    STAGE_INVALID = 0xFFFFFFFF
+    # words of the level's counter block (acn_pipeline.h)
+    QC = {"tasks": 0, "class0": 1, "children": 5, "flags": 6, "hard_shadow": 7, "hard_path": 8, "walk_rays": 12, "s_hard_shadow": 13,
+          "s_hard_path": 14, "s_children": 15, "s_tasks": 16, "s_probes": 19, "dead_t": 28, "dead_c": 29, "dead_hp": 30, "dead_r": 31, "gen0": 32}
+
+    def stage_info(self):
+        """Sizes of the five records, words of a counter block, DevScene.class0_min, nodes, lights and the handle's kernel variant."""
+        w = np.zeros(abi.ACN_STAGE_INFO_WORDS, dtype=np.uint32)
+        check(hip.acn_stage_info(self.h, w.ctypes.data, w.size), "acn_stage_info")
+        names = ("ray", "task", "hit", "hard_shadow", "hard_path")
+        info = {"sizeof": {k: int(w[i]) for i, k in enumerate(names)}, "counter_words": int(w[5]), "class0_min": int(w[6]),
+                "nodes": int(w[7]), "lights": int(w[8]), "prune": bool(w[9] & 1), "leaf_lights": bool(w[9] & 2)}
+        return info
+
+    def run_stage(self, stage, records, index=None, cls=0, shard_rank=0, shard_world=1, prune=True, leaf_lights=True, emit_terms=True):
+        """Runs one production shading kernel on `records` and returns everything it wrote as a dict of numpy arrays.
+        stage "shade_hits": records are "hit" records (pixel = own index, or STAGE_INVALID); returns tasks, idx (four lists), rays,
+        hard_shadow (the probes), counts, flags, accum.  stage "shade": records are "task" records, index the uint32 list the kernel of
+        size class `cls` works off; returns children, hard_shadow, hard_path, counts, flags, accum.  Queues come back up to their
+        high-water mark with the dead slots (pixel STAGE_INVALID) taken out; accum is [n, 3] int64 in units of 2^-40."""
+        info = self.stage_info()
+        for k, dt in self.STAGE_RECORDS.items():
+            assert dt.itemsize == info["sizeof"][k], (k, dt.itemsize, info["sizeof"][k])
+        shade = {"shade_hits": False, "shade": True}[stage]
+        rec = np.ascontiguousarray(records, dtype=self.STAGE_RECORDS["task" if shade else "hit"])
+        a = abi.StageArgs()
+        a.stage = abi.ACN_STAGE_SHADE if shade else abi.ACN_STAGE_SHADE_HITS
+        a.flags = ((0 if prune else abi.ACN_STAGE_NO_PRUNE) | (0 if leaf_lights else abi.ACN_STAGE_NO_LEAF_LIGHTS)
+                   | (0 if emit_terms else abi.ACN_STAGE_NO_EMIT_TERMS))
+        a.cls, a.shard_rank, a.shard_world, a.n = int(cls), int(shard_rank), int(shard_world), rec.shape[0]
+        a.input = rec.ctypes.data
+        ix = None
+        if shade:
+            ix = np.ascontiguousarray(np.arange(rec.shape[0]) if index is None else index, dtype=np.uint32)
+            a.index, a.n_index = ix.ctypes.data, ix.shape[0]
+        caps = abi.StageCaps()
+        check(hip.acn_stage_plan(self.h, C.byref(a), C.byref(caps)), "acn_stage_plan")
+        R = self.STAGE_RECORDS
+        bufs = {"counts": np.zeros(info["counter_words"], dtype=np.uint32), "accum": np.zeros((rec.shape[0], 3), dtype=np.int64),
+                "hard_shadow": np.zeros(max(caps.cap_hard_shadow, 1), dtype=R["hard_shadow"])}
+        if shade:
+            bufs["children"] = np.zeros(max(caps.cap_children, 1), dtype=R["hit"])
+            bufs["hard_path"] = np.zeros(max(caps.cap_hard_path, 1), dtype=R["hard_path"])
+        else:
+            bufs["tasks"] = np.zeros(max(caps.cap_tasks, 1), dtype=R["task"])
+            bufs["rays"] = np.zeros(max(caps.cap_rays, 1), dtype=R["ray"])
+            idx = [np.zeros(max(caps.cap_tasks, 1), dtype=np.uint32) for _ in range(4)]
+        o = abi.StageOut()
+        for k, b in bufs.items():
+            setattr(o, k, b.ctypes.data)
+        if not shade:
+            for k in range(4):
+                o.idx[k] = idx[k].ctypes.data
+        check(hip.acn_run_stage(self.h, C.byref(a), C.byref(o)), "acn_run_stage")
+        c = bufs["counts"]
+        live = lambda q, mark: q[:mark][q["pixel"][:mark] != self.STAGE_INVALID]   # noqa: E731
+        res = {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps,
+               "hard_shadow": live(bufs["hard_shadow"], c[self.QC["hard_shadow"]])}
+        if shade:
+            res["children"] = live(bufs["children"], c[self.QC["children"]])
+            res["hard_path"] = live(bufs["hard_path"], c[self.QC["hard_path"]])
+        else:
+            res["tasks"] = bufs["tasks"][:c[self.QC["tasks"]]]       # with the unused ends of reservations: reached through idx only
+            res["rays"] = live(bufs["rays"], c[self.QC["gen0"]])
+            res["idx"] = [l[:c[self.QC["class0"] + k]][l[:c[self.QC["class0"] + k]] != self.STAGE_INVALID] for k, l in enumerate(idx)]
+        return res
+
+
 class Surface:
     """Named views over the [n,16] float64 records of a surface call (include/actinon_hip.h, acn_surface_rays)."""
 
@@ -892,7 +974,7 @@ def device_count():
 
 def detmath_eval(op, x, y=None, device=0):
     ops = {"sin": 0, "cos": 1, "tan": 2, "acos": 3, "log": 4, "exp": 5, "pow": 6, "sqrt": 7, "div": 8, "u64_to_f64": 9,
-           "frexp_mant": 10}
+           "frexp_mant": 10, "asin": 11, "atan": 12, "atan2": 13, "llrint": 14}
     x = np.ascontiguousarray(x, dtype=np.float64)
     out = np.empty_like(x)
     yp = None

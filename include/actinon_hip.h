@@ -790,7 +790,8 @@ int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_t samples, 
                            double radius_factor, double* out_pos3_radius );
 
 /* Test hook: evaluates the deterministic fp64 kernels of csrc/acn_detmath.h on the device.
- * op: 0 sin 1 cos 2 tan 3 acos 4 log 5 exp 6 pow(x,y) 7 sqrt 8 div(x/y) 9 u64->f64 (x bits) 10 frexp-mantissa */
+ * op: 0 sin 1 cos 2 tan 3 acos 4 log 5 exp 6 pow(x,y) 7 sqrt 8 div(x/y) 9 u64->f64 (x bits) 10 frexp-mantissa
+ * 11 asin 12 atan 13 atan2(x,y): x is the ordinate 14 llrint as a double (|x| < 2^62) */
 int acn_detmath_eval( int device, int op, const double* x, const double* y, double* out, size_t n );
 
 /* Test hook: the traversal shortcuts of the device (csrc/acn_device.h), one ray per lane, in the arrangement of the
@@ -830,6 +831,56 @@ enum acn_query_op
 #define ACN_Q_EL_PROGRAM         8u
 #define ACN_Q_EL_ENVELOPE       16u
 int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const double* rays, size_t n, const double* limits, void* out );
+
+/* Test hook: one shading kernel of the pipeline alone (csrc/k_stage.hip).  acn_run_stage launches the production kernel of one stage
+ * once, on queues it owns and fills from the caller's records, and fetches back everything the kernel wrote; it has no device code of
+ * its own.  The records are the pipeline's own (csrc/acn_pipeline.h: HitRec, DTask, RayTask, HardShadow, HardPath), the counter block
+ * is the level's (QC_*, QS_*); acn_stage_info reports their sizes so that a caller asserts its layouts.
+ *   ACN_STAGE_SHADE_HITS  k_shade_hits on in = HitRec[ n ]: the split of scene_s_lum.  Written: tasks, idx[ 0 .. 3 ], rays, hard_shadow
+ *                         (the probes of dead children), counts, flags, accum.
+ *   ACN_STAGE_SHADE       k_shade of size class `cls` on in = DTask[ n ] and index[ n_index ] (entries < n, or 0xFFFFFFFF: a dead
+ *                         slot), whatever class the sample counts of a task ask for.  Written: children, hard_shadow, hard_path,
+ *                         counts, flags, accum.  shard_rank < shard_world: the rank's share of the sample loops (0, 1: all of them).
+ * Every record's pixel is < n or 0xFFFFFFFF (HitRec: a dead slot); accum is [ n ][ 3 ] raw fixed-point words (2^-40), zero before the launch.
+ * The kernel variant is the handle's; ACN_STAGE_NO_PRUNE and ACN_STAGE_NO_LEAF_LIGHTS select the variant without interval-prune
+ * programs / with the generic light hit (equal results), ACN_STAGE_NO_EMIT_TERMS runs the split as a shard rank > 0 does (emit_terms 0).
+ * acn_stage_plan makes every check on the host and sizes the queues from the input so that none can overflow (the records the input
+ * can produce at most, plus one reservation per wave of the small grid the seam launches); a caller allocates each output it
+ * wants with the planned capacity, a null output is not fetched.  ACN_ERR_ARG before anything is launched, acn_last_error set: a null
+ * handle, args or input; an unknown stage or flag; cls > 3; shard_rank >= shard_world; n or n_index 0 or above ACN_STAGE_MAX_RECORDS;
+ * a pixel, index entry or object (-1 .. nodes - 1) out of range; a depth outside 0 .. ACN_STAGE_MAX_DEPTH; a diffuse_intensity that is
+ * not finite or asks for more than ACN_STAGE_MAX_SAMPLES samples of a loop.  A raised overflow flag is ACN_ERR_DEVICE. */
+enum acn_stage { ACN_STAGE_SHADE_HITS = 0, ACN_STAGE_SHADE = 1, ACN_STAGE_N };
+#define ACN_STAGE_NO_PRUNE       1u
+#define ACN_STAGE_NO_LEAF_LIGHTS 2u
+#define ACN_STAGE_NO_EMIT_TERMS  4u
+#define ACN_STAGE_MAX_RECORDS ( 1u << 20 )
+#define ACN_STAGE_MAX_SAMPLES ( 1u << 16 )
+#define ACN_STAGE_MAX_DEPTH   ( 1 << 20 )
+typedef struct acn_stage_args
+{
+    uint32_t stage, flags;              /* ACN_STAGE_*, ACN_STAGE_NO_* */
+    uint32_t cls;                       /* SHADE */
+    uint32_t shard_rank, shard_world;   /* SHADE; shard_world 0 reads as 1 */
+    uint32_t n, n_index;                /* input records; SHADE: entries of index */
+    uint32_t pad;
+    const void* in;
+    const uint32_t* index;
+} acn_stage_args;
+/* capacities in records, and the launch; cap_tasks also holds for each index list */
+typedef struct acn_stage_caps { uint32_t cap_tasks, cap_rays, cap_children, cap_hard_shadow, cap_hard_path, grid, chunk, pad; } acn_stage_caps;
+typedef struct acn_stage_out
+{
+    void* tasks; uint32_t* idx[ 4 ]; void* rays; void* children; void* hard_shadow; void* hard_path;
+    uint32_t* counts;                   /* the counter block, acn_stage_info[ 5 ] words (word 6: the ACN_FLAG_* bits) */
+    uint64_t* accum;                    /* [ n ][ 3 ] */
+} acn_stage_out;
+/* out[ 0 .. 4 ] sizeof RayTask, DTask, HitRec, HardShadow, HardPath; [ 5 ] words of a counter block; [ 6 ] DevScene.class0_min; [ 7 ] nodes;
+ * [ 8 ] lights; [ 9 ] bit 0 prune, bit 1 leaf_lights: the kernel variant of the handle.  n <= 10 */
+#define ACN_STAGE_INFO_WORDS 10
+int acn_stage_info( acn_scene_handle* h, uint32_t* out, int n );
+int acn_stage_plan( acn_scene_handle* h, const acn_stage_args* args, acn_stage_caps* caps );   /* no GPU work */
+int acn_run_stage( acn_scene_handle* h, const acn_stage_args* args, const acn_stage_out* out );
 
 const char* acn_last_error( void );
 

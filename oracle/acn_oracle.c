@@ -61,7 +61,23 @@ typedef struct
      * of the terms under no such loop everything if rank == 0, nothing otherwise.  world <= 1: the whole thing. */
     uint32_t rank, world;
     int level;
+    /* acn_oracle_shade_point: scene_lum writes what it computes for ONE hit into rows and does not recurse (nullable) */
+    struct tap_s* tap;
 } ctx_t;
+
+/* the recorder of acn_oracle_shade_point (acn_oracle.h states the rows).  A row past the caller's room is counted, not written */
+typedef struct tap_s { double* rows; size_t room, n; double spill[ ACN_ORACLE_TAP_STRIDE ]; } tap_t;
+static double* tap_row( ctx_t* c, int kind )
+{
+    tap_t* t = c->tap;
+    double* r = t->n < t->room ? t->rows + ACN_ORACLE_TAP_STRIDE * t->n : t->spill;
+    t->n++;
+    for( int k = 0; k < ACN_ORACLE_TAP_STRIDE; k++ ) r[ k ] = 0;
+    r[ 0 ] = kind;
+    return r;
+}
+static void tap_v3( double* d, double x, double y, double z ) { d[ 0 ] = x; d[ 1 ] = y; d[ 2 ] = z; }
+#define TAP_V3( d, v ) tap_v3( ( d ), ( v ).x, ( v ).y, ( v ).z )
 static int shard_skips_terms( const ctx_t* c ) { return c->world > 1 && c->level == 0 && c->rank != 0; }
 static int shard_skips_sample( const ctx_t* c, uint64_t j, uint64_t n )
 {
@@ -867,6 +883,14 @@ static double oren_nayar_weight( ctx_t* c, double weight, double theta_i, double
     );
 }
 
+/* a specular child of the tapped hit: the arguments of the scene_s_lum call the reference makes if the ray hits, and the colour the
+ * reference multiplies onto what it returns */
+static void tap_child( ctx_t* c, int kind, const ray_t* out, double intensity, uint64_t depth, v3 color )
+{
+    double* r = tap_row( c, kind );
+    TAP_V3( r + 1, out->p ); TAP_V3( r + 4, out->d ); r[ 7 ] = intensity; r[ 8 ] = ( double )depth; TAP_V3( r + 9, color );
+}
+
 /* ---- src/scene.c:420-667 ----------------------------------------------------------------------------------------- */
 static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, uint64_t depth, double intensity )
 {
@@ -888,7 +912,9 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         double light_intensity = ( diff_sqr > 0 ) ? ( enter_obj->radiance / diff_sqr ) : F3_MAG;
         COST( c, ACN_F_EMISSION, 0 );
         if( shard_skips_terms( c ) ) return lum;
-        return v3_mlf( obj_color( c->sc, enter_obj, pos ), light_intensity * intensity );
+        lum = v3_mlf( obj_color( c->sc, enter_obj, pos ), light_intensity * intensity );
+        if( c->tap ) { double* r = tap_row( c, ACN_ORACLE_TAP_EMISSION ); TAP_V3( r + 1, lum ); r[ 4 ] = diff_sqr; r[ 5 ] = light_intensity; }
+        return lum;
     }
 
     double trans_refractive_index = 1.0;
@@ -926,6 +952,12 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     /* obj_color( trans->enter_obj, pos ) (objects.c:411-422; texture fields unsupported). The reference
      * dereferences a NULL enter_obj here when trace_min_intensity == 0; the restatement uses white. */
     v3 enter_color = enter_obj ? obj_color( c->sc, enter_obj, pos ) : V( 1, 1, 1 );
+    if( c->tap )
+    {
+        double* r = tap_row( c, ACN_ORACLE_TAP_SURFACE );
+        TAP_V3( r + 1, pos ); TAP_V3( r + 4, enter_color ); r[ 7 ] = trans_refractive_index; r[ 8 ] = on_a; r[ 9 ] = on_b;
+        r[ 10 ] = fresnel_reflectivity; r[ 11 ] = chromatic_reflectivity; r[ 12 ] = diffuse_reflectivity; r[ 13 ] = transparent;
+    }
 
     /* fresnel reflection :473-495 */
     if( fresnel_reflectivity > 0 && intensity >= scene->trace_min_intensity )
@@ -939,7 +971,8 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
         double a;
         v3 lum_l = { 0, 0, 0 };
-        if( ( a = scene_trans_hit( c, &out, &trans_l ) ) < F3_INF )
+        if( c->tap ) tap_child( c, ACN_ORACLE_TAP_FRESNEL, &out, reflectance * intensity, depth - 1, V( 1, 1, 1 ) );
+        else if( ( a = scene_trans_hit( c, &out, &trans_l ) ) < F3_INF )
         {
             lum_l = scene_lum( c, &out, a, &trans_l, depth - 1, reflectance * intensity );
         }
@@ -961,7 +994,8 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
         double a;
         v3 lum_l = { 0, 0, 0 };
-        if( ( a = scene_trans_hit( c, &out, &trans_l ) ) < F3_INF )
+        if( c->tap ) tap_child( c, ACN_ORACLE_TAP_CHROMATIC, &out, chromatic_reflectivity * intensity, depth - 1, enter_color );
+        else if( ( a = scene_trans_hit( c, &out, &trans_l ) ) < F3_INF )
         {
             lum_l = scene_lum( c, &out, a, &trans_l, depth - 1, chromatic_reflectivity * intensity );
         }
@@ -987,6 +1021,12 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         v3 ray_projection = v3_of_length( v3_orthogonal_projection( ray->d, surface.d ), 1.0 );
 
         uint64_t rv = v3_random_seed( surface.p, 3294479285ull ) + v3_random_seed( surface.d, 3247146734ull );
+        if( c->tap )
+        {
+            double* r = tap_row( c, ACN_ORACLE_TAP_DIFFUSE );
+            TAP_V3( r + 1, surface.d ); r[ 4 ] = theta_i; TAP_V3( r + 5, ray_projection ); r[ 8 ] = diffuse_intensity;
+            memcpy( r + 9, &rv, sizeof( rv ) ); r[ 10 ] = ( double )depth;
+        }
 
         v3 lum_l = { 0, 0, 0 };
 
@@ -1004,6 +1044,11 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
             v3 color = obj_color( c->sc, light_src, v3_ld( light_src->pos ) );
             uint64_t direct_samples = ( uint64_t )( scene->direct_samples * diffuse_intensity );
             direct_samples = ( direct_samples == 0 ) ? 1 : direct_samples;
+            if( c->tap )
+            {
+                double* r = tap_row( c, ACN_ORACLE_TAP_LIGHT );
+                r[ 1 ] = light_idx; r[ 2 ] = cyl_hgt; TAP_V3( r + 3, color ); r[ 6 ] = ( double )direct_samples; TAP_V3( r + 7, fov_to_src.ray.d );
+            }
 
             for( uint64_t j = 0; j < direct_samples; j++ )
             {
@@ -1012,20 +1057,30 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
                 out.d = m3_mlv( &src_con, v3_random_sphere_cap( &rv, cyl_hgt ) );
                 if( shard_skips_sample( c, j, direct_samples ) ) continue;   /* the draws were made: the stream stays in step */
                 double weight = v3_mlv( out.d, surface.d );
+                double* tr = NULL;   /* the sample's row: filled as far as the sample gets */
+                if( c->tap )
+                {
+                    tr = tap_row( c, ACN_ORACLE_TAP_DIRECT );
+                    tr[ 1 ] = ( double )j; tr[ 2 ] = light_idx; TAP_V3( tr + 3, out.d ); tr[ 6 ] = weight; tr[ 7 ] = F3_INF;
+                }
                 if( weight <= 0 ) continue;
 
                 double a = obj_ray_hit( c, light_idx, &out, NULL );
+                if( tr ) tr[ 7 ] = a;
                 if( a >= F3_INF ) continue;
 
                 if( on_b > 0 ) weight = oren_nayar_weight( c, weight, theta_i, on_a, on_b, out.d, surface.d, ray_projection );
+                if( tr ) { tr[ 8 ] = weight; tr[ 9 ] = 1; }
 
                 COUNT( c, ORC_N_SHADOW_RAY );
                 if( compound_ray_hit( c, c->sc->matter_root, &out, NULL, NULL ) > a )
                 {
+                    if( tr ) tr[ 9 ] = 0;
                     COST( c, ACN_F_DIRECT_TAIL, 0 );
                     v3 hit_pos = ray_pos( &out, a );
                     double diff_sqr = v3_diff_sqr( hit_pos, v3_ld( light_src->pos ) );
                     double local_intensity = ( diff_sqr > 0 ) ? ( light_src->radiance / diff_sqr ) : F3_MAG;
+                    if( tr ) { tr[ 10 ] = local_intensity; tr[ 11 ] = local_intensity * weight * diffuse_intensity; }
                     cl_sum = v3_add( cl_sum, v3_mlf( color, local_intensity * weight * diffuse_intensity ) );
                 }
             }
@@ -1042,6 +1097,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
 
             uint64_t path_samples = ( uint64_t )( scene->path_samples * diffuse_intensity );
             path_samples = ( path_samples == 0 ) ? 1 : path_samples;
+            if( c->tap ) { double* r = tap_row( c, ACN_ORACLE_TAP_PATHS ); r[ 1 ] = ( double )path_samples; }
 
             for( uint64_t i = 0; i < path_samples; i++ )
             {
@@ -1050,6 +1106,12 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
                 out.d = m3_mlv( &out_con, v3_random_sphere_cap( &rv, 1.0 ) );
                 if( shard_skips_sample( c, i, path_samples ) ) continue;
                 double weight = v3_mlv( out.d, surface.d );
+                double* tr = NULL;
+                if( c->tap )
+                {
+                    tr = tap_row( c, ACN_ORACLE_TAP_PATH );
+                    tr[ 1 ] = ( double )i; TAP_V3( tr + 2, out.d ); tr[ 5 ] = weight; tr[ 7 ] = F3_INF; tr[ 11 ] = -1; tr[ 12 ] = -1;
+                }
                 if( weight <= 0 ) continue;
                 COST( c, ACN_F_PATH_TAIL, 0 );
 
@@ -1057,8 +1119,14 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
 
                 trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
                 double a = compound_ray_trans_hit( c, c->sc->matter_root, &out, &trans_l );
+                if( tr )
+                {
+                    tr[ 6 ] = weight; tr[ 7 ] = a; TAP_V3( tr + 8, trans_l.exit_nor ); tr[ 11 ] = trans_l.exit_obj; tr[ 12 ] = trans_l.enter_obj;
+                    tr[ 13 ] = weight * diffuse_intensity; tr[ 14 ] = a < scene->max_path_length;
+                }
 
-                if( a < scene->max_path_length )
+                if( c->tap && a < scene->max_path_length ) {}   /* the hit is the caller's next point */
+                else if( a < scene->max_path_length )
                 {
                     c->level++;
                     v3 lum_c = scene_lum( c, &out, a, &trans_l, depth - 10, weight * diffuse_intensity );
@@ -1092,7 +1160,8 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
         double a;
         v3 lum_l = { 0, 0, 0 };
-        if( ( a = scene_trans_hit( c, &out, &trans_l ) ) < F3_INF )
+        if( c->tap ) tap_child( c, ACN_ORACLE_TAP_REFRACTION, &out, intensity, depth - 1, V( 1, 1, 1 ) );
+        else if( ( a = scene_trans_hit( c, &out, &trans_l ) ) < F3_INF )
         {
             lum_l = scene_lum( c, &out, a, &trans_l, depth - 1, intensity );
         }
@@ -1110,6 +1179,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         double rf = offs > 0 ? M_POW( exit_obj->transparency[ 0 ], offs ) : 1.0;
         double gf = offs > 0 ? M_POW( exit_obj->transparency[ 1 ], offs ) : 1.0;
         double bf = offs > 0 ? M_POW( exit_obj->transparency[ 2 ], offs ) : 1.0;
+        if( c->tap ) { double* r = tap_row( c, ACN_ORACLE_TAP_ABSORB ); tap_v3( r + 1, rf, gf, bf ); }
         lum.x *= rf;
         lum.y *= gf;
         lum.z *= bf;
@@ -1520,3 +1590,21 @@ int acn_oracle_query_rays( const acn_flat_scene* scene, int op, int32_t node, co
 uint64_t acn_oracle_random_seed( const double* v, uint64_t rv ) { return v3_random_seed( v3_ld( v ), rv ); }
 
 void acn_oracle_sphere_cap( uint64_t* rv, double h, double* out3 ) { st3( out3, v3_random_sphere_cap( rv, h ) ); }
+
+/* ---- the tap: scene_lum for one hit, recorded ---------------------------------------------------------------------- */
+int acn_oracle_shade_point( const acn_flat_scene* scene, const double* hit, double* rows, size_t room, size_t* n_rows, double* out_lum3 )
+{
+    if( !scene || !hit || !n_rows || ( room && !rows ) ) return -1;
+    int st = validate( scene );
+    if( st ) return st;
+    const int exit_obj = ( int )hit[ 10 ], enter_obj = ( int )hit[ 11 ];
+    if( exit_obj < -1 || exit_obj >= ( int )scene->n_nodes || enter_obj < -1 || enter_obj >= ( int )scene->n_nodes || hit[ 12 ] < 0 ) return -1;
+    tap_t tap = { rows, room, 0, { 0 } };
+    ctx_t c = { scene, NULL, 0, 1, 0, &tap };
+    ray_t ray = { v3_ld( hit ), v3_ld( hit + 3 ) };
+    trans_t trans = { v3_ld( hit + 7 ), exit_obj, enter_obj };
+    v3 lum = scene_lum( &c, &ray, hit[ 6 ], &trans, ( uint64_t )hit[ 12 ], hit[ 13 ] );
+    if( out_lum3 ) st3( out_lum3, lum );
+    *n_rows = tap.n;
+    return 0;
+}

@@ -84,6 +84,30 @@ double acn_oracle_trans_hit( const acn_flat_scene* scene, const double* ray_p3, 
 enum { ACN_ORACLE_Q_OBJ_RAY_HIT = 0, ACN_ORACLE_Q_OBJ_SIDE, ACN_ORACLE_Q_COMPOUND_RAY_HIT, ACN_ORACLE_Q_TRANS_HIT, ACN_ORACLE_Q_OCCLUDED,
        ACN_ORACLE_Q_N };
 #define ACN_ORACLE_QUERY_STRIDE 8
+
+/* The tap: scene_s_lum (src/scene.c:420-667) for ONE hit, without recursing, recorded.  scene_lum itself writes the rows while it
+ * runs (the arithmetic is not restated); where the reference would call itself for a child, the row holds the arguments of that call.
+ * hit: [ 14 ] ray origin[3], direction[3], offs, exit normal[3], exit object, enter object (-1: none), depth, intensity.
+ * rows: [ room ][ ACN_ORACLE_TAP_STRIDE ] doubles, row[ 0 ] the kind, in the order scene_s_lum computes them; *n_rows: the rows the hit
+ * has (above room: the rest was not written).  out_lum3 (nullable): what the call returns with every child's radiance zero.
+ *   EMISSION    [1..3] the returned colour, [4] diff_sqr, [5] light_intensity                     (the only row of such a hit)
+ *   SURFACE     [1..3] pos, [4..6] enter_color, [7] trix, [8] on_a, [9] on_b, [10] fresnel, [11] chromatic, [12] diffuse
+ *               reflectivity, [13] transparent
+ *   FRESNEL, CHROMATIC, REFRACTION   a specular child: [1..3] origin, [4..6] direction, [7] intensity, [8] depth, [9..11] the colour
+ *               multiplied onto what it returns
+ *   DIFFUSE     [1..3] surface_d, [4] theta_i, [5..7] ray_projection, [8] diffuse_intensity, [9] rv (raw 64 bits), [10] depth
+ *   LIGHT       [1] light node, [2] cyl_hgt, [3..5] colour, [6] direct samples, [7..9] axis of the sampling cone
+ *   DIRECT      sample j of the light before: [1] j, [2] light node, [3..5] out_d, [6] raw weight, [7] light-hit distance (inf: none,
+ *               or not asked because weight <= 0), [8] exact Oren-Nayar weight, [9] 1: occluded, [10] local_intensity, [11] the
+ *               term local_intensity * weight * diffuse_intensity ([8] .. [11] zero where the sample did not get that far)
+ *   PATHS       [1] path samples
+ *   PATH        sample j: [1] j, [2..4] out_d, [5] raw weight, [6] exact weight, [7] a, [8..10] exit normal, [11] exit, [12] enter
+ *               object, [13] weight * diffuse_intensity, [14] 1: a < max_path_length, the reference recurses
+ *   ABSORB      [1..3] the factors on everything the call returns */
+enum { ACN_ORACLE_TAP_EMISSION = 0, ACN_ORACLE_TAP_SURFACE, ACN_ORACLE_TAP_FRESNEL, ACN_ORACLE_TAP_CHROMATIC, ACN_ORACLE_TAP_REFRACTION,
+       ACN_ORACLE_TAP_DIFFUSE, ACN_ORACLE_TAP_LIGHT, ACN_ORACLE_TAP_DIRECT, ACN_ORACLE_TAP_PATHS, ACN_ORACLE_TAP_PATH, ACN_ORACLE_TAP_ABSORB };
+#define ACN_ORACLE_TAP_STRIDE 16
+int acn_oracle_shade_point( const acn_flat_scene* scene, const double* hit, double* rows, size_t room, size_t* n_rows, double* out_lum3 );
 int acn_oracle_query_rays( const acn_flat_scene* scene, int op, int32_t node, const double* rays, size_t n, const double* limits,
                            double* out, int threads );
 uint64_t acn_oracle_random_seed( const double* v3, uint64_t rv );

@@ -20,6 +20,10 @@ void detmath_eval( int op, const double* x, const double* y, double* out, size_t
             case 8: r = a / b; break;
             case 9: r = ( double )acn_f64_bits( a ); break;
             case 10: r = acn_frexp_mant( a ); break;
+            case 11: r = acn_asin( a ); break;
+            case 12: r = acn_atan( a ); break;
+            case 13: r = acn_atan2( a, b ); break;
+            case 14: r = ( double )acn_llrint( a ); break;   /* |a| < 2^62 (the conversion is undefined beyond long long) */
             default: break;
         }
         out[ i ] = r;

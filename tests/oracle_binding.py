@@ -41,6 +41,7 @@ class Oracle:
         L.acn_oracle_sphere_cap.argtypes = [vp, C.c_double, vp]
         L.acn_oracle_sphere_cap.restype = None
         L.acn_oracle_query_rays.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, C.c_int]
+        L.acn_oracle_shade_point.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
 
     def math_mode(self):
         return self.lib.acn_oracle_math_mode()
@@ -145,3 +146,23 @@ class Oracle:
     def trans_hits(self, flat, node, rays, threads=16):
         o = self.query_rays(flat, "trans_hit", node, rays, threads=threads)
         return o[:, 0], o[:, 1:4], o[:, 4].astype(np.int64), o[:, 5].astype(np.int64)
+
+    # the rows of acn_oracle_shade_point (oracle/acn_oracle.h)
+    TAP = {"emission": 0, "surface": 1, "fresnel": 2, "chromatic": 3, "refraction": 4, "diffuse": 5, "light": 6, "direct": 7, "paths": 8,
+           "path": 9, "absorb": 10}
+    TAP_STRIDE = 16
+
+    def shade_point(self, flat, hit):
+        """scene_s_lum for one hit without recursing: (rows [k, 16], lum [3]).  hit: [14] ray origin, direction, offs, exit normal,
+        exit object, enter object, depth, intensity."""
+        hit = np.ascontiguousarray(hit, dtype=np.float64).reshape(14)
+        lum, n = np.zeros(3), C.c_size_t(0)
+        room = 64
+        while True:
+            rows = np.zeros((room, self.TAP_STRIDE), dtype=np.float64)
+            st = self.lib.acn_oracle_shade_point(C.addressof(flat.c), hit.ctypes.data, rows.ctypes.data, room, C.byref(n), lum.ctypes.data)
+            if st != 0:
+                raise RuntimeError(f"oracle status {st}")
+            if n.value <= room:
+                return rows[:n.value], lum
+            room = n.value

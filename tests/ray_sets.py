@@ -976,3 +976,404 @@ def rough_distance_scene_rays(rng, oracle, flat, per=80):
     rs.extend(secondary(rng, oracle, flat, rs.rays[pick], a[pick], nor[pick], n_refract=60))
     rs.extend(far(rng, np.zeros(3), 8.0, 200))
     return rs
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the scenes of the shading stages (tests/test_gpu_stages.py, tests/test_stages_cpu.py)
+
+STAGE_MATTER = ("floor", "wall", "mirror", "chromatic", "water", "glass", "glass_core", "rough", "occluder", "csg", "torus")
+STAGE_LIGHTS = ("sphere_light", "plane_light", "pair_light")
+# of the torus element: the shading points of the tests lie inside, so every shadow ray enters it.  (The in-line pass of k_shade leaves
+# a distance object or a nested compound to the machine whenever the ray hits its envelope; a CSG pair it may still rule out itself,
+# by surely_outside or its prune program, so the pair's own envelope does not keep a sample out of the in-line sums.)
+STAGE_ENVELOPE = ((0.0, 0.0, 2.0), 12.0)
+STAGE_LIMIT_R = 1.0                        # radius of the spheres that path rays meet at max_path_length (stage_limit_cases)
+
+
+def shade_stage_scene(pair_light=False, direct_samples=200, path_samples=200, limit_spheres=True, **params):
+    """Scene A of the stage tests, and with pair_light scene B (a light that is no leaf: k_shade< LEAF_LIGHTS = false >).
+    A "diffuse" floor (sigma 0.29), a "diffuse_polished" wall, a perfect mirror, a coloured chromatic 0.7 sphere, coloured glass
+    inside water with a core of the glass's index (trix above 1, below 1 and exactly 1 between them), a diffuse sphere with a
+    roughness call, a plain sphere in the line of the lights, a torus-and-ball pair, and a torus whose envelope encloses where the
+    tests shade: a shadow ray that starts there is never decided in line.  limit_spheres: far outside, the six plain spheres of
+    stage_limit_cases, each at max_path_length (or a neighbour of it) along one path sample of a task of scene A.  Lights: a sphere of radius 0.5 with a chess texture, a plane.
+    params: acn_params fields set after the scene's own.  Returns (scene, node): node[ name ] after flattening is the node index of
+    the object."""
+    rng = np.random.default_rng(11)
+    sc = A.Scene()
+    sc.set(image_width=32, image_height=32, gamma=1.0, trace_depth=22, trace_min_intensity=0.002, direct_samples=direct_samples,
+           path_samples=path_samples, max_path_length=30.0, camera_position=(0, -8, 3), camera_view_direction=(0, 8, -2),
+           camera_top_direction=(0, 0, 1), camera_focal_length=3, background_color=(0.3, 0.35, 0.4))
+    sc.set(**params)
+    order = []
+
+    def push(name, o):
+        sc.push(o)
+        host.acn_obj_discard(o)
+        order.append(name)
+
+    def ball(r, at, material, color=None):
+        o = host.acn_obj_sphere_s_create(float(r))
+        host.acn_obj_set_material(o, material)
+        if color is not None:
+            host.acn_obj_set_color(o, A.v3(*color))
+        host.acn_obj_move(o, A.v3(*at))
+        return o
+
+    light = host.acn_obj_sphere_s_create(0.5)
+    host.acn_obj_set_radiance(light, 40.0)
+    host.acn_obj_set_texture_field_chess(light, A.v3(1.0, 0.9, 0.7), A.v3(0.6, 0.7, 1.0), 3.0)
+    host.acn_obj_move(light, A.v3(0.5, -0.5, 5.0))
+    push("sphere_light", light)
+    light = host.acn_obj_plane_s_create()
+    m = host.acn_rotx(180.0)
+    host.acn_obj_rotate(light, C.byref(m))                     # faces down
+    host.acn_obj_set_color(light, A.v3(0.9, 1.0, 0.8))
+    host.acn_obj_set_radiance(light, 300.0)
+    host.acn_obj_move(light, A.v3(0.0, 0.0, 9.0))
+    push("plane_light", light)
+    if pair_light:
+        a, b = host.acn_obj_sphere_s_create(0.6), host.acn_obj_plane_s_create()
+        light = _pair_inside(a, b)
+        host.acn_obj_set_color(light, A.v3(1.0, 0.8, 0.8))
+        host.acn_obj_set_radiance(light, 30.0)
+        host.acn_obj_move(light, A.v3(-2.0, 1.0, 4.0))
+        host.acn_obj_set_envelope(light, A.v3(-2.0, 1.0, 4.0), 0.65)
+        push("pair_light", light)
+
+    o = host.acn_obj_plane_s_create()
+    host.acn_obj_set_material(o, b"diffuse")
+    host.acn_obj_set_color(o, A.v3(0.8, 0.7, 0.6))
+    push("floor", o)
+    o = host.acn_obj_plane_s_create()
+    host.acn_obj_set_material(o, b"diffuse_polished")
+    host.acn_obj_set_color(o, A.v3(0.5, 0.8, 0.9))
+    m = host.acn_rotx(90.0)
+    host.acn_obj_rotate(o, C.byref(m))
+    host.acn_obj_move(o, A.v3(0.0, 6.0, 0.0))
+    push("wall", o)
+    push("mirror", ball(1.0, (-3.0, 0.5, 1.0), b"perfect_mirror"))
+    o = ball(0.8, (-1.0, 2.5, 0.8), b"mirror", (0.9, 0.5, 0.3))
+    host.acn_obj_set_chromatic_reflectivity(o, 0.7)
+    host.acn_obj_set_diffuse_reflectivity(o, 1.0)
+    push("chromatic", o)
+    push("water", ball(1.2, (3.0, 0.5, 1.2), b"water"))
+    o = ball(0.7, (3.0, 0.5, 1.2), b"glass")
+    host.acn_obj_set_transparency(o, A.v3(0.6, 0.9, 0.7))
+    push("glass", o)
+    push("glass_core", ball(0.3, (3.0, 0.5, 1.2), b"glass"))
+    o = ball(0.8, (0.5, -2.0, 0.8), b"diffuse", (0.7, 0.8, 0.5))
+    host.acn_obj_set_surface_roughness(o, 0.1)
+    push("rough", o)
+    push("occluder", ball(0.4, (0.4, -0.4, 2.6), b"diffuse"))
+    t = host.acn_obj_torus_create(0.5, 0.18)
+    host.acn_obj_set_material(t, b"diffuse")
+    o = _pair_inside(_place(t, rng, spread=0.1), ball(0.5, (0.3, 0.1, 0.0), b"diffuse"))
+    host.acn_obj_move(o, A.v3(-1.5, -1.5, 3.0))
+    host.acn_obj_set_envelope(o, A.v3(-1.5, -1.5, 3.0), 1.2)
+    push("csg", o)
+    t = host.acn_obj_torus_create(0.4, 0.12)
+    host.acn_obj_set_material(t, b"diffuse")
+    host.acn_obj_move(t, A.v3(1.8, 1.6, 3.2))
+    host.acn_obj_set_envelope(t, A.v3(*STAGE_ENVELOPE[0]), STAGE_ENVELOPE[1])
+    push("torus", t)
+    if limit_spheres:
+        for k, case in enumerate(stage_limit_cases()):
+            push("limit%d" % k, ball(STAGE_LIMIT_R, case["centre"], b"diffuse"))
+
+    flat = sc.flatten()
+    lights, matter = flat.elems_of(flat.c.light_root), flat.elems_of(flat.c.matter_root)
+    names_l = [n for n in order if n in STAGE_LIGHTS]
+    names_m = [n for n in order if n not in STAGE_LIGHTS]
+    assert len(lights) == len(names_l) and len(matter) == len(names_m), (len(lights), len(matter))
+    node = dict(zip(names_l, lights))
+    node.update(zip(names_m, matter))
+    return sc, node
+
+
+STAGE_N = (1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 63, 64, 65, 200)   # sample counts of the sample test: around every lane width
+_LIMIT_CASES = []
+
+
+def _sample_point(dtype, prm, fl, pos, nor_up, d, n, depth, T, offs=1.0):
+    """a hit record on the floor's material that shades at pos with surface direction nor_up (the side the samples go to), seen along d,
+    with n samples per loop"""
+    pos, d = np.asarray(pos, dtype=np.float64), unit(np.asarray(d, dtype=np.float64))
+    samples = max(prm.direct_samples, prm.path_samples)
+    return _hit(dtype, pos - d * offs, d, offs, -unit(np.asarray(nor_up, dtype=np.float64)), -1, fl, depth, (n + 0.5) / samples, T)
+
+
+def stage_limit_cases():
+    """Path hits AT max_path_length.  For scene A with its own sampling parameters: six tasks far outside the scene, and for each a
+    plain sphere placed on the ray of one of its path samples so that the oracle's hit distance is max_path_length exactly, its
+    predecessor or its successor (the centre is stepped along the ray and by ulps of its coordinates until sphere_ray_hit says so).  Group "inline": the
+    ray's line misses the torus' envelope and the sample is bright, so k_shade decides it itself: a child below the limit, a background
+    term at and above it.  Group "probe": the line enters the envelope beyond the sphere and the sample is dark (weight *
+    diffuse_intensity below trace_min_intensity), so it is an any-hit probe with limit "largest double below max_path_length": not
+    written where the sphere is hit below the limit, written at and above it.  The draws of a task depend on its position and normal
+    alone, so the cases are found on the scene without the spheres.  Returns dicts: hit (the record), j, target, group, kind, centre."""
+    if _LIMIT_CASES:
+        return _LIMIT_CASES
+    from oracle_binding import Oracle
+    import shade_model as M
+    oracle = Oracle()
+    sc, node = shade_stage_scene(limit_spheres=False)
+    flat = sc.flatten()
+    prm = flat.params
+    dtype = A.Handle.STAGE_RECORDS["hit"]
+    rng = np.random.default_rng(41)
+    c_env, r_env = np.array(STAGE_ENVELOPE[0]), STAGE_ENVELOPE[1]
+    lim = prm.max_path_length
+    targets = (("below", np.nextafter(lim, 0.0)), ("at", lim), ("above", np.nextafter(lim, np.inf)))
+    kinds = {("inline", "below"): "child", ("inline", "at"): "bsum", ("inline", "above"): "bsum",
+             ("probe", "below"): "none", ("probe", "at"): "probe", ("probe", "above"): "probe"}
+    cases = []
+    for group in ("inline", "probe"):
+        for k, (name, target) in enumerate(targets):
+            found = None
+            for _ in range(20000):
+                if group == "inline":
+                    pos = np.array([100.0 + 60.0 * k + rng.uniform(0, 20), 100.0 + rng.uniform(0, 20), 40.0])
+                    nor_up, n = np.array([0.0, 0.0, -1.0]), 17
+                else:
+                    u = unit(rng.normal(size=3) + np.array([0.0, 0.0, 1.5]))
+                    # the three cases look from different sides, all from above the plane light: of their direct samples the plane's
+                    # miss it and the sphere's enter the envelope, so none is decided in line
+                    u = unit(np.array([u[0] + 2.0 * (k - 1), u[1], abs(u[2]) + 1.0]))
+                    pos = c_env + u * 45.0
+                    t = unit(np.cross(u, rng.normal(size=3)))
+                    nor_up, n = unit(t - u * 0.03), 5
+                t2 = unit(np.cross(nor_up, rng.normal(size=3)))
+                hit = _sample_point(dtype, prm, node["floor"], pos, nor_up, -nor_up + 0.2 * t2, n, int(prm.trace_depth), rng.uniform(0.3, 1.0, 3))
+                rows = oracle.shade_point(flat, M.tap_input(hit))[0]
+                pos = M.rows_of(rows, "surface")[0, 1:4]
+                for r in M.rows_of(rows, "path"):
+                    d = r[2:5]
+                    tca = float((c_env - pos) @ d)
+                    off2 = float((c_env - pos) @ (c_env - pos)) - tca * tca
+                    enters = tca > 0 and off2 < (0.9 * r_env) ** 2
+                    clear = tca <= 0 or off2 > (1.1 * r_env) ** 2
+                    dark = r[13] < prm.trace_min_intensity
+                    if not (r[5] > 0 and r[7] > lim + 2.5) or any(np.linalg.norm(np.cross(c["centre"] - pos, d)) < 1.5 for c in cases):
+                        continue
+                    if (group == "inline" and clear and not dark) or (group == "probe" and enters and dark):
+                        found = (hit, int(r[1]), pos, d)
+                        break
+                if found:
+                    break
+            assert found, (group, name)
+            hit, j, pos, d = found
+            centre = None
+            far = lim + STAGE_LIMIT_R
+            far += target - oracle.sphere_ray_hit(pos + d * far, STAGE_LIMIT_R, pos, d)[0]      # (the hit routine has its own f3_eps)
+            # (the centre's coordinates are coarser than the distance: its neighbours in each coordinate are tried as well)
+            for step in range(-40, 40):
+                c0 = pos + d * (far + step * 2.0 ** -49)
+                for sh in np.ndindex(5, 5, 5):
+                    c = c0 + (np.array(sh) - 2) * np.spacing(c0)
+                    if oracle.sphere_ray_hit(c, STAGE_LIMIT_R, pos, d)[0] == target:
+                        centre = c
+                        break
+                if centre is not None:
+                    break
+            assert centre is not None, (group, name)
+            cases.append({"hit": hit, "j": j, "target": target, "group": group, "kind": kinds[(group, name)], "centre": centre})
+    _LIMIT_CASES.extend(cases)
+    return _LIMIT_CASES
+
+
+def _hit(dtype, p, d, offs, exit_nor, exit_obj, enter_obj, depth, intensity, T):
+    r = np.zeros((), dtype=dtype)
+    r["p"], r["d"], r["offs"], r["exit_nor"], r["T"], r["intensity"] = p, d, offs, exit_nor, T, intensity
+    r["exit_obj"], r["enter_obj"], r["depth"] = exit_obj, enter_obj, depth
+    return r
+
+
+def stage_base_hits(oracle, flat, node, dtype, seed=21):
+    """Transition hits of the oracle on rays aimed at every object of the stage scene from outside, and from inside the water, the
+    glass and its core: hit records with intensity 1, the scene's trace_depth and a random throughput."""
+    rng = np.random.default_rng(seed)
+    depth = int(flat.params.trace_depth)
+    rays = []
+    eye = np.array([0.0, -8.0, 3.0])
+    for name in STAGE_MATTER + STAGE_LIGHTS:
+        if name not in node:
+            continue
+        c, r = node_ball(flat, node[name], default_r=2.0)
+        c = np.array([0.0, 0.0, 0.0]) if name == "floor" else np.array([0.0, 6.0, 2.0]) if name == "wall" else np.array([0.0, 0.0, 9.0]) if name == "plane_light" else c
+        for _ in range(6):
+            t = c + rng.uniform(-0.6, 0.6, 3) * min(r, 2.0)
+            rays.append(np.concatenate([eye, unit(t - eye)]))
+    gc = np.array(list(flat.node(node["glass"]).pos))
+    for rad in (0.1, 0.5, 1.0):                       # inside the core, the glass, the water
+        for _ in range(8):
+            o = gc + unit(rng.normal(size=3)) * rad
+            rays.append(np.concatenate([o, unit(rng.normal(size=3))]))
+    out = []
+    for ry in rays:
+        a, nor, ex, en = oracle.trans_hit(flat, ry[:3], ry[3:])
+        if a < np.inf:
+            out.append(_hit(dtype, ry[:3], ry[3:], a, nor, ex, en, depth, 1.0, rng.uniform(0.2, 1.0, 3)))
+    return out
+
+
+def stage_split_hits(oracle, flat, node, dtype, seed=22):
+    """The records of the split test: every base hit under the intensities and depths at which shade_hit's guards turn, the sample
+    counts on an integer and one ulp either side, media set by hand (trix above, below and exactly 1), incidence at the normal and
+    1e-8 from grazing, offs = 0 on an exit, a point at a light's pos, and dead slots.  pixel = index."""
+    rng = np.random.default_rng(seed)
+    prm = flat.params
+    tmin, depth = prm.trace_min_intensity, int(prm.trace_depth)
+    base = stage_base_hits(oracle, flat, node, dtype)
+    recs = []
+
+    def add(r, **kw):
+        r = r.copy()
+        for k, v in kw.items():
+            r[k] = v
+        recs.append(r)
+
+    intens = (1.0, tmin, np.nextafter(tmin, 0.0), np.nextafter(tmin, 1.0), 0.5)
+    depths = (0, 1, 10, 11, 12, depth)
+    for k, b in enumerate(base):
+        for i in intens:
+            for d in (depths if k % 3 == 0 else (depths[(k + int(i * 7)) % 6], depth)):
+                add(b, intensity=i, depth=d)
+    # direct_samples * diffuse_intensity and path_samples * diffuse_intensity on an integer and one ulp either side (the floor: reflectivity 1)
+    floor_hits = [b for b in base if b["enter_obj"] == node["floor"] and b["exit_obj"] < 0]
+    assert floor_hits
+    for b in floor_hits[:3]:
+        for n in (7, 8, 9, 16, 17, 64, 65, 199):
+            for samples in (prm.direct_samples, prm.path_samples):
+                v = n / samples
+                for i in (np.nextafter(v, 0.0), v, np.nextafter(v, 1.0)):
+                    add(b, intensity=i)
+    # more samples than any class0_min (the 64-lane class begins above 32 or 255, as the upload decides): 256, 257 and 300 of them
+    for b in floor_hits[:2]:
+        for n in (256, 257, 300):
+            add(b, intensity=(n + 0.25) / prm.direct_samples)
+    # media by hand: the stage takes any pair of objects
+    w, g, gcore = node["water"], node["glass"], node["glass_core"]
+    inside = [b for b in base if b["exit_obj"] >= 0]
+    assert inside
+    for b in inside:
+        for ex, en in ((g, w), (w, g), (g, gcore), (gcore, g), (g, -1), (w, -1), (-1, g), (-1, w)):
+            add(b, exit_obj=ex, enter_obj=en)
+            add(b, exit_obj=ex, enter_obj=en, offs=0.0, p=ray_pos(b["p"], b["d"], b["offs"]))
+    # the critical angle inside the glass against water: sin( theta ) * trix = 1, and the direction's component +- 1, 2 ulp
+    trix = flat.node(w).refractive_index / flat.node(g).refractive_index
+    nor = np.array([0.0, 0.0, 1.0])
+    s = 1.0 / trix if trix > 1 else trix          # sin of the critical angle on the dense side
+    for ex, en in ((g, w), (w, g)):
+        for k in (-2, -1, 0, 1, 2):
+            sx = s
+            for _ in range(abs(k)):
+                sx = np.nextafter(sx, 2.0 if k > 0 else 0.0)
+            d = np.array([sx, 0.0, np.sqrt(1.0 - sx * sx)])
+            add(_hit(dtype, (3.0, 0.5, 1.2), d, 0.4, nor, ex, en, depth, 1.0, (0.9, 0.8, 0.7)))
+    # incidence at the normal (the projection onto the surface is the zero vector) and 1e-8 from grazing
+    fl, rg = node["floor"], node["rough"]
+    for en in (fl, node["wall"], node["chromatic"]):
+        add(_hit(dtype, (0.3, 0.2, 2.0), (0.0, 0.0, -1.0), 2.0, (0.0, 0.0, -1.0), -1, en, depth, 1.0, (0.7, 0.9, 0.8)))
+        gz = unit(np.array([1.0, 0.0, -1e-8]))
+        add(_hit(dtype, (-1.0, 0.2, 1e-8), gz, 1.0, (0.0, 0.0, -1.0), -1, en, depth, 1.0, (0.7, 0.9, 0.8)))
+    # a normal that faces away from the ray (a rough surface's): theta_i above pi / 2
+    add(_hit(dtype, (0.5, -4.0, 0.8), (0.0, 1.0, 0.0), 1.2, unit(np.array([0.1, -0.2, 1.0])), -1, rg, depth, 1.0, (1.0, 1.0, 1.0)))
+    # a hit on each light, and one at a light's pos exactly (diff_sqr == 0: F3_MAG, which the fixed-point sum clamps)
+    for name in STAGE_LIGHTS:
+        if name in node:
+            lp = np.array(list(flat.node(node[name]).pos))
+            add(_hit(dtype, lp, (0.0, 0.0, 1.0), 0.0, (0.0, 0.0, 1.0), -1, node[name], depth, 1.0, (0.5, 0.25, 0.125)))
+            add(_hit(dtype, lp - (0.0, 0.0, 2.0), (0.0, 0.0, 1.0), 1.5, (0.0, 0.0, 1.0), -1, node[name], depth, 0.5, (0.5, 0.25, 0.125)))
+    out = np.array(recs, dtype=dtype)
+    out["pixel"] = np.arange(len(out))
+    dead = rng.choice(len(out), len(out) // 20, replace=False)
+    out["pixel"][dead] = 0xFFFFFFFF
+    return out
+
+
+def stage_sample_hits(flat, node, dtype, seed=23, oracle=None):
+    """The shading points of the sample test as hit records on the floor's material (the tap and the model make the tasks of them;
+    neither asks whether the point lies on the floor): every count of STAGE_N for both loops, with and without a path loop, inside
+    the CSG envelope and outside it, on and around the light's sphere, at its centre, 1e6 radii away, on both sides of the plane
+    light, the surface direction within 1e-9 .. 1e-3 rad of the light's axis, theta_i at pi / 2 and above, theta_i == theta_r for the
+    cone's axis, a sphere's distance at max_path_length (stage_limit_cases).  Tasks of more than one sample per loop lie inside the
+    torus' envelope, or ("outside") face away from both lights: nothing of them is decided in line but path rays; the in-line direct
+    samples are those of "outside_one", one sample per light, the plane light's in line.  With `oracle` the tasks of the split follow
+    ("split": every hit record of stage_split_hits that makes a task without Oren-Nayar term, a quarter of the others), so that the sample
+    loops also run without the Oren-Nayar term, with carried colours and on the rough sphere's normals.
+    Returns (records, labels, expect): expect[ ( task, j ) ] is what stage_limit_cases says path sample j of the task becomes."""
+    rng = np.random.default_rng(seed)
+    prm = flat.params
+    depth, fl = int(prm.trace_depth), node["floor"]
+    lp, lr = np.array(list(flat.node(node["sphere_light"]).pos)), flat.node(node["sphere_light"]).prm[0]
+    recs, labels = [], []
+
+    def point(label, pos, nor_up, d, n, depth=depth):
+        recs.append(_sample_point(dtype, prm, fl, pos, nor_up, d, n, depth, rng.uniform(0.3, 1.0, 3))); labels.append(label)
+
+    k = 0
+    for n in STAGE_N:
+        for dp in (depth, 12, 10):
+            for where in ("inside", "outside"):
+                if where == "inside":
+                    xy = rng.uniform(-2.5, 2.5, 2)
+                    point(where, (xy[0], xy[1], 0.0), (0, 0, 1), (rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), -1.0), n, dp)
+                else:   # a ceiling point: its samples go down to the floor, away from both lights
+                    point(where, (rng.uniform(-2, 2), 20.0 + rng.uniform(0, 2), 1.0), (0, 0, -1), (rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), 1.0), n, dp)
+                k += 1
+    for _ in range(12):
+        point("outside_one", (rng.uniform(-4, 4), 20.0 + rng.uniform(0, 4), 0.0), (0, 0, 1), (rng.uniform(-0.5, 0.5), rng.uniform(-0.5, 0.5), -1.0), 1, 10)
+    up = np.array([0.0, 0.0, 1.0])
+    for n in (1, 5, 17, 64):
+        u = unit(rng.normal(size=3))
+        point("far", lp + u * (1e6 * lr), -u, u + 0.3 * unit(np.cross(u, up)), n)
+        for label, pos in stage_light_sphere_points(lp, lr).items():
+            point(label, pos, (-1, 0, 0), (1.0, 0.3, 0.1), n)
+        point("centre", lp, up, -up, n)
+        for z in (8.0, 10.0):
+            point("plane_side", (0.3, 0.2, z), (0, 0, 1) if z < 9 else (0, 0, -1), (0.1, 0.0, -1.0 if z < 9 else 1.0), n)
+        for eps in (1e-9, 1e-6, 1e-3):
+            pos = np.array([1.0, 0.5, 0.0])
+            ax = unit(lp - pos)
+            t = unit(np.cross(ax, up))
+            point("axis", pos, ax * np.cos(eps) + t * np.sin(eps), (0.2, 0.1, -1.0), n)
+        for th in (np.pi / 2 - 1e-8, np.pi / 2, np.pi / 2 + 1e-8, 2.0):
+            point("grazing", (0.5, 0.5, 0.0), up, (np.sin(th), 0.0, -np.cos(th)), n)
+        # theta_i == theta_r for the axis of the cone: the ray comes in as the mirror image of the light's direction
+        pos = np.array([-0.5, 0.8, 0.0])
+        ax = unit(lp - pos)
+        point("tie", pos, up, ax - 2 * up * ax[2], n)
+    expect = {}
+    for case in stage_limit_cases():
+        expect[(len(recs), case["j"])] = case
+        r = case["hit"].copy()
+        r["enter_obj"] = fl                                   # (the floor's node of THIS scene)
+        recs.append(r); labels.append("path_limit")
+    if oracle is not None:
+        import shade_model as M
+        k = 0
+        for r in stage_split_hits(oracle, flat, node, dtype):
+            if r["pixel"] == 0xFFFFFFFF:
+                continue
+            rows = oracle.shade_point(flat, M.tap_input(r))[0]
+            df = M.rows_of(rows, "diffuse")
+            if not len(df) or not np.isfinite(df[0, 4]):      # (a NaN theta_i makes NaN weights, and which NaN is no part of the contract)
+                continue
+            k += 1
+            if M.rows_of(rows, "surface")[0, 9] > 0 and k % 4:
+                continue
+            recs.append(r.copy()); labels.append("split")
+    out = np.array(recs, dtype=dtype)
+    out["pixel"] = np.arange(len(out))
+    return out, np.array(labels, dtype=object), expect
+
+
+def stage_light_sphere_points(lp, lr):
+    """Points whose v_diff_sqr to the light's centre is radius^2 exactly, the double below it and the double above it (sphere_fov turns
+    at diff_sqr > radius_sqr): along x the difference 0.5 is exact, and a y offset of 2^-27 adds one ulp of 0.25; below, x steps in by
+    2^-53 (four ulps of the square) and y^2 = 3 * 2^-55 brings the sum back up to the neighbour of 0.25."""
+    assert lr == 0.5 and lp[0] == 0.5
+    return {"on_light": np.array([lp[0] + lr, lp[1], lp[2]]),
+            "off_light": np.array([lp[0] + lr, lp[1] + 2.0 ** -27, lp[2]]),
+            "in_light": np.array([lp[0] + (lr - 2.0 ** -53), lp[1] + np.sqrt(3 * 2.0 ** -55), lp[2]])}

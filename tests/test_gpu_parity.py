@@ -50,6 +50,28 @@ def test_detmath_bit_identical_cpu_gpu(detmath_cpu):
     assert np.array_equal(A.detmath_eval("u64_to_f64", u.view(np.float64)), u.astype(np.float64))
     sub = np.array([5e-324, 2.2e-308, 1e-310, 0.0, -0.0])
     assert np.array_equal(A.detmath_eval("sqrt", np.abs(sub)).view(np.uint64), np.sqrt(np.abs(sub)).view(np.uint64))
+    # what decides the cell of a chess texture (obj_color_dev): asin, atan, atan2, llrint, with the edges of tests/test_detmath.py.
+    # Where a result is a NaN, which NaN is not part of the contract: NaNs compare as NaNs
+    inf, nan = np.inf, np.nan
+
+    def same(op, x, y=None):
+        g, c = A.detmath_eval(op, x, y), cpu_eval(detmath_cpu, op, x, y)
+        isn = np.isnan(c)
+        assert np.array_equal(np.isnan(g), isn), op
+        assert np.array_equal(g[~isn].view(np.uint64), c[~isn].view(np.uint64)), op
+
+    e1 = np.array([0.0, -0.0, 2.0 ** -27, 0.5, 0.975, 1.0, -1.0, 1.0 + 2.0 ** -52, -1.0 - 2.0 ** -52, 5e-324, inf, nan])
+    same("asin", np.concatenate([rng.uniform(-1, 1, n), 1.0 - np.exp(rng.uniform(-36, 0, 4096)), e1, np.nextafter(e1, 2.0), np.nextafter(e1, -2.0)]))
+    e2 = np.array([0.0, -0.0, 2.0 ** -29, 0.4375, 0.6875, 1.0, 1.1875, 2.4375, 2.0 ** 66, 1e300, inf, -inf, nan])
+    same("atan", np.concatenate([rng.normal(size=n) * np.exp(rng.uniform(-30, 50, n)), e2, -e2, np.nextafter(e2, inf), np.nextafter(e2, -inf)]))
+    ay, ax = rng.normal(size=n) * np.exp(rng.uniform(-20, 20, n)), rng.normal(size=n) * np.exp(rng.uniform(-20, 20, n))
+    ax[:4096] = 1.0
+    ev = np.array([0.0, -0.0, 1.0, -1.0, 2.0, -2.0, 5e-324, -5e-324, 1e-300, -1e-300, 1e300, -1e300, inf, -inf, nan])
+    same("atan2", np.concatenate([ay, np.repeat(ev, ev.size)]), np.concatenate([ax, np.tile(ev, ev.size)]))   # every pair of the edges
+    k = np.concatenate([np.arange(-9, 10), [2 ** 31, 2 ** 32, 2 ** 51, -2 ** 51, 2 ** 52 - 2, -(2 ** 52) + 2]]).astype(np.float64)
+    h = k + 0.5
+    same("llrint", np.concatenate([rng.uniform(-1e6, 1e6, n // 2), rng.normal(size=n // 2) * np.exp(rng.uniform(-5, 38, n // 2)), h, np.nextafter(h, inf),
+                                   np.nextafter(h, -inf), k, [0.0, -0.0, 0.49999999999999994, 5e-324, 2.0 ** 53, 2.0 ** 62 - 512, -(2.0 ** 62) + 512]]))
 
 
 @pytest.mark.parametrize("count_work", [False, True], ids=["production_kernels", "instrumented_kernels"])
