@@ -13,13 +13,16 @@
  *                  LENS_TILE_K * 24 bytes), and lane t < 3 * positions then adds channel t % 3 of position t / 3 from LDS, alone
  *                  and in the order of k: ( ( 0.0 + L0 ) + L1 ) + ...  No lane reads another lane's registers and no sum is
  *                  split, so a result does not depend on which positions share a wavefront or a workgroup.
- *   k_lens_reduce_stats  the sibling of k_lens_reduce behind acn_render_lens_stats*, on the same tiling: pass 1 is that sum, pass 2
+ *                  lens_stage copies a tile, for this kernel and both passes of the next.
+ *   k_lens_reduce_stats  k_lens_reduce with the record of every position, behind acn_render_lens_stats*: pass 1 is that sum, pass 2
  *                  stages the tiles again (not when K <= LENS_TILE_K: the one tile is still in LDS) and the same lane adds the
  *                  squared deviations from its mean in the order of k.  The 64-byte records of the workgroup are put together in
  *                  LDS and leave as 16-byte pieces, consecutive lanes on consecutive pieces: 64 positions are one run of 4 KiB.
- *   k_stats_merge, k_stats_resolve  one record per lane, read and written as four 16-byte pieces. */
+ *   k_stats_merge, k_stats_resolve  one record per lane, read and written as four 16-byte pieces; the record's rules (EMPTY, the
+ *                  variance of the mean) are those of acn_stats_dev.h, which the filters read too. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
+#include "acn_stats_dev.h"
 
 #define LENS_TILE_POS 64
 #define LENS_TILE_K   16
@@ -74,6 +77,17 @@ void k_lens_rays( DevScene sc, const double* __restrict__ pos_xy, size_t first_p
     r[ 3 ] = d.x; r[ 4 ] = d.y; r[ 5 ] = d.z;
 }
 
+/* samples [ k0, k0 + row / 3 ) of the workgroup's positions [ p0, p0 + np ) -> LDS, consecutive lanes on consecutive doubles.  The
+ * barriers around it are the caller's */
+__device__ static inline void lens_stage( double* tile, const double* __restrict__ rad, size_t p0, uint32_t np, uint32_t K, uint32_t k0, uint32_t row )
+{
+    for( uint32_t idx = threadIdx.x; idx < np * row; idx += 256 )
+    {
+        const uint32_t p = idx / row, r = idx - p * row;
+        tile[ idx ] = rad[ ( ( p0 + p ) * K + k0 ) * 3 + r ];
+    }
+}
+
 __global__ __launch_bounds__( 256 )
 void k_lens_reduce( const double* __restrict__ rad, size_t n, uint32_t K, double gamma, int linear, double* __restrict__ out_rgb )
 {
@@ -87,11 +101,7 @@ void k_lens_reduce( const double* __restrict__ rad, size_t n, uint32_t K, double
     for( uint32_t k0 = 0; k0 < K; k0 += LENS_TILE_K )
     {
         const uint32_t kc = K - k0 < LENS_TILE_K ? K - k0 : LENS_TILE_K, row = kc * 3;
-        for( uint32_t idx = tid; idx < np * row; idx += 256 )
-        {
-            const uint32_t p = idx / row, r = idx - p * row;
-            tile[ idx ] = rad[ ( ( p0 + p ) * K + k0 ) * 3 + r ];
-        }
+        lens_stage( tile, rad, p0, np, K, k0, row );
         __syncthreads();
         if( adds ) for( uint32_t k = 0; k < kc; k++ ) sum = sum + tile[ my_p * row + k * 3 + my_c ];
         __syncthreads();
@@ -120,11 +130,7 @@ void k_lens_reduce_stats( const double* __restrict__ rad, size_t n, uint32_t K, 
     {
         const uint32_t kc = K - k0 < LENS_TILE_K ? K - k0 : LENS_TILE_K, row = kc * 3;
         if( k0 ) __syncthreads();   /* (the adds of the tile before) */
-        for( uint32_t idx = tid; idx < np * row; idx += 256 )
-        {
-            const uint32_t p = idx / row, r = idx - p * row;
-            tile[ idx ] = rad[ ( ( p0 + p ) * K + k0 ) * 3 + r ];
-        }
+        lens_stage( tile, rad, p0, np, K, k0, row );
         __syncthreads();
         if( adds ) for( uint32_t k = 0; k < kc; k++ ) sum = sum + tile[ my_p * row + k * 3 + my_c ];
     }
@@ -136,11 +142,7 @@ void k_lens_reduce_stats( const double* __restrict__ rad, size_t n, uint32_t K, 
         if( K > LENS_TILE_K )   /* else the one tile of pass 1 is still there */
         {
             __syncthreads();
-            for( uint32_t idx = tid; idx < np * row; idx += 256 )
-            {
-                const uint32_t p = idx / row, r = idx - p * row;
-                tile[ idx ] = rad[ ( ( p0 + p ) * K + k0 ) * 3 + r ];
-            }
+            lens_stage( tile, rad, p0, np, K, k0, row );
             __syncthreads();
         }
         if( adds ) for( uint32_t k = 0; k < kc; k++ )
@@ -160,9 +162,6 @@ void k_lens_reduce_stats( const double* __restrict__ rad, size_t n, uint32_t K, 
     __syncthreads();
     if( tid < np * 4 ) stats[ p0 * 4 + tid ] = rec[ tid ];
 }
-
-/* a record whose [ 0 ] is not a finite number >= 1 is EMPTY (a NaN fails both comparisons) */
-__device__ static inline bool stats_empty( double n ) { return !( n >= 1.0 && n < __builtin_inf() ); }
 
 /* acc[ i ] <- merge( acc[ i ], part[ j ] ), i = index ? index[ j ] : j; an i outside [ 0, n_acc ) is skipped: nothing is read or written */
 __global__ __launch_bounds__( 256 )
@@ -213,7 +212,7 @@ void k_stats_resolve( const double2* __restrict__ stats, size_t n, double bg_x, 
         double noise = __builtin_inf();
         if( !empty && cnt > 1.0 )
         {
-            const double vx = ( r2.x / ( cnt - 1.0 ) ) / cnt, vy = ( r2.y / ( cnt - 1.0 ) ) / cnt, vz = ( r3.x / ( cnt - 1.0 ) ) / cnt;
+            const double vx = stats_var_of_mean( r2.x, cnt ), vy = stats_var_of_mean( r2.y, cnt ), vz = stats_var_of_mean( r3.x, cnt );
             const double lum = ( 0.2126 * r0.y + 0.7152 * r1.x ) + 0.0722 * r1.y;
             noise = acn_sqrt( ( ( 0.2126 * 0.2126 ) * vx + ( 0.7152 * 0.7152 ) * vy ) + ( 0.0722 * 0.0722 ) * vz ) / ( acn_fabs( lum ) + ACN_STATS_NOISE_FLOOR );
         }

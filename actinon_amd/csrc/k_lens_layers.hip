@@ -1,151 +1,50 @@
 /* k_lens_layers.hip -- the layered records of acn_lens_layers_reduce* / acn_render_lens_layers* (include/actinon_hip.h states the
  * split and both records; tests/lens_layers_model.py restates them in numpy and the two are compared bit for bit).
  *
- * The arrangement is that of k_surface_reduce (k_lens_surface.hip): a workgroup takes LAY_TILE_POS consecutive positions and copies
- * LAY_TILE_K samples of each at a time into LDS -- the surface records as 16-byte pieces, the radiances as doubles, consecutive lanes
- * on consecutive pieces -- and a position has 16 lanes, which read its samples' keys from LDS at the same addresses (a broadcast).
- *   pass 1  twice: the dominant class of all samples (layer 0), then the dominant class of the samples outside layer 0 (layer 1),
- *           each by the rounds of k_surface_reduce over a table of LAY_CLASSES classes in registers: a sample that finds the table full
- *           and its class not in it is where the next round starts, so either class is exact for any K and any number of classes.
- *           The second search skips the members of layer 0: they are counted nowhere and take no place in the table.
+ * The arrangement and the steps are those of acn_surfclass.h, which k_surface_reduce (k_lens_surface.hip) runs too: a workgroup
+ * takes SURF_TILE_POS consecutive positions and surf_stage copies SURF_TILE_K samples of each at a time into LDS -- the surface
+ * records as 16-byte pieces, the radiances as doubles, consecutive lanes on consecutive pieces -- and a position has 16 lanes.
+ *   pass 1  surf_dominant twice: the dominant class of all samples (layer 0), then, with its exclusion, the dominant class of the
+ *           samples outside layer 0 (layer 1).  Either class is exact for any K and any number of classes.
  *   pass 2  lane f adds double f of the members of layer 0 and, apart, of layer 1, alone and in the order of k, each sum starting at
  *           its first member; lanes 0 .. 8 are also ( part, channel ) = ( f / 3, f % 3 ) of the statistics -- part 0, 1 the layers,
  *           2 the rest -- and add that channel of their part's radiances to +0.0 in the order of k.
  *   pass 3  lanes 0 .. 8 again over the samples: the squared deviations from the mean of pass 2, added to +0.0 in the order of k.
- * With K <= LAY_TILE_K the one tile stays in LDS for all passes.  No lane reads another lane's registers and no sum is split: a record
- * depends on the K records and K radiances of its position alone.  The three lanes of a normal hand their means to each other through
- * LDS; the records of the workgroup are put together in LDS and leave as 16-byte pieces, consecutive lanes on consecutive pieces.
- * LDS: 16 x 17 x 128 (records, rows padded as in k_surface_reduce) + 16 x 16 x 24 (radiances) + 4 KiB + 3 KiB (the records that
- * leave) + 768 (normals) = 48 KiB per workgroup, three workgroups per compute unit; no CSG machine runs and no dynamic LDS is taken. */
+ * With K <= SURF_TILE_K the one tile stays in LDS for all passes.  No lane reads another lane's registers and no sum is split: a
+ * record depends on the K records and K radiances of its position alone.  The three lanes of a normal hand their means to each other
+ * through LDS; surf_value makes double f of either surface record -- plane 0 is the record of k_surface_reduce because it is made by
+ * the same steps --; the records of the workgroup are put together in LDS and leave as 16-byte pieces, consecutive lanes on
+ * consecutive pieces.
+ * LDS: 16 x 17 x 128 (records, rows padded: acn_surfclass.h) + 16 x 16 x 24 (radiances) + 4 KiB + 3 KiB (the records that leave)
+ * + 768 (normals) = 48 KiB per workgroup, three workgroups per compute unit; no CSG machine runs and no dynamic LDS is taken. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
 #include "acn_surfclass.h"
-
-#define LAY_TILE_POS 16
-#define LAY_TILE_K   16
-#define LAY_ROW      ( ( LAY_TILE_K + 1 ) * ACN_SURF_STRIDE )   /* doubles of a position's row of records in LDS */
-#define LAY_RAD_ROW  ( LAY_TILE_K * 3 )                         /* ... and of its row of radiances */
-#define LAY_CLASSES  8
-#define LAY_NO_K     0xFFFFFFFFu
-
-/* positions of one launch: a multiple of the tile, far below the grid limit of 2^31 - 1 workgroups */
-#define LAY_LAUNCH_POS ( ( size_t )1 << 30 )
-
-/* double f of the aggregate record over the m members of a class (k_surface_reduce's last step): sum is the ordered sum of double f,
- * gn the means of the normal's three components (read only where hit && m > 1), cover the [ 15 ] of the record */
-__device__ static inline double lay_surface_value( uint32_t f, const SurfKey& key, double sum, uint32_t m, uint32_t kinds, const double* gn, double cover )
-{
-    const bool hit = ( key.hh & 1u ) != 0;
-    const double mean = sum / ( double )m;
-    if( f == 15 ) return cover;
-    if( f == 14 ) return mean;
-    if( f == 13 ) return ( double )( int32_t )( uint32_t )( key.hh >> 1 );
-    if( !hit ) return f == 0 ? __builtin_inf() : ( f == 7 || f == 8 ) ? -1.0 : 0.0;
-    if( f == 7 ) return ( double )( int32_t )( uint32_t )( key.ex >> 32 );
-    if( f == 8 ) return ( double )( int32_t )( uint32_t )key.ex;
-    if( f == 12 ) return ( double )kinds;
-    if( f >= 4 && f <= 6 && m > 1 )
-    {
-        const double gx = gn[ 0 ], gy = gn[ 1 ], gz = gn[ 2 ];
-        const double q = ( gx * gx + gy * gy ) + gz * gz;
-        return q > 0 ? mean / acn_sqrt( q ) : 0.0;
-    }
-    return mean;   /* (m == 1: sum / 1.0 is the sample's bits) */
-}
 
 /* out_surf: plane l at out_surf + l * surf_plane, out_stats: plane l at out_stats + l * stats_plane (both counted in double2) */
 __global__ __launch_bounds__( 256 )
 void k_lens_layers( const double2* __restrict__ records, const double* __restrict__ rad, size_t n, uint32_t K,
                     double2* __restrict__ out_surf, size_t surf_plane, double2* __restrict__ out_stats, size_t stats_plane )
 {
-    __shared__ double2 tile2[ LAY_TILE_POS * LAY_ROW / 2 ];
-    __shared__ double rtile[ LAY_TILE_POS * LAY_RAD_ROW ];
-    __shared__ double2 srec2[ 2 ][ LAY_TILE_POS * ACN_SURF_STRIDE / 2 ];
-    __shared__ double2 trec2[ 3 ][ LAY_TILE_POS * ACN_STATS_STRIDE / 2 ];
-    __shared__ double gnor[ 2 ][ LAY_TILE_POS * 3 ];
-    const double* tile = ( const double* )tile2;
-    const size_t p0 = ( size_t )blockIdx.x * LAY_TILE_POS;
-    const uint32_t np = n - p0 < LAY_TILE_POS ? ( uint32_t )( n - p0 ) : LAY_TILE_POS;
+    __shared__ double2 tile2[ SURF_TILE_POS * SURF_ROW / 2 ];
+    __shared__ double rtile[ SURF_TILE_POS * SURF_RAD_ROW ];
+    __shared__ double2 srec2[ 2 ][ SURF_TILE_POS * ACN_SURF_STRIDE / 2 ];
+    __shared__ double2 trec2[ 3 ][ SURF_TILE_POS * ACN_STATS_STRIDE / 2 ];
+    __shared__ double gnor[ 2 ][ SURF_TILE_POS * 3 ];
+    const size_t p0 = ( size_t )blockIdx.x * SURF_TILE_POS;
+    const uint32_t np = n - p0 < SURF_TILE_POS ? ( uint32_t )( n - p0 ) : SURF_TILE_POS;
     const uint32_t tid = threadIdx.x;
     const uint32_t my_p = tid / ACN_SURF_STRIDE, my_f = tid % ACN_SURF_STRIDE;
     const bool mine = my_p < np;
-    const double* row = tile + my_p * LAY_ROW;
-    const double* rrow = rtile + my_p * LAY_RAD_ROW;
+    const double* row = ( const double* )tile2 + my_p * SURF_ROW;
+    const double* rrow = rtile + my_p * SURF_RAD_ROW;
+    SurfTile t = { records, rad, p0, np, K, tile2, rtile, SURF_NO_K };
 
-    uint32_t staged = LAY_NO_K;   /* the k0 of the tile in LDS: the same in every lane */
-    /* samples [ k0, k0 + kc ) of the workgroup's positions -> LDS, unless they are there */
-    #define LAY_STAGE( k0, kc ) \
-        if( staged != ( k0 ) ) \
-        { \
-            if( staged != LAY_NO_K ) __syncthreads();   /* (the reads of the tile before) */ \
-            const uint32_t pieces = ( kc ) * ( ACN_SURF_STRIDE / 2 ), words = ( kc ) * 3; \
-            for( uint32_t idx = tid; idx < np * pieces; idx += 256 ) \
-            { \
-                const uint32_t p = idx / pieces, r = idx - p * pieces; \
-                tile2[ p * ( LAY_ROW / 2 ) + r ] = records[ ( ( p0 + p ) * K + ( k0 ) ) * ( ACN_SURF_STRIDE / 2 ) + r ]; \
-            } \
-            for( uint32_t idx = tid; idx < np * words; idx += 256 ) \
-            { \
-                const uint32_t p = idx / words, r = idx - p * words; \
-                rtile[ p * LAY_RAD_ROW + r ] = rad[ ( ( p0 + p ) * K + ( k0 ) ) * 3 + r ]; \
-            } \
-            __syncthreads(); \
-            staged = ( k0 ); \
-        }
-
-    /* pass 1: the dominant class of all samples, then of those outside it */
+    /* pass 1: the dominant class of all samples, then of those outside it (nothing outside layer 0: nothing to search) */
     SurfKey lkey[ 2 ];
     uint32_t lcnt[ 2 ];
-    #pragma unroll 1
-    for( int layer = 0; layer < 2; layer++ )
-    {
-        SurfKey best_key; best_key.ex = 0; best_key.hh = 0;
-        uint32_t best_cnt = 0, best_first = LAY_NO_K;
-        uint32_t start = ( layer == 1 && lcnt[ 0 ] == K ) ? LAY_NO_K : 0;   /* (nothing outside layer 0: nothing to search) */
-        bool more;
-        do
-        {
-            SurfKey ckey[ LAY_CLASSES ];
-            uint32_t ccnt[ LAY_CLASSES ], cfirst[ LAY_CLASSES ];
-            #pragma unroll
-            for( int j = 0; j < LAY_CLASSES; j++ ) { ckey[ j ].ex = 0; ckey[ j ].hh = 0; ccnt[ j ] = 0; cfirst[ j ] = LAY_NO_K; }
-            uint32_t ncls = 0, next = LAY_NO_K;
-            for( uint32_t k0 = 0; k0 < K; k0 += LAY_TILE_K )
-            {
-                const uint32_t kc = K - k0 < LAY_TILE_K ? K - k0 : LAY_TILE_K;
-                LAY_STAGE( k0, kc )
-                if( !mine || start == LAY_NO_K ) continue;
-                for( uint32_t k = start > k0 ? start - k0 : 0; k < kc; k++ )
-                {
-                    const SurfKey key = surf_key( row + k * ACN_SURF_STRIDE );
-                    if( layer == 1 && surf_key_eq( key, lkey[ 0 ] ) ) continue;
-                    bool found = false;
-                    #pragma unroll
-                    for( int j = 0; j < LAY_CLASSES; j++ )
-                        if( ( uint32_t )j < ncls && surf_key_eq( ckey[ j ], key ) ) { ccnt[ j ]++; found = true; }
-                    if( found ) continue;
-                    if( ncls < LAY_CLASSES )
-                    {
-                        #pragma unroll
-                        for( int j = 0; j < LAY_CLASSES; j++ )
-                            if( ( uint32_t )j == ncls ) { ckey[ j ] = key; ccnt[ j ] = 1; cfirst[ j ] = k0 + k; }
-                        ncls++;
-                    }
-                    else if( next == LAY_NO_K ) next = k0 + k;
-                }
-            }
-            #pragma unroll
-            for( int j = 0; j < LAY_CLASSES; j++ )
-                if( ( uint32_t )j < ncls && ( ccnt[ j ] > best_cnt || ( ccnt[ j ] == best_cnt && cfirst[ j ] < best_first ) ) )
-                {
-                    best_key = ckey[ j ]; best_cnt = ccnt[ j ]; best_first = cfirst[ j ];
-                }
-            start = next;
-            more = __syncthreads_or( mine && next != LAY_NO_K ) != 0;
-        } while( more );
-        if( layer == 0 ) { lkey[ 0 ] = best_key; lcnt[ 0 ] = best_cnt; }   /* (constant indices: the arrays stay in registers) */
-        else             { lkey[ 1 ] = best_key; lcnt[ 1 ] = best_cnt; }
-    }
+    surf_dominant< true, false >( t, row, mine, 0, SurfKey{ 0, 0 }, &lkey[ 0 ], &lcnt[ 0 ] );
+    surf_dominant< true, true >( t, row, mine, lcnt[ 0 ] == K ? SURF_NO_K : 0, lkey[ 0 ], &lkey[ 1 ], &lcnt[ 1 ] );
     const bool have1 = lcnt[ 1 ] != 0;
 
     /* pass 2: the ordered sums over the members of either layer, and of the radiances of the lane's part */
@@ -153,10 +52,10 @@ void k_lens_layers( const double2* __restrict__ records, const double* __restric
     const uint32_t my_part = my_f / 3, my_c = my_f - my_part * 3;
     double sum[ 2 ] = { 0.0, 0.0 }, rsum = 0.0;
     uint32_t kinds[ 2 ] = { 0, 0 }, m[ 2 ] = { 0, 0 };
-    for( uint32_t k0 = 0; k0 < K; k0 += LAY_TILE_K )
+    for( uint32_t k0 = 0; k0 < K; k0 += SURF_TILE_K )
     {
-        const uint32_t kc = K - k0 < LAY_TILE_K ? K - k0 : LAY_TILE_K;
-        LAY_STAGE( k0, kc )
+        const uint32_t kc = K - k0 < SURF_TILE_K ? K - k0 : SURF_TILE_K;
+        surf_stage< true >( t, k0, kc );
         if( !mine ) continue;
         for( uint32_t k = 0; k < kc; k++ )
         {
@@ -181,10 +80,10 @@ void k_lens_layers( const double2* __restrict__ records, const double* __restric
 
     /* pass 3: the squared deviations */
     double m2 = 0.0;
-    for( uint32_t k0 = 0; k0 < K; k0 += LAY_TILE_K )
+    for( uint32_t k0 = 0; k0 < K; k0 += SURF_TILE_K )
     {
-        const uint32_t kc = K - k0 < LAY_TILE_K ? K - k0 : LAY_TILE_K;
-        LAY_STAGE( k0, kc )
+        const uint32_t kc = K - k0 < SURF_TILE_K ? K - k0 : SURF_TILE_K;
+        surf_stage< true >( t, k0, kc );
         if( !mine || !stat_lane ) continue;
         for( uint32_t k = 0; k < kc; k++ )
         {
@@ -195,7 +94,6 @@ void k_lens_layers( const double2* __restrict__ records, const double* __restric
             m2 = m2 + d * d;
         }
     }
-    #undef LAY_STAGE
 
     /* the records.  The means of the normals' components go through LDS first */
     const bool is_nor = my_f >= 4 && my_f <= 6;
@@ -207,8 +105,8 @@ void k_lens_layers( const double2* __restrict__ records, const double* __restric
     {
         double* s0 = ( double* )srec2[ 0 ];
         double* s1 = ( double* )srec2[ 1 ];
-        s0[ tid ] = lay_surface_value( my_f, lkey[ 0 ], sum[ 0 ], m[ 0 ], kinds[ 0 ], gnor[ 0 ] + my_p * 3, ( double )m[ 0 ] / ( double )K );
-        if( have1 ) s1[ tid ] = lay_surface_value( my_f, lkey[ 1 ], sum[ 1 ], m[ 1 ], kinds[ 1 ], gnor[ 1 ] + my_p * 3, ( double )m[ 1 ] / ( double )K );
+        s0[ tid ] = surf_value( my_f, lkey[ 0 ], sum[ 0 ], m[ 0 ], kinds[ 0 ], gnor[ 0 ] + my_p * 3, ( double )m[ 0 ] / ( double )K );
+        if( have1 ) s1[ tid ] = surf_value( my_f, lkey[ 1 ], sum[ 1 ], m[ 1 ], kinds[ 1 ], gnor[ 1 ] + my_p * 3, ( double )m[ 1 ] / ( double )K );
         else s1[ tid ] = my_f == 0 ? __builtin_inf() : ( my_f == 7 || my_f == 8 ) ? -1.0 : 0.0;   /* absent: the miss record, [ 13 .. 15 ] zero */
         if( stat_lane )
         {
@@ -234,10 +132,10 @@ void k_lens_layers( const double2* __restrict__ records, const double* __restric
 void acn_launch_lens_layers( const double* records, const double* rad, size_t n, uint32_t samples, double* out_surface, size_t surface_plane,
                              double* out_stats, size_t stats_plane, hipStream_t stream )
 {
-    for( size_t first = 0; first < n; first += LAY_LAUNCH_POS )
+    for( size_t first = 0; first < n; first += SURF_LAUNCH_POS )
     {
-        const size_t cnt = n - first < LAY_LAUNCH_POS ? n - first : LAY_LAUNCH_POS;
-        hipLaunchKernelGGL( k_lens_layers, dim3( ( unsigned )( ( cnt + LAY_TILE_POS - 1 ) / LAY_TILE_POS ) ), dim3( 256 ), 0, stream,
+        const size_t cnt = n - first < SURF_LAUNCH_POS ? n - first : SURF_LAUNCH_POS;
+        hipLaunchKernelGGL( k_lens_layers, dim3( ( unsigned )( ( cnt + SURF_TILE_POS - 1 ) / SURF_TILE_POS ) ), dim3( 256 ), 0, stream,
                             ( const double2* )( records + first * samples * ( size_t )ACN_SURF_STRIDE ), rad + first * samples * ( size_t )3, cnt, samples,
                             ( double2* )( out_surface + first * ( size_t )ACN_SURF_STRIDE ), surface_plane * ( ACN_SURF_STRIDE / 2 ),
                             ( double2* )( out_stats + first * ( size_t )ACN_STATS_STRIDE ), stats_plane * ( ACN_STATS_STRIDE / 2 ) );
