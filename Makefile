@@ -35,7 +35,7 @@ $(BUILD)/%.o: actinon_amd/csrc/%.hip $(wildcard actinon_amd/csrc/*.h) include/ac
 	@mkdir -p $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 # the scene tables of the upload: host-only C++, no HIP (tests/test_tables_cpu.py compiles the same unit on its own)
-$(BUILD)/acn_tables.o: actinon_amd/csrc/acn_tables.cpp actinon_amd/csrc/acn_tables.h include/actinon_hip.h
+$(BUILD)/acn_tables.o: actinon_amd/csrc/acn_tables.cpp actinon_amd/csrc/acn_tables.h actinon_amd/csrc/acn_counts.h include/actinon_hip.h
 	@mkdir -p $(BUILD)
 	$(CXX) -O2 -fPIC -std=c++17 -Wall -ffp-contract=off -fno-fast-math -Iinclude -Iactinon_amd/csrc -c -o $@ $<
 $(LIBDIR)/libactinon_hip.so: $(HIP_OBJS) $(BUILD)/acn_tables.o

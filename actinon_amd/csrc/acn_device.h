@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "actinon_hip.h"
 #include "acn_tables.h"   /* GNode, GMat, SCEntry, the flag / opcode constants and the depth and LDS limits: shared with the host-only table builder */
+#include "acn_counts.h"   /* the ACN_FLAG_* bits of a chunk's flag word */
 #include "acn_detmath.h"
 #include "acn_costs.h"
 
@@ -213,10 +214,6 @@ __device__ __forceinline__ void phase_tally( int k, bool x )
 /* the two read-only scene arrays, passed BY VALUE into the non-inlined machines (global address space, so the
  * scene struct is never forced into scratch) */
 template< class NP > struct SceneRefT { NP nodes; const GNode ACN_CONST* gnodes; ElemP elems; uint32_t* flags; uint32_t n_elems; uint32_t lds_stack; };
-#define ACN_FLAG_TASK_OVERFLOW  1u
-#define ACN_FLAG_CHILD_OVERFLOW 2u
-#define ACN_FLAG_STACK_OVERFLOW 4u   /* CSG / compound / ray stack exhausted: the result would be wrong, the call fails */
-#define ACN_FLAG_CLAMPED        8u   /* a single pixel contribution exceeded the fixed-point clamp (reported, not an error) */
 template< class NP > __device__ __forceinline__ SceneRefT< NP > sref( const DevSceneT< NP >& sc ) { SceneRefT< NP > r; r.nodes = sc.nodes; r.gnodes = sc.gnodes; r.elems = sc.elems; r.flags = sc.flags; r.n_elems = sc.n_elems; r.lds_stack = sc.lds_stack; return r; }
 
 /* ---- vectors.h ---- */

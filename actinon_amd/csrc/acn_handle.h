@@ -183,7 +183,7 @@ struct Workspace
     DevBuf< HardPath >   hard_path;
     DevBuf< RayTask >    rays[ 2 ];
     DevBuf< RayTask >    stacks;   size_t stack_waves = 0;
-    uint32_t    cap[ 5 ] = { 0, 0, 0, 0, 0 };   /* records per queue, WQ_* */
+    uint32_t    cap[ WQ_N ] = {};  /* records per queue, WQ_* */
     size_t      bytes = 0;          /* device memory of the queues and stacks */
     uint64_t    allocs = 0;         /* times this workspace was (re)allocated */
     bool        trimmed = false;    /* it was already re-allocated smaller once */
@@ -209,6 +209,14 @@ struct RunStats
     uint64_t chunks = 0, retries = 0, levels = 0;
     uint64_t peak_tasks = 0, peak_children = 0;
     void reset() { *this = RunStats(); }
+    /* a chunk's that fitted into its run's (acn_read_chunk): sums, the peaks' maxima */
+    void take( const acn_chunk_report& c )
+    {
+        levels += c.levels; walk_rays += c.walk_rays; walk_steps += c.walk_steps; hard_rays += c.hard_rays; shade_hit_recs += c.shade_hit_recs;
+        private_rays += c.private_rays; probe_rays += c.probe_rays;
+        if( c.peak_tasks > peak_tasks ) peak_tasks = c.peak_tasks;
+        if( c.peak_children > peak_children ) peak_children = c.peak_children;
+    }
     /* a lane's into its call's: sums, but the flags' union and the deepest level (the peaks of concurrent lanes add up) */
     void add( const RunStats& l )
     {
@@ -224,12 +232,12 @@ struct RunStats
 /* what a pipeline run has learned about the scene; it stays with the run for its next call */
 struct Learned
 {
-    double rate[ 5 ] = { 0, 0, 0, 0, 0 };      /* records per sample position a chunk leaves in each queue (WQ_*); 0: not known yet */
+    double rate[ WQ_N ] = {};                  /* records per sample position a chunk leaves in each queue (WQ_*); 0: not known yet */
     uint32_t rate_cnt = 0;                     /* positions of the chunk the rates were taken from */
     acn_chunk_ctl ctl = { 0.7, 0, 0 };         /* acn_chunkplan.h.  fill_target: fraction of its capacity the fullest queue of a chunk is
                                                   planned to reach: lowered by every overflow (a redone chunk is lost work), raised slowly
                                                   by chunks that fit */
-    uint32_t walk_passes_seen[ ACN_MAX_PATH_LEVELS + 1 ] = { 0, 0, 0, 0, 0, 0 };   /* passes of a level that had input in the last chunk (0: not known yet) */
+    uint32_t walk_passes_seen[ ACN_LEVEL_BLOCKS ] = {};   /* passes of a level that had input in the last chunk (0: not known yet) */
     bool known() const { return acn_rates_known( rate ) != 0; }
     void forget_passes() { for( uint32_t& seen : walk_passes_seen ) seen = 0; }   /* the full number of passes again */
     /* what one arrangement (the handle's own run, its lanes) learned about the scene (records per position) holds for the
@@ -265,7 +273,7 @@ struct PipeRun
     unsigned grid = 1024, shade_grid = 1024;   /* workgroups of the persistent kernels / of k_shade */
     unsigned walk_grid = 1024;                 /* ... of k_walk */
     Workspace ws;
-    DevBuf< uint32_t > d_counts;               /* ACN_MAX_PATH_LEVELS + 1 counter blocks of QC_N words */
+    DevBuf< uint32_t > d_counts;               /* ACN_LEVEL_BLOCKS counter blocks of QC_N words (acn_counts.h) */
     Buf< uint32_t, HipPinned > h_counts;       /* pinned copy */
     DevBuf< unsigned long long > d_accum;
     DevBuf< unsigned long long > d_counters;

@@ -42,6 +42,7 @@
 #define ACN_PIPELINE_H
 
 #include "acn_device.h"
+#include "acn_counts.h"
 
 /* ---- LCG jump-ahead: x -> a^(2^K) x + c_K in one step, constants folded at compile time ---- */
 struct LcgStep { uint64_t a, c; };
@@ -159,27 +160,7 @@ static_assert( sizeof( HardShadow ) == 88 && sizeof( HardPath ) == 96, "record s
 
 #define ACN_INVALID 0xFFFFFFFFu
 #define ACN_INVALID_SLOT 0xFFFFFFFFu
-#define ACN_NCLASS 4
-/* One counter block per path level (uint32 each), all blocks of a chunk zeroed by one memset before its first launch.
- * Queue counters are high-water marks of reserved slots (dead slots included); QS_* are exact statistics.
- * QC_GEN + g: rays waiting for walk pass g of the level (g = 0: filled by k_shade_hits; g > 0: by pass g - 1);
- * QC_CUR_GEN + g: the work-fetch cursor of pass g. */
-#define ACN_MAX_WALK_PASSES 32
-enum
-{
-    QC_TASKS = 0, QC_CLASS0 = 1, QC_CHILDREN = 5, QC_FLAGS = 6, QC_HARD_SHADOW = 7, QC_HARD_PATH = 8,
-    QC_CUR_HS = 9, QC_CUR_HP = 10, QC_CUR_HITS = 11, QC_CUR_SHADE0 = 20,   /* .. QC_CUR_SHADE0 + 3: one per size class */
-    /* ( words 24 .. 27 are unused ) */
-    /* reserved slots no record was written to (the unused ends of the waves' reservations): mark - dead = records, exactly.
-     * Tasks, path-sample hits, deferred path rays, specular rays (all generations of the level together); the deferred-shadow
-     * queue has QS_HARD_SHADOW + QS_PROBES.  The dead slots of a chunk do not scale with it -- ~64 per wave, queue and launch --
-     * so the marks of a SMALL chunk overstate its demand several times (learn_rates) */
-    QS_DEAD_T = 28, QS_DEAD_C = 29, QS_DEAD_HP = 30, QS_DEAD_R = 31,
-    QS_WALK_RAYS = 12, QS_HARD_SHADOW = 13, QS_HARD_PATH = 14, QS_CHILDREN = 15, QS_TASKS = 16, QS_WALK_STEPS = 17, QS_PRIVATE_RAYS = 18,
-    QS_PROBES = 19,   /* specular rays that were answered by an any-hit probe instead of a walk (probe_push) */
-    QC_GEN = 32, QC_CUR_GEN = QC_GEN + ACN_MAX_WALK_PASSES + 1,
-    QC_N = 104
-};
+/* (the counter block of a path level -- QC_*, QS_*, ACN_NCLASS, ACN_MAX_WALK_PASSES, ACN_QCHUNK -- and the ACN_FLAG_* bits: acn_counts.h) */
 
 /* Size classes of the shading tasks: 64 / 16 / 4 / 1 lanes per task, by the larger of the task's two sample counts.
  * Narrow groups lose less in the last, partly filled round of a sample loop (200 samples on 64 lanes: 4 rounds, 78 %
@@ -200,10 +181,7 @@ DEV int size_class( uint64_t n, uint32_t class0_min )
  * append.  When a request does not fit the rest of the reservation, the rest is marked dead and a new one is taken;
  * consumers skip dead slots.  The state ( next free slot, end ) of a wave's reservation lives in LDS, one pair per
  * wave and queue, and is touched by one lane per append -- which makes appends legal under divergent control flow
- * (the sample loops of k_shade): the lanes that reach an append together form its ballot. */
-#ifndef ACN_QCHUNK
-#define ACN_QCHUNK 64
-#endif
+ * (the sample loops of k_shade): the lanes that reach an append together form its ballot.  (ACN_QCHUNK: acn_counts.h) */
 #ifndef ACN_QCHUNK_MAX
 #define ACN_QCHUNK_MAX 512u
 #endif
@@ -655,7 +633,7 @@ DEV void wave_add_counters( unsigned long long*, const Cnt< false >& ) {}
  * 0.5 ms of the 71 ms frame, ~200 launches of which each is on the chunk's critical path) */
 #define ACN_CHUNK_FLAGS_LOAD const uint32_t chunk_flags_ = *( const uint32_t* )sc_in.flags;
 #define ACN_LEAVE_IF_CHUNK_IS_LOST \
-    if( __builtin_amdgcn_readfirstlane( ( int )chunk_flags_ ) & ( int )( ACN_FLAG_TASK_OVERFLOW | ACN_FLAG_CHILD_OVERFLOW ) ) return;
+    if( __builtin_amdgcn_readfirstlane( ( int )chunk_flags_ ) & ( int )ACN_FLAGS_CHUNK_LOST ) return;
 /* The same for the kernels whose waves depend on each other afterwards (ACN_STAGE_NODES: every wave copies its quarter of the
  * node array into LDS, then the block synchronises).  Other workgroups of the SAME launch set the word concurrently, so the waves
  * of one workgroup may read different values; a wave that left alone would leave its quarter of the staged nodes unwritten and
@@ -664,7 +642,7 @@ DEV void wave_add_counters( unsigned long long*, const Cnt< false >& ) {}
 #define ACN_LEAVE_IF_CHUNK_IS_LOST_BLOCK \
     { \
         __shared__ uint32_t chunk_lost_; \
-        if( threadIdx.x == 0 ) chunk_lost_ = chunk_flags_ & ( ACN_FLAG_TASK_OVERFLOW | ACN_FLAG_CHILD_OVERFLOW ); \
+        if( threadIdx.x == 0 ) chunk_lost_ = chunk_flags_ & ACN_FLAGS_CHUNK_LOST; \
         __syncthreads(); \
         if( chunk_lost_ ) return; \
     }

@@ -1,12 +1,15 @@
 /* acn_queueplan.h -- the planning arithmetic of the pipeline runner (actinon_hip.hip) as plain host C, next to acn_chunkplan.h:
- * queue capacities, chunk sizes, learned rates, walk passes, lanes and the tile order.  No HIP header: capacities, rates, record
- * sizes and counter words come in as arguments and the decisions go out, so every rule runs without a GPU
- * (tests/csrc/queueplan_cpu.cpp, tests/test_queueplan_cpu.py).  Compiled by two compilers: keep -ffp-contract=off. */
+ * queue capacities, chunk sizes, learned rates, the reading of a chunk's counter blocks (acn_counts.h), walk passes, lanes and the
+ * tile order.  No HIP header: capacities, rates, record sizes and the copied counter blocks come in as arguments and the decisions
+ * go out, so every rule runs without a GPU (tests/csrc/queueplan_cpu.cpp, tests/test_queueplan_cpu.py).  Compiled by two compilers:
+ * keep -ffp-contract=off. */
 #ifndef ACN_QUEUEPLAN_H
 #define ACN_QUEUEPLAN_H
 
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
+#include "acn_counts.h"
 
 /* the queues of a pipeline run.  Each is sized from its OWN demand per sample position (learned, below): on the wine glass a
  * position leaves 15 deferred shadow rays but 2 shading points, and one common capacity -- the former layout -- made every
@@ -21,7 +24,7 @@ static inline double acn_plan_max( double a, double b ) { return a > b ? a : b; 
 static inline int acn_rates_known( const double* rate ) { return rate[ WQ_TASKS ] > 0 || rate[ WQ_RAYS ] > 0 || rate[ WQ_HARD_SHADOW ] > 0; }
 /* records per position a queue of the current call needs: the learned rate, and in the ray queue of a ray call at least one
  * slot per position whatever earlier calls taught the handle -- its seeded generation is a KNOWN demand, kept out of the
- * learned rates (render_chunk) */
+ * learned rates (acn_read_chunk) */
 static inline double acn_queue_demand( const double* rate, int q, int seeded ) { return seeded && q == WQ_RAYS && rate[ q ] < 1.0 ? 1.0 : rate[ q ]; }
 
 /* positions a chunk may have so that every queue stays below fill_target (70 %) of its capacity */
@@ -164,15 +167,6 @@ static inline void acn_overflow_rates( double* rate, uint32_t cnt, const uint32_
     for( int q = 0; q < WQ_N; q++ ) { const double r = ( double )fill[ q ] / ( double )cnt; if( r > rate[ q ] ) rate[ q ] = r; }
 }
 
-/* where the words of a level's counter block are (QC_* / QS_* of acn_pipeline.h, which this header does not know) */
-typedef struct
-{
-    uint32_t words;        /* of one level's block */
-    uint32_t tasks, children, hard_path, gen, gens;   /* marks; gens: words from gen on, one per generation */
-    uint32_t hard_shadow_recs, probes, dead_tasks, dead_children, dead_hard_path, dead_rays;   /* counted records and dead slots */
-    uint32_t qchunk;       /* slots a wave reserves per atomic */
-} acn_count_index;
-
 /* The rates from the learning sample of cnt positions: the records the sample left in each queue, exactly (marks minus dead
  * slots; the fullest level counts, the queues are the levels' in turn), plus a fifth for what a sample of a few thousand
  * positions does not see.
@@ -182,26 +176,25 @@ typedef struct
  * call will run -- plan_positions, on persistent grids of plan_grid workgroups -- are spread over its positions:
  * tasks, specular rays and probes are appended by k_shade_hits and ~4 walk passes, path-sample hits and the two deferred
  * queues by the four k_shade launches (and k_hard_path). */
-static inline void acn_sample_rates( const uint32_t* counts, int levels, const acn_count_index* ix, uint32_t cnt, size_t plan_positions,
-                                     unsigned plan_grid, double* rate )
+static inline void acn_sample_rates( const uint32_t* counts, int levels, uint32_t cnt, size_t plan_positions, unsigned plan_grid, double* rate )
 {
     double live[ WQ_N ] = { 0, 0, 0, 0, 0 };
     for( int level = 0; level < levels; level++ )
     {
-        const uint32_t* c = counts + ( size_t )level * ix->words;
+        const uint32_t* c = counts + ( size_t )level * QC_N;
 #define ACN_UP( q, v ) do { const double v_ = ( v ); if( v_ > live[ q ] ) live[ q ] = v_; } while( 0 )
-        ACN_UP( WQ_TASKS, ( double )c[ ix->tasks ] - ( double )c[ ix->dead_tasks ] );
-        ACN_UP( WQ_CHILDREN, ( double )c[ ix->children ] - ( double )c[ ix->dead_children ] );
-        ACN_UP( WQ_HARD_SHADOW, ( double )c[ ix->hard_shadow_recs ] + ( double )c[ ix->probes ] );
-        ACN_UP( WQ_HARD_PATH, ( double )c[ ix->hard_path ] - ( double )c[ ix->dead_hard_path ] );
+        ACN_UP( WQ_TASKS, ( double )c[ QC_TASKS ] - ( double )c[ QS_DEAD_T ] );
+        ACN_UP( WQ_CHILDREN, ( double )c[ QC_CHILDREN ] - ( double )c[ QS_DEAD_C ] );
+        ACN_UP( WQ_HARD_SHADOW, ( double )c[ QS_HARD_SHADOW ] + ( double )c[ QS_PROBES ] );
+        ACN_UP( WQ_HARD_PATH, ( double )c[ QC_HARD_PATH ] - ( double )c[ QS_DEAD_HP ] );
         /* rays: no generation holds more than the largest mark, nor more than all the level's generations together */
         double sum = 0, top = 0;
-        for( uint32_t g = 0; g < ix->gens; g++ ) { sum += c[ ix->gen + g ]; if( c[ ix->gen + g ] > top ) top = c[ ix->gen + g ]; }
-        sum -= ( double )c[ ix->dead_rays ];
+        for( uint32_t g = 0; g < ACN_MAX_WALK_PASSES + 1; g++ ) { sum += c[ QC_GEN + g ]; if( c[ QC_GEN + g ] > top ) top = c[ QC_GEN + g ]; }
+        sum -= ( double )c[ QS_DEAD_R ];
         ACN_UP( WQ_RAYS, sum < top ? sum : top );
 #undef ACN_UP
     }
-    const double per_launch = ( double )ix->qchunk * 4.0 * ( double )plan_grid;
+    const double per_launch = ( double )ACN_QCHUNK * 4.0 * ( double )plan_grid;
     const double walkers = 3.0 * per_launch, shaders = 3.0 * per_launch;   /* (not every wave of every launch leaves a full reservation behind) */
     const double dead[ WQ_N ] = { walkers, shaders, walkers + shaders, shaders, walkers };
     const double pp = ( double )( plan_positions < ACN_CHUNK_TARGET ? plan_positions : ACN_CHUNK_TARGET );
@@ -233,6 +226,74 @@ static inline uint32_t acn_walk_passes_seen( const uint32_t* gen, uint32_t launc
     for( uint32_t g = 0; g < launched; g++ ) if( gen[ g ] ) used = g + 1;
     /* the last launch ran in private mode: if it still had input the level may need more passes than were launched */
     return ( used == launched && launched > 1 ) ? used + 2 : used;
+}
+
+/* ---- a chunk's counter blocks: everything the host decides after the chunk's one synchronisation ---- */
+enum { ACN_CHUNK_FITS = 0, ACN_CHUNK_OVERFLOW /* a queue overflowed: redo it smaller */, ACN_CHUNK_STACK_OVERFLOW /* the call fails */ };
+typedef struct
+{
+    uint32_t flags;                          /* OR of the levels' QC_FLAGS, + ACN_FLAG_CHILD_OVERFLOW where a level's last pass left rays */
+    int      verdict;                        /* ACN_CHUNK_* */
+    uint32_t fill[ WQ_N ];                   /* high-water marks per queue */
+    double   dead_share;                     /* of the marks of the deferred-shadow queue */
+    /* of a chunk that fits (zero otherwise): */
+    uint32_t passes_seen[ ACN_LEVEL_BLOCKS ];   /* acn_walk_passes_seen per level */
+    uint64_t levels, walk_rays, walk_steps, hard_rays, shade_hit_recs, private_rays, probe_rays;
+    uint32_t peak_tasks, peak_children;
+} acn_chunk_report;
+
+/* counts: `levels` blocks of QC_N words as the device left them; passes[ level ]: the launches of k_walk the level got (at most
+ * ACN_MAX_WALK_PASSES); seeded: the chunk rendered the caller's rays */
+static inline void acn_read_chunk( uint32_t* counts, int levels, const uint32_t* passes, int seeded, acn_chunk_report* out )
+{
+    memset( out, 0, sizeof( *out ) );
+    /* the seeded generation of a ray call is a known demand (acn_queue_demand), not a learned one: with its word cleared the queue
+     * marks, the learned passes and acn_sample_rates see the counts of a position call, where level 0 has no generation 0 */
+    if( seeded ) counts[ QC_GEN + 0 ] = 0;
+    for( int level = 0; level < levels; level++ )
+    {
+        const uint32_t* c = counts + ( size_t )level * QC_N;
+        out->flags |= c[ QC_FLAGS ];
+        if( c[ QC_GEN + passes[ level ] ] ) out->flags |= ACN_FLAG_CHILD_OVERFLOW;   /* rays left over by the last pass */
+    }
+    /* what the chunk put into each queue (high-water marks of reserved slots, dead slots included; of a chunk that
+     * overflowed: at least this much): the next chunk's size and the queue capacities are derived from it.
+     * How much of the marks are dead slots (the ends of the waves' reservations) is known exactly for the deferred-shadow
+     * queue, whose records are counted; the share does not scale with the chunk, so a small chunk's marks over-state
+     * the demand per position by 1 / ( 1 - share ) */
+    uint32_t mark = 0, recs = 0;
+    for( int level = 0; level < levels; level++ )
+    {
+        const uint32_t* c = counts + ( size_t )level * QC_N;
+#define ACN_UP( q, v ) do { if( ( v ) > out->fill[ q ] ) out->fill[ q ] = ( v ); } while( 0 )
+        ACN_UP( WQ_TASKS, c[ QC_TASKS ] );
+        for( int k = 0; k < ACN_NCLASS; k++ ) ACN_UP( WQ_TASKS, c[ QC_CLASS0 + k ] );
+        ACN_UP( WQ_CHILDREN, c[ QC_CHILDREN ] );
+        ACN_UP( WQ_HARD_SHADOW, c[ QC_HARD_SHADOW ] );
+        ACN_UP( WQ_HARD_PATH, c[ QC_HARD_PATH ] );
+        for( int g = 0; g <= ACN_MAX_WALK_PASSES; g++ ) ACN_UP( WQ_RAYS, c[ QC_GEN + g ] );
+#undef ACN_UP
+        if( c[ QC_HARD_SHADOW ] > mark ) { mark = c[ QC_HARD_SHADOW ]; recs = c[ QS_HARD_SHADOW ] + c[ QS_PROBES ]; }
+    }
+    if( mark > 0 && recs < mark ) out->dead_share = ( double )( mark - recs ) / ( double )mark;
+    /* a lost chunk first: it is redone smaller, and a stack overflow that is real shows again in the retry */
+    out->verdict = out->flags & ACN_FLAGS_CHUNK_LOST ? ACN_CHUNK_OVERFLOW : out->flags & ACN_FLAG_STACK_OVERFLOW ? ACN_CHUNK_STACK_OVERFLOW : ACN_CHUNK_FITS;
+    if( out->verdict != ACN_CHUNK_FITS ) return;
+    for( int level = 0; level < levels; level++ )
+    {
+        const uint32_t* c = counts + ( size_t )level * QC_N;
+        if( c[ QC_TASKS ] == 0 && c[ QS_WALK_RAYS ] == 0 ) break;
+        out->levels++;
+        out->walk_rays += c[ QS_WALK_RAYS ];
+        out->walk_steps += c[ QS_WALK_STEPS ];
+        out->hard_rays += ( uint64_t )c[ QS_HARD_SHADOW ] + c[ QS_HARD_PATH ];
+        out->shade_hit_recs += c[ QS_CHILDREN ];
+        if( c[ QC_TASKS ] > out->peak_tasks ) out->peak_tasks = c[ QC_TASKS ];
+        if( c[ QC_CHILDREN ] > out->peak_children ) out->peak_children = c[ QC_CHILDREN ];
+        out->private_rays += c[ QS_PRIVATE_RAYS ];
+        out->probe_rays += c[ QS_PROBES ];
+    }
+    for( int level = 0; level < levels; level++ ) out->passes_seen[ level ] = acn_walk_passes_seen( counts + ( size_t )level * QC_N + QC_GEN, passes[ level ] );
 }
 
 /* ---- lanes, shards and the order of work ---- */

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "actinon_hip.h"
+#include "acn_counts.h"   /* ACN_MAX_PATH_LEVELS */
 
 #ifndef ACN_CSG_MAX_DEPTH
 #define ACN_CSG_MAX_DEPTH   24   /* nesting of pair / neg / scale wrappers */
@@ -16,7 +17,6 @@
 #ifndef ACN_CMP_MAX_DEPTH
 #define ACN_CMP_MAX_DEPTH   12   /* nesting of compounds */
 #endif
-#define ACN_MAX_PATH_LEVELS 5    /* suspended path loops: trace_depth <= 10 * 5 + 10 */
 
 /* Device layout of a node: geometry only (192 B); shading properties live in GMat (104 B, read once per shading
  * point).  Built from the ABI's acn_node by acn_tables_build. */

@@ -15,7 +15,6 @@ extern "C" const char* acn_last_error( void ) { return g_last_error.c_str(); }
 
 /* bytes per record of each queue (WQ_*) */
 static const size_t wq_bytes[ WQ_N ] = { sizeof( DTask ) + ACN_NCLASS * sizeof( uint32_t ), sizeof( HitRec ), sizeof( HardShadow ), sizeof( HardPath ), 2 * sizeof( RayTask ) };
-#define ACN_LEVEL_BLOCKS ( ACN_MAX_PATH_LEVELS + 1 )
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* kernels */
@@ -341,11 +340,8 @@ static uint32_t walk_passes_of_level( const PipeRun* r, int level )
  * launches of waves that exit at once.  The host synchronises ONCE, at the end, to read the counter blocks: overflow
  * flags (the chunk is then redone smaller) and statistics.  sw: the switches of the call, or those of the learning pass. */
 static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, uint32_t base, uint32_t cnt, TileOrder order,
-                         hipStream_t stream, int* overflow, uint32_t* fill, double* dead_share )
+                         hipStream_t stream, acn_chunk_report* report )
 {
-    *overflow = 0;
-    *dead_share = 0;
-    for( int q = 0; q < WQ_N; q++ ) fill[ q ] = 0;
     const Tunables& tun = r->h->tun;
     RunStats& stats = r->stats;
     const int levels = r->h->scene.n_levels;
@@ -362,6 +358,7 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
         ACN_LAUNCH( r, sw, 0, stream, acn_launch_seed_rays( prim.rays, base, cnt, order, ( int )r->dev.prm.trace_depth, level_queues( r, sw, 0 ), stream ) );
     }
     const uint32_t n_cam = prim.rays ? 0u : cnt;
+    uint32_t passes[ ACN_LEVEL_BLOCKS ];   /* launches of k_walk per level */
     for( int level = 0; level < levels; level++ )
     {
         LevelQ q = level_queues( r, sw, level );
@@ -375,11 +372,11 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
          * (profiles/r03/private_limit_small_frames.txt) */
         if( !tun.private_limit_set && r->dev.prm.path_samples == 0 && cnt <= ( 1u << 17 ) && cnt > q.private_limit ) q.private_limit = cnt;
         if( level > 0 ) ACN_LAUNCH( r, sw, 0, stream, acn_launch_shade_hits( f.count, q, stream, s, accum, counters ) );
-        const uint32_t passes = walk_passes_of_level( r, level );
-        for( uint32_t pass = 0; pass < passes; pass++ )
+        passes[ level ] = walk_passes_of_level( r, level );
+        for( uint32_t pass = 0; pass < passes[ level ]; pass++ )
         {
             /* (the last launch of a level finishes whatever is left on the private stacks: the input of all later generations) */
-            ACN_LAUNCH( r, sw, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes, q, lds, stream, s, prim.pos_xy, prim.first, base,
+            ACN_LAUNCH( r, sw, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes[ level ], q, lds, stream, s, prim.pos_xy, prim.first, base,
                                                            level == 0 && pass == 0 ? n_cam : 0u, order, accum, counters ) );
         }
         ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade64( f, q, stream, s, accum, counters ) );
@@ -393,70 +390,26 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
     HIP_TRY( hipMemcpyAsync( h_counts, r->d_counts.get(), sizeof( uint32_t ) * QC_N * levels, hipMemcpyDeviceToHost, stream ) );
     HIP_TRY( hipStreamSynchronize( stream ) );
     stats.host_syncs++;
-    /* the seeded generation of a ray call is a known demand (acn_queue_demand), not a learned one: with its word cleared the queue
-     * marks, the learned passes and learn_rates see the counts of a position call, where level 0 has no generation 0 */
-    if( prim.rays ) h_counts[ QC_GEN + 0 ] = 0;
-    uint32_t flags = 0;
-    for( int level = 0; level < levels; level++ )
-    {
-        const uint32_t* c = h_counts + ( size_t )level * QC_N;
-        flags |= c[ QC_FLAGS ];
-        if( c[ QC_GEN + walk_passes_of_level( r, level ) ] ) flags |= ACN_FLAG_CHILD_OVERFLOW;   /* rays left over by the last pass */
-    }
-    stats.flags_seen |= flags & ACN_FLAG_CLAMPED;
-    /* what the chunk put into each queue (high-water marks of reserved slots, dead slots included; of a chunk that
-     * overflowed: at least this much): the next chunk's size and the queue capacities are derived from it */
-    for( int level = 0; level < levels; level++ )
-    {
-        const uint32_t* c = h_counts + ( size_t )level * QC_N;
-        auto up = [ & ]( int q, uint32_t v ) { if( v > fill[ q ] ) fill[ q ] = v; };
-        up( WQ_TASKS, c[ QC_TASKS ] );
-        for( int k = 0; k < ACN_NCLASS; k++ ) up( WQ_TASKS, c[ QC_CLASS0 + k ] );
-        up( WQ_CHILDREN, c[ QC_CHILDREN ] );
-        up( WQ_HARD_SHADOW, c[ QC_HARD_SHADOW ] );
-        up( WQ_HARD_PATH, c[ QC_HARD_PATH ] );
-        for( int g = 0; g <= ACN_MAX_WALK_PASSES; g++ ) up( WQ_RAYS, c[ QC_GEN + g ] );
-    }
-    {
-        /* how much of the marks are dead slots (the ends of the waves' reservations): known exactly for the deferred-shadow
-         * queue, whose records are counted; the share does not scale with the chunk, so a small chunk's marks over-state
-         * the demand per position by 1 / ( 1 - share ) */
-        uint32_t mark = 0, recs = 0;
-        for( int level = 0; level < levels; level++ )
-        {
-            const uint32_t* c = h_counts + ( size_t )level * QC_N;
-            if( c[ QC_HARD_SHADOW ] > mark ) { mark = c[ QC_HARD_SHADOW ]; recs = c[ QS_HARD_SHADOW ] + c[ QS_PROBES ]; }
-        }
-        if( mark > 0 && recs < mark ) *dead_share = ( double )( mark - recs ) / ( double )mark;
-    }
-    /* a lost chunk first: it is redone smaller, and a stack overflow that is real shows again in the retry */
-    if( flags & ( ACN_FLAG_TASK_OVERFLOW | ACN_FLAG_CHILD_OVERFLOW ) ) { *overflow = 1; return ACN_OK; }
-    if( flags & ACN_FLAG_STACK_OVERFLOW ) return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow (or a walk that did not end)" );
-    for( int level = 0; level < levels; level++ )
-    {
-        const uint32_t* c = h_counts + ( size_t )level * QC_N;
-        if( c[ QC_TASKS ] == 0 && c[ QS_WALK_RAYS ] == 0 ) break;
-        stats.levels++;
-        stats.walk_rays += c[ QS_WALK_RAYS ];
-        stats.walk_steps += c[ QS_WALK_STEPS ];
-        stats.hard_rays += ( uint64_t )c[ QS_HARD_SHADOW ] + c[ QS_HARD_PATH ];
-        stats.shade_hit_recs += c[ QS_CHILDREN ];
-        if( c[ QC_TASKS ] > stats.peak_tasks ) stats.peak_tasks = c[ QC_TASKS ];
-        if( c[ QC_CHILDREN ] > stats.peak_children ) stats.peak_children = c[ QC_CHILDREN ];
-        stats.private_rays += c[ QS_PRIVATE_RAYS ];
-        stats.probe_rays += c[ QS_PROBES ];
-    }
-    if( cnt >= 4096 )   /* a chunk large enough to stand for the next one */
-    {
-        uint32_t seen[ ACN_MAX_PATH_LEVELS + 1 ];
-        for( int level = 0; level < levels; level++ ) seen[ level ] = acn_walk_passes_seen( h_counts + ( size_t )level * QC_N + QC_GEN, walk_passes_of_level( r, level ) );
-        for( int level = 0; level < levels; level++ ) r->learned.walk_passes_seen[ level ] = seen[ level ];
-    }
+    /* every decision is made from the counter blocks (acn_read_chunk: flags and verdict, queue marks, statistics, passes seen) */
+    acn_read_chunk( h_counts, levels, passes, prim.rays != nullptr, report );
+    stats.flags_seen |= report->flags & ACN_FLAG_CLAMPED;
+    if( report->verdict == ACN_CHUNK_STACK_OVERFLOW ) return fail( ACN_ERR_UNSUPPORTED, "device CSG / compound stack overflow (or a walk that did not end)" );
+    if( report->verdict != ACN_CHUNK_FITS ) return ACN_OK;
+    stats.take( *report );
+    /* a chunk large enough to stand for the next one */
+    if( cnt >= 4096 ) for( int level = 0; level < levels; level++ ) r->learned.walk_passes_seen[ level ] = report->passes_seen[ level ];
     return ACN_OK;
 }
 
-static const acn_count_index count_index = { QC_N, QC_TASKS, QC_CHILDREN, QC_HARD_PATH, QC_GEN, ACN_MAX_WALK_PASSES + 1,
-                                             QS_HARD_SHADOW, QS_PROBES, QS_DEAD_T, QS_DEAD_C, QS_DEAD_HP, QS_DEAD_R, ACN_QCHUNK };
+/* the ACN_DEBUG_CHUNKS lines: " T x C x HS x HP x R x", one value per queue (decimals 0: a count) */
+template< class F > static std::string per_queue( int decimals, F value )
+{
+    static const char* const name[ WQ_N ] = { "T", "C", "HS", "HP", "R" };
+    std::string s;
+    char b[ 336 ];   /* (the longest %.1f of a double) */
+    for( int q = 0; q < WQ_N; q++ ) { snprintf( b, sizeof( b ), " %s %.*f", name[ q ], decimals, ( double )value( q ) ); s += b; }
+    return s;
+}
 
 /* Cold handle: the queue demand per position is learned from a SAMPLE of the call's own positions -- every ( n / m )-th of them,
  * m = 512 .. 4096 -- rendered once on the starter queues and thrown away, before anything is sized.  Round 3 let the first
@@ -490,19 +443,18 @@ static int learn_rates( PipeRun* r, const Primary& prim, size_t n, hipStream_t s
         const uint32_t cnt = ( uint32_t )want;
         hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, r->d_accum.get(), 0u, cnt, order );
         HIP_TRY( hipGetLastError() );
-        int overflow = 0;
-        uint32_t fill[ WQ_N ];
-        double dead_share = 0;
-        st = render_chunk( r, sw, prim, 0u, cnt, order, stream, &overflow, fill, &dead_share );
+        acn_chunk_report c;
+        st = render_chunk( r, sw, prim, 0u, cnt, order, stream, &c );
         if( st != ACN_OK ) break;
+        const bool overflow = c.verdict != ACN_CHUNK_FITS;
         if( tun.debug_chunks )
             fprintf( stderr, "[acn sample] chain done after %.2f ms\n", since() );
         if( tun.debug_chunks )
-            fprintf( stderr, "[acn sample] %u positions (every %u-th) %s dead %.2f | per pos T %.1f C %.1f HS %.1f HP %.1f R %.1f\n", cnt, order.sample_stride, overflow ? "OVERFLOW" : "ok",
-                     dead_share, fill[ 0 ] / ( double )cnt, fill[ 1 ] / ( double )cnt, fill[ 2 ] / ( double )cnt, fill[ 3 ] / ( double )cnt, fill[ 4 ] / ( double )cnt );
+            fprintf( stderr, "[acn sample] %u positions (every %u-th) %s dead %.2f | per pos%s\n", cnt, order.sample_stride, overflow ? "OVERFLOW" : "ok",
+                     c.dead_share, per_queue( 1, [ & ]( int q ) { return c.fill[ q ] / ( double )cnt; } ).c_str() );
         if( overflow ) continue;
-        acn_sample_rates( r->h_counts.get(), r->h->scene.n_levels, &count_index, cnt, plan_positions, plan_grid, L.rate );
-        if( tun.debug_chunks ) fprintf( stderr, "[acn sample] rates T %.1f C %.1f HS %.1f HP %.1f R %.1f\n", L.rate[ 0 ], L.rate[ 1 ], L.rate[ 2 ], L.rate[ 3 ], L.rate[ 4 ] );
+        acn_sample_rates( r->h_counts.get(), r->h->scene.n_levels, cnt, plan_positions, plan_grid, L.rate );
+        if( tun.debug_chunks ) fprintf( stderr, "[acn sample] rates%s\n", per_queue( 1, [ & ]( int q ) { return L.rate[ q ]; } ).c_str() );
         L.rate_cnt = 8192;   /* a sample of the whole frame: trusted like a chunk that size (launch_render re-sizes for the whole rest at once) */
         break;
     }
@@ -568,18 +520,17 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
         uint32_t cnt = acn_ctl_next( &L.ctl, n_slots - base, chunk, tun.chunk != 0, L.known(), plan, r->ws.cap );
         /* (the seeded generation of a ray call takes one ray-queue slot per position, also under ACN_CHUNK) */
         if( prim.rays && cnt > r->ws.cap[ WQ_RAYS ] ) cnt = r->ws.cap[ WQ_RAYS ];
-        int overflow = 0;
-        uint32_t fill[ WQ_N ];
-        double dead_share = 0;
+        acn_chunk_report c;
         /* the work counters of a chunk that has to be redone must not count twice */
         if( sw.count_work ) HIP_TRY( hipMemcpyAsync( r->d_counters_keep.get(), r->d_counters.get(), sizeof( unsigned long long ) * ACN_CNT_SLOTS, hipMemcpyDeviceToDevice, stream ) );
-        st = render_chunk( r, sw, prim, ( uint32_t )base, cnt, order, stream, &overflow, fill, &dead_share );
+        st = render_chunk( r, sw, prim, ( uint32_t )base, cnt, order, stream, &c );
         if( st != ACN_OK ) return st;
+        const bool overflow = c.verdict != ACN_CHUNK_FITS;
         if( tun.debug_chunks )
-            fprintf( stderr, "[acn chunk] base %zu cnt %u %s target %.2f dead %.2f | fill T %u C %u HS %u HP %u R %u | per pos T %.1f C %.1f HS %.1f HP %.1f R %.1f | rate T %.1f C %.1f HS %.1f HP %.1f R %.1f | cap T %u C %u HS %u HP %u R %u\n",
-                     base, cnt, overflow ? "OVERFLOW" : "ok", L.ctl.fill_target, dead_share, fill[ 0 ], fill[ 1 ], fill[ 2 ], fill[ 3 ], fill[ 4 ],
-                     fill[ 0 ] / ( double )cnt, fill[ 1 ] / ( double )cnt, fill[ 2 ] / ( double )cnt, fill[ 3 ] / ( double )cnt, fill[ 4 ] / ( double )cnt,
-                     L.rate[ 0 ], L.rate[ 1 ], L.rate[ 2 ], L.rate[ 3 ], L.rate[ 4 ], r->ws.cap[ 0 ], r->ws.cap[ 1 ], r->ws.cap[ 2 ], r->ws.cap[ 3 ], r->ws.cap[ 4 ] );
+            fprintf( stderr, "[acn chunk] base %zu cnt %u %s target %.2f dead %.2f | fill%s | per pos%s | rate%s | cap%s\n",
+                     base, cnt, overflow ? "OVERFLOW" : "ok", L.ctl.fill_target, c.dead_share, per_queue( 0, [ & ]( int q ) { return c.fill[ q ]; } ).c_str(),
+                     per_queue( 1, [ & ]( int q ) { return c.fill[ q ] / ( double )cnt; } ).c_str(), per_queue( 1, [ & ]( int q ) { return L.rate[ q ]; } ).c_str(),
+                     per_queue( 0, [ & ]( int q ) { return r->ws.cap[ q ]; } ).c_str() );
         if( overflow )
         {
             if( cnt <= 1 ) return fail( ACN_ERR_DEVICE, "work queues overflow for a single position: raise ACN_WORKSPACE_MB" );
@@ -588,7 +539,7 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
             /* scenes whose demand per position varies much between chunks (many_spheres p256: 49 of 220 chunks were redone at
              * a fixed 70 %) plan with more head room */
             chunk = acn_ctl_overflow( &L.ctl, cnt );
-            acn_overflow_rates( L.rate, cnt, fill );
+            acn_overflow_rates( L.rate, cnt, c.fill );
             L.forget_passes();
             hipLaunchKernelGGL( k_clear_slots, dim3( ( cnt + 255 ) / 256 ), dim3( 256 ), 0, stream, r->d_accum.get(), ( uint32_t )base, cnt, order );
             HIP_TRY( hipGetLastError() );
@@ -598,7 +549,7 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
         base += cnt;
         acn_ctl_fit( &L.ctl );
         if( tun.chunk ) continue;
-        acn_learn_rates( L.rate, &L.rate_cnt, cnt, fill, dead_share );
+        acn_learn_rates( L.rate, &L.rate_cnt, cnt, c.fill, c.dead_share );
         const size_t remaining = n_slots - base;
         if( remaining && ( double )chunk_for_caps( r ) * ( 0.85 / L.ctl.fill_target ) < ( double )remaining )
         {
@@ -1000,7 +951,7 @@ static std::vector< const PipeRun* > last_runs( const acn_scene_handle* h )
 
 extern "C" int acn_last_stage_ms( acn_scene_handle* h, double* out, int n )
 {
-    if( !h || !out || n < 0 || n > 25 || !h->timed ) return fail( ACN_ERR_ARG, "no timed launch" );
+    if( !h || !out || n < 0 || n > ACN_LAST_N || !h->timed ) return fail( ACN_ERR_ARG, "no timed launch" );
     HIP_TRY( hipSetDevice( h->device ) );
     HIP_TRY( hipEventSynchronize( h->run.ev1.get() ) );
     double ms[ 4 ] = { 0, 0, 0, 0 };
@@ -1018,12 +969,18 @@ extern "C" int acn_last_stage_ms( acn_scene_handle* h, double* out, int n )
     float total = 0;
     HIP_TRY( hipEventElapsedTime( &total, h->run.ev0.get(), h->run.ev1.get() ) );
     const RunStats& s = h->run.stats;
-    double v[ 25 ] = { ms[ 0 ], ms[ 1 ], ms[ 2 ], total, ( double )s.launches[ 0 ], ( double )s.launches[ 1 ], ( double )s.launches[ 2 ],
-                       ( double )s.chunks, ( double )s.retries, ( double )s.levels, ( double )s.peak_tasks, ( double )s.peak_children,
-                       ( double )queue_cap, ms[ 3 ], ( double )s.launches[ 3 ], ( double )s.hard_rays,
-                       ( double )s.walk_rays, ( double )s.shade_hit_recs, ( double )s.host_syncs, ( double )s.walk_steps,
-                       ( double )s.flags_seen, ( double )s.private_rays, ( double )s.probe_rays, ( double )ws_bytes, ( double )ws_allocs };
-    for( int k = 0; k < n && k < 25; k++ ) out[ k ] = v[ k ];
+    double v[ ACN_LAST_N ];
+    v[ ACN_LAST_WALK_MS ] = ms[ 0 ]; v[ ACN_LAST_SHADE_MS ] = ms[ 1 ]; v[ ACN_LAST_FINALIZE_MS ] = ms[ 2 ]; v[ ACN_LAST_HARD_MS ] = ms[ 3 ];
+    v[ ACN_LAST_TOTAL_MS ] = total;
+    v[ ACN_LAST_WALK_LAUNCHES ] = ( double )s.launches[ 0 ]; v[ ACN_LAST_SHADE_LAUNCHES ] = ( double )s.launches[ 1 ];
+    v[ ACN_LAST_FINALIZE_LAUNCHES ] = ( double )s.launches[ 2 ]; v[ ACN_LAST_HARD_LAUNCHES ] = ( double )s.launches[ 3 ];
+    v[ ACN_LAST_CHUNKS ] = ( double )s.chunks; v[ ACN_LAST_RETRIES ] = ( double )s.retries; v[ ACN_LAST_LEVELS ] = ( double )s.levels;
+    v[ ACN_LAST_PEAK_TASKS ] = ( double )s.peak_tasks; v[ ACN_LAST_PEAK_CHILDREN ] = ( double )s.peak_children; v[ ACN_LAST_QUEUE_CAP ] = ( double )queue_cap;
+    v[ ACN_LAST_HARD_RAYS ] = ( double )s.hard_rays; v[ ACN_LAST_WALK_RAYS ] = ( double )s.walk_rays; v[ ACN_LAST_PATH_HITS ] = ( double )s.shade_hit_recs;
+    v[ ACN_LAST_HOST_SYNCS ] = ( double )s.host_syncs; v[ ACN_LAST_WALK_STEPS ] = ( double )s.walk_steps; v[ ACN_LAST_FLAGS ] = ( double )s.flags_seen;
+    v[ ACN_LAST_PRIVATE_RAYS ] = ( double )s.private_rays; v[ ACN_LAST_PROBE_RAYS ] = ( double )s.probe_rays;
+    v[ ACN_LAST_WORKSPACE_BYTES ] = ( double )ws_bytes; v[ ACN_LAST_WORKSPACE_ALLOCS ] = ( double )ws_allocs;
+    for( int k = 0; k < n; k++ ) out[ k ] = v[ k ];
     return ACN_OK;
 }
 

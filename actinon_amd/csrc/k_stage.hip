@@ -121,7 +121,7 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     uint32_t counts[ QC_N ];
     if( ( st = DevCopies::fetch( counts, d_counts, sizeof( counts ) ) ) != ACN_OK ) return st;
     if( out->counts ) memcpy( out->counts, counts, sizeof( counts ) );
-    if( counts[ QC_FLAGS ] & ( ACN_FLAG_TASK_OVERFLOW | ACN_FLAG_CHILD_OVERFLOW | ACN_FLAG_STACK_OVERFLOW ) )
+    if( counts[ QC_FLAGS ] & ( ACN_FLAGS_CHUNK_LOST | ACN_FLAG_STACK_OVERFLOW ) )
         return fail( ACN_ERR_DEVICE, "acn_run_stage: the kernel raised overflow flags " + std::to_string( counts[ QC_FLAGS ] ) + ": a queue the plan sized was too small" );
     struct { void* dst; const void* d; size_t bytes; } outs[] = {
         { shade ? nullptr : out->tasks, d_tasks, b_tasks },

@@ -304,15 +304,17 @@ class Handle:
         check(hip.acn_last_kernel_ms(self.h, C.byref(ms)), "acn_last_kernel_ms")
         return ms.value
 
+    # the slots of acn_last_stage_ms, in order: the ACN_LAST_* enum of include/actinon_hip.h
+    STAGES = ["walk_ms", "shade_ms", "finalize_ms", "total_ms", "walk_launches", "shade_launches", "finalize_launches",
+              "chunks", "retries", "levels", "peak_tasks", "peak_children", "queue_cap", "hard_ms", "hard_launches",
+              "hard_rays", "walk_rays", "path_hits", "host_syncs", "walk_steps", "flags", "private_rays", "probe_rays",
+              "workspace_bytes", "workspace_allocs"]
+
     def last_stages(self):
         """Per-stage device time (ms) and pipeline statistics of the last render call."""
-        names = ["walk_ms", "shade_ms", "finalize_ms", "total_ms", "walk_launches", "shade_launches", "finalize_launches",
-                 "chunks", "retries", "levels", "peak_tasks", "peak_children", "queue_cap", "hard_ms", "hard_launches",
-                 "hard_rays", "walk_rays", "path_hits", "host_syncs", "walk_steps", "flags", "private_rays", "probe_rays",
-                 "workspace_bytes", "workspace_allocs"]
-        buf = (C.c_double * 25)()
-        check(hip.acn_last_stage_ms(self.h, buf, 25), "acn_last_stage_ms")
-        return dict(zip(names, [float(v) for v in buf]))
+        buf = (C.c_double * len(self.STAGES))()
+        check(hip.acn_last_stage_ms(self.h, buf, len(self.STAGES)), "acn_last_stage_ms")
+        return dict(zip(self.STAGES, [float(v) for v in buf]))
 
     def last_counters(self):
         names = ["trans_rays", "shadow_rays", "obj_hits", "lum_calls", "cap_samples", "side_calls", "sdf_evals",
@@ -810,7 +812,7 @@ class Handle:
     }
     del _V
     STAGE_INVALID = 0xFFFFFFFF
-    # words of the level's counter block (acn_pipeline.h)
+    # words of the level's counter block (acn_counts.h)
     QC = {"tasks": 0, "class0": 1, "children": 5, "flags": 6, "hard_shadow": 7, "hard_path": 8, "walk_rays": 12, "s_hard_shadow": 13,
           "s_hard_path": 14, "s_children": 15, "s_tasks": 16, "s_probes": 19, "dead_t": 28, "dead_c": 29, "dead_hp": 30, "dead_r": 31, "gen0": 32}
 

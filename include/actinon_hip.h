@@ -777,6 +777,15 @@ int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );
  * trace_min_intensity, src/scene.c:430) and that were therefore answered by an any-hit probe instead of a walk, [23] bytes
  * of device memory the call's work queues and ray stacks occupy (all lanes), [24] how often they were (re)allocated
  * since the upload. n <= 25. */
+enum
+{
+    ACN_LAST_WALK_MS = 0, ACN_LAST_SHADE_MS, ACN_LAST_FINALIZE_MS, ACN_LAST_TOTAL_MS, ACN_LAST_WALK_LAUNCHES, ACN_LAST_SHADE_LAUNCHES,
+    ACN_LAST_FINALIZE_LAUNCHES, ACN_LAST_CHUNKS, ACN_LAST_RETRIES, ACN_LAST_LEVELS, ACN_LAST_PEAK_TASKS, ACN_LAST_PEAK_CHILDREN,
+    ACN_LAST_QUEUE_CAP, ACN_LAST_HARD_MS, ACN_LAST_HARD_LAUNCHES, ACN_LAST_HARD_RAYS, ACN_LAST_WALK_RAYS, ACN_LAST_PATH_HITS,
+    ACN_LAST_HOST_SYNCS, ACN_LAST_WALK_STEPS, ACN_LAST_FLAGS, ACN_LAST_PRIVATE_RAYS, ACN_LAST_PROBE_RAYS, ACN_LAST_WORKSPACE_BYTES,
+    ACN_LAST_WORKSPACE_ALLOCS,
+    ACN_LAST_N   /* 25 */
+};
 int acn_last_stage_ms( acn_scene_handle* h, double* out, int n );
 
 /* Work counters of the last render call (rays cast, node visits ...), see DESIGN.md: [0..7] events, [8] flop and
@@ -835,7 +844,7 @@ int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const double* ray
 /* Test hook: one shading kernel of the pipeline alone (csrc/k_stage.hip).  acn_run_stage launches the production kernel of one stage
  * once, on queues it owns and fills from the caller's records, and fetches back everything the kernel wrote; it has no device code of
  * its own.  The records are the pipeline's own (csrc/acn_pipeline.h: HitRec, DTask, RayTask, HardShadow, HardPath), the counter block
- * is the level's (QC_*, QS_*); acn_stage_info reports their sizes so that a caller asserts its layouts.
+ * is the level's (QC_*, QS_* of csrc/acn_counts.h); acn_stage_info reports their sizes so that a caller asserts its layouts.
  *   ACN_STAGE_SHADE_HITS  k_shade_hits on in = HitRec[ n ]: the split of scene_s_lum.  Written: tasks, idx[ 0 .. 3 ], rays, hard_shadow
  *                         (the probes of dead children), counts, flags, accum.
  *   ACN_STAGE_SHADE       k_shade of size class `cls` on in = DTask[ n ] and index[ n_index ] (entries < n, or 0xFFFFFFFF: a dead

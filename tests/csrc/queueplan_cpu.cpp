@@ -45,8 +45,33 @@ uint64_t qp_chunk_for_caps( const double* rate, int seeded, double fill_target, 
 void qp_set_rates( double* rate, uint32_t* rate_cnt, uint32_t cnt, const uint32_t* fill, double dead_share ) { acn_set_rates( rate, rate_cnt, cnt, fill, dead_share ); }
 void qp_learn_rates( double* rate, uint32_t* rate_cnt, uint32_t cnt, const uint32_t* fill, double dead_share ) { acn_learn_rates( rate, rate_cnt, cnt, fill, dead_share ); }
 void qp_overflow_rates( double* rate, uint32_t cnt, const uint32_t* fill ) { acn_overflow_rates( rate, cnt, fill ); }
-void qp_sample_rates( const uint32_t* counts, int levels, const acn_count_index* ix, uint32_t cnt, uint64_t plan_positions, unsigned plan_grid, double* rate )
-{ acn_sample_rates( counts, levels, ix, cnt, ( size_t )plan_positions, plan_grid, rate ); }
+void qp_sample_rates( const uint32_t* counts, int levels, uint32_t cnt, uint64_t plan_positions, unsigned plan_grid, double* rate )
+{ acn_sample_rates( counts, levels, cnt, ( size_t )plan_positions, plan_grid, rate ); }
+/* acn_read_chunk; the report as words: flags, verdict, fill[ WQ_N ], passes_seen[ ACN_LEVEL_BLOCKS ], then the nine statistics in the order of the struct */
+void qp_read_chunk( uint32_t* counts, int levels, const uint32_t* passes, int seeded, uint64_t* words, double* dead_share )
+{
+    acn_chunk_report r;
+    acn_read_chunk( counts, levels, passes, seeded, &r );
+    *words++ = r.flags; *words++ = ( uint64_t )r.verdict;
+    for( int q = 0; q < WQ_N; q++ ) *words++ = r.fill[ q ];
+    for( int level = 0; level < ACN_LEVEL_BLOCKS; level++ ) *words++ = r.passes_seen[ level ];
+    for( uint64_t v : { r.levels, r.walk_rays, r.walk_steps, r.hard_rays, r.shade_hit_recs, r.private_rays, r.probe_rays, ( uint64_t )r.peak_tasks, ( uint64_t )r.peak_children } ) *words++ = v;
+    *dead_share = r.dead_share;
+}
+/* a constant of acn_counts.h or acn_queueplan.h by its name; -1: not one of these */
+int64_t qp_constant( const char* name )
+{
+#define K( x ) { #x, ( int64_t )( x ) }
+    static const struct { const char* name; int64_t value; } known[] = {
+        K( QC_TASKS ), K( QC_CLASS0 ), K( QC_CHILDREN ), K( QC_FLAGS ), K( QC_HARD_SHADOW ), K( QC_HARD_PATH ), K( QS_WALK_RAYS ), K( QS_HARD_SHADOW ),
+        K( QS_HARD_PATH ), K( QS_CHILDREN ), K( QS_TASKS ), K( QS_WALK_STEPS ), K( QS_PRIVATE_RAYS ), K( QS_PROBES ), K( QS_DEAD_T ), K( QS_DEAD_C ),
+        K( QS_DEAD_HP ), K( QS_DEAD_R ), K( QC_GEN ), K( QC_CUR_GEN ), K( QC_N ), K( ACN_QCHUNK ), K( ACN_NCLASS ), K( ACN_MAX_WALK_PASSES ),
+        K( ACN_MAX_PATH_LEVELS ), K( ACN_LEVEL_BLOCKS ), K( ACN_FLAG_TASK_OVERFLOW ), K( ACN_FLAG_CHILD_OVERFLOW ), K( ACN_FLAG_STACK_OVERFLOW ),
+        K( ACN_FLAG_CLAMPED ), K( ACN_FLAGS_CHUNK_LOST ), K( WQ_N ), K( ACN_CHUNK_FITS ), K( ACN_CHUNK_OVERFLOW ), K( ACN_CHUNK_STACK_OVERFLOW ) };
+#undef K
+    for( const auto& k : known ) if( !strcmp( k.name, name ) ) return k.value;
+    return -1;
+}
 uint32_t qp_walk_passes( uint64_t trace_depth, int level, uint32_t tun_passes, uint32_t seen ) { return acn_walk_passes( trace_depth, level, tun_passes, seen ); }
 uint32_t qp_walk_passes_seen( const uint32_t* gen, uint32_t launched ) { return acn_walk_passes_seen( gen, launched ); }
 uint64_t qp_lane_count( uint64_t n, int lanes, int lane ) { return acn_lane_count( ( size_t )n, lanes, lane ); }
@@ -129,14 +154,60 @@ int main()
         acn_overflow_rates( rate.get(), 1, fill.get() );
         EXPECT( rate[ 4 ] == 4294967295.0 );
     }
-    /* the learning sample: two levels of counter words in blocks of exactly their size */
+    /* the learning sample: two levels of counter words in a block of exactly their size */
     {
-        const acn_count_index ix = { 41, 0, 1, 2, 8, 33, 3, 4, 5, 6, 7, 7, 64 };
-        std::unique_ptr< uint32_t[] > c( new uint32_t[ 82 ] );
-        for( int i = 0; i < 82; i++ ) c[ i ] = ( uint32_t )( i * 37 % 1000 );
+        std::unique_ptr< uint32_t[] > c( new uint32_t[ 2 * QC_N ] );
+        for( int i = 0; i < 2 * QC_N; i++ ) c[ i ] = ( uint32_t )( i * 37 % 1000 );
         auto rate = block< double >( { 0, 0, 0, 0, 0 } );
-        acn_sample_rates( c.get(), 2, &ix, 4096, 19200, 256, rate.get() );
+        acn_sample_rates( c.get(), 2, 4096, 19200, 256, rate.get() );
         for( int q = 0; q < WQ_N; q++ ) EXPECT( rate[ q ] >= 1e-3 );
+    }
+    /* the reader of a chunk's counter blocks: every level the device has, every pass a level can get, in a block of exactly
+     * levels * QC_N words -- QC_GEN + passes is then the last generation word of each level */
+    {
+        const int levels = ACN_LEVEL_BLOCKS;
+        std::unique_ptr< uint32_t[] > c( new uint32_t[ ( size_t )levels * QC_N ] );
+        std::unique_ptr< uint32_t[] > passes( new uint32_t[ levels ] );
+        auto level = [ & ]( int l ) { return c.get() + ( size_t )l * QC_N; };
+        auto clear = [ & ]() { memset( c.get(), 0, sizeof( uint32_t ) * levels * QC_N ); for( int l = 0; l < levels; l++ ) passes[ l ] = ACN_MAX_WALK_PASSES; };
+        acn_chunk_report r;
+        /* a chunk that fits: marks, statistics up to the first empty level, the seeded word cleared */
+        clear();
+        for( int l = 0; l < 3; l++ ) { level( l )[ QC_TASKS ] = 10 + l; level( l )[ QS_WALK_RAYS ] = 100; level( l )[ QS_WALK_STEPS ] = 7; level( l )[ QC_GEN + 1 ] = 50 + l; }
+        level( 4 )[ QC_TASKS ] = 999; level( 4 )[ QS_WALK_RAYS ] = 5;    /* behind the empty level 3: in the marks, not in the statistics */
+        level( 0 )[ QC_GEN + 0 ] = 4000; level( 0 )[ QC_FLAGS ] = ACN_FLAG_CLAMPED;
+        level( 1 )[ QC_CLASS0 + 3 ] = 2000;
+        acn_read_chunk( c.get(), levels, passes.get(), 1, &r );
+        EXPECT( r.verdict == ACN_CHUNK_FITS && r.flags == ACN_FLAG_CLAMPED && level( 0 )[ QC_GEN ] == 0 );
+        EXPECT( r.fill[ WQ_TASKS ] == 2000 && r.fill[ WQ_RAYS ] == 52 && r.fill[ WQ_CHILDREN ] == 0 && r.dead_share == 0 );
+        EXPECT( r.levels == 3 && r.walk_rays == 300 && r.walk_steps == 21 && r.peak_tasks == 12 );
+        EXPECT( r.passes_seen[ 0 ] == 2 && r.passes_seen[ 2 ] == 2 && r.passes_seen[ 3 ] == 1 && r.passes_seen[ 5 ] == 1 );
+        /* rays left in the last generation word of the last level, no flag anywhere: overflow, and no statistics */
+        level( levels - 1 )[ QC_GEN + ACN_MAX_WALK_PASSES ] = 1;
+        acn_read_chunk( c.get(), levels, passes.get(), 0, &r );
+        EXPECT( r.verdict == ACN_CHUNK_OVERFLOW && r.flags == ( ACN_FLAG_CLAMPED | ACN_FLAG_CHILD_OVERFLOW ) && r.levels == 0 && r.passes_seen[ 0 ] == 0 && r.fill[ WQ_TASKS ] == 2000 );
+        /* a stack overflow alone fails the call; together with a task overflow in a middle level the chunk is redone */
+        clear();
+        level( 2 )[ QC_FLAGS ] = ACN_FLAG_STACK_OVERFLOW;
+        acn_read_chunk( c.get(), levels, passes.get(), 0, &r );
+        EXPECT( r.verdict == ACN_CHUNK_STACK_OVERFLOW );
+        level( 3 )[ QC_FLAGS ] = ACN_FLAG_TASK_OVERFLOW;
+        acn_read_chunk( c.get(), levels, passes.get(), 0, &r );
+        EXPECT( r.verdict == ACN_CHUNK_OVERFLOW && r.flags == ( ACN_FLAG_STACK_OVERFLOW | ACN_FLAG_TASK_OVERFLOW ) );
+        /* the dead share: the fullest deferred-shadow mark is the last level's; records equal to the mark, then one below */
+        clear();
+        level( 0 )[ QC_HARD_SHADOW ] = 400; level( 0 )[ QS_HARD_SHADOW ] = 100;
+        level( levels - 1 )[ QC_HARD_SHADOW ] = 1000; level( levels - 1 )[ QS_HARD_SHADOW ] = 600; level( levels - 1 )[ QS_PROBES ] = 400;
+        acn_read_chunk( c.get(), levels, passes.get(), 0, &r );
+        EXPECT( r.dead_share == 0 && r.fill[ WQ_HARD_SHADOW ] == 1000 );
+        level( levels - 1 )[ QS_PROBES ] = 399;
+        acn_read_chunk( c.get(), levels, passes.get(), 0, &r );
+        EXPECT( r.dead_share == 1.0 / 1000.0 );
+        /* every word at its largest */
+        memset( c.get(), 0xFF, sizeof( uint32_t ) * levels * QC_N );
+        for( int l = 0; l < levels; l++ ) level( l )[ QC_FLAGS ] = 0, level( l )[ QC_GEN + ACN_MAX_WALK_PASSES ] = 0;
+        acn_read_chunk( c.get(), levels, passes.get(), 0, &r );
+        EXPECT( r.verdict == ACN_CHUNK_FITS && r.levels == ( uint64_t )levels && r.hard_rays == 2ull * levels * 0xFFFFFFFFull && r.passes_seen[ 0 ] == ACN_MAX_WALK_PASSES + 2 );   /* (the last launch had input: two more) */
     }
     /* walk passes */
     EXPECT( acn_walk_passes( 10, 0, 4, 0 ) == 4 && acn_walk_passes( 10, 1, 4, 0 ) == 2 && acn_walk_passes( 2, 0, 4, 0 ) == 3 && acn_walk_passes( 50, 0, 32, 1 ) == 2 );

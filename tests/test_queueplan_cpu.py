@@ -1,11 +1,12 @@
 """The planning arithmetic of the pipeline runner (actinon_amd/csrc/acn_queueplan.h) without a GPU: queue capacities, chunk sizes,
-learned rates, walk passes, lanes and the tile order behind the shim tests/csrc/queueplan_cpu.cpp.  Every function is compared with
+learned rates, the reading of a chunk's counter blocks, walk passes, lanes and the tile order behind the shim tests/csrc/queueplan_cpu.cpp.  Every function is compared with
 a short Python model of the expressions launch_render, ensure_workspace, learn_rates, render_chunk, render_lanes and render_dispatch
 had in line before the header existed: integers with ==, doubles bit for bit (Python floats are the same IEEE doubles; the shim is
 built with -ffp-contract=off, as the library is).  The same file with its own main runs under the address and undefined-behaviour
 sanitizers.  And the lane counts the GPU tests that say they run on concurrent lanes rely on."""
 import ctypes as C
 import os
+import re
 import struct
 import subprocess
 from math import gcd
@@ -21,9 +22,13 @@ REC = [112 + 16, 48, 64, 96, 2 * 80]              # bytes per record of the five
 MAXCAP = 0xFFFFFF00
 
 
-class Ix(C.Structure):
-    _fields_ = [(k, C.c_uint32) for k in ("words", "tasks", "children", "hard_path", "gen", "gens", "hard_shadow_recs", "probes",
-                                          "dead_tasks", "dead_children", "dead_hard_path", "dead_rays", "qchunk")]
+# the counter block of a path level as it is today (actinon_amd/csrc/acn_counts.h): pinned, the device writes these words
+LAYOUT = {"QC_TASKS": 0, "QC_CLASS0": 1, "QC_CHILDREN": 5, "QC_FLAGS": 6, "QC_HARD_SHADOW": 7, "QC_HARD_PATH": 8, "QS_WALK_RAYS": 12,
+          "QS_HARD_SHADOW": 13, "QS_HARD_PATH": 14, "QS_CHILDREN": 15, "QS_TASKS": 16, "QS_WALK_STEPS": 17, "QS_PRIVATE_RAYS": 18, "QS_PROBES": 19,
+          "QS_DEAD_T": 28, "QS_DEAD_C": 29, "QS_DEAD_HP": 30, "QS_DEAD_R": 31, "QC_GEN": 32, "QC_N": 104, "ACN_QCHUNK": 64}
+QC_N, GEN, GENS, LEVEL_BLOCKS = LAYOUT["QC_N"], LAYOUT["QC_GEN"], 33, 6         # ACN_MAX_WALK_PASSES + 1 generation words; ACN_MAX_PATH_LEVELS + 1 levels
+TASK_OVERFLOW, CHILD_OVERFLOW, STACK_OVERFLOW, CLAMPED = 1, 2, 4, 8            # ACN_FLAG_*
+FITS, OVERFLOW, FAILS = 0, 1, 2                                                 # ACN_CHUNK_*
 
 
 def dbl(v):
@@ -52,7 +57,8 @@ def qp(tmp_path_factory):
                             ("qp_wanted_caps", None, [p, i, u, u, u, u, u, u, p, p]), ("qp_keep_caps", i, [p, u, u, p, p, i, C.c_uint32, i, p, p]),
                             ("qp_halve_caps", i, [p]), ("qp_rates_known", i, [p]), ("qp_queue_demand", d, [p, i, i]), ("qp_chunk_for_caps", u, [p, i, d, p]),
                             ("qp_set_rates", None, [p, p, C.c_uint32, p, d]), ("qp_learn_rates", None, [p, p, C.c_uint32, p, d]),
-                            ("qp_overflow_rates", None, [p, C.c_uint32, p]), ("qp_sample_rates", None, [p, i, p, C.c_uint32, u, C.c_uint, p]),
+                            ("qp_overflow_rates", None, [p, C.c_uint32, p]), ("qp_sample_rates", None, [p, i, C.c_uint32, u, C.c_uint, p]),
+                            ("qp_read_chunk", None, [p, i, p, i, p, p]), ("qp_constant", C.c_int64, [C.c_char_p]),
                             ("qp_walk_passes", C.c_uint32, [u, i, C.c_uint32, C.c_uint32]), ("qp_walk_passes_seen", C.c_uint32, [p, C.c_uint32]),
                             ("qp_lane_count", u, [u, i, i]), ("qp_lanes_for_counts", i, [i, u, u]), ("qp_one_lane", i, [p, i, u, p, u, i]),
                             ("qp_tile_order", C.c_uint32, [u, i, p])):
@@ -153,22 +159,23 @@ def m_learn_rates(rate, rate_cnt, cnt, fill, dead_share):
     return [max(max(float(fill[q]) / float(cnt), 0.85 * rate[q]), 1e-3) for q in range(5)], max(cnt, rate_cnt)
 
 
-def m_sample_rates(counts, levels, ix, cnt, plan_positions, plan_grid):
+def m_sample_rates(counts, levels, cnt, plan_positions, plan_grid):
+    w = LAYOUT
     live = [0.0] * 5
     for level in range(levels):
-        c = counts[level * ix.words:(level + 1) * ix.words]
-        gens = [c[ix.gen + g] for g in range(ix.gens)]
+        c = counts[level * QC_N:(level + 1) * QC_N]
+        gens = [c[GEN + g] for g in range(GENS)]
         s = 0.0
         for g in gens:
             s += g
-        s -= float(c[ix.dead_rays])
+        s -= float(c[w["QS_DEAD_R"]])
         top = float(max(gens))
-        for q, v in ((T, float(c[ix.tasks]) - float(c[ix.dead_tasks])), (CH, float(c[ix.children]) - float(c[ix.dead_children])),
-                     (HS, float(c[ix.hard_shadow_recs]) + float(c[ix.probes])), (HP, float(c[ix.hard_path]) - float(c[ix.dead_hard_path])),
+        for q, v in ((T, float(c[w["QC_TASKS"]]) - float(c[w["QS_DEAD_T"]])), (CH, float(c[w["QC_CHILDREN"]]) - float(c[w["QS_DEAD_C"]])),
+                     (HS, float(c[w["QS_HARD_SHADOW"]]) + float(c[w["QS_PROBES"]])), (HP, float(c[w["QC_HARD_PATH"]]) - float(c[w["QS_DEAD_HP"]])),
                      (R, s if s < top else top)):
             if v > live[q]:
                 live[q] = v
-    per_launch = float(ix.qchunk) * 4.0 * float(plan_grid)
+    per_launch = float(w["ACN_QCHUNK"]) * 4.0 * float(plan_grid)
     walkers, shaders = 3.0 * per_launch, 3.0 * per_launch
     dead = [walkers, shaders, walkers + shaders, shaders, walkers]
     pp = float(min(plan_positions, 1 << 22))
@@ -194,6 +201,53 @@ def m_walk_passes_seen(gen, launched):
         if gen[g]:
             used = g + 1
     return used + 2 if used == launched and launched > 1 else used
+
+
+STATS = ("levels", "walk_rays", "walk_steps", "hard_rays", "shade_hit_recs", "private_rays", "probe_rays", "peak_tasks", "peak_children")
+
+
+def m_read_chunk(counts, levels, passes, seeded):
+    """What render_chunk did between its synchronisation and its return -> the report, and the words as it left them"""
+    w = LAYOUT
+    h = list(counts)
+    if seeded:
+        h[GEN + 0] = 0
+    blocks = [h[level * QC_N:(level + 1) * QC_N] for level in range(levels)]
+    flags = 0
+    for level, c in enumerate(blocks):
+        flags |= c[w["QC_FLAGS"]]
+        if c[GEN + passes[level]]:
+            flags |= CHILD_OVERFLOW
+    fill = [0] * 5
+    for c in blocks:
+        for q, v in [(T, c[w["QC_TASKS"]])] + [(T, c[w["QC_CLASS0"] + k]) for k in range(4)] + [(CH, c[w["QC_CHILDREN"]]), (HS, c[w["QC_HARD_SHADOW"]]),
+                                                                                               (HP, c[w["QC_HARD_PATH"]])] + [(R, c[GEN + g]) for g in range(GENS)]:
+            if v > fill[q]:
+                fill[q] = v
+    mark = recs = 0
+    for c in blocks:
+        if c[w["QC_HARD_SHADOW"]] > mark:
+            mark, recs = c[w["QC_HARD_SHADOW"]], (c[w["QS_HARD_SHADOW"]] + c[w["QS_PROBES"]]) % (1 << 32)
+    dead_share = float(mark - recs) / float(mark) if mark > 0 and recs < mark else 0.0
+    rep = dict(flags=flags, fill=fill, dead_share=dead_share, passes_seen=[0] * LEVEL_BLOCKS, **{k: 0 for k in STATS})
+    rep["verdict"] = OVERFLOW if flags & (TASK_OVERFLOW | CHILD_OVERFLOW) else FAILS if flags & STACK_OVERFLOW else FITS
+    if rep["verdict"] != FITS:
+        return rep, h
+    for c in blocks:
+        if c[w["QC_TASKS"]] == 0 and c[w["QS_WALK_RAYS"]] == 0:
+            break
+        rep["levels"] += 1
+        rep["walk_rays"] += c[w["QS_WALK_RAYS"]]
+        rep["walk_steps"] += c[w["QS_WALK_STEPS"]]
+        rep["hard_rays"] += c[w["QS_HARD_SHADOW"]] + c[w["QS_HARD_PATH"]]
+        rep["shade_hit_recs"] += c[w["QS_CHILDREN"]]
+        rep["peak_tasks"] = max(rep["peak_tasks"], c[w["QC_TASKS"]])
+        rep["peak_children"] = max(rep["peak_children"], c[w["QC_CHILDREN"]])
+        rep["private_rays"] += c[w["QS_PRIVATE_RAYS"]]
+        rep["probe_rays"] += c[w["QS_PROBES"]]
+    for level, c in enumerate(blocks):
+        rep["passes_seen"][level] = m_walk_passes_seen(c[GEN:GEN + GENS], passes[level])
+    return rep, h
 
 
 def m_lane_count(n, lanes, lane):
@@ -358,19 +412,147 @@ def test_rate_updates(qp):
 def test_rates_of_the_learning_sample(qp):
     """Live records per level from the counter words (marks less dead slots, the fullest level), the ray bound, a fifth on top and the
     dead slots of a chunk of the planned size on the planned grid"""
-    ix = Ix(104, 0, 5, 8, 32, 33, 13, 19, 28, 29, 30, 31, 64)          # where acn_pipeline.h keeps these words (any layout will do)
     rng = np.random.default_rng(9)
     for trial in range(200):
         levels = int(rng.integers(1, 7))
-        counts = [int(x) for x in rng.integers(0, 1 << int(rng.integers(1, 31)), 104 * levels)]
+        counts = [int(x) for x in rng.integers(0, 1 << int(rng.integers(1, 31)), QC_N * levels)]
         if trial % 3 == 0:                                              # dead slots above the marks: negative live counts lose
             for level in range(levels):
-                counts[level * 104 + 28] = MAXCAP
-                counts[level * 104 + 31] = MAXCAP
+                counts[level * QC_N + LAYOUT["QS_DEAD_T"]] = MAXCAP
+                counts[level * QC_N + LAYOUT["QS_DEAD_R"]] = MAXCAP
         cnt, pp, grid = int(rng.choice([64, 256, 4096])), int(rng.choice([1, 9600, 57600, 1 << 22, 1 << 25])), int(rng.choice([7, 256, 1024]))
         r = dbl([0.0] * 5)
-        qp.qp_sample_rates(u32(counts), levels, C.byref(ix), cnt, pp, grid, r)
-        assert same_bits(list(r), m_sample_rates(counts, levels, ix, cnt, pp, grid)), (trial, levels, cnt, pp, grid)
+        qp.qp_sample_rates(u32(counts), levels, cnt, pp, grid, r)
+        assert same_bits(list(r), m_sample_rates(counts, levels, cnt, pp, grid)), (trial, levels, cnt, pp, grid)
+
+
+def test_the_counter_block_is_where_it_was(qp):
+    """The words of a level's counter block, stated: the kernels write them, acn_counts.h names them once, and the planner, Handle.QC
+    and these tests read the same table"""
+    import actinon_amd as A
+    for name, value in LAYOUT.items():
+        assert qp.qp_constant(name.encode()) == value, name
+    assert qp.qp_constant(b"QS_NO_SUCH_WORD") == -1
+    for name, value in (("ACN_MAX_WALK_PASSES", GENS - 1), ("ACN_LEVEL_BLOCKS", LEVEL_BLOCKS), ("ACN_MAX_PATH_LEVELS", LEVEL_BLOCKS - 1), ("ACN_NCLASS", 4),
+                        ("QC_CUR_GEN", GEN + GENS), ("WQ_N", 5), ("ACN_FLAG_TASK_OVERFLOW", TASK_OVERFLOW), ("ACN_FLAG_CHILD_OVERFLOW", CHILD_OVERFLOW),
+                        ("ACN_FLAG_STACK_OVERFLOW", STACK_OVERFLOW), ("ACN_FLAG_CLAMPED", CLAMPED), ("ACN_FLAGS_CHUNK_LOST", TASK_OVERFLOW | CHILD_OVERFLOW),
+                        ("ACN_CHUNK_FITS", FITS), ("ACN_CHUNK_OVERFLOW", OVERFLOW), ("ACN_CHUNK_STACK_OVERFLOW", FAILS)):
+        assert qp.qp_constant(name.encode()) == value, name
+    names = {"tasks": "QC_TASKS", "class0": "QC_CLASS0", "children": "QC_CHILDREN", "flags": "QC_FLAGS", "hard_shadow": "QC_HARD_SHADOW",
+             "hard_path": "QC_HARD_PATH", "walk_rays": "QS_WALK_RAYS", "s_hard_shadow": "QS_HARD_SHADOW", "s_hard_path": "QS_HARD_PATH",
+             "s_children": "QS_CHILDREN", "s_tasks": "QS_TASKS", "s_probes": "QS_PROBES", "dead_t": "QS_DEAD_T", "dead_c": "QS_DEAD_C",
+             "dead_hp": "QS_DEAD_HP", "dead_r": "QS_DEAD_R", "gen0": "QC_GEN"}
+    assert A.Handle.QC == {k: LAYOUT[v] for k, v in names.items()}
+
+
+def test_last_stage_names_are_the_headers_enum():
+    """Handle.last_stages names the 25 slots of acn_last_stage_ms as the ACN_LAST_* enum of include/actinon_hip.h does, in its order"""
+    import actinon_amd as A
+    text = open(os.path.join(ROOT, "include", "actinon_hip.h")).read()
+    body = re.search(r"enum\s*\{([^}]*?ACN_LAST_N[^}]*)\};\s*int acn_last_stage_ms\s*\(", text, re.S).group(1)
+    members = re.findall(r"\bACN_LAST_(\w+)", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert members[-1] == "N" and "= 0" in body.split(",")[0] and body.count("=") == 1          # counted from 0, no slot moved by hand
+    assert [m.lower() for m in members[:-1]] == A.Handle.STAGES and len(A.Handle.STAGES) == 25
+
+
+def read_chunk(qp, counts, levels, passes, seeded):
+    """acn_read_chunk on a copy of the words -> the report as m_read_chunk makes it, and the words as it left them"""
+    c, words, dead = u32(counts), u64([0] * (7 + LEVEL_BLOCKS + len(STATS))), C.c_double(-1.0)
+    qp.qp_read_chunk(c, levels, u32(passes), seeded, words, C.byref(dead))
+    words = list(words)
+    rep = dict(flags=words[0], verdict=words[1], fill=words[2:7], passes_seen=words[7:7 + LEVEL_BLOCKS], dead_share=dead.value)
+    rep.update(zip(STATS, words[7 + LEVEL_BLOCKS:]))
+    return rep, list(c)
+
+
+def same_report(a, b):
+    return {k: v for k, v in a.items() if k != "dead_share"} == {k: v for k, v in b.items() if k != "dead_share"} and same_bits([a["dead_share"]], [b["dead_share"]])
+
+
+def test_reading_a_chunks_counter_blocks(qp):
+    """acn_read_chunk against the expressions render_chunk had after its synchronisation: random blocks, then every edge by hand"""
+    w = LAYOUT
+    rng = np.random.default_rng(12)
+    verdicts = set()
+    for trial in range(400):
+        levels = int(rng.integers(1, LEVEL_BLOCKS + 1))
+        counts = [int(x) for x in rng.integers(0, 1 << int(rng.integers(1, 31)), QC_N * levels)]
+        passes = [int(x) for x in rng.integers(1, GENS, LEVEL_BLOCKS)]
+        if trial % 4:                                                   # random flag words nearly always say overflow: mostly choose them
+            for level in range(levels):
+                counts[level * QC_N + w["QC_FLAGS"]] = int(rng.choice([0, 0, 0, CLAMPED, STACK_OVERFLOW, TASK_OVERFLOW, CHILD_OVERFLOW | CLAMPED], p=[.3, .2, .2, .15, .05, .05, .05]))
+                if trial % 4 > 1:
+                    counts[level * QC_N + GEN + passes[level]] = 0     # ... and leave no rays behind the last pass
+        if trial % 5 == 0:                                              # levels that end early
+            for i in range(int(rng.integers(0, levels)) * QC_N, levels * QC_N):
+                counts[i] = 0 if rng.random() < 0.9 else counts[i]
+        seeded = int(rng.random() < 0.5)
+        got, want = read_chunk(qp, counts, levels, passes, seeded), m_read_chunk(counts, levels, passes, seeded)
+        assert same_report(got[0], want[0]) and got[1] == want[1], (trial, levels, passes, seeded)
+        verdicts.add(want[0]["verdict"])
+    assert verdicts == {FITS, OVERFLOW, FAILS}
+
+    def chunk(levels, words, passes=4, seeded=0):
+        """levels zero blocks with words[(level, name or index)] = value -> the report both ways agree on, and the words left"""
+        counts = [0] * (QC_N * levels)
+        for (level, word), v in words.items():
+            counts[level * QC_N + (w[word] if isinstance(word, str) else word)] = v
+        got, want = read_chunk(qp, counts, levels, [passes] * LEVEL_BLOCKS, seeded), m_read_chunk(counts, levels, [passes] * LEVEL_BLOCKS, seeded)
+        assert same_report(got[0], want[0]) and got[1] == want[1], words
+        return got
+
+    busy, busy2 = ({(level, k): 10 + level for level in range(n) for k in ("QC_TASKS", "QS_WALK_RAYS")} for n in (3, 2))
+    # a task overflow in a middle level only
+    r, _ = chunk(3, {**busy, (1, "QC_FLAGS"): TASK_OVERFLOW})
+    assert r["verdict"] == OVERFLOW and r["flags"] == TASK_OVERFLOW and r["levels"] == 0 and r["fill"][T] == 12
+    # rays left in QC_GEN + passes of one level and no flag anywhere
+    r, _ = chunk(3, {**busy, (2, GEN + 4): 1})
+    assert r["verdict"] == OVERFLOW and r["flags"] == CHILD_OVERFLOW and r["fill"][R] == 1
+    r, _ = chunk(3, {**busy, (2, GEN + 3): 1, (2, GEN + 5): 1})         # ... the words beside it do not say so
+    assert r["verdict"] == FITS and r["flags"] == 0
+    # a stack overflow with a task overflow is a lost chunk, alone it fails the call
+    r, _ = chunk(3, {**busy, (0, "QC_FLAGS"): STACK_OVERFLOW, (2, "QC_FLAGS"): TASK_OVERFLOW})
+    assert r["verdict"] == OVERFLOW and r["flags"] == STACK_OVERFLOW | TASK_OVERFLOW
+    r, _ = chunk(3, {**busy, (1, "QC_FLAGS"): STACK_OVERFLOW})
+    assert r["verdict"] == FAILS and r["flags"] == STACK_OVERFLOW and r["levels"] == 0
+    # a clamped contribution alone: the chunk fits and the flag is carried -- whatever the verdict
+    r, _ = chunk(3, {**busy, (2, "QC_FLAGS"): CLAMPED})
+    assert r["verdict"] == FITS and r["flags"] == CLAMPED and r["levels"] == 3 and r["walk_rays"] == 33
+    assert chunk(3, {**busy, (2, "QC_FLAGS"): CLAMPED, (0, "QC_FLAGS"): CHILD_OVERFLOW})[0]["flags"] == CLAMPED | CHILD_OVERFLOW
+    assert chunk(3, {**busy, (2, "QC_FLAGS"): CLAMPED | STACK_OVERFLOW})[0]["flags"] == CLAMPED | STACK_OVERFLOW
+    # the seeded generation: cleared before anything reads it, in level 0 alone
+    r, left = chunk(2, {**busy2, (0, GEN): 5000, (1, GEN): 7, (0, GEN + 1): 40}, seeded=1)
+    assert left[GEN] == 0 and left[QC_N + GEN] == 7 and r["fill"][R] == 40 and r["passes_seen"][:2] == [2, 1]
+    r, left = chunk(2, {**busy2, (0, GEN): 5000, (1, GEN): 7, (0, GEN + 1): 40}, seeded=0)
+    assert left[GEN] == 5000 and r["fill"][R] == 5000 and r["passes_seen"][:2] == [2, 1]
+    r, _ = chunk(1, {(0, GEN): 5000}, passes=1, seeded=1)               # ... also where it is the only pass: no rays are left over
+    assert r["verdict"] == FITS and r["fill"][R] == 0 and r["passes_seen"][0] == 1
+    assert chunk(1, {(0, GEN + 1): 5000}, passes=1, seeded=1)[0]["verdict"] == OVERFLOW
+    # an all-zero level followed by a non-zero one: the statistics stop before it, the marks do not
+    r, _ = chunk(4, {(0, "QC_TASKS"): 9, (0, "QS_WALK_STEPS"): 3, (1, "QS_WALK_STEPS"): 100, (1, "QC_CHILDREN"): 50, (2, "QS_WALK_RAYS"): 77, (2, "QC_TASKS"): 400})
+    assert (r["levels"], r["walk_rays"], r["walk_steps"], r["peak_tasks"], r["peak_children"]) == (1, 0, 3, 9, 0) and r["fill"][:2] == [400, 50]
+    r, _ = chunk(3, {(0, "QC_TASKS"): 9, (0, "QS_WALK_RAYS"): 4, (2, "QC_TASKS"): 400, (2, "QS_WALK_RAYS"): 77})
+    assert (r["levels"], r["walk_rays"], r["peak_tasks"]) == (1, 4, 9) and r["fill"][T] == 400
+    r, _ = chunk(3, {(0, "QS_WALK_RAYS"): 1, (1, "QC_TASKS"): 1, (2, "QS_WALK_STEPS"): 5, (1, "QS_HARD_SHADOW"): 0xFFFFFFFF, (1, "QS_HARD_PATH"): 0xFFFFFFFF,
+                     (0, "QS_CHILDREN"): 6, (1, "QS_PRIVATE_RAYS"): 8, (1, "QS_PROBES"): 2})
+    assert (r["levels"], r["hard_rays"], r["shade_hit_recs"], r["private_rays"], r["probe_rays"]) == (2, 2 * 0xFFFFFFFF, 6, 8, 2)
+    # the marks of the size classes count into the task queue
+    for k in range(4):
+        r, _ = chunk(2, {**busy2, (1, w["QC_CLASS0"] + k): 300 + k})
+        assert r["fill"][T] == 300 + k and r["peak_tasks"] == 11
+    # the dead share comes from the level with the largest deferred-shadow mark: the last one here
+    marks = {**busy, (0, "QC_HARD_SHADOW"): 999, (0, "QS_HARD_SHADOW"): 1, (2, "QC_HARD_SHADOW"): 1000}
+    r, _ = chunk(3, {**marks, (2, "QS_HARD_SHADOW"): 900, (2, "QS_PROBES"): 100})
+    assert r["dead_share"] == 0.0 and r["fill"][HS] == 1000
+    r, _ = chunk(3, {**marks, (2, "QS_HARD_SHADOW"): 900, (2, "QS_PROBES"): 99})
+    assert r["dead_share"] == 1.0 / 1000.0
+    r, _ = chunk(3, {**marks, (2, "QS_HARD_SHADOW"): 900, (2, "QS_PROBES"): 101})               # (more records than the mark: no share)
+    assert r["dead_share"] == 0.0
+    r, _ = chunk(3, {**marks, (2, "QC_HARD_SHADOW"): 999, (2, "QS_HARD_SHADOW"): 999})          # an equal mark: the first level keeps it
+    assert r["dead_share"] == 998.0 / 999.0
+    # every level and every pass the device has
+    r, _ = chunk(LEVEL_BLOCKS, {(LEVEL_BLOCKS - 1, GEN + GENS - 1): 3}, passes=GENS - 1)
+    assert r["verdict"] == OVERFLOW and r["fill"][R] == 3
 
 
 def test_walk_passes(qp):
