@@ -37,7 +37,8 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_re
                "acn_key_hist_threshold",
                "acn_surface_reduce", "acn_surface_reduce_dev", "acn_surface_lens", "acn_surface_lens_dev", "acn_surface_lens_main_pass_dev",
                "acn_lens_layers_reduce", "acn_lens_layers_reduce_dev", "acn_render_lens_layers", "acn_render_lens_layers_dev",
-               "acn_render_lens_layers_main_pass_dev", "acn_denoise_layers", "acn_denoise_layers_dev"]
+               "acn_render_lens_layers_main_pass_dev", "acn_denoise_layers", "acn_denoise_layers_dev",
+               "acn_lens_layers_merge", "acn_lens_layers_merge_dev", "acn_lens_layers_resolve_dev"]
 # symbols declared by include/acn_scene.h
 HOST_SYMBOLS = ["acn_rotx", "acn_roty", "acn_rotz", "acn_obj_plane_s_create", "acn_obj_sphere_s_create",
                 "acn_obj_squaroid_s_create_squaroid", "acn_obj_squaroid_s_create_ellipsoid",
@@ -105,7 +106,10 @@ for _n in ["acn_render_lens_layers", "acn_render_lens_layers_dev"]:
 hip.acn_render_lens_layers_main_pass_dev.argtypes = [vp, C.c_size_t, C.c_size_t, P(abi.LensParams), C.c_uint32, vp, vp, vp, P(abi.RenderOpts)]
 for _n in ["acn_denoise_layers", "acn_denoise_layers_dev"]:
     getattr(hip, _n).argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, P(abi.DenoiseParams), vp, P(abi.RenderOpts)]
-hip.acn_select_above_dev.argtypes = [vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, vp, P(C.c_uint64), P(abi.RenderOpts)]
+for _n in ["acn_lens_layers_merge", "acn_lens_layers_merge_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, P(abi.RenderOpts)]
+hip.acn_lens_layers_resolve_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, P(abi.RenderOpts)]
+hip.acn_select_above_dev.argtypes =[vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, vp, P(C.c_uint64), P(abi.RenderOpts)]
 hip.acn_select_above.argtypes = [vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, P(C.c_uint64)]
 hip.acn_key_histogram_dev.argtypes = [vp, vp, C.c_size_t, vp, P(abi.RenderOpts)]
 hip.acn_key_histogram.argtypes = [vp, vp, C.c_size_t, vp]

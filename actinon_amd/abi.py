@@ -28,7 +28,8 @@ ACN_LENS_SEED = 2718281828
 ACN_STATS_STRIDE = 8
 ACN_STATS_NOISE_FLOOR = 0.01
 
-# layered lens records (acn_lens_layers_reduce, acn_render_lens_layers, acn_denoise_layers): planes of surface and statistics records
+# layered lens records (acn_lens_layers_reduce, acn_render_lens_layers, acn_denoise_layers, acn_lens_layers_merge,
+# acn_lens_layers_resolve_dev): planes of surface and statistics records
 ACN_LAYERS_SURFACE_PLANES, ACN_LAYERS_STATS_PLANES = 2, 3
 
 # selecting positions by a key (acn_select_above, acn_key_histogram): bins of the histogram, its words (the last counts NaN keys)

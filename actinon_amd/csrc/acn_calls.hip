@@ -795,6 +795,57 @@ extern "C" int acn_denoise_layers( acn_scene_handle* h, const double* stats, con
     return hc.run( [ & ] { return acn_denoise_layers_dev( h, d_st, d_surf, width, height, prm, d_rgb, &c.opts ); } );
 }
 
+/* ---- layered records merged across passes and resolved (k_lens_layers_merge.hip; the checks: acn_layers_host.h) ---- */
+extern "C" int acn_lens_layers_merge_dev( acn_scene_handle* h, void* d_acc_surface, void* d_acc_stats, size_t n_acc, const void* d_part_surface,
+                                          const void* d_part_stats, size_t n_part, const int64_t* d_index, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_layers_merge_check( h != nullptr, d_acc_surface, d_acc_stats, n_acc, d_part_surface, d_part_stats, n_part, d_index, false,
+                                c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_lens_layers_merge( ( double* )d_acc_surface, ( double* )d_acc_stats, n_acc, ( const double* )d_part_surface, ( const double* )d_part_stats,
+                                  n_part, d_index, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_lens_layers_merge( acn_scene_handle* h, double* acc_surface, double* acc_stats, size_t n_acc, const double* part_surface,
+                                      const double* part_stats, size_t n_part, const int64_t* index, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_layers_merge_check( h != nullptr, acc_surface, acc_stats, n_acc, part_surface, part_stats, n_part, index, true, c.opts.shard_world,
+                                &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n_part == 0 || n_acc == 0 ) return ACN_OK;
+    const size_t srec = sizeof( double ) * ACN_SURF_STRIDE * ACN_LAYERS_SURFACE_PLANES, trec = sizeof( double ) * ACN_STATS_STRIDE * ACN_LAYERS_STATS_PLANES;
+    HostCall hc( h );
+    void* d_as = hc.inout( acc_surface, acc_surface, srec * n_acc );
+    void* d_at = hc.inout( acc_stats, acc_stats, trec * n_acc );
+    void* d_ps = hc.in( part_surface, srec * n_part );
+    void* d_pt = hc.in( part_stats, trec * n_part );
+    void* d_index = index ? hc.in( index, sizeof( int64_t ) * n_part ) : nullptr;
+    c.opts.stream = nullptr;
+    return hc.run( [ & ] { return acn_lens_layers_merge_dev( h, d_as, d_at, n_acc, d_ps, d_pt, n_part, ( const int64_t* )d_index, &c.opts ); } );
+}
+
+extern "C" int acn_lens_layers_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb, void* d_out_noise, void* d_out_pooled,
+                                            const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_layers_resolve_check( h != nullptr, d_stats, n, d_out_rgb, d_out_noise, d_out_pooled, c.opts.shard_world, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 || ( !d_out_rgb && !d_out_noise && !d_out_pooled ) ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_lens_layers_resolve( ( const double* )d_stats, n, h->dev.prm.background_color, h->dev.prm.gamma, ( c.opts.flags & ACN_OPT_LINEAR_OUT ) ? 1 : 0,
+                                    ( double* )d_out_rgb, ( double* )d_out_noise, ( double* )d_out_pooled, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
 /* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */
 extern "C" int acn_select_above_dev( acn_scene_handle* h, const void* d_key, size_t n, const acn_select_params* prm, const void* d_src_pos_xy,
                                      void* d_out_index, void* d_out_pos_xy, void* d_out_count, uint64_t* out_count, const acn_render_opts* opts )

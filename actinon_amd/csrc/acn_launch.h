@@ -121,6 +121,16 @@ void acn_launch_surface_reduce( const double* records, size_t n, uint32_t sample
 void acn_launch_lens_layers( const double* records, const double* rad, size_t n, uint32_t samples, double* out_surface, size_t surface_plane,
                              double* out_stats, size_t stats_plane, hipStream_t stream );
 
+/* layered records of two passes merged by surface class, and their resolve (k_lens_layers_merge.hip; include/actinon_hip.h states
+ * both).  merge: the accumulator's planes acc_surface [ 2 ][ n_acc ][ ACN_SURF_STRIDE ] and acc_stats [ 3 ][ n_acc ][ ACN_STATS_STRIDE ] take the
+ * part's planes [ . ][ n_part ][ . ], position j into index ? index[ j ] : j; indices outside [ 0, n_acc ) are skipped; n_part >= 1.
+ * resolve: stats [ 3 ][ n ][ ACN_STATS_STRIDE ] -> out_rgb, out_noise as acn_launch_stats_resolve of the pooled record, out_pooled
+ * [ n ][ ACN_STATS_STRIDE ]; each nullable.  Every record buffer 16-byte aligned */
+void acn_launch_lens_layers_merge( double* acc_surface, double* acc_stats, size_t n_acc, const double* part_surface, const double* part_stats,
+                                   size_t n_part, const int64_t* index, hipStream_t stream );
+void acn_launch_lens_layers_resolve( const double* stats, size_t n, const double* background, double gamma, int linear, double* out_rgb,
+                                     double* out_noise, double* out_pooled, hipStream_t stream );
+
 /* the filter of acn_denoise_layers (k_denoise_layers.hip): stats [ 3 ][ n ][ ACN_STATS_STRIDE ], surf [ 2 ][ n ][ ACN_SURF_STRIDE ], both 16-byte
  * aligned; the parameters are final values; scratch: ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL bytes per pixel, 128-byte aligned */
 #define ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL 256

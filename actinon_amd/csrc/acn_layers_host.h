@@ -1,6 +1,7 @@
-/* acn_layers_host.h -- what acn_lens_layers_reduce*, acn_render_lens_layers* and acn_denoise_layers* check without a handle and without
- * the GPU.  Plain C++, no HIP header: acn_calls.hip calls these before it touches a handle; tests/csrc/layers_cpu.cpp compiles the
- * header on its own into a program that runs under the address and undefined-behaviour sanitizers.  A check returns an acn_status
+/* acn_layers_host.h -- what acn_lens_layers_reduce*, acn_render_lens_layers*, acn_denoise_layers*, acn_lens_layers_merge* and
+ * acn_lens_layers_resolve_dev check without a handle and without the GPU.  Plain C++, no HIP header: acn_calls.hip calls these before
+ * it touches a handle; tests/csrc/layers_cpu.cpp and tests/csrc/layers_merge_cpu.cpp compile the header on its own into programs
+ * that run under the address and undefined-behaviour sanitizers.  A check returns an acn_status
  * and, on a refusal, the message acn_last_error will carry.  What needs the handle's scene (an open aperture without a focal
  * length, a pixel range outside the image) and the parameters of the filter (denoise_check) stay with acn_calls.hip. */
 #ifndef ACN_LAYERS_HOST_H
@@ -60,6 +61,43 @@ static inline int acn_layers_denoise_check( const void* stats, const void* surfa
 {
     if( ( uintptr_t )stats % 16 ) { *msg = "the statistics planes of a layered denoise call are read 16 bytes at a time: align the buffer"; return ACN_ERR_ARG; }
     if( ( uintptr_t )surface % 16 ) { *msg = "the surface planes of a layered denoise call are read 16 bytes at a time: align the buffer"; return ACN_ERR_ARG; }
+    return ACN_OK;
+}
+
+/* every check of acn_lens_layers_merge* that needs no handle, in the order the header lists them.  index_is_host: the host form, whose
+ * index list is read here -- acn_stats_index_check, as for acn_lens_stats_merge: in range and none twice --; the _dev form's list is
+ * on the device, and only its alignment is checked */
+static inline int acn_layers_merge_check( bool have_handle, const void* acc_surface, const void* acc_stats, uint64_t n_acc, const void* part_surface,
+                                          const void* part_stats, uint64_t n_part, const int64_t* index, bool index_is_host, uint32_t shard_world,
+                                          std::string* msg )
+{
+    if( !have_handle ) { *msg = "null argument: handle"; return ACN_ERR_ARG; }
+    if( n_acc && !acc_surface ) { *msg = "null argument: acc_surface"; return ACN_ERR_ARG; }
+    if( n_acc && !acc_stats ) { *msg = "null argument: acc_stats"; return ACN_ERR_ARG; }
+    if( n_part && !part_surface ) { *msg = "null argument: part_surface"; return ACN_ERR_ARG; }
+    if( n_part && !part_stats ) { *msg = "null argument: part_stats"; return ACN_ERR_ARG; }
+    if( shard_world > 1 ) { *msg = "a merge of layered records is not sharded"; return ACN_ERR_ARG; }
+    if( ( uintptr_t )acc_surface % 16 || ( uintptr_t )acc_stats % 16 || ( uintptr_t )part_surface % 16 || ( uintptr_t )part_stats % 16 )
+    {
+        *msg = "surface and statistics records are read and written 16 bytes at a time: align the buffers";
+        return ACN_ERR_ARG;
+    }
+    if( ( uintptr_t )index % 8 ) { *msg = "index is an array of int64_t: align the buffer"; return ACN_ERR_ARG; }
+    if( n_acc > ACN_LENSSURF_MAX_N || n_part > ACN_LENSSURF_MAX_N ) { *msg = "more than 2^38 positions in one call"; return ACN_ERR_ARG; }
+    if( index_is_host || !index ) return acn_stats_index_check( index, ( size_t )n_part, ( size_t )n_acc, msg );
+    return ACN_OK;
+}
+
+/* every check of acn_lens_layers_resolve_dev that needs no handle */
+static inline int acn_layers_resolve_check( bool have_handle, const void* stats, uint64_t n, const void* out_rgb, const void* out_noise,
+                                            const void* out_pooled, uint32_t shard_world, std::string* msg )
+{
+    if( !have_handle ) { *msg = "null argument: handle"; return ACN_ERR_ARG; }
+    if( n && !stats ) { *msg = "null argument: stats"; return ACN_ERR_ARG; }
+    if( shard_world > 1 ) { *msg = "a resolve of layered records is not sharded"; return ACN_ERR_ARG; }
+    if( ( uintptr_t )stats % 16 || ( uintptr_t )out_pooled % 16 ) { *msg = "statistics records are read and written 16 bytes at a time: align the buffers"; return ACN_ERR_ARG; }
+    if( ( uintptr_t )out_rgb % 8 || ( uintptr_t )out_noise % 8 ) { *msg = "out_rgb and out_noise are arrays of doubles: align the buffers"; return ACN_ERR_ARG; }
+    if( n > ACN_LENSSURF_MAX_N ) { *msg = "n " + std::to_string( n ) + " is above 2^38 positions in one call"; return ACN_ERR_ARG; }
     return ACN_OK;
 }
 

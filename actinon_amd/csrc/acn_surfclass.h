@@ -26,14 +26,17 @@
 /* the class of a sample as two words: ( e, x ) and ( h, hit ) */
 struct SurfKey { uint64_t ex, hh; };
 
-__device__ static inline SurfKey surf_key( const double* r )
+/* from doubles [ 0 ], [ 7 ], [ 8 ], [ 13 ] of a record (k_lens_layers_merge.hip holds its records in registers) */
+__device__ static inline SurfKey surf_key_of( double dist, double de, double dx, double dh )
 {
     SurfKey key;
-    const uint32_t e = ( uint32_t )( int32_t )r[ 7 ], x = ( uint32_t )( int32_t )r[ 8 ], h = ( uint32_t )( int32_t )r[ 13 ];
+    const uint32_t e = ( uint32_t )( int32_t )de, x = ( uint32_t )( int32_t )dx, h = ( uint32_t )( int32_t )dh;
     key.ex = ( ( uint64_t )e << 32 ) | x;
-    key.hh = ( ( uint64_t )h << 1 ) | ( r[ 0 ] < __builtin_inf() ? 1u : 0u );
+    key.hh = ( ( uint64_t )h << 1 ) | ( dist < __builtin_inf() ? 1u : 0u );
     return key;
 }
+
+__device__ static inline SurfKey surf_key( const double* r ) { return surf_key_of( r[ 0 ], r[ 7 ], r[ 8 ], r[ 13 ] ); }
 
 __device__ static inline bool surf_key_eq( const SurfKey& a, const SurfKey& b ) { return a.ex == b.ex && a.hh == b.hh; }
 

@@ -176,19 +176,14 @@ void k_stats_merge( double2* acc, size_t n_acc, const double2* __restrict__ part
         if( i < 0 ) return;
     }
     if( ( size_t )i >= n_acc ) return;
-    const double2 b0 = part[ 4 * j ], b1 = part[ 4 * j + 1 ], b2 = part[ 4 * j + 2 ], b3 = part[ 4 * j + 3 ];
-    if( stats_empty( b0.x ) ) return;
+    StatsRec rb;
+    rb.q[ 0 ] = part[ 4 * j ]; rb.q[ 1 ] = part[ 4 * j + 1 ]; rb.q[ 2 ] = part[ 4 * j + 2 ]; rb.q[ 3 ] = part[ 4 * j + 3 ];
+    if( stats_empty( rb.q[ 0 ].x ) ) return;
     double2* a = acc + 4 * ( size_t )i;
-    const double2 a0 = a[ 0 ], a1 = a[ 1 ], a2 = a[ 2 ], a3 = a[ 3 ];
-    if( stats_empty( a0.x ) ) { a[ 0 ] = b0; a[ 1 ] = b1; a[ 2 ] = b2; a[ 3 ] = b3; return; }
-    const double na = a0.x, nb = b0.x, nn = na + nb;
-    const double fb = nb / nn, fab = ( na * nb ) / nn;
-    const double dx = b0.y - a0.y, dy = b1.x - a1.x, dz = b1.y - a1.y;
-    const double mx = a0.y + dx * fb, my = a1.x + dy * fb, mz = a1.y + dz * fb;
-    const double sx = ( a2.x + b2.x ) + ( dx * dx ) * fab;
-    const double sy = ( a2.y + b2.y ) + ( dy * dy ) * fab;
-    const double sz = ( a3.x + b3.x ) + ( dz * dz ) * fab;
-    a[ 0 ] = make_double2( nn, mx ); a[ 1 ] = make_double2( my, mz ); a[ 2 ] = make_double2( sx, sy ); a[ 3 ] = make_double2( sz, 0.0 );
+    StatsRec ra;
+    ra.q[ 0 ] = a[ 0 ]; ra.q[ 1 ] = a[ 1 ]; ra.q[ 2 ] = a[ 2 ]; ra.q[ 3 ] = a[ 3 ];
+    const StatsRec r = stats_empty( ra.q[ 0 ].x ) ? rb : stats_pair_merge( ra, rb );   /* (an EMPTY a: b, bit for bit) */
+    a[ 0 ] = r.q[ 0 ]; a[ 1 ] = r.q[ 1 ]; a[ 2 ] = r.q[ 2 ]; a[ 3 ] = r.q[ 3 ];
 }
 
 /* out_rgb (nullable): the mean, or the background of an EMPTY record, through cl_s_sat unless linear; out_noise (nullable): `noise` */
@@ -198,26 +193,9 @@ void k_stats_resolve( const double2* __restrict__ stats, size_t n, double bg_x, 
 {
     const size_t i = ( size_t )blockIdx.x * blockDim.x + threadIdx.x;
     if( i >= n ) return;
-    const double2 r0 = stats[ 4 * i ], r1 = stats[ 4 * i + 1 ], r2 = stats[ 4 * i + 2 ], r3 = stats[ 4 * i + 3 ];
-    const bool empty = stats_empty( r0.x );
-    const double cnt = r0.x;
-    if( out_rgb )
-    {
-        V3 c = empty ? mk( bg_x, bg_y, bg_z ) : mk( r0.y, r1.x, r1.y );
-        if( !linear ) c = cl_sat( c, gamma );
-        out_rgb[ 3 * i ] = c.x; out_rgb[ 3 * i + 1 ] = c.y; out_rgb[ 3 * i + 2 ] = c.z;
-    }
-    if( out_noise )
-    {
-        double noise = __builtin_inf();
-        if( !empty && cnt > 1.0 )
-        {
-            const double vx = stats_var_of_mean( r2.x, cnt ), vy = stats_var_of_mean( r2.y, cnt ), vz = stats_var_of_mean( r3.x, cnt );
-            const double lum = ( 0.2126 * r0.y + 0.7152 * r1.x ) + 0.0722 * r1.y;
-            noise = acn_sqrt( ( ( 0.2126 * 0.2126 ) * vx + ( 0.7152 * 0.7152 ) * vy ) + ( 0.0722 * 0.0722 ) * vz ) / ( acn_fabs( lum ) + ACN_STATS_NOISE_FLOOR );
-        }
-        out_noise[ i ] = noise;
-    }
+    StatsRec r;
+    r.q[ 0 ] = stats[ 4 * i ]; r.q[ 1 ] = stats[ 4 * i + 1 ]; r.q[ 2 ] = stats[ 4 * i + 2 ]; r.q[ 3 ] = stats[ 4 * i + 3 ];
+    stats_resolve_write( r, i, bg_x, bg_y, bg_z, gamma, linear, out_rgb, out_noise );
 }
 
 void acn_launch_lens_rays( const DevScene& sc, const double* pos_xy, size_t first_pixel, size_t n, const LensSetup& ls,

@@ -708,6 +708,55 @@ class Handle:
         check(hip.acn_denoise_layers_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)),
               "acn_denoise_layers_dev")
 
+    # layered records across passes (acn_lens_layers_merge, acn_lens_layers_resolve_dev): layers matched by surface class
+    def lens_layers_merge(self, acc_surface, acc_stats, part_surface, part_stats, index=None):
+        """Merges the layered records of a part into copies of an accumulator's (acn_lens_layers_merge), position j of the part into
+        position index[j] (index None: j).  Surface planes: two Surface or [2,n,16]; statistics planes: three LensStats or [3,n,8]
+        -> ( [Surface, Surface], [LensStats, LensStats, LensStats] ).  Indices out of range or given twice are refused."""
+        a_s = np.array(self._planes(acc_surface, Surface, abi.ACN_LAYERS_SURFACE_PLANES, abi.ACN_SURF_STRIDE))
+        a_t = np.array(self._planes(acc_stats, LensStats, abi.ACN_LAYERS_STATS_PLANES, abi.ACN_STATS_STRIDE))
+        b_s = self._planes(part_surface, Surface, abi.ACN_LAYERS_SURFACE_PLANES, abi.ACN_SURF_STRIDE)
+        b_t = self._planes(part_stats, LensStats, abi.ACN_LAYERS_STATS_PLANES, abi.ACN_STATS_STRIDE)
+        if a_s.shape[1] != a_t.shape[1] or b_s.shape[1] != b_t.shape[1]:
+            raise ValueError(f"surface and statistics planes of one side hold the same positions, got {a_s.shape}, {a_t.shape}, {b_s.shape}, {b_t.shape}")
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int64).reshape(-1)
+        if idx is not None and len(idx) != b_t.shape[1]:
+            raise ValueError(f"{b_t.shape[1]} positions need {b_t.shape[1]} indices, got {len(idx)}")
+        o = self._plain_opts(False, None)
+        check(hip.acn_lens_layers_merge(self.h, a_s.ctypes.data, a_t.ctypes.data, a_t.shape[1], b_s.ctypes.data, b_t.ctypes.data, b_t.shape[1],
+                                        None if idx is None else idx.ctypes.data, C.byref(o)), "acn_lens_layers_merge")
+        return [Surface(p) for p in a_s], [LensStats(p, self) for p in a_t]
+
+    def lens_layers_merge_dev(self, d_acc_surface_ptr, d_acc_stats_ptr, n_acc, d_part_surface_ptr, d_part_stats_ptr, n_part, d_index_ptr=None,
+                              stream=None):
+        """Device buffers: accumulator [2,n_acc,16] and [3,n_acc,8], part [2,n_part,16] and [3,n_part,8] float64, 16-byte aligned;
+        d_index int64 [n_part] or None.  An index outside [0, n_acc) is skipped; a caller's stream is never synchronised."""
+        o = self._plain_opts(False, stream)
+        check(hip.acn_lens_layers_merge_dev(self.h, d_acc_surface_ptr, d_acc_stats_ptr, n_acc, d_part_surface_ptr, d_part_stats_ptr, n_part,
+                                            d_index_ptr, C.byref(o)), "acn_lens_layers_merge_dev")
+
+    def lens_layers_resolve_dev(self, d_stats_ptr, n, d_out_rgb_ptr=None, d_out_noise_ptr=None, d_out_pooled_ptr=None, linear=False, stream=None):
+        """Device statistics planes [3,n,8] as one population per position: the colour [n,3] (saturated unless linear; the
+        background where all three records are EMPTY), the noise [n] and the pooled record [n,8]; each output may be None."""
+        o = self._plain_opts(linear, stream)
+        check(hip.acn_lens_layers_resolve_dev(self.h, d_stats_ptr, n, d_out_rgb_ptr, d_out_noise_ptr, d_out_pooled_ptr, C.byref(o)),
+              "acn_lens_layers_resolve_dev")
+
+    def lens_layers_resolve(self, stats, linear=False):
+        """acn_lens_layers_resolve_dev on host planes (three LensStats or [3,n,8]) -> ( rgb [n,3], noise [n], pooled LensStats ); the
+        copies go through torch."""
+        import torch
+        raw = self._planes(stats, LensStats, abi.ACN_LAYERS_STATS_PLANES, abi.ACN_STATS_STRIDE)
+        n = raw.shape[1]
+        dev = torch.device("cuda", self.device)
+        d = torch.from_numpy(raw).to(dev)
+        rgb = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        noise = torch.empty((n,), dtype=torch.float64, device=dev)
+        pooled = torch.empty((n, abi.ACN_STATS_STRIDE), dtype=torch.float64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.lens_layers_resolve_dev(d.data_ptr(), n, rgb.data_ptr(), noise.data_ptr(), pooled.data_ptr(), linear=linear)
+        return rgb.cpu().numpy(), noise.cpu().numpy(), LensStats(pooled.cpu().numpy(), self)
+
     # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
     @staticmethod
     def select_params(threshold, capacity=0, raster_width=0, raster_first=0):

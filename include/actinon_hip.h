@@ -664,8 +664,63 @@ int acn_surface_lens              ( acn_scene_handle* h, const double* pos_xy, s
  *   With plane 1 and the rest EMPTY everywhere the call is therefore acn_denoise_stats( stats plane 0, surface plane 0 ) bit for bit.
  * acn_lens_layers_reduce* and acn_denoise_layers* touch no work queue, counter or learned rate: renders before and after them are
  * bit-identical, acn_last_stage_ms ([ 23 ], [ 24 ] included), acn_last_counters and acn_last_kernel_ms do not move.
- * Out of scope: merging layered records across passes -- acn_lens_stats_merge* has no notion of which class a layer of either pass
- * is -- and with it tools/render_progressive.py on layers; acn_denoise_stats of a single plane stays what that tool uses. */
+ *
+ * acn_lens_layers_merge*: the layered records of another pass (another seed) merged into an accumulator of layered records, layer to
+ * layer by surface class (k_lens_layers_merge.hip); tools/render_progressive.py --layers is a caller.  The accumulator is
+ * acc_surface [ 2 ][ n_acc ][ ACN_SURF_STRIDE ] and acc_stats [ 3 ][ n_acc ][ ACN_STATS_STRIDE ], the part part_surface [ 2 ][ n_part ][ . ] and
+ * part_stats [ 3 ][ n_part ][ . ].  For j in [ 0, n_part ), i = index ? index[ j ] : j, the slots of position i of the accumulator are
+ * A0, A1 (a surface and a statistics record each) and Ar (statistics), those of position j of the part B0, B1, Br.
+ *   PRESENT    a layer slot whose statistics record is not EMPTY.  Its KEY is ( hit, e, x, h ) of its surface record, read as
+ *              acn_surface_reduce* reads a sample's: [ 0 ] < inf; [ 7 ], [ 8 ], [ 13 ] converted to int32.  n of a slot is [ 0 ] of its
+ *              statistics record.
+ *   Br, B0 and B1 all EMPTY (B0, B1 not PRESENT): position i is not written.  Else
+ *   CLASS LIST at most four entries, each a surface record, a statistics record and a key: first the PRESENT ones of A0, A1 in that
+ *              order, as they are.  Then for B0, then for B1, if PRESENT: if its key equals the key of an entry of the list it is
+ *              merged into the FIRST such entry (PAIR MERGE, the entry as a, the slot as b; the entry keeps its key and its place),
+ *              else it is appended as it is.
+ *   PAIR MERGE statistics: the expressions of acn_lens_stats_merge* above (neither record is EMPTY).  Surface record, with na, nb the
+ *              n of a and b BEFORE the merge and f = nb / ( na + nb ) (the nb / n of the statistics):
+ *                the key is a hit:   [ 0 ], [ 1 .. 3 ], [ 9 .. 11 ], [ 14 ]:  q = q_a + ( q_b - q_a ) * f per component
+ *                                    [ 4 .. 6 ]:  g = N_a + ( N_b - N_a ) * f per component,  q = ( g.x * g.x + g.y * g.y ) + g.z * g.z,
+ *                                                 the normal is q > 0 ? g / acn_sqrt( q ) per component : ( 0, 0, 0 )
+ *                                    [ 7 ], [ 8 ], [ 13 ]:  those of a, bit for bit
+ *                                    [ 12 ]:  ( double )( ( uint32 )a[ 12 ] | ( uint32 )b[ 12 ] )
+ *                the key is a miss:  inf, six zeros, -1, -1, four zeros, [ 13 ] of a bit for bit, [ 14 ] = w_a + ( w_b - w_a ) * f
+ *                [ 15 ] is set last (COVERAGE).
+ *   RANKING    the entries by their n after the merges, descending; among entries of equal n the earlier entry of the list first.
+ *              The first becomes layer 0, the second layer 1.  A layer without an entry is the absent layer of the split (inf, six
+ *              zeros, -1, -1, seven zeros) with a statistics record of eight zeros.
+ *   REST       Ar, then Br, then the statistics of the third entry of the ranking, then of the fourth, folded left to right by
+ *              acn_lens_stats_merge* with its EMPTY rules (the fold so far as a, the next as b).  The surface records of the third and
+ *              fourth entry are dropped.  A rest that is still EMPTY after the fold is eight zeros.
+ *   COVERAGE   n_l = n of a resulting layer, 0 for an absent one, nr = n of the resulting rest, 0 for an EMPTY one;
+ *              K_p = ( n0 + n1 ) + nr;  [ 15 ] of a layer that is not absent = n_l / K_p.
+ *   An entry that no slot was merged into -- a class with a single contributor -- keeps the 15 other doubles of its surface record and
+ *   its whole statistics record bit for bit.
+ * What follows from it:  an accumulator position whose three statistics records are EMPTY (a zero-filled accumulator is a valid
+ * start) becomes the part, bit for bit in all five planes, wherever the part is what the split writes (layer 1 present only with
+ * layer 0 and not larger, EMPTY records all zeros, [ 15 ] = n_l / K).  Where plane 1 and the rest are EMPTY on both sides and the keys
+ * of A0 and B0 agree, statistics plane 0 is acn_lens_stats_merge* bit for bit.  n0 + n1 + nr of the result is exactly the number of
+ * samples behind the six slots (sums of small integers in binary64).  Layers can swap places between passes.  A class demoted to
+ * the rest stays there: the rest has no key, so if the class returns in a later pass it starts a new entry -- a stated limitation;
+ * the rest has no guide and is never filtered.  A merged record is not the record one call with all the samples would write: it
+ * equals it to rounding, and only while no class was demoted.
+ * Index, stream and argument rules are those of acn_lens_stats_merge*: a null index requires n_part <= n_acc; in the _dev form an
+ * index outside [ 0, n_acc ) is skipped -- the lane reads its index first, and nothing else is read or written for it --, duplicate
+ * indices leave the records at those positions, and only those, unspecified, and a caller's stream is never synchronised; the host
+ * form refuses an index that is out of range or comes twice with ACN_ERR_ARG before anything is written.  All five records of a
+ * position are read from both sides before the first is written; a record depends on the six slots of its position alone, not on
+ * which positions share a wavefront or a workgroup.  ACN_ERR_ARG, on the host before any launch, acn_last_error set: a null handle;
+ * a null buffer with entries to hold (n_acc > 0, n_part > 0); shard_world > 1; a plane buffer that is not 16-byte aligned or a
+ * d_index that is not 8-byte aligned; n_acc or n_part above 2^38.  n_part == 0 is ACN_OK with no launch.
+ *
+ * acn_lens_layers_resolve_dev: stats [ 3 ][ n ][ ACN_STATS_STRIDE ] -> the pixel as one population.
+ *   pooled = merge( merge( s0, s1 ), sr ) by acn_lens_stats_merge* with its EMPTY rules; three EMPTY records give eight zeros.
+ *   out_pooled (nullable) [ n ][ ACN_STATS_STRIDE ] = pooled, 16-byte aligned.  out_rgb (nullable) [ n ][ 3 ] and out_noise (nullable) [ n ]
+ *   are acn_lens_stats_resolve_dev of pooled: the mean through cl_s_sat unless ACN_OPT_LINEAR_OUT, the scene's background_color for
+ *   three EMPTY records; noise +inf for them and for n == 1.  The noise plane is what acn_select_above_dev and acn_key_histogram_dev
+ *   take.  Streams, flags and refusals as for acn_lens_stats_resolve_dev; three null outputs are ACN_OK with no launch.
+ * Neither call touches a work queue, counter, learned rate or acn_last_* value. */
 #define ACN_LAYERS_SURFACE_PLANES 2   /* out_surface: layer 0, layer 1 */
 #define ACN_LAYERS_STATS_PLANES   3   /* out_stats: layer 0, layer 1, rest */
 int acn_lens_layers_reduce_dev( acn_scene_handle* h, const void* d_records, const void* d_radiance, size_t n, uint32_t K, void* d_out_surface,
@@ -682,6 +737,12 @@ int acn_denoise_layers_dev( acn_scene_handle* h, const void* d_stats, const void
                             const acn_denoise_params* prm /* nullable: defaults */, void* d_out_rgb, const acn_render_opts* opts );
 int acn_denoise_layers    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
                             const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
+int acn_lens_layers_merge_dev  ( acn_scene_handle* h, void* d_acc_surface, void* d_acc_stats, size_t n_acc, const void* d_part_surface,
+                                 const void* d_part_stats, size_t n_part, const int64_t* d_index /* nullable */, const acn_render_opts* opts );
+int acn_lens_layers_merge      ( acn_scene_handle* h, double* acc_surface, double* acc_stats, size_t n_acc, const double* part_surface,
+                                 const double* part_stats, size_t n_part, const int64_t* index /* nullable */, const acn_render_opts* opts );
+int acn_lens_layers_resolve_dev( acn_scene_handle* h, const void* d_stats, size_t n, void* d_out_rgb /* nullable */,
+                                 void* d_out_noise /* nullable, [ n ] f64 */, void* d_out_pooled /* nullable */, const acn_render_opts* opts );
 
 /* Selecting positions by a key on the device (k_select.hip): the step between acn_lens_stats_resolve_dev, which leaves a noise
  * figure per pixel in d_out_noise, and acn_render_lens_stats_dev / acn_lens_stats_merge_dev, which take an ordered index list and

@@ -2,7 +2,7 @@
 """A frame of an Actinon scene rendered in passes that go where the frame is still noisy (acn_render_lens_stats, acn_lens_stats_*).
 
     python tools/render_progressive.py SCENE OUT.pnm --samples K --passes P --target-noise T [--denoise] [--noise-map FILE]
-                                       [--select torch|library] [--rays-per-pass B] [--guides pinhole|lens] [--min-coverage C]
+                                       [--select torch|library] [--rays-per-pass B] [--guides pinhole|lens] [--min-coverage C] [--layers]
                                        [--aperture A --focus D --width W --height H --path-samples P --direct-samples D]
 
 SCENE is an .acn script (the scene of its first create_image) or a flattened scene .npz, as for tools/render_panorama.py.
@@ -28,7 +28,14 @@ policy lives here, in a tool a caller can read and change, and not in the librar
 tool's --samples, --aperture, --focus, jitter and seed 0), which at a defocused edge or an anti-aliased silhouette names the surface
 most of the pixel's samples met.  --min-coverage C (with lens guides): a pixel whose dominant class holds less than C of its K
 samples gets distance inf in its record before the filter, so it is copied through and is never a tap; a pixel of coverage 0.55
-still carries 45 % of another surface's radiance, and how much of that a frame tolerates is the caller's decision, like the rest."""
+still carries 45 % of another surface's radiance, and how much of that a frame tolerates is the caller's decision, like the rest.
+
+--layers keeps the two largest surfaces of every pixel apart through all passes: a pass is acn_render_lens_layers_dev (FOLLOW records)
+on the selected pixels, merged into the accumulator's five planes by surface class (acn_lens_layers_merge_dev) by the selection's
+index list; the noise that selects is that of the pixel's pooled record (acn_lens_layers_resolve_dev): all its samples as one
+population, which is the noise of the tool without --layers to rounding.  With --denoise the end is acn_denoise_layers_dev, which
+filters each surface of a mixed pixel with its own neighbours; without it the end is the pooled mean.  The guides are the passes' own
+records: --guides and --min-coverage do not apply."""
 import argparse
 import os
 import sys
@@ -60,8 +67,12 @@ def sync(dev):
         torch.cuda.synchronize(dev)
 
 
-def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=print, *, select_mode="torch", rays_per_pass=None, on_pass=None):
+def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=print, *, select_mode="torch", rays_per_pass=None, on_pass=None,
+               layers=False):
     """-> the accumulator [n,8] and the noise [n] as tensors on dev, and the rays of every pass.  h: an actinon_amd.Handle.
+    layers: every pass is a layered call (FOLLOW records), the accumulator is the pair ( surface planes [2,n,16], statistics planes
+    [3,n,8] ), a pass is merged into it by surface class (lens_layers_merge_dev) and the noise is that of the pooled record
+    (lens_layers_resolve_dev); the selection is the same.
     select_mode "library": the pixels of a pass come from h.select_above_dev, not from select and centres.  rays_per_pass B: a pass
     after the first selects above max( target, key_hist_threshold( histogram of the noise, B // samples ) ).
     on_pass( p, threshold, idx, d_noise ): called for every pass after the first with its threshold, the selected indices and the noise
@@ -69,8 +80,15 @@ def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=pr
     import torch
     lens = dict(lens or {})
     n = width * height
-    d_acc = torch.zeros((n, 8), dtype=torch.float64, device=dev)
+    d_acc = torch.zeros((3, n, 8) if layers else (n, 8), dtype=torch.float64, device=dev)
+    d_acc_surf = torch.zeros((2, n, 16), dtype=torch.float64, device=dev) if layers else None
     d_noise = torch.empty((n,), dtype=torch.float64, device=dev)
+
+    def resolve_noise():
+        if layers:
+            h.lens_layers_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), None, linear=True)
+        else:
+            h.lens_stats_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), linear=True)
     budget = None if rays_per_pass is None else int(rays_per_pass) // samples
     if budget is not None:
         import actinon_amd as A
@@ -80,11 +98,14 @@ def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=pr
         d_idx_all = torch.empty((max(room, 1),), dtype=torch.int64, device=dev)
         d_pos_all = torch.empty((max(room, 1), 2), dtype=torch.float64, device=dev)
     sync(dev)
-    h.render_lens_stats_main_pass_dev(0, n, None, d_acc.data_ptr(), linear=True, samples=samples, seed=0, **lens)
+    if layers:
+        h.render_lens_layers_main_pass_dev(0, n, None, d_acc_surf.data_ptr(), d_acc.data_ptr(), follow=True, linear=True, samples=samples, seed=0, **lens)
+    else:
+        h.render_lens_stats_main_pass_dev(0, n, None, d_acc.data_ptr(), linear=True, samples=samples, seed=0, **lens)
     rays = [n * samples]
     log(f"pass 0: {n} pixels, {rays[0]} rays")
     for p in range(1, passes):
-        h.lens_stats_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), linear=True)
+        resolve_noise()
         above = target
         if budget is not None:
             h.key_histogram_dev(d_noise.data_ptr(), n, d_hist.data_ptr())
@@ -103,19 +124,25 @@ def run_passes(h, width, height, samples, passes, target, dev, lens=None, log=pr
             break
         if select_mode != "library":
             d_pos = centres(idx, width)
-        d_part = torch.empty((m, 8), dtype=torch.float64, device=dev)
+        d_part = torch.empty((3, m, 8) if layers else (m, 8), dtype=torch.float64, device=dev)
+        d_part_surf = torch.empty((2, m, 16), dtype=torch.float64, device=dev) if layers else None
         sync(dev)
-        h.render_lens_stats_dev(d_pos.data_ptr(), m, None, d_part.data_ptr(), linear=True, samples=samples, seed=p, **lens)
-        h.lens_stats_merge_dev(d_acc.data_ptr(), n, d_part.data_ptr(), m, idx.data_ptr())
+        if layers:
+            h.render_lens_layers_dev(d_pos.data_ptr(), m, None, d_part_surf.data_ptr(), d_part.data_ptr(), follow=True, linear=True, samples=samples,
+                                     seed=p, **lens)
+            h.lens_layers_merge_dev(d_acc_surf.data_ptr(), d_acc.data_ptr(), n, d_part_surf.data_ptr(), d_part.data_ptr(), m, idx.data_ptr())
+        else:
+            h.render_lens_stats_dev(d_pos.data_ptr(), m, None, d_part.data_ptr(), linear=True, samples=samples, seed=p, **lens)
+            h.lens_stats_merge_dev(d_acc.data_ptr(), n, d_part.data_ptr(), m, idx.data_ptr())
         rays.append(m * samples)
         log(f"pass {p}: {m} pixels, {rays[-1]} rays")
-    h.lens_stats_resolve_dev(d_acc.data_ptr(), n, None, d_noise.data_ptr(), linear=True)
-    return d_acc, d_noise, rays
+    resolve_noise()
+    return ((d_acc_surf, d_acc) if layers else d_acc), d_noise, rays
 
 
 def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0, log=print, *, select_mode="torch", rays_per_pass=None,
-           on_pass=None, guides="pinhole", min_coverage=0.0):
-    """-> the frame [H,W,3] uint8, the records [n,8], the noise [H,W] and the rays of every pass"""
+           on_pass=None, guides="pinhole", min_coverage=0.0, layers=False):
+    """-> the frame [H,W,3] uint8, the records [n,8] (layers: the statistics planes [3,n,8]), the noise [H,W] and the rays of every pass"""
     import torch
     import actinon_amd as A
     w, hh = int(flat.params.image_width), int(flat.params.image_height)
@@ -123,11 +150,17 @@ def render(flat, samples, passes, target, denoise=False, aperture=0.0, focus=0.0
     h = A.Handle(flat)
     dev = torch.device("cuda", h.device)
     d_acc, d_noise, rays = run_passes(h, w, hh, samples, passes, target, dev, lens=dict(jitter=True, aperture=aperture, focus=focus), log=log,
-                                     select_mode=select_mode, rays_per_pass=rays_per_pass, on_pass=on_pass)
+                                     select_mode=select_mode, rays_per_pass=rays_per_pass, on_pass=on_pass, layers=layers)
+    if layers:
+        d_surf, d_acc = d_acc
     d_lin = torch.empty((n, 3), dtype=torch.float64, device=dev)
     d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
     sync(dev)
-    if denoise:
+    if layers and denoise:
+        h.denoise_layers_dev(d_acc.data_ptr(), d_surf.data_ptr(), w, hh, d_lin.data_ptr())
+    elif layers:
+        h.lens_layers_resolve_dev(d_acc.data_ptr(), n, d_lin.data_ptr(), None, None, linear=True)
+    elif denoise:
         d_surf = torch.empty((n, A.abi.ACN_SURF_STRIDE), dtype=torch.float64, device=dev)
         if guides == "lens":
             sync(dev)
@@ -165,6 +198,8 @@ def parse_args(argv=None):
                     help="the surface records that guide --denoise: of the pixel centres, or the aggregate of the K lens rays (acn_surface_lens)")
     ap.add_argument("--min-coverage", type=float, default=0.0, metavar="C",
                     help="with lens guides: a pixel whose coverage is below C is copied through the filter and is never a tap")
+    ap.add_argument("--layers", action="store_true",
+                    help="layered passes: the two largest surfaces of a pixel kept apart, merged by class, filtered by acn_denoise_layers")
     ap.add_argument("--aperture", type=float, default=0.0, help="lens radius in scene units (default 0: a pinhole with jitter)")
     ap.add_argument("--focus", type=float, default=0.0, help="distance of the plane in focus, for an open aperture")
     ap.add_argument("--width", type=int, default=None)
@@ -182,6 +217,8 @@ def parse_args(argv=None):
         ap.error("--rays-per-pass is not negative")
     if not 0 <= args.min_coverage <= 1:
         ap.error("--min-coverage is 0 .. 1")
+    if args.layers and (args.guides != "pinhole" or args.min_coverage > 0):
+        ap.error("--layers takes its guides from the passes themselves: --guides and --min-coverage do not apply")
     if args.aperture < 0 or (args.aperture > 0 and not args.focus > 0):
         ap.error("the aperture is not negative and the focus distance of an open aperture is positive")
     for value in (args.width, args.height, args.path_samples, args.direct_samples):
@@ -203,7 +240,7 @@ def main(argv=None):
         sys.exit("the image needs a width of at least 1 and a height of at least 2")
     out8, records, noise, rays = render(flat, args.samples, args.passes, args.target_noise, denoise=args.denoise,
                                         aperture=args.aperture, focus=args.focus, select_mode=args.select, rays_per_pass=args.rays_per_pass,
-                                        guides=args.guides, min_coverage=args.min_coverage)
+                                        guides=args.guides, min_coverage=args.min_coverage, layers=args.layers)
     write_pnm(args.out, np.ascontiguousarray(out8))
     if args.noise_map:
         with open(args.noise_map, "wb") as f:
