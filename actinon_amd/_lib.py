@@ -22,7 +22,8 @@ hip = _load("libactinon_hip.so")
 host = _load("libactinon_host.so")
 
 # symbols declared by include/actinon_hip.h
-HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_render_positions",
+HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_scene_replace", "acn_scene_set_params", "acn_scene_info",
+               "acn_render_positions",
                "acn_render_positions_dev", "acn_render_main_pass_dev", "acn_resolve_dev", "acn_last_kernel_ms", "acn_last_stage_ms", "acn_last_counters",
                "acn_estimate_envelope", "acn_detmath_eval", "acn_last_error", "acn_shard_tile_count", "acn_shard_tile_padded",
                "acn_shard_tile_index", "acn_render_main_pass_shard_dev", "acn_shard_unpack_dev", "acn_query_rays",
@@ -56,7 +57,7 @@ HOST_SYMBOLS = ["acn_rotx", "acn_roty", "acn_rotz", "acn_obj_plane_s_create", "a
                 "acn_compound_s_clear", "acn_compound_s_set_sphere_envelopes", "acn_scene_s_create",
                 "acn_scene_s_discard", "acn_scene_s_clear", "acn_scene_s_push", "acn_scene_s_objects",
                 "acn_scene_s_flatten", "acn_flat_scene_free", "acn_obj_flatten", "acn_lum_machine_s_run",
-                "acn_scene_s_create_image_file", "acn_write_pnm", "acn_cps_from_cl", "acn_scene_primitives",
+                "acn_scene_s_create_image_file", "acn_scene_s_create_image_file_keep", "acn_write_pnm", "acn_cps_from_cl", "acn_scene_primitives",
                 "acn_scene_wine_glass", "acn_scene_diamond", "acn_scene_many_spheres", "acn_obj_get_pos",
                 "acn_obj_sphere_s_get_radius", "acn_obj_get_field", "acn_obj_set_field", "acn_set_envelope_estimator"]
 # symbols declared by include/acn_interp.h
@@ -70,6 +71,9 @@ hip.acn_device_count.restype = C.c_int
 hip.acn_scene_upload.argtypes = [P(abi.FlatScene), C.c_int, P(vp)]
 hip.acn_scene_free.argtypes = [vp]
 hip.acn_scene_free.restype = None
+hip.acn_scene_replace.argtypes = [vp, P(abi.FlatScene), C.c_uint32]
+hip.acn_scene_set_params.argtypes = [vp, P(abi.Params)]
+hip.acn_scene_info.argtypes = [vp, P(C.c_uint64), C.c_int]
 hip.acn_render_positions.argtypes = [vp, vp, C.c_size_t, vp, P(abi.RenderOpts)]
 hip.acn_render_positions_dev.argtypes = [vp, vp, C.c_size_t, vp, P(abi.RenderOpts)]
 hip.acn_render_main_pass_dev.argtypes = [vp, C.c_size_t, C.c_size_t, vp, P(abi.RenderOpts)]
@@ -250,6 +254,7 @@ host.acn_flat_scene_free.restype = None
 host.acn_obj_flatten.argtypes = [vp, P(abi.FlatScene), P(C.c_int32)]
 host.acn_lum_machine_s_run.argtypes = [vp, vp, C.c_size_t]
 host.acn_scene_s_create_image_file.argtypes = [vp, C.c_char_p]
+host.acn_scene_s_create_image_file_keep.argtypes = [vp, C.c_char_p, P(vp)]
 host.acn_write_pnm.argtypes = [C.c_char_p, vp, C.c_size_t, C.c_size_t]
 host.acn_cps_from_cl.argtypes = [P(C.c_double)]
 host.acn_cps_from_cl.restype = C.c_uint32

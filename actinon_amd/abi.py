@@ -35,6 +35,10 @@ ACN_LAYERS_SURFACE_PLANES, ACN_LAYERS_STATS_PLANES = 2, 3
 # selecting positions by a key (acn_select_above, acn_key_histogram): bins of the histogram, its words (the last counts NaN keys)
 ACN_KEY_HIST_BINS, ACN_KEY_HIST_WORDS = 256, 257
 
+# replacing the scene of a live handle (acn_scene_replace, acn_scene_info): the flag, the slots of the counters
+ACN_REPLACE_FORGET = 1
+ACN_INFO_N = 8
+
 ACN_OK, ACN_ERR_ARG, ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV, ACN_ERR_DEVICE, ACN_ERR_CANCELLED = 0, -1, -2, -3, -4, -5
 
 NODE_TYPES = {1: "plane", 2: "sphere", 3: "squaroid", 4: "distance", 5: "pair_inside", 6: "pair_outside",

@@ -32,3 +32,22 @@ def panorama_rays(origin, view, top, width, height):
     rays[:, :3] = np.asarray(origin, dtype=np.float64).reshape(3)
     rays[:, 3:] = d
     return rays
+
+
+def orbit_camera(params, degrees, target_distance=None):
+    """The scene's pinhole camera moved on a circle around its view target, for Handle.set_params: `params` is an abi.Params (or
+    anything with camera_position, camera_view_direction, camera_top_direction), the target the point target_distance along the view
+    direction (None: the length of camera_view_direction, which is how the shipped scenes state what they look at), the axis the top
+    direction through the target.  Returns dict( camera_position=..., camera_view_direction=... ); the top direction and the length of
+    the view direction stay."""
+    pos = np.array([params.camera_position[i] for i in range(3)], dtype=np.float64)
+    view = np.array([params.camera_view_direction[i] for i in range(3)], dtype=np.float64)
+    axis = _unit([params.camera_top_direction[i] for i in range(3)])
+    target = pos + (view if target_distance is None else _unit(view) * float(target_distance))
+    a = np.deg2rad(float(degrees))
+
+    def turn(v):                                   # Rodrigues' rotation about `axis`
+        return v * np.cos(a) + np.cross(axis, v) * np.sin(a) + axis * (axis @ v) * (1.0 - np.cos(a))
+
+    return dict(camera_position=tuple(float(x) for x in target + turn(pos - target)),
+                camera_view_direction=tuple(float(x) for x in turn(view)))

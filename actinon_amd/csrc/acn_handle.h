@@ -283,6 +283,7 @@ struct PipeRun
     size_t budget_div = 1;                     /* workspace budget of a lane = the handle's budget / lanes */
     Switches sw;                               /* of the current call */
     Learned learned;
+    uint64_t learn_passes = 0;                 /* learning passes this runner has run (learn_rates); acn_scene_info sums them */
     RunStats stats;                            /* of the last call */
     /* of a lane */
     std::unique_ptr< LaneWorker > worker;
@@ -313,13 +314,15 @@ struct acn_scene_handle
     } scene;
     DevBuf< SCEntry > d_sc_table;
     DevBuf< double > d_sc_spheres;             /* ( pos, radius ) of the sphere leaves of d_sc_table */
+    acn_scene_kind kind{};                     /* of the resident scene: what decides whether a change of scene keeps the learned rates */
+    uint64_t replaces = 0, param_sets = 0;     /* acn_scene_replace / acn_scene_set_params calls accepted since the upload */
     Tunables tun;
     unsigned cus = 256;                        /* compute units of the device */
     size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
     PipeRun run;                               /* a call that runs alone; its stream is the handle's own, its statistics the last call's */
     /* concurrent lanes (render_lanes): runners that own a stream, a workspace and a host thread each */
     std::vector< std::unique_ptr< PipeRun > > lanes;
-    /* lanes made during acn_scene_upload on a helper thread (early_lanes_begin), taken over by the first call that runs on lanes */
+    /* lanes made during acn_scene_upload on a helper thread (early_lanes_begin), taken over before the upload returns (quiesce) */
     std::thread early_maker;
     std::vector< std::unique_ptr< PipeRun > > early_made;
     bool timed = false;

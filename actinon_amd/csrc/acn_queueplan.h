@@ -205,6 +205,29 @@ static inline void acn_sample_rates( const uint32_t* counts, int levels, uint32_
     for( int q = 0; q < WQ_N; q++ ) rate[ q ] = acn_plan_max( 1.2 * live[ q ] / ( double )cnt + dead[ q ] / pp, 1e-3 );
 }
 
+/* ---- a change of scene on a live handle (acn_scene_replace, acn_scene_set_params) ---- */
+/* What the learned rates depend on.  They are records per POSITION, so the raster size is no part of it, nor is the camera: a frame
+ * of the same kind from another angle leaves about the same records per position, and rates that are off cost a redone chunk, never
+ * a pixel (a chunk that overflows is rendered again, bit-identically). */
+typedef struct
+{
+    uint32_t n_nodes, n_elems;
+    uint64_t n_lights;
+    int32_t  n_levels, prune;
+    uint64_t path_samples, direct_samples, trace_depth;
+    double   trace_min_intensity;
+} acn_scene_kind;
+/* 1: the runners keep what they learned (rates, fill target, walk passes) across the change: iff every member is equal, the double by
+ * its bit pattern (-0.0 is not 0.0: no rule about values, only "nothing changed") */
+static inline int acn_replace_keeps_learned( const acn_scene_kind* was, const acn_scene_kind* now )
+{
+    uint64_t a, b;
+    memcpy( &a, &was->trace_min_intensity, sizeof( a ) ); memcpy( &b, &now->trace_min_intensity, sizeof( b ) );
+    return was->n_nodes == now->n_nodes && was->n_elems == now->n_elems && was->n_lights == now->n_lights && was->n_levels == now->n_levels &&
+           was->prune == now->prune && was->path_samples == now->path_samples && was->direct_samples == now->direct_samples &&
+           was->trace_depth == now->trace_depth && a == b;
+}
+
 /* ---- walk passes ---- */
 /* launches of k_walk for path level `level`: ACN_WALK_PASSES (tun_passes), but no more than the hits of the level have depth left.
  * The chunks of a call see the same mix of pixels (TileOrder), so the passes that had input in the last chunk (seen; 0: not

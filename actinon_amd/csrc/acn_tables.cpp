@@ -62,6 +62,23 @@ static int compound_depth( const acn_flat_scene* sc, int node, int d, int* max_c
     return m;
 }
 
+/* the checks that read the render parameters alone (acn_scene_set_params runs these and nothing else) */
+int acn_tables_validate_params( const acn_params* prm, std::string* err )
+{
+    auto fail = [ & ]( int code, const char* msg ) { *err = msg; return code; };
+    if( prm->experimental_level != 0 ) return fail( ACN_ERR_UNSUPPORTED, "Unsupported experimental level" );   /* scene.c:1004-1007 */
+    if( prm->image_height < 2 || prm->image_width < 1 ) return fail( ACN_ERR_ARG, "image size" );
+    if( prm->trace_depth > 10 * ACN_MAX_PATH_LEVELS + 10 ) return fail( ACN_ERR_UNSUPPORTED, "trace_depth exceeds device path-level limit" );
+    return ACN_OK;
+}
+
+/* path levels: level L shades hits at depth trace_depth - 10 L and spawns the next one while that is > 10 (scene.c:584) */
+int acn_tables_levels( const acn_params* prm )
+{
+    const uint64_t td = prm->trace_depth;
+    return prm->path_samples && td > 10 ? 1 + ( int )( ( td - 10 + 9 ) / 10 ) : 1;
+}
+
 int acn_tables_validate( const acn_flat_scene* sc, int* max_csg, std::string* err )
 {
     auto fail = [ & ]( int code, const char* msg ) { *err = msg; return code; };
@@ -70,9 +87,7 @@ int acn_tables_validate( const acn_flat_scene* sc, int* max_csg, std::string* er
     if( sc->n_nodes == 0 || sc->light_root < 0 || sc->matter_root < 0 || ( uint32_t )sc->light_root >= sc->n_nodes ||
         ( uint32_t )sc->matter_root >= sc->n_nodes ) return fail( ACN_ERR_ARG, "bad root index" );
     if( sc->n_elems && !sc->elems ) return fail( ACN_ERR_ARG, "null elems" );
-    if( sc->params.experimental_level != 0 ) return fail( ACN_ERR_UNSUPPORTED, "Unsupported experimental level" );   /* scene.c:1004-1007 */
-    if( sc->params.image_height < 2 || sc->params.image_width < 1 ) return fail( ACN_ERR_ARG, "image size" );
-    if( sc->params.trace_depth > 10 * ACN_MAX_PATH_LEVELS + 10 ) return fail( ACN_ERR_UNSUPPORTED, "trace_depth exceeds device path-level limit" );
+    if( const int st = acn_tables_validate_params( &sc->params, err ) ) return st;
     for( uint32_t i = 0; i < sc->n_nodes; i++ )
     {
         const acn_node* n = &sc->nodes[ i ];
@@ -460,9 +475,7 @@ static void build_simple_compounds( const acn_flat_scene* scene, const acn_table
 /* what the render path asks about the light root and the path depth */
 static void light_facts( const acn_flat_scene* scene, acn_scene_tables& t )
 {
-    /* path levels: level L shades hits at depth trace_depth - 10 L and spawns the next one while that is > 10 (scene.c:584) */
-    uint64_t td = scene->params.trace_depth;
-    t.n_levels = scene->params.path_samples && td > 10 ? 1 + ( int )( ( td - 10 + 9 ) / 10 ) : 1;
+    t.n_levels = acn_tables_levels( &scene->params );
     const acn_node& lr = scene->nodes[ scene->light_root ];
     t.n_lights = lr.child1 > 0 ? ( size_t )lr.child1 : 1;
     for( int k = 0; k < lr.child1; k++ )

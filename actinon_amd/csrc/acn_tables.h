@@ -125,6 +125,10 @@ struct acn_scene_tables
 
 /* what the reference would abort on, plus the device limits: ACN_OK, or the code with its text in *err */
 int acn_tables_validate( const acn_flat_scene* sc, int* max_csg, std::string* err );
+/* the part of it that reads the render parameters alone, and the path levels of parameters it accepted: all that
+ * acn_scene_set_params needs of this unit */
+int acn_tables_validate_params( const acn_params* prm, std::string* err );
+int acn_tables_levels( const acn_params* prm );
 /* the tables of a scene that acn_tables_validate accepted */
 void acn_tables_build( const acn_flat_scene* sc, const acn_table_opts& opts, acn_scene_tables* out );
 

@@ -94,7 +94,8 @@ static hipError_t run_objects( PipeRun* r, bool on_stream, Mark mark )
  * thread beside the upload's host work and copies, while nothing of this handle runs on the device (ACN_EARLY_LANES=1; off by
  * default: the runtime makes streams one after the other, so the time only moves from the first call into the upload).  A handle that would render its
  * raster on one lane (small rasters, path_samples >= 256 on a cold handle: render_positions) makes none.  Failures are not reported
- * from here: the first call that needs the lanes makes what is missing and reports its own. */
+ * from here: the first call that needs the lanes makes what is missing and reports its own.  The thread is joined and its lanes
+ * become the handle's before the upload's first kernel (quiesce). */
 static void early_lanes_begin( acn_scene_handle* h, size_t n, uint64_t path_samples )
 {
     const int lanes = acn_lanes_for_counts( h->tun.lanes, n, path_samples );
@@ -111,6 +112,150 @@ static void early_lanes_begin( acn_scene_handle* h, size_t n, uint64_t path_samp
     } );
 }
 static void early_lanes_join( acn_scene_handle* h ) { if( h->early_maker.joinable() ) h->early_maker.join(); }
+
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* The resident scene: made by acn_scene_upload, changed by acn_scene_replace and acn_scene_set_params through the same steps.  What
+ * can refuse a change -- the checks, the device blocks of the new scene, the camera kernel -- comes BEFORE the handle is touched: a
+ * change that fails leaves the handle rendering what it rendered. */
+static void bind_lane( const acn_scene_handle* h, int lanes, PipeRun* l );
+
+/* the device blocks of a scene, fresh ones: the handle's own stay valid until they are exchanged */
+struct StagedScene
+{
+    acn_scene_handle::Resident scene;
+    DevBuf< SCEntry > d_sc_table;
+    DevBuf< double > d_sc_spheres;
+};
+static int stage_scene( const acn_flat_scene* scene, int max_csg, const acn_scene_tables& t, StagedScene* s )
+{
+    acn_scene_handle::Resident& r = s->scene;
+    r.max_csg_depth = max_csg;
+    r.lds_bytes = t.lds_bytes; r.lds_stack_bytes = t.lds_stack_bytes;
+    r.prune = t.prune; r.leaf_lights = t.leaf_lights; r.elem_pos_base = t.elem_pos_base;
+    r.n_levels = t.n_levels; r.n_lights = t.n_lights;
+    const size_t n_tex = scene->n_textures ? scene->n_textures : 1, n_sc = t.sc_table.size() ? t.sc_table.size() : 1, n_sph = t.sc_spheres.size() ? t.sc_spheres.size() : 4;
+    if( r.d_nodes.grow( sizeof( GNode ) * t.nodes.size() ) || r.d_mats.grow( sizeof( GMat ) * t.mats.size() ) || r.d_elems.grow( sizeof( int32_t ) * t.elems.size() ) ) return ACN_ERR_DEVICE;
+    if( s->d_sc_table.grow( sizeof( SCEntry ) * n_sc ) ) return ACN_ERR_DEVICE;
+    if( t.sc_table.size() ) HIP_TRY( hipMemcpy( s->d_sc_table.get(), t.sc_table.data(), sizeof( SCEntry ) * t.sc_table.size(), hipMemcpyHostToDevice ) );
+    if( s->d_sc_spheres.grow( sizeof( double ) * n_sph ) ) return ACN_ERR_DEVICE;
+    if( t.sc_spheres.size() ) HIP_TRY( hipMemcpy( s->d_sc_spheres.get(), t.sc_spheres.data(), sizeof( double ) * t.sc_spheres.size(), hipMemcpyHostToDevice ) );
+    if( r.d_textures.grow( sizeof( acn_texture ) * n_tex ) ) return ACN_ERR_DEVICE;
+    if( scene->n_textures ) HIP_TRY( hipMemcpy( r.d_textures.get(), scene->textures, sizeof( acn_texture ) * scene->n_textures, hipMemcpyHostToDevice ) );
+    HIP_TRY( hipMemcpy( r.d_nodes.get(), t.nodes.data(), r.d_nodes.bytes(), hipMemcpyHostToDevice ) );
+    HIP_TRY( hipMemcpy( r.d_mats.get(), t.mats.data(), r.d_mats.bytes(), hipMemcpyHostToDevice ) );
+    HIP_TRY( hipMemcpy( r.d_elems.get(), t.elems.data(), r.d_elems.bytes(), hipMemcpyHostToDevice ) );
+    return ACN_OK;
+}
+
+/* Nothing of the handle runs: the helper thread of the upload is joined and the lanes it made are the handle's (budget_div: set by the
+ * call that runs on them), the handle's own stream and every lane's are idle.  What callers queued on streams of their own is
+ * theirs to wait for (include/actinon_hip.h). */
+static int quiesce( acn_scene_handle* h )
+{
+    early_lanes_join( h );
+    for( auto& l : h->early_made ) { bind_lane( h, 1, l.get() ); h->lanes.push_back( std::move( l ) ); }
+    h->early_made.clear();
+    HIP_TRY( hipStreamSynchronize( h->run.stream.get() ) );
+    for( auto& l : h->lanes ) HIP_TRY( hipStreamSynchronize( l->stream.get() ) );
+    return ACN_OK;
+}
+
+/* camera basis on the device so that it shares the device's arithmetic (the kernel reads the parameters alone) */
+static int camera_basis( acn_scene_handle* h, const acn_params& prm, M3* rot, double* unit_f )
+{
+    DevBuf< M3 > d_rot; DevBuf< double > d_uf;
+    if( d_rot.grow( sizeof( M3 ) ) || d_uf.grow( sizeof( double ) ) ) return ACN_ERR_DEVICE;
+    DevScene sc = h->dev;
+    sc.prm = prm;
+    hipLaunchKernelGGL( k_camera_setup, dim3( 1 ), dim3( 1 ), 0, h->run.stream.get(), sc, d_rot.get(), d_uf.get() );
+    HIP_TRY( hipGetLastError() );
+    HIP_TRY( hipStreamSynchronize( h->run.stream.get() ) );
+    HIP_TRY( hipMemcpy( rot, d_rot.get(), sizeof( M3 ), hipMemcpyDeviceToHost ) );
+    HIP_TRY( hipMemcpy( unit_f, d_uf.get(), sizeof( double ), hipMemcpyDeviceToHost ) );
+    return ACN_OK;
+}
+
+static void commit_params( acn_scene_handle* h, const acn_params& prm, int n_levels, const M3& rot, double unit_f )
+{
+    h->dev.prm = prm;
+    h->dev.camera_rotation = rot; h->dev.unit_f = unit_f;
+    h->scene.n_levels = n_levels;
+}
+
+/* a runner's copy of the handle's DevScene; the flags word stays the runner's own */
+static void refresh_run( const acn_scene_handle* h, PipeRun* r )
+{
+    r->dev = h->dev;
+    r->dev.flags = r->d_counts.get() + QC_FLAGS;
+}
+
+/* After h->dev and h->scene have changed: every runner sees the new scene, the statistics of the last call are gone, and what the
+ * runners learned stays iff the scene is of the kind it was (acn_replace_keeps_learned) and the caller does not ask to forget.  Else the
+ * next call learns as a cold handle does, on the lanes and the queues that exist (capacities without rates: ensure_workspace keeps
+ * queues that hold the starter set, and the trim window of acn_keep_caps opens again with the new rates). */
+static void settle( acn_scene_handle* h, bool forget )
+{
+    acn_scene_kind now;
+    now.n_nodes = h->dev.n_nodes; now.n_elems = h->dev.n_elems; now.n_lights = h->scene.n_lights;
+    now.n_levels = h->scene.n_levels; now.prune = h->scene.prune ? 1 : 0;
+    now.path_samples = h->dev.prm.path_samples; now.direct_samples = h->dev.prm.direct_samples; now.trace_depth = h->dev.prm.trace_depth;
+    now.trace_min_intensity = h->dev.prm.trace_min_intensity;
+    const bool keep = !forget && acn_replace_keeps_learned( &h->kind, &now );
+    h->kind = now;
+    auto each = [ & ]( PipeRun* r )
+    {
+        refresh_run( h, r );
+        r->stats.reset();
+        if( !keep ) { r->learned = Learned(); r->ws.trimmed = false; r->ws.sized_calls = 0; }
+    };
+    each( &h->run );
+    for( auto& l : h->lanes ) each( l.get() );
+    h->timed = false; h->used_lanes = false; h->lanes_used = 0; h->one_lane = false;
+}
+
+/* `scene`, which acn_tables_validate accepted, becomes the resident scene of h.  mark( i ): the tables are built (0), the device blocks
+ * are staged (1), nothing of the handle runs (2). */
+template< class Mark >
+static int install_scene( acn_scene_handle* h, const acn_flat_scene* scene, int max_csg, bool forget, Mark mark )
+{
+    acn_scene_tables t;   /* everything the traversal shortcuts read, built on the host alone (acn_tables.cpp) */
+    acn_tables_build( scene, h->tun.tables, &t );
+    mark( 0 );
+    StagedScene s;
+    int st = stage_scene( scene, max_csg, t, &s );
+    if( st != ACN_OK ) return st;
+    mark( 1 );
+    if( ( st = quiesce( h ) ) != ACN_OK ) return st;   /* before the first kernel: nothing of this handle runs while hardware queues are being made */
+    mark( 2 );
+    M3 rot; double unit_f = 0;
+    if( ( st = camera_basis( h, scene->params, &rot, &unit_f ) ) != ACN_OK ) return st;
+    /* from here on nothing fails.  The blocks of the scene before go back to the device as these are moved in. */
+    h->scene = std::move( s.scene );
+    h->d_sc_table = std::move( s.d_sc_table );
+    h->d_sc_spheres = std::move( s.d_sc_spheres );
+    const acn_scene_handle::Resident& r = h->scene;
+    h->dev.nodes = ( NodeP )r.d_nodes.get(); h->dev.gnodes = ( NodeP )r.d_nodes.get();
+    h->dev.mats = ( MatP )r.d_mats.get();
+    h->dev.elems = ( ElemP )r.d_elems.get();
+    h->dev.textures = ( TexP )r.d_textures.get();
+    h->dev.sc_table = h->d_sc_table.get();
+    h->dev.sc_spheres = h->d_sc_spheres.get();
+    h->dev.prune_base = t.prune_base;
+    h->dev.light_root = scene->light_root;
+    h->dev.matter_root = scene->matter_root;
+    h->dev.n_nodes = scene->n_nodes;
+    h->dev.n_elems = scene->n_elems;
+    h->dev.lds_stack = r.lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
+    /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
+     * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
+     * and divergent (nested compounds, CSG objects with prune programs: the scenes of the "extras" kernel variants).
+     * Measured, 4 lanes: wine_glass 1080p (200 / 64 samples) 79.8 ms narrow, 85.2 wide from 33 samples; many_spheres
+     * 1080p p256 every 16th pixel 3.94 s narrow, 2.90 s wide; diamond 1080p p512 4.58 s narrow, 4.05 s wide. */
+    h->dev.class0_min = h->tun.class0_min ? h->tun.class0_min : ( r.prune ? 32u : 255u );
+    commit_params( h, scene->params, t.n_levels, rot, unit_f );
+    settle( h, forget );
+    return ACN_OK;
+}
 
 extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_scene_handle** out )
 {
@@ -133,7 +278,7 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     h->device = device;
     h->tun.read();
     if( h->tun.early_lanes ) early_lanes_begin( h.get(), ( size_t )scene->params.image_width * ( size_t )scene->params.image_height, scene->params.path_samples );
-    double t_events = 0, t_up[ 4 ] = { 0, 0, 0, 0 };   /* ACN_DEBUG_CHUNKS: stream + events, host-side tables, device copies, the camera kernel */
+    double t_events = 0, t_objects = 0, t_in[ 3 ] = { 0, 0, 0 };   /* ACN_DEBUG_CHUNKS: stream + events; the marks of install_scene: host-side tables, device copies, the helper thread */
     {
         /* Workspace BOUND of the handle: ACN_WORKSPACE_MB, or 64 GiB / a quarter of the free device memory (288 GB per
          * MI355X).  It is a bound, not an allocation: the queues are sized from measured demand (ensure_workspace) and take
@@ -164,64 +309,72 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     /* (a stream costs ~10 ms of host time to make: the second one only where it is used) */
     const hipError_t made = run_objects( own, false, [ & ]( int i ) { if( i == 0 ) t_events = since(); } );
     if( made != hipSuccess ) return fail( ACN_ERR_DEVICE, std::string( "events and counter blocks of the handle's run: " ) + hipGetErrorString( made ) );
-    t_up[ 0 ] = since();   /* (the counter blocks, made between t_events and here, are counted with the device copies below) */
-    acn_scene_tables t;   /* everything the traversal shortcuts read, built on the host alone (acn_tables.cpp) */
-    acn_tables_build( scene, h->tun.tables, &t );
-    t_up[ 1 ] = since();
-    acn_scene_handle::Resident& r = h->scene;
-    r.max_csg_depth = max_csg;
-    r.lds_bytes = t.lds_bytes; r.lds_stack_bytes = t.lds_stack_bytes;
-    r.prune = t.prune; r.leaf_lights = t.leaf_lights; r.elem_pos_base = t.elem_pos_base;
-    r.n_levels = t.n_levels; r.n_lights = t.n_lights;
-    const size_t n_tex = scene->n_textures ? scene->n_textures : 1, n_sc = t.sc_table.size() ? t.sc_table.size() : 1, n_sph = t.sc_spheres.size() ? t.sc_spheres.size() : 4;
-    if( r.d_nodes.grow( sizeof( GNode ) * t.nodes.size() ) || r.d_mats.grow( sizeof( GMat ) * t.mats.size() ) || r.d_elems.grow( sizeof( int32_t ) * t.elems.size() ) ) return ACN_ERR_DEVICE;
-    if( h->d_sc_table.grow( sizeof( SCEntry ) * n_sc ) ) return ACN_ERR_DEVICE;
-    if( t.sc_table.size() ) HIP_TRY( hipMemcpy( h->d_sc_table.get(), t.sc_table.data(), sizeof( SCEntry ) * t.sc_table.size(), hipMemcpyHostToDevice ) );
-    if( h->d_sc_spheres.grow( sizeof( double ) * n_sph ) ) return ACN_ERR_DEVICE;
-    if( t.sc_spheres.size() ) HIP_TRY( hipMemcpy( h->d_sc_spheres.get(), t.sc_spheres.data(), sizeof( double ) * t.sc_spheres.size(), hipMemcpyHostToDevice ) );
-    if( r.d_textures.grow( sizeof( acn_texture ) * n_tex ) ) return ACN_ERR_DEVICE;
-    if( scene->n_textures ) HIP_TRY( hipMemcpy( r.d_textures.get(), scene->textures, sizeof( acn_texture ) * scene->n_textures, hipMemcpyHostToDevice ) );
-    HIP_TRY( hipMemcpy( r.d_nodes.get(), t.nodes.data(), r.d_nodes.bytes(), hipMemcpyHostToDevice ) );
-    HIP_TRY( hipMemcpy( r.d_mats.get(), t.mats.data(), r.d_mats.bytes(), hipMemcpyHostToDevice ) );
-    HIP_TRY( hipMemcpy( r.d_elems.get(), t.elems.data(), r.d_elems.bytes(), hipMemcpyHostToDevice ) );
-    h->dev.nodes = ( NodeP )r.d_nodes.get(); h->dev.gnodes = ( NodeP )r.d_nodes.get();
-    h->dev.mats = ( MatP )r.d_mats.get();
-    h->dev.elems = ( ElemP )r.d_elems.get();
-    h->dev.textures = ( TexP )r.d_textures.get();
-    h->dev.sc_table = h->d_sc_table.get();
-    h->dev.sc_spheres = h->d_sc_spheres.get();
-    h->dev.prune_base = t.prune_base;
-    h->dev.light_root = scene->light_root;
-    h->dev.matter_root = scene->matter_root;
-    h->dev.n_nodes = scene->n_nodes;
-    h->dev.n_elems = scene->n_elems;
-    h->dev.prm = scene->params;
+    t_objects = since();   /* (the counter blocks, made between t_events and here, are counted with the device copies below) */
     h->dev.flags = own->d_counts.get() + QC_FLAGS;
-    h->dev.lds_stack = r.lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
-    /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
-     * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
-     * and divergent (nested compounds, CSG objects with prune programs: the scenes of the "extras" kernel variants).
-     * Measured, 4 lanes: wine_glass 1080p (200 / 64 samples) 79.8 ms narrow, 85.2 wide from 33 samples; many_spheres
-     * 1080p p256 every 16th pixel 3.94 s narrow, 2.90 s wide; diamond 1080p p512 4.58 s narrow, 4.05 s wide. */
-    h->dev.class0_min = h->tun.class0_min ? h->tun.class0_min : ( r.prune ? 32u : 255u );
-    /* camera basis on the device so that it shares the device's arithmetic */
-    {
-        DevBuf< M3 > d_rot; DevBuf< double > d_uf;
-        if( d_rot.grow( sizeof( M3 ) ) || d_uf.grow( sizeof( double ) ) ) return ACN_ERR_DEVICE;
-        t_up[ 2 ] = since();
-        early_lanes_join( h.get() );   /* before the first kernel: nothing of this handle runs while hardware queues are being made */
-        t_up[ 3 ] = since();
-        hipLaunchKernelGGL( k_camera_setup, dim3( 1 ), dim3( 1 ), 0, own->stream.get(), h->dev, d_rot.get(), d_uf.get() );
-        HIP_TRY( hipGetLastError() );
-        HIP_TRY( hipStreamSynchronize( own->stream.get() ) );
-        HIP_TRY( hipMemcpy( &h->dev.camera_rotation, d_rot.get(), sizeof( M3 ), hipMemcpyDeviceToHost ) );
-        HIP_TRY( hipMemcpy( &h->dev.unit_f, d_uf.get(), sizeof( double ), hipMemcpyDeviceToHost ) );
-    }
-    own->dev = h->dev;
+    st = install_scene( h.get(), scene, max_csg, false, [ & ]( int i ) { t_in[ i ] = since(); } );
+    if( st != ACN_OK ) return st;
     if( h->tun.debug_chunks )
         fprintf( stderr, "[acn upload] %u nodes: the handle's stream %.2f ms, events %.2f, tables on the host %.2f, device copies %.2f, waited for %d early lanes %.2f, first kernel of the library (camera set-up) %.2f\n",
-                 ( unsigned )scene->n_nodes, t_stream1 - t_stream0, t_events - t_stream1 + t_stream0, t_up[ 1 ] - t_up[ 0 ], t_up[ 2 ] - t_up[ 1 ] + t_up[ 0 ] - t_events, ( int )h->early_made.size(), t_up[ 3 ] - t_up[ 2 ], since() - t_up[ 3 ] );
+                 ( unsigned )scene->n_nodes, t_stream1 - t_stream0, t_events - t_stream1 + t_stream0, t_in[ 0 ] - t_objects, t_in[ 1 ] - t_in[ 0 ] + t_objects - t_events, ( int )h->lanes.size(), t_in[ 2 ] - t_in[ 1 ], since() - t_in[ 2 ] );
     *out = h.release();
+    return ACN_OK;
+}
+
+/* The scene of a live handle is replaced.  Everything that costs a fresh handle its first frames stays: the streams, the lanes with their
+ * threads, the queues as allocated and -- for a scene of the same kind (acn_replace_keeps_learned) -- what the runners learned. */
+extern "C" int acn_scene_replace( acn_scene_handle* h, const acn_flat_scene* scene, uint32_t flags )
+{
+    if( !h || !scene ) return fail( ACN_ERR_ARG, "null argument" );
+    if( flags & ~ACN_REPLACE_FORGET ) return fail( ACN_ERR_ARG, "unknown flag bits" );
+    int max_csg = 0;
+    std::string err;
+    int st = acn_tables_validate( scene, &max_csg, &err );
+    if( st != ACN_OK ) return fail( st, err );
+    HIP_TRY( hipSetDevice( h->device ) );
+    const auto t_begin = std::chrono::steady_clock::now();
+    double t_in[ 3 ] = { 0, 0, 0 }, t_end = 0;
+    auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
+    const bool known = h->run.learned.known() || ( !h->lanes.empty() && h->lanes[ 0 ]->learned.known() );
+    st = install_scene( h, scene, max_csg, ( flags & ACN_REPLACE_FORGET ) != 0, [ & ]( int i ) { t_in[ i ] = since(); } );
+    if( st != ACN_OK ) return st;
+    t_end = since();
+    h->replaces++;
+    if( h->tun.debug_chunks )
+        fprintf( stderr, "[acn replace] %u nodes: tables on the host %.2f ms, device copies %.2f, streams idle %.2f, camera set-up and commit %.2f; learned rates %s\n",
+                 ( unsigned )scene->n_nodes, t_in[ 0 ], t_in[ 1 ] - t_in[ 0 ], t_in[ 2 ] - t_in[ 1 ], t_end - t_in[ 2 ],
+                 !known ? "not known yet" : h->run.learned.known() || ( !h->lanes.empty() && h->lanes[ 0 ]->learned.known() ) ? "kept" : "dropped" );
+    return ACN_OK;
+}
+
+/* the same change for the render parameters alone: no table is built, nothing is allocated for the scene */
+extern "C" int acn_scene_set_params( acn_scene_handle* h, const acn_params* prm )
+{
+    if( !h || !prm ) return fail( ACN_ERR_ARG, "null argument" );
+    std::string err;
+    int st = acn_tables_validate_params( prm, &err );
+    if( st != ACN_OK ) return fail( st, err );
+    const int n_levels = acn_tables_levels( prm );
+    HIP_TRY( hipSetDevice( h->device ) );
+    M3 rot; double unit_f = 0;
+    if( ( st = quiesce( h ) ) != ACN_OK || ( st = camera_basis( h, *prm, &rot, &unit_f ) ) != ACN_OK ) return st;
+    commit_params( h, *prm, n_levels, rot, unit_f );
+    settle( h, false );
+    h->param_sets++;
+    return ACN_OK;
+}
+
+extern "C" int acn_scene_info( acn_scene_handle* h, uint64_t* out, int n )
+{
+    if( !h || !out || n < 0 || n > ACN_INFO_N ) return fail( ACN_ERR_ARG, "bad argument" );
+    uint64_t v[ ACN_INFO_N ];
+    uint64_t learn_passes = h->run.learn_passes; bool known = h->run.learned.known();
+    for( auto& l : h->lanes ) { learn_passes += l->learn_passes; known = known || l->learned.known(); }
+    v[ ACN_INFO_REPLACES ] = h->replaces; v[ ACN_INFO_PARAM_SETS ] = h->param_sets;
+    /* (every stream of a handle is a member of a runner, and a runner lives as long as the handle) */
+    v[ ACN_INFO_STREAMS ] = 1 + h->lanes.size(); v[ ACN_INFO_LANES ] = h->lanes.size();
+    v[ ACN_INFO_LEARNING_PASSES ] = learn_passes; v[ ACN_INFO_NODES ] = h->dev.n_nodes; v[ ACN_INFO_RATES_KNOWN ] = known ? 1 : 0;
+    v[ ACN_INFO_DEVICE ] = ( uint64_t )h->device;
+    for( int k = 0; k < n; k++ ) out[ k ] = v[ k ];
     return ACN_OK;
 }
 
@@ -426,6 +579,7 @@ static int learn_rates( PipeRun* r, const Primary& prim, size_t n, hipStream_t s
     if( L.known() || !tun.learn_sample || tun.chunk || n < 16384 ) return ACN_OK;
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [ & ]() { return std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
+    r->learn_passes++;
     int st = ensure_workspace( r, 4096 );   /* the starter set */
     if( st != ACN_OK ) return st;
     if( r->d_accum.grow( sizeof( unsigned long long ) * 3 * n ) ) return ACN_ERR_DEVICE;
@@ -645,8 +799,7 @@ static void bind_lane( const acn_scene_handle* h, int lanes, PipeRun* l )
 {
     l->h = h;
     l->budget_div = ( size_t )lanes;
-    l->dev = h->dev;
-    l->dev.flags = l->d_counts.get() + QC_FLAGS;
+    refresh_run( h, l );
     /* Round 4: six lanes on grids of ONE workgroup per CU (k_shade: one and a half) instead of four lanes on two.  With k_walk at
      * four waves per SIMD a grid of 256 workgroups is resident at once, and six shorter chains fill each other's tails better than
      * four: 1080p 50.2 -> 49.1 ms, c2 26.4 -> 25.0, and the share one of 8 GPUs gets 12.25 -> 11.4 ms (profiles/r04/ab_lanes6_*).
@@ -667,9 +820,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     double t_mark[ 5 ] = { 0, 0, 0, 0, 0 };
     auto mark = [ & ]( int i ) { t_mark[ i ] = std::chrono::duration< double, std::milli >( std::chrono::steady_clock::now() - t_begin ).count(); };
     /* the lanes this call lacks: made on a helper thread while the learning pass of a cold handle runs (see lane_objects) */
-    early_lanes_join( h );
-    for( auto& l : h->early_made ) { bind_lane( h, lanes, l.get() ); h->lanes.push_back( std::move( l ) ); }   /* made during the upload */
-    h->early_made.clear();
+    /* (lanes made during the upload are the handle's already: quiesce) */
     const int missing = lanes - ( int )h->lanes.size();
     std::vector< std::unique_ptr< PipeRun > > made;
     int made_status = ACN_OK; std::string made_message;

@@ -193,7 +193,30 @@ static int recovery_load( const char* path, lum_image* img, uint64_t* cycle, uin
 
 static int file_exists( const char* path ) { FILE* f = fopen( path, "rb" ); if( f ) fclose( f ); return f != NULL; }
 
-int acn_scene_s_create_image_file( acn_scene* o, const char* file )
+/* the handle the image is rendered on: uploaded, or the caller's kept one with the scene replaced (another device: a fresh handle) */
+static int handle_for( const acn_scene* o, const acn_flat_scene* flat, acn_scene_handle** keep, acn_scene_handle** out )
+{
+    if( keep && *keep )
+    {
+        uint64_t info[ ACN_INFO_N ];
+        int st = acn_scene_info( *keep, info, ACN_INFO_N );
+        if( st != ACN_OK ) return st;
+        if( info[ ACN_INFO_DEVICE ] == ( uint64_t )o->device )
+        {
+            if( ( st = acn_scene_replace( *keep, flat, 0 ) ) == ACN_OK ) *out = *keep;
+            return st;
+        }
+        acn_scene_free( *keep );
+        *keep = NULL;
+    }
+    int st = acn_scene_upload( flat, o->device, out );
+    if( st == ACN_OK && keep ) *keep = *out;
+    return st;
+}
+
+int acn_scene_s_create_image_file( acn_scene* o, const char* file ) { return acn_scene_s_create_image_file_keep( o, file, NULL ); }
+
+int acn_scene_s_create_image_file_keep( acn_scene* o, const char* file, acn_scene_handle** keep )
 {
     if( !acn_scene_s_overwrite_output_files_g && file_exists( file ) )
     {
@@ -209,7 +232,7 @@ int acn_scene_s_create_image_file( acn_scene* o, const char* file )
     int st = acn_scene_s_flatten( o, &flat );
     if( st != ACN_OK ) { free( tmp_file ); return st; }
     acn_scene_handle* h = NULL;
-    st = acn_scene_upload( &flat, o->device, &h );
+    st = handle_for( o, &flat, keep, &h );
     if( st != ACN_OK ) { acn_flat_scene_free( &flat ); free( tmp_file ); return st; }
 
     size_t w = o->prm.image_width, hgt = o->prm.image_height;
@@ -289,7 +312,7 @@ int acn_scene_s_create_image_file( acn_scene* o, const char* file )
     free( tmp_file );
     free( arr );
     free( img.data );
-    acn_scene_free( h );
+    if( !keep ) acn_scene_free( h );   /* (a kept handle is the caller's to free, whatever the status) */
     acn_flat_scene_free( &flat );
     return st;
 }

@@ -170,9 +170,39 @@ class Scene:
         f._owned = True
         return f
 
-    def create_image_file(self, path, overwrite=True):
+    def create_image_file(self, path, overwrite=True, keep=None):
+        """Renders the scene and writes the PNM (acn_scene_s_create_image_file).  keep: a KeptHandle that holds one handle over many
+        images -- of this scene as it changes, or of other scenes; the caller closes it after the last image."""
         C.c_int.in_dll(host, "acn_scene_s_overwrite_output_files_g").value = 1 if overwrite else 0
-        check(host.acn_scene_s_create_image_file(self.ptr, path.encode()), "acn_scene_s_create_image_file")
+        ptr = self.ptr or self._borrowed
+        if keep is None:
+            check(host.acn_scene_s_create_image_file(ptr, path.encode()), "acn_scene_s_create_image_file")
+        else:
+            check(host.acn_scene_s_create_image_file_keep(ptr, path.encode(), C.byref(keep.h)), "acn_scene_s_create_image_file_keep")
+
+
+class KeptHandle:
+    """The handle Scene.create_image_file( keep=... ) renders on: uploaded by the first image, its scene replaced by every later one."""
+
+    def __init__(self):
+        self.h = C.c_void_p()
+
+    def info(self):
+        return Handle.info(self)
+
+    def close(self):
+        if self.h.value:
+            hip.acn_scene_free(self.h)
+            self.h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        self.close()
 
 
 def run_script(path, on_create_image=None, auto_envelope=0, readonly_fs=False, args=(), overwrite=True):
@@ -230,6 +260,46 @@ class Handle:
 
     def __del__(self):
         self.close()
+
+    # the scene of a live handle changes (acn_scene_replace, acn_scene_set_params): streams, lanes and queues stay
+    @property
+    def params(self):
+        """The render parameters the handle renders with now: a copy (abi.Params) of the flat scene's, as set_params left them."""
+        if getattr(self, "_params", None) is None:
+            p = abi.Params()
+            C.memmove(C.addressof(p), C.addressof(self.flat.c.params), C.sizeof(abi.Params))
+            self._params = p
+        return self._params
+
+    def replace(self, flat, forget=False):
+        """Makes `flat` the resident scene (acn_scene_replace); self.flat follows.  What the handle learned about its queue demand
+        stays if the scene is of the kind it was (include/actinon_hip.h), unless forget.  A refused scene raises and changes nothing."""
+        check(hip.acn_scene_replace(self.h, C.byref(flat.c), abi.ACN_REPLACE_FORGET if forget else 0), "acn_scene_replace")
+        self.flat = flat
+        self._params = None
+
+    def set_params(self, **fields):
+        """Changes members of the acn_params the handle renders with (acn_scene_set_params): camera, raster, samples, depth.
+        self.params follows; self.flat is the caller's and stays as it is."""
+        p = abi.Params()
+        C.memmove(C.addressof(p), C.addressof(self.params), C.sizeof(abi.Params))
+        for k, v in fields.items():
+            cur = getattr(p, k)
+            if hasattr(cur, "__len__"):
+                for i in range(len(cur)):
+                    cur[i] = float(v[i])
+            else:
+                setattr(p, k, v)
+        check(hip.acn_scene_set_params(self.h, C.byref(p)), "acn_scene_set_params")
+        self._params = p
+
+    INFO = ["replaces", "param_sets", "streams", "lanes", "learning_passes", "nodes", "rates_known", "device"]
+
+    def info(self):
+        """Counters of the handle since its upload (acn_scene_info): how a caller sees that it stayed warm."""
+        buf = (C.c_uint64 * abi.ACN_INFO_N)()
+        check(hip.acn_scene_info(self.h, buf, abi.ACN_INFO_N), "acn_scene_info")
+        return dict(zip(Handle.INFO, [int(v) for v in buf]))
 
     def _opts(self, linear, stream):
         o = abi.RenderOpts()

@@ -142,6 +142,12 @@ extern int acn_scene_s_automatic_recover_g;         /* scene.h:36  (actinon -r):
  * SIGINT during a gradient cycle stops softly: the accumulated image goes to `<file>.tmp.lum_image` and the call
  * returns ACN_ERR_CANCELLED; a later call with acn_scene_s_automatic_recover_g resumes at that cycle. */
 int acn_scene_s_create_image_file( acn_scene* o, const char* file );
+/* The same on a handle that outlives the call: a script that makes many images (a video's frames) pays the cold start of a handle once.
+ * keep == NULL: the call above.  *keep == NULL: a handle is uploaded and stored.  *keep != NULL: the scene is put on that handle with
+ * acn_scene_replace; if the scene's device is not the handle's, the handle is freed and a fresh one uploaded and stored.  The call never
+ * frees a handle it stores or finds: the caller does, with acn_scene_free, after its last image.  The images have the bytes the call
+ * above writes. */
+int acn_scene_s_create_image_file_keep( acn_scene* o, const char* file, acn_scene_handle** keep );
 /* image_cps_s_write_pnm on an RGB float image already gamma-saturated (values in [0,1]) */
 int acn_write_pnm( const char* file, const double* rgb, size_t w, size_t h );
 /* cps_from_cl scene.c:76-82 */

@@ -205,6 +205,45 @@ int acn_device_count( void );
 int acn_scene_upload( const acn_flat_scene* scene, int device, acn_scene_handle** out );
 void acn_scene_free( acn_scene_handle* h );
 
+/* Replacing the scene of a live handle: the next frame of an animation, another camera, preview samples turned into final ones --
+ * without the cold start of a fresh handle.  acn_scene_replace makes `scene` the resident scene of h, on the handle's device;
+ * acn_scene_set_params is the same change for the render parameters alone (camera, raster, samples, depth: no table is built and
+ * nothing is allocated).  Every later call on the handle renders the new scene with exactly the bits a fresh handle of it gives.
+ *   Kept       the handle's stream and events; every concurrent lane (stream, events, counter blocks, worker thread); the work queues as
+ *              allocated (neither call allocates or frees a queue); the scratch buffers of the other entry points; the workspace bound
+ *              and every tunable of the environment, which are read at acn_scene_upload and not again.
+ *   Learned    What the pipeline learned about the scene (queue demand per position, walk passes) is kept iff the new scene is of the
+ *              KIND of the old one: equal numbers of nodes, elements, light elements and path levels, both or neither with prune
+ *              programs, equal path_samples, direct_samples and trace_depth, and a trace_min_intensity of the same bits
+ *              (csrc/acn_queueplan.h: acn_replace_keeps_learned).  The raster and the camera are no part of the kind: a moved camera or a
+ *              moved object keeps it.  Otherwise, or with ACN_REPLACE_FORGET, the next call learns again as a cold handle does -- on
+ *              the lanes and queues that exist.  Pixels never depend on this: demand that was misjudged costs a chunk rendered twice.
+ *   Statistics acn_last_stage_ms, acn_last_kernel_ms and acn_last_counters describe a render call: after a change there is none until
+ *              the next one.  acn_last_stage_ms [ 24 ] keeps counting since the upload.
+ *   Failure    ACN_ERR_ARG (a null handle, scene or params; unknown flag bits; a malformed scene), ACN_ERR_UNSUPPORTED, ACN_ERR_NO_FOV --
+ *              what acn_scene_upload refuses -- and ACN_ERR_DEVICE while the new scene's device blocks are made leave the handle
+ *              rendering the scene and parameters it had; acn_last_error says why.
+ *   Caller     Both calls wait for the handle's own stream and for its lanes.  Work that earlier _dev calls queued on streams of the
+ *              CALLER's must be complete before either is called: the library cannot see those streams.  A handle serves one
+ *              caller at a time, here as everywhere. */
+#define ACN_REPLACE_FORGET 1u   /* drop what the runners learned even if the rule above would keep it */
+int acn_scene_replace( acn_scene_handle* h, const acn_flat_scene* scene, uint32_t flags );
+int acn_scene_set_params( acn_scene_handle* h, const acn_params* prm );
+/* Counters of a handle, since its upload unless said otherwise: how a host (or a test) sees that a handle stayed warm.  n <= ACN_INFO_N. */
+enum
+{
+    ACN_INFO_REPLACES = 0,      /* acn_scene_replace calls accepted */
+    ACN_INFO_PARAM_SETS,        /* acn_scene_set_params calls accepted */
+    ACN_INFO_STREAMS,           /* streams made by this handle: its own and its lanes' */
+    ACN_INFO_LANES,             /* lanes alive now */
+    ACN_INFO_LEARNING_PASSES,   /* learning passes run (the sampled pass of a handle that does not know its scene's queue demand) */
+    ACN_INFO_NODES,             /* nodes resident now */
+    ACN_INFO_RATES_KNOWN,       /* 1 if some runner's rates are known now */
+    ACN_INFO_DEVICE,            /* the device of the handle */
+    ACN_INFO_N   /* 8 */
+};
+int acn_scene_info( acn_scene_handle* h, uint64_t* out, int n );
+
 /* lum_machine_s_run counterpart on host buffers (src/scene.c:1017): out_rgb[i] = cl_s_sat( lum( pos_xy[i] ) ).
  * Synchronous. Returns acn_status. */
 int acn_render_positions( acn_scene_handle* h, const double* pos_xy, size_t n, double* out_rgb,

@@ -11,6 +11,13 @@
 
 #include "acn_interp.h"
 
+/* every create_image of the script renders on one handle, whose scene is replaced from image to image: the frames of a video loop
+ * pay the cold start of a handle once */
+static int create_image_on_kept_handle( void* ctx, acn_scene* scene, const char* file )
+{
+    return acn_scene_s_create_image_file_keep( scene, file, ( acn_scene_handle** )ctx );
+}
+
 int main( int argc, const char** argv )
 {
     /* the library's concurrent lanes want their streams on distinct hardware queues (ROCm maps streams onto
@@ -40,8 +47,12 @@ int main( int argc, const char** argv )
     memset( &opts, 0, sizeof( opts ) );
     opts.argc = n;
     opts.argv = args;
+    acn_scene_handle* kept = NULL;
+    opts.on_create_image = create_image_on_kept_handle;
+    opts.ctx = &kept;
     printf( "Processing '%s'\n", argv[ 1 ] );
     int st = acn_interpret_file( argv[ 1 ], &opts );
+    acn_scene_free( kept );
     if( st != ACN_OK ) fprintf( stderr, "%s\n", acn_interp_last_error() );
     free( args );
     return st == ACN_OK ? 0 : 3;
