@@ -35,6 +35,12 @@ ACN_LAYERS_SURFACE_PLANES, ACN_LAYERS_STATS_PLANES = 2, 3
 # selecting positions by a key (acn_select_above, acn_key_histogram): bins of the histogram, its words (the last counts NaN keys)
 ACN_KEY_HIST_BINS, ACN_KEY_HIST_WORDS = 256, 257
 
+# projecting points and reprojecting sample statistics (acn_project_points, acn_reproject): flags and defaults of acn_reproject_params
+ACN_REPROJECT_KINDS_SET, ACN_REPROJECT_HOPS_SET = 1, 2
+ACN_REPROJECT_DEFAULT_REJECT_KINDS = ACN_SURF_CHROMATIC | ACN_SURF_FRESNEL | ACN_SURF_TRANSPARENT | ACN_SURF_CUT
+ACN_REPROJECT_DEFAULT_MAX_HOPS = 0
+ACN_REPROJECT_DEFAULT_NORMAL_MIN, ACN_REPROJECT_DEFAULT_PLANE_TOLERANCE, ACN_REPROJECT_DEFAULT_MAX_HISTORY = 0.9, 0.01, 32.0
+
 # replacing the scene of a live handle (acn_scene_replace, acn_scene_info): the flag, the slots of the counters
 ACN_REPLACE_FORGET = 1
 ACN_INFO_N = 8
@@ -99,6 +105,11 @@ class SelectParams(C.Structure):
                 ("raster_width", C.c_uint64), ("raster_first", C.c_uint64)]
 
 
+class ReprojectParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reject_kinds", C.c_uint32), ("max_hops", C.c_int32),
+                ("normal_min", C.c_double), ("plane_tolerance", C.c_double), ("max_history", C.c_double)]
+
+
 # the stage-runner test seam (acn_run_stage): stages, option bits, limits
 ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE = 0, 1
 ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_LEAF_LIGHTS, ACN_STAGE_NO_EMIT_TERMS = 1, 2, 4
@@ -140,3 +151,4 @@ assert C.sizeof(Node) == 304, C.sizeof(Node)
 assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
 assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)
 assert C.sizeof(SelectParams) == 40, C.sizeof(SelectParams)
+assert C.sizeof(ReprojectParams) == 40, C.sizeof(ReprojectParams)

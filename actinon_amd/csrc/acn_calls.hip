@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points.
  * The lens calls that cut their positions into slices share one loop, lens_slices; a host-buffer form is a HostCall (acn_handle.h). */
@@ -12,6 +12,7 @@
 #include "acn_select_host.h"
 #include "acn_lenssurf_host.h"
 #include "acn_layers_host.h"
+#include "acn_reproject_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* kernels */
@@ -844,6 +845,82 @@ extern "C" int acn_lens_layers_resolve_dev( acn_scene_handle* h, const void* d_s
                                     ( double* )d_out_rgb, ( double* )d_out_noise, ( double* )d_out_pooled, c.stream );
     HIP_TRY( hipGetLastError() );
     return call_end( c );
+}
+
+/* ---- projected points and reprojected statistics (k_reproject.hip; the checks that need no handle: acn_reproject_host.h) ---- */
+extern "C" int acn_project_points_dev( acn_scene_handle* h, const void* d_points, size_t n, void* d_out_pos_xy, void* d_out_depth, const acn_render_opts* opts )
+{
+    Call c( opts );
+    if( !h || ( n && ( !d_points || !d_out_pos_xy ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many points in one call" );
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    acn_launch_project_points( h->dev, ( const double* )d_points, n, ( double* )d_out_pos_xy, ( double* )d_out_depth, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_project_points( acn_scene_handle* h, const double* points, size_t n, double* out_pos_xy, double* out_depth )
+{
+    if( !h || ( n && ( !points || !out_pos_xy ) ) ) return fail( ACN_ERR_ARG, "null argument" );
+    if( n == 0 ) return ACN_OK;
+    if( n > 0xFFFFFF00ull ) return fail( ACN_ERR_ARG, "too many points in one call" );
+    HostCall hc( h );
+    void* d_points = hc.in( points, sizeof( double ) * 3 * n );
+    void* d_pos = hc.out( out_pos_xy, sizeof( double ) * 2 * n );
+    void* d_depth = hc.out( out_depth, sizeof( double ) * n );
+    return hc.run( [ & ] { return acn_project_points_dev( h, d_points, n, d_pos, d_depth, nullptr ); } );
+}
+
+/* every check of a reproject call, on the host before the handle is touched: those that need no handle, then what acn_scene_set_params
+ * refuses of the previous frame's parameters */
+static int reproject_check( const acn_scene_handle* h, const void* cur_surface, size_t n, const acn_params* prev_params, const void* prev_surface,
+                            const void* prev_stats, const acn_reproject_params* prm, const void* out_stats, const void* out_motion,
+                            const acn_render_opts& opts, ReprojectSetup* su )
+{
+    std::string msg;
+    acn_reproject_params p;
+    if( acn_reproject_check( h != nullptr, cur_surface, n, prev_params, prev_surface, prev_stats, prm, out_stats, out_motion, opts.shard_world,
+                             &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( acn_tables_validate_params( prev_params, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, "prev_params: " + msg );
+    su->reject_kinds = p.reject_kinds; su->max_hops = p.max_hops;
+    su->normal_min = p.normal_min; su->plane_tolerance = p.plane_tolerance; su->max_history = p.max_history;
+    return ACN_OK;
+}
+
+extern "C" int acn_reproject_dev( acn_scene_handle* h, const void* d_cur_surface, size_t n, const acn_params* prev_params, const void* d_prev_surface,
+                                  const void* d_prev_stats, const acn_reproject_params* prm, void* d_out_stats, void* d_out_motion,
+                                  const acn_render_opts* opts )
+{
+    Call c( opts );
+    ReprojectSetup su;
+    int st = reproject_check( h, d_cur_surface, n, prev_params, d_prev_surface, d_prev_stats, prm, d_out_stats, d_out_motion, c.opts, &su );
+    if( st != ACN_OK || n == 0 ) return st;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    acn_launch_reproject( ( const double* )d_cur_surface, n, *prev_params, ( const double* )d_prev_surface, ( const double* )d_prev_stats, su,
+                          ( double* )d_out_stats, ( double* )d_out_motion, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_reproject( acn_scene_handle* h, const double* cur_surface, size_t n, const acn_params* prev_params, const double* prev_surface,
+                              const double* prev_stats, const acn_reproject_params* prm, double* out_stats, double* out_motion,
+                              const acn_render_opts* opts )
+{
+    Call c( opts );
+    ReprojectSetup su;
+    int st = reproject_check( h, cur_surface, n, prev_params, prev_surface, prev_stats, prm, out_stats, out_motion, c.opts, &su );
+    if( st != ACN_OK || n == 0 ) return st;
+    const size_t prev_n = ( size_t )( prev_params->image_width * prev_params->image_height );
+    HostCall hc( h );
+    void* d_cur = hc.in( cur_surface, sizeof( double ) * ACN_SURF_STRIDE * n );
+    void* d_ps = hc.in( prev_surface, sizeof( double ) * ACN_SURF_STRIDE * prev_n );
+    void* d_pt = hc.in( prev_stats, sizeof( double ) * ACN_STATS_STRIDE * prev_n );
+    void* d_out = hc.out( out_stats, sizeof( double ) * ACN_STATS_STRIDE * n );
+    void* d_motion = hc.out( out_motion, sizeof( double ) * 2 * n );
+    c.opts.stream = nullptr;
+    return hc.run( [ & ] { return acn_reproject_dev( h, d_cur, n, prev_params, d_ps, d_pt, prm, d_out, d_motion, &c.opts ); } );
 }
 
 /* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */

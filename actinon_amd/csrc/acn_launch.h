@@ -131,6 +131,16 @@ void acn_launch_lens_layers_merge( double* acc_surface, double* acc_stats, size_
 void acn_launch_lens_layers_resolve( const double* stats, size_t n, const double* background, double gamma, int linear, double* out_rgb,
                                      double* out_noise, double* out_pooled, hipStream_t stream );
 
+/* acn_project_points* and acn_reproject* (k_reproject.hip; include/actinon_hip.h states both).  project: points [ n ][ 3 ] -> out_pos_xy
+ * [ n ][ 2 ] and out_depth [ n ] (nullable) with the camera of sc.  reproject: cur_surface [ n ][ ACN_SURF_STRIDE ], the previous raster's
+ * prev_surface and prev_stats [ prev.image_height * prev.image_width ][ . ] -> out_stats [ n ][ ACN_STATS_STRIDE ] and out_motion [ n ][ 2 ]
+ * (nullable); of prev the raster size and the camera are read.  ReprojectSetup: acn_reproject_params after the host's checks, final
+ * values, no defaults.  Every record buffer 16-byte aligned; n >= 1 */
+struct ReprojectSetup { uint32_t reject_kinds; int32_t max_hops; double normal_min, plane_tolerance, max_history; };
+void acn_launch_project_points( const DevScene& sc, const double* points, size_t n, double* out_pos_xy, double* out_depth, hipStream_t stream );
+void acn_launch_reproject( const double* cur_surface, size_t n, const acn_params& prev, const double* prev_surface, const double* prev_stats,
+                           const ReprojectSetup& su, double* out_stats, double* out_motion, hipStream_t stream );
+
 /* the filter of acn_denoise_layers (k_denoise_layers.hip): stats [ 3 ][ n ][ ACN_STATS_STRIDE ], surf [ 2 ][ n ][ ACN_SURF_STRIDE ], both 16-byte
  * aligned; the parameters are final values; scratch: ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL bytes per pixel, 128-byte aligned */
 #define ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL 256

@@ -24,12 +24,7 @@ __global__ void k_camera_setup( DevScene sc, M3* out_rot, double* out_unit_f )
 {
     uint64_t unit_sz = ( sc.prm.image_height >> 1 );
     *out_unit_f = 1.0 / unit_sz;
-    V3 ry = v_of_length( ld3( sc.prm.camera_view_direction ), 1 );
-    V3 rz = v_of_length( ld3( sc.prm.camera_top_direction ), 1 );
-    rz = v_von( ry, rz );
-    V3 rx = v_mlx( ry, rz );
-    M3 r; r.x = rx; r.y = ry; r.z = rz;
-    *out_rot = m_transposed( r );
+    *out_rot = camera_rotation_of( sc.prm );
 }
 
 /* fixed point -> f64 (+ optional cl_s_sat) for positions [ base, base + n ) */

@@ -827,6 +827,65 @@ class Handle:
         self.lens_layers_resolve_dev(d.data_ptr(), n, rgb.data_ptr(), noise.data_ptr(), pooled.data_ptr(), linear=linear)
         return rgb.cpu().numpy(), noise.cpu().numpy(), LensStats(pooled.cpu().numpy(), self)
 
+    # projected points and reprojected statistics (acn_project_points, acn_reproject): the history of the next frame of an animation
+    def project_points(self, points):
+        """The sample positions of world points with the handle's current camera (acn_project_points), the inverse of camera_rays:
+        points [n,3] -> ( pos_xy [n,2], NaN where the point is not in front of the camera; depth [n] along the view direction )."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        pos = np.empty((pts.shape[0], 2), dtype=np.float64)
+        depth = np.empty((pts.shape[0],), dtype=np.float64)
+        check(hip.acn_project_points(self.h, pts.ctypes.data, pts.shape[0], pos.ctypes.data, depth.ctypes.data), "acn_project_points")
+        return pos, depth
+
+    def project_points_dev(self, d_points_ptr, n, d_out_pos_ptr, d_out_depth_ptr=None, stream=None):
+        o = self._plain_opts(False, stream)
+        check(hip.acn_project_points_dev(self.h, d_points_ptr, n, d_out_pos_ptr, d_out_depth_ptr, C.byref(o)), "acn_project_points_dev")
+
+    @staticmethod
+    def reproject_params(reject_kinds=None, max_hops=None, normal_min=None, plane_tolerance=None, max_history=None):
+        """acn_reproject_params of keyword arguments; None is the library's default"""
+        p = abi.ReprojectParams()
+        p.struct_size = C.sizeof(abi.ReprojectParams)
+        if reject_kinds is not None:
+            p.reject_kinds = int(reject_kinds)
+            p.flags |= abi.ACN_REPROJECT_KINDS_SET
+        if max_hops is not None:
+            p.max_hops = int(max_hops)
+            p.flags |= abi.ACN_REPROJECT_HOPS_SET
+        p.normal_min = 0.0 if normal_min is None else float(normal_min)
+        p.plane_tolerance = 0.0 if plane_tolerance is None else float(plane_tolerance)
+        p.max_history = 0.0 if max_history is None else float(max_history)
+        return p
+
+    def reproject(self, cur_surface, prev_params, prev_surface, prev_stats, **params):
+        """The statistics the previous frame accumulated where the current frame's surface points lay in it (acn_reproject):
+        cur_surface the Surface (or [n,16] records) of the current positions, prev_params the abi.Params the previous frame was rendered
+        with, prev_surface and prev_stats the Surface and LensStats (or records) of its whole raster -> ( LensStats over [n,8], motion
+        [n,2]: the position on the previous raster, NaN where there is none ).  params: reject_kinds, max_hops, normal_min,
+        plane_tolerance, max_history (Handle.reproject_params).  Merge the result with the current frame's statistics by lens_stats_merge."""
+        cur = np.ascontiguousarray(cur_surface.raw if isinstance(cur_surface, Surface) else cur_surface, dtype=np.float64).reshape(-1, abi.ACN_SURF_STRIDE)
+        ps = np.ascontiguousarray(prev_surface.raw if isinstance(prev_surface, Surface) else prev_surface, dtype=np.float64).reshape(-1, abi.ACN_SURF_STRIDE)
+        pt = np.ascontiguousarray(prev_stats.raw if isinstance(prev_stats, LensStats) else prev_stats, dtype=np.float64).reshape(-1, abi.ACN_STATS_STRIDE)
+        pixels = int(prev_params.image_width) * int(prev_params.image_height)
+        if len(ps) != pixels or len(pt) != pixels:
+            raise ValueError(f"the previous raster has {pixels} pixels: got {len(ps)} surface and {len(pt)} statistics records")
+        out = np.empty((cur.shape[0], abi.ACN_STATS_STRIDE), dtype=np.float64)
+        motion = np.empty((cur.shape[0], 2), dtype=np.float64)
+        p = self.reproject_params(**params)
+        o = self._plain_opts(False, None)
+        check(hip.acn_reproject(self.h, cur.ctypes.data, cur.shape[0], C.byref(prev_params), ps.ctypes.data, pt.ctypes.data, C.byref(p),
+                                out.ctypes.data, motion.ctypes.data, C.byref(o)), "acn_reproject")
+        return LensStats(out, self), motion
+
+    def reproject_dev(self, d_cur_surface_ptr, n, prev_params, d_prev_surface_ptr, d_prev_stats_ptr, d_out_stats_ptr, d_out_motion_ptr=None,
+                      stream=None, **params):
+        """Device buffers: records 16-byte aligned, d_out_motion [n,2] float64 or None; enqueued on `stream` without a synchronisation
+        (None: the handle's stream, synchronous)."""
+        p = self.reproject_params(**params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_reproject_dev(self.h, d_cur_surface_ptr, n, C.byref(prev_params), d_prev_surface_ptr, d_prev_stats_ptr, C.byref(p),
+                                    d_out_stats_ptr, d_out_motion_ptr, C.byref(o)), "acn_reproject_dev")
+
     # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
     @staticmethod
     def select_params(threshold, capacity=0, raster_width=0, raster_first=0):

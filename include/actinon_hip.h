@@ -860,6 +860,107 @@ int acn_key_histogram    ( acn_scene_handle* h, const double* key, size_t n, uin
 double acn_key_hist_edge( uint32_t bin );                                  /* no GPU */
 double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget );   /* no GPU */
 
+/* Projecting points and reprojecting sample statistics: the history of the next frame of an animation (k_reproject.hip).  A frame of
+ * an animation shows mostly surface points the frame before it has sampled already.  acn_reproject* finds, for each position of the
+ * new frame, where its surface point lay in the previous frame and gathers the statistics record accumulated there; the caller pools
+ * it with the new frame's own samples by acn_lens_stats_merge*.  All of it is a definition of this library: the reference renders
+ * single frames.  tools/render_turntable.py --temporal is a caller.
+ * Everything is IEEE binary64 without contraction, a / b is IEEE division, dot( a, b ) = ( a.x * b.x + a.y * b.y ) + a.z * b.z, floor is
+ * exact, sums are formed in the order written.  Where a result is a NaN, which NaN it is (sign, payload) is not defined.
+ *
+ * acn_project_points*: the inverse of acn_camera_rays*, with the handle's current camera (acn_scene_set_params moves it).
+ *   R, V, T = m_mlv( camera_rotation, ( 1, 0, 0 ) ), m_mlv( camera_rotation, ( 0, 1, 0 ) ), m_mlv( camera_rotation, ( 0, 0, 1 ) ): right, view
+ *             and top direction, as the lens forms them (m_mlv: csrc/acn_device.h; camera_rotation: the matrix camera_ray uses)
+ *   W = image_width, H = image_height, hh = ( double )( H >> 1 ), hw = ( double )( W >> 1 )
+ *   v  = P - camera_position                (per component)
+ *   ly = dot( v, V )                        the depth along the view direction: out_depth
+ *   s  = camera_focal_length / ly
+ *   qx = ( dot( v, R ) * s ) * hh + hw
+ *   qy = hh - ( dot( v, T ) * s ) * hh
+ *   PROJECTED iff ly > 0.0 (false for a NaN) and qx and qy are finite.  out_pos_xy is ( qx, qy ) then, else ( NaN, NaN ); out_depth
+ *   (nullable) is ly as computed, PROJECTED or not.  So acn_project_points( origin + direction * t of acn_camera_rays( pos ) ) is pos to
+ *   rounding for every t > 0.  points [ n ][ 3 ], out_pos_xy [ n ][ 2 ], out_depth [ n ], arrays of doubles.  Of opts only `stream` is
+ *   used, with the rules of acn_camera_rays_dev (NULL: the handle's own stream, and the call waits; a caller's stream is never
+ *   synchronised); the refusals are those of acn_camera_rays*: a null handle or (n > 0) a null points or out_pos_xy, n > 2^32 - 256.
+ *
+ * acn_reproject*: cur_surface [ n ][ ACN_SURF_STRIDE ] are the surface records of the current frame's positions -- any list of positions,
+ * not only a raster --; prev_surface [ H' * W' ][ ACN_SURF_STRIDE ] and prev_stats [ H' * W' ][ ACN_STATS_STRIDE ] the records of the WHOLE previous
+ * raster, pixel centres row-major, W' = prev_params->image_width, H' = prev_params->image_height.  prev_params is the acn_params the
+ * previous frame was rendered with; it must pass the checks of acn_scene_set_params, and of it only the raster size and the four
+ * camera members are read.  The handle's own scene and camera are not consulted: the handle supplies the device and the stream.
+ * The previous camera's basis is formed per lane by the expressions of k_camera_setup (csrc/acn_device.h: camera_rotation_of): its
+ * bits are those of a handle whose params are prev_params, and the motion plane equals acn_project_points on such a handle bit for bit.
+ * out_stats [ n ][ ACN_STATS_STRIDE ]; out_motion (nullable) [ n ][ 2 ].  Per current record r, in this order:
+ *   1 HIT        r[ 0 ] < inf, else the motion is ( NaN, NaN ) and the record EMPTY.
+ *   2 MOTION     ( qx, qy ) = the projection of P = r[ 1 .. 3 ] as above with the previous camera and W', H': where the point was on the
+ *                previous raster.  Not PROJECTED: the motion is ( NaN, NaN ) and the record EMPTY.  Else the motion is ( qx, qy ).
+ *   3 ELIGIBLE   iff ( ( uint32 )r[ 12 ] & reject_kinds ) == 0 and ( int32 )r[ 13 ] <= max_hops.  Else the record is EMPTY; the motion stays.
+ *   4 TAPS       fx = qx - 0.5;  fy = qy - 0.5;  x0 = floor( fx );  y0 = floor( fy );  tx = fx - x0;  ty = fy - y0.  The taps, in this order:
+ *                ( x0, y0 ), ( x0 + 1, y0 ), ( x0, y0 + 1 ), ( x0 + 1, y0 + 1 ) with the weights ( 1 - tx ) * ( 1 - ty ), tx * ( 1 - ty ),
+ *                ( 1 - tx ) * ty, tx * ty.  A tap ( x, y ) is in the image iff x >= 0.0, x < ( double )W', y >= 0.0 and y < ( double )H',
+ *                compared as doubles; only a tap in the image is converted to the index y * W' + x, and only then is anything of it read.
+ *   5 VALID      a tap with weight w, previous records r' (surface) and t' (statistics), N = r[ 4 .. 6 ], D = P' - P per component, iff
+ *                it is in the image;  w > 0.0;  t' is not EMPTY;  r'[ 0 ] < inf;  r'[ 7 ], r'[ 8 ], r'[ 13 ] converted to int32 equal those of
+ *                r (the MATCH rule of acn_denoise);  dot( N, N' ) >= normal_min;  |dot( N, D )| <= plane_tolerance * r[ 0 ].
+ *   6 GATHER     no valid tap: the record is EMPTY.  Else over the valid taps a, b, ... in the order of 4:
+ *                  sw     = ( ( 0.0 + w_a ) + w_b ) ...
+ *                  n      = ( ( ( 0.0 + w_a * n_a ) + w_b * n_b ) ... ) / sw
+ *                  mean.c = ( ( ( 0.0 + w_a * mean_a.c ) + w_b * mean_b.c ) ... ) / sw
+ *                  m2.c   = ( ( ( 0.0 + w_a * m2_a.c ) + w_b * m2_b.c ) ... ) / sw
+ *                  if n > max_history:  m2.c = m2.c * ( max_history / n );  n = max_history
+ *                  [ 7 ]  = 0
+ *   7 EMPTY      an EMPTY record is eight zeros.
+ * n is fractional; the record format allows it, and acn_lens_stats_merge*, acn_lens_stats_resolve_dev and acn_denoise_stats* take it as
+ * it is.  n >= 1 holds for every record that is not EMPTY: every n_a is >= 1, so w_a * n_a >= w_a * 1.0, which is w_a; the two sums are
+ * formed in the same order and rounding is monotone, so each partial sum of the w * n is >= that of the w; the quotient of x >= sw by
+ * sw is >= 1 after rounding; and max_history is >= 1.  A point on a pixel centre of the previous raster has one tap of weight 1 and
+ * gets that pixel's record bit for bit (( 0.0 + 1.0 * q ) / 1.0; a -0.0 becomes 0.0), up to the cap.  The cap bounds how long old samples outweigh new
+ * ones: after the merge with K new samples the history holds at most max_history / ( max_history + K ) of the weight.
+ * A record depends on its own current record and the four previous positions alone, not on which positions share a wavefront.
+ * Limitation, stated: the WORLD IS TAKEN TO BE AT REST between the two frames -- only the camera moves.  A surface that moved off
+ * its tangent plane fails the plane test and starts without history; one that moved within it, or whose light changed, keeps a
+ * history that is no longer its own.  Motion per object is the caller's: reject such positions (a kind bit, or an EMPTY previous
+ * record).  With the default reject_kinds history is taken only where the radiance does not depend on the view direction (no
+ * mirror, no glass, no Fresnel term); max_hops > 0 accepts records of ACN_SURF_FOLLOW behind glass or in mirrors, whose parallax
+ * is not that of the surface point: the caller's risk.  Layered records (acn_lens_layers_*) are not reprojected.
+ * The caller then runs acn_lens_stats_merge_dev( history, n, current statistics, n ); the library adds no fused call.
+ * Work goes to opts->stream; NULL is the handle's own stream, and then the call waits.  A caller's stream is never synchronised.  Of
+ * opts only `stream` is used.  The call touches no work queue, counter, learned rate or acn_last_* value.
+ * ACN_ERR_ARG, on the host before any launch, acn_last_error set, nothing written: a null handle or prev_params, or (n > 0) a null
+ * cur_surface, prev_surface, prev_stats or out_stats; n or W' * H' above 2^31, H' < 2 or W' < 1 (and what else acn_scene_set_params
+ * refuses of prev_params); a record buffer that is not 16-byte aligned or an out_motion that is not 8-byte aligned; struct_size < 4;
+ * unknown flags; a normal_min outside [ -1, 1 ] or NaN; a plane_tolerance that is negative or not finite; a max_history that is
+ * not 0 and not a finite number >= 1; shard_world > 1.  n == 0 is ACN_OK with no launch. */
+#define ACN_REPROJECT_KINDS_SET 1u   /* reject_kinds is taken as it stands: without this flag a 0 there means the default */
+#define ACN_REPROJECT_HOPS_SET  2u   /* the same for max_hops (whose default is 0 anyway: the flag is for symmetry and for later defaults) */
+#define ACN_REPROJECT_DEFAULT_REJECT_KINDS    ( ACN_SURF_CHROMATIC | ACN_SURF_FRESNEL | ACN_SURF_TRANSPARENT | ACN_SURF_CUT )
+#define ACN_REPROJECT_DEFAULT_MAX_HOPS        0
+#define ACN_REPROJECT_DEFAULT_NORMAL_MIN      0.9
+#define ACN_REPROJECT_DEFAULT_PLANE_TOLERANCE 0.01
+#define ACN_REPROJECT_DEFAULT_MAX_HISTORY     32.0
+typedef struct acn_reproject_params
+{
+    uint32_t struct_size;      /* sizeof as the CALLER was compiled; nothing beyond it is read, members it does not reach take their
+                                  defaults; < 4 is ACN_ERR_ARG */
+    uint32_t flags;            /* ACN_REPROJECT_*; unknown bits are ACN_ERR_ARG */
+    uint32_t reject_kinds;     /* ACN_SURF_* kind bits whose positions take no history; 0 = the default, unless ACN_REPROJECT_KINDS_SET */
+    int32_t  max_hops;         /* positions of more hops take no history; default 0 */
+    double   normal_min;       /* a tap needs dot( N, N' ) >= this; in [ -1, 1 ]; 0 = default 0.9; -1: no normal test */
+    double   plane_tolerance;  /* a tap needs |dot( N, P' - P )| <= this * distance; >= 0, finite; 0 = default 0.01 */
+    double   max_history;      /* the n a gathered record carries at most; finite, >= 1; 0 = default 32 */
+} acn_reproject_params;
+#define ACN_REPROJECT_PARAMS_INIT { ( uint32_t )sizeof( acn_reproject_params ), 0u, 0u, 0, 0.0, 0.0, 0.0 }
+int acn_project_points    ( acn_scene_handle* h, const double* points /* [ n ][ 3 ] */, size_t n, double* out_pos_xy /* [ n ][ 2 ] */,
+                            double* out_depth /* nullable [ n ] */ );
+int acn_project_points_dev( acn_scene_handle* h, const void* d_points, size_t n, void* d_out_pos_xy, void* d_out_depth /* nullable */,
+                            const acn_render_opts* opts );
+int acn_reproject_dev( acn_scene_handle* h, const void* d_cur_surface, size_t n, const acn_params* prev_params, const void* d_prev_surface,
+                       const void* d_prev_stats, const acn_reproject_params* prm /* nullable: defaults */, void* d_out_stats /* [ n ][ 8 ] */,
+                       void* d_out_motion /* nullable [ n ][ 2 ] */, const acn_render_opts* opts );
+int acn_reproject    ( acn_scene_handle* h, const double* cur_surface, size_t n, const acn_params* prev_params, const double* prev_surface,
+                       const double* prev_stats, const acn_reproject_params* prm, double* out_stats, double* out_motion /* nullable */,
+                       const acn_render_opts* opts );
+
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );
 

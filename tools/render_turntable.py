@@ -8,7 +8,17 @@ orbits the scene's view target -- the point camera_view_direction away from the 
 top direction, --orbit-deg degrees in all, frame 0 at the scene's own camera (actinon_amd.cameras.orbit_camera).  Only the first frame pays
 for a handle: the streams, the lanes and what the pipeline learned about the scene's queue demand stay from frame to frame, since a moved
 camera does not change the kind of the scene (include/actinon_hip.h: acn_scene_replace).  Each frame is a main pass on the device
-(acn_render_main_pass_dev, linear), resolved to 8 bits there (acn_resolve_dev) and written as a P6 PNM to OUT % frame."""
+(acn_render_main_pass_dev, linear), resolved to 8 bits there (acn_resolve_dev) and written as a P6 PNM to OUT % frame.
+
+    ... --temporal --samples K [--denoise] [--max-history M] [--allow-fresnel]
+
+keeps the samples of the frames before: every frame renders K jittered samples per pixel with their statistics
+(acn_render_lens_stats_main_pass_dev, pinhole, seed = frame), fetches for every pixel the statistics accumulated where its surface point
+lay in the previous frame (acn_reproject_dev, against the previous frame's first-hit surface records) and pools the two
+(acn_lens_stats_merge_dev); --denoise filters the pooled frame with its measured variance (acn_denoise_stats_dev).  History is taken
+only where the radiance does not depend on the view direction -- --allow-fresnel also takes it on Fresnel surfaces -- and carries at
+most --max-history samples (default 32), so a pixel converges over the frames without lagging behind the camera for long.  The world is
+taken to be at rest: only the camera moves (include/actinon_hip.h: acn_reproject)."""
 import argparse
 import os
 import sys
@@ -43,6 +53,61 @@ def render(flat, frames, orbit_deg, write, target_distance=None):
         h.close()
 
 
+def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=None, denoise=False, max_history=None, allow_fresnel=False):
+    """The same frames with the history of the frames before them; write( frame, rgb8 ) -> ( Handle.info, per frame the share of pixels
+    that took a history and their mean n after the merge )"""
+    import ctypes as C
+    import torch
+    import actinon_amd as A
+    from actinon_amd import abi
+    from actinon_amd.cameras import orbit_camera
+    w, hh = int(flat.params.image_width), int(flat.params.image_height)
+    n = w * hh
+    params = {}
+    if max_history is not None:
+        params["max_history"] = max_history
+    if allow_fresnel:
+        params["reject_kinds"] = abi.ACN_REPROJECT_DEFAULT_REJECT_KINDS & ~abi.ACN_SURF_FRESNEL
+    h = A.Handle(flat)
+    try:
+        dev = torch.device("cuda", h.device)
+        new = lambda *shape: torch.zeros(shape, dtype=torch.float64, device=dev)
+        d_pos = torch.from_numpy(A.main_pass_positions(w, hh)).to(dev)
+        d_surf, d_prev_surf = new(n, abi.ACN_SURF_STRIDE), new(n, abi.ACN_SURF_STRIDE)
+        d_cur, d_acc, d_prev = new(n, abi.ACN_STATS_STRIDE), new(n, abi.ACN_STATS_STRIDE), new(n, abi.ACN_STATS_STRIDE)
+        d_lin = new(n, 3)
+        d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)
+        prev_params, report = None, []
+        for f in range(frames):
+            if f:
+                h.set_params(**orbit_camera(flat.params, orbit_deg * f / frames, target_distance))
+            h.surface_positions_dev(d_pos.data_ptr(), n, d_surf.data_ptr())
+            h.render_lens_stats_main_pass_dev(0, n, None, d_cur.data_ptr(), linear=True, samples=samples, jitter=True, seed=f)
+            if f:
+                h.reproject_dev(d_surf.data_ptr(), n, prev_params, d_prev_surf.data_ptr(), d_prev.data_ptr(), d_acc.data_ptr(), **params)
+                took = float((d_acc[:, 0] >= 1).double().mean())
+                h.lens_stats_merge_dev(d_acc.data_ptr(), n, d_cur.data_ptr(), n)
+            else:
+                took = 0.0
+                d_acc.copy_(d_cur)
+                torch.cuda.synchronize(dev)
+            report.append((took, float(d_acc[:, 0].mean())))
+            if denoise:
+                h.denoise_stats_dev(d_acc.data_ptr(), d_surf.data_ptr(), w, hh, d_lin.data_ptr())
+            else:
+                h.lens_stats_resolve_dev(d_acc.data_ptr(), n, d_lin.data_ptr(), None, linear=True)
+            h.resolve_dev(d_lin.data_ptr(), n, None, d_rgb8.data_ptr())
+            write(f, d_rgb8.cpu().numpy().reshape(hh, w, 3))
+            d_surf, d_prev_surf = d_prev_surf, d_surf                          # this frame's records and pooled statistics become "previous"
+            d_acc, d_prev = d_prev, d_acc
+            prev_params = abi.Params()
+            C.memmove(C.addressof(prev_params), C.addressof(h.params), C.sizeof(abi.Params))
+        return h.info(), report
+    finally:
+        h.close()
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="A turntable of an Actinon scene on one handle (acn_scene_set_params)")
     ap.add_argument("scene", help=".acn script or flattened scene .npz")
@@ -52,9 +117,20 @@ def main(argv=None):
     ap.add_argument("--path-samples", type=int, default=None)
     ap.add_argument("--direct-samples", type=int, default=None)
     ap.add_argument("--target-distance", type=float, default=None, help="distance of the view target from the camera (default: the length of camera_view_direction)")
+    ap.add_argument("--temporal", action="store_true", help="keep the samples of the frames before: K jittered samples per frame, pooled with the reprojected history")
+    ap.add_argument("--samples", type=int, default=None, help="--temporal: samples per pixel and frame")
+    ap.add_argument("--denoise", action="store_true", help="--temporal: filter every pooled frame with its measured variance")
+    ap.add_argument("--max-history", type=float, default=None, help="--temporal: samples a history carries at most (default 32)")
+    ap.add_argument("--allow-fresnel", action="store_true", help="--temporal: take history on Fresnel surfaces too")
     args = ap.parse_args(argv)
     if args.frames < 1:
         ap.error("--frames is at least 1")
+    if args.temporal and (args.samples is None or args.samples < 1):
+        ap.error("--temporal needs --samples K, at least 1")
+    if not args.temporal and (args.samples is not None or args.denoise or args.max_history is not None or args.allow_fresnel):
+        ap.error("--samples, --denoise, --max-history and --allow-fresnel belong to --temporal")
+    if args.max_history is not None and not args.max_history >= 1:
+        ap.error("--max-history is at least 1")
     try:
         if args.out % 0 == args.out % 1:
             raise TypeError
@@ -69,7 +145,14 @@ def main(argv=None):
             if value < 0:
                 ap.error("sample counts are not negative")
             setattr(flat.params, name, value)
-    info = render(flat, args.frames, args.orbit_deg, lambda f, rgb8: write_pnm(args.out % f, np.ascontiguousarray(rgb8)), args.target_distance)
+    write = lambda f, rgb8: write_pnm(args.out % f, np.ascontiguousarray(rgb8))
+    if args.temporal:
+        info, report = render_temporal(flat, args.frames, args.orbit_deg, write, args.samples, args.target_distance, args.denoise, args.max_history,
+                                       args.allow_fresnel)
+        for f, (took, mean_n) in enumerate(report):
+            print(f"frame {f}: {took:.3f} of the pixels took a history, mean n {mean_n:.1f}")
+    else:
+        info = render(flat, args.frames, args.orbit_deg, write, args.target_distance)
     print(f"{args.frames} frames on one handle: {info['param_sets']} parameter changes, {info['streams']} streams, {info['lanes']} lanes, "
           f"{info['learning_passes']} learning pass(es)")
 
