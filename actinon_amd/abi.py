@@ -111,10 +111,11 @@ class ReprojectParams(C.Structure):
 
 
 # the stage-runner test seam (acn_run_stage): stages, option bits, limits
-ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE = 0, 1
+ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE, ACN_STAGE_HARD_SHADOW, ACN_STAGE_HARD_PATH = 0, 1, 2, 3
 ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_LEAF_LIGHTS, ACN_STAGE_NO_EMIT_TERMS = 1, 2, 4
 ACN_STAGE_MAX_RECORDS, ACN_STAGE_MAX_SAMPLES, ACN_STAGE_MAX_DEPTH = 1 << 20, 1 << 16, 1 << 20
 ACN_STAGE_INFO_WORDS = 10
+QS_DEAD_HS = 24          # word of a level's counter block (csrc/acn_counts.h): dead slots k_hard_shadow stepped over
 
 
 class StageArgs(C.Structure):

@@ -26,10 +26,12 @@ enum
 {
     QC_TASKS = 0, QC_CLASS0 = 1, QC_CHILDREN = 5, QC_FLAGS = 6, QC_HARD_SHADOW = 7, QC_HARD_PATH = 8,
     QC_CUR_HS = 9, QC_CUR_HP = 10, QC_CUR_HITS = 11, QC_CUR_SHADE0 = 20,   /* .. QC_CUR_SHADE0 + 3: one per size class */
-    /* ( words 24 .. 27 are unused ) */
+    QS_DEAD_HS = 24,   /* dead slots of the deferred-shadow queue: QC_HARD_SHADOW - QS_HARD_SHADOW - QS_PROBES, counted by k_hard_shadow,
+                          which steps over them.  No planner reads it (acn_read_chunk takes the difference) */
+    /* ( words 25 .. 27 are unused ) */
     /* reserved slots no record was written to (the unused ends of the waves' reservations): mark - dead = records, exactly.
      * Tasks, path-sample hits, deferred path rays, specular rays (all generations of the level together); the deferred-shadow
-     * queue has QS_HARD_SHADOW + QS_PROBES.  The dead slots of a chunk do not scale with it -- ~64 per wave, queue and launch --
+     * queue has QS_HARD_SHADOW + QS_PROBES, and QS_DEAD_HS above.  The dead slots of a chunk do not scale with it -- ~64 per wave, queue and launch --
      * so the marks of a SMALL chunk overstate its demand several times (learn_rates) */
     QS_DEAD_T = 28, QS_DEAD_C = 29, QS_DEAD_HP = 30, QS_DEAD_R = 31,
     QS_WALK_RAYS = 12, QS_HARD_SHADOW = 13, QS_HARD_PATH = 14, QS_CHILDREN = 15, QS_TASKS = 16, QS_WALK_STEPS = 17, QS_PRIVATE_RAYS = 18,

@@ -1,11 +1,12 @@
 /* acn_stage_host.h -- what acn_stage_plan / acn_run_stage (include/actinon_hip.h, the stage-runner test seam) do without the GPU: every
  * argument check, and the capacities of the output queues.  Plain C++, no HIP header: k_stage.hip calls acn_stage_check before it
  * launches anything, and tests/csrc/stage_cpu.cpp compiles the header on its own into a program that runs under the address and
- * undefined-behaviour sanitizers.  The two input records are restated here as plain structs; k_stage.hip asserts that they are the
+ * undefined-behaviour sanitizers.  The four input records are restated here as plain structs; k_stage.hip asserts that they are the
  * pipeline's (sizes and offsets). */
 #ifndef ACN_STAGE_HOST_H
 #define ACN_STAGE_HOST_H
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
@@ -26,6 +27,10 @@ struct acn_stage_dtask
     acn_stage_v3 pos, surface_d, ray_projection; double theta_i, on_a, on_b, diffuse_intensity; acn_stage_v3 Tc;
     uint64_t rv; int32_t depth; uint32_t pixel;
 };
+
+/* HardShadow and HardPath of acn_pipeline.h */
+struct acn_stage_hardshadow { acn_stage_v3 pos, d; double limit; acn_stage_v3 contrib; uint32_t pixel, pad; };
+struct acn_stage_hardpath { acn_stage_v3 pos, d, T; double intensity; int32_t depth; uint32_t pixel, resume, pad; };
 
 /* what the checks read of the uploaded scene */
 struct acn_stage_scene
@@ -48,6 +53,12 @@ static inline uint64_t acn_stage_samples( uint64_t samples, double diffuse_inten
     return n == 0 ? 1 : n;
 }
 
+static inline bool acn_stage_finite_ray( const acn_stage_v3& p, const acn_stage_v3& d )
+{
+    return std::isfinite( p.x ) && std::isfinite( p.y ) && std::isfinite( p.z ) && std::isfinite( d.x ) && std::isfinite( d.y ) && std::isfinite( d.z );
+}
+#define ACN_STAGE_RESUME_FLAG 2u        /* ACN_RESUME_FLAG of acn_device.h: the word is a resume word */
+
 /* slots a wave reserves at a time: ACN_QCHUNK of k_shade, chunks_resize( n ) of k_shade_hits (acn_pipeline.h) */
 static inline uint32_t acn_stage_chunk( uint32_t stage, uint32_t n, uint32_t grid )
 {
@@ -67,8 +78,28 @@ static inline int acn_stage_check( bool have_handle, const acn_stage_args* a, co
     if( !a->in ) { *msg = "null argument: in"; return ACN_ERR_ARG; }
     if( a->n == 0 || a->n > ACN_STAGE_MAX_RECORDS ) { *msg = "n " + std::to_string( a->n ) + " is outside 1 .. 2^20 records"; return ACN_ERR_ARG; }
     const bool shade = a->stage == ACN_STAGE_SHADE;
+    const bool hard = a->stage == ACN_STAGE_HARD_SHADOW || a->stage == ACN_STAGE_HARD_PATH;
     uint64_t sum_direct = 0, sum_path = 0;
-    if( !shade )
+    if( hard )
+    {
+        if( a->cls > ACN_STAGE_MAX_GRID ) { *msg = "workgroups (cls) " + std::to_string( a->cls ) + " are above 64"; return ACN_ERR_ARG; }
+        for( uint32_t i = 0; i < a->n; i++ )
+        {
+            const std::string who = ( a->stage == ACN_STAGE_HARD_SHADOW ? "hard-shadow record " : "hard-path record " ) + std::to_string( i );
+            const acn_stage_hardshadow* hs = a->stage == ACN_STAGE_HARD_SHADOW ? ( const acn_stage_hardshadow* )a->in + i : nullptr;
+            const acn_stage_hardpath* hp = hs ? nullptr : ( const acn_stage_hardpath* )a->in + i;
+            const uint32_t pixel = hs ? hs->pixel : hp->pixel;
+            if( pixel == ACN_STAGE_DEAD ) continue;
+            if( pixel >= a->n ) { *msg = who + ": pixel " + std::to_string( pixel ) + " is not below n"; return ACN_ERR_ARG; }
+            if( !acn_stage_finite_ray( hs ? hs->pos : hp->pos, hs ? hs->d : hp->d ) ) { *msg = who + ": the ray is not finite"; return ACN_ERR_ARG; }
+            if( hs && !( hs->limit > 0.0 ) ) { *msg = who + ": limit is not above 0"; return ACN_ERR_ARG; }
+            const uint32_t word = hs ? hs->pad : hp->resume;
+            if( ( word & 1u ) && ( ( word & ACN_STAGE_RESUME_FLAG ) || hp ) ) { *msg = who + ": bit 0 of the word is set beside a resume word"; return ACN_ERR_ARG; }
+            if( !( word & ACN_STAGE_RESUME_FLAG ) && word > 1u ) { *msg = who + ": a word without the resume flag names candidates"; return ACN_ERR_ARG; }
+            if( hp && ( hp->depth < 0 || hp->depth > ACN_STAGE_MAX_DEPTH ) ) { *msg = who + ": depth " + std::to_string( hp->depth ) + " is outside 0 .. 2^20"; return ACN_ERR_ARG; }
+        }
+    }
+    else if( !shade )
     {
         const acn_stage_hitrec* r = ( const acn_stage_hitrec* )a->in;
         for( uint32_t i = 0; i < a->n; i++ )
@@ -108,12 +139,14 @@ static inline int acn_stage_check( bool have_handle, const acn_stage_args* a, co
     acn_stage_caps c;
     memset( &c, 0, sizeof( c ) );
     const uint32_t items = shade ? a->n_index : a->n;
-    c.grid = ( items + 3u ) / 4u;
+    c.grid = hard ? ( a->cls ? a->cls : ( items + 255u ) / 256u ) : ( items + 3u ) / 4u;
     c.grid = c.grid > ACN_STAGE_MAX_GRID ? ACN_STAGE_MAX_GRID : c.grid;
     c.chunk = acn_stage_chunk( a->stage, a->n, c.grid );
     const uint64_t slack = ( uint64_t )c.grid * 4u * c.chunk;
     uint64_t tasks, rays, children, hs, hp;
     if( shade ) { tasks = a->n_index; rays = 0; children = sum_path + slack; hp = sum_path + slack; hs = sum_direct + sum_path + slack; }
+    else if( a->stage == ACN_STAGE_HARD_SHADOW ) { tasks = 0; rays = 0; children = 0; hp = 0; hs = a->n; }                      /* the input queue; nothing is appended */
+    else if( a->stage == ACN_STAGE_HARD_PATH )   { tasks = 0; rays = 0; children = ( uint64_t )a->n + slack; hp = a->n; hs = 0; }   /* a hit record per ray at most */
     else        { tasks = ( uint64_t )a->n + slack; rays = 3ull * a->n + slack; children = a->n; hp = 0; hs = 3ull * a->n + slack; }
     for( uint64_t v : { tasks, rays, children, hs, hp } )
         if( v > ACN_STAGE_MAX_CAP ) { *msg = "the input can produce " + std::to_string( v ) + " records of one queue: above 2^26"; return ACN_ERR_ARG; }

@@ -1,7 +1,7 @@
 /* k_stage.hip -- test seam: one shading kernel of the pipeline alone (acn_run_stage, include/actinon_hip.h).
  *
- * No device code: the unit launches k_shade_hits and k_shade through the wrappers of acn_launch.h, as render_chunk does, on queues it
- * owns for the length of the call.  The caller's records are the input queue; the counter block is zeroed and the input count set
+ * No device code: the unit launches k_shade_hits, k_shade, k_hard_shadow and k_hard_path through the wrappers of acn_launch.h, as
+ * render_chunk does, on queues it owns for the length of the call.  The caller's records are the input queue; the counter block is zeroed and the input count set
  * here; every output queue is sized by acn_stage_check (acn_stage_host.h) so that the kernel cannot fill it, and comes back whole,
  * dead slots included (pixel 0xFFFFFFFF: the ends of the waves' reservations).  k_shade never asks which class a task's sample count
  * belongs to, so the same task runs on 64, 16, 4 and 1 lanes: the index list goes where the kernel of `cls` reads it. */
@@ -15,6 +15,10 @@ static_assert( sizeof( acn_stage_hitrec ) == sizeof( HitRec ) && sizeof( acn_sta
 ACN_STAGE_SAME( acn_stage_hitrec, HitRec, exit_obj ); ACN_STAGE_SAME( acn_stage_hitrec, HitRec, enter_obj );
 ACN_STAGE_SAME( acn_stage_hitrec, HitRec, depth );    ACN_STAGE_SAME( acn_stage_hitrec, HitRec, pixel );
 ACN_STAGE_SAME( acn_stage_dtask, DTask, diffuse_intensity ); ACN_STAGE_SAME( acn_stage_dtask, DTask, depth ); ACN_STAGE_SAME( acn_stage_dtask, DTask, pixel );
+static_assert( sizeof( acn_stage_hardshadow ) == sizeof( HardShadow ) && sizeof( acn_stage_hardpath ) == sizeof( HardPath ), "acn_stage_host.h restates the records" );
+ACN_STAGE_SAME( acn_stage_hardshadow, HardShadow, limit ); ACN_STAGE_SAME( acn_stage_hardshadow, HardShadow, pixel ); ACN_STAGE_SAME( acn_stage_hardshadow, HardShadow, pad );
+ACN_STAGE_SAME( acn_stage_hardpath, HardPath, depth ); ACN_STAGE_SAME( acn_stage_hardpath, HardPath, pixel ); ACN_STAGE_SAME( acn_stage_hardpath, HardPath, resume );
+static_assert( ACN_STAGE_RESUME_FLAG == ACN_RESUME_FLAG, "acn_stage_host.h restates the resume flag" );
 
 /* the kernel of one size class (the four wrappers carry their class: the list it reads, its cursor) */
 void acn_launch_shade( int cls, KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s, unsigned long long* accum, unsigned long long* counters )
@@ -58,7 +62,8 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     if( !out ) return fail( ACN_ERR_ARG, "acn_run_stage: null argument: out" );
     Call c( nullptr );
     if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
-    const bool shade = a->stage == ACN_STAGE_SHADE;
+    const bool shade = a->stage == ACN_STAGE_SHADE, split = a->stage == ACN_STAGE_SHADE_HITS;
+    const bool hs_in = a->stage == ACN_STAGE_HARD_SHADOW, hp_in = a->stage == ACN_STAGE_HARD_PATH;
 
     /* the queues of one level.  Every queue exists (a kernel closes the reservations of all its queues), one record at least */
     auto bytes_of = []( uint32_t n, size_t rec ) { return ( size_t )( n ? n : 1u ) * rec; };
@@ -72,9 +77,9 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     uint32_t* d_idx[ ACN_NCLASS ];
     for( int k = 0; k < ACN_NCLASS; k++ ) d_idx[ k ] = ( uint32_t* )dc.make( shade && ( uint32_t )k == a->cls ? a->index : nullptr, b_idx );
     RayTask* d_rays = ( RayTask* )dc.make( nullptr, b_rays );
-    HitRec* d_children = ( HitRec* )dc.make( shade ? nullptr : a->in, b_children );
-    HardShadow* d_hs = ( HardShadow* )dc.make( nullptr, b_hs );
-    HardPath* d_hp = ( HardPath* )dc.make( nullptr, b_hp );
+    HitRec* d_children = ( HitRec* )dc.make( split ? a->in : nullptr, b_children );
+    HardShadow* d_hs = ( HardShadow* )dc.make( hs_in ? a->in : nullptr, b_hs );
+    HardPath* d_hp = ( HardPath* )dc.make( hp_in ? a->in : nullptr, b_hp );
     uint32_t* d_counts = ( uint32_t* )dc.make( nullptr, b_counts );      /* the level's block, and behind it the input count of k_shade_hits */
     unsigned long long* d_accum = ( unsigned long long* )dc.make( nullptr, b_accum );
     unsigned long long* d_counters = ( unsigned long long* )dc.make( nullptr, sizeof( unsigned long long ) * ACN_CNT_SLOTS );
@@ -86,14 +91,16 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     if( !shade ) HIP_TRY( hipMemsetAsync( d_tasks, 0xFF, b_tasks, c.stream ) );
     for( int k = 0; k < ACN_NCLASS; k++ ) if( !( shade && ( uint32_t )k == a->cls ) ) HIP_TRY( hipMemsetAsync( d_idx[ k ], 0xFF, b_idx, c.stream ) );
     HIP_TRY( hipMemsetAsync( d_rays, 0xFF, b_rays, c.stream ) );
-    if( shade ) HIP_TRY( hipMemsetAsync( d_children, 0xFF, b_children, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_hs, 0xFF, b_hs, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_hp, 0xFF, b_hp, c.stream ) );
+    if( !split ) HIP_TRY( hipMemsetAsync( d_children, 0xFF, b_children, c.stream ) );
+    if( !hs_in ) HIP_TRY( hipMemsetAsync( d_hs, 0xFF, b_hs, c.stream ) );
+    if( !hp_in ) HIP_TRY( hipMemsetAsync( d_hp, 0xFF, b_hp, c.stream ) );
     HIP_TRY( hipMemsetAsync( d_counts, 0, b_counts, c.stream ) );
     HIP_TRY( hipMemsetAsync( d_accum, 0, b_accum, c.stream ) );
     HIP_TRY( hipMemsetAsync( d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS, c.stream ) );
     const uint32_t n_in = shade ? a->n_index : a->n;
-    HIP_TRY( hipMemcpyAsync( shade ? d_counts + QC_CLASS0 + a->cls : d_counts + QC_N, &n_in, sizeof( n_in ), hipMemcpyHostToDevice, c.stream ) );
+    /* where the kernel reads how much input it has: its class list's mark, the previous level's children, its own queue's mark */
+    uint32_t* const d_n_in = shade ? d_counts + QC_CLASS0 + a->cls : hs_in ? d_counts + QC_HARD_SHADOW : hp_in ? d_counts + QC_HARD_PATH : d_counts + QC_N;
+    HIP_TRY( hipMemcpyAsync( d_n_in, &n_in, sizeof( n_in ), hipMemcpyHostToDevice, c.stream ) );
     HIP_TRY( hipStreamSynchronize( c.stream ) );   /* n_in leaves the stack */
 
     LevelQ q;
@@ -113,8 +120,10 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     DevScene dev = h->dev;
     dev.flags = d_counts + QC_FLAGS;
     const SceneArgs s = scene_args( dev, h->scene );
-    if( shade ) acn_launch_shade( ( int )a->cls, f, q, c.stream, s, d_accum, d_counters );
-    else        acn_launch_shade_hits( false, q, c.stream, s, d_accum, d_counters );
+    if( shade )      acn_launch_shade( ( int )a->cls, f, q, c.stream, s, d_accum, d_counters );
+    else if( hs_in ) acn_launch_hard_shadow( f, q, machine_lds_bytes( h->scene ), c.stream, s, d_accum, d_counters );
+    else if( hp_in ) acn_launch_hard_path( f, q, machine_lds_bytes( h->scene ), c.stream, s, d_accum, d_counters );
+    else             acn_launch_shade_hits( false, q, c.stream, s, d_accum, d_counters );
     HIP_TRY( hipGetLastError() );
     HIP_TRY( hipStreamSynchronize( c.stream ) );
 
@@ -124,11 +133,11 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     if( counts[ QC_FLAGS ] & ( ACN_FLAGS_CHUNK_LOST | ACN_FLAG_STACK_OVERFLOW ) )
         return fail( ACN_ERR_DEVICE, "acn_run_stage: the kernel raised overflow flags " + std::to_string( counts[ QC_FLAGS ] ) + ": a queue the plan sized was too small" );
     struct { void* dst; const void* d; size_t bytes; } outs[] = {
-        { shade ? nullptr : out->tasks, d_tasks, b_tasks },
-        { shade ? nullptr : ( void* )out->idx[ 0 ], d_idx[ 0 ], b_idx }, { shade ? nullptr : ( void* )out->idx[ 1 ], d_idx[ 1 ], b_idx },
-        { shade ? nullptr : ( void* )out->idx[ 2 ], d_idx[ 2 ], b_idx }, { shade ? nullptr : ( void* )out->idx[ 3 ], d_idx[ 3 ], b_idx },
-        { shade ? nullptr : out->rays, d_rays, b_rays }, { shade ? out->children : nullptr, d_children, b_children },
-        { out->hard_shadow, d_hs, b_hs }, { shade ? out->hard_path : nullptr, d_hp, b_hp }, { out->accum, d_accum, b_accum } };
+        { split ? out->tasks : nullptr, d_tasks, b_tasks },
+        { split ? ( void* )out->idx[ 0 ] : nullptr, d_idx[ 0 ], b_idx }, { split ? ( void* )out->idx[ 1 ] : nullptr, d_idx[ 1 ], b_idx },
+        { split ? ( void* )out->idx[ 2 ] : nullptr, d_idx[ 2 ], b_idx }, { split ? ( void* )out->idx[ 3 ] : nullptr, d_idx[ 3 ], b_idx },
+        { split ? out->rays : nullptr, d_rays, b_rays }, { shade || hp_in ? out->children : nullptr, d_children, b_children },
+        { shade || split || hs_in ? out->hard_shadow : nullptr, d_hs, b_hs }, { shade ? out->hard_path : nullptr, d_hp, b_hp }, { out->accum, d_accum, b_accum } };
     for( const auto& o : outs ) if( o.dst && ( st = DevCopies::fetch( o.dst, o.d, o.bytes ) ) != ACN_OK ) return st;
     return ACN_OK;
 }

@@ -1003,22 +1003,27 @@ class Handle:
                 "nodes": int(w[7]), "lights": int(w[8]), "prune": bool(w[9] & 1), "leaf_lights": bool(w[9] & 2)}
         return info
 
-    def run_stage(self, stage, records, index=None, cls=0, shard_rank=0, shard_world=1, prune=True, leaf_lights=True, emit_terms=True):
+    def run_stage(self, stage, records, index=None, cls=0, shard_rank=0, shard_world=1, prune=True, leaf_lights=True, emit_terms=True, grid=0):
         """Runs one production shading kernel on `records` and returns everything it wrote as a dict of numpy arrays.
         stage "shade_hits": records are "hit" records (pixel = own index, or STAGE_INVALID); returns tasks, idx (four lists), rays,
         hard_shadow (the probes), counts, flags, accum.  stage "shade": records are "task" records, index the uint32 list the kernel of
-        size class `cls` works off; returns children, hard_shadow, hard_path, counts, flags, accum.  Queues come back up to their
+        size class `cls` works off; returns children, hard_shadow, hard_path, counts, flags, accum.  stage "hard_shadow" / "hard_path":
+        records are the queue of k_hard_shadow / k_hard_path as the kernel meets it, dead slots (pixel STAGE_INVALID) included, on
+        `grid` workgroups (0: one per 256 records); returns counts, flags, accum, the queue slot for slot as "hard_shadow" left it, and
+        children for "hard_path".  Queues come back up to their
         high-water mark with the dead slots (pixel STAGE_INVALID) taken out; accum is [n, 3] int64 in units of 2^-40."""
         info = self.stage_info()
         for k, dt in self.STAGE_RECORDS.items():
             assert dt.itemsize == info["sizeof"][k], (k, dt.itemsize, info["sizeof"][k])
-        shade = {"shade_hits": False, "shade": True}[stage]
-        rec = np.ascontiguousarray(records, dtype=self.STAGE_RECORDS["task" if shade else "hit"])
+        code, kind = {"shade_hits": (abi.ACN_STAGE_SHADE_HITS, "hit"), "shade": (abi.ACN_STAGE_SHADE, "task"),
+                      "hard_shadow": (abi.ACN_STAGE_HARD_SHADOW, "hard_shadow"), "hard_path": (abi.ACN_STAGE_HARD_PATH, "hard_path")}[stage]
+        shade, hard = stage == "shade", stage in ("hard_shadow", "hard_path")
+        rec = np.ascontiguousarray(records, dtype=self.STAGE_RECORDS[kind])
         a = abi.StageArgs()
-        a.stage = abi.ACN_STAGE_SHADE if shade else abi.ACN_STAGE_SHADE_HITS
+        a.stage = code
         a.flags = ((0 if prune else abi.ACN_STAGE_NO_PRUNE) | (0 if leaf_lights else abi.ACN_STAGE_NO_LEAF_LIGHTS)
                    | (0 if emit_terms else abi.ACN_STAGE_NO_EMIT_TERMS))
-        a.cls, a.shard_rank, a.shard_world, a.n = int(cls), int(shard_rank), int(shard_world), rec.shape[0]
+        a.cls, a.shard_rank, a.shard_world, a.n = int(grid if hard else cls), int(shard_rank), int(shard_world), rec.shape[0]
         a.input = rec.ctypes.data
         ix = None
         if shade:
@@ -1027,30 +1032,36 @@ class Handle:
         caps = abi.StageCaps()
         check(hip.acn_stage_plan(self.h, C.byref(a), C.byref(caps)), "acn_stage_plan")
         R = self.STAGE_RECORDS
-        bufs = {"counts": np.zeros(info["counter_words"], dtype=np.uint32), "accum": np.zeros((rec.shape[0], 3), dtype=np.int64),
-                "hard_shadow": np.zeros(max(caps.cap_hard_shadow, 1), dtype=R["hard_shadow"])}
-        if shade:
+        bufs = {"counts": np.zeros(info["counter_words"], dtype=np.uint32), "accum": np.zeros((rec.shape[0], 3), dtype=np.int64)}
+        if stage != "hard_path":
+            bufs["hard_shadow"] = np.zeros(max(caps.cap_hard_shadow, 1), dtype=R["hard_shadow"])
+        if shade or stage == "hard_path":
             bufs["children"] = np.zeros(max(caps.cap_children, 1), dtype=R["hit"])
+        if shade:
             bufs["hard_path"] = np.zeros(max(caps.cap_hard_path, 1), dtype=R["hard_path"])
-        else:
+        elif not hard:
             bufs["tasks"] = np.zeros(max(caps.cap_tasks, 1), dtype=R["task"])
             bufs["rays"] = np.zeros(max(caps.cap_rays, 1), dtype=R["ray"])
             idx = [np.zeros(max(caps.cap_tasks, 1), dtype=np.uint32) for _ in range(4)]
         o = abi.StageOut()
         for k, b in bufs.items():
             setattr(o, k, b.ctypes.data)
-        if not shade:
+        if not shade and not hard:
             for k in range(4):
                 o.idx[k] = idx[k].ctypes.data
         check(hip.acn_run_stage(self.h, C.byref(a), C.byref(o)), "acn_run_stage")
         c = bufs["counts"]
         live = lambda q, mark: q[:mark][q["pixel"][:mark] != self.STAGE_INVALID]   # noqa: E731
-        res = {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps,
-               "hard_shadow": live(bufs["hard_shadow"], c[self.QC["hard_shadow"]])}
-        if shade:
+        res = {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps}
+        if not hard:
+            res["hard_shadow"] = live(bufs["hard_shadow"], c[self.QC["hard_shadow"]])
+        elif stage == "hard_shadow":
+            res["hard_shadow"] = bufs["hard_shadow"][:rec.shape[0]]   # slot for slot, as the kernel left it
+        if shade or stage == "hard_path":
             res["children"] = live(bufs["children"], c[self.QC["children"]])
+        if shade:
             res["hard_path"] = live(bufs["hard_path"], c[self.QC["hard_path"]])
-        else:
+        elif not hard:
             res["tasks"] = bufs["tasks"][:c[self.QC["tasks"]]]       # with the unused ends of reservations: reached through idx only
             res["rays"] = live(bufs["rays"], c[self.QC["gen0"]])
             res["idx"] = [l[:c[self.QC["class0"] + k]][l[:c[self.QC["class0"] + k]] != self.STAGE_INVALID] for k, l in enumerate(idx)]

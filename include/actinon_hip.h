@@ -1051,16 +1051,26 @@ int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const double* ray
  *   ACN_STAGE_SHADE       k_shade of size class `cls` on in = DTask[ n ] and index[ n_index ] (entries < n, or 0xFFFFFFFF: a dead
  *                         slot), whatever class the sample counts of a task ask for.  Written: children, hard_shadow, hard_path,
  *                         counts, flags, accum.  shard_rank < shard_world: the rank's share of the sample loops (0, 1: all of them).
- * Every record's pixel is < n or 0xFFFFFFFF (HitRec: a dead slot); accum is [ n ][ 3 ] raw fixed-point words (2^-40), zero before the launch.
+ *   ACN_STAGE_HARD_SHADOW k_hard_shadow on in = HardShadow[ n ], the queue as the kernel meets it, dead slots included.  pad is 0 or 1
+ *                         (nothing is known; bit 0: the light root counts too) or a resume word (bit 1 set, bit 0 clear).  Written:
+ *                         counts, flags, accum, and hard_shadow: the queue as the kernel leaves it (the fill phase gives a probe
+ *                         that is left for a machine its resume word).
+ *   ACN_STAGE_HARD_PATH   k_hard_path on in = HardPath[ n ], dead slots included; resume is 0 or a resume word.  Written: children,
+ *                         counts, flags, accum.
+ *                         Both: `cls` is the number of workgroups of the launch (0: one per 256 records, 64 at most) -- with one
+ *                         workgroup and n >= 8192 every wave draws 256 consecutive slots at a time, so a test decides what a wave's
+ *                         pending list holds.  Rays are finite, limit > 0 (not NaN), depth as below.
+ * Every record's pixel is < n or 0xFFFFFFFF (HitRec, HardShadow, HardPath: a dead slot, of which nothing else is read); accum is [ n ][ 3 ] raw fixed-point words (2^-40), zero before the launch.
  * The kernel variant is the handle's; ACN_STAGE_NO_PRUNE and ACN_STAGE_NO_LEAF_LIGHTS select the variant without interval-prune
  * programs / with the generic light hit (equal results), ACN_STAGE_NO_EMIT_TERMS runs the split as a shard rank > 0 does (emit_terms 0).
  * acn_stage_plan makes every check on the host and sizes the queues from the input so that none can overflow (the records the input
  * can produce at most, plus one reservation per wave of the small grid the seam launches); a caller allocates each output it
  * wants with the planned capacity, a null output is not fetched.  ACN_ERR_ARG before anything is launched, acn_last_error set: a null
- * handle, args or input; an unknown stage or flag; cls > 3; shard_rank >= shard_world; n or n_index 0 or above ACN_STAGE_MAX_RECORDS;
+ * handle, args or input; an unknown stage or flag; cls > 3 (HARD_*: > 64); a ray that is not finite, a limit that is not > 0, a pad
+ * or resume word with bit 0 beside bit 1; shard_rank >= shard_world; n or n_index 0 or above ACN_STAGE_MAX_RECORDS;
  * a pixel, index entry or object (-1 .. nodes - 1) out of range; a depth outside 0 .. ACN_STAGE_MAX_DEPTH; a diffuse_intensity that is
  * not finite or asks for more than ACN_STAGE_MAX_SAMPLES samples of a loop.  A raised overflow flag is ACN_ERR_DEVICE. */
-enum acn_stage { ACN_STAGE_SHADE_HITS = 0, ACN_STAGE_SHADE = 1, ACN_STAGE_N };
+enum acn_stage { ACN_STAGE_SHADE_HITS = 0, ACN_STAGE_SHADE = 1, ACN_STAGE_HARD_SHADOW = 2, ACN_STAGE_HARD_PATH = 3, ACN_STAGE_N };
 #define ACN_STAGE_NO_PRUNE       1u
 #define ACN_STAGE_NO_LEAF_LIGHTS 2u
 #define ACN_STAGE_NO_EMIT_TERMS  4u
@@ -1070,7 +1080,7 @@ enum acn_stage { ACN_STAGE_SHADE_HITS = 0, ACN_STAGE_SHADE = 1, ACN_STAGE_N };
 typedef struct acn_stage_args
 {
     uint32_t stage, flags;              /* ACN_STAGE_*, ACN_STAGE_NO_* */
-    uint32_t cls;                       /* SHADE */
+    uint32_t cls;                       /* SHADE: size class; HARD_*: workgroups, 0 = by n */
     uint32_t shard_rank, shard_world;   /* SHADE; shard_world 0 reads as 1 */
     uint32_t n, n_index;                /* input records; SHADE: entries of index */
     uint32_t pad;
