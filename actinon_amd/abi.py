@@ -115,12 +115,20 @@ ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE, ACN_STAGE_HARD_SHADOW, ACN_STAGE_HARD_PAT
 ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_LEAF_LIGHTS, ACN_STAGE_NO_EMIT_TERMS = 1, 2, 4
 ACN_STAGE_MAX_RECORDS, ACN_STAGE_MAX_SAMPLES, ACN_STAGE_MAX_DEPTH = 1 << 20, 1 << 16, 1 << 20
 ACN_STAGE_INFO_WORDS = 10
+# the walk of a level alone (acn_run_stage_walk)
+ACN_STAGE_WALK, ACN_STAGE_GLOBAL_NODES, ACN_STAGE_WALK_MAX_STACK, ACN_MAX_WALK_PASSES = 4, 8, 4096, 32
 QS_DEAD_HS = 24          # word of a level's counter block (csrc/acn_counts.h): dead slots k_hard_shadow stepped over
 
 
 class StageArgs(C.Structure):
     _fields_ = [("stage", C.c_uint32), ("flags", C.c_uint32), ("cls", C.c_uint32), ("shard_rank", C.c_uint32), ("shard_world", C.c_uint32),
                 ("n", C.c_uint32), ("n_index", C.c_uint32), ("pad", C.c_uint32), ("input", C.c_void_p), ("index", C.c_void_p)]
+
+
+class StageWalkArgs(C.Structure):
+    _fields_ = [("stage", C.c_uint32), ("flags", C.c_uint32), ("n", C.c_uint32), ("camera", C.c_uint32), ("passes", C.c_uint32),
+                ("private_limit", C.c_uint32), ("stack_cap", C.c_uint32), ("stack_use", C.c_uint32), ("fetch", C.c_uint32), ("grid", C.c_uint32),
+                ("room_rays", C.c_uint32), ("pad", C.c_uint32), ("input", C.c_void_p), ("pos_xy", C.c_void_p), ("first_pixel", C.c_uint64)]
 
 
 class StageCaps(C.Structure):
@@ -153,3 +161,4 @@ assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
 assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)
 assert C.sizeof(SelectParams) == 40, C.sizeof(SelectParams)
 assert C.sizeof(ReprojectParams) == 40, C.sizeof(ReprojectParams)
+assert C.sizeof(StageWalkArgs) == 72, C.sizeof(StageWalkArgs)

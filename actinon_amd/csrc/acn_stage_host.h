@@ -1,8 +1,8 @@
 /* acn_stage_host.h -- what acn_stage_plan / acn_run_stage (include/actinon_hip.h, the stage-runner test seam) do without the GPU: every
  * argument check, and the capacities of the output queues.  Plain C++, no HIP header: k_stage.hip calls acn_stage_check before it
  * launches anything, and tests/csrc/stage_cpu.cpp compiles the header on its own into a program that runs under the address and
- * undefined-behaviour sanitizers.  The four input records are restated here as plain structs; k_stage.hip asserts that they are the
- * pipeline's (sizes and offsets). */
+ * undefined-behaviour sanitizers (tests/csrc/stage_walk_cpu.cpp: the walk's checks, acn_stage_walk_check).  The five input records
+ * are restated here as plain structs; k_stage.hip asserts that they are the pipeline's (sizes and offsets). */
 #ifndef ACN_STAGE_HOST_H
 #define ACN_STAGE_HOST_H
 
@@ -13,6 +13,7 @@
 #include <string>
 
 #include "actinon_hip.h"
+#include "acn_counts.h"
 
 struct acn_stage_v3 { double x, y, z; };
 /* HitRec of acn_pipeline.h */
@@ -31,12 +32,15 @@ struct acn_stage_dtask
 /* HardShadow and HardPath of acn_pipeline.h */
 struct acn_stage_hardshadow { acn_stage_v3 pos, d; double limit; acn_stage_v3 contrib; uint32_t pixel, pad; };
 struct acn_stage_hardpath { acn_stage_v3 pos, d, T; double intensity; int32_t depth; uint32_t pixel, resume, pad; };
+/* RayTask of acn_pipeline.h */
+struct acn_stage_raytask { acn_stage_v3 p, d, T; double intensity; int32_t depth; uint32_t pixel; };
 
 /* what the checks read of the uploaded scene */
 struct acn_stage_scene
 {
     uint32_t n_nodes, n_lights;
     uint64_t direct_samples, path_samples;
+    double trace_min_intensity;
 };
 
 #define ACN_STAGE_DEAD 0xFFFFFFFFu
@@ -152,6 +156,60 @@ static inline int acn_stage_check( bool have_handle, const acn_stage_args* a, co
         if( v > ACN_STAGE_MAX_CAP ) { *msg = "the input can produce " + std::to_string( v ) + " records of one queue: above 2^26"; return ACN_ERR_ARG; }
     c.cap_tasks = ( uint32_t )tasks; c.cap_rays = ( uint32_t )rays; c.cap_children = ( uint32_t )children;
     c.cap_hard_shadow = ( uint32_t )hs; c.cap_hard_path = ( uint32_t )hp;
+    *caps = c;
+    return ACN_OK;
+}
+
+/* ---- the walk (acn_stage_walk_plan / acn_run_stage_walk) ---- */
+
+/* input slots of a walk call: the rays, or every slot of the tiles of 256 positions of the camera form (ACN_ORDER_SHIFT) */
+static inline uint32_t acn_stage_walk_slots( const acn_stage_walk_args* a ) { return a->camera ? ( ( a->n + 255u ) >> 8 ) << 8 : a->n; }
+
+/* every check of a walk call, then the launch and the capacities.  Each launch of k_walk appends to the tasks, to the probes and
+ * to ONE ray buffer (the next generation's, which it fills from slot 0), so the slack of a wave's reservations is one per launch
+ * for the tasks and the probes and one for a ray buffer. */
+static inline int acn_stage_walk_check( bool have_handle, const acn_stage_walk_args* a, const acn_stage_scene& sc, acn_stage_caps* caps, std::string* msg )
+{
+    if( !have_handle ) { *msg = "null argument: handle"; return ACN_ERR_ARG; }
+    if( !a || !caps ) { *msg = "null argument: acn_stage_walk_args / acn_stage_caps"; return ACN_ERR_ARG; }
+    if( a->stage != ACN_STAGE_WALK ) { *msg = "stage " + std::to_string( a->stage ) + " is not ACN_STAGE_WALK"; return ACN_ERR_ARG; }
+    if( a->flags & ~( ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES ) ) { *msg = "unknown acn_stage_walk_args.flags bits"; return ACN_ERR_ARG; }
+    if( a->camera ? a->in != nullptr : a->pos_xy != nullptr ) { *msg = "both input forms: rays and the camera form"; return ACN_ERR_ARG; }
+    if( !a->camera && !a->in ) { *msg = "neither input form: null argument in without the camera form"; return ACN_ERR_ARG; }
+    if( a->n == 0 || a->n > ACN_STAGE_MAX_RECORDS ) { *msg = "n " + std::to_string( a->n ) + " is outside 1 .. 2^20 records"; return ACN_ERR_ARG; }
+    if( a->passes == 0 || a->passes > ACN_MAX_WALK_PASSES ) { *msg = "passes " + std::to_string( a->passes ) + " are outside 1 .. 32"; return ACN_ERR_ARG; }
+    if( a->stack_cap == 0 || a->stack_cap > ACN_STAGE_WALK_MAX_STACK ) { *msg = "stack_cap " + std::to_string( a->stack_cap ) + " is outside 1 .. 4096"; return ACN_ERR_ARG; }
+    if( a->stack_use > a->stack_cap ) { *msg = "stack_use " + std::to_string( a->stack_use ) + " is above stack_cap"; return ACN_ERR_ARG; }
+    if( a->fetch < 64u || a->fetch > ACN_STAGE_MAX_RECORDS ) { *msg = "fetch " + std::to_string( a->fetch ) + " is outside 64 .. 2^20"; return ACN_ERR_ARG; }
+    if( a->grid > ACN_STAGE_MAX_GRID ) { *msg = "workgroups (grid) " + std::to_string( a->grid ) + " are above 64"; return ACN_ERR_ARG; }
+    if( a->room_rays < a->n ) { *msg = "room_rays " + std::to_string( a->room_rays ) + " is below n"; return ACN_ERR_ARG; }
+    if( !a->camera )
+    {
+        const acn_stage_raytask* r = ( const acn_stage_raytask* )a->in;
+        for( uint32_t i = 0; i < a->n; i++ )
+        {
+            const std::string who = "ray " + std::to_string( i );
+            if( r[ i ].pixel == ACN_STAGE_DEAD ) continue;
+            if( r[ i ].pixel >= a->n ) { *msg = who + ": pixel " + std::to_string( r[ i ].pixel ) + " is not below n"; return ACN_ERR_ARG; }
+            if( !acn_stage_finite_ray( r[ i ].p, r[ i ].d ) ) { *msg = who + ": the ray is not finite"; return ACN_ERR_ARG; }
+            if( !( std::isfinite( r[ i ].T.x ) && std::isfinite( r[ i ].T.y ) && std::isfinite( r[ i ].T.z ) ) ) { *msg = who + ": T is not finite"; return ACN_ERR_ARG; }
+            if( r[ i ].d.x == 0.0 && r[ i ].d.y == 0.0 && r[ i ].d.z == 0.0 ) { *msg = who + ": the direction has no length"; return ACN_ERR_ARG; }
+            if( r[ i ].depth < 1 || r[ i ].depth > ACN_STAGE_MAX_DEPTH ) { *msg = who + ": depth " + std::to_string( r[ i ].depth ) + " is outside 1 .. 2^20"; return ACN_ERR_ARG; }
+            /* (a NaN intensity fails the first test) */
+            if( !std::isfinite( r[ i ].intensity ) || r[ i ].intensity < sc.trace_min_intensity )
+            { *msg = who + ": the intensity is not finite or below trace_min_intensity (such a ray is a probe, never a queued ray)"; return ACN_ERR_ARG; }
+        }
+    }
+    acn_stage_caps c;
+    memset( &c, 0, sizeof( c ) );
+    c.grid = a->grid ? a->grid : ( acn_stage_walk_slots( a ) + 255u ) / 256u;
+    c.grid = c.grid > ACN_STAGE_MAX_GRID ? ACN_STAGE_MAX_GRID : c.grid;
+    c.chunk = ACN_QCHUNK;
+    const uint64_t slack = ( uint64_t )c.grid * 4u * c.chunk;
+    const uint64_t rays = ( uint64_t )a->room_rays + slack, tasks = ( uint64_t )a->room_rays + slack * a->passes, hs = 3ull * a->room_rays + slack * a->passes;
+    for( uint64_t v : { tasks, rays, hs } )
+        if( v > ACN_STAGE_MAX_CAP ) { *msg = "room_rays asks for " + std::to_string( v ) + " records of one queue: above 2^26"; return ACN_ERR_ARG; }
+    c.cap_tasks = ( uint32_t )tasks; c.cap_rays = ( uint32_t )rays; c.cap_hard_shadow = ( uint32_t )hs;
     *caps = c;
     return ACN_OK;
 }

@@ -993,14 +993,17 @@ class Handle:
     # words of the level's counter block (acn_counts.h)
     QC = {"tasks": 0, "class0": 1, "children": 5, "flags": 6, "hard_shadow": 7, "hard_path": 8, "walk_rays": 12, "s_hard_shadow": 13,
           "s_hard_path": 14, "s_children": 15, "s_tasks": 16, "s_probes": 19, "dead_t": 28, "dead_c": 29, "dead_hp": 30, "dead_r": 31, "gen0": 32}
+    # the words only the walk writes: QS_WALK_STEPS, QS_PRIVATE_RAYS, QC_CUR_GEN + 0 (the work-fetch cursor of pass 0)
+    QC_WALK = {"walk_steps": 17, "private_rays": 18, "cur_gen0": 65}
 
     def stage_info(self):
-        """Sizes of the five records, words of a counter block, DevScene.class0_min, nodes, lights and the handle's kernel variant."""
+        """Sizes of the five records, words of a counter block, DevScene.class0_min, nodes, lights and the handle's kernel variant
+        (prune programs, leaf lights, the node array staged in LDS)."""
         w = np.zeros(abi.ACN_STAGE_INFO_WORDS, dtype=np.uint32)
         check(hip.acn_stage_info(self.h, w.ctypes.data, w.size), "acn_stage_info")
         names = ("ray", "task", "hit", "hard_shadow", "hard_path")
         info = {"sizeof": {k: int(w[i]) for i, k in enumerate(names)}, "counter_words": int(w[5]), "class0_min": int(w[6]),
-                "nodes": int(w[7]), "lights": int(w[8]), "prune": bool(w[9] & 1), "leaf_lights": bool(w[9] & 2)}
+                "nodes": int(w[7]), "lights": int(w[8]), "prune": bool(w[9] & 1), "leaf_lights": bool(w[9] & 2), "lds_nodes": bool(w[9] & 4)}
         return info
 
     def run_stage(self, stage, records, index=None, cls=0, shard_rank=0, shard_world=1, prune=True, leaf_lights=True, emit_terms=True, grid=0):
@@ -1066,6 +1069,54 @@ class Handle:
             res["rays"] = live(bufs["rays"], c[self.QC["gen0"]])
             res["idx"] = [l[:c[self.QC["class0"] + k]][l[:c[self.QC["class0"] + k]] != self.STAGE_INVALID] for k, l in enumerate(idx)]
         return res
+
+    def run_stage_walk(self, rays=None, pos_xy=None, n=None, first_pixel=0, room_rays=None, passes=1, private_limit=0xFFFFFFFF, stack_cap=512,
+                       stack_use=0, fetch=64, grid=0, prune=True, lds=True, emit_terms=True, flags=None):
+        """The specular walk of one path level alone (acn_run_stage_walk): `passes` launches of k_walk as the pipeline runner enqueues
+        them.  rays: "ray" records (pixel = own index, or STAGE_INVALID), generation 0 of the level; or the camera form: pos_xy [n, 2],
+        or n pixel centres of the raster from first_pixel.  room_rays: the rays the walk traces in all, by the caller's model.  Returns
+        tasks, idx (four lists), hard_shadow (the probes), counts, flags, accum [n, 3] int64, and rays: what the last pass left for a
+        generation no launch reads (dead slots taken out), and gen: the generation marks QC_GEN + 0 .. passes."""
+        info = self.stage_info()
+        R = self.STAGE_RECORDS
+        for k, dt in R.items():
+            assert dt.itemsize == info["sizeof"][k], (k, dt.itemsize, info["sizeof"][k])
+        a = abi.StageWalkArgs()
+        a.stage = abi.ACN_STAGE_WALK
+        a.flags = ((0 if prune else abi.ACN_STAGE_NO_PRUNE) | (0 if lds else abi.ACN_STAGE_GLOBAL_NODES)
+                   | (0 if emit_terms else abi.ACN_STAGE_NO_EMIT_TERMS)) if flags is None else int(flags)
+        rec = pos = None
+        if rays is not None:
+            rec = np.ascontiguousarray(rays, dtype=R["ray"])
+            a.n, a.input = rec.shape[0], rec.ctypes.data
+        if pos_xy is not None:
+            pos = np.ascontiguousarray(pos_xy, dtype=np.float64).reshape(-1, 2)
+            a.pos_xy = pos.ctypes.data
+        if rays is None:
+            a.n = pos.shape[0] if pos is not None else int(n or 0)
+        a.camera = 1 if (pos_xy is not None or n is not None) else 0
+        a.first_pixel = int(first_pixel)
+        a.passes, a.private_limit, a.stack_cap, a.stack_use, a.fetch, a.grid = int(passes), int(private_limit), int(stack_cap), int(stack_use), int(fetch), int(grid)
+        a.room_rays = int(a.n if room_rays is None else room_rays)
+        caps = abi.StageCaps()
+        check(hip.acn_stage_walk_plan(self.h, C.byref(a), C.byref(caps)), "acn_stage_walk_plan")
+        bufs = {"counts": np.zeros(info["counter_words"], dtype=np.uint32), "accum": np.zeros((a.n, 3), dtype=np.int64),
+                "hard_shadow": np.zeros(caps.cap_hard_shadow, dtype=R["hard_shadow"]), "tasks": np.zeros(caps.cap_tasks, dtype=R["task"]),
+                "rays": np.zeros(caps.cap_rays, dtype=R["ray"])}
+        idx = [np.zeros(caps.cap_tasks, dtype=np.uint32) for _ in range(4)]
+        o = abi.StageOut()
+        for k, b in bufs.items():
+            setattr(o, k, b.ctypes.data)
+        for k in range(4):
+            o.idx[k] = idx[k].ctypes.data
+        check(hip.acn_run_stage_walk(self.h, C.byref(a), C.byref(o)), "acn_run_stage_walk")
+        c = bufs["counts"]
+        live = lambda q, mark: q[:mark][q["pixel"][:mark] != self.STAGE_INVALID]   # noqa: E731
+        gen = c[self.QC["gen0"]:self.QC["gen0"] + a.passes + 1].copy()
+        return {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps, "gen": gen,
+                "hard_shadow": live(bufs["hard_shadow"], c[self.QC["hard_shadow"]]), "tasks": bufs["tasks"][:c[self.QC["tasks"]]],
+                "rays": live(bufs["rays"], gen[a.passes]),
+                "idx": [l[:c[self.QC["class0"] + k]][l[:c[self.QC["class0"] + k]] != self.STAGE_INVALID] for k, l in enumerate(idx)]}
 
 
 class Surface:

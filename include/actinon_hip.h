@@ -1096,11 +1096,57 @@ typedef struct acn_stage_out
     uint64_t* accum;                    /* [ n ][ 3 ] */
 } acn_stage_out;
 /* out[ 0 .. 4 ] sizeof RayTask, DTask, HitRec, HardShadow, HardPath; [ 5 ] words of a counter block; [ 6 ] DevScene.class0_min; [ 7 ] nodes;
- * [ 8 ] lights; [ 9 ] bit 0 prune, bit 1 leaf_lights: the kernel variant of the handle.  n <= 10 */
+ * [ 8 ] lights; [ 9 ] bit 0 prune, bit 1 leaf_lights, bit 2 the node array is staged in LDS: the kernel variant of the handle.  n <= 10 */
 #define ACN_STAGE_INFO_WORDS 10
 int acn_stage_info( acn_scene_handle* h, uint32_t* out, int n );
 int acn_stage_plan( acn_scene_handle* h, const acn_stage_args* args, acn_stage_caps* caps );   /* no GPU work */
 int acn_run_stage( acn_scene_handle* h, const acn_stage_args* args, const acn_stage_out* out );
+
+/* Test hook: the specular walk of one path level alone (csrc/k_stage.hip): the passes of k_walk in the loop of the pipeline runner,
+ *     for pass in 0 .. passes - 1:  acn_launch_walk( pass, last = pass + 1 == passes, ... )
+ * on queues the call owns.  No device code of its own, and the arrangement of the walk is the caller's: how many launches, from which
+ * size of a generation on its rays are finished on the waves' private stacks (private_limit), how many slots of a stack every launch
+ * but the last uses (stack_use), the fetch batch and the grid.  The arrangement decides where a ray is traced, never what it produces.
+ * Input, one of two forms:
+ *   rays    in = RayTask[ n ]: generation 0 of the level as k_shade_hits or the ray seeding leaves it, dead slots (pixel 0xFFFFFFFF,
+ *           of which nothing else is read) included; every other pixel is < n.
+ *   camera  camera != 0, in null: n sample positions pos_xy[ n ][ 2 ], or (pos_xy null) the pixel centres first_pixel + i of the
+ *           scene's raster, in the order of work of a render call (tiles of 256 positions; the launch covers every slot of the last
+ *           tile, so slots past position n - 1 are met as the renderer meets them); position i is pixel i.
+ * Written (acn_stage_out; a null output is not fetched): tasks, idx[ 0 .. 3 ], hard_shadow (the probes: k_hard_shadow is not run),
+ * counts (the whole block: the generation marks QC_GEN + g and the statistics the planner reads), accum [ n ][ 3 ] (the walk's own
+ * terms: background of a miss, emission), and rays: what the last pass left in the queue of generation `passes`, up to the mark
+ * QC_GEN + passes -- the generation no launch reads.  Rays there raise no device flag (declaring the chunk lost is acn_read_chunk's).
+ * room_rays: the rays the caller's model says the walk traces, all generations together (a ray has up to three children, so the
+ * input does not bound the output); acn_stage_walk_plan sizes each ray buffer for room_rays, the tasks for room_rays and the probes
+ * for 3 * room_rays records, each plus one reservation per wave and launch that appends to the queue (acn_stage_caps; cap_children
+ * and cap_hard_path are 0, chunk is the reservation).  A raised overflow flag is ACN_ERR_DEVICE.
+ * ACN_ERR_ARG before anything is launched, acn_last_error set: a null handle, args or caps; stage not ACN_STAGE_WALK; a flag other
+ * than ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_EMIT_TERMS, ACN_STAGE_GLOBAL_NODES (the node array read from global memory on a handle that
+ * stages it in LDS, as ACN_QUERY_GLOBAL_NODES); both input forms or neither; n outside 1 .. ACN_STAGE_MAX_RECORDS; passes outside
+ * 1 .. ACN_MAX_WALK_PASSES (32); stack_cap outside 1 .. ACN_STAGE_WALK_MAX_STACK; stack_use above stack_cap (0: stack_cap); fetch
+ * outside 64 .. ACN_STAGE_MAX_RECORDS; grid above 64 (0: one workgroup per 256 input slots); room_rays below n or so large that a
+ * queue would exceed 2^26 records; a live ray whose pixel is not < n, whose origin, direction or T is not finite, whose direction
+ * has no length, whose depth is outside 1 .. ACN_STAGE_MAX_DEPTH or whose intensity is not finite or below the scene's
+ * trace_min_intensity (the production queue never holds such a ray: spawn_child turns it into a probe). */
+#define ACN_STAGE_WALK 4u                 /* the stage of acn_run_stage_walk (acn_run_stage itself has no stage 4) */
+#define ACN_STAGE_GLOBAL_NODES 8u
+#define ACN_STAGE_WALK_MAX_STACK 4096u
+typedef struct acn_stage_walk_args
+{
+    uint32_t stage, flags;              /* ACN_STAGE_WALK; ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES */
+    uint32_t n;                         /* input rays (dead slots included), or positions of the camera form */
+    uint32_t camera;                    /* != 0: the camera form */
+    uint32_t passes, private_limit;     /* launches of k_walk; generations of at most private_limit rays run on private stacks */
+    uint32_t stack_cap, stack_use;      /* slots of a wave's stack; of them used by every launch but the last (0: all) */
+    uint32_t fetch, grid;               /* input rays a wave reserves per cursor atomic; workgroups (0: by n) */
+    uint32_t room_rays, pad;
+    const void* in;                     /* RayTask[ n ] */
+    const double* pos_xy;               /* camera form: [ n ][ 2 ], or null: the raster from first_pixel */
+    uint64_t first_pixel;
+} acn_stage_walk_args;
+int acn_stage_walk_plan( acn_scene_handle* h, const acn_stage_walk_args* args, acn_stage_caps* caps );   /* no GPU work */
+int acn_run_stage_walk( acn_scene_handle* h, const acn_stage_walk_args* args, const acn_stage_out* out );
 
 const char* acn_last_error( void );
 

@@ -1377,3 +1377,134 @@ def stage_light_sphere_points(lp, lr):
     return {"on_light": np.array([lp[0] + lr, lp[1], lp[2]]),
             "off_light": np.array([lp[0] + lr, lp[1] + 2.0 ** -27, lp[2]]),
             "in_light": np.array([lp[0] + (lr - 2.0 ** -53), lp[1] + np.sqrt(3 * 2.0 ** -55), lp[2]])}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the input of the walk stage (tests/test_gpu_stage_walk.py, tests/test_stage_walk_cpu.py): "ray" records, pixel = index
+
+WALK_DEPTHS = (1, 2, 10, 11, 12)     # depth 1: every child is a probe; 10 | 11: the boundary of the path loop
+
+
+def _walk_records(dtype, rays, T, intensity, depth):
+    out = np.zeros(len(rays), dtype=dtype)
+    out["p"], out["d"], out["T"], out["intensity"], out["depth"] = rays[:, :3], rays[:, 3:], T, intensity, depth
+    return out
+
+
+def _walk_with_dead_slots(rng, recs):
+    """5 % dead slots put in at random places (no ray is lost to them), pixel = index, a total that is a multiple of neither 64 nor 256"""
+    n_dead = max(len(recs) // 20, 1)
+    while (len(recs) + n_dead) % 64 == 0:
+        n_dead += 1
+    out = np.zeros(len(recs) + n_dead, dtype=recs.dtype)
+    dead = np.zeros(len(out), dtype=bool)
+    dead[rng.choice(len(out), n_dead, replace=False)] = True
+    out[~dead] = recs
+    # what a dead slot holds is not read: values the checks of the seam would refuse
+    out["depth"][dead], out["intensity"][dead], out["p"][dead] = -7, np.nan, np.inf
+    out["pixel"] = np.arange(len(out))
+    out["pixel"][dead] = 0xFFFFFFFF
+    return out
+
+
+def walk_camera_rays(prm, pos=None):
+    """the rays of sample positions (default: the scene's raster) in plain numpy: the input of the model and of the device alike"""
+    import surface_model
+    if pos is None:
+        pos = A.main_pass_positions(prm.image_width, prm.image_height)
+    return surface_model.camera_rays(prm, np.asarray(pos, dtype=np.float64))
+
+
+def walk_rays_stage_scene(flat, node, dtype, seed=41):
+    """Scene A: the camera rays of its raster and 180 rays started inside the water / glass / core nest, with a random throughput in
+    [ 0.2, 1 ]; a copy of every eighth of them at each depth of WALK_DEPTHS, and at each intensity trace_min_intensity, the double
+    above it and 0.5; dead slots."""
+    rng = np.random.default_rng(seed)
+    prm = flat.params
+    tmin, depth = prm.trace_min_intensity, int(prm.trace_depth)
+    rays = [walk_camera_rays(prm)]
+    gc = np.array(list(flat.node(node["glass"]).pos))
+    for rad in (0.1, 0.5, 1.0):                       # inside the core, the glass, the water
+        o = gc + random_dirs(rng, 60) * rad
+        rays.append(np.concatenate([o, random_dirs(rng, 60)], axis=1))
+    rays = np.concatenate(rays)
+    base = _walk_records(dtype, rays, rng.uniform(0.2, 1.0, (len(rays), 3)), 1.0, depth)
+    parts = [base]
+    for d in WALK_DEPTHS:
+        c = base[::8].copy()
+        c["depth"] = d
+        parts.append(c)
+    for i in (tmin, np.nextafter(tmin, 1.0), 0.5):
+        c = base[::8].copy()
+        c["intensity"] = i
+        parts.append(c)
+    return _walk_with_dead_slots(rng, np.concatenate(parts))
+
+
+def walk_scene_wine_glass():
+    sc = A.Scene.build("wine_glass", image_width=48, image_height=27, path_samples=64, direct_samples=50)
+    return sc, sc.flatten()
+
+
+def walk_rays_wine_glass(flat, dtype, seed=42):
+    """the wine glass: its camera rays as the pipeline starts them (T = 1, intensity 1, the scene's trace_depth), dead slots"""
+    rng = np.random.default_rng(seed)
+    prm = flat.params
+    rays = walk_camera_rays(prm)
+    return _walk_with_dead_slots(rng, _walk_records(dtype, rays, 1.0, 1.0, int(prm.trace_depth)))
+
+
+def walk_small_scene(diffuse_floor=True, **params):
+    """A scene of a dozen nodes whose matter root holds a generic compound (a glass lens cut from two spheres, and a mirror sphere
+    beside it): small enough that the upload stages its node array in LDS, and with ACN_PRUNE_MIN=1 the lens gets an interval-prune
+    program -- the handle then runs k_walk< LDS, PRUNE >.  Beside the compound a mirror sphere, a sphere light, a sky that rays reach;
+    diffuse_floor: a diffuse plane under it all (without it no surface of the scene has a diffuse block, and the picture is the sum
+    of the walk's own terms)."""
+    sc = A.Scene()
+    sc.set(image_width=24, image_height=16, gamma=1.0, trace_depth=12, trace_min_intensity=0.01, direct_samples=4, path_samples=2,
+           max_path_length=30.0, camera_position=(0.3, -7, 1.5), camera_view_direction=(0, 7, -0.8), camera_top_direction=(0, 0, 1),
+           camera_focal_length=2.2, background_color=(0.3, 0.35, 0.4))
+    sc.set(**params)
+
+    def ball(r, at, material):
+        o = host.acn_obj_sphere_s_create(float(r))
+        host.acn_obj_set_material(o, material)
+        host.acn_obj_move(o, A.v3(*at))
+        return o
+
+    light = host.acn_obj_sphere_s_create(0.5)
+    host.acn_obj_set_radiance(light, 20.0)
+    host.acn_obj_move(light, A.v3(-1.5, -1.0, 3.5))
+    sc.push(light); host.acn_obj_discard(light)
+    lens = _pair_inside(ball(1.0, (0.0, 0.0, 1.0), b"glass"), ball(1.0, (0.7, 0.0, 1.0), b"glass"))
+    host.acn_obj_set_material(lens, b"glass")
+    cmp = host.acn_compound_s_create()
+    host.acn_compound_s_push(cmp, lens)
+    s2 = ball(0.4, (-0.9, 0.2, 0.6), b"perfect_mirror")
+    host.acn_compound_s_push(cmp, s2)
+    host.acn_obj_set_envelope(cmp, A.v3(0.0, 0.0, 1.0), 2.5)
+    sc.push(cmp)
+    for o in (lens, s2, cmp):
+        host.acn_obj_discard(o)
+    o = ball(0.7, (2.0, 1.0, 0.7), b"perfect_mirror")
+    sc.push(o); host.acn_obj_discard(o)
+    o = ball(0.5, (-2.2, 0.5, 0.5), b"water")
+    sc.push(o); host.acn_obj_discard(o)
+    if diffuse_floor:
+        o = host.acn_obj_plane_s_create()
+        host.acn_obj_set_material(o, b"diffuse")
+        host.acn_obj_set_color(o, A.v3(0.8, 0.7, 0.6))
+        sc.push(o); host.acn_obj_discard(o)
+    return sc, sc.flatten()
+
+
+def walk_rays_small_scene(flat, dtype, seed=43):
+    """the small scene: its camera rays, and as many aimed at the lens and the mirrors from all around; dead slots"""
+    rng = np.random.default_rng(seed)
+    prm = flat.params
+    cam = walk_camera_rays(prm)
+    o = np.array([0.3, 0.0, 1.0]) + random_dirs(rng, len(cam)) * 4.0
+    o[:, 2] = np.abs(o[:, 2]) + 0.1
+    t = np.array([0.3, 0.0, 0.9]) + rng.uniform(-1.2, 1.2, (len(cam), 3))
+    rays = np.concatenate([cam, np.concatenate([o, unit(t - o)], axis=1)])
+    return _walk_with_dead_slots(rng, _walk_records(dtype, rays, rng.uniform(0.2, 1.0, (len(rays), 3)), 1.0, int(prm.trace_depth)))
