@@ -40,7 +40,8 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_sc
                "acn_lens_layers_reduce", "acn_lens_layers_reduce_dev", "acn_render_lens_layers", "acn_render_lens_layers_dev",
                "acn_render_lens_layers_main_pass_dev", "acn_denoise_layers", "acn_denoise_layers_dev",
                "acn_lens_layers_merge", "acn_lens_layers_merge_dev", "acn_lens_layers_resolve_dev",
-               "acn_project_points", "acn_project_points_dev", "acn_reproject", "acn_reproject_dev"]
+               "acn_project_points", "acn_project_points_dev", "acn_reproject", "acn_reproject_dev",
+               "acn_reproject_moving", "acn_reproject_moving_dev", "acn_motion_from_scenes"]
 # symbols declared by include/acn_scene.h
 HOST_SYMBOLS = ["acn_rotx", "acn_roty", "acn_rotz", "acn_obj_plane_s_create", "acn_obj_sphere_s_create",
                 "acn_obj_squaroid_s_create_squaroid", "acn_obj_squaroid_s_create_ellipsoid",
@@ -118,6 +119,9 @@ hip.acn_project_points.argtypes = [vp, vp, C.c_size_t, vp, vp]
 hip.acn_project_points_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, P(abi.RenderOpts)]
 for _n in ["acn_reproject", "acn_reproject_dev"]:
     getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, P(abi.Params), vp, vp, P(abi.ReprojectParams), vp, vp, P(abi.RenderOpts)]
+for _n in ["acn_reproject_moving", "acn_reproject_moving_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, P(abi.Params), vp, vp, vp, C.c_size_t, P(abi.ReprojectParams), vp, vp, P(abi.RenderOpts)]
+hip.acn_motion_from_scenes.argtypes = [P(abi.FlatScene), P(abi.FlatScene), C.c_double, vp, P(abi.MotionReport)]
 hip.acn_select_above_dev.argtypes =[vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, vp, P(C.c_uint64), P(abi.RenderOpts)]
 hip.acn_select_above.argtypes = [vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, P(C.c_uint64)]
 hip.acn_key_histogram_dev.argtypes = [vp, vp, C.c_size_t, vp, P(abi.RenderOpts)]

@@ -41,6 +41,10 @@ ACN_REPROJECT_DEFAULT_REJECT_KINDS = ACN_SURF_CHROMATIC | ACN_SURF_FRESNEL | ACN
 ACN_REPROJECT_DEFAULT_MAX_HOPS = 0
 ACN_REPROJECT_DEFAULT_NORMAL_MIN, ACN_REPROJECT_DEFAULT_PLANE_TOLERANCE, ACN_REPROJECT_DEFAULT_MAX_HISTORY = 0.9, 0.01, 32.0
 
+# reprojection through moving objects (acn_reproject_moving, acn_motion_from_scenes): doubles per row of the motion table, the states
+ACN_MOTION_STRIDE = 16
+ACN_MOTION_REST, ACN_MOTION_MOVED, ACN_MOTION_NONE = 0.0, 1.0, 2.0
+
 # replacing the scene of a live handle (acn_scene_replace, acn_scene_info): the flag, the slots of the counters
 ACN_REPLACE_FORGET = 1
 ACN_INFO_N = 8
@@ -108,6 +112,10 @@ class SelectParams(C.Structure):
 class ReprojectParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reject_kinds", C.c_uint32), ("max_hops", C.c_int32),
                 ("normal_min", C.c_double), ("plane_tolerance", C.c_double), ("max_history", C.c_double)]
+
+
+class MotionReport(C.Structure):
+    _fields_ = [("n_rest", C.c_uint32), ("n_moved", C.c_uint32), ("n_none", C.c_uint32), ("same_shape", C.c_uint32)]
 
 
 # the stage-runner test seam (acn_run_stage): stages, option bits, limits

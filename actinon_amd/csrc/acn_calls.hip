@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection, and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points.
  * The lens calls that cut their positions into slices share one loop, lens_slices; a host-buffer form is a HostCall (acn_handle.h). */
@@ -13,6 +13,7 @@
 #include "acn_lenssurf_host.h"
 #include "acn_layers_host.h"
 #include "acn_reproject_host.h"
+#include "acn_motion_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* kernels */
@@ -921,6 +922,62 @@ extern "C" int acn_reproject( acn_scene_handle* h, const double* cur_surface, si
     void* d_motion = hc.out( out_motion, sizeof( double ) * 2 * n );
     c.opts.stream = nullptr;
     return hc.run( [ & ] { return acn_reproject_dev( h, d_cur, n, prev_params, d_ps, d_pt, prm, d_out, d_motion, &c.opts ); } );
+}
+
+/* ---- reprojection through moving objects (k_reproject.hip; the table's checks and acn_motion_from_scenes: acn_motion_host.h) ---- */
+static int reproject_moving_check( const acn_scene_handle* h, const void* cur_surface, size_t n, const acn_params* prev_params, const void* prev_surface,
+                                   const void* prev_stats, const void* motion, size_t n_motion, const acn_reproject_params* prm,
+                                   const void* out_stats, const void* out_motion, const acn_render_opts& opts, ReprojectSetup* su )
+{
+    int st = reproject_check( h, cur_surface, n, prev_params, prev_surface, prev_stats, prm, out_stats, out_motion, opts, su );
+    if( st != ACN_OK ) return st;
+    std::string msg;
+    if( acn_motion_table_check( motion, n_motion, n, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    return ACN_OK;
+}
+
+extern "C" int acn_reproject_moving_dev( acn_scene_handle* h, const void* d_cur_surface, size_t n, const acn_params* prev_params,
+                                         const void* d_prev_surface, const void* d_prev_stats, const void* d_motion, size_t n_motion,
+                                         const acn_reproject_params* prm, void* d_out_stats, void* d_out_motion, const acn_render_opts* opts )
+{
+    Call c( opts );
+    ReprojectSetup su;
+    int st = reproject_moving_check( h, d_cur_surface, n, prev_params, d_prev_surface, d_prev_stats, d_motion, n_motion, prm, d_out_stats, d_out_motion,
+                                     c.opts, &su );
+    if( st != ACN_OK || n == 0 ) return st;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    acn_launch_reproject_moving( ( const double* )d_cur_surface, n, *prev_params, ( const double* )d_prev_surface, ( const double* )d_prev_stats,
+                                 ( const double* )d_motion, n_motion, su, ( double* )d_out_stats, ( double* )d_out_motion, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_reproject_moving( acn_scene_handle* h, const double* cur_surface, size_t n, const acn_params* prev_params, const double* prev_surface,
+                                     const double* prev_stats, const double* motion, size_t n_motion, const acn_reproject_params* prm,
+                                     double* out_stats, double* out_motion, const acn_render_opts* opts )
+{
+    Call c( opts );
+    ReprojectSetup su;
+    int st = reproject_moving_check( h, cur_surface, n, prev_params, prev_surface, prev_stats, motion, n_motion, prm, out_stats, out_motion, c.opts, &su );
+    if( st != ACN_OK || n == 0 ) return st;
+    const size_t prev_n = ( size_t )( prev_params->image_width * prev_params->image_height );
+    HostCall hc( h );
+    void* d_cur = hc.in( cur_surface, sizeof( double ) * ACN_SURF_STRIDE * n );
+    void* d_ps = hc.in( prev_surface, sizeof( double ) * ACN_SURF_STRIDE * prev_n );
+    void* d_pt = hc.in( prev_stats, sizeof( double ) * ACN_STATS_STRIDE * prev_n );
+    void* d_table = hc.in( motion, sizeof( double ) * ACN_MOTION_STRIDE * n_motion );
+    void* d_out = hc.out( out_stats, sizeof( double ) * ACN_STATS_STRIDE * n );
+    void* d_motion = hc.out( out_motion, sizeof( double ) * 2 * n );
+    c.opts.stream = nullptr;
+    return hc.run( [ & ] { return acn_reproject_moving_dev( h, d_cur, n, prev_params, d_ps, d_pt, d_table, n_motion, prm, d_out, d_motion, &c.opts ); } );
+}
+
+extern "C" int acn_motion_from_scenes( const acn_flat_scene* prev, const acn_flat_scene* cur, double moved_max_history, double* out_table,
+                                       acn_motion_report* report )
+{
+    std::string msg;
+    const int st = acn_motion_from_scenes_impl( prev, cur, moved_max_history, out_table, report, &msg );
+    return st == ACN_OK ? ACN_OK : fail( st, msg );
 }
 
 /* ---- selecting positions by a key (k_select.hip; the checks and the host arithmetic: acn_select_host.h) ---- */

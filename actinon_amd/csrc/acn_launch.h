@@ -140,6 +140,10 @@ struct ReprojectSetup { uint32_t reject_kinds; int32_t max_hops; double normal_m
 void acn_launch_project_points( const DevScene& sc, const double* points, size_t n, double* out_pos_xy, double* out_depth, hipStream_t stream );
 void acn_launch_reproject( const double* cur_surface, size_t n, const acn_params& prev, const double* prev_surface, const double* prev_stats,
                            const ReprojectSetup& su, double* out_stats, double* out_motion, hipStream_t stream );
+/* acn_reproject_moving*: the same with motion [ n_motion ][ ACN_MOTION_STRIDE ], 16-byte aligned, n_motion >= 1: one row per node index */
+void acn_launch_reproject_moving( const double* cur_surface, size_t n, const acn_params& prev, const double* prev_surface, const double* prev_stats,
+                                  const double* motion, uint64_t n_motion, const ReprojectSetup& su, double* out_stats, double* out_motion,
+                                  hipStream_t stream );
 
 /* the filter of acn_denoise_layers (k_denoise_layers.hip): stats [ 3 ][ n ][ ACN_STATS_STRIDE ], surf [ 2 ][ n ][ ACN_SURF_STRIDE ], both 16-byte
  * aligned; the parameters are final values; scratch: ACN_DENOISE_LAYERS_SCRATCH_PER_PIXEL bytes per pixel, 128-byte aligned */

@@ -863,6 +863,10 @@ class Handle:
         with, prev_surface and prev_stats the Surface and LensStats (or records) of its whole raster -> ( LensStats over [n,8], motion
         [n,2]: the position on the previous raster, NaN where there is none ).  params: reject_kinds, max_hops, normal_min,
         plane_tolerance, max_history (Handle.reproject_params).  Merge the result with the current frame's statistics by lens_stats_merge."""
+        return self._reproject_host(cur_surface, prev_params, prev_surface, prev_stats, None, params)
+
+    def _reproject_host(self, cur_surface, prev_params, prev_surface, prev_stats, motion, params):
+        """the host form of acn_reproject, or with a motion table of acn_reproject_moving"""
         cur = np.ascontiguousarray(cur_surface.raw if isinstance(cur_surface, Surface) else cur_surface, dtype=np.float64).reshape(-1, abi.ACN_SURF_STRIDE)
         ps = np.ascontiguousarray(prev_surface.raw if isinstance(prev_surface, Surface) else prev_surface, dtype=np.float64).reshape(-1, abi.ACN_SURF_STRIDE)
         pt = np.ascontiguousarray(prev_stats.raw if isinstance(prev_stats, LensStats) else prev_stats, dtype=np.float64).reshape(-1, abi.ACN_STATS_STRIDE)
@@ -870,12 +874,17 @@ class Handle:
         if len(ps) != pixels or len(pt) != pixels:
             raise ValueError(f"the previous raster has {pixels} pixels: got {len(ps)} surface and {len(pt)} statistics records")
         out = np.empty((cur.shape[0], abi.ACN_STATS_STRIDE), dtype=np.float64)
-        motion = np.empty((cur.shape[0], 2), dtype=np.float64)
+        out_motion = np.empty((cur.shape[0], 2), dtype=np.float64)
         p = self.reproject_params(**params)
         o = self._plain_opts(False, None)
-        check(hip.acn_reproject(self.h, cur.ctypes.data, cur.shape[0], C.byref(prev_params), ps.ctypes.data, pt.ctypes.data, C.byref(p),
-                                out.ctypes.data, motion.ctypes.data, C.byref(o)), "acn_reproject")
-        return LensStats(out, self), motion
+        if motion is None:
+            check(hip.acn_reproject(self.h, cur.ctypes.data, cur.shape[0], C.byref(prev_params), ps.ctypes.data, pt.ctypes.data, C.byref(p),
+                                    out.ctypes.data, out_motion.ctypes.data, C.byref(o)), "acn_reproject")
+        else:
+            table = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, abi.ACN_MOTION_STRIDE)
+            check(hip.acn_reproject_moving(self.h, cur.ctypes.data, cur.shape[0], C.byref(prev_params), ps.ctypes.data, pt.ctypes.data, table.ctypes.data,
+                                           table.shape[0], C.byref(p), out.ctypes.data, out_motion.ctypes.data, C.byref(o)), "acn_reproject_moving")
+        return LensStats(out, self), out_motion
 
     def reproject_dev(self, d_cur_surface_ptr, n, prev_params, d_prev_surface_ptr, d_prev_stats_ptr, d_out_stats_ptr, d_out_motion_ptr=None,
                       stream=None, **params):
@@ -885,6 +894,21 @@ class Handle:
         o = self._plain_opts(False, stream)
         check(hip.acn_reproject_dev(self.h, d_cur_surface_ptr, n, C.byref(prev_params), d_prev_surface_ptr, d_prev_stats_ptr, C.byref(p),
                                     d_out_stats_ptr, d_out_motion_ptr, C.byref(o)), "acn_reproject_dev")
+
+    # reprojection through moving objects (acn_reproject_moving): a motion table, one row per node index (motion_from_scenes)
+    def reproject_moving(self, cur_surface, prev_params, prev_surface, prev_stats, motion, **params):
+        """reproject() with a motion table [n_nodes,16] (motion_from_scenes, or hand-made rows: include/actinon_hip.h): the history of
+        a point on a moved object is taken where that point was one frame ago -> ( LensStats over [n,8], motion [n,2] )."""
+        return self._reproject_host(cur_surface, prev_params, prev_surface, prev_stats, motion, params)
+
+    def reproject_moving_dev(self, d_cur_surface_ptr, n, prev_params, d_prev_surface_ptr, d_prev_stats_ptr, d_motion_ptr, n_motion, d_out_stats_ptr,
+                             d_out_motion_ptr=None, stream=None, **params):
+        """Device buffers, the table [n_motion,16] float64 among them, all 16-byte aligned; enqueued on `stream` without a synchronisation
+        (None: the handle's stream, synchronous)."""
+        p = self.reproject_params(**params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_reproject_moving_dev(self.h, d_cur_surface_ptr, n, C.byref(prev_params), d_prev_surface_ptr, d_prev_stats_ptr, d_motion_ptr,
+                                           n_motion, C.byref(p), d_out_stats_ptr, d_out_motion_ptr, C.byref(o)), "acn_reproject_moving_dev")
 
     # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
     @staticmethod
@@ -1201,6 +1225,17 @@ def key_hist_threshold(hist, budget):
     if hh.shape[0] != abi.ACN_KEY_HIST_WORDS:
         raise ValueError(f"a key histogram has {abi.ACN_KEY_HIST_WORDS} words, got {hh.shape[0]}")
     return float(hip.acn_key_hist_threshold(hh.ctypes.data, int(budget)))
+
+
+def motion_from_scenes(prev_flat, cur_flat, moved_max_history=None):
+    """The motion table of two flat scenes, prev_flat one frame before cur_flat (acn_motion_from_scenes): per node of cur_flat where a
+    point of that object was one frame ago -> ( table [n_nodes,16], report: rows `rest`, `moved`, `none` and `same_shape` ).
+    moved_max_history: the history cap of the rows that moved, None for the call's own.  No GPU."""
+    table = np.empty((cur_flat.c.n_nodes, abi.ACN_MOTION_STRIDE), dtype=np.float64)
+    rep = abi.MotionReport()
+    check(hip.acn_motion_from_scenes(C.byref(prev_flat.c), C.byref(cur_flat.c), 0.0 if moved_max_history is None else float(moved_max_history),
+                                     table.ctypes.data, C.byref(rep)), "acn_motion_from_scenes")
+    return table, dict(rest=int(rep.n_rest), moved=int(rep.n_moved), none=int(rep.n_none), same_shape=bool(rep.same_shape))
 
 
 def cps_from_cl(rgb):

@@ -919,8 +919,8 @@ double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget );   /* no 
  * A record depends on its own current record and the four previous positions alone, not on which positions share a wavefront.
  * Limitation, stated: the WORLD IS TAKEN TO BE AT REST between the two frames -- only the camera moves.  A surface that moved off
  * its tangent plane fails the plane test and starts without history; one that moved within it, or whose light changed, keeps a
- * history that is no longer its own.  Motion per object is the caller's: reject such positions (a kind bit, or an EMPTY previous
- * record).  With the default reject_kinds history is taken only where the radiance does not depend on the view direction (no
+ * history that is no longer its own.  Objects that move between the frames are what acn_reproject_moving* below is for; a change
+ * of the light is detected by neither call.  With the default reject_kinds history is taken only where the radiance does not depend on the view direction (no
  * mirror, no glass, no Fresnel term); max_hops > 0 accepts records of ACN_SURF_FOLLOW behind glass or in mirrors, whose parallax
  * is not that of the surface point: the caller's risk.  Layered records (acn_lens_layers_*) are not reprojected.
  * The caller then runs acn_lens_stats_merge_dev( history, n, current statistics, n ); the library adds no fused call.
@@ -960,6 +960,87 @@ int acn_reproject_dev( acn_scene_handle* h, const void* d_cur_surface, size_t n,
 int acn_reproject    ( acn_scene_handle* h, const double* cur_surface, size_t n, const acn_params* prev_params, const double* prev_surface,
                        const double* prev_stats, const acn_reproject_params* prm, double* out_stats, double* out_motion /* nullable */,
                        const acn_render_opts* opts );
+
+/* Reprojection through moving objects: per-object motion (k_reproject.hip: k_reproject_moving; csrc/acn_motion_host.h).  acn_reproject*
+ * takes the world to be at rest.  acn_reproject_moving* takes, per node index of the CURRENT scene, where a point of that object was
+ * one frame ago: a surface record names the object that carries its point ([ 7 ] enter, [ 8 ] exit: node indices), a flat scene gives
+ * every node a rigid frame (acn_node.pos, acn_node.rax; the local point is rax * ( P - pos )), and acn_scene_replace keeps node indices
+ * stable for a scene of the same shape.  All of it is a definition of this library.  tools/render_turntable.py --spin is a caller.
+ *
+ * The motion table: motion [ n_motion ][ ACN_MOTION_STRIDE ] doubles, 16-byte aligned, read 16 bytes at a time; row i belongs to node i.
+ *   m[ 0 .. 8 ]   A, rows x, y, z:  A.x = m[ 0 .. 2 ], A.y = m[ 3 .. 5 ], A.z = m[ 6 .. 8 ]
+ *   m[ 9 .. 11 ]  t
+ *   m[ 12 ]       the state: m[ 12 ] == ACN_MOTION_REST (0.0; compared as doubles, so -0.0 too) is REST, m[ 12 ] == ACN_MOTION_MOVED (1.0)
+ *                 is MOVED, anything else, a NaN included, is NONE: no history for this object.  ACN_MOTION_NONE (2.0) is what
+ *                 acn_motion_from_scenes writes for it
+ *   m[ 13 ]       the object's own history cap: a finite value >= 1 is a cap, anything else means "the call's max_history"
+ *   m[ 14 .. 15 ] 0
+ * A and t are read only of a MOVED row.  With dot and the arithmetic rules of the acn_reproject block above (binary64, no contraction,
+ * dot( a, b ) = ( a.x * b.x + a.y * b.y ) + a.z * b.z), for a point P and a normal N of the current frame:
+ *   MOVED:  Pp = ( dot( A.x, P ) + t.x, dot( A.y, P ) + t.y, dot( A.z, P ) + t.z )      where the point was one frame ago
+ *           Np = ( dot( A.x, N ), dot( A.y, N ), dot( A.z, N ) )                        how its normal pointed then
+ *   REST:   Pp = P and Np = N with NO arithmetic: the row is not multiplied by an identity, which would turn a -0.0 into +0.0.
+ *
+ * acn_reproject_moving*: the arguments, the buffers, the stream rules and the steps of acn_reproject*, with these differences:
+ *   1a OBJECT    (after 1 HIT) id = ( int32 )r[ 7 ] if that is >= 0, else ( int32 )r[ 8 ]: obj_color's rule for the object that carries
+ *                the point.  id < 0 or id >= n_motion: the state is NONE; else the state, the cap and (MOVED) A and t are those of row
+ *                id.  NONE: the record is EMPTY and the motion is ( NaN, NaN ).
+ *   2 MOTION     projects Pp, not P: ( qx, qy ) is where the point of the moved object was on the previous raster.
+ *   5 VALID      D = P' - Pp per component;  dot( Np, N' ) >= normal_min;  |dot( Np, D )| <= plane_tolerance * r[ 0 ].  The other terms stay;
+ *                the MATCH rule already forces the tap to show the same object.
+ *   6 GATHER     the cap is m[ 13 ] where m[ 13 ] >= 1.0 and m[ 13 ] < max_history, else max_history (so an infinite or NaN m[ 13 ] is none).
+ * A table whose rows are all REST with m[ 13 ] = 0 gives the bits of acn_reproject* on every input.  The lane reads m[ 12 .. 13 ] of its
+ * row first and the other 96 bytes only if the row is MOVED.
+ * Limitations, stated: a moved object's own shading changes as it turns to the light, and a static surface's shading changes where a
+ * mover's shadow or reflection falls.  Neither is detected: the history of such a point is no longer its own.  That is what the
+ * per-object cap m[ 13 ] and max_history are for: they bound how long old samples outweigh new ones.  Clipping the history to the
+ * new samples' spread is a separate feature and not part of this call.  What acn_reproject* says of reject_kinds and max_hops holds.
+ * ACN_ERR_ARG, on the host before any launch, acn_last_error set, nothing written: what acn_reproject* refuses, and (n > 0) a null
+ * motion or n_motion == 0; a table that is not 16-byte aligned; n_motion > 2^31.  n == 0 is ACN_OK with no launch.
+ *
+ * acn_motion_from_scenes (no GPU; csrc/acn_motion_host.h): the table of two flat scenes, prev one frame before cur.  out_table
+ * [ cur->n_nodes ][ ACN_MOTION_STRIDE ]; report (nullable) counts the rows by state.  The rules, in this order:
+ *   SHAPE        the scenes have the same shape iff n_nodes, n_elems, every entry of elems, light_root, matter_root and, per node, type,
+ *                child0 and child1 are equal.  If not: every row is NONE, same_shape = 0, and the status is ACN_OK.
+ *   CHANGED      per node: the row is NONE if any of prm, sdf_kind, cycles, texture (and, where texture >= 0, the bytes of that
+ *                acn_texture; an index outside textures counts as different) or the members color .. transparency differs bitwise: the
+ *                object changed, so its radiance history is stale.  flags, env_pos and env_radius are ignored.
+ *   REST         else the row is REST iff pos and rax are bitwise equal.
+ *   MOVED        else the row is MOVED iff both rax are orthonormal within 1e-9: max over i, j of | dot( rax.row i, rax.row j ) - ( i == j ) |
+ *                <= 1e-9 (the usual conservative margin of this library: a rule, not a measurement).  With p = prev, c = cur, rax[ k ][ i ]
+ *                element i of row k:
+ *                  A[ i ][ j ] = ( p.rax[ 0 ][ i ] * c.rax[ 0 ][ j ] + p.rax[ 1 ][ i ] * c.rax[ 1 ][ j ] ) + p.rax[ 2 ][ i ] * c.rax[ 2 ][ j ]      (rax_prev^T * rax_cur)
+ *                  t[ i ]      = p.pos[ i ] - ( ( A[ i ][ 0 ] * c.pos[ 0 ] + A[ i ][ 1 ] * c.pos[ 1 ] ) + A[ i ][ 2 ] * c.pos[ 2 ] )
+ *                  m[ 13 ]     = moved_max_history
+ *                so that the point with the local coordinates rax_cur * ( P - pos_cur ) now had them at A * P + t.  If either rax is
+ *                not orthonormal the row is NONE.
+ *   SCALE        every node strictly below an ACN_SCALE node lives in that node's scaled frame.  It takes the row of its OUTERMOST
+ *                ACN_SCALE ancestor iff every node strictly below that ancestor is equal in both scenes byte for byte (and the bytes of
+ *                its texture), the ancestor's prm being equal by CHANGED.  Otherwise every node of that subtree, the ancestor
+ *                included, is NONE.  (Below: child0 of ACN_SCALE and ACN_NEG, child0 and child1 of a pair, the elements of a compound,
+ *                from light_root and matter_root.)
+ * A row that is not MOVED is zeros but for m[ 12 ].  ACN_ERR_ARG, acn_last_error set, nothing written: a null scene or table (or null
+ * nodes / elems where there are any); a NaN or negative moved_max_history, or one in ( 0, 1 ); a child or element index outside cur. */
+#define ACN_MOTION_STRIDE 16
+#define ACN_MOTION_REST   0.0
+#define ACN_MOTION_MOVED  1.0
+#define ACN_MOTION_NONE   2.0
+typedef struct acn_motion_report
+{
+    uint32_t n_rest;       /* rows by state */
+    uint32_t n_moved;
+    uint32_t n_none;
+    uint32_t same_shape;   /* 1 iff the SHAPE rule held */
+} acn_motion_report;
+int acn_motion_from_scenes( const acn_flat_scene* prev, const acn_flat_scene* cur, double moved_max_history /* 0: none */,
+                            double* out_table /* [ cur->n_nodes ][ ACN_MOTION_STRIDE ] */, acn_motion_report* report /* nullable */ );
+int acn_reproject_moving_dev( acn_scene_handle* h, const void* d_cur_surface, size_t n, const acn_params* prev_params, const void* d_prev_surface,
+                              const void* d_prev_stats, const void* d_motion /* [ n_motion ][ ACN_MOTION_STRIDE ] */, size_t n_motion,
+                              const acn_reproject_params* prm /* nullable: defaults */, void* d_out_stats /* [ n ][ 8 ] */,
+                              void* d_out_motion /* nullable [ n ][ 2 ] */, const acn_render_opts* opts );
+int acn_reproject_moving    ( acn_scene_handle* h, const double* cur_surface, size_t n, const acn_params* prev_params, const double* prev_surface,
+                              const double* prev_stats, const double* motion, size_t n_motion, const acn_reproject_params* prm,
+                              double* out_stats, double* out_motion /* nullable */, const acn_render_opts* opts );
 
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );

@@ -18,7 +18,16 @@ lay in the previous frame (acn_reproject_dev, against the previous frame's first
 (acn_lens_stats_merge_dev); --denoise filters the pooled frame with its measured variance (acn_denoise_stats_dev).  History is taken
 only where the radiance does not depend on the view direction -- --allow-fresnel also takes it on Fresnel surfaces -- and carries at
 most --max-history samples (default 32), so a pixel converges over the frames without lagging behind the camera for long.  The world is
-taken to be at rest: only the camera moves (include/actinon_hip.h: acn_reproject)."""
+taken to be at rest: only the camera moves (include/actinon_hip.h: acn_reproject).
+
+    ... --spin NODE [--spin-axis x,y,z] [--moved-max-history M]
+
+turns an object instead of the camera: the camera stays, and root element NODE of the scene's matter turns about the axis (default
+0,0,1) through its own position, --orbit-deg degrees in all.  Every frame is a copy of the scene with that object turned
+(actinon_amd.motion.rigid_copy) made resident by acn_scene_replace.  With --temporal the history comes from acn_reproject_moving_dev
+with the motion table of the previous and the current scene (acn_motion_from_scenes): a point of the turned object takes the samples
+of where it was one frame ago.  Its shading changes as it turns to the light, and so does that of surfaces its shadow crosses; neither
+is detected, so --moved-max-history (a cap for the object that moved) and --max-history bound how long old samples weigh."""
 import argparse
 import os
 import sys
@@ -29,8 +38,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def render(flat, frames, orbit_deg, write, target_distance=None):
-    """write( frame, rgb8 [H,W,3] uint8 ) for every frame -> the handle's counters after the last (Handle.info)"""
+def spun(flat, spin, degrees):
+    """a copy of the scene with the node spin[ 0 ] turned by `degrees` about the axis spin[ 1 ] through its own position"""
+    from actinon_amd.motion import rigid_copy, rotation_about
+    return rigid_copy(flat, spin[0], rotation_about(spin[1], degrees), pivot=list(flat.node(spin[0]).pos))
+
+
+def render(flat, frames, orbit_deg, write, target_distance=None, spin=None):
+    """write( frame, rgb8 [H,W,3] uint8 ) for every frame -> the handle's counters after the last (Handle.info).  spin: None, or
+    ( node index, axis ): that object turns and the camera stays"""
     import torch
     import actinon_amd as A
     from actinon_amd.cameras import orbit_camera
@@ -43,7 +59,9 @@ def render(flat, frames, orbit_deg, write, target_distance=None):
         d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
         for f in range(frames):
-            if f:
+            if f and spin:
+                h.replace(spun(flat, spin, orbit_deg * f / frames))
+            elif f:
                 h.set_params(**orbit_camera(flat.params, orbit_deg * f / frames, target_distance))
             h.render_main_pass_dev(0, n, d_lin.data_ptr(), linear=True)
             h.resolve_dev(d_lin.data_ptr(), n, None, d_rgb8.data_ptr())
@@ -53,9 +71,11 @@ def render(flat, frames, orbit_deg, write, target_distance=None):
         h.close()
 
 
-def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=None, denoise=False, max_history=None, allow_fresnel=False):
+def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=None, denoise=False, max_history=None, allow_fresnel=False,
+                    spin=None, moved_max_history=None):
     """The same frames with the history of the frames before them; write( frame, rgb8 ) -> ( Handle.info, per frame the share of pixels
-    that took a history and their mean n after the merge )"""
+    that took a history and their mean n after the merge ).  spin: None, or ( node index, axis ): that object turns, the camera stays,
+    and the history goes through the motion table of the two scenes"""
     import ctypes as C
     import torch
     import actinon_amd as A
@@ -78,14 +98,24 @@ def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=Non
         d_lin = new(n, 3)
         d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
         torch.cuda.synchronize(dev)
-        prev_params, report = None, []
+        prev_params, prev_flat, report = None, flat, []
         for f in range(frames):
-            if f:
+            if f and spin:
+                cur_flat = spun(flat, spin, orbit_deg * f / frames)
+                h.replace(cur_flat)
+            elif f:
                 h.set_params(**orbit_camera(flat.params, orbit_deg * f / frames, target_distance))
             h.surface_positions_dev(d_pos.data_ptr(), n, d_surf.data_ptr())
             h.render_lens_stats_main_pass_dev(0, n, None, d_cur.data_ptr(), linear=True, samples=samples, jitter=True, seed=f)
-            if f:
+            if f and spin:
+                table, _ = A.motion_from_scenes(prev_flat, cur_flat, moved_max_history)
+                d_table = torch.from_numpy(table).to(dev)
+                h.reproject_moving_dev(d_surf.data_ptr(), n, prev_params, d_prev_surf.data_ptr(), d_prev.data_ptr(), d_table.data_ptr(), len(table),
+                                       d_acc.data_ptr(), **params)
+                prev_flat = cur_flat
+            elif f:
                 h.reproject_dev(d_surf.data_ptr(), n, prev_params, d_prev_surf.data_ptr(), d_prev.data_ptr(), d_acc.data_ptr(), **params)
+            if f:
                 took = float((d_acc[:, 0] >= 1).double().mean())
                 h.lens_stats_merge_dev(d_acc.data_ptr(), n, d_cur.data_ptr(), n)
             else:
@@ -122,6 +152,9 @@ def main(argv=None):
     ap.add_argument("--denoise", action="store_true", help="--temporal: filter every pooled frame with its measured variance")
     ap.add_argument("--max-history", type=float, default=None, help="--temporal: samples a history carries at most (default 32)")
     ap.add_argument("--allow-fresnel", action="store_true", help="--temporal: take history on Fresnel surfaces too")
+    ap.add_argument("--spin", type=int, default=None, metavar="NODE", help="turn root element NODE of the scene's matter instead of the camera, --orbit-deg in all")
+    ap.add_argument("--spin-axis", default=None, metavar="x,y,z", help="--spin: the axis through the object's position (default 0,0,1)")
+    ap.add_argument("--moved-max-history", type=float, default=None, help="--spin --temporal: samples the history of the turned object carries at most")
     args = ap.parse_args(argv)
     if args.frames < 1:
         ap.error("--frames is at least 1")
@@ -131,6 +164,18 @@ def main(argv=None):
         ap.error("--samples, --denoise, --max-history and --allow-fresnel belong to --temporal")
     if args.max_history is not None and not args.max_history >= 1:
         ap.error("--max-history is at least 1")
+    if args.spin is None and (args.spin_axis is not None or args.moved_max_history is not None):
+        ap.error("--spin-axis and --moved-max-history belong to --spin")
+    if args.moved_max_history is not None and not (args.temporal and args.moved_max_history >= 1):
+        ap.error("--moved-max-history belongs to --temporal and is at least 1")
+    axis = (0.0, 0.0, 1.0)
+    if args.spin_axis is not None:
+        try:
+            axis = tuple(float(v) for v in args.spin_axis.split(","))
+        except ValueError:
+            axis = ()
+        if len(axis) != 3 or not sum(v * v for v in axis) > 0:
+            ap.error("--spin-axis is x,y,z with a length")
     try:
         if args.out % 0 == args.out % 1:
             raise TypeError
@@ -146,14 +191,21 @@ def main(argv=None):
                 ap.error("sample counts are not negative")
             setattr(flat.params, name, value)
     write = lambda f, rgb8: write_pnm(args.out % f, np.ascontiguousarray(rgb8))
+    spin = None
+    if args.spin is not None:
+        elems = flat.elems_of(flat.c.matter_root)
+        if not 0 <= args.spin < len(elems):
+            ap.error(f"--spin: the scene's matter has {len(elems)} root elements")
+        spin = (elems[args.spin], axis)
     if args.temporal:
         info, report = render_temporal(flat, args.frames, args.orbit_deg, write, args.samples, args.target_distance, args.denoise, args.max_history,
-                                       args.allow_fresnel)
+                                       args.allow_fresnel, spin, args.moved_max_history)
         for f, (took, mean_n) in enumerate(report):
             print(f"frame {f}: {took:.3f} of the pixels took a history, mean n {mean_n:.1f}")
     else:
-        info = render(flat, args.frames, args.orbit_deg, write, args.target_distance)
-    print(f"{args.frames} frames on one handle: {info['param_sets']} parameter changes, {info['streams']} streams, {info['lanes']} lanes, "
+        info = render(flat, args.frames, args.orbit_deg, write, args.target_distance, spin)
+    changes = f"{info['replaces']} scene changes" if spin else f"{info['param_sets']} parameter changes"
+    print(f"{args.frames} frames on one handle: {changes}, {info['streams']} streams, {info['lanes']} lanes, "
           f"{info['learning_passes']} learning pass(es)")
 
 
