@@ -96,7 +96,8 @@ struct Tunables
     size_t   workspace_mb = 0;         /* ACN_WORKSPACE_MB: upper bound of the queue workspace of one handle (all its lanes); 0: 64 GiB or a
                                           quarter of the device memory that is free at upload, whichever is less */
     size_t   chunk = 0;                /* ACN_CHUNK: sample positions per pipeline run, 0 = derived from the queue capacity */
-    int      lanes = 6;                /* ACN_LANES: concurrent pipeline runs of a large call (4 until round 4, each on grids twice the size: create_lane) */
+    int      lanes = 0;                /* ACN_LANES: concurrent pipeline runs of a large call, as the host gave it ... */
+    bool     lanes_given = false;      /* ... if it gave one.  The count and the lanes' grids a handle uses: acn_lane_plan (acn_queueplan.h) */
     unsigned grid = 0;                 /* ACN_GRID: workgroups of the persistent kernels, 0 = 4 per compute unit */
     unsigned shade_grid = 0;           /* ACN_SHADE_GRID: workgroups of k_shade, 0 = 4 per compute unit */
     unsigned walk_grid = 0;            /* ACN_WALK_GRID: workgroups of k_walk (256 VGPRs: two of its waves fill a SIMD's register file), 0 = as ACN_GRID */
@@ -139,7 +140,7 @@ struct Tunables
         if( const char* e = getenv( "ACN_LDS_MAX" ) ) { tables.lds_max = ( size_t )atoll( e ); tables.lds_max_set = true; }
         if( const char* e = getenv( "ACN_WORKSPACE_MB" ) ) workspace_mb = ( size_t )atoll( e );
         if( const char* e = getenv( "ACN_CHUNK" ) ) chunk = ( size_t )atoll( e );
-        if( const char* e = getenv( "ACN_LANES" ) ) lanes = atoi( e );
+        if( const char* e = getenv( "ACN_LANES" ) ) { lanes = atoi( e ); lanes_given = true; }
         if( const char* e = getenv( "ACN_GRID" ) ) grid = ( unsigned )atoi( e );
         if( const char* e = getenv( "ACN_SHADE_GRID" ) ) shade_grid = ( unsigned )atoi( e );
         if( const char* e = getenv( "ACN_WALK_GRID" ) ) walk_grid = ( unsigned )atoi( e );
@@ -166,8 +167,6 @@ struct Tunables
         if( const char* e = getenv( "ACN_EARLY_LANES" ) ) early_lanes = atoi( e ) != 0;
         debug_chunks = getenv( "ACN_DEBUG_CHUNKS" ) != nullptr;
         stage_timing = getenv( "ACN_STAGE_TIMING" ) != nullptr;
-        if( lanes < 1 ) lanes = 1;
-        if( lanes > 16 ) lanes = 16;
         if( stack_cap < 256 ) stack_cap = 256;
         if( stack_use == 0 || stack_use > stack_cap ) stack_use = stack_cap;
     }
@@ -319,6 +318,7 @@ struct acn_scene_handle
     Tunables tun;
     unsigned cus = 256;                        /* compute units of the device */
     size_t workspace_budget = 0;               /* bytes this handle's queues may take (all lanes together) */
+    acn_lane_plan_t plan = { 1, 0, 0, 0 };     /* lanes of a large call and a lane's grids: acn_lane_plan of the tunables and the device's compute units (acn_scene_upload) */
     PipeRun run;                               /* a call that runs alone; its stream is the handle's own, its statistics the last call's */
     /* concurrent lanes (render_lanes): runners that own a stream, a workspace and a host thread each */
     std::vector< std::unique_ptr< PipeRun > > lanes;

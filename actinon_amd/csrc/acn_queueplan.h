@@ -341,6 +341,32 @@ static inline int acn_lanes_for_counts( int tun_lanes, size_t n, uint64_t path_s
     while( lanes > 1 && ( n < ( size_t )lanes * 32 * ACN_LANE_TILE || work < ( size_t )lanes << 20 ) ) lanes--;
     return lanes;
 }
+/* The lane plan of a handle: how many concurrent lanes a large call gets (before acn_lanes_for_counts) and the persistent grids of
+ * a lane (bind_lane).  A lane is a stream, and lanes pay only while every stream has a hardware queue of its own: two lanes that
+ * share a queue run their chains of ~45 launches one after the other.  HIP gives a process that asks for nothing FOUR hardware
+ * queues, and the caller's stream and the handle's own are streams as well, so the default is made for that process:
+ * ACN_DEFAULT_LANES lanes on ACN_DEFAULT_LANE_WGS workgroups per compute unit, k_shade too (fewer, longer chains on grids that
+ * fill the chip with two of them running).  Chosen from profiles/r19/NOTES.md section 2, the run "L2 768/768/768" of its second
+ * table: on four queues the 1080p frame takes 48.4 ms that way, 50.1 on two workgroups per compute unit, 52.6 on one lane, 56 - 64
+ * on three or four lanes and 60.6 on the six of round 4.  A host that exports more queues (GPU_MAX_HW_QUEUES=8) sets ACN_LANES:
+ * a given count is the host's, on the round-4 grids -- one workgroup per compute unit, k_shade one and a half -- that six lanes
+ * with a queue each were measured on (profiles/r04/ab_lanes6_*).  Nothing here reads the process: the arguments are the handle's
+ * tunables (lanes_given: ACN_LANES was set, lanes_env its value; *_grid_env: ACN_GRID / ACN_SHADE_GRID / ACN_WALK_GRID, 0 = not
+ * set) and the compute units of its device. */
+#define ACN_DEFAULT_LANES 2
+#define ACN_DEFAULT_LANE_WGS 3
+#define ACN_MAX_LANES 16
+typedef struct { int lanes; unsigned grid, shade_grid, walk_grid; } acn_lane_plan_t;
+static inline acn_lane_plan_t acn_lane_plan( int lanes_given, int lanes_env, unsigned cus, unsigned grid_env, unsigned shade_grid_env, unsigned walk_grid_env )
+{
+    acn_lane_plan_t p;
+    p.lanes = lanes_given ? ( lanes_env < 1 ? 1 : lanes_env > ACN_MAX_LANES ? ACN_MAX_LANES : lanes_env ) : ACN_DEFAULT_LANES;
+    p.grid = grid_env ? grid_env : lanes_given ? cus : cus * ACN_DEFAULT_LANE_WGS;
+    p.shade_grid = shade_grid_env ? shade_grid_env : lanes_given ? cus * 3u / 2u : cus * ACN_DEFAULT_LANE_WGS;
+    p.walk_grid = walk_grid_env ? walk_grid_env : p.grid;
+    return p;
+}
+
 /* 1: the call's queues cannot hold it in one chunk per lane within the workspace bound, it runs on one lane (render_dispatch).
  * was_one_lane: sticky by 30 % -- rates move a little from call to call, and changing the arrangement re-allocates everything */
 static inline int acn_one_lane( const double* rate, int seeded, size_t n, const size_t* rec_bytes, size_t budget, int was_one_lane )

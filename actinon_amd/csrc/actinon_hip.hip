@@ -93,7 +93,7 @@ static hipError_t run_objects( PipeRun* r, bool on_stream, Mark mark )
  * become the handle's before the upload's first kernel (quiesce). */
 static void early_lanes_begin( acn_scene_handle* h, size_t n, uint64_t path_samples )
 {
-    const int lanes = acn_lanes_for_counts( h->tun.lanes, n, path_samples );
+    const int lanes = acn_lanes_for_counts( h->plan.lanes, n, path_samples );
     if( lanes <= 1 || path_samples >= 256 ) return;
     const int device = h->device; const bool debug = h->tun.debug_chunks;
     h->early_maker = std::thread( [ h, lanes, device, debug ]()
@@ -272,6 +272,12 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
     own->h = h.get();
     h->device = device;
     h->tun.read();
+    {
+        int cus = 0;
+        if( hipDeviceGetAttribute( &cus, hipDeviceAttributeMultiprocessorCount, device ) != hipSuccess || cus <= 0 ) cus = 256;
+        h->cus = ( unsigned )cus;
+        h->plan = acn_lane_plan( h->tun.lanes_given, h->tun.lanes, h->cus, h->tun.grid, h->tun.shade_grid, h->tun.walk_grid );
+    }
     if( h->tun.early_lanes ) early_lanes_begin( h.get(), ( size_t )scene->params.image_width * ( size_t )scene->params.image_height, scene->params.path_samples );
     double t_events = 0, t_objects = 0, t_in[ 3 ] = { 0, 0, 0 };   /* ACN_DEBUG_CHUNKS: stream + events; the marks of install_scene: host-side tables, device copies, the helper thread */
     {
@@ -287,15 +293,10 @@ extern "C" int acn_scene_upload( const acn_flat_scene* scene, int device, acn_sc
         if( !h->tun.workspace_mb && h->workspace_budget > free_b / 4 ) h->workspace_budget = free_b / 4;
     }
     {
-        int cus = 0;
-        if( hipDeviceGetAttribute( &cus, hipDeviceAttributeMultiprocessorCount, device ) != hipSuccess || cus <= 0 ) cus = 256;
         /* persistent grids.  A call that runs alone on its stream: 4 workgroups of 256 lanes per CU, what fits of the
-         * 128-VGPR kernels.  The concurrent lanes of a call (bind_lane): 2 per CU each -- what is resident of k_walk
-         * (256 VGPRs); four lanes keep the chip full and leave room for each other's kernels (1080p: 83.4 ms against
-         * 85.2 with 4 per CU; a lone lane with 2 per CU: 106 ms against 88) */
-        h->cus = ( unsigned )cus;
-        own->grid = h->tun.grid ? h->tun.grid : ( unsigned )cus * 4u;
-        own->shade_grid = h->tun.shade_grid ? h->tun.shade_grid : ( unsigned )cus * 4u;
+         * 128-VGPR kernels.  The concurrent lanes of a call: the handle's lane plan (acn_lane_plan, bind_lane) */
+        own->grid = h->tun.grid ? h->tun.grid : h->cus * 4u;
+        own->shade_grid = h->tun.shade_grid ? h->tun.shade_grid : h->cus * 4u;
         own->walk_grid = h->tun.walk_grid ? h->tun.walk_grid : own->grid;
     }
     const double t_stream0 = since();
@@ -611,8 +612,10 @@ static int learn_rates( PipeRun* r, const Primary& prim, size_t n, hipStream_t s
     return st;
 }
 
+/* tail (nullable): what follows k_finalize on `stream` within the call (a lane scatters its share: render_lanes); ev1 is recorded
+ * behind it */
 static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_out_rgb,
-                          const acn_render_opts* opts, hipStream_t stream )
+                          const acn_render_opts* opts, hipStream_t stream, const std::function< int() >* tail = nullptr )
 {
     const Tunables& tun = r->h->tun;
     Learned& L = r->learned;
@@ -714,6 +717,7 @@ static int launch_render( PipeRun* r, const Primary& prim, size_t n, double* d_o
                         ( const unsigned long long* )r->d_accum.get(), ( uint32_t )n, r->dev.prm.gamma, linear, d_out_rgb );
     HIP_TRY( hipGetLastError() );
     if( ( st = stage_end( r, sw, stream ) ) != ACN_OK ) return st;
+    if( tail && ( st = ( *tail )() ) != ACN_OK ) return st;
     HIP_TRY( hipEventRecord( r->ev1.get(), stream ) );
     return ACN_OK;
 }
@@ -789,7 +793,7 @@ static int lane_objects( int device, bool debug, std::unique_ptr< PipeRun >* out
     return ACN_OK;
 }
 
-static unsigned lane_grid( const acn_scene_handle* h ) { return h->tun.grid ? h->tun.grid : h->cus * 1u; }
+static unsigned lane_grid( const acn_scene_handle* h ) { return h->plan.grid; }
 static void bind_lane( const acn_scene_handle* h, int lanes, PipeRun* l )
 {
     l->h = h;
@@ -798,13 +802,15 @@ static void bind_lane( const acn_scene_handle* h, int lanes, PipeRun* l )
     /* Round 4: six lanes on grids of ONE workgroup per CU (k_shade: one and a half) instead of four lanes on two.  With k_walk at
      * four waves per SIMD a grid of 256 workgroups is resident at once, and six shorter chains fill each other's tails better than
      * four: 1080p 50.2 -> 49.1 ms, c2 26.4 -> 25.0, and the share one of 8 GPUs gets 12.25 -> 11.4 ms (profiles/r04/ab_lanes6_*).
-     * A call that runs ALONE on the handle keeps four workgroups per CU (diamond on one lane: 2.3 s with them, 6.7 s with one). */
+     * A call that runs ALONE on the handle keeps four workgroups per CU (diamond on one lane: 2.3 s with them, 6.7 s with one).
+     * That is the plan of a host that sets ACN_LANES, measured with a hardware queue per lane.  The default plan is made for the
+     * four queues of a process that asks for none: fewer lanes on larger grids (acn_lane_plan). */
     l->grid = lane_grid( h );
-    l->shade_grid = h->tun.shade_grid ? h->tun.shade_grid : h->cus * 3u / 2u;
-    l->walk_grid = h->tun.walk_grid ? h->tun.walk_grid : l->grid;
+    l->shade_grid = h->plan.shade_grid;
+    l->walk_grid = h->plan.walk_grid;
 }
 
-static int lanes_for( const acn_scene_handle* h, size_t n ) { return acn_lanes_for_counts( h->tun.lanes, n, h->dev.prm.path_samples ); }
+static int lanes_for( const acn_scene_handle* h, size_t n ) { return acn_lanes_for_counts( h->plan.lanes, n, h->dev.prm.path_samples ); }
 
 static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, size_t n, double* d_out_rgb,
                          const acn_render_opts* opts, hipStream_t stream )
@@ -832,9 +838,11 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
     const bool learn = h->lanes.empty() ? !own->learned.known() : !h->lanes[ 0 ]->learned.known() && !own->learned.known();
     const bool maker_used = missing > 0 && learn && h->tun.cold_pipeline;
     if( missing > 0 ) { if( maker_used ) maker = std::thread( make_missing ); else make_missing(); }
-    /* what the caller queued on `stream` before this call must be done before the lanes read the positions */
+    /* what the caller queued on `stream` before this call must be done before the lanes read the positions: every lane's stream
+     * waits for ev0 on the device (post_lane), the host does not.  A cold handle waits here as well: its learning pass and the
+     * sizing that follows it (hipFree) run while nothing else of the caller's does */
     hipError_t drained = hipEventRecord( own->ev0.get(), stream );
-    if( drained == hipSuccess ) drained = hipEventSynchronize( own->ev0.get() );
+    if( drained == hipSuccess && learn ) drained = hipEventSynchronize( own->ev0.get() );
     mark( 0 );
     /* a cold handle learns the scene's queue demand once, for all lanes, from a sample of the call (learn_rates) */
     int learned = ACN_OK;
@@ -875,6 +883,7 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
                 if( l->d_lane_in.grow( sizeof( double ) * ( prim.rays ? 6 : 2 ) * cnt ) || l->d_lane_out.grow( sizeof( double ) * 3 * cnt ) ) return ACN_ERR_DEVICE;
                 double* const d_in = l->d_lane_in.get(); double* const d_out = l->d_lane_out.get();
                 hipStream_t const ls = l->stream.get();
+                HIP_TRY( hipStreamWaitEvent( ls, own->ev0.get(), 0 ) );
                 if( prim.rays )
                     hipLaunchKernelGGL( k_lane_gather_rays, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
                                         prim.rays, cnt, lanes, k, d_in );
@@ -882,13 +891,17 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
                     hipLaunchKernelGGL( k_lane_gather, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
                                         prim.pos_xy, prim.first, ( uint64_t )h->dev.prm.image_width, cnt, lanes, k, d_in );
                 HIP_TRY( hipGetLastError() );
-                const int st = launch_render( l, prim.rays ? primary_rays( d_in ) : primary_positions( d_in ), cnt, d_out, &lane_opts, ls );
-                if( st != ACN_OK ) return st;
-                hipLaunchKernelGGL( k_lane_scatter, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
-                                    ( const double* )d_out, cnt, lanes, k, d_out_rgb );
-                HIP_TRY( hipGetLastError() );
-                HIP_TRY( hipStreamSynchronize( ls ) );
-                return ACN_OK;
+                /* the lane's share of the frame goes to its places in the caller's buffer behind k_finalize; the lane's ev1 is
+                 * recorded behind that (launch_render) and the caller's stream waits for it (below): the worker does not.  Its
+                 * last wait is its last chunk's; d_lane_in and d_lane_out are used again by the next call on this stream, in order */
+                const std::function< int() > scatter = [ & ]() -> int
+                {
+                    hipLaunchKernelGGL( k_lane_scatter, dim3( ( unsigned )( ( cnt + 255 ) / 256 ) ), dim3( 256 ), 0, ls,
+                                        ( const double* )d_out, cnt, lanes, k, d_out_rgb );
+                    HIP_TRY( hipGetLastError() );
+                    return ACN_OK;
+                };
+                return launch_render( l, prim.rays ? primary_rays( d_in ) : primary_positions( d_in ), cnt, d_out, &lane_opts, ls, &scatter );
             };
             status[ k ] = run();
             if( status[ k ] != ACN_OK ) message[ k ] = g_last_error;   /* thread-local in the worker */
@@ -910,6 +923,8 @@ static int render_lanes( acn_scene_handle* h, int lanes, const Primary& prim, si
         fprintf( stderr, "[acn call] %zu positions on %d lanes: %d lanes made%s, caller's stream drained after %.2f ms, learning pass %.2f, queues sized %.2f, lanes done %.2f\n",
                  n, lanes, missing > 0 ? missing : 0, maker_used ? " beside the learning pass" : "", t_mark[ 0 ], t_mark[ 1 ] - t_mark[ 0 ], t_mark[ 2 ] - t_mark[ 1 ], t_mark[ 3 ] - t_mark[ 2 ] );
     for( int k = 0; k < lanes; k++ ) if( status[ k ] != ACN_OK ) return fail( status[ k ], message[ k ] );
+    /* the join: whatever the caller queues on `stream` after this call follows the lanes' last kernels, in stream order */
+    for( int k = 0; k < lanes; k++ ) if( acn_lane_count( n, lanes, k ) ) HIP_TRY( hipStreamWaitEvent( stream, h->lanes[ k ]->ev1.get(), 0 ) );
     HIP_TRY( hipEventRecord( own->ev1.get(), stream ) );
     /* statistics of the call: the lanes' together (RunStats::add), without those that had no positions */
     own->stats.reset();
