@@ -434,9 +434,32 @@ DEV void probe_push( const TaskQ& tq, ChunkP pcs, bool want, V3 p, V3 d, double 
         else atomicOr( tq.flags, ACN_FLAG_CHILD_OVERFLOW );
     }
 }
+/* The same for k_shade_hits, which counts its probes per wave.  The statistics add above is one atomic per call, up to three per step
+ * of 64 records, and QS_PROBES lies on the 128-byte line of the reservation counters of the tasks, the class lists and the probes
+ * (acn_counts.h), where the device serves one atomic after the other: these adds, not the records' bytes and not the reservations,
+ * were what k_shade_hits spent its time on (profiles/r20/NOTES.md: 2.52 -> 1.63 ms per 1080p frame without them).  The kernel adds
+ * *n_probes once per wave when it ends; the word's final value is the same. */
+struct CountedTaskQ : TaskQ
+{
+    uint32_t* n_probes;   /* the wave's probes so far: the same in every lane, so every lane of the wave makes the call */
+};
+DEV void probe_push( const CountedTaskQ& tq, ChunkP pcs, bool want, V3 p, V3 d, double limit, V3 contrib, uint32_t pixel, uint32_t flags )
+{
+    *tq.n_probes += ( uint32_t )__popcll( __ballot( want ) );
+    uint32_t slot = chunk_alloc( pcs, &tq.counts[ QC_HARD_SHADOW ], want );
+    if( want )
+    {
+        if( slot < tq.probe_cap )
+        {
+            HardShadow& h = tq.probes[ slot ];
+            h.pos = p; h.d = d; h.limit = limit; h.contrib = contrib; h.pixel = pixel; h.pad = flags;
+        }
+        else atomicOr( tq.flags, ACN_FLAG_CHILD_OVERFLOW );
+    }
+}
 /* a specular child of shade_hit: onto the ray queue if scene_s_lum would look at its hit, else a probe */
-template< class RAYS, class CT >
-DEV void spawn_child( const DevScene& sc, RAYS& rays, const TaskQ& tq, ChunkP tcs, bool f, V3 p, V3 d, V3 T, double intensity, int depth, uint32_t pixel, CT* cnt )
+template< class RAYS, class CT, class TQ >
+DEV void spawn_child( const DevScene& sc, RAYS& rays, const TQ& tq, ChunkP tcs, bool f, V3 p, V3 d, V3 T, double intensity, int depth, uint32_t pixel, CT* cnt )
 {
     const bool dead = f && ( depth == 0 || intensity < sc.prm.trace_min_intensity );
     rays.push( f && !dead, p, d, T, intensity, depth, pixel );
@@ -447,9 +470,10 @@ DEV void spawn_child( const DevScene& sc, RAYS& rays, const TaskQ& tq, ChunkP tc
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* scene_s_lum for one hit, everything except the two sample loops (scene.c:420-537, 623-664).  Specular children
  * (Fresnel reflection, chromatic reflection, refraction) are pushed to `rays`; the diffuse block becomes a DTask.
- * Every lane of the wave must call this (the appends are wave-wide); lanes with nothing to shade pass depth 0. */
-template< class RAYS, class CT >
-DEV void shade_hit( const DevScene& sc, RAYS& rays, const TaskQ& tq, ChunkP tcs, V3 rp, V3 rd, double offs, const Trans& trans, int depth,
+ * Every lane of the wave must call this (the appends are wave-wide); lanes with nothing to shade pass depth 0.
+ * TQ: TaskQ, or k_shade_hits' CountedTaskQ (which probe_push the children's probes go through). */
+template< class RAYS, class CT, class TQ >
+DEV void shade_hit( const DevScene& sc, RAYS& rays, const TQ& tq, ChunkP tcs, V3 rp, V3 rd, double offs, const Trans& trans, int depth,
                     double intensity, V3 T, uint32_t pixel, V3& acc, CT* cnt )
 {
     const double min_intensity = sc.prm.trace_min_intensity;
@@ -660,8 +684,8 @@ DEV void wave_add_counters( unsigned long long*, const Cnt< false >& ) {}
 #define ACN_TASKQ_PARAMS DTask* __restrict__ p_tasks, uint32_t* __restrict__ p_idx0, uint32_t* __restrict__ p_idx1, \
     uint32_t* __restrict__ p_idx2, uint32_t* __restrict__ p_idx3, uint32_t* __restrict__ p_counts, uint32_t task_cap, \
     HardShadow* __restrict__ p_probes, uint32_t probe_cap, uint32_t probe_emit
-#define ACN_TASKQ_VIEW \
-    TaskQ tq; \
+#define ACN_TASKQ_VIEW TaskQ tq; ACN_TASKQ_FILL
+#define ACN_TASKQ_FILL \
     tq.tasks = p_tasks; tq.idx[ 0 ] = p_idx0; tq.idx[ 1 ] = p_idx1; tq.idx[ 2 ] = p_idx2; tq.idx[ 3 ] = p_idx3; \
     tq.counts = p_counts; tq.task_cap = task_cap; tq.probes = p_probes; tq.probe_cap = probe_cap; tq.emit_terms = probe_emit; tq.flags = sc_in.flags;
 
@@ -840,7 +864,10 @@ void k_shade_hits( ACN_SCENE_PARAMS, ACN_TASKQ_PARAMS, const HitRec* __restrict_
     if( n == 0 ) return;
     fetch_batch = balanced_batch( n, fetch_batch, 64u );
     ACN_SCENE_VIEW
-    ACN_TASKQ_VIEW
+    CountedTaskQ tq;
+    ACN_TASKQ_FILL
+    uint32_t n_probes = 0;
+    tq.n_probes = &n_probes;
     const ChunkP cs = ACN_CHUNKS_OF_WAVE;
     chunks_init( cs );
     chunks_resize( cs, n );
@@ -870,6 +897,7 @@ void k_shade_hits( ACN_SCENE_PARAMS, ACN_TASKQ_PARAMS, const HitRec* __restrict_
     }
     rq.close( p_counts + QS_DEAD_R );
     task_chunks_close( tq, cs );
+    if( ( threadIdx.x & 63 ) == 0 && n_probes ) atomicAdd( p_counts + QS_PROBES, n_probes );
     wave_add_counters( counters, cnt );
 }
 
