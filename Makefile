@@ -31,13 +31,15 @@ HIP_OBJS  := $(addprefix $(BUILD)/,$(addsuffix .o,$(HIP_UNITS)))
 # profiles/r03/ab_walk_max_ilp_scheduling.txt; same bits: scheduling does not reassociate)
 WALK_SCHED ?= -mllvm -amdgpu-sched-strategy=max-ilp
 $(BUILD)/k_walk_lds.o $(BUILD)/k_walk_glb.o: HIPFLAGS += $(WALK_SCHED)
-$(BUILD)/%.o: actinon_amd/csrc/%.hip $(wildcard actinon_amd/csrc/*.h) include/actinon_hip.h
+# (dependencies on headers: as the compiler sees them, $(BUILD)/*.d)
+$(BUILD)/%.o: actinon_amd/csrc/%.hip
 	@mkdir -p $(BUILD)
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
+	$(HIPCC) $(HIPFLAGS) -MMD -MP -c -o $@ $<
 # the scene tables of the upload: host-only C++, no HIP (tests/test_tables_cpu.py compiles the same unit on its own)
-$(BUILD)/acn_tables.o: actinon_amd/csrc/acn_tables.cpp actinon_amd/csrc/acn_tables.h actinon_amd/csrc/acn_counts.h include/actinon_hip.h
+$(BUILD)/acn_tables.o: actinon_amd/csrc/acn_tables.cpp
 	@mkdir -p $(BUILD)
-	$(CXX) -O2 -fPIC -std=c++17 -Wall -ffp-contract=off -fno-fast-math -Iinclude -Iactinon_amd/csrc -c -o $@ $<
+	$(CXX) -O2 -fPIC -std=c++17 -Wall -ffp-contract=off -fno-fast-math -Iinclude -Iactinon_amd/csrc -MMD -MP -c -o $@ $<
+-include $(HIP_OBJS:.o=.d) $(BUILD)/acn_tables.d
 $(LIBDIR)/libactinon_hip.so: $(HIP_OBJS) $(BUILD)/acn_tables.o
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $(HIP_OBJS) $(BUILD)/acn_tables.o
@@ -58,7 +60,19 @@ oracle/libacn_oracle.so: oracle/acn_oracle.c oracle/acn_oracle.h actinon_amd/csr
 oracle/libacn_oracle_libm.so: oracle/acn_oracle.c oracle/acn_oracle.h actinon_amd/csrc/acn_costs.h include/actinon_hip.h
 	$(CC) $(CFLAGS) -march=$(ORACLE_MARCH) -DACN_ORACLE_LIBM -Ioracle -shared -o $@ oracle/acn_oracle.c -lm -lpthread
 
+# Device code identity: per unit the SHA-256 of .text, of .rodata (- if none) and of the notes of its gfx950 code
+# object, from the objects as they are (- - -: a unit without device code); equal lines before and after a change: the kernels are the same
+LLVM_BIN ?= $(dir $(HIPCC))../lib/llvm/bin
+digests:
+	@t=$$(mktemp -d) && for u in $(HIP_UNITS); do \
+	    if ! $(LLVM_BIN)/llvm-objcopy --dump-section .hip_fatbin=$$t/fb $(BUILD)/$$u.o $$t/o 2>/dev/null; then echo $$u - - -; continue; fi; \
+	    $(LLVM_BIN)/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$$t/fb --output=$$t/elf || exit 1; \
+	    for s in text rodata; do $(LLVM_BIN)/llvm-objcopy -O binary --only-section=.$$s $$t/elf $$t/$$s || exit 1; done; \
+	    $(LLVM_BIN)/llvm-readelf --notes $$t/elf > $$t/notes || exit 1; \
+	    echo $$u $$(sha256sum < $$t/text | cut -c1-64) $$(if [ -s $$t/rodata ]; then sha256sum < $$t/rodata | cut -c1-64; else echo -; fi) $$(sha256sum < $$t/notes | cut -c1-64); \
+	done; rm -rf $$t
+
 clean:
 	rm -rf build; rm -f $(LIBDIR)/*.so oracle/*.so actinon_amd/bin/actinon_hip
 
-.PHONY: all hip host oracle cli clean
+.PHONY: all hip host oracle cli clean digests

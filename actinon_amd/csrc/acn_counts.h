@@ -1,5 +1,5 @@
 /* acn_counts.h -- the counter blocks of a chunk: the only thing the device tells the pipeline runner.  The words of a level's block,
- * the ACN_FLAG_* bits of its flag word and the constants that size it, defined ONCE for the kernels that write them (acn_pipeline.h,
+ * the ACN_FLAG_* bits of its flag word and the constants that size it, defined ONCE for the kernels that write them (acn_queues.h and the family headers,
  * acn_device.h), for the host planner that reads them (acn_queueplan.h: acn_read_chunk, acn_sample_rates) and for the tests.  Plain C,
  * valid as C99 and as C++, no HIP header: tests/csrc/chunkplan_cpu.c compiles the planner as C. */
 #ifndef ACN_COUNTS_H
@@ -40,7 +40,7 @@ enum
     QC_N = 104
 };
 
-/* slots a wave reserves of a queue per atomic (the queue appends of acn_pipeline.h) */
+/* slots a wave reserves of a queue per atomic (the queue appends of acn_queues.h) */
 #ifndef ACN_QCHUNK
 #define ACN_QCHUNK 64
 #endif

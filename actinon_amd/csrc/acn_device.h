@@ -1,5 +1,5 @@
 /* acn_device.h -- gfx950 device code of the trace / radiance path (every .hip unit includes it through
- * acn_pipeline.h and acn_launch.h).
+ * acn_records.h and acn_launch.h).
  *
  * What the reference does with recursion over heap objects and vtables (src/objects.c, src/compound.c,
  * src/scene.c:420-667) is done here with index-linked POD nodes, explicit per-lane stacks and state machines:
@@ -81,7 +81,7 @@ struct DevSceneT
     uint32_t* flags;     /* device word for ACN_FLAG_* error bits */
     uint32_t lds_stack;  /* byte offset of the CSG stack area in dynamic LDS, ACN_NO_LDS_STACK if the kernel has none */
     uint32_t prune_base; /* elems[ prune_base + node ]: offset of the node's prune program in elems[], or -1 */
-    uint32_t class0_min; /* shading tasks with more samples than this run on 64 lanes (ACN_CLASS0_MIN, acn_pipeline.h: size_class) */
+    uint32_t class0_min; /* shading tasks with more samples than this run on 64 lanes (ACN_CLASS0_MIN, acn_queues.h: size_class) */
     const SCEntry* sc_table;   /* pre-order tables of the simple compounds */
     const double* sc_spheres;  /* ( pos, radius ) of the sphere leaves of those tables, see SCEntry.flags */
     static constexpr bool prune = false;
@@ -117,6 +117,13 @@ __device__ __forceinline__ auto scene_view( const DevScene& sc, NP2 nodes )
         if constexpr( PK ) { ParkedScene< DevSceneT< NP2 > > r; static_cast< DevSceneT< NP2 >& >( r ) = scene_rebind( sc, nodes ); return r; }
         else return scene_rebind( sc, nodes );
     }
+}
+
+/* the scene as a machine kernel sees it: the node array where that kernel reads it (LDS: staged there by ACN_STAGE_NODES) */
+template< bool PR, bool LDS > __device__ __forceinline__ auto machine_view( const DevScene& sc )
+{
+    if constexpr( LDS ) return scene_view< PR, true >( sc, ( LdsNodeP )acn_lds_raw );
+    else                return scene_view< PR, true >( sc, sc.nodes );
 }
 
 enum

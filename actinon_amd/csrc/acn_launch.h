@@ -1,13 +1,13 @@
-/* acn_launch.h -- launch wrappers of the templated pipeline kernels, one translation unit per kernel family
- * (k_shade_*.hip, k_walk_*.hip, k_hard_*.hip) so that `make -j` compiles the families in parallel: the pipeline's 58 kernel
- * instantiations (32 of k_shade, 8 each of k_walk, k_hard_shadow and k_hard_path, 2 of k_shade_hits) in one file took 8.5 minutes,
- * the families side by side take about 3.  The wrappers pick the
- * instantiation from runtime flags; the orchestration stays in actinon_hip.hip (the pipeline) and acn_calls.hip (the entry points
- * beside it). */
+/* acn_launch.h -- what the host passes to the kernels (SceneArgs, KernelFlags, LevelQ, WalkLaunch, the setups of the side kernels)
+ * and the prototype of every launch wrapper, once.  No kernel template: the orchestrating units (actinon_hip.hip: the pipeline;
+ * acn_calls.hip: the entry points beside it; k_stage.hip, k_query.hip) and the side kernels see the records (acn_records.h) alone.  The
+ * pipeline kernels live in one header per family (acn_k_walk.h, acn_k_shade.h, acn_k_hard.h, over acn_queues.h), included by the
+ * family's own units: one unit per family and size, so that `make -j` compiles the 58 instantiations (32 of k_shade, 8 each of k_walk,
+ * k_hard_shadow and k_hard_path, 2 of k_shade_hits) side by side: about 3 minutes, 8.5 in one file.  Variants: acn_variant.h. */
 #ifndef ACN_LAUNCH_H
 #define ACN_LAUNCH_H
 
-#include "acn_pipeline.h"
+#include "acn_records.h"
 
 /* what every pipeline kernel receives first (ACN_SCENE_PARAMS) */
 struct SceneArgs
@@ -47,16 +47,22 @@ struct LevelQ
     uint32_t emit_terms;                                    /* 0: k_walk drops its pixel terms (level 0 of a rank > 0 of such a call) */
 };
 
-/* pass `pass` of the specular walk of the level.  n_cam > 0 (pass 0 of level 0): the input are the camera rays of
- * positions [ base, base + n_cam ); else generation `pass` of the level's ray queues.  last: the input is finished on the
- * private stacks whatever its size. */
-void acn_launch_walk( KernelFlags f, uint32_t pass, bool last, const LevelQ& q, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
-                      const double* pos_xy, size_t first_pixel, uint32_t base, uint32_t n_cam, TileOrder order,
-                      unsigned long long* accum, unsigned long long* counters );
+/* one launch of k_walk: pass `pass` of the specular walk of the level.  n_cam > 0 (pass 0 of level 0): the input are the camera rays
+ * of positions [ base, base + n_cam ); else generation `pass` of the level's ray queues.  last: the input is finished on the private
+ * stacks whatever its size. */
+struct WalkLaunch
+{
+    uint32_t pass; bool last; const double* pos_xy; size_t first_pixel; uint32_t base, n_cam; TileOrder order; size_t lds_bytes;
+    unsigned long long* accum; unsigned long long* counters;
+};
+/* acn_launch_walk launches its own instantiations or forwards down the chain of the k_walk units: _lds -> _count -> _count_prune, _lds -> _glb */
+void acn_launch_walk( KernelFlags f, const LevelQ& q, const WalkLaunch& w, hipStream_t stream, const SceneArgs& s );
+void acn_launch_walk_glb( KernelFlags f, const LevelQ& q, const WalkLaunch& w, hipStream_t stream, const SceneArgs& s );
+void acn_launch_walk_count( KernelFlags f, const LevelQ& q, const WalkLaunch& w, hipStream_t stream, const SceneArgs& s );
+void acn_launch_walk_count_prune( KernelFlags f, const LevelQ& q, const WalkLaunch& w, hipStream_t stream, const SceneArgs& s );
 void acn_launch_shade_hits( bool count, const LevelQ& q, hipStream_t stream, const SceneArgs& s,
                             unsigned long long* accum, unsigned long long* counters );
-void acn_launch_shade( int cls, KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s,
-                       unsigned long long* accum, unsigned long long* counters );
+/* k_shade, one wrapper per size class: it carries the class's lanes per task, the list it reads and its cursor */
 void acn_launch_shade64( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
 void acn_launch_shade16( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
 void acn_launch_shade4( KernelFlags, const LevelQ&, hipStream_t, const SceneArgs&, unsigned long long*, unsigned long long* );
@@ -164,24 +170,5 @@ void acn_launch_key_hist( const double* key, size_t n, unsigned long long* out_h
 
 #define ACN_SCENE_ARGS_OF( s ) ( s ).dev, ( s ).nodes, ( s ).mats, ( s ).elems, ( s ).textures
 #define ACN_TASKQ_ARGS_OF( q ) ( q ).tasks, ( q ).idx[ 0 ], ( q ).idx[ 1 ], ( q ).idx[ 2 ], ( q ).idx[ 3 ], ( q ).counts, ( q ).task_cap, ( q ).hard_shadow, ( q ).hs_cap, ( q ).emit_terms
-
-/* k_walk< C, L, R > */
-#define ACN_LW_( C, L, R ) \
-    hipLaunchKernelGGL( ( k_walk< C, L, R > ), dim3( q.walk_grid ), dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), ACN_TASKQ_ARGS_OF( q ), \
-        n_cam ? ( const RayTask* )nullptr : ( const RayTask* )q.rays[ pass & 1 ], q.ray_cap, pass, pos_xy, first_pixel, base, n_cam, order, \
-        q.rays[ ( pass + 1 ) & 1 ], q.ray_cap, last ? 0xFFFFFFFFu : q.private_limit, \
-        q.stacks, q.stack_cap, last ? q.stack_cap : q.stack_use, q.fetch_walk, q.emit_terms, accum, counters )
-
-/* body of acn_launch_shade<LPT>: shared by the four k_shade translation units */
-#define ACN_DEFINE_LAUNCH_SHADE( NAME, LPT, CLS ) \
-void NAME( KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s, unsigned long long* accum, unsigned long long* counters ) \
-{ \
-    if( f.count && f.prune ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, true, true, true );  else ACN_LS_( LPT, CLS, true, false, true ); } \
-    else if( f.count ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, true, true, false );  else ACN_LS_( LPT, CLS, true, false, false ); } \
-    else if( f.prune ) { if( f.leaf_lights ) ACN_LS_( LPT, CLS, false, true, true );  else ACN_LS_( LPT, CLS, false, false, true ); } \
-    else               { if( f.leaf_lights ) ACN_LS_( LPT, CLS, false, true, false ); else ACN_LS_( LPT, CLS, false, false, false ); } \
-}
-#define ACN_LS_( LPT, CLS, C, L, P ) hipLaunchKernelGGL( ( k_shade< LPT, C, L, P > ), dim3( q.shade_grid ), dim3( 256 ), 0, stream, ACN_SCENE_ARGS_OF( s ), \
-    ( const DTask* )q.tasks, ( const uint32_t* )q.idx[ CLS ], CLS, q.task_cap, q.fetch_shade * ( 64u / LPT ), q.children, q.child_cap, q.hard_shadow, q.hard_path, q.hs_cap, q.hard_cap, q.counts, q.shard_rank, q.shard_world, accum, counters )
 
 #endif

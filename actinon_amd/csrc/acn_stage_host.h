@@ -16,23 +16,23 @@
 #include "acn_counts.h"
 
 struct acn_stage_v3 { double x, y, z; };
-/* HitRec of acn_pipeline.h */
+/* HitRec of acn_records.h */
 struct acn_stage_hitrec
 {
     acn_stage_v3 p, d; double offs; acn_stage_v3 exit_nor, T; double intensity;
     int32_t exit_obj, enter_obj, depth; uint32_t pixel;
 };
-/* DTask of acn_pipeline.h */
+/* DTask of acn_records.h */
 struct acn_stage_dtask
 {
     acn_stage_v3 pos, surface_d, ray_projection; double theta_i, on_a, on_b, diffuse_intensity; acn_stage_v3 Tc;
     uint64_t rv; int32_t depth; uint32_t pixel;
 };
 
-/* HardShadow and HardPath of acn_pipeline.h */
+/* HardShadow and HardPath of acn_records.h */
 struct acn_stage_hardshadow { acn_stage_v3 pos, d; double limit; acn_stage_v3 contrib; uint32_t pixel, pad; };
 struct acn_stage_hardpath { acn_stage_v3 pos, d, T; double intensity; int32_t depth; uint32_t pixel, resume, pad; };
-/* RayTask of acn_pipeline.h */
+/* RayTask of acn_records.h */
 struct acn_stage_raytask { acn_stage_v3 p, d, T; double intensity; int32_t depth; uint32_t pixel; };
 
 /* what the checks read of the uploaded scene */
@@ -63,7 +63,7 @@ static inline bool acn_stage_finite_ray( const acn_stage_v3& p, const acn_stage_
 }
 #define ACN_STAGE_RESUME_FLAG 2u        /* ACN_RESUME_FLAG of acn_device.h: the word is a resume word */
 
-/* slots a wave reserves at a time: ACN_QCHUNK of k_shade, chunks_resize( n ) of k_shade_hits (acn_pipeline.h) */
+/* slots a wave reserves at a time: ACN_QCHUNK of k_shade, chunks_resize( n ) of k_shade_hits (acn_queues.h) */
 static inline uint32_t acn_stage_chunk( uint32_t stage, uint32_t n, uint32_t grid )
 {
     if( stage != ACN_STAGE_SHADE_HITS ) return 64u;

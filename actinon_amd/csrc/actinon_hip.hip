@@ -241,7 +241,7 @@ static int install_scene( acn_scene_handle* h, const acn_flat_scene* scene, int 
     h->dev.n_nodes = scene->n_nodes;
     h->dev.n_elems = scene->n_elems;
     h->dev.lds_stack = r.lds_stack_bytes ? 0u : ACN_NO_LDS_STACK;   /* the kernels that own a stack area set the offset */
-    /* Width of a shading task (size_class in acn_pipeline.h).  Narrow groups waste less of a sample loop's last round;
+    /* Width of a shading task (size_class in acn_queues.h).  Narrow groups waste less of a sample loop's last round;
      * a whole wavefront per point keeps the rays of a round on one origin, which pays when a sample's traversal is long
      * and divergent (nested compounds, CSG objects with prune programs: the scenes of the "extras" kernel variants).
      * Measured, 4 lanes: wine_glass 1080p (200 / 64 samples) 79.8 ms narrow, 85.2 wide from 33 samples; many_spheres
@@ -525,8 +525,8 @@ static int render_chunk( PipeRun* r, const Switches& sw, const Primary& prim, ui
         for( uint32_t pass = 0; pass < passes[ level ]; pass++ )
         {
             /* (the last launch of a level finishes whatever is left on the private stacks: the input of all later generations) */
-            ACN_LAUNCH( r, sw, 0, stream, acn_launch_walk( f, pass, pass + 1 == passes[ level ], q, lds, stream, s, prim.pos_xy, prim.first, base,
-                                                           level == 0 && pass == 0 ? n_cam : 0u, order, accum, counters ) );
+            const WalkLaunch w = { pass, pass + 1 == passes[ level ], prim.pos_xy, prim.first, base, level == 0 && pass == 0 ? n_cam : 0u, order, lds, accum, counters };
+            ACN_LAUNCH( r, sw, 0, stream, acn_launch_walk( f, q, w, stream, s ) );
         }
         ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade64( f, q, stream, s, accum, counters ) );
         ACN_LAUNCH( r, sw, 1, stream, acn_launch_shade16( f, q, stream, s, accum, counters ) );

@@ -7,6 +7,8 @@
  * kernels are untouched: this unit only instantiates the same templates once more. */
 #include <hip/hip_runtime.h>
 #include "acn_handle.h"
+#include "acn_kernel_params.h"
+#include "acn_variant.h"
 
 /* results per ray: ACN_Q_STRIDE doubles; integers are stored as doubles, skip masks as their 64 raw bits */
 #define ACN_Q_STRIDE ACN_QUERY_STRIDE
@@ -83,7 +85,7 @@ __device__ void query_one( const SC& scv, int op, int32_t node, V3 rp, V3 rd, do
     }
     else if( op == ACN_Q_CONE_CULL )
     {
-        /* k_shade's direct-light loop (acn_pipeline.h): node is the light, the ray origin the shading point */
+        /* k_shade's direct-light loop (acn_k_shade.h): node is the light, the ray origin the shading point */
         V3 fov_d; double cos_rs;
         obj_fov_dev( n, rp, &fov_d, &cos_rs );
         const M3 src_frame = m_con_z( fov_d );
@@ -123,8 +125,7 @@ void k_query( ACN_SCENE_PARAMS, int op, int32_t node, const double* __restrict__
     const uint64_t skip = limits ? ( ( const uint64_t* )limits )[ 2 * i + 1 ] : 0ull;
     double* o = out + ACN_Q_STRIDE * i;
     for( int k = 0; k < ACN_Q_STRIDE; k++ ) o[ k ] = 0;
-    if constexpr( LDS ) query_one( scene_view< PRUNE, true >( sc, ( LdsNodeP )acn_lds_raw ), op, node, rp, rd, limit, skip, pos_base, o );
-    else                query_one( scene_view< PRUNE, true >( sc, sc.nodes ), op, node, rp, rd, limit, skip, pos_base, o );
+    query_one( machine_view< PRUNE, LDS >( sc ), op, node, rp, rd, limit, skip, pos_base, o );
 }
 
 /* the elements of compound `node` with the device-only bits of their headers; one lane */
@@ -176,10 +177,8 @@ extern "C" int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const 
     {
         const dim3 grid( ( unsigned )( ( nr + 255 ) / 256 ) );
         const size_t lds_total = ( lds ? h->scene.lds_bytes : 0 ) + h->scene.lds_stack_bytes;
-        if( lds && prune )  hipLaunchKernelGGL( ( k_query< true, true > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-        else if( lds )      hipLaunchKernelGGL( ( k_query< true, false > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-        else if( prune )    hipLaunchKernelGGL( ( k_query< false, true > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
-        else                hipLaunchKernelGGL( ( k_query< false, false > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out );
+        acn_variant( lds, prune, [ & ]( auto L, auto P ) {
+            hipLaunchKernelGGL( ( k_query< L.value, P.value > ), grid, dim3( 256 ), lds_total, c.stream, ACN_SCENE_ARGS_OF( s ), op, node, d_rays, d_lim, nr, s.elem_pos_base, d_out ); } );
     }
     HIP_TRY( hipGetLastError() );
     if( ( st = call_end( c ) ) != ACN_OK ) return st;

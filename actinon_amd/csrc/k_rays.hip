@@ -4,7 +4,7 @@
  * it to scene_s_trans_hit + scene_s_lum.  A ray call enters the pipeline where k_walk already reads rays in every pass but
  * pass 0 of level 0: k_seed_rays fills generation 0 of level 0 with the caller's rays, and the host launches that pass with
  * no camera rays (n_cam = 0).  Everything after is the production chain, untouched.  A seed carries what k_walk gives a
- * camera ray (acn_pipeline.h, k_walk: T = 1, intensity = 1, depth = trace_depth, the slot's position as its pixel), so a
+ * camera ray (acn_k_walk.h, k_walk: T = 1, intensity = 1, depth = trace_depth, the slot's position as its pixel), so a
  * camera ray handed in as a caller's ray is traced and shaded exactly as the pipeline's own. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"

@@ -27,7 +27,7 @@
 
 static_assert( ACN_SELECT_TILE >= 256u && ACN_SELECT_TILE <= 8192u && ( ACN_SELECT_TILE & ( ACN_SELECT_TILE - 1u ) ) == 0u, "tile size" );
 
-/* (lanes_below: the mbcnt of acn_pipeline.h) */
+/* (lanes_below: the mbcnt of acn_records.h) */
 
 __global__ __launch_bounds__( 256 )
 void k_select_count( const double* __restrict__ key, size_t n, double threshold, unsigned long long* __restrict__ tile_counts )

@@ -26,15 +26,6 @@ ACN_STAGE_SAME( acn_stage_raytask, RayTask, T ); ACN_STAGE_SAME( acn_stage_rayta
 ACN_STAGE_SAME( acn_stage_raytask, RayTask, depth ); ACN_STAGE_SAME( acn_stage_raytask, RayTask, pixel );
 static_assert( ACN_STAGE_DEAD == ACN_INVALID && ACN_ORDER_SHIFT == 8, "acn_stage_host.h restates the dead mark and the tiles of the order of work" );
 
-/* the kernel of one size class (the four wrappers carry their class: the list it reads, its cursor) */
-void acn_launch_shade( int cls, KernelFlags f, const LevelQ& q, hipStream_t stream, const SceneArgs& s, unsigned long long* accum, unsigned long long* counters )
-{
-    if( cls == 0 )      acn_launch_shade64( f, q, stream, s, accum, counters );
-    else if( cls == 1 ) acn_launch_shade16( f, q, stream, s, accum, counters );
-    else if( cls == 2 ) acn_launch_shade4( f, q, stream, s, accum, counters );
-    else                acn_launch_shade1( f, q, stream, s, accum, counters );
-}
-
 static acn_stage_scene stage_scene( const acn_scene_handle* h )
 {
     acn_stage_scene sc;
@@ -61,6 +52,78 @@ extern "C" int acn_stage_plan( acn_scene_handle* h, const acn_stage_args* args, 
     return st == ACN_OK ? ACN_OK : fail( st, "acn_run_stage: " + msg );
 }
 
+/* The queues of one path level, owned for the length of a stage call; both seams run their kernels on one of these.  make(): every
+ * queue of a level exists (a kernel closes the reservations of all its queues), of its capacity in the plan and one record at least
+ * (tasks: n_tasks records, stacks: n_stacks, accum: n_accum pixels); what no kernel writes reads as dead (0xFF: pixel ACN_INVALID in every record, a dead index entry); the counter block (behind it the input count of k_shade_hits),
+ * accum and the counters are zero; q, f and s are what render_chunk passes, for these queues, the handle's tunables and the seam's
+ * flags.  The seam puts its input into the stream behind the fill, launches, and finish() waits, reads the counter block and refuses a
+ * run that raised overflow flags. */
+struct StageLevel
+{
+    struct Buf { void* d; size_t bytes; }; struct Out { void* dst; Buf from; };
+    DevCopies dc;
+    Buf tasks, idx[ ACN_NCLASS ], rays[ 2 ], children, hard_shadow, hard_path, accum;
+    uint32_t* d_counts; unsigned long long* d_counters;
+    LevelQ q; KernelFlags f; SceneArgs s;
+
+    int make( const acn_scene_handle* h, const acn_stage_caps& cap, uint32_t n_tasks, size_t n_stacks, uint32_t n_accum, uint32_t flags, hipStream_t stream )
+    {
+        auto buf = [ this ]( uint32_t n, size_t rec ) { const size_t bytes = ( size_t )( n ? n : 1u ) * rec; return Buf{ dc.make( nullptr, bytes ), bytes }; };
+        tasks = buf( n_tasks, sizeof( DTask ) );
+        for( Buf& b : idx ) b = buf( cap.cap_tasks, sizeof( uint32_t ) );
+        for( Buf& b : rays ) b = buf( cap.cap_rays, sizeof( RayTask ) );
+        children = buf( cap.cap_children, sizeof( HitRec ) ); hard_shadow = buf( cap.cap_hard_shadow, sizeof( HardShadow ) ); hard_path = buf( cap.cap_hard_path, sizeof( HardPath ) );
+        accum = buf( n_accum, sizeof( unsigned long long ) * 3 );
+        RayTask* d_stacks = ( RayTask* )dc.make( nullptr, n_stacks * sizeof( RayTask ) );
+        const size_t b_counts = sizeof( uint32_t ) * ( QC_N + 1 ), b_counters = sizeof( unsigned long long ) * ACN_CNT_SLOTS;
+        d_counts = ( uint32_t* )dc.make( nullptr, b_counts ); d_counters = ( unsigned long long* )dc.make( nullptr, b_counters );
+        const Buf* const queues[] = { &tasks, &idx[ 0 ], &idx[ 1 ], &idx[ 2 ], &idx[ 3 ], &rays[ 0 ], &rays[ 1 ], &children, &hard_shadow, &hard_path };
+        bool made = accum.d && d_stacks && d_counts && d_counters;
+        for( const Buf* b : queues ) made = made && b->d;
+        if( !made ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+        for( const Buf* b : queues ) HIP_TRY( hipMemsetAsync( b->d, 0xFF, b->bytes, stream ) );
+        HIP_TRY( hipMemsetAsync( d_counts, 0, b_counts, stream ) );
+        HIP_TRY( hipMemsetAsync( accum.d, 0, accum.bytes, stream ) );
+        HIP_TRY( hipMemsetAsync( d_counters, 0, b_counters, stream ) );
+
+        memset( &q, 0, sizeof( q ) );
+        q.tasks = ( DTask* )tasks.d; for( int k = 0; k < ACN_NCLASS; k++ ) q.idx[ k ] = ( uint32_t* )idx[ k ].d;
+        q.task_cap = cap.cap_tasks; q.child_cap = cap.cap_children; q.hs_cap = cap.cap_hard_shadow; q.hard_cap = cap.cap_hard_path; q.ray_cap = cap.cap_rays;
+        q.children = ( HitRec* )children.d; q.hard_shadow = ( HardShadow* )hard_shadow.d; q.hard_path = ( HardPath* )hard_path.d;
+        q.rays[ 0 ] = ( RayTask* )rays[ 0 ].d; q.rays[ 1 ] = ( RayTask* )rays[ 1 ].d; q.stacks = d_stacks;
+        q.counts = d_counts; q.prev_children = d_counts + QC_N;
+        q.grid = cap.grid; q.shade_grid = cap.grid; q.walk_grid = cap.grid;
+        q.fetch_walk = h->tun.fetch_walk; q.fetch_hard = h->tun.fetch_hard; q.fetch_shade = h->tun.fetch_shade; q.private_limit = h->tun.private_limit;
+        q.shard_rank = 0u; q.shard_world = 1u; q.emit_terms = flags & ACN_STAGE_NO_EMIT_TERMS ? 0u : 1u;
+        f.count = false; f.lds_nodes = h->scene.lds_bytes != 0 && !( flags & ACN_STAGE_GLOBAL_NODES );
+        f.leaf_lights = h->scene.leaf_lights && !( flags & ACN_STAGE_NO_LEAF_LIGHTS );
+        f.prune = h->scene.prune && !( flags & ACN_STAGE_NO_PRUNE );
+        DevScene dev = h->dev;
+        dev.flags = d_counts + QC_FLAGS;
+        s = scene_args( dev, h->scene );
+        return ACN_OK;
+    }
+    /* seam: the call's name; cause: what an overflow of this seam's queues means */
+    int finish( hipStream_t stream, uint32_t* out_counts, const char* seam, const char* cause )
+    {
+        HIP_TRY( hipGetLastError() );
+        HIP_TRY( hipStreamSynchronize( stream ) );
+        uint32_t counts[ QC_N ];
+        int st = DevCopies::fetch( counts, d_counts, sizeof( counts ) );
+        if( st != ACN_OK ) return st;
+        if( out_counts ) memcpy( out_counts, counts, sizeof( counts ) );
+        if( counts[ QC_FLAGS ] & ( ACN_FLAGS_CHUNK_LOST | ACN_FLAG_STACK_OVERFLOW ) )
+            return fail( ACN_ERR_DEVICE, std::string( seam ) + ": the kernel raised overflow flags " + std::to_string( counts[ QC_FLAGS ] ) + ": " + cause );
+        return ACN_OK;
+    }
+    static int fetch( std::initializer_list< Out > outs )
+    {
+        int st;
+        for( const Out& o : outs ) if( o.dst && ( st = DevCopies::fetch( o.dst, o.from.d, o.from.bytes ) ) != ACN_OK ) return st;
+        return ACN_OK;
+    }
+};
+
 extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, const acn_stage_out* out )
 {
     acn_stage_caps cap;
@@ -72,81 +135,34 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     const bool shade = a->stage == ACN_STAGE_SHADE, split = a->stage == ACN_STAGE_SHADE_HITS;
     const bool hs_in = a->stage == ACN_STAGE_HARD_SHADOW, hp_in = a->stage == ACN_STAGE_HARD_PATH;
 
-    /* the queues of one level.  Every queue exists (a kernel closes the reservations of all its queues), one record at least */
-    auto bytes_of = []( uint32_t n, size_t rec ) { return ( size_t )( n ? n : 1u ) * rec; };
-    const uint32_t n_tasks_in = shade ? a->n : 0u;                       /* SHADE reads tasks[ n ] through idx[ cls ][ n_index ] */
-    const size_t b_tasks = bytes_of( shade ? n_tasks_in : cap.cap_tasks, sizeof( DTask ) ), b_idx = bytes_of( cap.cap_tasks, sizeof( uint32_t ) );
-    const size_t b_rays = bytes_of( cap.cap_rays, sizeof( RayTask ) ), b_children = bytes_of( cap.cap_children, sizeof( HitRec ) );
-    const size_t b_hs = bytes_of( cap.cap_hard_shadow, sizeof( HardShadow ) ), b_hp = bytes_of( cap.cap_hard_path, sizeof( HardPath ) );
-    const size_t b_counts = sizeof( uint32_t ) * ( QC_N + 1 ), b_accum = sizeof( unsigned long long ) * 3 * a->n;
-    DevCopies dc;
-    DTask* d_tasks = ( DTask* )dc.make( shade ? a->in : nullptr, b_tasks );
-    uint32_t* d_idx[ ACN_NCLASS ];
-    for( int k = 0; k < ACN_NCLASS; k++ ) d_idx[ k ] = ( uint32_t* )dc.make( shade && ( uint32_t )k == a->cls ? a->index : nullptr, b_idx );
-    RayTask* d_rays = ( RayTask* )dc.make( nullptr, b_rays );
-    HitRec* d_children = ( HitRec* )dc.make( split ? a->in : nullptr, b_children );
-    HardShadow* d_hs = ( HardShadow* )dc.make( hs_in ? a->in : nullptr, b_hs );
-    HardPath* d_hp = ( HardPath* )dc.make( hp_in ? a->in : nullptr, b_hp );
-    uint32_t* d_counts = ( uint32_t* )dc.make( nullptr, b_counts );      /* the level's block, and behind it the input count of k_shade_hits */
-    unsigned long long* d_accum = ( unsigned long long* )dc.make( nullptr, b_accum );
-    unsigned long long* d_counters = ( unsigned long long* )dc.make( nullptr, sizeof( unsigned long long ) * ACN_CNT_SLOTS );
-    bool made = d_tasks && d_rays && d_children && d_hs && d_hp && d_counts && d_accum && d_counters;
-    for( int k = 0; k < ACN_NCLASS; k++ ) made = made && d_idx[ k ];
-    if( !made ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
+    StageLevel lv;   /* SHADE reads tasks[ n ] through idx[ cls ][ n_index ] */
+    if( ( st = lv.make( h, cap, shade ? a->n : cap.cap_tasks, 0, a->n, a->flags, c.stream ) ) != ACN_OK ) return st;
+    LevelQ& q = lv.q;
+    q.shard_rank = shade ? a->shard_rank : 0u; q.shard_world = shade && a->shard_world ? a->shard_world : 1u;
 
-    /* what the kernel does not write reads as dead: 0xFF is pixel ACN_INVALID in every record and a dead index entry */
-    if( !shade ) HIP_TRY( hipMemsetAsync( d_tasks, 0xFF, b_tasks, c.stream ) );
-    for( int k = 0; k < ACN_NCLASS; k++ ) if( !( shade && ( uint32_t )k == a->cls ) ) HIP_TRY( hipMemsetAsync( d_idx[ k ], 0xFF, b_idx, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_rays, 0xFF, b_rays, c.stream ) );
-    if( !split ) HIP_TRY( hipMemsetAsync( d_children, 0xFF, b_children, c.stream ) );
-    if( !hs_in ) HIP_TRY( hipMemsetAsync( d_hs, 0xFF, b_hs, c.stream ) );
-    if( !hp_in ) HIP_TRY( hipMemsetAsync( d_hp, 0xFF, b_hp, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_counts, 0, b_counts, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_accum, 0, b_accum, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS, c.stream ) );
+    /* the caller's records are the input queue, whole; SHADE: the index list goes where the kernel of `cls` reads it */
+    const StageLevel::Buf& in = shade ? lv.tasks : split ? lv.children : hs_in ? lv.hard_shadow : lv.hard_path;
+    HIP_TRY( hipMemcpyAsync( in.d, a->in, in.bytes, hipMemcpyHostToDevice, c.stream ) );
+    if( shade ) HIP_TRY( hipMemcpyAsync( lv.idx[ a->cls ].d, a->index, lv.idx[ a->cls ].bytes, hipMemcpyHostToDevice, c.stream ) );
     const uint32_t n_in = shade ? a->n_index : a->n;
     /* where the kernel reads how much input it has: its class list's mark, the previous level's children, its own queue's mark */
-    uint32_t* const d_n_in = shade ? d_counts + QC_CLASS0 + a->cls : hs_in ? d_counts + QC_HARD_SHADOW : hp_in ? d_counts + QC_HARD_PATH : d_counts + QC_N;
+    uint32_t* const d_n_in = shade ? q.counts + QC_CLASS0 + a->cls : hs_in ? q.counts + QC_HARD_SHADOW : hp_in ? q.counts + QC_HARD_PATH : q.counts + QC_N;
     HIP_TRY( hipMemcpyAsync( d_n_in, &n_in, sizeof( n_in ), hipMemcpyHostToDevice, c.stream ) );
-    HIP_TRY( hipStreamSynchronize( c.stream ) );   /* n_in leaves the stack */
+    HIP_TRY( hipStreamSynchronize( c.stream ) );   /* the caller's memory and n_in are read */
 
-    LevelQ q;
-    memset( &q, 0, sizeof( q ) );
-    q.tasks = d_tasks; for( int k = 0; k < ACN_NCLASS; k++ ) q.idx[ k ] = d_idx[ k ];
-    q.task_cap = cap.cap_tasks; q.child_cap = cap.cap_children; q.hs_cap = cap.cap_hard_shadow; q.hard_cap = cap.cap_hard_path; q.ray_cap = cap.cap_rays;
-    q.children = d_children; q.hard_shadow = d_hs; q.hard_path = d_hp; q.rays[ 0 ] = d_rays; q.rays[ 1 ] = d_rays;
-    q.counts = d_counts; q.prev_children = d_counts + QC_N;
-    q.grid = cap.grid; q.shade_grid = cap.grid; q.walk_grid = cap.grid;
-    q.fetch_walk = h->tun.fetch_walk; q.fetch_hard = h->tun.fetch_hard; q.fetch_shade = h->tun.fetch_shade; q.private_limit = h->tun.private_limit;
-    q.shard_rank = shade ? a->shard_rank : 0u; q.shard_world = shade && a->shard_world ? a->shard_world : 1u;
-    q.emit_terms = a->flags & ACN_STAGE_NO_EMIT_TERMS ? 0u : 1u;
-    KernelFlags f;
-    f.count = false; f.lds_nodes = h->scene.lds_bytes != 0;
-    f.leaf_lights = h->scene.leaf_lights && !( a->flags & ACN_STAGE_NO_LEAF_LIGHTS );
-    f.prune = h->scene.prune && !( a->flags & ACN_STAGE_NO_PRUNE );
-    DevScene dev = h->dev;
-    dev.flags = d_counts + QC_FLAGS;
-    const SceneArgs s = scene_args( dev, h->scene );
-    if( shade )      acn_launch_shade( ( int )a->cls, f, q, c.stream, s, d_accum, d_counters );
-    else if( hs_in ) acn_launch_hard_shadow( f, q, machine_lds_bytes( h->scene ), c.stream, s, d_accum, d_counters );
-    else if( hp_in ) acn_launch_hard_path( f, q, machine_lds_bytes( h->scene ), c.stream, s, d_accum, d_counters );
-    else             acn_launch_shade_hits( false, q, c.stream, s, d_accum, d_counters );
-    HIP_TRY( hipGetLastError() );
-    HIP_TRY( hipStreamSynchronize( c.stream ) );
-
-    uint32_t counts[ QC_N ];
-    if( ( st = DevCopies::fetch( counts, d_counts, sizeof( counts ) ) ) != ACN_OK ) return st;
-    if( out->counts ) memcpy( out->counts, counts, sizeof( counts ) );
-    if( counts[ QC_FLAGS ] & ( ACN_FLAGS_CHUNK_LOST | ACN_FLAG_STACK_OVERFLOW ) )
-        return fail( ACN_ERR_DEVICE, "acn_run_stage: the kernel raised overflow flags " + std::to_string( counts[ QC_FLAGS ] ) + ": a queue the plan sized was too small" );
-    struct { void* dst; const void* d; size_t bytes; } outs[] = {
-        { split ? out->tasks : nullptr, d_tasks, b_tasks },
-        { split ? ( void* )out->idx[ 0 ] : nullptr, d_idx[ 0 ], b_idx }, { split ? ( void* )out->idx[ 1 ] : nullptr, d_idx[ 1 ], b_idx },
-        { split ? ( void* )out->idx[ 2 ] : nullptr, d_idx[ 2 ], b_idx }, { split ? ( void* )out->idx[ 3 ] : nullptr, d_idx[ 3 ], b_idx },
-        { split ? out->rays : nullptr, d_rays, b_rays }, { shade || hp_in ? out->children : nullptr, d_children, b_children },
-        { shade || split || hs_in ? out->hard_shadow : nullptr, d_hs, b_hs }, { shade ? out->hard_path : nullptr, d_hp, b_hp }, { out->accum, d_accum, b_accum } };
-    for( const auto& o : outs ) if( o.dst && ( st = DevCopies::fetch( o.dst, o.d, o.bytes ) ) != ACN_OK ) return st;
-    return ACN_OK;
+    unsigned long long* const d_accum = ( unsigned long long* )lv.accum.d;
+    const auto launch_shade = a->cls == 0 ? acn_launch_shade64 : a->cls == 1 ? acn_launch_shade16 : a->cls == 2 ? acn_launch_shade4 : acn_launch_shade1;
+    if( shade )      launch_shade( lv.f, q, c.stream, lv.s, d_accum, lv.d_counters );
+    else if( hs_in ) acn_launch_hard_shadow( lv.f, q, machine_lds_bytes( h->scene ), c.stream, lv.s, d_accum, lv.d_counters );
+    else if( hp_in ) acn_launch_hard_path( lv.f, q, machine_lds_bytes( h->scene ), c.stream, lv.s, d_accum, lv.d_counters );
+    else             acn_launch_shade_hits( false, q, c.stream, lv.s, d_accum, lv.d_counters );
+    if( ( st = lv.finish( c.stream, out->counts, "acn_run_stage", "a queue the plan sized was too small" ) ) != ACN_OK ) return st;
+    return StageLevel::fetch( {
+        { split ? out->tasks : nullptr, lv.tasks },
+        { split ? ( void* )out->idx[ 0 ] : nullptr, lv.idx[ 0 ] }, { split ? ( void* )out->idx[ 1 ] : nullptr, lv.idx[ 1 ] },
+        { split ? ( void* )out->idx[ 2 ] : nullptr, lv.idx[ 2 ] }, { split ? ( void* )out->idx[ 3 ] : nullptr, lv.idx[ 3 ] },
+        { split ? out->rays : nullptr, lv.rays[ 0 ] }, { shade || hp_in ? out->children : nullptr, lv.children },
+        { shade || split || hs_in ? out->hard_shadow : nullptr, lv.hard_shadow }, { shade ? out->hard_path : nullptr, lv.hard_path }, { out->accum, lv.accum } } );
 }
 
 /* ---- the walk ---- */
@@ -167,86 +183,35 @@ extern "C" int acn_run_stage_walk( acn_scene_handle* h, const acn_stage_walk_arg
     Call c( nullptr );
     if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
 
-    const uint32_t waves = cap.grid * 4u;
-    const size_t b_tasks = ( size_t )cap.cap_tasks * sizeof( DTask ), b_idx = ( size_t )cap.cap_tasks * sizeof( uint32_t );
-    const size_t b_rays = ( size_t )cap.cap_rays * sizeof( RayTask ), b_hs = ( size_t )cap.cap_hard_shadow * sizeof( HardShadow );
-    const size_t b_stacks = ( size_t )waves * a->stack_cap * sizeof( RayTask );
-    const size_t b_counts = sizeof( uint32_t ) * QC_N, b_accum = sizeof( unsigned long long ) * 3 * a->n;
-    DevCopies dc;
-    DTask* d_tasks = ( DTask* )dc.make( nullptr, b_tasks );
-    uint32_t* d_idx[ ACN_NCLASS ];
-    for( int k = 0; k < ACN_NCLASS; k++ ) d_idx[ k ] = ( uint32_t* )dc.make( nullptr, b_idx );
-    RayTask* d_rays[ 2 ] = { ( RayTask* )dc.make( nullptr, b_rays ), ( RayTask* )dc.make( nullptr, b_rays ) };
-    RayTask* d_stacks = ( RayTask* )dc.make( nullptr, b_stacks );
-    HardShadow* d_hs = ( HardShadow* )dc.make( nullptr, b_hs );
-    /* the kernels take every queue of a level; what the walk never touches is one record */
-    HitRec* d_children = ( HitRec* )dc.make( nullptr, sizeof( HitRec ) );
-    HardPath* d_hp = ( HardPath* )dc.make( nullptr, sizeof( HardPath ) );
-    double* d_pos = a->camera && a->pos_xy ? ( double* )dc.make( a->pos_xy, sizeof( double ) * 2 * a->n ) : nullptr;
-    uint32_t* d_counts = ( uint32_t* )dc.make( nullptr, b_counts );
-    unsigned long long* d_accum = ( unsigned long long* )dc.make( nullptr, b_accum );
-    unsigned long long* d_counters = ( unsigned long long* )dc.make( nullptr, sizeof( unsigned long long ) * ACN_CNT_SLOTS );
-    bool made = d_tasks && d_rays[ 0 ] && d_rays[ 1 ] && d_stacks && d_hs && d_children && d_hp && d_counts && d_accum && d_counters && ( d_pos || !( a->camera && a->pos_xy ) );
-    for( int k = 0; k < ACN_NCLASS; k++ ) made = made && d_idx[ k ];
-    if( !made ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
-
-    /* what the kernel does not write reads as dead (0xFF: pixel ACN_INVALID, a dead index entry) */
-    HIP_TRY( hipMemsetAsync( d_tasks, 0xFF, b_tasks, c.stream ) );
-    for( int k = 0; k < ACN_NCLASS; k++ ) HIP_TRY( hipMemsetAsync( d_idx[ k ], 0xFF, b_idx, c.stream ) );
-    for( int k = 0; k < 2; k++ ) HIP_TRY( hipMemsetAsync( d_rays[ k ], 0xFF, b_rays, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_hs, 0xFF, b_hs, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_counts, 0, b_counts, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_accum, 0, b_accum, c.stream ) );
-    HIP_TRY( hipMemsetAsync( d_counters, 0, sizeof( unsigned long long ) * ACN_CNT_SLOTS, c.stream ) );
+    StageLevel lv;   /* (the kernels take every queue of a level; what the walk never touches -- children, hard paths -- is one record) */
+    if( ( st = lv.make( h, cap, cap.cap_tasks, ( size_t )cap.grid * 4u * a->stack_cap, a->n, a->flags, c.stream ) ) != ACN_OK ) return st;
+    LevelQ& q = lv.q;
+    q.stack_cap = a->stack_cap; q.stack_use = a->stack_use ? a->stack_use : a->stack_cap;
+    q.fetch_walk = a->fetch; q.private_limit = a->private_limit;
+    double* d_pos = nullptr;
+    if( a->camera && a->pos_xy && !( d_pos = ( double* )lv.dc.make( a->pos_xy, sizeof( double ) * 2 * a->n ) ) ) return fail( ACN_ERR_DEVICE, "device buffers of a host call" );
     if( !a->camera )
     {
         /* generation 0 of the level: the caller's rays, and their number where pass 0 reads it (room_rays >= n: they fit) */
-        HIP_TRY( hipMemcpyAsync( d_rays[ 0 ], a->in, ( size_t )a->n * sizeof( RayTask ), hipMemcpyHostToDevice, c.stream ) );
-        HIP_TRY( hipMemcpyAsync( d_counts + QC_GEN, &a->n, sizeof( uint32_t ), hipMemcpyHostToDevice, c.stream ) );
+        HIP_TRY( hipMemcpyAsync( q.rays[ 0 ], a->in, ( size_t )a->n * sizeof( RayTask ), hipMemcpyHostToDevice, c.stream ) );
+        HIP_TRY( hipMemcpyAsync( q.counts + QC_GEN, &a->n, sizeof( uint32_t ), hipMemcpyHostToDevice, c.stream ) );
     }
     HIP_TRY( hipStreamSynchronize( c.stream ) );   /* the caller's memory is read */
 
-    LevelQ q;
-    memset( &q, 0, sizeof( q ) );
-    q.tasks = d_tasks; for( int k = 0; k < ACN_NCLASS; k++ ) q.idx[ k ] = d_idx[ k ];
-    q.task_cap = cap.cap_tasks; q.child_cap = 1; q.hs_cap = cap.cap_hard_shadow; q.hard_cap = 1; q.ray_cap = cap.cap_rays;
-    q.children = d_children; q.hard_shadow = d_hs; q.hard_path = d_hp; q.rays[ 0 ] = d_rays[ 0 ]; q.rays[ 1 ] = d_rays[ 1 ];
-    q.stacks = d_stacks; q.stack_cap = a->stack_cap; q.stack_use = a->stack_use ? a->stack_use : a->stack_cap;
-    q.counts = d_counts; q.prev_children = d_counts + QC_CHILDREN;
-    q.grid = cap.grid; q.shade_grid = cap.grid; q.walk_grid = cap.grid;
-    q.fetch_walk = a->fetch; q.fetch_hard = h->tun.fetch_hard; q.fetch_shade = h->tun.fetch_shade; q.private_limit = a->private_limit;
-    q.shard_rank = 0u; q.shard_world = 1u;
-    q.emit_terms = a->flags & ACN_STAGE_NO_EMIT_TERMS ? 0u : 1u;
-    KernelFlags f;
-    f.count = false; f.leaf_lights = h->scene.leaf_lights;
-    f.lds_nodes = h->scene.lds_bytes != 0 && !( a->flags & ACN_STAGE_GLOBAL_NODES );
-    f.prune = h->scene.prune && !( a->flags & ACN_STAGE_NO_PRUNE );
-    DevScene dev = h->dev;
-    dev.flags = d_counts + QC_FLAGS;
-    const SceneArgs s = scene_args( dev, h->scene );
-    const size_t lds = machine_lds_bytes( h->scene );
     /* the camera form: the order of work of a render call over the n positions, every slot of its tiles in one chunk */
-    TileOrder order;
-    memset( &order, 0, sizeof( order ) );
+    TileOrder order = {};
     order.n = a->n; order.n_tiles = acn_tile_order( a->n, ACN_ORDER_SHIFT, &order.mul ); order.sample_stride = 0;
     const uint32_t n_cam = a->camera ? acn_stage_walk_slots( a ) : 0u;
     for( uint32_t pass = 0; pass < a->passes; pass++ )
     {
-        acn_launch_walk( f, pass, pass + 1 == a->passes, q, lds, c.stream, s, d_pos, ( size_t )a->first_pixel, 0u, pass == 0 ? n_cam : 0u, order, d_accum, d_counters );
+        const WalkLaunch w = { pass, pass + 1 == a->passes, d_pos, ( size_t )a->first_pixel, 0u, pass == 0 ? n_cam : 0u, order, machine_lds_bytes( h->scene ),
+                               ( unsigned long long* )lv.accum.d, lv.d_counters };
+        acn_launch_walk( lv.f, q, w, c.stream, lv.s );
         HIP_TRY( hipGetLastError() );
     }
-    HIP_TRY( hipStreamSynchronize( c.stream ) );
-
-    uint32_t counts[ QC_N ];
-    if( ( st = DevCopies::fetch( counts, d_counts, sizeof( counts ) ) ) != ACN_OK ) return st;
-    if( out->counts ) memcpy( out->counts, counts, sizeof( counts ) );
-    if( counts[ QC_FLAGS ] & ( ACN_FLAGS_CHUNK_LOST | ACN_FLAG_STACK_OVERFLOW ) )
-        return fail( ACN_ERR_DEVICE, "acn_run_stage_walk: the kernel raised overflow flags " + std::to_string( counts[ QC_FLAGS ] ) + ": room_rays is below what the walk traced" );
-    struct { void* dst; const void* d; size_t bytes; } outs[] = {
-        { out->tasks, d_tasks, b_tasks },
-        { ( void* )out->idx[ 0 ], d_idx[ 0 ], b_idx }, { ( void* )out->idx[ 1 ], d_idx[ 1 ], b_idx },
-        { ( void* )out->idx[ 2 ], d_idx[ 2 ], b_idx }, { ( void* )out->idx[ 3 ], d_idx[ 3 ], b_idx },
-        { out->rays, d_rays[ a->passes & 1 ], b_rays }, { out->hard_shadow, d_hs, b_hs }, { out->accum, d_accum, b_accum } };
-    for( const auto& o : outs ) if( o.dst && ( st = DevCopies::fetch( o.dst, o.d, o.bytes ) ) != ACN_OK ) return st;
-    return ACN_OK;
+    if( ( st = lv.finish( c.stream, out->counts, "acn_run_stage_walk", "room_rays is below what the walk traced" ) ) != ACN_OK ) return st;
+    return StageLevel::fetch( {
+        { out->tasks, lv.tasks },
+        { ( void* )out->idx[ 0 ], lv.idx[ 0 ] }, { ( void* )out->idx[ 1 ], lv.idx[ 1 ] }, { ( void* )out->idx[ 2 ], lv.idx[ 2 ] }, { ( void* )out->idx[ 3 ], lv.idx[ 3 ] },
+        { out->rays, lv.rays[ a->passes & 1 ] }, { out->hard_shadow, lv.hard_shadow }, { out->accum, lv.accum } } );
 }

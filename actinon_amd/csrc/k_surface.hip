@@ -12,8 +12,10 @@
  * stays wave-uniform.  The mode is a template argument: the FIRST_HIT kernel carries neither the loop nor the Fresnel code. */
 #include <hip/hip_runtime.h>
 #include "acn_launch.h"
+#include "acn_kernel_params.h"
+#include "acn_variant.h"
 
-/* The material rules of scene_s_lum for one hit (src/scene.c:432-470), with the expressions of shade_hit (acn_pipeline.h):
+/* The material rules of scene_s_lum for one hit (src/scene.c:432-470), with the expressions of shade_hit (acn_queues.h):
  * what the enter object sets, then what the exit object overrides. */
 struct SurfMat
 {
@@ -110,11 +112,7 @@ void k_surface( ACN_SCENE_PARAMS, const double* __restrict__ rays, const double*
 
     if constexpr( MODE == ACN_SURF_FIRST_HIT )
     {
-        if( mine )
-        {
-            if constexpr( LDS ) a = surface_trans_hit( scene_view< true, true >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &light_root );
-            else                a = surface_trans_hit( scene_view< true, true >( sc, sc.nodes ), rp, rd, &trans, &light_root );
-        }
+        if( mine ) a = surface_trans_hit( machine_view< true, LDS >( sc ), rp, rd, &trans, &light_root );
         dist = a;
         if( a < F3_INF ) kind = surface_kind( sc, surface_material( sc, trans ), trans, light_root );
     }
@@ -128,8 +126,7 @@ void k_surface( ACN_SCENE_PARAMS, const double* __restrict__ rays, const double*
             if( live )
             {
                 trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
-                if constexpr( LDS ) a = surface_trans_hit( scene_view< true, true >( sc, ( LdsNodeP )acn_lds_raw ), rp, rd, &trans, &light_root );
-                else                a = surface_trans_hit( scene_view< true, true >( sc, sc.nodes ), rp, rd, &trans, &light_root );
+                a = surface_trans_hit( machine_view< true, LDS >( sc ), rp, rd, &trans, &light_root );
                 dist += a;
                 live = a < F3_INF;
             }
@@ -209,15 +206,7 @@ void acn_launch_surface( uint32_t mode, bool lds_nodes, size_t lds_bytes, hipStr
         const double* r = rays ? rays + 6 * first : nullptr;
         const double* p = pos_xy ? pos_xy + 2 * first : nullptr;
         double* o = out + ( size_t )ACN_SURF_STRIDE * first;
-        if( mode == ACN_SURF_FOLLOW )
-        {
-            if( lds_nodes ) hipLaunchKernelGGL( ( k_surface< ACN_SURF_FOLLOW, true > ), grid, dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), r, p, cnt, o );
-            else            hipLaunchKernelGGL( ( k_surface< ACN_SURF_FOLLOW, false > ), grid, dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), r, p, cnt, o );
-        }
-        else
-        {
-            if( lds_nodes ) hipLaunchKernelGGL( ( k_surface< ACN_SURF_FIRST_HIT, true > ), grid, dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), r, p, cnt, o );
-            else            hipLaunchKernelGGL( ( k_surface< ACN_SURF_FIRST_HIT, false > ), grid, dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), r, p, cnt, o );
-        }
+        acn_variant( mode == ACN_SURF_FOLLOW, lds_nodes, [ & ]( auto F, auto L ) {
+            hipLaunchKernelGGL( ( k_surface< F.value ? ACN_SURF_FOLLOW : ACN_SURF_FIRST_HIT, L.value > ), grid, dim3( 256 ), lds_bytes, stream, ACN_SCENE_ARGS_OF( s ), r, p, cnt, o ); } );
     }
 }

@@ -1,11 +1,8 @@
 /* k_walk< false, false, * > (node array read from global memory / L2): see acn_launch.h */
 #include <hip/hip_runtime.h>
-#include "acn_launch.h"
+#include "acn_k_walk.h"
 
-void acn_launch_walk_glb( KernelFlags f, uint32_t pass, bool last, const LevelQ& q, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
-                          const double* pos_xy, size_t first_pixel, uint32_t base, uint32_t n_cam, TileOrder order,
-                          unsigned long long* accum, unsigned long long* counters )
+void acn_launch_walk_glb( KernelFlags f, const LevelQ& q, const WalkLaunch& w, hipStream_t stream, const SceneArgs& s )
 {
-    if( f.prune ) ACN_LW_( false, false, true );
-    else          ACN_LW_( false, false, false );
+    acn_variant( f.prune, [ & ]( auto P ) { ACN_LW_( false, false, P.value ); } );
 }

@@ -999,7 +999,7 @@ class Handle:
                                  None if lim is None else lim.ctypes.data, out.ctypes.data), "acn_query_rays")
         return out[:cnt]
 
-    # test seam acn_run_stage (include/actinon_hip.h): one shading kernel alone.  The records of csrc/acn_pipeline.h as numpy dtypes;
+    # test seam acn_run_stage (include/actinon_hip.h): one shading kernel alone.  The records of csrc/acn_records.h as numpy dtypes;
     # run_stage asserts their sizes against the library's
     _V = (np.float64, 3)
     STAGE_RECORDS = {

@@ -1125,7 +1125,7 @@ int acn_query_rays( acn_scene_handle* h, int op, int32_t node, const double* ray
 
 /* Test hook: one shading kernel of the pipeline alone (csrc/k_stage.hip).  acn_run_stage launches the production kernel of one stage
  * once, on queues it owns and fills from the caller's records, and fetches back everything the kernel wrote; it has no device code of
- * its own.  The records are the pipeline's own (csrc/acn_pipeline.h: HitRec, DTask, RayTask, HardShadow, HardPath), the counter block
+ * its own.  The records are the pipeline's own (csrc/acn_records.h: HitRec, DTask, RayTask, HardShadow, HardPath), the counter block
  * is the level's (QC_*, QS_* of csrc/acn_counts.h); acn_stage_info reports their sizes so that a caller asserts its layouts.
  *   ACN_STAGE_SHADE_HITS  k_shade_hits on in = HitRec[ n ]: the split of scene_s_lum.  Written: tasks, idx[ 0 .. 3 ], rays, hard_shadow
  *                         (the probes of dead children), counts, flags, accum.
@@ -1184,7 +1184,7 @@ int acn_stage_plan( acn_scene_handle* h, const acn_stage_args* args, acn_stage_c
 int acn_run_stage( acn_scene_handle* h, const acn_stage_args* args, const acn_stage_out* out );
 
 /* Test hook: the specular walk of one path level alone (csrc/k_stage.hip): the passes of k_walk in the loop of the pipeline runner,
- *     for pass in 0 .. passes - 1:  acn_launch_walk( pass, last = pass + 1 == passes, ... )
+ *     for pass in 0 .. passes - 1:  acn_launch_walk( WalkLaunch{ pass, last = pass + 1 == passes, ... } )
  * on queues the call owns.  No device code of its own, and the arrangement of the walk is the caller's: how many launches, from which
  * size of a generation on its rays are finished on the waves' private stacks (private_limit), how many slots of a stack every launch
  * but the last uses (stack_use), the fetch batch and the grid.  The arrangement decides where a ray is traced, never what it produces.

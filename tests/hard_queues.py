@@ -1,5 +1,5 @@
 """Queue layouts of the hard-ray stage tests (test_gpu_stages_hard.py) and a model of what a wave of k_hard_shadow / k_hard_path makes
-of them (acn_pipeline.h: the pending list).  A layout is a string, one letter per slot of the queue:
+of them (acn_k_hard.h: the pending list).  A layout is a string, one letter per slot of the queue:
     s   a record that is pending after the fill phase: one with a resume word, or a probe a machine element is left for
     f   a probe the fill phase finishes (an in-line element occludes it, or no machine element survives the pre-tests)
     d   a dead slot (pixel 0xFFFFFFFF)

@@ -1,4 +1,4 @@
-"""What the shading kernels (acn_pipeline.h: shade_hit, k_shade) do differently from the oracle, restated in numpy one IEEE operation
+"""What the shading kernels (acn_queues.h: shade_hit; acn_k_shade.h: k_shade) do differently from the oracle, restated in numpy one IEEE operation
 at a time, so that every intermediate is rounded as on the device.  The oracle's own arithmetic is NOT restated: it comes from the rows
 of acn_oracle_shade_point (oracle_binding.Oracle.shade_point), which scene_lum writes while it runs.
 
@@ -23,7 +23,7 @@ CLASS1_MIN = 8
 
 
 def to_fixed(x):
-    """acn_pipeline.h to_fixed: int64 per component"""
+    """acn_records.h to_fixed: int64 per component"""
     x = np.asarray(x, dtype=np.float64)
     c = np.where(x < FIX_CLAMP, x, FIX_CLAMP)
     c = np.where(c > -FIX_CLAMP, c, -FIX_CLAMP)

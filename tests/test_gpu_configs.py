@@ -63,7 +63,7 @@ def need_gpu():
 @pytest.mark.parametrize("wide", [False, True], ids=["tasks_on_16_lanes", "tasks_on_64_lanes"])
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_config_at_stated_size_matches_oracle_on_strided_pixels(oracle, name, wide, monkeypatch):
-    """Both widths of a shading task (size_class in acn_pipeline.h): a whole wavefront per point above 32 samples -- 8- and
+    """Both widths of a shading task (size_class in acn_queues.h): a whole wavefront per point above 32 samples -- 8- and
     16-round sample loops of k_shade<64> at these configs' 256 - 1024 path samples, the library's choice for these scenes --
     and 16 lanes per point whatever the count."""
     monkeypatch.setenv("ACN_CLASS0_MIN", "32" if wide else "1000000")

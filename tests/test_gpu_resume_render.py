@@ -1,4 +1,4 @@
-"""Whole frames through the resumed hard-ray kernels (acn_pipeline.h: k_hard_shadow, k_hard_path): records of k_shade,
+"""Whole frames through the resumed hard-ray kernels (acn_k_hard.h: k_hard_shadow, k_hard_path): records of k_shade,
 which carry a resume word, and the probes of k_walk, which carry none, meet in one queue and one loop.  Small frames of
 the scenes whose matter roots differ most -- 3 elements with a leaf pair beside a deep CSG object (wine_glass), 63 elements
 with machine elements beyond the positions a word can name (the lamps), a distance object (textured) -- against the CPU

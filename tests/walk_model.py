@@ -1,4 +1,4 @@
-"""The specular walk of one path level (acn_pipeline.h: k_walk) as a worklist over the oracle.  No arithmetic is restated here: a ray's
+"""The specular walk of one path level (acn_k_walk.h: k_walk) as a worklist over the oracle.  No arithmetic is restated here: a ray's
 hit is Oracle.trans_hit, what the hit produces is Oracle.shade_point (scene_lum for one hit, recorded while it runs) turned into
 records by shade_model.split_expected, and the only term the walk adds itself -- the background of a miss -- is
 to_fixed( T * ( background * intensity ) ), the order of v_mld( T, v_mlf( bg, intensity ) ).
