@@ -1845,17 +1845,31 @@ DEV uint64_t root_cone_cull( const SC& sc, int cmp, V3 pos, V3 axis, double cos_
     return skip;
 }
 
+/* The positions of the root that root_occluded_fast visits, and where it reads the root node's own fields: RootAll is every
+ * position in turn and the node itself at every call; k_shade passes the positions some lane of the wave still wants, with
+ * the node's fields resolved once per light (RootSet, acn_k_shade.h). */
+struct RootAll
+{
+    template< class NP > DEV bool env( NP o ) const { return node_has_env( o ); }
+    template< class NP > DEV int first( NP o ) const { return o->child0; }
+    template< class NP > DEV int count( NP o ) const { return o->child1; }
+    DEV bool none() const { return false; }
+    DEV int begin() const { return 0; }
+    DEV int next( int i ) { return i + 1; }
+};
+
 /* 0: not occluded, 1: occluded, 2: undecided (hard).  skip: root_cone_cull's bits.  *candidates: where the answer is 2, the
  * machine elements that were not ruled out (a candidate word; it takes the place of a `hard` flag in the loop) */
-template< class SC, class CT >
-DEV int root_occluded_fast( const SC& sc, int cmp, V3 rp, V3 rd, double limit, uint64_t skip, uint32_t* candidates, CT* cnt )
+template< class SC, class CT, class POS = RootAll >
+DEV int root_occluded_fast( const SC& sc, int cmp, V3 rp, V3 rd, double limit, uint64_t skip, uint32_t* candidates, CT* cnt, POS at = POS() )
 {
     auto o = &sc.nodes[ cmp ];
     *candidates = 0;
-    if( node_has_env( o ) && !env_ray_hits( o, rp, rd ) ) return 0;
-    int first = o->child0, count = o->child1;
+    if( !CT::counting && at.none() ) return 0;   /* (the envelope test below decides nothing then; a COUNT variant books it) */
+    if( at.env( o ) && !env_ray_hits( o, rp, rd ) ) return 0;
+    int first = at.first( o ), count = at.count( o );
     uint32_t hard = 0;
-    for( int i = 0; i < count; i++ )
+    for( int i = at.begin(); i < count; i = at.next( i ) )
     {
         if( i < 64 && ( ( skip >> i ) & 1ull ) ) continue;
         int element = __builtin_amdgcn_readfirstlane( sc.elems[ first + i ] );

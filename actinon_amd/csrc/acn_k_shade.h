@@ -99,6 +99,81 @@ template< class F > DEV M3 frame_con( const F& f )
 }
 template< class F > DEV void frame_set_con( F& f, bool w, const M3& m ) { f.set3( w, TF_CON, m.x ); f.set3( w, TF_CON + 3, m.y ); f.set3( w, TF_CON + 6, m.z ); }
 
+/* The root positions a wave's occlusion tests still visit for the light at hand (root_occluded_fast's POS).  root_cone_cull
+ * gives every task the positions no ray of its cone can hit; a position that every lane of the wave skips is visited by no
+ * sample, and on the wine glass most floor points skip them all.  So the positions some lane wants are formed once per light
+ * -- wave-uniform, bit i: position i < 64; positions from 64 on are always visited -- and the sample loop walks the set bits
+ * with scalar code instead of testing each lane's skip bit at every position.  A lane still tests a position only if its
+ * own skip bit is clear, returns at its first occluding element and ORs the same resume bits: the set only leaves out trips
+ * in which no lane did anything.  The root node's own fields are read here once as well. */
+struct RootSet
+{
+    uint64_t want;
+    int first_, count_;
+    bool env_;
+    template< class NP > DEV bool env( NP ) const { return env_; }
+    template< class NP > DEV int first( NP ) const { return first_; }
+    template< class NP > DEV int count( NP ) const { return count_; }
+    DEV bool none() const { return want == 0 && count_ <= 64; }
+    DEV int begin() const { return want ? ( int )__builtin_ctzll( want ) : 64; }
+    DEV int next( int i )
+    {
+        if( i >= 64 ) return i + 1;
+        want &= want - 1;
+        return begin();
+    }
+};
+/* (the narrow classes run one or two rounds per light, too few to earn the set back: they keep RootAll, and so do the PRUNE
+ * variants: WAVE_LOOPS in k_shade) */
+template< bool WAVE_SET, class SC > DEV auto root_set( const SC& sc, int cmp, uint64_t skip )
+{
+    if constexpr( !WAVE_SET ) return RootAll();
+    else
+    {
+        auto o = &sc.nodes[ cmp ];
+        RootSet s;
+        s.env_ = node_has_env( o ); s.first_ = o->child0; s.count_ = o->child1;
+        s.want = 0;
+        const int n = s.count_ < 64 ? s.count_ : 64;
+        for( int i = 0; i < n; i++ )
+            if( __ballot( !( ( skip >> i ) & 1ull ) ) != 0ull ) s.want |= 1ull << i;
+        return s;
+    }
+}
+
+/* The cap sample of the wide classes: v_random_sphere_cap (acn_device.h) with the quadrant of acn_sincos (acn_detmath.h) picked
+ * by selects.  The lanes of a wave fall into all four quadrants, so the switch runs every arm under its own exec mask; here the
+ * swap is bit 0 of n, the sign of the sine bit 1 of n and the sign of the cosine bit 1 of n + 1 -- four conditional moves.
+ * Same reduction, same kernels, and a negation is exact: the same bits.  (k_shade< 4 > got slower with it, 1.579 -> 1.600 ms, and
+ * the narrow classes keep the switch: profiles/r22/NOTES.md.) */
+DEV void sincos_select( double x, double* s, double* c )
+{
+    double y0, y1;
+    const int n = acn_rem_pio2( acn_fabs( x ), &y0, &y1 );
+    const double ks = acn_k_sin( y0, y1 ), kc = acn_k_cos( y0, y1 );
+    double ss = ( n & 1 ) ? kc : ks, cc = ( n & 1 ) ? ks : kc;
+    ss = ( n & 2 ) ? -ss : ss;
+    cc = ( ( n + 1 ) & 2 ) ? -cc : cc;
+    *s = ( x < 0 ) ? -ss : ss;
+    *c = cc;
+}
+template< bool SELECT > DEV V3 shade_sphere_cap( uint64_t* rv, double h )
+{
+    if constexpr( !SELECT ) return v_random_sphere_cap( rv, h );
+    else
+    {
+        V3 v;
+        double phi = 2.0 * ACN_PI * f3_rnd1( rv );
+        v.z = 1.0 - f3_rnd1( rv ) * h;
+        double scale = acn_sqrt( 1.0 - v.z * v.z );
+        double s, c;
+        sincos_select( phi, &s, &c );
+        v.x = s * scale;
+        v.y = c * scale;
+        return v;
+    }
+}
+
 /* LEAF_LIGHTS: every light is a plane / sphere / squaroid-free leaf, so the kernel contains no call into the CSG
  * machine at all (the usual case); otherwise the light hit goes through the generic element test.
  * The tasks are idx[ 0 .. min( p_counts[ QC_CLASS0 + cls ], task_cap ) ) (dead entries skipped); the persistent waves of
@@ -119,6 +194,9 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
     ACN_PHASE_INIT
     constexpr int G = 64 / LPT;
     constexpr bool FRAME_IN_LDS = LPT >= 16;
+    /* the wave's root set and the cap sample by selects (RootSet, shade_sphere_cap above): the wide classes without the interval
+     * stack of the PRUNE variants, which spilled more with them and got slower (many_spheres +1 %, profiles/r22/NOTES.md) */
+    constexpr bool WAVE_LOOPS = FRAME_IN_LDS && !PRUNE;
     __shared__ __attribute__( ( aligned( 16 ) ) ) double acn_task_frames[ FRAME_IN_LDS ? ( 256 / LPT ) * TF_N : 1 ];
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPT;
@@ -206,6 +284,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 fr_.set3( writer, TF_SCALE, mk( Tc.x * ( light_color.x * norm ), Tc.y * ( light_color.y * norm ), Tc.z * ( light_color.z * norm ) ) );
                 fr_.publish();
             }
+            const auto root_at = root_set< WAVE_LOOPS >( scp, sc.matter_root, skip );
 
             double s = 0;
             /* ACN_SHARD_SAMPLES (shard_world > 1, level 0 only): this rank's share of the loop; sample j keeps its
@@ -225,7 +304,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 rvj = lcg_stride< LPT >( rvj );
                 cnt.inc( CNT_CAP_SAMPLE );
                 cnt.cost( ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
-                const V3 cap = v_random_sphere_cap( &r, F.get( TF_CYL_HGT ) );
+                const V3 cap = shade_sphere_cap< WAVE_LOOPS >( &r, F.get( TF_CYL_HGT ) );
                 const V3 out_d = m_mlv( frame_con( F ), cap );
                 double weight = v_mlv( out_d, F.get3( TF_SURFACE_D ) );
                 ACN_LAP( PH_M_LEAF );
@@ -238,7 +317,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 cnt.inc( CNT_SHADOW_RAY );
                 ACN_LAP( PH_M_FRAME );
                 uint32_t cand;   /* occ == 2: the machine elements left for k_hard_shadow */
-                int occ = root_occluded_fast( scp, sc.matter_root, pos, out_d, a, skip, &cand, &cnt );
+                int occ = root_occluded_fast( scp, sc.matter_root, pos, out_d, a, skip, &cand, &cnt, root_at );
                 ACN_LAP( PH_M_SIDE );
                 if( occ == 1 ) continue;
                 /* what the sample adds if it is not occluded (scene.c:569-574); the weight of a direct-light sample only scales its
@@ -312,7 +391,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 rvj = lcg_stride< LPT >( rvj );
                 cnt.inc( CNT_CAP_SAMPLE );
                 cnt.cost( ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
-                const V3 cap = v_random_sphere_cap( &r, 1.0 );
+                const V3 cap = shade_sphere_cap< WAVE_LOOPS >( &r, 1.0 );
                 const V3 out_d = m_mlv( frame_con( F ), cap );
                 double weight = v_mlv( out_d, F.get3( TF_SURFACE_D ) );
                 bool live = weight > 0;
