@@ -8,9 +8,9 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # see actinon_hip.hip (concur
 
 from . import abi
 from ._lib import AcnError, check, hip, host
-from .scene import (Flat, Handle, KeptHandle, LensStats, Scene, Surface, cps_from_cl, detmath_eval, device_count, key_hist_edge, key_hist_threshold,
-                    main_pass_positions, motion_from_scenes, run_script, v3)
+from .scene import (Flat, Frame, Handle, KeptHandle, LensStats, Scene, Surface, cps_from_cl, detmath_eval, device_count, key_hist_edge, key_hist_threshold,
+                    lcg00_jump, main_pass_positions, motion_from_scenes, run_script, set_host_cycles, v3)
 from .motion import rigid_copy
 
-__all__ = ["abi", "AcnError", "check", "hip", "host", "Flat", "Handle", "KeptHandle", "LensStats", "Scene", "Surface", "cps_from_cl", "detmath_eval", "run_script",
-           "device_count", "key_hist_edge", "key_hist_threshold", "main_pass_positions", "motion_from_scenes", "rigid_copy", "v3"]
+__all__ = ["abi", "AcnError", "check", "hip", "host", "Flat", "Frame", "Handle", "KeptHandle", "LensStats", "Scene", "Surface", "cps_from_cl", "detmath_eval", "run_script",
+           "device_count", "key_hist_edge", "key_hist_threshold", "lcg00_jump", "main_pass_positions", "motion_from_scenes", "rigid_copy", "set_host_cycles", "v3"]

@@ -41,7 +41,9 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_sc
                "acn_render_lens_layers_main_pass_dev", "acn_denoise_layers", "acn_denoise_layers_dev",
                "acn_lens_layers_merge", "acn_lens_layers_merge_dev", "acn_lens_layers_resolve_dev",
                "acn_project_points", "acn_project_points_dev", "acn_reproject", "acn_reproject_dev",
-               "acn_reproject_moving", "acn_reproject_moving_dev", "acn_motion_from_scenes"]
+               "acn_reproject_moving", "acn_reproject_moving_dev", "acn_motion_from_scenes",
+               "acn_frame_create", "acn_frame_free", "acn_frame_upload", "acn_frame_download", "acn_frame_main_pass", "acn_frame_plan",
+               "acn_frame_render", "acn_frame_push", "acn_frame_pass", "acn_frame_image", "acn_frame_view", "acn_lcg00_jump"]
 # symbols declared by include/acn_scene.h
 HOST_SYMBOLS = ["acn_rotx", "acn_roty", "acn_rotz", "acn_obj_plane_s_create", "acn_obj_sphere_s_create",
                 "acn_obj_squaroid_s_create_squaroid", "acn_obj_squaroid_s_create_ellipsoid",
@@ -59,7 +61,7 @@ HOST_SYMBOLS = ["acn_rotx", "acn_roty", "acn_rotz", "acn_obj_plane_s_create", "a
                 "acn_compound_s_clear", "acn_compound_s_set_sphere_envelopes", "acn_scene_s_create",
                 "acn_scene_s_discard", "acn_scene_s_clear", "acn_scene_s_push", "acn_scene_s_objects",
                 "acn_scene_s_flatten", "acn_flat_scene_free", "acn_obj_flatten", "acn_lum_machine_s_run",
-                "acn_scene_s_create_image_file", "acn_scene_s_create_image_file_keep", "acn_write_pnm", "acn_cps_from_cl", "acn_scene_primitives",
+                "acn_scene_s_create_image_file", "acn_scene_s_create_image_file_keep", "acn_write_pnm", "acn_write_pnm8", "acn_cps_from_cl", "acn_scene_primitives",
                 "acn_scene_wine_glass", "acn_scene_diamond", "acn_scene_many_spheres", "acn_obj_get_pos",
                 "acn_obj_sphere_s_get_radius", "acn_obj_get_field", "acn_obj_set_field", "acn_set_envelope_estimator"]
 # symbols declared by include/acn_interp.h
@@ -130,6 +132,20 @@ hip.acn_key_hist_edge.argtypes = [C.c_uint32]
 hip.acn_key_hist_edge.restype = C.c_double
 hip.acn_key_hist_threshold.argtypes = [vp, C.c_uint64]
 hip.acn_key_hist_threshold.restype = C.c_double
+hip.acn_frame_create.argtypes = [vp, C.c_uint64, C.c_uint64, P(vp)]
+hip.acn_frame_free.argtypes = [vp]
+hip.acn_frame_free.restype = None
+hip.acn_frame_upload.argtypes = [vp, vp]
+hip.acn_frame_download.argtypes = [vp, vp]
+hip.acn_frame_main_pass.argtypes = [vp, P(abi.RenderOpts)]
+hip.acn_frame_plan.argtypes = [vp, C.c_double, C.c_uint64, C.c_uint64, P(C.c_uint64), P(C.c_uint64)]
+hip.acn_frame_render.argtypes = [vp, P(abi.RenderOpts)]
+hip.acn_frame_push.argtypes = [vp]
+hip.acn_frame_pass.argtypes = [vp, C.c_double, C.c_uint64, P(C.c_uint64), P(C.c_uint64), P(abi.RenderOpts)]
+hip.acn_frame_image.argtypes = [vp, vp, vp]
+hip.acn_frame_view.argtypes = [vp, P(abi.FrameBuffers)]
+hip.acn_lcg00_jump.argtypes = [C.c_uint64, C.c_uint64]
+hip.acn_lcg00_jump.restype = C.c_uint64
 hip.acn_resolve_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, P(abi.RenderOpts)]
 hip.acn_last_kernel_ms.argtypes = [vp, P(C.c_double)]
 hip.acn_last_stage_ms.argtypes = [vp, P(C.c_double), C.c_int]
@@ -267,6 +283,7 @@ host.acn_lum_machine_s_run.argtypes = [vp, vp, C.c_size_t]
 host.acn_scene_s_create_image_file.argtypes = [vp, C.c_char_p]
 host.acn_scene_s_create_image_file_keep.argtypes = [vp, C.c_char_p, P(vp)]
 host.acn_write_pnm.argtypes = [C.c_char_p, vp, C.c_size_t, C.c_size_t]
+host.acn_write_pnm8.argtypes = [C.c_char_p, vp, C.c_size_t, C.c_size_t]
 host.acn_cps_from_cl.argtypes = [P(C.c_double)]
 host.acn_cps_from_cl.restype = C.c_uint32
 

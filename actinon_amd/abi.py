@@ -109,6 +109,13 @@ class SelectParams(C.Structure):
                 ("raster_width", C.c_uint64), ("raster_first", C.c_uint64)]
 
 
+class FrameBuffers(C.Structure):
+    """acn_frame_buffers: what acn_frame_view reports of a device-resident frame"""
+    _fields_ = [("struct_size", C.c_uint32), ("planned", C.c_uint32), ("width", C.c_uint64), ("height", C.c_uint64),
+                ("flagged", C.c_uint64), ("samples", C.c_uint64), ("d_accumulator", C.c_void_p), ("d_key", C.c_void_p),
+                ("d_index", C.c_void_p), ("d_positions", C.c_void_p), ("d_colours", C.c_void_p)]
+
+
 class ReprojectParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("reject_kinds", C.c_uint32), ("max_hops", C.c_int32),
                 ("normal_min", C.c_double), ("plane_tolerance", C.c_double), ("max_history", C.c_double)]
@@ -169,4 +176,5 @@ assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
 assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)
 assert C.sizeof(SelectParams) == 40, C.sizeof(SelectParams)
 assert C.sizeof(ReprojectParams) == 40, C.sizeof(ReprojectParams)
+assert C.sizeof(FrameBuffers) == 80, C.sizeof(FrameBuffers)
 assert C.sizeof(StageWalkArgs) == 72, C.sizeof(StageWalkArgs)

@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), the device-resident frame, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points.
  * The lens calls that cut their positions into slices share one loop, lens_slices; a host-buffer form is a HostCall (acn_handle.h). */
@@ -1065,6 +1065,256 @@ extern "C" int acn_key_histogram( acn_scene_handle* h, const double* key, size_t
 
 extern "C" double acn_key_hist_edge( uint32_t bin ) { return acn_select_hist_edge( bin ); }
 extern "C" double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget ) { return acn_select_hist_threshold( hist, budget ); }
+
+/* ---- the device-resident frame (k_frame.hip; the checks and every expression: acn_frame_host.h) ---- */
+/* every frame call works on the handle's own stream and waits for it */
+static int frame_begin( acn_frame* f, hipStream_t* stream )
+{
+    HIP_TRY( hipSetDevice( f->h->device ) );
+    *stream = f->h->run.stream.get();
+    return ACN_OK;
+}
+
+static const long long* frame_index( const acn_frame* f ) { return f->centres ? nullptr : f->d_index.get(); }
+
+/* the slices of the current plan, in order: body( g0, groups ) of whole groups, at most the handle's slice bound of positions each */
+template< class Body >
+static int frame_slices( const acn_frame* f, Body body )
+{
+    const uint64_t per = acn_frame_slice_groups( f->h->tun.frame_slice, f->samples );
+    for( uint64_t g0 = 0; g0 < f->flagged; g0 += per )
+    {
+        const int st = body( g0, f->flagged - g0 < per ? f->flagged - g0 : per );
+        if( st != ACN_OK ) return st;
+    }
+    return ACN_OK;
+}
+
+/* the entry buffers of a plan of `flagged` groups, and its positions */
+static int frame_plan_entries( acn_frame* f, bool centres, uint64_t flagged, uint64_t samples, uint64_t rval, hipStream_t stream )
+{
+    const uint64_t entries = flagged * samples;
+    if( entries && ( f->d_pos.grow( sizeof( double ) * 2 * entries ) || f->d_clr.grow( sizeof( double ) * 3 * entries ) ) ) return ACN_ERR_DEVICE;
+    f->centres = centres; f->flagged = flagged; f->samples = samples;
+    int st = frame_slices( f, [ & ]( uint64_t g0, uint64_t groups )
+    {
+        acn_launch_frame_jitter( frame_index( f ), g0 * samples, groups * samples, samples, rval, f->width, f->d_pos.get(), stream );
+        HIP_TRY( hipGetLastError() );
+        return ( int )ACN_OK;
+    } );
+    if( st == ACN_OK && entries ) HIP_TRY( hipStreamSynchronize( stream ) );
+    f->planned = st == ACN_OK;
+    return st;
+}
+
+static int frame_plan( acn_frame* f, double sqr_threshold, uint64_t samples, uint64_t rval, uint64_t* out_flagged, uint64_t* out_rval )
+{
+    std::string msg;
+    if( acn_frame_plan_check( f != nullptr, f && f->planned, sqr_threshold, samples, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    acn_scene_handle* h = f->h;
+    const uint64_t n = f->width * f->height;
+    const size_t words = ( size_t )acn_select_tiles( n ) + 1;
+    if( h->d_select_tiles.grow( sizeof( unsigned long long ) * words ) ) return ACN_ERR_DEVICE;
+    acn_launch_frame_key( f->d_acc.get(), f->width, f->height, f->d_key.get(), stream );
+    HIP_TRY( hipGetLastError() );
+    acn_launch_select( f->d_key.get(), n, sqr_threshold, h->d_select_tiles.get(), n, nullptr, f->width, 0, ( int64_t* )f->d_index.get(), nullptr, nullptr, stream );
+    HIP_TRY( hipGetLastError() );
+    unsigned long long flagged = 0;
+    HIP_TRY( hipMemcpyAsync( &flagged, h->d_select_tiles.get() + ( words - 1 ), sizeof( flagged ), hipMemcpyDeviceToHost, stream ) );
+    HIP_TRY( hipStreamSynchronize( stream ) );
+    if( ( st = frame_plan_entries( f, false, flagged, samples, rval, stream ) ) != ACN_OK ) return st;
+    if( out_flagged ) *out_flagged = flagged;
+    if( out_rval ) *out_rval = acn_frame_lcg00_jump( rval, 2 * samples * flagged );
+    return ACN_OK;
+}
+
+static int frame_render( acn_frame* f, const Call& c )
+{
+    std::string msg;
+    if( acn_frame_step_check( f != nullptr, f && f->planned, "render", c.opts.shard_world, f ? f->width : 0, f ? f->height : 0,
+                              f ? f->h->dev.prm.image_width : 0, f ? f->h->dev.prm.image_height : 0, true, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    acn_render_opts opts = c.opts;
+    opts.stream = nullptr;
+    st = frame_slices( f, [ & ]( uint64_t g0, uint64_t groups )
+    {
+        const uint64_t e0 = g0 * f->samples;
+        return render_dispatch( f->h, primary_positions( f->d_pos.get() + 2 * e0 ), ( size_t )( groups * f->samples ), f->d_clr.get() + 3 * e0, &opts, stream );
+    } );
+    if( st == ACN_OK ) HIP_TRY( hipStreamSynchronize( stream ) );
+    return st;
+}
+
+static int frame_push( acn_frame* f )
+{
+    std::string msg;
+    if( acn_frame_step_check( f != nullptr, f && f->planned, "push", 0, 0, 0, 0, 0, false, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    f->planned = false;   /* consumed, whatever happens now */
+    const uint64_t entries = f->flagged * f->samples;
+    if( entries == 0 ) return ACN_OK;
+    const uint32_t slots = f->h->tun.frame_foreign_slots;
+    if( !f->centres )   /* (a pixel centre has no foreign target) */
+    {
+        if( f->d_foreign.grow( sizeof( unsigned long long ) * ( 1 + ( size_t )slots ) ) ) return ACN_ERR_DEVICE;
+        acn_launch_frame_foreign( frame_index( f ), f->d_pos.get(), f->d_clr.get(), entries, f->samples, f->width, f->height, slots, f->d_foreign.get(),
+                                  f->d_acc.get(), stream );
+        HIP_TRY( hipGetLastError() );
+    }
+    st = frame_slices( f, [ & ]( uint64_t g0, uint64_t groups )
+    {
+        acn_launch_frame_push( frame_index( f ), f->d_pos.get(), f->d_clr.get(), g0, groups, f->samples, f->width, f->height, f->d_acc.get(), stream );
+        HIP_TRY( hipGetLastError() );
+        return ( int )ACN_OK;
+    } );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_frame_create( acn_scene_handle* h, uint64_t width, uint64_t height, acn_frame** out )
+{
+    std::string msg;
+    if( acn_frame_create_check( h != nullptr, width, height, out, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    HIP_TRY( hipSetDevice( h->device ) );
+    std::unique_ptr< acn_frame > f( new acn_frame );
+    f->h = h; f->width = width; f->height = height;
+    const size_t n = ( size_t )( width * height );
+    if( f->d_acc.grow( sizeof( double ) * 6 * n ) || f->d_key.grow( sizeof( double ) * n ) || f->d_index.grow( sizeof( long long ) * n ) ) return ACN_ERR_DEVICE;
+    HIP_TRY( hipMemsetAsync( f->d_acc.get(), 0, sizeof( double ) * 6 * n, h->run.stream.get() ) );
+    HIP_TRY( hipStreamSynchronize( h->run.stream.get() ) );
+    *out = f.get();
+    h->frames.push_back( std::move( f ) );
+    return ACN_OK;
+}
+
+extern "C" void acn_frame_free( acn_frame* f )
+{
+    if( !f ) return;
+    acn_scene_handle* h = f->h;
+    hipSetDevice( h->device );
+    for( size_t i = 0; i < h->frames.size(); i++ )
+        if( h->frames[ i ].get() == f ) { h->frames.erase( h->frames.begin() + ( long )i ); return; }
+}
+
+extern "C" int acn_frame_upload( acn_frame* f, const double* lum )
+{
+    std::string msg;
+    if( acn_frame_copy_check( f != nullptr, lum, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    f->planned = false;
+    HIP_TRY( hipMemcpy( f->d_acc.get(), lum, sizeof( double ) * 6 * f->width * f->height, hipMemcpyHostToDevice ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_frame_download( acn_frame* f, double* lum )
+{
+    std::string msg;
+    if( acn_frame_copy_check( f != nullptr, lum, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    HIP_TRY( hipMemcpy( lum, f->d_acc.get(), sizeof( double ) * 6 * f->width * f->height, hipMemcpyDeviceToHost ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_frame_plan( acn_frame* f, double sqr_threshold, uint64_t samples, uint64_t rval, uint64_t* out_flagged, uint64_t* out_rval )
+{
+    return frame_plan( f, sqr_threshold, samples, rval, out_flagged, out_rval );
+}
+
+extern "C" int acn_frame_render( acn_frame* f, const acn_render_opts* opts )
+{
+    Call c( opts );
+    return frame_render( f, c );
+}
+
+extern "C" int acn_frame_push( acn_frame* f ) { return frame_push( f ); }
+
+/* render, the cancel flag once more, push; a pass that does not get to its push drops its plan */
+static int frame_render_push( acn_frame* f, const Call& c )
+{
+    int st = frame_render( f, c );
+    if( st == ACN_OK && c.opts.cancel && *c.opts.cancel ) st = fail( ACN_ERR_CANCELLED, "cancelled" );
+    if( st != ACN_OK ) { f->planned = false; return st; }
+    return frame_push( f );
+}
+
+extern "C" int acn_frame_main_pass( acn_frame* f, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_frame_plan_check( f != nullptr, f && f->planned, 0.0, 1, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( acn_frame_step_check( true, true, "render", c.opts.shard_world, f->width, f->height, f->h->dev.prm.image_width, f->h->dev.prm.image_height, true,
+                              &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    if( ( st = frame_plan_entries( f, true, f->width * f->height, 1, 0, stream ) ) != ACN_OK ) return st;
+    return frame_render_push( f, c );
+}
+
+extern "C" int acn_frame_pass( acn_frame* f, double sqr_threshold, uint64_t samples, uint64_t* rval, uint64_t* out_flagged, const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    if( acn_frame_pass_check( f != nullptr, rval, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( acn_frame_plan_check( true, f->planned, sqr_threshold, samples, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( acn_frame_step_check( true, true, "render", c.opts.shard_world, f->width, f->height, f->h->dev.prm.image_width, f->h->dev.prm.image_height, true,
+                              &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    uint64_t flagged = 0, next = 0;
+    int st = frame_plan( f, sqr_threshold, samples, *rval, &flagged, &next );
+    if( st != ACN_OK ) return st;
+    if( ( st = frame_render_push( f, c ) ) != ACN_OK ) return st;
+    *rval = next;
+    if( out_flagged ) *out_flagged = flagged;
+    return ACN_OK;
+}
+
+extern "C" int acn_frame_image( acn_frame* f, double* out_rgb, uint8_t* out_rgb8 )
+{
+    if( !f ) return fail( ACN_ERR_ARG, "null argument: frame" );
+    if( !out_rgb && !out_rgb8 ) return ACN_OK;
+    hipStream_t stream;
+    int st = frame_begin( f, &stream );
+    if( st != ACN_OK ) return st;
+    const size_t n = ( size_t )( f->width * f->height ), rgb_bytes = sizeof( double ) * 3 * n;
+    if( f->d_image.grow( rgb_bytes + 3 * n ) ) return ACN_ERR_DEVICE;
+    double* d_rgb = ( double* )f->d_image.get();
+    unsigned char* d_rgb8 = ( unsigned char* )f->d_image.get() + rgb_bytes;
+    acn_launch_frame_image( f->d_acc.get(), n, out_rgb ? d_rgb : nullptr, out_rgb8 ? d_rgb8 : nullptr, stream );
+    HIP_TRY( hipGetLastError() );
+    if( out_rgb ) HIP_TRY( hipMemcpyAsync( out_rgb, d_rgb, rgb_bytes, hipMemcpyDeviceToHost, stream ) );
+    if( out_rgb8 ) HIP_TRY( hipMemcpyAsync( out_rgb8, d_rgb8, 3 * n, hipMemcpyDeviceToHost, stream ) );
+    HIP_TRY( hipStreamSynchronize( stream ) );
+    return ACN_OK;
+}
+
+extern "C" int acn_frame_view( acn_frame* f, acn_frame_buffers* out )
+{
+    std::string msg;
+    if( acn_frame_view_check( f != nullptr, out, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    acn_frame_buffers b{};
+    b.struct_size = out->struct_size < sizeof( b ) ? out->struct_size : ( uint32_t )sizeof( b );
+    b.planned = f->planned ? 1u : 0u;
+    b.width = f->width; b.height = f->height;
+    b.flagged = f->planned ? f->flagged : 0; b.samples = f->planned ? f->samples : 0;
+    b.d_accumulator = f->d_acc.get(); b.d_key = f->d_key.get(); b.d_index = f->d_index.get();
+    b.d_positions = f->d_pos.get(); b.d_colours = f->d_clr.get();
+    memcpy( out, &b, b.struct_size );
+    return ACN_OK;
+}
+
+extern "C" uint64_t acn_lcg00_jump( uint64_t rval, uint64_t draws ) { return acn_frame_lcg00_jump( rval, draws ); }
 
 /* ---- test seams: the envelope estimate and the deterministic math library, on the device's arithmetic ---- */
 extern "C" int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_t samples, uint32_t rseed,

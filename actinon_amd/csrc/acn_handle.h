@@ -22,6 +22,7 @@
 #include "acn_chunkplan.h"
 #include "acn_queueplan.h"
 #include "acn_devbuf.h"
+#include "acn_frame_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* error plumbing */
@@ -124,6 +125,8 @@ struct Tunables
                                           417 - 426 -> 390 - 401); upload + first frame: 1080p 247 - 299 -> 277 - 323 ms, c2 189 - 261 -> 195 - 204, the
                                           lamps +30.  For a host that uploads long before it renders */
     size_t   lens_slice_rays = ( size_t )1 << 21;   /* ACN_LENS_SLICE_RAYS: rays of one slice of a lens call (acn_render_lens*): floor( this / K ) positions, at least 1 */
+    size_t   frame_slice = ACN_FRAME_SLICE;         /* ACN_FRAME_SLICE: positions of one slice of a frame pass (acn_frame_*), whole pixels, at least one */
+    uint32_t frame_foreign_slots = ACN_FRAME_FOREIGN_SLOTS;   /* ACN_FRAME_FOREIGN_SLOTS: foreign entries acn_frame_push lists, at most 1024; more are found by one lane's walk */
     bool     count_work = false;       /* ACN_COUNT_WORK */
     bool     stage_timing = false;     /* ACN_STAGE_TIMING */
     acn_table_opts tables;             /* the switches of the scene tables (acn_tables.h) */
@@ -155,6 +158,10 @@ struct Tunables
         if( const char* e = getenv( "ACN_PRIVATE_LIMIT" ) ) { private_limit = ( uint32_t )atoll( e ); private_limit_set = true; }
         if( const char* e = getenv( "ACN_LENS_SLICE_RAYS" ) ) lens_slice_rays = ( size_t )atoll( e );
         if( lens_slice_rays < 1 ) lens_slice_rays = 1;
+        if( const char* e = getenv( "ACN_FRAME_SLICE" ) ) frame_slice = ( size_t )atoll( e );
+        if( frame_slice < 1 || frame_slice > ACN_FRAME_SLICE ) frame_slice = ACN_FRAME_SLICE;
+        if( const char* e = getenv( "ACN_FRAME_FOREIGN_SLOTS" ) ) frame_foreign_slots = ( uint32_t )atoll( e );
+        if( frame_foreign_slots > ACN_FRAME_FOREIGN_SLOTS ) frame_foreign_slots = ACN_FRAME_FOREIGN_SLOTS;
         if( lens_slice_rays > ( ( size_t )1 << 28 ) ) lens_slice_rays = ( size_t )1 << 28;
         if( walk_passes < 1 ) walk_passes = 1;
         if( walk_passes > ACN_MAX_WALK_PASSES ) walk_passes = ACN_MAX_WALK_PASSES;
@@ -261,6 +268,21 @@ struct Switches
 
 struct acn_scene_handle;
 
+/* A device-resident frame (include/actinon_hip.h, acn_frame_*; the entry points: acn_calls.hip): owned by its handle */
+struct acn_frame
+{
+    acn_scene_handle* h = nullptr;
+    uint64_t width = 0, height = 0;
+    DevBuf< double > d_acc;                    /* [ height * width ][ 6 ]: the layout of acn_lum */
+    DevBuf< double > d_key;                    /* [ height * width ] */
+    DevBuf< long long > d_index;               /* the flagged pixels of a gradient plan, ascending */
+    DevBuf< double > d_pos, d_clr;             /* the entries of the plan: [ flagged * samples ][ 2 ], [ . ][ 3 ] */
+    DevBuf< unsigned long long > d_foreign;    /* push: the number of foreign entries, then ACN_FRAME_FOREIGN_SLOTS of them */
+    DevBuf< void > d_image;                    /* acn_frame_image: rgb f64, then rgb8 */
+    bool planned = false, centres = false;     /* a plan no push has consumed; ... of the main pass: no index list */
+    uint64_t flagged = 0, samples = 0;         /* of that plan */
+};
+
 /* One pipeline runner: what launch_render needs to work a call off on one stream.  A handle has its own, for a call that runs
  * alone, and one per concurrent lane (render_lanes); all of them read the scene, the tunables and the budget of the handle. */
 struct PipeRun
@@ -338,6 +360,7 @@ struct acn_scene_handle
     DevBuf< double > d_lens_rad;                    /* ... their radiance [ 3 ], grown by the calls that render, */
     DevBuf< double > d_lens_surf;                   /* ... and their surface records [ 16 ], grown by the calls that take records */
     DevBuf< unsigned long long > d_select_tiles;    /* acn_select_above*: the counts per tile and their total */
+    std::vector< std::unique_ptr< acn_frame > > frames;   /* acn_frame_create: what acn_frame_free has not released goes with the handle */
 };
 
 static SceneArgs scene_args( const DevScene& dev, const acn_scene_handle::Resident& r )

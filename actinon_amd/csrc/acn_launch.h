@@ -168,6 +168,21 @@ void acn_launch_select( const double* key, size_t n, double threshold, unsigned 
                         double* out_pos_xy, unsigned long long* out_count, hipStream_t stream );
 void acn_launch_key_hist( const double* key, size_t n, unsigned long long* out_hist, hipStream_t stream );
 
+/* the device-resident frame (k_frame.hip; include/actinon_hip.h states every step, acn_frame_host.h holds the expressions), after the
+ * host's checks.  acc [ height * width ][ 6 ], 16-byte aligned; index: the flagged pixels, or null for the plan of the main pass (group
+ * r is pixel r); pos_xy [ entries ][ 2 ] and clr [ entries ][ 3 ] with entries = groups * samples.
+ * key: every pixel.  jitter: entries [ e0, e0 + cnt ), cnt >= 1 and at most 2^24.  foreign: zeroes the count, lists the foreign entries
+ * of the whole plan in foreign [ 1 + slots ] and adds them with one lane.  push: groups [ g0, g0 + cnt ), their own entries.
+ * image: out_rgb [ pixels ][ 3 ] f64 and out_rgb8 [ pixels ][ 3 ], each nullable. */
+void acn_launch_frame_key( const double* acc, uint64_t width, uint64_t height, double* key, hipStream_t stream );
+void acn_launch_frame_jitter( const long long* index, uint64_t e0, uint64_t cnt, uint64_t samples, uint64_t rval, uint64_t width, double* pos_xy,
+                              hipStream_t stream );
+void acn_launch_frame_foreign( const long long* index, const double* pos_xy, const double* clr, uint64_t entries, uint64_t samples, uint64_t width,
+                               uint64_t height, uint32_t slots, unsigned long long* foreign, double* acc, hipStream_t stream );
+void acn_launch_frame_push( const long long* index, const double* pos_xy, const double* clr, uint64_t g0, uint64_t cnt, uint64_t samples,
+                            uint64_t width, uint64_t height, double* acc, hipStream_t stream );
+void acn_launch_frame_image( const double* acc, uint64_t pixels, double* out_rgb, unsigned char* out_rgb8, hipStream_t stream );
+
 #define ACN_SCENE_ARGS_OF( s ) ( s ).dev, ( s ).nodes, ( s ).mats, ( s ).elems, ( s ).textures
 #define ACN_TASKQ_ARGS_OF( q ) ( q ).tasks, ( q ).idx[ 0 ], ( q ).idx[ 1 ], ( q ).idx[ 2 ], ( q ).idx[ 3 ], ( q ).counts, ( q ).task_cap, ( q ).hard_shadow, ( q ).hs_cap, ( q ).emit_terms
 

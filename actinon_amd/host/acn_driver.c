@@ -6,6 +6,8 @@
  *   acn_write_pnm / acn_cps_from_cl<- image_cps_s_write_pnm, cps_from_cl   src/scene.c:76-82,122-137
  *
  *   SIGINT soft stop + recovery file <- signal_callabck, scene.c:887-895, 1046-1091, 1138-1147
+ *   cycles_on_frame                <- the same cycles on a device-resident frame (acn_frame_*): the default; the loop on host
+ *                                     arrays below it runs with acn_scene_s_host_cycles_g = 1 and is what the frame is compared with
  *
  * The recovery file `<image>.tmp.lum_image` holds the accumulated luminance image, the gradient cycle to resume
  * at and the position generator's state.  The reference serialises it with beth's binary markup; this driver
@@ -22,6 +24,7 @@
 
 int acn_scene_s_overwrite_output_files_g = 0;
 int acn_scene_s_automatic_recover_g = 0;
+int acn_scene_s_host_cycles_g = 0;
 
 static volatile int signal_received_g = 0;
 static void signal_callback( int sig ) { signal_received_g = sig; }
@@ -54,6 +57,16 @@ int acn_write_pnm( const char* file, const double* rgb, size_t w, size_t h )
     free( row );
     fclose( f );
     return ACN_OK;
+}
+
+int acn_write_pnm8( const char* file, const uint8_t* rgb8, size_t w, size_t h )
+{
+    FILE* f = fopen( file, "wb" );
+    if( !f ) return ACN_ERR_ARG;
+    fprintf( f, "P6\n%zu %zu\n255\n", w, h );
+    int ok = fwrite( rgb8, 3, w * h, f ) == w * h;
+    fclose( f );
+    return ok ? ACN_OK : ACN_ERR_ARG;
 }
 
 static int run_on_handle( acn_scene_handle* h, acn_lum* lum_arr, size_t n, const volatile int* cancel )
@@ -214,6 +227,74 @@ static int handle_for( const acn_scene* o, const acn_flat_scene* flat, acn_scene
     return st;
 }
 
+/* The cycles of acn_scene_s_create_image_file_keep on a device-resident frame of h: the loop below step for step, with the
+ * accumulator, the detector, the jitter, the push and the 8-bit picture on the device (include/actinon_hip.h, acn_frame_*).  The same
+ * text, the same file after every pass, the same recovery file. */
+static int cycles_on_frame( acn_scene* o, acn_scene_handle* h, const char* file, const char* tmp_file )
+{
+    size_t w = o->prm.image_width, hgt = o->prm.image_height;
+    acn_frame* frame = NULL;
+    int st = acn_frame_create( h, w, hgt, &frame );
+    if( st != ACN_OK ) return st;
+    uint8_t* rgb8 = malloc( w * hgt * 3 );
+    uint64_t rval = 21943294;   /* scene.c:799 */
+    uint64_t first_cycle = 0;
+    double sqr_gradient_threshold = o->gradient_threshold * o->gradient_threshold;
+
+    if( file_exists( tmp_file ) )   /* scene.c:1069-1091 */
+    {
+        if( acn_scene_s_automatic_recover_g )
+        {
+            lum_image img = { w, hgt, calloc( w * hgt, sizeof( acn_lum ) ) };
+            if( recovery_load( tmp_file, &img, &first_cycle, &rval ) )
+            {
+                printf( "Recovered from file %s: resuming at gradient cycle %llu\n", tmp_file, ( unsigned long long )first_cycle );
+                st = acn_frame_upload( frame, ( const double* )img.data );
+            }
+            else { first_cycle = 0; rval = 21943294; }
+            free( img.data );
+        }
+        else printf( "Recovery file %s ignored (set acn_scene_s_automatic_recover_g / -r to resume from it).\n", tmp_file );
+    }
+
+    signal_received_g = 0;
+    void ( *old_handler )( int ) = signal( SIGINT, signal_callback );
+    acn_render_opts opts;
+    memset( &opts, 0, sizeof( opts ) );
+    opts.struct_size = ( uint32_t )sizeof( opts );
+    opts.cancel = &signal_received_g;
+
+    printf( "Rendering ...\n" );
+    for( uint64_t cycle = first_cycle; cycle <= o->gradient_cycles && st == ACN_OK; cycle++ )
+    {
+        if( cycle == 0 ) printf( "\n\tmain image: " );
+        else printf( "\n\tgradient pass %3llu: ", ( unsigned long long )cycle );
+        fflush( stdout );
+        /* a pass that is cancelled leaves the accumulator and rval as they were at its start */
+        st = cycle == 0 ? acn_frame_main_pass( frame, &opts ) : acn_frame_pass( frame, sqr_gradient_threshold, o->gradient_samples, &rval, NULL, &opts );
+        if( st == ACN_ERR_CANCELLED )   /* scene.c:1138-1147 */
+        {
+            printf( "\nSIGINT received\n" );
+            if( cycle > 0 )
+            {
+                printf( "Saving result from last gradient cycle to file %s\n", tmp_file );
+                lum_image img = { w, hgt, malloc( w * hgt * sizeof( acn_lum ) ) };
+                if( acn_frame_download( frame, ( double* )img.data ) != ACN_OK || recovery_save( tmp_file, &img, cycle, rval ) != ACN_OK )
+                    fprintf( stderr, "Cannot write %s\n", tmp_file );
+                free( img.data );
+            }
+            break;
+        }
+        if( st != ACN_OK ) break;
+        if( ( st = acn_frame_image( frame, NULL, rgb8 ) ) == ACN_OK ) st = acn_write_pnm8( file, rgb8, w, hgt );
+    }
+    printf( "\n" );
+    signal( SIGINT, old_handler == SIG_ERR ? SIG_DFL : old_handler );
+    free( rgb8 );
+    acn_frame_free( frame );
+    return st;
+}
+
 int acn_scene_s_create_image_file( acn_scene* o, const char* file ) { return acn_scene_s_create_image_file_keep( o, file, NULL ); }
 
 int acn_scene_s_create_image_file_keep( acn_scene* o, const char* file, acn_scene_handle** keep )
@@ -234,6 +315,14 @@ int acn_scene_s_create_image_file_keep( acn_scene* o, const char* file, acn_scen
     acn_scene_handle* h = NULL;
     st = handle_for( o, &flat, keep, &h );
     if( st != ACN_OK ) { acn_flat_scene_free( &flat ); free( tmp_file ); return st; }
+    if( !acn_scene_s_host_cycles_g )
+    {
+        st = cycles_on_frame( o, h, file, tmp_file );
+        free( tmp_file );
+        if( !keep ) acn_scene_free( h );
+        acn_flat_scene_free( &flat );
+        return st;
+    }
 
     size_t w = o->prm.image_width, hgt = o->prm.image_height;
     lum_image img = { w, hgt, calloc( w * hgt, sizeof( acn_lum ) ) };

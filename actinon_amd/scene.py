@@ -205,12 +205,28 @@ class KeptHandle:
         self.close()
 
 
-def run_script(path, on_create_image=None, auto_envelope=0, readonly_fs=False, args=(), overwrite=True):
+def set_host_cycles(on):
+    """The render driver's gradient cycles on host arrays (True) or on a device-resident frame (False): acn_scene_s_host_cycles_g.
+    Returns what it was."""
+    g = C.c_int.in_dll(host, "acn_scene_s_host_cycles_g")
+    was = bool(g.value)
+    g.value = 1 if on else 0
+    return was
+
+
+def run_script(path, on_create_image=None, auto_envelope=0, readonly_fs=False, args=(), overwrite=True, host_cycles=None):
     """Interprets an .acn script (acn_interpret_file).  on_create_image( scene: Scene, file: str ) -> None replaces
     the render driver for `scene.create_image( file )`; None renders on the GPU and writes the PNM like the
-    reference's actinon binary does."""
+    reference's actinon binary does.  host_cycles: None leaves the driver as it is set, True / False selects its loop on host
+    arrays / on a device-resident frame for this script."""
     from ._lib import InterpOpts, CREATE_IMAGE_FN
     C.c_int.in_dll(host, "acn_scene_s_overwrite_output_files_g").value = 1 if overwrite else 0
+    if host_cycles is not None:
+        was = set_host_cycles(host_cycles)
+        try:
+            return run_script(path, on_create_image, auto_envelope, readonly_fs, args, overwrite)
+        finally:
+            set_host_cycles(was)
     raised = []
 
     def hook(ctx, scene_ptr, file):
@@ -910,6 +926,10 @@ class Handle:
         check(hip.acn_reproject_moving_dev(self.h, d_cur_surface_ptr, n, C.byref(prev_params), d_prev_surface_ptr, d_prev_stats_ptr, d_motion_ptr,
                                            n_motion, C.byref(p), d_out_stats_ptr, d_out_motion_ptr, C.byref(o)), "acn_reproject_moving_dev")
 
+    def frame(self, w=None, h=None):
+        """A device-resident frame of this handle (acn_frame_create), zeroed; by default of the raster the handle renders now."""
+        return Frame(self, self.params.image_width if w is None else w, self.params.image_height if h is None else h)
+
     # selecting positions by a key (acn_select_above, acn_key_histogram): the step between a noise map and the next pass
     @staticmethod
     def select_params(threshold, capacity=0, raster_width=0, raster_first=0):
@@ -1201,6 +1221,86 @@ class LensStats:
         if self.handle is None:
             raise AcnError(abi.ACN_ERR_ARG, "LensStats.noise is resolved on the device: construct it with a Handle")
         return self.handle.lens_stats_resolve(self.raw, linear=True)[1]
+
+
+class Frame:
+    """A device-resident frame of a handle (acn_frame_*): the accumulator of the gradient cycles in the layout of acn_lum.  Made by
+    Handle.frame(); the handle must outlive it (closing the handle releases its frames)."""
+
+    def __init__(self, handle, width, height):
+        self.handle, self.width, self.height = handle, int(width), int(height)
+        self.f = C.c_void_p()
+        check(hip.acn_frame_create(handle.h, self.width, self.height, C.byref(self.f)), "acn_frame_create")
+
+    def close(self):
+        """Releases the frame (acn_frame_free), unless its handle is closed already and took it along."""
+        if getattr(self, "f", None) and self.f.value:
+            if self.handle.h.value:
+                hip.acn_frame_free(self.f)
+            self.f = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def upload(self, lum):
+        """lum [h*w,6] float64: pos_x pos_y clr[3] weight per pixel, what a recovery file holds; drops a plan"""
+        a = np.ascontiguousarray(lum, dtype=np.float64)
+        if a.size != self.width * self.height * 6:
+            raise ValueError(f"a frame of {self.width} x {self.height} has {self.width * self.height} records of 6, got {a.size} words")
+        check(hip.acn_frame_upload(self.f, a.ctypes.data), "acn_frame_upload")
+
+    def download(self):
+        out = np.empty((self.width * self.height, 6), dtype=np.float64)
+        check(hip.acn_frame_download(self.f, out.ctypes.data), "acn_frame_download")
+        return out
+
+    def main_pass(self):
+        """The pixel centres of every pixel planned, rendered and pushed (cycle 0 of the render driver)."""
+        o = self.handle._opts(False, None)
+        check(hip.acn_frame_main_pass(self.f, C.byref(o)), "acn_frame_main_pass")
+
+    def plan(self, sqr_threshold, samples, rval):
+        """Key, selection and positions of one gradient pass -> ( flagged pixels, rval after the pass's draws )"""
+        flagged, out = C.c_uint64(0), C.c_uint64(0)
+        check(hip.acn_frame_plan(self.f, float(sqr_threshold), int(samples), int(rval), C.byref(flagged), C.byref(out)), "acn_frame_plan")
+        return int(flagged.value), int(out.value)
+
+    def render(self):
+        o = self.handle._opts(False, None)
+        check(hip.acn_frame_render(self.f, C.byref(o)), "acn_frame_render")
+
+    def push(self):
+        check(hip.acn_frame_push(self.f), "acn_frame_push")
+
+    def gradient_pass(self, sqr_threshold, samples, rval):
+        """plan + render + push (acn_frame_pass) -> ( flagged pixels, rval after the pass )"""
+        flagged, rv = C.c_uint64(0), C.c_uint64(int(rval))
+        o = self.handle._opts(False, None)
+        check(hip.acn_frame_pass(self.f, float(sqr_threshold), int(samples), C.byref(rv), C.byref(flagged), C.byref(o)), "acn_frame_pass")
+        return int(flagged.value), int(rv.value)
+
+    def image(self, rgb=True, rgb8=True):
+        """-> ( averages [h*w,3] float64 or None, their 8-bit values [h*w,3] uint8 or None )"""
+        n = self.width * self.height
+        a = np.empty((n, 3), dtype=np.float64) if rgb else None
+        b = np.empty((n, 3), dtype=np.uint8) if rgb8 else None
+        check(hip.acn_frame_image(self.f, a.ctypes.data if rgb else None, b.ctypes.data if rgb8 else None), "acn_frame_image")
+        return a, b
+
+    def view(self):
+        """abi.FrameBuffers: the device pointers of the frame's buffers and the counts of its plan, as they are now"""
+        b = abi.FrameBuffers()
+        b.struct_size = C.sizeof(abi.FrameBuffers)
+        check(hip.acn_frame_view(self.f, C.byref(b)), "acn_frame_view")
+        return b
+
+
+def lcg00_jump(rval, draws):
+    """rval after `draws` steps of the position generator (acn_lcg00_jump).  No GPU."""
+    return int(hip.acn_lcg00_jump(int(rval) & (2 ** 64 - 1), int(draws) & (2 ** 64 - 1)))
 
 
 def main_pass_positions(width, height, first=0, count=None):

@@ -138,6 +138,10 @@ int acn_lum_machine_s_run( const acn_scene* scene, acn_lum* lum_arr, size_t n );
 
 extern int acn_scene_s_overwrite_output_files_g;    /* scene.h:35  (actinon -f) */
 extern int acn_scene_s_automatic_recover_g;         /* scene.h:36  (actinon -r): resume from `<file>.tmp.lum_image` */
+/* 0: the gradient cycles run on a device-resident frame (acn_frame_*, include/actinon_hip.h); 1: on host arrays, the loop the frame
+ * is compared with.  The file, the recovery file and the printed text have the same bytes either way, and either resumes the other's
+ * recovery file */
+extern int acn_scene_s_host_cycles_g;
 /* Render driver: main pass + gradient cycles, writes `file` (PNM P6) after every pass. Returns acn_status.
  * SIGINT during a gradient cycle stops softly: the accumulated image goes to `<file>.tmp.lum_image` and the call
  * returns ACN_ERR_CANCELLED; a later call with acn_scene_s_automatic_recover_g resumes at that cycle. */
@@ -150,6 +154,8 @@ int acn_scene_s_create_image_file( acn_scene* o, const char* file );
 int acn_scene_s_create_image_file_keep( acn_scene* o, const char* file, acn_scene_handle** keep );
 /* image_cps_s_write_pnm on an RGB float image already gamma-saturated (values in [0,1]) */
 int acn_write_pnm( const char* file, const double* rgb, size_t w, size_t h );
+/* the same file from its 8-bit values [ h * w ][ 3 ] (acn_frame_image) */
+int acn_write_pnm8( const char* file, const uint8_t* rgb8, size_t w, size_t h );
 /* cps_from_cl scene.c:76-82 */
 uint32_t acn_cps_from_cl( const double* cl3 );
 

@@ -1229,6 +1229,83 @@ typedef struct acn_stage_walk_args
 int acn_stage_walk_plan( acn_scene_handle* h, const acn_stage_walk_args* args, acn_stage_caps* caps );   /* no GPU work */
 int acn_run_stage_walk( acn_scene_handle* h, const acn_stage_walk_args* args, const acn_stage_out* out );
 
+/* ------------------------------------------------------------------------------------------------------------------ */
+/* The device-resident frame (k_frame.hip): the lum_image_s of scene_s_create_image_file (src/scene.c:744-885, 1103-1159) kept on
+ * the device, so that a gradient cycle moves neither positions nor colours nor the picture through the host.  A frame is an opaque
+ * object owned by its handle (the host library is plain C and has no device allocator): width * height records in the layout of
+ * acn_lum -- pos_x pos_y clr[ 3 ] weight, 48 bytes -- zeroed by acn_frame_create, which is the empty lum_image.  A pass is
+ *     plan    the key of every pixel, the ascending list of the pixels whose key is above the threshold, their jittered positions
+ *     render  the planned positions -> the frame's colour buffer (a position call: acn_render_positions_dev of them)
+ *     push    the colours into the accumulator; the plan is consumed
+ * and acn_frame_pass is the three in that order; acn_frame_main_pass the same with the pixel centres of every pixel as the plan.
+ * actinon_amd/host/acn_driver.c keeps the loop on host arrays as a second implementation; the two give the same bits.
+ * Everything is IEEE binary64 without contraction, a / b is IEEE division, sums are formed in the order written, ( double )u of a
+ * uint64_t rounds to nearest even, ( int32_t )d truncates.  rec = the record of a pixel.
+ *   Key        avg( rec ) = rec.clr * ( rec.weight > 0 ? 1.0 / rec.weight : 1.0 ).  With v = avg of pixel ( x, y ) and g = 0.0, for
+ *              the neighbours ( x + dx, y + dy ) in the order ( -1, -1 ) ( -1, 0 ) ( -1, 1 ) ( 0, -1 ) ( 0, 1 ) ( 1, -1 ) ( 1, 0 ) ( 1, 1 ):
+ *                g1 = 0.0 outside the raster, else with d = v - avg( neighbour ):  ( d.x * d.x ) + ( d.y * d.y ) + ( d.z * d.z )
+ *                g  = g1 > g ? g1 : g
+ *              key[ y * width + x ] = g
+ *   Selection  pixel p is FLAGGED iff key[ p ] > sqr_threshold (acn_select_above_dev's comparison and launches); the index list is
+ *              ascending: raster order, y outer
+ *   Positions  K = samples; entry e = r * K + k belongs to the r-th flagged pixel ( i, j ):
+ *                s  = acn_lcg00_jump( rval, 2 * e ),  s1 = s * ACN_LCG00_A + ACN_LCG00_C,  s2 = s1 * ACN_LCG00_A + ACN_LCG00_C
+ *                pos[ e ] = ( ( double )i + ( double )s1 * 2^-64, ( double )j + ( double )s2 * 2^-64 )
+ *              *out_rval = acn_lcg00_jump( rval, 2 * K * flagged ): the state of a generator that drew them one after the other.
+ *              The main pass plans ( i + 0.5, j + 0.5 ) with K = 1 for every pixel and draws nothing
+ *   Push       lum_image_s_push with weight 1: the target of entry e is x = ( int32_t )pos_x, y = ( int32_t )pos_y; outside the raster the
+ *              entry is dropped whole, inside pos_x, pos_y, clr[ 0 ], clr[ 1 ], clr[ 2 ] and 1.0 are added to the six words of the
+ *              record, each word's sum in the order of the array.  A draw of 2^64 - 1024 or more converts to exactly 1.0, and the
+ *              sum i + d of a d just below 1.0 rounds up to i + 1 as well (in column 1 already for d = 1 - 2^-53, a tie to even), so an
+ *              entry can land in ( i + 1, j ), ( i, j + 1 ) or ( i + 1, j + 1 ): later in the array's order than every entry of its
+ *              own pixel, earlier than every entry of the target's.  Such FOREIGN entries (target != own pixel) are found first and
+ *              added in ascending e by one lane; then one lane per flagged pixel adds its own K entries in order k and writes the
+ *              record once
+ *   Image      out_rgb[ p ] = avg( rec ); out_rgb8[ p ][ c ] = a > 0.0 ? a < 1.0 ? ( uint8_t )( a * 256 ) : 255 : 0 of a = avg( rec )[ c ]:
+ *              acn_cps_from_cl, what acn_write_pnm makes of the averages
+ *   Frame size width * height must be the raster of the resident scene at every render (acn_scene_replace and acn_scene_set_params
+ *              may change it): a mismatch is ACN_ERR_ARG
+ *   Slices     a pass of more than 2^24 positions is jittered, rendered and pushed in slices of whole pixels, in order: the bits of one
+ *   Empty plan nothing flagged: no launch of render or push, *out_rval = rval, ACN_OK with *out_flagged = 0
+ *   Cancel     opts->cancel reaches the render, and acn_frame_pass reads it once more before it pushes: a cancelled or failed pass
+ *              leaves the accumulator as it was, drops its plan and does not write *rval
+ *   Errors     ACN_ERR_ARG, on the host before anything is written, acn_last_error set: a null frame, handle or array; samples == 0 or
+ *              above 65536; a NaN threshold; width * height == 0 or above 2^31, or a side of 2^31; render or push without a plan; a plan
+ *              on top of a plan that no push has consumed (acn_frame_upload drops a plan); shard_world > 1
+ *   Isolation  plan, push, image, upload and download use no work queue and leave acn_last_stage_ms, acn_last_counters and
+ *              acn_last_kernel_ms what they were; render is a position call and reports as one
+ *   Streams    every frame call works on the handle's own stream and waits; opts->stream is not used
+ *   Lifetime   acn_frame_free releases a frame; acn_scene_free releases the frames its handle still has
+ * acn_frame_view gives the device pointers of the frame's buffers as they are now (a plan or a larger pass may move positions and
+ * colours): tests write colours there between plan and push. */
+typedef struct acn_frame acn_frame;
+typedef struct acn_frame_buffers
+{
+    uint32_t struct_size;    /* sizeof as the CALLER was compiled; nothing beyond it is written; < 8 is ACN_ERR_ARG */
+    uint32_t planned;        /* 1: the frame holds a plan that no push has consumed */
+    uint64_t width, height;
+    uint64_t flagged, samples;   /* of that plan: positions and colours hold flagged * samples entries */
+    void*    d_accumulator;  /* [ height * width ][ 6 ] f64 */
+    void*    d_key;          /* [ height * width ] f64, of the last plan */
+    void*    d_index;        /* int64 [ flagged ]; the main pass leaves it unused */
+    void*    d_positions;    /* [ flagged * samples ][ 2 ] f64 */
+    void*    d_colours;      /* [ flagged * samples ][ 3 ] f64 */
+} acn_frame_buffers;
+int  acn_frame_create( acn_scene_handle* h, uint64_t width, uint64_t height, acn_frame** out );
+void acn_frame_free( acn_frame* f );
+int  acn_frame_upload  ( acn_frame* f, const double* lum /* [ height * width ][ 6 ] */ );
+int  acn_frame_download( acn_frame* f, double* lum );
+int  acn_frame_main_pass( acn_frame* f, const acn_render_opts* opts );
+int  acn_frame_plan  ( acn_frame* f, double sqr_threshold, uint64_t samples, uint64_t rval, uint64_t* out_flagged /* nullable */,
+                       uint64_t* out_rval /* nullable */ );
+int  acn_frame_render( acn_frame* f, const acn_render_opts* opts );
+int  acn_frame_push  ( acn_frame* f );
+int  acn_frame_pass  ( acn_frame* f, double sqr_threshold, uint64_t samples, uint64_t* rval /* in and out */, uint64_t* out_flagged /* nullable */,
+                       const acn_render_opts* opts );
+int  acn_frame_image ( acn_frame* f, double* out_rgb /* nullable [ height * width ][ 3 ] */, uint8_t* out_rgb8 /* nullable [ height * width ][ 3 ] */ );
+int  acn_frame_view  ( acn_frame* f, acn_frame_buffers* out );
+uint64_t acn_lcg00_jump( uint64_t rval, uint64_t draws );   /* no GPU: rval after `draws` steps x' = x * ACN_LCG00_A + ACN_LCG00_C */
+
 const char* acn_last_error( void );
 
 #ifdef __cplusplus
