@@ -42,6 +42,7 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_sc
                "acn_lens_layers_merge", "acn_lens_layers_merge_dev", "acn_lens_layers_resolve_dev",
                "acn_project_points", "acn_project_points_dev", "acn_reproject", "acn_reproject_dev",
                "acn_reproject_moving", "acn_reproject_moving_dev", "acn_motion_from_scenes",
+               "acn_shadow_records", "acn_shadow_records_dev", "acn_shadow_limit_history", "acn_shadow_limit_history_dev",
                "acn_frame_create", "acn_frame_free", "acn_frame_upload", "acn_frame_download", "acn_frame_main_pass", "acn_frame_plan",
                "acn_frame_render", "acn_frame_push", "acn_frame_pass", "acn_frame_image", "acn_frame_view", "acn_lcg00_jump"]
 # symbols declared by include/acn_scene.h
@@ -123,7 +124,11 @@ for _n in ["acn_reproject", "acn_reproject_dev"]:
     getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, P(abi.Params), vp, vp, P(abi.ReprojectParams), vp, vp, P(abi.RenderOpts)]
 for _n in ["acn_reproject_moving", "acn_reproject_moving_dev"]:
     getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, P(abi.Params), vp, vp, vp, C.c_size_t, P(abi.ReprojectParams), vp, vp, P(abi.RenderOpts)]
-hip.acn_motion_from_scenes.argtypes = [P(abi.FlatScene), P(abi.FlatScene), C.c_double, vp, P(abi.MotionReport)]
+for _n in ["acn_shadow_records", "acn_shadow_records_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, P(abi.ShadowParams), vp, P(abi.RenderOpts)]
+for _n in ["acn_shadow_limit_history", "acn_shadow_limit_history_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, vp, vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, P(abi.ShadowHistoryParams), vp, P(abi.RenderOpts)]
+hip.acn_motion_from_scenes.argtypes =[P(abi.FlatScene), P(abi.FlatScene), C.c_double, vp, P(abi.MotionReport)]
 hip.acn_select_above_dev.argtypes =[vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, vp, P(C.c_uint64), P(abi.RenderOpts)]
 hip.acn_select_above.argtypes = [vp, vp, C.c_size_t, P(abi.SelectParams), vp, vp, vp, P(C.c_uint64)]
 hip.acn_key_histogram_dev.argtypes = [vp, vp, C.c_size_t, vp, P(abi.RenderOpts)]

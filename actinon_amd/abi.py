@@ -125,6 +125,22 @@ class MotionReport(C.Structure):
     _fields_ = [("n_rest", C.c_uint32), ("n_moved", C.c_uint32), ("n_none", C.c_uint32), ("same_shape", C.c_uint32)]
 
 
+# shadow records and the history guard (acn_shadow_records, acn_shadow_limit_history): doubles per record, states, defaults, the flag
+ACN_SHADOW_STRIDE = 16
+ACN_SHADOW_NONE, ACN_SHADOW_SAMPLED = 0.0, 1.0
+ACN_SHADOW_DEFAULT_SAMPLES, ACN_SHADOW_MAX_SAMPLES = 16, 64
+ACN_SHADOW_HISTORY_DROP = 1
+ACN_SHADOW_HISTORY_DEFAULT_TOLERANCE, ACN_SHADOW_HISTORY_DEFAULT_MAX_HISTORY = 0.25, 1.0
+
+
+class ShadowParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("samples", C.c_uint32)]
+
+
+class ShadowHistoryParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flags", C.c_uint32), ("tolerance", C.c_double), ("changed_max_history", C.c_double)]
+
+
 # the stage-runner test seam (acn_run_stage): stages, option bits, limits
 ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE, ACN_STAGE_HARD_SHADOW, ACN_STAGE_HARD_PATH = 0, 1, 2, 3
 ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_LEAF_LIGHTS, ACN_STAGE_NO_EMIT_TERMS = 1, 2, 4
@@ -176,5 +192,7 @@ assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
 assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)
 assert C.sizeof(SelectParams) == 40, C.sizeof(SelectParams)
 assert C.sizeof(ReprojectParams) == 40, C.sizeof(ReprojectParams)
+assert C.sizeof(ShadowParams) == 12, C.sizeof(ShadowParams)
+assert C.sizeof(ShadowHistoryParams) == 24, C.sizeof(ShadowHistoryParams)
 assert C.sizeof(FrameBuffers) == 80, C.sizeof(FrameBuffers)
 assert C.sizeof(StageWalkArgs) == 72, C.sizeof(StageWalkArgs)

@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), the device-resident frame, and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), shadow records and the history guard, the device-resident frame, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points.
  * The lens calls that cut their positions into slices share one loop, lens_slices; a host-buffer form is a HostCall (acn_handle.h). */
@@ -14,6 +14,7 @@
 #include "acn_layers_host.h"
 #include "acn_reproject_host.h"
 #include "acn_motion_host.h"
+#include "acn_shadow_host.h"
 
 /* ------------------------------------------------------------------------------------------------------------------ */
 /* kernels */
@@ -970,6 +971,78 @@ extern "C" int acn_reproject_moving( acn_scene_handle* h, const double* cur_surf
     void* d_motion = hc.out( out_motion, sizeof( double ) * 2 * n );
     c.opts.stream = nullptr;
     return hc.run( [ & ] { return acn_reproject_moving_dev( h, d_cur, n, prev_params, d_ps, d_pt, d_table, n_motion, prm, d_out, d_motion, &c.opts ); } );
+}
+
+/* ---- shadow records and the history guard (k_shadow.hip; the checks that need no handle: acn_shadow_host.h) ---- */
+extern "C" int acn_shadow_records_dev( acn_scene_handle* h, const void* d_surface, size_t n, const acn_shadow_params* prm, void* d_out,
+                                       const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    uint32_t log2_samples = 0;
+    if( acn_shadow_records_check( h != nullptr, d_surface, n, prm, d_out, c.opts.shard_world, &log2_samples, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    SceneArgs s;
+    if( ( st = surface_flags_begin( h, &s ) ) != ACN_OK ) return st;
+    acn_launch_shadow( h->scene.lds_bytes != 0, h->scene.leaf_lights, machine_lds_bytes( h->scene ), c.stream, s, ( const double* )d_surface, n,
+                       log2_samples, ( double* )d_out );
+    HIP_TRY( hipGetLastError() );
+    return surface_flags_end( h, c );
+}
+
+extern "C" int acn_shadow_records( acn_scene_handle* h, const double* surface, size_t n, const acn_shadow_params* prm, double* out,
+                                   const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    uint32_t log2_samples = 0;
+    if( acn_shadow_records_check( h != nullptr, surface, n, prm, out, c.opts.shard_world, &log2_samples, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    c.opts.stream = nullptr;
+    return host_in_out( h, surface, sizeof( double ) * ACN_SURF_STRIDE * n, out, sizeof( double ) * ACN_SHADOW_STRIDE * n,
+                        [ & ]( void* d_in, void* d_out ) { return acn_shadow_records_dev( h, d_in, n, prm, d_out, &c.opts ); } );
+}
+
+extern "C" int acn_shadow_limit_history_dev( acn_scene_handle* h, void* d_stats, const void* d_motion, const void* d_cur_shadow, const void* d_prev_shadow,
+                                             size_t n, size_t prev_width, size_t prev_height, const acn_shadow_history_params* prm, void* d_out_change,
+                                             const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_shadow_history_params p;
+    if( acn_shadow_limit_history_check( h != nullptr, d_stats, d_motion, d_cur_shadow, d_prev_shadow, n, prev_width, prev_height, prm, d_out_change,
+                                        c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    int st = call_begin( h, &c );
+    if( st != ACN_OK ) return st;
+    ShadowHistorySetup su;
+    su.drop = ( p.flags & ACN_SHADOW_HISTORY_DROP ) ? 1u : 0u; su.tolerance = p.tolerance; su.cap = p.changed_max_history;
+    acn_launch_shadow_limit_history( ( double* )d_stats, ( const double* )d_motion, ( const double* )d_cur_shadow, ( const double* )d_prev_shadow, n,
+                                     prev_width, prev_height, su, ( double* )d_out_change, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_shadow_limit_history( acn_scene_handle* h, double* stats, const double* motion, const double* cur_shadow, const double* prev_shadow,
+                                         size_t n, size_t prev_width, size_t prev_height, const acn_shadow_history_params* prm, double* out_change,
+                                         const acn_render_opts* opts )
+{
+    Call c( opts );
+    std::string msg;
+    acn_shadow_history_params p;
+    if( acn_shadow_limit_history_check( h != nullptr, stats, motion, cur_shadow, prev_shadow, n, prev_width, prev_height, prm, out_change,
+                                        c.opts.shard_world, &p, &msg ) != ACN_OK ) return fail( ACN_ERR_ARG, msg );
+    if( n == 0 ) return ACN_OK;
+    HostCall hc( h );
+    void* d_stats = hc.inout( stats, stats, sizeof( double ) * ACN_STATS_STRIDE * n );
+    void* d_motion = hc.in( motion, sizeof( double ) * 2 * n );
+    void* d_cur = hc.in( cur_shadow, sizeof( double ) * ACN_SHADOW_STRIDE * n );
+    void* d_prev = hc.in( prev_shadow, sizeof( double ) * ACN_SHADOW_STRIDE * prev_width * prev_height );
+    void* d_change = hc.out( out_change, sizeof( double ) * n );
+    c.opts.stream = nullptr;
+    return hc.run( [ & ] { return acn_shadow_limit_history_dev( h, d_stats, d_motion, d_cur, d_prev, n, prev_width, prev_height, prm, d_change, &c.opts ); } );
 }
 
 extern "C" int acn_motion_from_scenes( const acn_flat_scene* prev, const acn_flat_scene* cur, double moved_max_history, double* out_table,

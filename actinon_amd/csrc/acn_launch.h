@@ -87,6 +87,17 @@ void acn_launch_camera_rays( const DevScene& sc, const double* pos_xy, size_t n,
 void acn_launch_surface( uint32_t mode, bool lds_nodes, size_t lds_bytes, hipStream_t stream, const SceneArgs& s,
                          const double* rays, const double* pos_xy, size_t n, double* out );
 
+/* shadow records and the history guard (k_shadow.hip; include/actinon_hip.h states both).  shadow: surface [ n ][ ACN_SURF_STRIDE ] -> out
+ * [ n ][ ACN_SHADOW_STRIDE ], both 16-byte aligned, 1 << log2_samples <= 64 lanes per position; lds_bytes and s.dev.flags as for
+ * acn_launch_surface; leaf_lights: KernelFlags.leaf_lights of the handle's scene.  limit_history: stats [ n ][ ACN_STATS_STRIDE ] in place,
+ * motion [ n ][ 2 ], cur_shadow [ n ][ . ], prev_shadow [ height * width ][ . ], out_change (nullable) [ n ]; n >= 1.  ShadowHistorySetup:
+ * acn_shadow_history_params after the host's checks, final values, no defaults. */
+struct ShadowHistorySetup { uint32_t drop; double tolerance, cap; };
+void acn_launch_shadow( bool lds_nodes, bool leaf_lights, size_t lds_bytes, hipStream_t stream, const SceneArgs& s, const double* surface,
+                        size_t n, uint32_t log2_samples, double* out );
+void acn_launch_shadow_limit_history( double* stats, const double* motion, const double* cur_shadow, const double* prev_shadow, size_t n,
+                                      uint64_t width, uint64_t height, const ShadowHistorySetup& su, double* out_change, hipStream_t stream );
+
 /* the filter of acn_denoise (k_denoise.hip): prepare, variance and one launch per level, the last of which writes out_rgb (which may
  * be lin).  scratch: ACN_DENOISE_SCRATCH_PER_PIXEL bytes per pixel, 128-byte aligned.  The parameters are final values, no defaults. */
 #define ACN_DENOISE_SCRATCH_PER_PIXEL 128

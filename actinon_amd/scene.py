@@ -926,6 +926,70 @@ class Handle:
         check(hip.acn_reproject_moving_dev(self.h, d_cur_surface_ptr, n, C.byref(prev_params), d_prev_surface_ptr, d_prev_stats_ptr, d_motion_ptr,
                                            n_motion, C.byref(p), d_out_stats_ptr, d_out_motion_ptr, C.byref(o)), "acn_reproject_moving_dev")
 
+    # shadow records and the history guard (acn_shadow_records, acn_shadow_limit_history)
+    @staticmethod
+    def shadow_params(samples=None):
+        """acn_shadow_params of keyword arguments; None is the library's default"""
+        p = abi.ShadowParams()
+        p.struct_size = C.sizeof(abi.ShadowParams)
+        p.samples = 0 if samples is None else int(samples)
+        return p
+
+    @staticmethod
+    def shadow_history_params(tolerance=None, changed_max_history=None, drop=False):
+        """acn_shadow_history_params of keyword arguments; None is the library's default"""
+        p = abi.ShadowHistoryParams()
+        p.struct_size = C.sizeof(abi.ShadowHistoryParams)
+        p.flags = abi.ACN_SHADOW_HISTORY_DROP if drop else 0
+        p.tolerance = 0.0 if tolerance is None else float(tolerance)
+        p.changed_max_history = 0.0 if changed_max_history is None else float(changed_max_history)
+        return p
+
+    def shadow_records(self, surface, samples=16):
+        """How much of each light the surface points see (acn_shadow_records): surface a Surface or [n,16] records, samples one of
+        1, 2, 4, 8, 16, 32, 64 -> [n,16] float64: state, S, L, asked, clear, clear / asked, clear of lights 0..4, asked of lights 0..4."""
+        s = np.ascontiguousarray(surface.raw if isinstance(surface, Surface) else surface, dtype=np.float64).reshape(-1, abi.ACN_SURF_STRIDE)
+        out = np.empty((s.shape[0], abi.ACN_SHADOW_STRIDE), dtype=np.float64)
+        p = self.shadow_params(samples)
+        o = self._plain_opts(False, None)
+        check(hip.acn_shadow_records(self.h, s.ctypes.data, s.shape[0], C.byref(p), out.ctypes.data, C.byref(o)), "acn_shadow_records")
+        return out
+
+    def shadow_records_dev(self, d_surface_ptr, n, d_out_ptr, samples=16, stream=None):
+        """Device buffers, both 16-byte aligned: d_out [n,16] float64; enqueued on `stream` (None: the handle's stream, synchronous)."""
+        p = self.shadow_params(samples)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_shadow_records_dev(self.h, d_surface_ptr, n, C.byref(p), d_out_ptr, C.byref(o)), "acn_shadow_records_dev")
+
+    def shadow_limit_history(self, stats, motion, cur_shadow, prev_shadow, prev_w, prev_h, tolerance=None, changed_max_history=None, drop=False):
+        """Limits a reprojected history where the light a point sees has changed (acn_shadow_limit_history): stats the LensStats (or
+        [n,8] records) and motion [n,2] that reproject / reproject_moving returned, cur_shadow [n,16] the shadow records of the same
+        positions, prev_shadow those of the whole previous raster prev_w x prev_h -> ( LensStats over a limited COPY, change [n]: NaN
+        where nothing was compared )."""
+        t = np.array(stats.raw if isinstance(stats, LensStats) else stats, dtype=np.float64).reshape(-1, abi.ACN_STATS_STRIDE)
+        m = np.ascontiguousarray(motion, dtype=np.float64).reshape(-1, 2)
+        c = np.ascontiguousarray(cur_shadow, dtype=np.float64).reshape(-1, abi.ACN_SHADOW_STRIDE)
+        q = np.ascontiguousarray(prev_shadow, dtype=np.float64).reshape(-1, abi.ACN_SHADOW_STRIDE)
+        if len(m) != len(t) or len(c) != len(t):
+            raise ValueError(f"{len(t)} statistics records: got {len(m)} motion rows and {len(c)} shadow records")
+        if len(q) != int(prev_w) * int(prev_h):
+            raise ValueError(f"the previous raster has {int(prev_w) * int(prev_h)} pixels: got {len(q)} shadow records")
+        change = np.empty((t.shape[0],), dtype=np.float64)
+        p = self.shadow_history_params(tolerance, changed_max_history, drop)
+        o = self._plain_opts(False, None)
+        check(hip.acn_shadow_limit_history(self.h, t.ctypes.data, m.ctypes.data, c.ctypes.data, q.ctypes.data, t.shape[0], int(prev_w), int(prev_h),
+                                           C.byref(p), change.ctypes.data, C.byref(o)), "acn_shadow_limit_history")
+        return LensStats(t, self), change
+
+    def shadow_limit_history_dev(self, d_stats_ptr, d_motion_ptr, d_cur_shadow_ptr, d_prev_shadow_ptr, n, prev_w, prev_h, d_out_change_ptr=None,
+                                 tolerance=None, changed_max_history=None, drop=False, stream=None):
+        """Device buffers, the records 16-byte aligned; d_stats [n,8] is limited IN PLACE, d_out_change [n] float64 or None; enqueued on
+        `stream` without a synchronisation (None: the handle's stream, synchronous)."""
+        p = self.shadow_history_params(tolerance, changed_max_history, drop)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_shadow_limit_history_dev(self.h, d_stats_ptr, d_motion_ptr, d_cur_shadow_ptr, d_prev_shadow_ptr, n, int(prev_w), int(prev_h),
+                                               C.byref(p), d_out_change_ptr, C.byref(o)), "acn_shadow_limit_history_dev")
+
     def frame(self, w=None, h=None):
         """A device-resident frame of this handle (acn_frame_create), zeroed; by default of the raster the handle renders now."""
         return Frame(self, self.params.image_width if w is None else w, self.params.image_height if h is None else h)

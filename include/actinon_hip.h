@@ -920,7 +920,7 @@ double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget );   /* no 
  * Limitation, stated: the WORLD IS TAKEN TO BE AT REST between the two frames -- only the camera moves.  A surface that moved off
  * its tangent plane fails the plane test and starts without history; one that moved within it, or whose light changed, keeps a
  * history that is no longer its own.  Objects that move between the frames are what acn_reproject_moving* below is for; a change
- * of the light is detected by neither call.  With the default reject_kinds history is taken only where the radiance does not depend on the view direction (no
+ * of the light is detected by acn_shadow_limit_history* where the caller runs it (reflections stay undetected).  With the default reject_kinds history is taken only where the radiance does not depend on the view direction (no
  * mirror, no glass, no Fresnel term); max_hops > 0 accepts records of ACN_SURF_FOLLOW behind glass or in mirrors, whose parallax
  * is not that of the surface point: the caller's risk.  Layered records (acn_lens_layers_*) are not reprojected.
  * The caller then runs acn_lens_stats_merge_dev( history, n, current statistics, n ); the library adds no fused call.
@@ -992,7 +992,8 @@ int acn_reproject    ( acn_scene_handle* h, const double* cur_surface, size_t n,
  * A table whose rows are all REST with m[ 13 ] = 0 gives the bits of acn_reproject* on every input.  The lane reads m[ 12 .. 13 ] of its
  * row first and the other 96 bytes only if the row is MOVED.
  * Limitations, stated: a moved object's own shading changes as it turns to the light, and a static surface's shading changes where a
- * mover's shadow or reflection falls.  Neither is detected: the history of such a point is no longer its own.  That is what the
+ * mover's shadow or reflection falls.  The shadow is detected by acn_shadow_limit_history* where the caller runs it; the turning and the
+ * reflection are not: the history of such a point is no longer its own.  That is what the
  * per-object cap m[ 13 ] and max_history are for: they bound how long old samples outweigh new ones.  Clipping the history to the
  * new samples' spread is a separate feature and not part of this call.  What acn_reproject* says of reject_kinds and max_hops holds.
  * ACN_ERR_ARG, on the host before any launch, acn_last_error set, nothing written: what acn_reproject* refuses, and (n > 0) a null
@@ -1041,6 +1042,101 @@ int acn_reproject_moving_dev( acn_scene_handle* h, const void* d_cur_surface, si
 int acn_reproject_moving    ( acn_scene_handle* h, const double* cur_surface, size_t n, const acn_params* prev_params, const double* prev_surface,
                               const double* prev_stats, const double* motion, size_t n_motion, const acn_reproject_params* prm,
                               double* out_stats, double* out_motion /* nullable */, const acn_render_opts* opts );
+
+/* Shadow records: how much of each light a surface point sees, and the guard of a reprojected history built on them (k_shadow.hip;
+ * the checks that need no handle: csrc/acn_shadow_host.h).  The quantity is the direct-light loop of scene_s_lum (src/scene.c:542-581)
+ * with everything but the occlusion answer left out: the shadow guide of temporal filters, and an output pass of its own
+ * (tools/render_aovs.py --shadow).  tools/render_turntable.py --temporal --shadow-guard is a caller of both calls.
+ *
+ * acn_shadow_records*: surface [ n ][ ACN_SURF_STRIDE ] are surface records as acn_surface_rays* / acn_surface_positions* write them, first
+ * hit, ACN_SURF_FOLLOW or aggregate: a record is taken as it stands, and of it only [ 0 ], [ 1 .. 3 ], [ 4 .. 6 ] and [ 12 ] are read.
+ * out [ n ][ ACN_SHADOW_STRIDE ], all f64, integers stored as doubles; both buffers 16-byte aligned; each record is written whole by one
+ * lane as eight 16-byte stores.  S = acn_shadow_params.samples (0: ACN_SHADOW_DEFAULT_SAMPLES), one of 1, 2, 4, 8, 16, 32, 64:
+ *   [ 0 ]         state: 0 = ACN_SHADOW_NONE, 1 = ACN_SHADOW_SAMPLED
+ *   [ 1 ]         S
+ *   [ 2 ]         L, the number of elements of the light root
+ *   [ 3 ]         asked: the samples, over all lights, that face the surface and hit their light -- the shadow rays scene_s_lum casts
+ *   [ 4 ]         clear: those of asked that are not occluded
+ *   [ 5 ]         asked > 0 ? clear / asked : 0.0  (IEEE division of the two doubles)
+ *   [ 6 .. 10 ]   clear of lights 0 .. 4
+ *   [ 11 .. 15 ]  asked of lights 0 .. 4        (lights from the sixth on count in [ 3 ] and [ 4 ] only)
+ * A record r is SAMPLED iff r[ 0 ] < inf and ( uint32 )r[ 12 ] & ACN_SURF_EMITTER is 0; otherwise it is NONE: sixteen zeros.
+ * A SAMPLED record, every expression the reference's in its order (src/scene.c:537-569; csrc/acn_k_shade.h is the production form):
+ *   P = r[ 1 .. 3 ];  D = -r[ 4 .. 6 ] (IEEE negation per component);
+ *   rv0 = random_seed( P, 3294479285 ) + random_seed( D, 3247146734 )  mod 2^64
+ *   for light i in the element order of the light root:
+ *     ( axis, cos_rs ) = obj_fov( light_i, P );  src_con = transposed( m_con_z( axis ) );  cyl_hgt = 1 - cos_rs
+ *     for j = 0 .. S - 1:
+ *       rv = acn_lcg00_jump( rv0, 2 * ( i * S + j ) );  cap = v_random_sphere_cap( &rv, cyl_hgt );  out_d = m_mlv( src_con, cap )
+ *       if dot( out_d, D ) <= 0: next sample
+ *       a = obj_ray_hit( light_i, ( P, out_d ) );  if a >= inf: next sample
+ *       asked_i++;  if compound_s_ray_hit( matter_root, ( P, out_d ) ) > a: clear_i++
+ * That is the stream scene_s_lum draws at the point whenever its own ( uint64 )( direct_samples * diffuse_intensity ) is S for every
+ * light; the counts are integers, so they do not depend on the order they are formed in.  A record depends on its own input record
+ * and S alone, never on which records share a wavefront (lanes are samples: S consecutive lanes share a position).
+ * Of opts only `stream` is used, with the rules of acn_surface_positions_dev; the device flag word is that of the surface calls.  The
+ * call touches no work queue, counter, learned rate or acn_last_* value.  ACN_ERR_ARG, on the host before any launch, acn_last_error
+ * set, nothing written: a null handle or (n > 0) a null buffer; n above 2^31; a buffer that is not 16-byte aligned; struct_size < 4; an
+ * unknown flag (there is none yet); an S that is not one of the seven; shard_world > 1.  n == 0 is ACN_OK with no launch.
+ *
+ * acn_shadow_limit_history*: the guard acn_reproject* lacks, a call of its own so that acn_reproject* keeps its bits.  stats [ n ][
+ * ACN_STATS_STRIDE ], IN PLACE, is what acn_reproject[_moving]* wrote; motion [ n ][ 2 ] is that call's out_motion; cur_shadow [ n ][
+ * ACN_SHADOW_STRIDE ] the shadow records of the same positions; prev_shadow [ H' * W' ][ ACN_SHADOW_STRIDE ] those of the WHOLE previous
+ * raster, row-major; out_change (nullable) [ n ].  Arithmetic as in the acn_reproject block (binary64, no contraction, IEEE division,
+ * floor exact).  max( m, t ) below is t if t > m, else m: a NaN term leaves m as it is.  Per position, in this order:
+ *   1 HISTORY    the statistics record is EMPTY, or a motion component ( qx, qy ) is a NaN: the record is untouched, change = NaN.
+ *   2 PLACE      x = floor( qx ), y = floor( qy ); in the image iff x >= 0.0, x < ( double )W', y >= 0.0 and y < ( double )H', compared as
+ *                doubles; only then is it converted to the index y * W' + x, and only then is anything of it read.  Not in the image:
+ *                untouched, change = NaN.
+ *   3 SAMPLED    c = cur_shadow[ i ], p = prev_shadow[ y * W' + x ]; c[ 0 ] == 1.0 and p[ 0 ] == 1.0, else: untouched, change = NaN.
+ *   4 CHANGE     m = 0.0;  for l = 0 .. 4 with ( double )l < c[ 2 ]:  m = max( m, | c[ 6 + l ] / c[ 1 ] - p[ 6 + l ] / p[ 1 ] | );
+ *                m = max( m, | c[ 4 ] / ( c[ 1 ] * c[ 2 ] ) - p[ 4 ] / ( p[ 1 ] * p[ 2 ] ) | );  change = m.
+ *   5 LIMIT      if change > tolerance:  with ACN_SHADOW_HISTORY_DROP the record becomes eight zeros;  otherwise, if n > cap:
+ *                m2.c = m2.c * ( cap / n ), then n = cap (the expressions of acn_reproject step 6; mean and [ 7 ] stay).
+ *   6            in every other case the record is untouched.  A lane writes nothing of a record it leaves untouched.
+ * What follows: with a resting camera and a resting world the positions, and therefore the seeds, are the previous frame's bit for bit;
+ * change is then exactly 0 everywhere and nothing is limited.  With a moving camera the sampling noise of a penumbra can exceed the
+ * tolerance; the cost is a shorter history there, never a wrong one.  A change that reaches a point only through a mirror or through
+ * glass (reflections, caustics) is not seen by a shadow record and stays undetected.
+ * Stream rules and what the call leaves alone: as acn_reproject*.  ACN_ERR_ARG, on the host before any launch, acn_last_error set,
+ * nothing written: a null handle or (n > 0) a null stats, motion, cur_shadow or prev_shadow; n or W' * H' above 2^31, W' < 1 or H' < 1;
+ * a record buffer that is not 16-byte aligned, a motion or out_change that is not 8-byte aligned; struct_size < 4; unknown flags; a
+ * tolerance that is negative or not finite; a changed_max_history that is not 0 and not a finite number >= 1; shard_world > 1.
+ * n == 0 is ACN_OK with no launch. */
+#define ACN_SHADOW_STRIDE 16            /* doubles per record: 128 bytes */
+#define ACN_SHADOW_NONE    0.0
+#define ACN_SHADOW_SAMPLED 1.0
+#define ACN_SHADOW_DEFAULT_SAMPLES 16
+#define ACN_SHADOW_MAX_SAMPLES     64
+typedef struct acn_shadow_params
+{
+    uint32_t struct_size;      /* sizeof as the CALLER was compiled; < 4 is ACN_ERR_ARG (the convention of acn_reproject_params) */
+    uint32_t flags;            /* none defined: any bit is ACN_ERR_ARG */
+    uint32_t samples;          /* S: 1, 2, 4, 8, 16, 32 or 64; 0 = default 16 */
+} acn_shadow_params;
+#define ACN_SHADOW_PARAMS_INIT { ( uint32_t )sizeof( acn_shadow_params ), 0u, 0u }
+#define ACN_SHADOW_HISTORY_DROP 1u      /* a changed position loses its history instead of having it capped */
+#define ACN_SHADOW_HISTORY_DEFAULT_TOLERANCE   0.25
+#define ACN_SHADOW_HISTORY_DEFAULT_MAX_HISTORY 1.0
+typedef struct acn_shadow_history_params
+{
+    uint32_t struct_size;          /* as above */
+    uint32_t flags;                /* ACN_SHADOW_HISTORY_*; unknown bits are ACN_ERR_ARG */
+    double   tolerance;            /* a position is limited iff change > this; finite, >= 0; 0 = default 0.25 */
+    double   changed_max_history;  /* cap: the n a limited record carries at most; finite, >= 1; 0 = default 1 */
+} acn_shadow_history_params;
+#define ACN_SHADOW_HISTORY_PARAMS_INIT { ( uint32_t )sizeof( acn_shadow_history_params ), 0u, 0.0, 0.0 }
+int acn_shadow_records_dev( acn_scene_handle* h, const void* d_surface /* [ n ][ 16 ] */, size_t n, const acn_shadow_params* prm /* nullable: defaults */,
+                            void* d_out /* [ n ][ ACN_SHADOW_STRIDE ] */, const acn_render_opts* opts );
+int acn_shadow_records    ( acn_scene_handle* h, const double* surface, size_t n, const acn_shadow_params* prm, double* out,
+                            const acn_render_opts* opts );
+int acn_shadow_limit_history_dev( acn_scene_handle* h, void* d_stats /* [ n ][ 8 ], in place */, const void* d_motion /* [ n ][ 2 ] */,
+                                  const void* d_cur_shadow /* [ n ][ 16 ] */, const void* d_prev_shadow /* [ prev_height * prev_width ][ 16 ] */,
+                                  size_t n, size_t prev_width, size_t prev_height, const acn_shadow_history_params* prm /* nullable: defaults */,
+                                  void* d_out_change /* nullable [ n ] */, const acn_render_opts* opts );
+int acn_shadow_limit_history    ( acn_scene_handle* h, double* stats, const double* motion, const double* cur_shadow, const double* prev_shadow,
+                                  size_t n, size_t prev_width, size_t prev_height, const acn_shadow_history_params* prm,
+                                  double* out_change /* nullable */, const acn_render_opts* opts );
 
 /* Timing of the kernels of the last render call on this handle (HIP events on the launch stream), ms. */
 int acn_last_kernel_ms( acn_scene_handle* h, double* trace_ms );

@@ -2,7 +2,7 @@
 """Depth, normal, albedo and object-id images of an Actinon scene: one surface call (acn_surface_positions) over the
 main-pass positions.
 
-    python tools/render_aovs.py SCENE OUTDIR [--follow] [--width W --height H]
+    python tools/render_aovs.py SCENE OUTDIR [--follow] [--shadow S] [--width W --height H]
 
 SCENE is an .acn script (the scene of its first create_image) or a flattened scene .npz, as for tools/render_panorama.py.
 OUTDIR receives
@@ -11,7 +11,10 @@ OUTDIR receives
     albedo.pnm      the surface colour, 8 bit, the reference's quantisation (cps_from_cl)
     object_id.pgm   16 bit, big endian: 1 + the enter object if there is one, else 1 + the exit object; misses 0
     surface.npy     the raw records [ H * W, 16 ] float64 (include/actinon_hip.h)
---follow looks through glass and mirrors: the dominant specular branch to the first diffuse or emitting surface."""
+--follow looks through glass and mirrors: the dominant specular branch to the first diffuse or emitting surface.
+--shadow S adds shadow.pfm, the share of the lights each surface point sees (acn_shadow_records with S samples per light: clear /
+asked, one channel of float32; misses, emitters and points no sample could ask a light from are 0) and shadow.npy, the raw shadow
+records [ H * W, 16 ]."""
 import argparse
 import os
 import sys
@@ -113,14 +116,28 @@ def write_aovs(outdir, surface, width, height):
     np.save(os.path.join(outdir, "surface.npy"), surface.raw)
 
 
+def shadow_image(records, width, height):
+    """the share plane [ 5 ] of shadow records over H * W positions -> [H,W] float32"""
+    return np.asarray(records, dtype=np.float64).reshape(height * width, 16)[:, 5].astype(np.float32).reshape(height, width)
+
+
+def write_shadow(outdir, records, width, height):
+    os.makedirs(outdir, exist_ok=True)
+    write_pfm(os.path.join(outdir, "shadow.pfm"), shadow_image(records, width, height))
+    np.save(os.path.join(outdir, "shadow.npy"), np.asarray(records))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Depth, normal, albedo and object-id images of an Actinon scene (acn_surface_positions)")
     ap.add_argument("scene", help=".acn script or flattened scene .npz")
     ap.add_argument("outdir", help="directory for depth.pfm, normal.pnm, albedo.pnm, object_id.pgm, surface.npy")
     ap.add_argument("--follow", action="store_true", help="follow the dominant specular branch to the first diffuse / emitting surface")
+    ap.add_argument("--shadow", type=int, default=None, metavar="S", help="also write shadow.pfm: the share of the lights each point sees, S samples per light (1, 2, 4, ... 64)")
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     args = ap.parse_args(argv)
+    if args.shadow is not None and args.shadow not in (1, 2, 4, 8, 16, 32, 64):
+        ap.error("--shadow S: S is 1, 2, 4, 8, 16, 32 or 64")
     import actinon_amd as A
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from render_panorama import load_scene
@@ -135,8 +152,11 @@ def main(argv=None):
         ap.error("the image needs a width of at least 1 and a height of at least 2")
     h = A.Handle(flat)
     surface = h.surface_positions(A.main_pass_positions(w, hh), follow=args.follow)
+    shadow = h.shadow_records(surface, args.shadow) if args.shadow is not None else None
     h.close()
     write_aovs(args.outdir, surface, w, hh)
+    if shadow is not None:
+        write_shadow(args.outdir, shadow, w, hh)
 
 
 if __name__ == "__main__":

@@ -26,8 +26,15 @@ turns an object instead of the camera: the camera stays, and root element NODE o
 0,0,1) through its own position, --orbit-deg degrees in all.  Every frame is a copy of the scene with that object turned
 (actinon_amd.motion.rigid_copy) made resident by acn_scene_replace.  With --temporal the history comes from acn_reproject_moving_dev
 with the motion table of the previous and the current scene (acn_motion_from_scenes): a point of the turned object takes the samples
-of where it was one frame ago.  Its shading changes as it turns to the light, and so does that of surfaces its shadow crosses; neither
-is detected, so --moved-max-history (a cap for the object that moved) and --max-history bound how long old samples weigh."""
+of where it was one frame ago.  Its shading changes as it turns to the light, and so does that of surfaces its shadow crosses; the
+first is not detected, so --moved-max-history (a cap for the object that moved) and --max-history bound how long old samples weigh.
+
+    ... --temporal --shadow-guard [--shadow-samples S] [--shadow-tolerance T] [--shadow-drop]
+
+detects the second: every frame computes shadow records (acn_shadow_records_dev: how much of each light a pixel's surface point sees,
+S samples per light, default 16), keeps the previous frame's, and between reproject and merge acn_shadow_limit_history_dev caps the
+history at one sample -- or with --shadow-drop takes it away -- wherever that share changed by more than T (default 0.25).  A change
+that arrives through a mirror or through glass stays undetected."""
 import argparse
 import os
 import sys
@@ -72,10 +79,12 @@ def render(flat, frames, orbit_deg, write, target_distance=None, spin=None):
 
 
 def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=None, denoise=False, max_history=None, allow_fresnel=False,
-                    spin=None, moved_max_history=None):
+                    spin=None, moved_max_history=None, shadow_guard=None):
     """The same frames with the history of the frames before them; write( frame, rgb8 ) -> ( Handle.info, per frame the share of pixels
-    that took a history and their mean n after the merge ).  spin: None, or ( node index, axis ): that object turns, the camera stays,
-    and the history goes through the motion table of the two scenes"""
+    that took a history and their mean n after the merge, and with shadow_guard the share of the history-carrying pixels it limited ).
+    spin: None, or ( node index, axis ): that object turns, the camera stays, and the history goes through the motion table of the two
+    scenes.  shadow_guard: None, or dict( samples, tolerance, drop ): shadow records of every frame (acn_shadow_records_dev), the previous
+    frame's kept, and acn_shadow_limit_history_dev between reproject and merge"""
     import ctypes as C
     import torch
     import actinon_amd as A
@@ -97,6 +106,8 @@ def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=Non
         d_cur, d_acc, d_prev = new(n, abi.ACN_STATS_STRIDE), new(n, abi.ACN_STATS_STRIDE), new(n, abi.ACN_STATS_STRIDE)
         d_lin = new(n, 3)
         d_rgb8 = torch.empty((n, 3), dtype=torch.uint8, device=dev)
+        if shadow_guard:
+            d_shadow, d_prev_shadow, d_motion, d_change = new(n, abi.ACN_SHADOW_STRIDE), new(n, abi.ACN_SHADOW_STRIDE), new(n, 2), new(n)
         torch.cuda.synchronize(dev)
         prev_params, prev_flat, report = None, flat, []
         for f in range(frames):
@@ -107,22 +118,32 @@ def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=Non
                 h.set_params(**orbit_camera(flat.params, orbit_deg * f / frames, target_distance))
             h.surface_positions_dev(d_pos.data_ptr(), n, d_surf.data_ptr())
             h.render_lens_stats_main_pass_dev(0, n, None, d_cur.data_ptr(), linear=True, samples=samples, jitter=True, seed=f)
+            if shadow_guard:
+                h.shadow_records_dev(d_surf.data_ptr(), n, d_shadow.data_ptr(), samples=shadow_guard["samples"])
+            d_out_motion = d_motion.data_ptr() if shadow_guard else None
             if f and spin:
                 table, _ = A.motion_from_scenes(prev_flat, cur_flat, moved_max_history)
                 d_table = torch.from_numpy(table).to(dev)
                 h.reproject_moving_dev(d_surf.data_ptr(), n, prev_params, d_prev_surf.data_ptr(), d_prev.data_ptr(), d_table.data_ptr(), len(table),
-                                       d_acc.data_ptr(), **params)
+                                       d_acc.data_ptr(), d_out_motion, **params)
                 prev_flat = cur_flat
             elif f:
-                h.reproject_dev(d_surf.data_ptr(), n, prev_params, d_prev_surf.data_ptr(), d_prev.data_ptr(), d_acc.data_ptr(), **params)
+                h.reproject_dev(d_surf.data_ptr(), n, prev_params, d_prev_surf.data_ptr(), d_prev.data_ptr(), d_acc.data_ptr(), d_out_motion, **params)
+            limited = 0.0
             if f:
                 took = float((d_acc[:, 0] >= 1).double().mean())
+                if shadow_guard:
+                    h.shadow_limit_history_dev(d_acc.data_ptr(), d_motion.data_ptr(), d_shadow.data_ptr(), d_prev_shadow.data_ptr(), n,
+                                               int(prev_params.image_width), int(prev_params.image_height), d_change.data_ptr(),
+                                               tolerance=shadow_guard["tolerance"], drop=shadow_guard["drop"])
+                    tol = abi.ACN_SHADOW_HISTORY_DEFAULT_TOLERANCE if not shadow_guard["tolerance"] else shadow_guard["tolerance"]
+                    limited = float((d_change > tol).double().sum()) / max(1.0, took * n)      # (a NaN change compares false)
                 h.lens_stats_merge_dev(d_acc.data_ptr(), n, d_cur.data_ptr(), n)
             else:
                 took = 0.0
                 d_acc.copy_(d_cur)
                 torch.cuda.synchronize(dev)
-            report.append((took, float(d_acc[:, 0].mean())))
+            report.append((took, float(d_acc[:, 0].mean())) + ((limited,) if shadow_guard else ()))
             if denoise:
                 h.denoise_stats_dev(d_acc.data_ptr(), d_surf.data_ptr(), w, hh, d_lin.data_ptr())
             else:
@@ -131,6 +152,8 @@ def render_temporal(flat, frames, orbit_deg, write, samples, target_distance=Non
             write(f, d_rgb8.cpu().numpy().reshape(hh, w, 3))
             d_surf, d_prev_surf = d_prev_surf, d_surf                          # this frame's records and pooled statistics become "previous"
             d_acc, d_prev = d_prev, d_acc
+            if shadow_guard:
+                d_shadow, d_prev_shadow = d_prev_shadow, d_shadow
             prev_params = abi.Params()
             C.memmove(C.addressof(prev_params), C.addressof(h.params), C.sizeof(abi.Params))
         return h.info(), report
@@ -155,9 +178,21 @@ def main(argv=None):
     ap.add_argument("--spin", type=int, default=None, metavar="NODE", help="turn root element NODE of the scene's matter instead of the camera, --orbit-deg in all")
     ap.add_argument("--spin-axis", default=None, metavar="x,y,z", help="--spin: the axis through the object's position (default 0,0,1)")
     ap.add_argument("--moved-max-history", type=float, default=None, help="--spin --temporal: samples the history of the turned object carries at most")
+    ap.add_argument("--shadow-guard", action="store_true", help="--temporal: limit the history where the light a point sees has changed (acn_shadow_limit_history)")
+    ap.add_argument("--shadow-samples", type=int, default=None, metavar="S", help="--shadow-guard: samples per light of the shadow records (default 16)")
+    ap.add_argument("--shadow-tolerance", type=float, default=None, metavar="T", help="--shadow-guard: the change of the visible share that limits a history (default 0.25)")
+    ap.add_argument("--shadow-drop", action="store_true", help="--shadow-guard: a changed pixel loses its history instead of having it capped at 1")
     args = ap.parse_args(argv)
     if args.frames < 1:
         ap.error("--frames is at least 1")
+    if args.shadow_guard and not args.temporal:
+        ap.error("--shadow-guard belongs to --temporal")
+    if not args.shadow_guard and (args.shadow_samples is not None or args.shadow_tolerance is not None or args.shadow_drop):
+        ap.error("--shadow-samples, --shadow-tolerance and --shadow-drop belong to --shadow-guard")
+    if args.shadow_samples is not None and args.shadow_samples not in (1, 2, 4, 8, 16, 32, 64):
+        ap.error("--shadow-samples is 1, 2, 4, 8, 16, 32 or 64")
+    if args.shadow_tolerance is not None and not (0 < args.shadow_tolerance < float("inf")):
+        ap.error("--shadow-tolerance is a positive number")
     if args.temporal and (args.samples is None or args.samples < 1):
         ap.error("--temporal needs --samples K, at least 1")
     if not args.temporal and (args.samples is not None or args.denoise or args.max_history is not None or args.allow_fresnel):
@@ -198,10 +233,12 @@ def main(argv=None):
             ap.error(f"--spin: the scene's matter has {len(elems)} root elements")
         spin = (elems[args.spin], axis)
     if args.temporal:
+        guard = dict(samples=args.shadow_samples or 16, tolerance=args.shadow_tolerance, drop=args.shadow_drop) if args.shadow_guard else None
         info, report = render_temporal(flat, args.frames, args.orbit_deg, write, args.samples, args.target_distance, args.denoise, args.max_history,
-                                       args.allow_fresnel, spin, args.moved_max_history)
-        for f, (took, mean_n) in enumerate(report):
-            print(f"frame {f}: {took:.3f} of the pixels took a history, mean n {mean_n:.1f}")
+                                       args.allow_fresnel, spin, args.moved_max_history, guard)
+        for f, row in enumerate(report):
+            said = f"frame {f}: {row[0]:.3f} of the pixels took a history, mean n {row[1]:.1f}"
+            print(said + (f", the shadow guard limited {row[2]:.4f} of the histories" if guard else ""))
     else:
         info = render(flat, args.frames, args.orbit_deg, write, args.target_distance, spin)
     changes = f"{info['replaces']} scene changes" if spin else f"{info['param_sets']} parameter changes"
