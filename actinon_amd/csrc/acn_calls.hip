@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <string>
 
+#include "acn_device.h"   /* a ray unit: the whole tracer */
 #include "acn_handle.h"
 #include "acn_stats_host.h"
 #include "acn_select_host.h"

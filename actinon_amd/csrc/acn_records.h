@@ -3,7 +3,8 @@
 #ifndef ACN_RECORDS_H
 #define ACN_RECORDS_H
 
-#include "acn_device.h"   /* (and through it acn_counts.h: the ACN_FLAG_* bits) */
+#include "acn_dev_base.h"    /* V3, DEV, f_abs */
+#include "acn_dev_scene.h"   /* DevScene for acn_launch.h (and through it acn_counts.h: the ACN_FLAG_* bits); no ray layer */
 
 /* ---- fixed-point pixel accumulation ---- */
 #define ACN_FIX_SCALE 1099511627776.0          /* 2^40 */
@@ -74,7 +75,7 @@ struct HardShadow
     double limit;        /* distance of the light hit */
     V3 contrib;          /* what the sample adds to the pixel if it is not occluded */
     uint32_t pixel, pad; /* pixel == ACN_INVALID: dead slot.  pad bit 0: a probe of a specular ray (see probe_push): the light root counts too;
-                            bits 1 .. 31: the resume word of k_shade's in-line pass over the matter root (acn_device.h: ACN_RESUME_FLAG,
+                            bits 1 .. 31: the resume word of k_shade's in-line pass over the matter root (acn_dev_traverse.h: ACN_RESUME_FLAG,
                             resume_record); bit 1 clear: nothing is known, every element is to be tested */
 };
 

@@ -5,7 +5,7 @@
 #define ACN_STATS_DEV_H
 
 #include <hip/hip_runtime.h>
-#include "acn_device.h"   /* V3, cl_sat; acn_sqrt of acn_detmath.h */
+#include "acn_dev_image.h"   /* V3, cl_sat; acn_sqrt of acn_detmath.h */
 
 /* a record whose [ 0 ] is not a finite number >= 1 is EMPTY (a NaN fails both comparisons) */
 __device__ static inline bool stats_empty( double n ) { return !( n >= 1.0 && n < __builtin_inf() ); }

@@ -82,7 +82,7 @@ struct SCEntry
 #define ACN_SC_ROUGH  0x20000u
 #define ACN_SC_BOUNDING 0x40000u   /* the upload step has verified that the envelope contains every leaf below the entry (all of them spheres) */
 
-/* opcodes of the interval-prune programs (acn_device.h: prune_run; acn_tables.cpp: build_prune_programs) */
+/* opcodes of the interval-prune programs (acn_dev_prune.h: prune_run; acn_tables.cpp: build_prune_programs) */
 enum { ACN_PO_END = 0, ACN_PO_PLANE, ACN_PO_SPHERE, ACN_PO_QUAD, ACN_PO_ALL, ACN_PO_NEG, ACN_PO_AND, ACN_PO_OR, ACN_PO_ENV };
 #define ACN_PO( op, node ) ( ( uint32_t )( op ) | ( ( uint32_t )( node ) << 4 ) )
 #define ACN_PRUNE_STACK 5
@@ -112,7 +112,7 @@ struct acn_scene_tables
     std::vector< GNode > nodes;
     std::vector< GMat > mats;
     std::vector< int32_t > elems;         /* given order | cost order | per node: program / table offset or -1 | programs and table headers | elem_pos */
-    std::vector< SCEntry > sc_table;      /* pre-order tables of the simple compounds (acn_device.h: simple_compound_hit) */
+    std::vector< SCEntry > sc_table;      /* pre-order tables of the simple compounds (acn_dev_traverse.h: simple_compound_hit) */
     std::vector< double > sc_spheres;     /* ( pos, radius ) of the sphere leaves of sc_table, ( direction, 0 ) of the reversed tables */
     uint32_t prune_base = 0;              /* elems[ prune_base + node ] */
     uint32_t elem_pos_base = 0;           /* elems[ elem_pos_base + k ]: given-order position of entry k of the cost-ordered copy */

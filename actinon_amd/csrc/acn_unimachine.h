@@ -1,4 +1,4 @@
-/* acn_unimachine.h -- the two CSG machines in LOCK-STEP form (included by acn_device.h).
+/* acn_unimachine.h -- the two CSG machines in LOCK-STEP form (included by acn_dev_machines.h).
  *
  * obj_ray_hit / obj_side (objects.c:261-284, 366-370) of a CSG tree whose ROOT is the same in every lane of the wave --
  * which is how the root-compound loops call them (element_hit).  The per-lane machines above let every lane keep its
@@ -49,7 +49,7 @@ template< class SR > DEV SceneRefT< NodeP > uni_view( const SR& sc )
 /* obj_side for the lanes with `act`, the others get 0.  Side frame word: node << 4 | phase << 2 | early << 1 | in
  * (early: the lane's first child already decided the pair, objects.c:1096-1099 / 1253-1256). */
 template< class SR, class CT >
-DEV_SIDE int obj_side_uni( SR sc, int root, bool act, V3 pos, CT* cnt )
+DEV int obj_side_uni( SR sc, int root, bool act, V3 pos, CT* cnt )
 {
     const SceneRefT< NodeP > g = uni_view( sc );
     uint32_t st[ ACN_CSG_MAX_DEPTH ];
@@ -64,13 +64,13 @@ DEV_SIDE int obj_side_uni( SR sc, int root, bool act, V3 pos, CT* cnt )
     for( ;; )
     {
         /* EVAL( node ) for the lanes with act */
-        ACN_NODE_UNIFORM( n, &g.nodes[ node ] )
+        ACN_NODE( n, &g.nodes[ node ] )
         const int type = n->type;
         const uint32_t nflags = n->flags;
         bool have = true;
         bool in = act;
         if( act ) { cnt->inc( CNT_SIDE ); r = 1; }
-        if( nflags & ACN_NODE_HAS_ENVELOPE ) { if( act ) in = env_side( n, pos ) != 1; }
+        if( nflags & ACN_NODE_HAS_ENVELOPE ) { if( act ) in = env_side( n, pos, cnt ) != 1; }
         if( !wave_any( in ) )
         {
             /* every lane is outside the envelope: r = 1 */
@@ -80,9 +80,9 @@ DEV_SIDE int obj_side_uni( SR sc, int root, bool act, V3 pos, CT* cnt )
             if( in )
             {
                 if( type == ACN_PLANE )         { cnt->cost( ACN_F_SIDE_PLANE ); r = v_sub_mlv( pos, ld3( n->pos ), ld3( n->rax + 6 ) ) > 0 ? 1 : -1; }   /* gmath.h:52-55 */
-                else if( type == ACN_SPHERE )   r = sphere_observer_side( ld3( n->pos ), n->prm[ 0 ], pos );
-                else if( type == ACN_SQUAROID ) r = squaroid_side( n, pos );
-                else                            { r = distance_side( n, pos ); cnt->inc( CNT_SDF_EVAL ); }
+                else if( type == ACN_SPHERE )   r = sphere_observer_side( ld3( n->pos ), n->prm[ 0 ], pos, cnt );
+                else if( type == ACN_SQUAROID ) r = squaroid_side( n, pos, cnt );
+                else                            { r = distance_side( n, pos, cnt ); cnt->inc( CNT_SDF_EVAL ); }
             }
         }
         else if( nflags & ( ACN_GFLAG_LEAF_PAIR | ACN_GFLAG_PAIR2 ) )
@@ -157,11 +157,11 @@ DEV_SIDE int obj_side_uni( SR sc, int root, bool act, V3 pos, CT* cnt )
 }
 
 /* obj_ray_hit of the tree under `root` for every lane that calls (same root in all of them).
- * PARK: the origin of the ray the machine is evaluating lives in the lane's LDS slot (OrgLds, acn_device.h) instead of a register
+ * PARK: the origin of the ray the machine is evaluating lives in the lane's LDS slot (OrgLds, acn_dev_leaves.h) instead of a register
  * that the allocator would spill: written where the reference's recursion passes another origin down (scale wrappers, the walk
  * steps of a pair) or returns to the frame's own, read where a leaf, an envelope or an in-line pair uses it. */
 template< bool NOR, bool PARK = false, class SR, class CT >
-DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, CT* cnt )
+DEV double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, CT* cnt )
 {
     const SceneRefT< NodeP > g = uni_view( sc );
     OrgLds org;
@@ -194,13 +194,13 @@ DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, C
     {
         /* ---- EVAL( node, rp, rd ) for the lanes with act ---- */
         ACN_LAP( PH_M_FRAME );
-        ACN_NODE_UNIFORM( n, &g.nodes[ node ] )
+        ACN_NODE( n, &g.nodes[ node ] )
         const int type = n->type;
         const uint32_t nflags = n->flags;
         bool have = true;
         bool in = act;
         if( act ) { cnt->inc( CNT_OBJ_HIT ); ret_a = F3_INF; }
-        if( nflags & ACN_NODE_HAS_ENVELOPE ) { if( act ) in = env_ray_hits( n, RP(), rd ); }
+        if( nflags & ACN_NODE_HAS_ENVELOPE ) { if( act ) in = env_ray_hits( n, RP(), rd, cnt ); }
         if( !wave_any( in ) )
         {
             /* no lane gets inside the envelope: f3_inf for all */
@@ -210,11 +210,11 @@ DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, C
             ACN_TALLY( 14, in );
             if( in )
             {
-                if( type == ACN_PLANE )         ret_a = plane_ray_hit( ld3( n->pos ), ld3( n->rax + 6 ), RP(), rd, NOR, &ret_n );
-                else if( type == ACN_SPHERE )   ret_a = sphere_ray_hit( ld3( n->pos ), n->prm[ 0 ], RP(), rd, NOR, &ret_n );
-                else if( type == ACN_SQUAROID ) ret_a = squaroid_ray_hit( n, RP(), rd, NOR, &ret_n );
+                if( type == ACN_PLANE )         ret_a = plane_ray_hit( ld3( n->pos ), ld3( n->rax + 6 ), RP(), rd, NOR, &ret_n, cnt );
+                else if( type == ACN_SPHERE )   ret_a = sphere_ray_hit( ld3( n->pos ), n->prm[ 0 ], RP(), rd, NOR, &ret_n, cnt );
+                else if( type == ACN_SQUAROID ) ret_a = squaroid_ray_hit( n, RP(), rd, NOR, &ret_n, cnt );
                 else                            { V3 dn = mk( 0, 0, 0 ); ret_a = distance_ray_hit( n, RP(), rd, NOR, &dn, cnt ); if( NOR && ret_a < F3_INF ) ret_n = dn; }   /* (a real call: only dn's address escapes) */
-                if( NOR && ret_a < F3_INF && n->surface_roughness > 0 ) ret_n = roughness_normal( n, ret_n, ray_pos( RP(), rd, ret_a ) );
+                if( NOR && ret_a < F3_INF && n->surface_roughness > 0 ) ret_n = roughness_normal( n, ret_n, ray_pos( RP(), rd, ret_a ), cnt );
             }
             ACN_LAP( PH_M_LEAF );
         }
@@ -227,7 +227,7 @@ DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, C
                  * and the kernel carries one expansion of the pair code instead of two) */
                 if constexpr( PARK ) ret_a = pair_hit< 2, true >( g, n, org, rd, NOR, &ret_n, cnt );
                 else                 ret_a = pair_hit< 2, true >( g, n, rp, rd, NOR, &ret_n, cnt );
-                if( NOR && ret_a < F3_INF && n->surface_roughness > 0 ) ret_n = roughness_normal( n, ret_n, ray_pos( RP(), rd, ret_a ) );
+                if( NOR && ret_a < F3_INF && n->surface_roughness > 0 ) ret_n = roughness_normal( n, ret_n, ray_pos( RP(), rd, ret_a ), cnt );
             }
             ACN_LAP( PH_M_PAIR );
         }
@@ -423,7 +423,7 @@ DEV_HIT double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, C
             {
                 /* POST of the composite itself (objects.c:266-282), then hand its result to its parent */
                 SET_RP( cur_rp );
-                if( NOR && fn->surface_roughness > 0 ) { if( fin && ret_a < F3_INF ) ret_n = roughness_normal( fn, ret_n, ray_pos( cur_rp, rd, ret_a ) ); }
+                if( NOR && fn->surface_roughness > 0 ) { if( fin && ret_a < F3_INF ) ret_n = roughness_normal( fn, ret_n, ray_pos( cur_rp, rd, ret_a ), cnt ); }
                 if( !( uw & UF_INHERIT ) ) cur_rp = aux[ --na ];
                 derived = false;
                 depth--;

@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <algorithm>
 
+#include "acn_device.h"   /* a ray unit: the whole tracer */
 #include "acn_handle.h"   /* (and the standard headers its types need) */
 
 /* ------------------------------------------------------------------------------------------------------------------ */

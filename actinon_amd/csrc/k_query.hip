@@ -100,12 +100,12 @@ __device__ void query_one( const SC& scv, int op, int32_t node, V3 rp, V3 rd, do
         V3 nor = mk( 0, 0, 0 );
         int ho = -1;
         double a = F3_INF;
-        if( !node_has_env( n ) || env_ray_hits( n, rp, rd ) ) a = simple_compound_hit< true >( scv, node, rp, rd, &nor, &ho, -F3_INF, cnt );
+        if( !node_has_env( n ) || env_ray_hits( n, rp, rd, cnt ) ) a = simple_compound_hit< true >( scv, node, rp, rd, &nor, &ho, -F3_INF, cnt );
         o[ 0 ] = a; o[ 1 ] = nor.x; o[ 2 ] = nor.y; o[ 3 ] = nor.z; o[ 4 ] = ho;
         /* the any-hit form (root_occluded_fast) */
         int ho2 = -1;
         double b = F3_INF;
-        if( !node_has_env( n ) || env_ray_hits( n, rp, rd ) ) b = simple_compound_hit< false >( scv, node, rp, rd, nullptr, &ho2, limit, cnt );
+        if( !node_has_env( n ) || env_ray_hits( n, rp, rd, cnt ) ) b = simple_compound_hit< false >( scv, node, rp, rd, nullptr, &ho2, limit, cnt );
         o[ 5 ] = b <= limit;
     }
 }

@@ -7,6 +7,7 @@
  * camera ray (acn_k_walk.h, k_walk: T = 1, intensity = 1, depth = trace_depth, the slot's position as its pixel), so a
  * camera ray handed in as a caller's ray is traced and shaded exactly as the pipeline's own. */
 #include <hip/hip_runtime.h>
+#include "acn_device.h"   /* a ray unit: the whole tracer */
 #include "acn_launch.h"
 
 __global__ void k_seed_rays( const double* __restrict__ rays, uint32_t base, uint32_t cnt, TileOrder order, int depth,

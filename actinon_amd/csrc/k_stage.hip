@@ -9,6 +9,7 @@
  * belongs to, so the same task runs on 64, 16, 4 and 1 lanes: the index list goes where the kernel of `cls` reads it. */
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include "acn_device.h"   /* a ray unit: the whole tracer */
 #include "acn_handle.h"
 #include "acn_stage_host.h"
 

@@ -429,7 +429,7 @@ int acn_denoise    ( acn_scene_handle* h, const double* linear_rgb, const double
  *
  * The ray of position ( px, py ), sample k (0 <= k < K).  Everything is IEEE binary64 without contraction, a / b is IEEE division,
  * sqrt is acn_sqrt of csrc/acn_detmath.h; f3_rnd0, f3_rnd1 (one step of the LCG each, uniform in [ -1, 1 ] and [ 0, 1 ]),
- * v_random_seed, v_of_length, camera_ray and m_mlv are those of csrc/acn_device.h; camera_rotation is the matrix camera_ray uses;
+ * v_random_seed, v_of_length and m_mlv are those of csrc/acn_dev_base.h, camera_ray that of csrc/acn_dev_image.h; camera_rotation is the matrix camera_ray uses;
  * dot( a, b ) = ( a.x * b.x + a.y * b.y ) + a.z * b.z; vector sums, differences and products by a number are per component.
  *   rv = v_random_seed( ( px, py, ( double )( 2 * k + 1 ) ), ACN_LENS_SEED + seed )        (64-bit sum.  v_random_seed reads of a
  *                     component only its frexp mantissa, which 1, 2, 4, 8 ... share: the odd numbers 2 k + 1 all differ in it,
@@ -870,7 +870,7 @@ double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget );   /* no 
  *
  * acn_project_points*: the inverse of acn_camera_rays*, with the handle's current camera (acn_scene_set_params moves it).
  *   R, V, T = m_mlv( camera_rotation, ( 1, 0, 0 ) ), m_mlv( camera_rotation, ( 0, 1, 0 ) ), m_mlv( camera_rotation, ( 0, 0, 1 ) ): right, view
- *             and top direction, as the lens forms them (m_mlv: csrc/acn_device.h; camera_rotation: the matrix camera_ray uses)
+ *             and top direction, as the lens forms them (m_mlv: csrc/acn_dev_base.h; camera_rotation: the matrix camera_ray uses)
  *   W = image_width, H = image_height, hh = ( double )( H >> 1 ), hw = ( double )( W >> 1 )
  *   v  = P - camera_position                (per component)
  *   ly = dot( v, V )                        the depth along the view direction: out_depth
@@ -888,7 +888,7 @@ double acn_key_hist_threshold( const uint64_t* hist, uint64_t budget );   /* no 
  * raster, pixel centres row-major, W' = prev_params->image_width, H' = prev_params->image_height.  prev_params is the acn_params the
  * previous frame was rendered with; it must pass the checks of acn_scene_set_params, and of it only the raster size and the four
  * camera members are read.  The handle's own scene and camera are not consulted: the handle supplies the device and the stream.
- * The previous camera's basis is formed per lane by the expressions of k_camera_setup (csrc/acn_device.h: camera_rotation_of): its
+ * The previous camera's basis is formed per lane by the expressions of k_camera_setup (csrc/acn_dev_image.h: camera_rotation_of): its
  * bits are those of a handle whose params are prev_params, and the motion plane equals acn_project_points on such a handle bit for bit.
  * out_stats [ n ][ ACN_STATS_STRIDE ]; out_motion (nullable) [ n ][ 2 ].  Per current record r, in this order:
  *   1 HIT        r[ 0 ] < inf, else the motion is ( NaN, NaN ) and the record EMPTY.
@@ -1181,7 +1181,7 @@ int acn_estimate_envelope( acn_scene_handle* h, int32_t node, uint64_t samples, 
  * 11 asin 12 atan 13 atan2(x,y): x is the ordinate 14 llrint as a double (|x| < 2^62) */
 int acn_detmath_eval( int device, int op, const double* x, const double* y, double* out, size_t n );
 
-/* Test hook: the traversal shortcuts of the device (csrc/acn_device.h), one ray per lane, in the arrangement of the
+/* Test hook: the traversal shortcuts of the device (csrc/acn_dev_traverse.h, csrc/acn_dev_prune.h), one ray per lane, in the arrangement of the
  * pipeline's machine kernels (256-lane workgroups, the handle's scene, CSG stacks in LDS).  Ray i runs on lane i % 64 of
  * wave i / 64.  rays: [ n ][ 6 ] origin, direction.  limits (nullable: limit inf, no skips): [ n ][ 2 ], a limit and a
  * 64-bit skip mask (raw bits; root_occluded_fast).  out: [ n ][ ACN_QUERY_STRIDE ] doubles (integers as doubles, masks as

@@ -30,7 +30,7 @@ def upload(flat, **env):
 
 
 def env_enters(node, rays):
-    """env_ray_hits_ (acn_device.h) in the device's order of operations; True where the node has no envelope"""
+    """env_ray_hits (acn_dev_leaves.h) in the device's order of operations; True where the node has no envelope"""
     if not (node.flags & 1):
         return np.ones(len(rays), bool)
     c, r = np.array(node.env_pos[:]), float(node.env_radius)
@@ -96,7 +96,7 @@ def check_trans_and_occlusion(flat, handles, rs, a, oracle, special=()):
                         p = h.query_rays("prune", m, sub.rays[hard], limits=lim[hard], lds=lds, prune=prune)
                         live |= (p[:, 0] == 0) & (p[:, 1] == 0)
                     elif t in (R.ACN_COMPOUND, R.ACN_DISTANCE):
-                        # what root_occluded_fast asks of them: no envelope, or the ray enters it (env_ray_hits_)
+                        # what root_occluded_fast asks of them: no envelope, or the ray enters it (env_ray_hits)
                         live |= env_enters(flat.node(m), sub.rays[hard])
                     else:
                         raise AssertionError(f"element {m} of type {t}: no rule for a hard answer")

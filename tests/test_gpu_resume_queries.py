@@ -53,7 +53,7 @@ def bits(x):
 
 
 def env_enters(node, rays):
-    """env_ray_hits_ (acn_device.h) in the device's order of operations; True where the node has no envelope"""
+    """env_ray_hits (acn_dev_leaves.h) in the device's order of operations; True where the node has no envelope"""
     if not (node.flags & 1):
         return np.ones(len(rays), bool)
     c, r = np.array(node.env_pos[:]), float(node.env_radius)

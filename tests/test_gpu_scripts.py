@@ -2,6 +2,7 @@
 on the GPU to the oracle's result; the render driver behind scene.create_image writes the reference's PNM; the
 actinon_hip command line tool stops softly on SIGINT and resumes from its recovery file."""
 import os
+import select
 import signal
 import subprocess
 import time
@@ -218,23 +219,34 @@ def test_gradient_cycles_match_an_independent_evaluation(oracle, tmp_path):
 
 
 def run_cli_until(cmd, log_path, marker, deadline_s=300):
-    """Starts the command line tool, sends SIGINT once `marker` shows up in its output; returns (rc, text)."""
-    log = open(log_path, "wb")
-    p = subprocess.Popen(cmd, stdout=log, stderr=subprocess.STDOUT)
+    """Starts the command line tool, sends SIGINT once `marker` shows up in its output; returns (rc, text).
+    The output comes through a pipe and is read as it is written (the tool flushes the line of a pass before it starts the pass), so
+    the signal leaves when the marker's pass begins: a pass of cycles24.acn takes about a millisecond on the device, and a reader that
+    looked every 20 ms could find all 24 done and the tool's handler gone."""
+    p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    out = b""
     try:
+        fd = p.stdout.fileno()
         deadline = time.time() + deadline_s
+        sent = marker is None
         while time.time() < deadline:
-            time.sleep(0.02)
-            if marker is not None and marker in open(log_path, "rb").read():
+            if not select.select([fd], [], [], max(0.0, deadline - time.time()))[0]:
+                break
+            piece = os.read(fd, 65536)
+            if not piece:
+                break
+            out += piece
+            if not sent and marker in out:
                 p.send_signal(signal.SIGINT)
-                break
-            if p.poll() is not None:
-                break
-        rc = p.wait(timeout=deadline_s)
+                sent = True
+        rc = p.wait(timeout=max(1.0, deadline - time.time()))
     finally:
         if p.poll() is None:
             p.kill()
-    return rc, open(log_path).read()
+        p.stdout.close()
+    with open(log_path, "wb") as log:
+        log.write(out)
+    return rc, out.decode()
 
 
 def test_interrupted_and_resumed_render_equals_uninterrupted(tmp_path):
