@@ -24,7 +24,7 @@ oracle: oracle/libacn_oracle.so oracle/libacn_oracle_libm.so
 cli: actinon_amd/bin/actinon_hip
 
 # one object per kernel family: `make -j` compiles them side by side (acn_launch.h)
-HIP_UNITS := actinon_hip acn_calls k_query k_stage k_rays k_surface k_denoise k_denoise_layers k_lens k_lens_surface k_lens_layers k_lens_layers_merge k_reproject k_shadow k_select k_frame k_shade_64 k_shade_16 k_shade_4 k_shade_1 k_walk_lds k_walk_glb k_walk_count k_walk_count_prune k_hard_shadow k_hard_path
+HIP_UNITS := actinon_hip acn_calls k_query k_stage k_rays k_surface k_denoise k_denoise_layers k_fill k_lens k_lens_surface k_lens_layers k_lens_layers_merge k_reproject k_shadow k_select k_frame k_shade_64 k_shade_16 k_shade_4 k_shade_1 k_walk_lds k_walk_glb k_walk_count k_walk_count_prune k_hard_shadow k_hard_path
 HIP_OBJS  := $(addprefix $(BUILD)/,$(addsuffix .o,$(HIP_UNITS)))
 # the two production units of k_walk are scheduled for instruction-level parallelism: __launch_bounds__ fixes their occupancy
 # (2 waves per SIMD), which is what the default strategy schedules for (hanging_lamp 600x800 -3 %, everything else equal:

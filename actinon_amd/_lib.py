@@ -34,6 +34,7 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_sc
                "acn_lens_rays", "acn_lens_rays_dev", "acn_render_lens", "acn_render_lens_dev", "acn_render_lens_main_pass_dev",
                "acn_render_lens_stats", "acn_render_lens_stats_dev", "acn_render_lens_stats_main_pass_dev", "acn_lens_stats_merge",
                "acn_lens_stats_merge_dev", "acn_lens_stats_resolve_dev", "acn_denoise_stats", "acn_denoise_stats_dev",
+               "acn_fill_stats", "acn_fill_stats_dev",
                "acn_select_above", "acn_select_above_dev", "acn_key_histogram", "acn_key_histogram_dev", "acn_key_hist_edge",
                "acn_key_hist_threshold",
                "acn_surface_reduce", "acn_surface_reduce_dev", "acn_surface_lens", "acn_surface_lens_dev", "acn_surface_lens_main_pass_dev",
@@ -103,6 +104,8 @@ for _n in ["acn_lens_stats_merge", "acn_lens_stats_merge_dev"]:
 hip.acn_lens_stats_resolve_dev.argtypes = [vp, vp, C.c_size_t, vp, vp, P(abi.RenderOpts)]
 for _n in ["acn_denoise_stats", "acn_denoise_stats_dev"]:
     getattr(hip, _n).argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, P(abi.DenoiseParams), vp, P(abi.RenderOpts)]
+for _n in ["acn_fill_stats", "acn_fill_stats_dev"]:
+    getattr(hip, _n).argtypes = [vp, vp, vp, C.c_size_t, C.c_size_t, P(abi.FillParams), vp, vp, P(abi.RenderOpts)]
 for _n in ["acn_surface_reduce", "acn_surface_reduce_dev"]:
     getattr(hip, _n).argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, P(abi.RenderOpts)]
 for _n in ["acn_surface_lens", "acn_surface_lens_dev"]:

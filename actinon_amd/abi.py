@@ -28,6 +28,10 @@ ACN_LENS_SEED = 2718281828
 ACN_STATS_STRIDE = 8
 ACN_STATS_NOISE_FLOOR = 0.01
 
+# filling a sparse frame (acn_fill_stats): defaults and the limit of acn_fill_params; its flags are the two ACN_DENOISE_* above
+ACN_FILL_DEFAULT_RADIUS, ACN_FILL_MAX_RADIUS = 3, 8
+ACN_FILL_DEFAULT_SIGMA_PX, ACN_FILL_DEFAULT_SIGMA_PLANE = 1.5, 0.1
+
 # layered lens records (acn_lens_layers_reduce, acn_render_lens_layers, acn_denoise_layers, acn_lens_layers_merge,
 # acn_lens_layers_resolve_dev): planes of surface and statistics records
 ACN_LAYERS_SURFACE_PLANES, ACN_LAYERS_STATS_PLANES = 2, 3
@@ -97,6 +101,11 @@ class RenderOpts(C.Structure):
 class DenoiseParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32),
                 ("sigma_plane", C.c_double), ("sigma_lum", C.c_double)]
+
+
+class FillParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("radius", C.c_uint32), ("normal_power_log2", C.c_uint32), ("flags", C.c_uint32),
+                ("sigma_px", C.c_double), ("sigma_plane", C.c_double)]
 
 
 class LensParams(C.Structure):
@@ -189,6 +198,7 @@ class SceneStruct(C.Structure):
 
 assert C.sizeof(Node) == 304, C.sizeof(Node)
 assert C.sizeof(DenoiseParams) == 32, C.sizeof(DenoiseParams)
+assert C.sizeof(FillParams) == 32, C.sizeof(FillParams)
 assert C.sizeof(LensParams) == 32, C.sizeof(LensParams)
 assert C.sizeof(SelectParams) == 40, C.sizeof(SelectParams)
 assert C.sizeof(ReprojectParams) == 40, C.sizeof(ReprojectParams)

@@ -1,5 +1,5 @@
 /* acn_calls.hip -- the entry points of include/actinon_hip.h that stand beside the pipeline: camera rays, surface records, resolve,
- * denoise, the thin-lens camera, its sample statistics, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), shadow records and the history guard, the device-resident frame, and the two test seams acn_estimate_envelope
+ * denoise, the thin-lens camera, its sample statistics and the fill of a sparse frame of them, its surface records and its layered records, select and key histogram, projection and reprojection (with the motion table), shadow records and the history guard, the device-resident frame, and the two test seams acn_estimate_envelope
  * and acn_detmath_eval with the kernels only they launch.  Each is a frame (Call, acn_handle.h) around launch wrappers of
  * acn_launch.h; what renders goes through render_dispatch of actinon_hip.hip, which holds the pipeline and its own entry points.
  * The lens calls that cut their positions into slices share one loop, lens_slices; a host-buffer form is a HostCall (acn_handle.h). */
@@ -10,6 +10,7 @@
 #include "acn_device.h"   /* a ray unit: the whole tracer */
 #include "acn_handle.h"
 #include "acn_stats_host.h"
+#include "acn_fill_host.h"
 #include "acn_select_host.h"
 #include "acn_lenssurf_host.h"
 #include "acn_layers_host.h"
@@ -348,6 +349,53 @@ extern "C" int acn_denoise_stats( acn_scene_handle* h, const double* stats, cons
                                   const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts )
 {
     return denoise_host( h, stats, surface, width, height, prm, out_rgb, opts, true );
+}
+
+/* ---- filling a sparse frame (k_fill.hip; every check: acn_fill_host.h) ---- */
+static int fill_check( const acn_scene_handle* h, const void* stats, const void* surface, size_t width, size_t height, const acn_fill_params* prm,
+                       const void* out_stats, const void* out_need, const acn_render_opts& opts, FillSetup* su )
+{
+    std::string msg;
+    return acn_fill_check( h != nullptr, stats, surface, width, height, prm, out_stats, out_need, opts.shard_world, su, &msg ) == ACN_OK
+           ? ACN_OK : fail( ACN_ERR_ARG, msg );
+}
+
+static int fill_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height, const acn_fill_params* prm,
+                     void* d_out_stats, void* d_out_need, Call& c )
+{
+    FillSetup su;
+    int st = fill_check( h, d_stats, d_surface, width, height, prm, d_out_stats, d_out_need, c.opts, &su );
+    if( st != ACN_OK ) return st;
+    if( ( st = call_begin( h, &c ) ) != ACN_OK ) return st;
+    if( h->d_denoise.grow( width * height * ( size_t )ACN_DENOISE_SCRATCH_PER_PIXEL ) ) return ACN_ERR_DEVICE;
+    acn_launch_fill_stats( ( const double* )d_stats, ( const double* )d_surface, width, height, su.radius, su.normal_power_log2, su.no_demodulate,
+                           su.sigma_px, su.sigma_plane, h->dev.prm.background_color, h->d_denoise.get(), ( double* )d_out_stats, ( double* )d_out_need, c.stream );
+    HIP_TRY( hipGetLastError() );
+    return call_end( c );
+}
+
+extern "C" int acn_fill_stats_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                                   const acn_fill_params* prm, void* d_out_stats, void* d_out_need, const acn_render_opts* opts )
+{
+    Call c( opts );
+    return fill_dev( h, d_stats, d_surface, width, height, prm, d_out_stats, d_out_need, c );
+}
+
+extern "C" int acn_fill_stats( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                               const acn_fill_params* prm, double* out_stats, double* out_need, const acn_render_opts* opts )
+{
+    Call c( opts );
+    FillSetup su;
+    int st = fill_check( h, stats, surface, width, height, prm, out_stats, out_need, c.opts, &su );
+    if( st != ACN_OK ) return st;
+    const size_t n = width * height;
+    HostCall hc( h );
+    void* d_stats = hc.in( stats, sizeof( double ) * ACN_STATS_STRIDE * n );
+    void* d_surf = hc.in( surface, sizeof( double ) * ACN_SURF_STRIDE * n );
+    void* d_out = hc.out( out_stats, sizeof( double ) * ACN_STATS_STRIDE * n );
+    void* d_need = hc.out( out_need, sizeof( double ) * n );
+    c.opts.stream = nullptr;
+    return hc.run( [ & ] { return fill_dev( h, d_stats, d_surf, width, height, prm, d_out, d_need, c ); } );
 }
 
 /* ---- the thin-lens camera (k_lens.hip) ---- */

@@ -110,6 +110,14 @@ void acn_launch_denoise_stats( const double* stats, const double* surf, size_t w
                                uint32_t no_demodulate, double sigma_plane, double sigma_lum, const double* background, void* scratch,
                                double* out_rgb, hipStream_t stream );
 
+/* acn_fill_stats (k_fill.hip): prepare, which also writes every position's output but a FILLED one's, and one gather over the
+ * ( 2 * radius + 1 )^2 window.  stats, surf, out_stats 16-byte aligned, out_need nullable; the parameters are final values; scratch:
+ * ACN_FILL_SCRATCH_PER_PIXEL bytes per pixel (no more than the denoiser's, whose scratch serves), 128-byte aligned */
+#define ACN_FILL_SCRATCH_PER_PIXEL 112
+void acn_launch_fill_stats( const double* stats, const double* surf, size_t width, size_t height, uint32_t radius, uint32_t normal_power_log2,
+                            uint32_t no_demodulate, double sigma_px, double sigma_plane, const double* background, void* scratch,
+                            double* out_stats, double* out_need, hipStream_t stream );
+
 /* the thin-lens camera (k_lens.hip).  LensSetup: acn_lens_params after the host's checks, final values, no defaults.
  * rays: out_rays[ i ][ s ][ 6 ] = the ray of position i, sample first_sample + s (s < n_samples); pos_xy [ n ][ 2 ], or null: the pixel
  * centres first_pixel + i of the scene's raster.  n * n_samples fits a grid of 256-lane workgroups (the host checks).

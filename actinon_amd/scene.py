@@ -664,6 +664,48 @@ class Handle:
         check(hip.acn_denoise_stats_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_ptr, C.byref(o)),
               "acn_denoise_stats_dev")
 
+    # filling a sparse frame (acn_fill_stats): the EMPTY records of a frame from the rendered neighbours of the same surface
+    @staticmethod
+    def fill_params(radius=None, normal_power_log2=None, demodulate=True, sigma_px=None, sigma_plane=None):
+        """acn_fill_params of keyword arguments; None is the library's default"""
+        p = abi.FillParams()
+        p.struct_size = C.sizeof(abi.FillParams)
+        p.radius = 0 if radius is None else int(radius)
+        if normal_power_log2 is not None:
+            p.normal_power_log2 = int(normal_power_log2)
+            p.flags |= abi.ACN_DENOISE_NORMAL_POWER_SET
+        if not demodulate:
+            p.flags |= abi.ACN_DENOISE_NO_DEMODULATE
+        p.sigma_px = 0.0 if sigma_px is None else float(sigma_px)
+        p.sigma_plane = 0.0 if sigma_plane is None else float(sigma_plane)
+        return p
+
+    def fill_stats(self, stats, surface, width, height, **params):
+        """Fills the unrendered positions of a sparse frame (acn_fill_stats): stats the LensStats (or [h*w,8] records) of the raster,
+        EMPTY where nothing was rendered, surface the Surface of EVERY position -> ( LensStats over [h*w,8], need [h,w] float64:
+        -1 rendered, 0 background, 1 - sw / sa filled, +inf unfilled ).  params: radius, normal_power_log2, demodulate, sigma_px,
+        sigma_plane (Handle.fill_params)."""
+        raw = np.ascontiguousarray(stats.raw if isinstance(stats, LensStats) else stats, dtype=np.float64)
+        srf = np.ascontiguousarray(surface.raw if isinstance(surface, Surface) else surface, dtype=np.float64)
+        n = int(width) * int(height)
+        if raw.size != n * abi.ACN_STATS_STRIDE or srf.size != n * abi.ACN_SURF_STRIDE:
+            raise ValueError(f"{height}x{width} pixels need {n} statistics and surface records, got {raw.shape} and {srf.shape}")
+        out = np.empty((n, abi.ACN_STATS_STRIDE), dtype=np.float64)
+        need = np.empty((int(height), int(width)), dtype=np.float64)
+        p = self.fill_params(**params)
+        o = self._plain_opts(False, None)
+        check(hip.acn_fill_stats(self.h, raw.ctypes.data, srf.ctypes.data, width, height, C.byref(p), out.ctypes.data, need.ctypes.data,
+                                 C.byref(o)), "acn_fill_stats")
+        return LensStats(out, self), need
+
+    def fill_stats_dev(self, d_stats_ptr, d_surface_ptr, width, height, d_out_stats_ptr, d_out_need_ptr=None, stream=None, **params):
+        """Device buffers: d_stats, d_out_stats [h*w,8] (they may not overlap), d_surface [h*w,16], d_out_need [h*w] float64 or None;
+        enqueued on `stream` without a synchronisation (None: the handle's stream, synchronous)."""
+        p = self.fill_params(**params)
+        o = self._plain_opts(False, stream)
+        check(hip.acn_fill_stats_dev(self.h, d_stats_ptr, d_surface_ptr, width, height, C.byref(p), d_out_stats_ptr, d_out_need_ptr,
+                                     C.byref(o)), "acn_fill_stats_dev")
+
     # lens surface records (acn_surface_reduce, acn_surface_lens): the K records of a position reduced to one aggregate record
     def surface_reduce(self, records):
         """The aggregate record of every position (acn_surface_reduce): records [n,K,16] float64, the surface records of the K rays

@@ -579,6 +579,83 @@ int acn_denoise_stats_dev( acn_scene_handle* h, const void* d_stats, const void*
 int acn_denoise_stats    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
                            const acn_denoise_params* prm, double* out_rgb, const acn_render_opts* opts );
 
+/* Filling: the unrendered positions of a sparse frame from their rendered neighbours (k_fill.hip).  A frame of which only a subset
+ * was rendered (a lattice, the positions of acn_select_above*, the history acn_reproject* kept) holds EMPTY records elsewhere, which
+ * resolve and the filters show as background.  The surface records of the whole raster cost a small part of shading it and say, for
+ * every position, which object it shows, through which hops, with which normal, position and albedo: which rendered neighbours a
+ * position may borrow from, and which positions no neighbour explains and must be rendered.  All of it is a definition of this library.
+ *   stats      [ height * width ][ ACN_STATS_STRIDE ]  records, EMPTY where nothing was rendered
+ *   surface    [ height * width ][ ACN_SURF_STRIDE ]   the records of EVERY position of the raster, either mode (ACN_SURF_FOLLOW
+ *              recommended, as for acn_denoise)
+ *   out_stats  [ height * width ][ ACN_STATS_STRIDE ]  the records and the filled estimates
+ *   out_need   [ height * width ] f64, nullable        how much each position still wants rendering
+ * Everything is IEEE binary64 without contraction, a / b is IEEE division, exp and sqrt are acn_exp and acn_sqrt of
+ * csrc/acn_detmath.h, a sum a + b + c is ( a + b ) + c, dot( u, v ) is ( u.x * v.x + u.y * v.y ) + u.z * v.z, max( 0, x ) is
+ * x > 0 ? x : 0, and a tap that is skipped adds nothing (the preamble of acn_denoise).  Every sum starts at +0.
+ * Per position, from its surface record r: a.c = r[ 9 + c ] > 0.01 ? r[ 9 + c ] : 1 (1 with ACN_DENOISE_NO_DEMODULATE), N = r[ 4 .. 6 ],
+ * P = r[ 1 .. 3 ], and the KEY ( r[ 7 ], r[ 8 ], r[ 13 ] ) converted to int32: enter object, exit object, hops.  From its statistics
+ * record: n, mean, m2, and vm.c = ( m2.c / ( n - 1 ) ) / n where n > 1.
+ * A position is a DONOR iff its record is not EMPTY, r[ 0 ] < inf, ( uint32 )r[ 12 ] has no ACN_SURF_EMITTER and c = mean / a is finite
+ * in all three channels (a FILTERABLE pixel of acn_denoise_stats).
+ * Each position gets exactly one class, tested in this order:
+ * 1 RENDERED    its record is not EMPTY:  out_stats = the record, bit for bit;  need = -1.0.
+ * 2 BACKGROUND  r[ 0 ] is not < inf (a miss):  out_stats = { 1, background_color, 0, 0, 0, 0 } -- the colour acn_lens_stats_resolve_dev
+ *               gives an EMPTY record with ACN_OPT_LINEAR_OUT;  need = 0.0.
+ * 3 RECEIVER    no ACN_SURF_EMITTER in ( uint32 )r[ 12 ], and the six numbers of N and P are finite.  It gathers over the window
+ *               dy = -R .. R outer, dx = -R .. R inner, R = radius; a tap ( x + dx, y + dy ) off the image is skipped (the centre is
+ *               EMPTY and adds nothing).  Per tap, primes marking what is the tap's:
+ *                 t_s = ( double )( dx * dx + dy * dy ) / ( sigma_px * sigma_px );   k = exp( -t_s )
+ *                 the tap's record is not EMPTY:   sa += k
+ *                 the tap is a DONOR and its KEY equals the receiver's, all three numbers:
+ *                   w_n = max( 0, dot( N, N' ) ), then normal_power_log2 times w_n = w_n * w_n          (step 3 of acn_denoise)
+ *                   D = P' - P;  len = sqrt( dot( D, D ) );  t_p = len > 0 ? ( |dot( N, D )| / len ) / sigma_plane : 0
+ *                   w = w_n * exp( -( t_s + t_p ) )
+ *                   sw += w;   sc.c += w * c'.c
+ *                   n' > 1:   swv += w;   su.c += w * ( vm'.c / ( a'.c * a'.c ) )
+ *               sw > 0: the position is FILLED:
+ *                 mean.c = ( sc.c / sw ) * a.c
+ *                 swv > 0:  n = 2,  m2.c = ( ( su.c / swv ) * ( a.c * a.c ) ) * 2.0  -- so that the record's vm, ( m2 / 1 ) / 2, is the
+ *                           weighted mean of its donors' demodulated vm, remodulated: acn_denoise_stats filters it as it filters them
+ *                 else      n = 1,  m2 = 0
+ *                 [ 7 ] = 0;   need = 1.0 - sw / sa: 0 in a flat region all of whose rendered taps are of the receiver's surface, near
+ *                 1 where few taps of its surface exist (w_n can exceed 1 by a rounding of dot( N, N ): need may then be a few ulp below 0)
+ *               else the position is UNFILLED.
+ * 4 UNFILLED    also emitters and positions whose N or P is not finite:  out_stats = the input record, bit for bit (still EMPTY);
+ *               need = +inf.
+ * The workflow.  The need of every rendered position is below 0, so acn_select_above_dev( need, T ) with T >= 0 is the position list of
+ * the next pass: T = 0.5 asks for the positions most of whose neighbourhood is of other surfaces, and every UNFILLED one.  A filled
+ * record is an estimate, not a sample: a caller keeps its sparse accumulator, merges the new pass into THAT by index (an EMPTY record
+ * takes the part bit for bit) and fills again; it never merges into a filled frame.  A result does not depend on which positions share
+ * a wavefront or a tile.  What the fill leaves open: a receiver none of whose window's rendered taps is of its surface, and the view
+ * dependence of glossy surfaces, which the neighbours of a pixel do not share.
+ * Streams, scratch and the host form are those of acn_denoise_stats: the scene is not consulted, the handle supplies the device, the
+ * stream, background_color and the denoiser's scratch (128 bytes per pixel, of which the fill uses 112); work goes to opts->stream;
+ * NULL is the handle's own stream, and then the call waits; a caller's stream is never synchronised; render calls before and after
+ * compute the same bits.  ACN_ERR_ARG, with acn_last_error set and nothing written: a null handle or buffer (out_need may be null); a zero
+ * width or height or width * height above 2^31; radius > 8; normal_power_log2 > 10; a negative or non-finite sigma; struct_size < 4;
+ * unknown flag bits; shard_world > 1; stats, out_stats or surface not 16-byte aligned, out_need not 8-byte aligned; out_stats or
+ * out_need overlapping stats, or each other (the gather reads its neighbours' inputs). */
+#define ACN_FILL_DEFAULT_RADIUS      3
+#define ACN_FILL_MAX_RADIUS          8
+#define ACN_FILL_DEFAULT_SIGMA_PX    1.5
+#define ACN_FILL_DEFAULT_SIGMA_PLANE 0.1
+typedef struct acn_fill_params
+{
+    uint32_t struct_size;        /* sizeof( acn_fill_params ) as the CALLER was compiled; the library reads nothing beyond it, and
+                                    members it does not reach take their defaults */
+    uint32_t radius;             /* R: the window is ( 2 R + 1 )^2 taps, 1 .. 8; 0 = default 3 */
+    uint32_t normal_power_log2;  /* as in acn_denoise_params: 0 .. 10; 0 = default 7 unless flags has ACN_DENOISE_NORMAL_POWER_SET */
+    uint32_t flags;              /* ACN_DENOISE_NO_DEMODULATE, ACN_DENOISE_NORMAL_POWER_SET: their names and meaning reused */
+    double   sigma_px;           /* default 1.5; a sigma that is 0 takes its default */
+    double   sigma_plane;        /* default 0.1 */
+} acn_fill_params;
+#define ACN_FILL_PARAMS_INIT { ( uint32_t )sizeof( acn_fill_params ), 0u, 0u, 0u, 0.0, 0.0 }
+int acn_fill_stats_dev( acn_scene_handle* h, const void* d_stats, const void* d_surface, size_t width, size_t height,
+                        const acn_fill_params* prm /* nullable: defaults */, void* d_out_stats, void* d_out_need /* nullable */,
+                        const acn_render_opts* opts );
+int acn_fill_stats    ( acn_scene_handle* h, const double* stats, const double* surface, size_t width, size_t height,
+                        const acn_fill_params* prm, double* out_stats, double* out_need /* nullable */, const acn_render_opts* opts );
+
 /* Lens surface records: the guides of a depth-of-field frame (k_lens_surface.hip).  A pinhole record describes the one ray through
  * the sample position; at a defocused edge or an anti-aliased silhouette most of the K lens rays of the position meet something
  * else.  These calls reduce the K surface records of a position to one AGGREGATE record of the same layout (ACN_SURF_STRIDE doubles),
