@@ -113,7 +113,12 @@ template<> struct Cnt< false >
 #define ACN_PH_N 16
 #define ACN_PH_KERNELS 4
 #define ACN_CNT_SLOTS ( CNT_N + 2 + ACN_PH_N * ACN_PH_KERNELS )
-enum { PH_OTHER = 0, PH_LIGHT, PH_ROOT_LEAF, PH_PRUNE, PH_M_LEAF, PH_M_PAIR, PH_M_FRAME, PH_M_SIDE, PH_SHADE, PH_COMPOUND, PH_FETCH, PH_TAIL };
+enum { PH_OTHER = 0, PH_LIGHT, PH_ROOT_LEAF, PH_PRUNE, PH_M_LEAF, PH_M_PAIR, PH_M_FRAME, PH_M_SIDE, PH_SHADE, PH_COMPOUND, PH_FETCH, PH_TAIL,
+       /* k_shade alone (its slots 0 .. 3 hold the round tallies of ACN_TALLY; slots 12 .. 15 are the machine tallies of the other
+        * kernels, acn_unimachine.h).  All 16 slots are taken, so these two are clean only where k_shade enters no machine: in the
+        * LEAF_LIGHTS variants.  With a light that is no leaf, light_hit_call's machine adds its lanes and entries (counts, not
+        * ticks) into them: read the set-up shares of such a scene with that in mind */
+       PH_LIGHT_SETUP, PH_PATH_SETUP };
 #ifdef ACN_PHASE_TIMERS
 __shared__ unsigned long long acn_phase_lds[ 4 ][ ACN_PH_N + 1 ];
 __device__ __forceinline__ void phase_lap( int k )

@@ -68,7 +68,12 @@ enum
     TF_CYL_HGT = 22, TF_LIGHT_POS = 23, TF_RADIANCE = 26,
     TF_SCALE = 27,        /* 3: direct loop: Tc * light_color * ( 2 cyl_hgt / direct_samples ), what a deferred sample's c is multiplied with;
                                 path loop: Tchild = Tc * ( 2 / path_samples ) */
-    TF_N = 30
+    TF_N = 30,
+    /* the batched set-up (k_shade, BATCHED) sets a task up on one lane and runs its loops on a group of lanes, so what a group
+     * holds in registers across a task otherwise is part of the frame: the origin, the luminance so far, the light's colour and
+     * the loop's normalisation, the state of the LCG stream the loop at hand starts from, the cone cull's skip word, the task slot.
+     * 43 doubles: the 16 frames of a batch, and the four of a sub-step, start in distinct LDS banks */
+    TF_POS = 30, TF_LUM = 33, TF_LIGHT_COLOR = 36, TF_NORM = 39, TF_RV, TF_SKIP, TF_SLOT, TF_BATCH_N
 };
 template< bool IN_LDS > struct TaskFrame;
 template<> struct TaskFrame< true >
@@ -78,6 +83,8 @@ template<> struct TaskFrame< true >
     DEV V3 get3( int k ) const { return mk( p[ k ], p[ k + 1 ], p[ k + 2 ] ); }
     DEV void set( bool writer, int k, double v ) { if( writer ) p[ k ] = v; }
     DEV void set3( bool writer, int k, V3 v ) { if( writer ) { p[ k ] = v.x; p[ k + 1 ] = v.y; p[ k + 2 ] = v.z; } }
+    DEV uint64_t getu( int k ) const { return ( ( volatile uint64_t ACN_LDS* )p )[ k ]; }   /* a slot that holds 64 bits as they are */
+    DEV void setu( int k, uint64_t v ) { ( ( volatile uint64_t ACN_LDS* )p )[ k ] = v; }
     /* the writes of the task's first lane are visible to the reads of the others: same wave, program order; the fence keeps the
      * compiler from moving memory operations across */
     DEV void publish() const { __builtin_amdgcn_fence( __ATOMIC_SEQ_CST, "wavefront" ); __builtin_amdgcn_wave_barrier(); }
@@ -197,7 +204,16 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
     /* the wave's root set and the cap sample by selects (RootSet, shade_sphere_cap above): the wide classes without the interval
      * stack of the PRUNE variants, which spilled more with them and got slower (many_spheres +1 %, profiles/r22/NOTES.md) */
     constexpr bool WAVE_LOOPS = FRAME_IN_LDS && !PRUNE;
-    __shared__ __attribute__( ( aligned( 16 ) ) ) double acn_task_frames[ FRAME_IN_LDS ? ( 256 / LPT ) * TF_N : 1 ];
+    /* Batched set-up.  What runs before a task's sample loops -- its frame, and per light the sampling frame, the cone cull and the
+     * colour -- is the same in all LPT lanes of its group: with G tasks per step a wave issues all of it for G distinct values.  Here
+     * a wave takes B tasks at a time and sets them up one task per lane, light by light; the sub-steps q = 0 .. ceil( got / G ) - 1
+     * then run the loops of task q * G + grp on group grp against that task's frame, as a step does otherwise.  Per task the same
+     * arithmetic on the same operands in the same order: lights in their order, then the path loop; its LCG stream; its samples on
+     * lanes ( j - j_lo ) % LPT.  Only the order of the records in the three output queues changes.  Class 16 alone: a task of class
+     * 64 runs dozens of rounds per set-up, and 16 of them in one fetch would unbalance the end of a launch (balanced_batch). */
+    constexpr bool BATCHED = WAVE_LOOPS && LPT == 16;
+    constexpr int B = BATCHED ? 16 : G;   /* tasks a wave takes at a time */
+    __shared__ __attribute__( ( aligned( 16 ) ) ) double acn_task_frames[ BATCHED ? 4 * B * TF_BATCH_N : FRAME_IN_LDS ? ( 256 / LPT ) * TF_N : 1 ];
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPT;
     const int grp = lane / LPT;
@@ -211,16 +227,188 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
     n_tasks = n_tasks < task_cap ? n_tasks : task_cap;
     n_tasks = ( uint32_t )__builtin_amdgcn_readfirstlane( ( int )n_tasks );
     ACN_LEAVE_IF_CHUNK_IS_LOST
-    fetch_batch = balanced_batch( n_tasks, fetch_batch, ( uint32_t )( 64 / LPT ) );
+    fetch_batch = balanced_batch( n_tasks, fetch_batch, ( uint32_t )B );
     uint32_t n_hs = 0, n_hp = 0, n_ch = 0;   /* statistics: records written by this lane */
     auto kill_hs = [ p_hard_shadow ]( uint32_t k ) { p_hard_shadow[ k ].pixel = ACN_INVALID; };
     auto kill_hp = [ p_hard_path ]( uint32_t k ) { p_hard_path[ k ].pixel = ACN_INVALID; };
     auto kill_ch = [ p_children ]( uint32_t k ) { p_children[ k ].pixel = ACN_INVALID; };
 
-    /* persistent waves: G tasks per step, fetched fetch_batch at a time through the class's cursor */
     FetchRange fr;
     range_init( fr, n_tasks > 0 );
-    for( ;; )
+    /* persistent waves, batched: B tasks per step, in sub-steps of G; fetched fetch_batch at a time through the class's cursor.
+     * (The step of the other variants below is left as it was, to the letter: their code objects do not change.  The two forms
+     * share the sample loops as text, acn_k_shade_direct_loop.h and acn_k_shade_path_loop.h.) */
+    if constexpr( BATCHED )
+    {
+        /* What is set up before the loops, into the frame f of the lane's own task.
+         * A SECOND COPY of the set-up in the plain step below ("plain step: task set-up", "... light set-up", "... path set-up"):
+         * shared code changed the code objects of the variants that keep that step.  An edit to either copy belongs in both; what
+         * catches a difference is the comparison of class 16 with class 4 in tests/test_gpu_shade_batches.py.
+         * The task's own values: */
+        auto task_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t )
+        {
+            const V3 surface_d = ldc( t.surface_d );
+            f.set3( true, TF_SURFACE_D, surface_d );
+            f.set3( true, TF_RAY_PRJ, ldc( t.ray_projection ) );
+            const double theta_i = t.theta_i;
+            double sin_i = 0, cos_i = 1;   /* loop invariant half of the Oren-Nayar term */
+            if( t.on_b > 0 ) acn_sincos( theta_i, &sin_i, &cos_i );
+            f.set( true, TF_SIN_I, sin_i ); f.set( true, TF_COS_I, cos_i );
+            f.set( true, TF_TAN_I, cos_i > 0 ? sin_i / cos_i : 0.0 );   /* direct-light loop only, and only where cos_i > weight > 0 */
+            f.set( true, TF_THETA_I, theta_i );
+            f.set( true, TF_ON_A, t.on_a ); f.set( true, TF_ON_B, t.on_b );
+            f.set( true, TF_DIFF_I, t.diffuse_intensity );
+        };
+        /* a light's, scene.c:542-555: the sampling frame, the root elements the cone cull leaves, colour and normalisation */
+        auto light_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t, const V3 pos, const uint64_t direct_samples, const int light_idx,
+                                  uint64_t* skip, V3* light_color, double* norm )
+        {
+            NodeP light_src = &sc.nodes[ light_idx ];
+            MatP light_mat = &sc.mats[ light_idx ];
+            V3 fov_d; double cos_rs;
+            obj_fov_dev( light_src, pos, &fov_d, &cos_rs );
+            const M3 src_frame = m_con_z( fov_d );
+            const double cyl_hgt = 1 - cos_rs;
+            /* root elements no shadow ray of this loop can reach (all of them lie in the light's sampling cone; src_frame.z is
+             * the axis the cap samples are drawn around) */
+            *skip = root_cone_cull( scp, sc.matter_root, pos, src_frame.z, 1.0 - cyl_hgt );
+            const V3 light_pos = ld3( light_src->pos );
+            *light_color = obj_color_dev( sc, light_idx, light_pos );   /* scene.c:552 */
+            *norm = 2.0 * cyl_hgt / direct_samples;
+            frame_set_con( f, true, m_transposed( src_frame ) );
+            f.set( true, TF_CYL_HGT, cyl_hgt );
+            f.set3( true, TF_LIGHT_POS, light_pos );
+            f.set( true, TF_RADIANCE, light_mat->radiance );
+            const V3 Tc = ldc( t.Tc );
+            f.set3( true, TF_SCALE, mk( Tc.x * ( light_color->x * *norm ), Tc.y * ( light_color->y * *norm ), Tc.z * ( light_color->z * *norm ) ) );
+        };
+        /* the path loop's, scene.c:584-595 */
+        auto path_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t, const double norm )
+        {
+            frame_set_con( f, true, m_transposed( m_con_z( f.get3( TF_SURFACE_D ) ) ) );
+            f.set3( true, TF_SCALE, v_mlf( ldc( t.Tc ), norm ) );
+        };
+        auto sample_count = []( const double per_unit, const double diffuse_intensity ) { const uint64_t n = ( uint64_t )( per_unit * diffuse_intensity ); return n == 0 ? ( uint64_t )1 : n; };
+        /* "a < max_path_length" as the any-hit limit "a <= path_limit": the largest double below it */
+        auto path_limit_of = [ & ]() { return sc.prm.max_path_length < F3_INF ? acn_bits_f64( acn_f64_bits( sc.prm.max_path_length ) - 1ull ) : F3_BIG; };
+
+        volatile double ACN_LDS* const wave_frames = ( volatile double ACN_LDS* )acn_task_frames + ( threadIdx.x >> 6 ) * ( B * TF_BATCH_N );
+        TaskFrame< true > mine;   /* the frame of the task this lane sets up: lanes 0 .. B - 1 */
+        mine.p = wave_frames + ( lane % B ) * TF_BATCH_N;
+        NodeP light = &sc.nodes[ sc.light_root ];
+        const int n_lights = light->child1;
+        for( ;; )
+        {
+            uint32_t base = 0;
+            const uint32_t got = range_take( fr, p_counts + QC_CUR_SHADE0 + cls, fetch_batch, n_tasks, ( uint32_t )B, &base );
+            if( got == 0 ) break;
+            const uint32_t n_sub = ( got + G - 1 ) / G;
+            /* task phase: lane k < got has entry base + k of the index list; a dead entry leaves a dead frame */
+            uint32_t slot = ACN_INVALID;
+            if( ( uint32_t )lane < got ) slot = ( ( ElemP )( const void* )idx )[ base + lane ];
+            const bool setup = slot != ACN_INVALID;
+            const DTask ACN_CONST& t = ( ( const DTask ACN_CONST* )tasks )[ setup ? slot : 0u ];   /* read under `setup` alone */
+            if( lane < B ) mine.setu( TF_SLOT, slot );
+            if( setup )
+            {
+                task_setup( mine, t );
+                mine.set3( true, TF_POS, ldc( t.pos ) );
+                mine.set3( true, TF_LUM, mk( 0, 0, 0 ) );   /* lum_l of scene.c:539 */
+                mine.setu( TF_RV, t.rv );
+            }
+            ACN_LAP( PH_FETCH );
+
+            /* ---- direct light, scene.c:542-581 ---- */
+            for( int li = 0; li < n_lights; li++ )
+            {
+                const int light_idx = __builtin_amdgcn_readfirstlane( sc.elems[ light->child0 + li ] );
+                NodeP light_src = &sc.nodes[ light_idx ];
+                if( setup )
+                {
+                    cnt.cost( ACN_F_FOV + ACN_F_FRAME );   /* per task and light */
+                    const uint64_t direct_samples = sample_count( sc.prm.direct_samples, mine.get( TF_DIFF_I ) );
+                    if( li > 0 ) mine.setu( TF_RV, lcg00_jump( mine.getu( TF_RV ), 2 * direct_samples ) );   /* behind the loop of light li - 1 */
+                    uint64_t skip; V3 light_color; double norm;
+                    light_setup( mine, t, mine.get3( TF_POS ), direct_samples, light_idx, &skip, &light_color, &norm );
+                    mine.setu( TF_SKIP, skip );
+                    mine.set3( true, TF_LIGHT_COLOR, light_color );
+                    mine.set( true, TF_NORM, norm );
+                }
+                mine.publish();
+                ACN_LAP( PH_LIGHT_SETUP );
+                for( uint32_t q = 0; q < n_sub; q++ )
+                {
+                    fr_.p = wave_frames + ( q * G + grp ) * TF_BATCH_N;
+                    const uint32_t q_slot = ( uint32_t )F.getu( TF_SLOT );
+                    if( q_slot == ACN_INVALID ) continue;
+                    const DTask ACN_CONST& t = ( ( const DTask ACN_CONST* )tasks )[ q_slot ];   /* the group's task, as the loop names it */
+                    const V3 pos = F.get3( TF_POS );
+                    const bool oren_nayar = F.get( TF_ON_B ) > 0;
+                    const uint64_t skip = F.getu( TF_SKIP ), rv = F.getu( TF_RV );
+                    const uint64_t direct_samples = sample_count( sc.prm.direct_samples, F.get( TF_DIFF_I ) );
+                    const auto root_at = root_set< true >( scp, sc.matter_root, skip );
+#include "acn_k_shade_direct_loop.h"
+                    s = group_sum< LPT >( s );
+                    const double f = s * F.get( TF_NORM );
+                    if( writer )
+                    {
+                        V3 lum = F.get3( TF_LUM );
+                        const V3 light_color = F.get3( TF_LIGHT_COLOR );
+                        lum.x += light_color.x * f; lum.y += light_color.y * f; lum.z += light_color.z * f;
+                        fr_.set3( true, TF_LUM, lum );
+                    }
+                    ACN_LAP( PH_SHADE );
+                }
+                fr_.publish();
+            }
+
+            /* ---- path tracing, scene.c:584-621 ---- */
+            if( sc.prm.path_samples )
+            {
+                const V3 bg = ld3( sc.prm.background_color );
+                const double path_limit = path_limit_of();
+                if( setup && t.depth > 10 )
+                {
+                    cnt.cost( ACN_F_FRAME );
+                    const double diffuse_intensity = mine.get( TF_DIFF_I );
+                    if( n_lights > 0 ) mine.setu( TF_RV, lcg00_jump( mine.getu( TF_RV ), 2 * sample_count( sc.prm.direct_samples, diffuse_intensity ) ) );
+                    const double norm = 2.0 / sample_count( sc.prm.path_samples, diffuse_intensity );
+                    path_setup( mine, t, norm );
+                    mine.set( true, TF_NORM, norm );
+                }
+                mine.publish();
+                ACN_LAP( PH_PATH_SETUP );
+                for( uint32_t q = 0; q < n_sub; q++ )
+                {
+                    fr_.p = wave_frames + ( q * G + grp ) * TF_BATCH_N;
+                    const uint32_t q_slot = ( uint32_t )F.getu( TF_SLOT );
+                    if( q_slot == ACN_INVALID ) continue;
+                    const DTask ACN_CONST& t = ( ( const DTask ACN_CONST* )tasks )[ q_slot ];
+                    if( !( t.depth > 10 ) ) continue;
+                    const V3 pos = F.get3( TF_POS );
+                    const bool oren_nayar = F.get( TF_ON_B ) > 0;
+                    const double diffuse_intensity = F.get( TF_DIFF_I );
+                    const uint64_t rv = F.getu( TF_RV );
+                    const uint64_t path_samples = sample_count( sc.prm.path_samples, diffuse_intensity );
+#include "acn_k_shade_path_loop.h"
+                    bsum = group_sum< LPT >( bsum ) * F.get( TF_NORM );
+                    if( writer )
+                    {
+                        V3 lum = F.get3( TF_LUM );
+                        lum.x += bg.x * bsum; lum.y += bg.y * bsum; lum.z += bg.z * bsum;
+                        fr_.set3( true, TF_LUM, lum );
+                    }
+                }
+                fr_.publish();
+            }
+
+            /* end phase */
+            if( setup ) pixel_add( accum, sc.flags, t.pixel, v_mld( ldc( t.Tc ), mine.get3( TF_LUM ) ) );
+            ACN_LAP( PH_SHADE );
+        }
+    }
+    /* persistent waves: G tasks per step, fetched fetch_batch at a time through the class's cursor */
+    else for( ;; )
     {
         uint32_t base = 0;
         uint32_t got = range_take( fr, p_counts + QC_CUR_SHADE0 + cls, fetch_batch, n_tasks, ( uint32_t )G, &base );
@@ -234,6 +422,8 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
         const V3 pos = ldc( t.pos );   /* the origin of every ray of the task: stays in registers */
         const double diffuse_intensity = t.diffuse_intensity;
         const bool oren_nayar = t.on_b > 0;
+        /* plain step: task set-up.  The batched form above has a copy of it and of the two below (task_setup, light_setup,
+         * path_setup, sample_count, path_limit_of): an edit here belongs there as well */
         {
             const V3 surface_d = ldc( t.surface_d );
             fr_.set3( writer, TF_SURFACE_D, surface_d );
@@ -249,8 +439,9 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
         }
         uint64_t rv = t.rv;
         V3 lum = mk( 0, 0, 0 );   /* lum_l of scene.c:539, identical in all lanes of the group after each reduction */
-        ACN_LAP( PH_FETCH );      /* diagnostic build: k_shade books 10 task fetch / set-up, 4 cap sample, 5 light hit, 6 Oren-Nayar,
-                                     7 occlusion, 8 queue appends and sums, 9 path sample, 11 path transition hit */
+        ACN_LAP( PH_FETCH );      /* diagnostic build: k_shade books 10 task fetch / set-up, 12 light set-up (cone cull, frame, root set),
+                                     4 cap sample, 5 light hit, 6 Oren-Nayar, 7 occlusion, 8 queue appends and sums, 13 path set-up,
+                                     9 path sample, 11 path transition hit; batched: the set-up of the tasks of a batch, one per lane */
         const uint64_t direct_samples = [ & ]() { uint64_t n = ( uint64_t )( sc.prm.direct_samples * diffuse_intensity ); return n == 0 ? ( uint64_t )1 : n; }();
         NodeP light = &sc.nodes[ sc.light_root ];
         const int n_lights = light->child1;
@@ -265,6 +456,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
             uint64_t skip;
             V3 light_color;
             double norm;
+            /* plain step: light set-up (copy in the batched form: light_setup) */
             {
                 V3 fov_d; double cos_rs;
                 obj_fov_dev( light_src, pos, &fov_d, &cos_rs );
@@ -285,74 +477,9 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 fr_.publish();
             }
             const auto root_at = root_set< WAVE_LOOPS >( scp, sc.matter_root, skip );
+            ACN_LAP( PH_LIGHT_SETUP );
 
-            double s = 0;
-            /* ACN_SHARD_SAMPLES (shard_world > 1, level 0 only): this rank's share of the loop; sample j keeps its
-             * place in the LCG stream and the normalisation above keeps the whole loop's n */
-            uint64_t j_lo = 0, j_hi = direct_samples;
-            uint64_t rv0 = rv;
-            if( shard_world > 1 )
-            {
-                j_lo = direct_samples * shard_rank / shard_world; j_hi = direct_samples * ( shard_rank + 1 ) / shard_world;
-                rv0 = lcg00_jump( rv, 2 * j_lo );
-            }
-            uint64_t rvj = lcg_jump_lane( rv0, sub );
-            for( uint64_t j = j_lo + sub; j < j_hi; j += LPT )
-            {
-                ACN_TALLY( 0, true );   /* diagnostic build: lanes in a round of the direct-light loop */
-                uint64_t r = rvj;
-                rvj = lcg_stride< LPT >( rvj );
-                cnt.inc( CNT_CAP_SAMPLE );
-                cnt.cost( ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
-                const V3 cap = shade_sphere_cap< WAVE_LOOPS >( &r, F.get( TF_CYL_HGT ) );
-                const V3 out_d = m_mlv( frame_con( F ), cap );
-                double weight = v_mlv( out_d, F.get3( TF_SURFACE_D ) );
-                ACN_LAP( PH_M_LEAF );
-                if( weight <= 0 ) continue;
-                double a;
-                if( LEAF_LIGHTS ) a = leaf_element_hit< false >( light_src, light_src->type, pos, out_d, nullptr, &cnt );
-                else a = light_hit_call( sc, light_idx, pos, out_d, &cnt );
-                ACN_LAP( PH_M_PAIR );
-                if( a >= F3_INF ) continue;
-                cnt.inc( CNT_SHADOW_RAY );
-                ACN_LAP( PH_M_FRAME );
-                uint32_t cand;   /* occ == 2: the machine elements left for k_hard_shadow */
-                int occ = root_occluded_fast( scp, sc.matter_root, pos, out_d, a, skip, &cand, &cnt, root_at );
-                ACN_LAP( PH_M_SIDE );
-                if( occ == 1 ) continue;
-                /* what the sample adds if it is not occluded (scene.c:569-574); the weight of a direct-light sample only scales its
-                 * colour: closed form (oren_nayar_weight_direct).  Computed behind the occlusion test: an occluded sample needs none
-                 * of it, and the test above holds no register for it */
-                if( oren_nayar )
-                {
-                    cnt.cost( ACN_F_OREN_NAYAR_DIRECT );
-                    weight = oren_nayar_weight_direct( weight, F.get( TF_SIN_I ), F.get( TF_COS_I ), F.get( TF_TAN_I ), F.get( TF_ON_A ), F.get( TF_ON_B ), out_d,
-                                                       F.get3( TF_SURFACE_D ), F.get3( TF_RAY_PRJ ) );
-                }
-                V3 hit_pos = ray_pos( pos, out_d, a );
-                double diff_sqr = v_diff_sqr( hit_pos, F.get3( TF_LIGHT_POS ) );
-                double local_intensity = ( diff_sqr > 0 ) ? ( F.get( TF_RADIANCE ) / diff_sqr ) : F3_MAG;
-                double c = local_intensity * weight * F.get( TF_DIFF_I );
-                if( cand == 0 ) { s += c; cnt.cost( ACN_F_DIRECT_TAIL ); }
-                /* hard shadow rays: appended to the queue of k_hard_shadow, which adds the contribution itself if unoccluded */
-                uint32_t hs = chunk_alloc( cs + 0, &p_counts[ QC_HARD_SHADOW ], cand != 0 );
-                if( cand != 0 )
-                {
-                    if( hs < hs_cap )
-                    {
-                        HardShadow& h = p_hard_shadow[ hs ];
-                        const V3 scale = F.get3( TF_SCALE );
-                        h.pos = pos; h.d = out_d; h.limit = a;
-                        h.contrib = mk( scale.x * c, scale.y * c, scale.z * c );
-                        h.pixel = t.pixel; h.pad = resume_record( cand );
-                        n_hs++;
-                    }
-                    else
-                    {
-                        atomicOr( sc_in.flags, ACN_FLAG_CHILD_OVERFLOW );
-                    }
-                }
-            }
+#include "acn_k_shade_direct_loop.h"
             rv = lcg00_jump( rv, 2 * direct_samples );
             s = group_sum< LPT >( s );
             double f = s * norm;
@@ -364,6 +491,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
         if( sc.prm.path_samples && t.depth > 10 )
         {
             if( sub == 0 ) cnt.cost( ACN_F_FRAME );
+            /* plain step: path set-up (copy in the batched form: path_setup, sample_count, path_limit_of) */
             uint64_t path_samples = ( uint64_t )( sc.prm.path_samples * diffuse_intensity );
             path_samples = ( path_samples == 0 ) ? 1 : path_samples;
             const double norm = 2.0 / path_samples;
@@ -375,107 +503,8 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 fr_.set3( writer, TF_SCALE, v_mlf( ldc( t.Tc ), norm ) );
                 fr_.publish();
             }
-            double bsum = 0;
-            uint64_t j_lo = 0, j_hi = path_samples;
-            uint64_t rv0 = rv;
-            if( shard_world > 1 )
-            {
-                j_lo = path_samples * shard_rank / shard_world; j_hi = path_samples * ( shard_rank + 1 ) / shard_world;
-                rv0 = lcg00_jump( rv, 2 * j_lo );
-            }
-            uint64_t rvj = lcg_jump_lane( rv0, sub );
-            for( uint64_t j = j_lo + sub; j < j_hi; j += LPT )
-            {
-                ACN_TALLY( 2, true );   /* ... of the path loop */
-                uint64_t r = rvj;
-                rvj = lcg_stride< LPT >( rvj );
-                cnt.inc( CNT_CAP_SAMPLE );
-                cnt.cost( ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
-                const V3 cap = shade_sphere_cap< WAVE_LOOPS >( &r, 1.0 );
-                const V3 out_d = m_mlv( frame_con( F ), cap );
-                double weight = v_mlv( out_d, F.get3( TF_SURFACE_D ) );
-                bool live = weight > 0;
-                double a = F3_INF;
-                Trans trans;
-                trans.exit_nor = mk( 0, 0, 0 ); trans.exit_obj = -1; trans.enter_obj = -1;
-                bool hard = false;
-                uint32_t machines = 0, inline_hits = 0;   /* candidate words of the in-line pass: what is left for the hard-ray kernels */
-                if( live )
-                {
-                    if( oren_nayar )
-                    {
-                        cnt.cost( ACN_F_OREN_NAYAR, ACN_T_OREN_NAYAR );
-                        weight = oren_nayar_weight_pre( weight, F.get( TF_THETA_I ), F.get( TF_SIN_I ), F.get( TF_COS_I ), F.get( TF_ON_A ), F.get( TF_ON_B ), out_d,
-                                                        F.get3( TF_SURFACE_D ), F.get3( TF_RAY_PRJ ) );
-                    }
-                    cnt.cost( ACN_F_PATH_TAIL );
-                    ACN_LAP( PH_COMPOUND );
-                    a = root_trans_hit_fast( scp, sc.matter_root, pos, out_d, &trans, &hard, &machines, &inline_hits, &cnt );
-                    ACN_LAP( PH_TAIL );
-                }
-                const double child_intensity = weight * diffuse_intensity;
-                bool hit = live && !hard && a < sc.prm.max_path_length;
-                if( live && !hard && !hit ) bsum += child_intensity;
-                /* scene_s_lum of a hit with depth - 10 == 0 or too little intensity is zero (scene.c:430): such a hit is not
-                 * queued, and such a ray that needs the machine only needs a yes / no (see probe_push) */
-                const bool dark = t.depth - 10 == 0 || child_intensity < sc.prm.trace_min_intensity;
-                if( dark ) hit = false;
-                const bool probe = hard && dark;
-                if( probe ) { hard = false; cnt.inc( CNT_TRANS_RAY ); }   /* the compound_s_ray_trans_hit this probe stands for */
-                /* a probe whose in-line elements already hit within the limit is occluded whatever the machines say: not written */
-                const bool probe_open = probe && !( a <= path_limit );
-                uint32_t ps = chunk_alloc( cs + 0, &p_counts[ QC_HARD_SHADOW ], probe_open );
-                if( probe_open )
-                {
-                    if( ps < hs_cap )
-                    {
-                        HardShadow& h = p_hard_shadow[ ps ];
-                        h.pos = pos; h.d = out_d; h.limit = path_limit;
-                        h.contrib = v_mld( F.get3( TF_SCALE ), v_mlf( bg, child_intensity ) );   /* k_hard_path's term for a miss */
-                        h.pixel = t.pixel; h.pad = resume_record( machines );
-                        n_hs++;
-                    }
-                    else
-                    {
-                        atomicOr( sc_in.flags, ACN_FLAG_CHILD_OVERFLOW );
-                    }
-                }
-                /* hard path rays: the transition hit is finished by k_hard_path */
-                uint32_t hp = chunk_alloc( cs + 1, &p_counts[ QC_HARD_PATH ], hard );
-                if( hard )
-                {
-                    if( hp < hard_cap )
-                    {
-                        HardPath& h = p_hard_path[ hp ];
-                        h.pos = pos; h.d = out_d; h.T = F.get3( TF_SCALE ); h.intensity = child_intensity;
-                        h.depth = t.depth - 10; h.pixel = t.pixel;
-                        h.resume = resume_record( machines | inline_hits ); h.pad = 0;
-                        n_hp++;
-                    }
-                    else
-                    {
-                        atomicOr( sc_in.flags, ACN_FLAG_CHILD_OVERFLOW );
-                    }
-                }
-                /* the surviving path rays: the next level's queue */
-                uint32_t csl = chunk_alloc( cs + 2, &p_counts[ QC_CHILDREN ], hit );
-                if( hit )
-                {
-                    if( csl < child_cap )
-                    {
-                        HitRec& c = p_children[ csl ];
-                        c.p = pos; c.d = out_d; c.offs = a; c.exit_nor = trans.exit_nor; c.T = F.get3( TF_SCALE );
-                        c.intensity = child_intensity;
-                        c.exit_obj = trans.exit_obj; c.enter_obj = trans.enter_obj;
-                        c.depth = t.depth - 10; c.pixel = t.pixel;
-                        n_ch++;
-                    }
-                    else
-                    {
-                        atomicOr( sc_in.flags, ACN_FLAG_CHILD_OVERFLOW );
-                    }
-                }
-            }
+            ACN_LAP( PH_PATH_SETUP );
+#include "acn_k_shade_path_loop.h"
             bsum = group_sum< LPT >( bsum ) * norm;
             lum.x += bg.x * bsum; lum.y += bg.y * bsum; lum.z += bg.z * bsum;
         }

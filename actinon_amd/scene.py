@@ -410,7 +410,7 @@ class Handle:
         return dict(zip(names, [int(v) for v in buf]))
 
     PHASES = ["other", "light", "root_leaf", "prune", "m_leaf", "m_pair", "m_frame", "m_side", "shade", "compound", "fetch",
-              "tail"]
+              "tail", "light_setup", "path_setup"]   # the last two: k_shade alone (machine tallies in the other kernels' slots)
 
     def last_counters_raw(self, n):
         buf = (C.c_uint64 * n)()
