@@ -181,6 +181,66 @@ template< bool SELECT > DEV V3 shade_sphere_cap( uint64_t* rv, double h )
     }
 }
 
+/* What runs before a task's sample loops.  Both forms of k_shade's step use it, the plain step and the batched form (BATCHED): this
+ * is the one place it is defined.  The three set-ups are text, as the sample loops are (acn_k_shade_direct_loop.h): a form
+ * compiles from the tokens it would have written out, and a change to one form's step leaves the other's code object alone; through
+ * DEV functions or lambdas shared by the two forms it did not.  f is the frame that is set up and w whether
+ * the lane writes it: fr_ and writer in the plain step, the frame of the lane's own task and true in the batched form.
+ * ACN_SHADE_TASK_SETUP: the task's own values, the surface frame and the Oren-Nayar constants.  In scope: t (the DTask). */
+#define ACN_SHADE_TASK_SETUP( f, w ) \
+    { \
+        const V3 surface_d = ldc( t.surface_d ); \
+        f.set3( w, TF_SURFACE_D, surface_d ); \
+        f.set3( w, TF_RAY_PRJ, ldc( t.ray_projection ) ); \
+        const double theta_i = t.theta_i; \
+        double sin_i = 0, cos_i = 1;   /* loop invariant half of the Oren-Nayar term */ \
+        if( t.on_b > 0 ) acn_sincos( theta_i, &sin_i, &cos_i ); \
+        f.set( w, TF_SIN_I, sin_i ); f.set( w, TF_COS_I, cos_i ); \
+        f.set( w, TF_TAN_I, cos_i > 0 ? sin_i / cos_i : 0.0 );   /* direct-light loop only, and only where cos_i > weight > 0 */ \
+        f.set( w, TF_THETA_I, theta_i ); \
+        f.set( w, TF_ON_A, t.on_a ); f.set( w, TF_ON_B, t.on_b ); \
+        f.set( w, TF_DIFF_I, t.diffuse_intensity ); \
+    }
+/* ACN_SHADE_LIGHT_SETUP: a light's, scene.c:542-555: the sampling frame, the root elements the cone cull leaves, colour and
+ * normalisation.  In scope: t, pos, light_idx, light_src and light_mat (the light's node and material), direct_samples, and the
+ * scene (sc, scp).  It assigns skip, light_color and norm. */
+#define ACN_SHADE_LIGHT_SETUP( f, w ) \
+    { \
+        V3 fov_d; double cos_rs; \
+        obj_fov_dev( light_src, pos, &fov_d, &cos_rs ); \
+        const M3 src_frame = m_con_z( fov_d ); \
+        const double cyl_hgt = 1 - cos_rs; \
+        /* root elements no shadow ray of this loop can reach (all of them lie in the light's sampling cone; src_frame.z is \
+         * the axis the cap samples are drawn around) */ \
+        skip = root_cone_cull( scp, sc.matter_root, pos, src_frame.z, 1.0 - cyl_hgt ); \
+        const V3 light_pos = ld3( light_src->pos ); \
+        light_color = obj_color_dev( sc, light_idx, light_pos );   /* scene.c:552 */ \
+        norm = 2.0 * cyl_hgt / direct_samples; \
+        frame_set_con( f, w, m_transposed( src_frame ) ); \
+        f.set( w, TF_CYL_HGT, cyl_hgt ); \
+        f.set3( w, TF_LIGHT_POS, light_pos ); \
+        f.set( w, TF_RADIANCE, light_mat->radiance ); \
+        const V3 Tc = ldc( t.Tc ); \
+        f.set3( w, TF_SCALE, mk( Tc.x * ( light_color.x * norm ), Tc.y * ( light_color.y * norm ), Tc.z * ( light_color.z * norm ) ) ); \
+    }
+/* ACN_SHADE_PATH_SETUP: the path loop's, scene.c:584-595.  In scope: t, and norm, 2 / path_samples. */
+#define ACN_SHADE_PATH_SETUP( f, w ) \
+    { \
+        frame_set_con( f, w, m_transposed( m_con_z( f.get3( TF_SURFACE_D ) ) ) ); \
+        f.set3( w, TF_SCALE, v_mlf( ldc( t.Tc ), norm ) ); \
+    }
+/* the samples of a loop: per_unit is the scene's direct_samples or path_samples */
+DEV uint64_t shade_sample_count( double per_unit, double diffuse_intensity )
+{
+    const uint64_t n = ( uint64_t )( per_unit * diffuse_intensity );
+    return n == 0 ? ( uint64_t )1 : n;
+}
+/* "a < max_path_length" as the any-hit limit "a <= path_limit": the largest double below it */
+DEV double shade_path_limit( double max_path_length )
+{
+    return max_path_length < F3_INF ? acn_bits_f64( acn_f64_bits( max_path_length ) - 1ull ) : F3_BIG;
+}
+
 /* LEAF_LIGHTS: every light is a plane / sphere / squaroid-free leaf, so the kernel contains no call into the CSG
  * machine at all (the usual case); otherwise the light hit goes through the generic element test.
  * The tasks are idx[ 0 .. min( p_counts[ QC_CLASS0 + cls ], task_cap ) ) (dead entries skipped); the persistent waves of
@@ -236,61 +296,20 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
     FetchRange fr;
     range_init( fr, n_tasks > 0 );
     /* persistent waves, batched: B tasks per step, in sub-steps of G; fetched fetch_batch at a time through the class's cursor.
-     * (The step of the other variants below is left as it was, to the letter: their code objects do not change.  The two forms
-     * share the sample loops as text, acn_k_shade_direct_loop.h and acn_k_shade_path_loop.h.) */
+     * (The two forms share the set-up, ACN_SHADE_TASK_SETUP and what follows it above, and the sample loops as text,
+     * acn_k_shade_direct_loop.h and acn_k_shade_path_loop.h.) */
     if constexpr( BATCHED )
     {
-        /* What is set up before the loops, into the frame f of the lane's own task.
-         * A SECOND COPY of the set-up in the plain step below ("plain step: task set-up", "... light set-up", "... path set-up"):
-         * shared code changed the code objects of the variants that keep that step.  An edit to either copy belongs in both; what
-         * catches a difference is the comparison of class 16 with class 4 in tests/test_gpu_shade_batches.py.
-         * The task's own values: */
-        auto task_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t )
-        {
-            const V3 surface_d = ldc( t.surface_d );
-            f.set3( true, TF_SURFACE_D, surface_d );
-            f.set3( true, TF_RAY_PRJ, ldc( t.ray_projection ) );
-            const double theta_i = t.theta_i;
-            double sin_i = 0, cos_i = 1;   /* loop invariant half of the Oren-Nayar term */
-            if( t.on_b > 0 ) acn_sincos( theta_i, &sin_i, &cos_i );
-            f.set( true, TF_SIN_I, sin_i ); f.set( true, TF_COS_I, cos_i );
-            f.set( true, TF_TAN_I, cos_i > 0 ? sin_i / cos_i : 0.0 );   /* direct-light loop only, and only where cos_i > weight > 0 */
-            f.set( true, TF_THETA_I, theta_i );
-            f.set( true, TF_ON_A, t.on_a ); f.set( true, TF_ON_B, t.on_b );
-            f.set( true, TF_DIFF_I, t.diffuse_intensity );
-        };
-        /* a light's, scene.c:542-555: the sampling frame, the root elements the cone cull leaves, colour and normalisation */
+        /* What is set up before the loops (ACN_SHADE_TASK_SETUP and what follows it, above), into the frame f of the lane's own task.
+         * The task's and a light's set-up stay lambdas here: with the text where they are called, instructions of this form moved */
+        auto task_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t ) { ACN_SHADE_TASK_SETUP( f, true ) };
         auto light_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t, const V3 pos, const uint64_t direct_samples, const int light_idx,
-                                  uint64_t* skip, V3* light_color, double* norm )
+                                  uint64_t& skip, V3& light_color, double& norm )
         {
             NodeP light_src = &sc.nodes[ light_idx ];
             MatP light_mat = &sc.mats[ light_idx ];
-            V3 fov_d; double cos_rs;
-            obj_fov_dev( light_src, pos, &fov_d, &cos_rs );
-            const M3 src_frame = m_con_z( fov_d );
-            const double cyl_hgt = 1 - cos_rs;
-            /* root elements no shadow ray of this loop can reach (all of them lie in the light's sampling cone; src_frame.z is
-             * the axis the cap samples are drawn around) */
-            *skip = root_cone_cull( scp, sc.matter_root, pos, src_frame.z, 1.0 - cyl_hgt );
-            const V3 light_pos = ld3( light_src->pos );
-            *light_color = obj_color_dev( sc, light_idx, light_pos );   /* scene.c:552 */
-            *norm = 2.0 * cyl_hgt / direct_samples;
-            frame_set_con( f, true, m_transposed( src_frame ) );
-            f.set( true, TF_CYL_HGT, cyl_hgt );
-            f.set3( true, TF_LIGHT_POS, light_pos );
-            f.set( true, TF_RADIANCE, light_mat->radiance );
-            const V3 Tc = ldc( t.Tc );
-            f.set3( true, TF_SCALE, mk( Tc.x * ( light_color->x * *norm ), Tc.y * ( light_color->y * *norm ), Tc.z * ( light_color->z * *norm ) ) );
+            ACN_SHADE_LIGHT_SETUP( f, true )
         };
-        /* the path loop's, scene.c:584-595 */
-        auto path_setup = [ & ]( TaskFrame< FRAME_IN_LDS >& f, const DTask ACN_CONST& t, const double norm )
-        {
-            frame_set_con( f, true, m_transposed( m_con_z( f.get3( TF_SURFACE_D ) ) ) );
-            f.set3( true, TF_SCALE, v_mlf( ldc( t.Tc ), norm ) );
-        };
-        auto sample_count = []( const double per_unit, const double diffuse_intensity ) { const uint64_t n = ( uint64_t )( per_unit * diffuse_intensity ); return n == 0 ? ( uint64_t )1 : n; };
-        /* "a < max_path_length" as the any-hit limit "a <= path_limit": the largest double below it */
-        auto path_limit_of = [ & ]() { return sc.prm.max_path_length < F3_INF ? acn_bits_f64( acn_f64_bits( sc.prm.max_path_length ) - 1ull ) : F3_BIG; };
 
         volatile double ACN_LDS* const wave_frames = ( volatile double ACN_LDS* )acn_task_frames + ( threadIdx.x >> 6 ) * ( B * TF_BATCH_N );
         TaskFrame< true > mine;   /* the frame of the task this lane sets up: lanes 0 .. B - 1 */
@@ -326,10 +345,10 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                 if( setup )
                 {
                     cnt.cost( ACN_F_FOV + ACN_F_FRAME );   /* per task and light */
-                    const uint64_t direct_samples = sample_count( sc.prm.direct_samples, mine.get( TF_DIFF_I ) );
+                    const uint64_t direct_samples = shade_sample_count( sc.prm.direct_samples, mine.get( TF_DIFF_I ) );
                     if( li > 0 ) mine.setu( TF_RV, lcg00_jump( mine.getu( TF_RV ), 2 * direct_samples ) );   /* behind the loop of light li - 1 */
                     uint64_t skip; V3 light_color; double norm;
-                    light_setup( mine, t, mine.get3( TF_POS ), direct_samples, light_idx, &skip, &light_color, &norm );
+                    light_setup( mine, t, mine.get3( TF_POS ), direct_samples, light_idx, skip, light_color, norm );
                     mine.setu( TF_SKIP, skip );
                     mine.set3( true, TF_LIGHT_COLOR, light_color );
                     mine.set( true, TF_NORM, norm );
@@ -345,7 +364,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                     const V3 pos = F.get3( TF_POS );
                     const bool oren_nayar = F.get( TF_ON_B ) > 0;
                     const uint64_t skip = F.getu( TF_SKIP ), rv = F.getu( TF_RV );
-                    const uint64_t direct_samples = sample_count( sc.prm.direct_samples, F.get( TF_DIFF_I ) );
+                    const uint64_t direct_samples = shade_sample_count( sc.prm.direct_samples, F.get( TF_DIFF_I ) );
                     const auto root_at = root_set< true >( scp, sc.matter_root, skip );
 #include "acn_k_shade_direct_loop.h"
                     s = group_sum< LPT >( s );
@@ -366,14 +385,14 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
             if( sc.prm.path_samples )
             {
                 const V3 bg = ld3( sc.prm.background_color );
-                const double path_limit = path_limit_of();
+                const double path_limit = shade_path_limit( sc.prm.max_path_length );
                 if( setup && t.depth > 10 )
                 {
                     cnt.cost( ACN_F_FRAME );
                     const double diffuse_intensity = mine.get( TF_DIFF_I );
-                    if( n_lights > 0 ) mine.setu( TF_RV, lcg00_jump( mine.getu( TF_RV ), 2 * sample_count( sc.prm.direct_samples, diffuse_intensity ) ) );
-                    const double norm = 2.0 / sample_count( sc.prm.path_samples, diffuse_intensity );
-                    path_setup( mine, t, norm );
+                    if( n_lights > 0 ) mine.setu( TF_RV, lcg00_jump( mine.getu( TF_RV ), 2 * shade_sample_count( sc.prm.direct_samples, diffuse_intensity ) ) );
+                    const double norm = 2.0 / shade_sample_count( sc.prm.path_samples, diffuse_intensity );
+                    ACN_SHADE_PATH_SETUP( mine, true )
                     mine.set( true, TF_NORM, norm );
                 }
                 mine.publish();
@@ -389,7 +408,7 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
                     const bool oren_nayar = F.get( TF_ON_B ) > 0;
                     const double diffuse_intensity = F.get( TF_DIFF_I );
                     const uint64_t rv = F.getu( TF_RV );
-                    const uint64_t path_samples = sample_count( sc.prm.path_samples, diffuse_intensity );
+                    const uint64_t path_samples = shade_sample_count( sc.prm.path_samples, diffuse_intensity );
 #include "acn_k_shade_path_loop.h"
                     bsum = group_sum< LPT >( bsum ) * F.get( TF_NORM );
                     if( writer )
@@ -422,27 +441,13 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
         const V3 pos = ldc( t.pos );   /* the origin of every ray of the task: stays in registers */
         const double diffuse_intensity = t.diffuse_intensity;
         const bool oren_nayar = t.on_b > 0;
-        /* plain step: task set-up.  The batched form above has a copy of it and of the two below (task_setup, light_setup,
-         * path_setup, sample_count, path_limit_of): an edit here belongs there as well */
-        {
-            const V3 surface_d = ldc( t.surface_d );
-            fr_.set3( writer, TF_SURFACE_D, surface_d );
-            fr_.set3( writer, TF_RAY_PRJ, ldc( t.ray_projection ) );
-            const double theta_i = t.theta_i;
-            double sin_i = 0, cos_i = 1;   /* loop invariant half of the Oren-Nayar term */
-            if( oren_nayar ) acn_sincos( theta_i, &sin_i, &cos_i );
-            fr_.set( writer, TF_SIN_I, sin_i ); fr_.set( writer, TF_COS_I, cos_i );
-            fr_.set( writer, TF_TAN_I, cos_i > 0 ? sin_i / cos_i : 0.0 );   /* direct-light loop only, and only where cos_i > weight > 0 */
-            fr_.set( writer, TF_THETA_I, theta_i );
-            fr_.set( writer, TF_ON_A, t.on_a ); fr_.set( writer, TF_ON_B, t.on_b );
-            fr_.set( writer, TF_DIFF_I, diffuse_intensity );
-        }
+        ACN_SHADE_TASK_SETUP( fr_, writer )
         uint64_t rv = t.rv;
         V3 lum = mk( 0, 0, 0 );   /* lum_l of scene.c:539, identical in all lanes of the group after each reduction */
         ACN_LAP( PH_FETCH );      /* diagnostic build: k_shade books 10 task fetch / set-up, 12 light set-up (cone cull, frame, root set),
                                      4 cap sample, 5 light hit, 6 Oren-Nayar, 7 occlusion, 8 queue appends and sums, 13 path set-up,
                                      9 path sample, 11 path transition hit; batched: the set-up of the tasks of a batch, one per lane */
-        const uint64_t direct_samples = [ & ]() { uint64_t n = ( uint64_t )( sc.prm.direct_samples * diffuse_intensity ); return n == 0 ? ( uint64_t )1 : n; }();
+        const uint64_t direct_samples = shade_sample_count( sc.prm.direct_samples, diffuse_intensity );
         NodeP light = &sc.nodes[ sc.light_root ];
         const int n_lights = light->child1;
 
@@ -456,26 +461,8 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
             uint64_t skip;
             V3 light_color;
             double norm;
-            /* plain step: light set-up (copy in the batched form: light_setup) */
-            {
-                V3 fov_d; double cos_rs;
-                obj_fov_dev( light_src, pos, &fov_d, &cos_rs );
-                const M3 src_frame = m_con_z( fov_d );
-                const double cyl_hgt = 1 - cos_rs;
-                /* root elements no shadow ray of this loop can reach (all of them lie in the light's sampling cone; src_frame.z is
-                 * the axis the cap samples are drawn around) */
-                skip = root_cone_cull( scp, sc.matter_root, pos, src_frame.z, 1.0 - cyl_hgt );
-                const V3 light_pos = ld3( light_src->pos );
-                light_color = obj_color_dev( sc, light_idx, light_pos );   /* scene.c:552 */
-                norm = 2.0 * cyl_hgt / direct_samples;
-                frame_set_con( fr_, writer, m_transposed( src_frame ) );
-                fr_.set( writer, TF_CYL_HGT, cyl_hgt );
-                fr_.set3( writer, TF_LIGHT_POS, light_pos );
-                fr_.set( writer, TF_RADIANCE, light_mat->radiance );
-                const V3 Tc = ldc( t.Tc );
-                fr_.set3( writer, TF_SCALE, mk( Tc.x * ( light_color.x * norm ), Tc.y * ( light_color.y * norm ), Tc.z * ( light_color.z * norm ) ) );
-                fr_.publish();
-            }
+            ACN_SHADE_LIGHT_SETUP( fr_, writer )
+            fr_.publish();
             const auto root_at = root_set< WAVE_LOOPS >( scp, sc.matter_root, skip );
             ACN_LAP( PH_LIGHT_SETUP );
 
@@ -491,18 +478,12 @@ void k_shade( ACN_SCENE_PARAMS, const DTask* __restrict__ tasks, const uint32_t*
         if( sc.prm.path_samples && t.depth > 10 )
         {
             if( sub == 0 ) cnt.cost( ACN_F_FRAME );
-            /* plain step: path set-up (copy in the batched form: path_setup, sample_count, path_limit_of) */
-            uint64_t path_samples = ( uint64_t )( sc.prm.path_samples * diffuse_intensity );
-            path_samples = ( path_samples == 0 ) ? 1 : path_samples;
+            const uint64_t path_samples = shade_sample_count( sc.prm.path_samples, diffuse_intensity );
             const double norm = 2.0 / path_samples;
             const V3 bg = ld3( sc.prm.background_color );
-            /* "a < max_path_length" as the any-hit limit "a <= path_limit": the largest double below it */
-            const double path_limit = sc.prm.max_path_length < F3_INF ? acn_bits_f64( acn_f64_bits( sc.prm.max_path_length ) - 1ull ) : F3_BIG;
-            {
-                frame_set_con( fr_, writer, m_transposed( m_con_z( F.get3( TF_SURFACE_D ) ) ) );
-                fr_.set3( writer, TF_SCALE, v_mlf( ldc( t.Tc ), norm ) );
-                fr_.publish();
-            }
+            const double path_limit = shade_path_limit( sc.prm.max_path_length );
+            ACN_SHADE_PATH_SETUP( fr_, writer )
+            fr_.publish();
             ACN_LAP( PH_PATH_SETUP );
 #include "acn_k_shade_path_loop.h"
             bsum = group_sum< LPT >( bsum ) * norm;

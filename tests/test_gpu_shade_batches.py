@@ -5,7 +5,8 @@ to light and into the path loop (rv, lum) now that they live in the frame, neigh
 set-up.  On hand-made queues through the stage seam, as tests/test_gpu_shade_loops.py does, and against its three references:
 
   class 4      the three output queues, as sorted byte strings, are those of the same tasks on 4 lanes per task: that kernel keeps the
-               plain step of four tasks, set up by every lane of a group
+               plain step of four tasks, set up by every lane of a group.  Both forms expand one definition of the set-up, so
+               what this comparison guards is the batching itself: the frames, the sub-steps, what a task carries in LDS
   the tap      every record is a sample of the oracle's scene_lum at that point (check_records)
   the sums     accum equals exact_accum for 16 lanes per task, bit for bit
 
