@@ -27,7 +27,7 @@ HIP_SYMBOLS = ["acn_device_count", "acn_scene_upload", "acn_scene_free", "acn_sc
                "acn_render_positions_dev", "acn_render_main_pass_dev", "acn_resolve_dev", "acn_last_kernel_ms", "acn_last_stage_ms", "acn_last_counters",
                "acn_estimate_envelope", "acn_detmath_eval", "acn_last_error", "acn_shard_tile_count", "acn_shard_tile_padded",
                "acn_shard_tile_index", "acn_render_main_pass_shard_dev", "acn_shard_unpack_dev", "acn_query_rays",
-               "acn_stage_info", "acn_stage_plan", "acn_run_stage", "acn_stage_walk_plan", "acn_run_stage_walk",
+               "acn_stage_info", "acn_stage_plan", "acn_run_stage", "acn_stage_walk_plan", "acn_run_stage_walk", "acn_stage_last_counters",
                "acn_render_rays", "acn_render_rays_dev", "acn_camera_rays", "acn_camera_rays_dev",
                "acn_surface_rays", "acn_surface_rays_dev", "acn_surface_positions", "acn_surface_positions_dev",
                "acn_denoise", "acn_denoise_dev",
@@ -166,6 +166,7 @@ hip.acn_stage_plan.argtypes = [vp, P(abi.StageArgs), P(abi.StageCaps)]
 hip.acn_run_stage.argtypes = [vp, P(abi.StageArgs), P(abi.StageOut)]
 hip.acn_stage_walk_plan.argtypes = [vp, P(abi.StageWalkArgs), P(abi.StageCaps)]
 hip.acn_run_stage_walk.argtypes = [vp, P(abi.StageWalkArgs), P(abi.StageOut)]
+hip.acn_stage_last_counters.argtypes = [vp, P(C.c_uint64), C.c_int]
 hip.acn_last_error.restype = C.c_char_p
 hip.acn_shard_tile_count.argtypes = [C.c_size_t, C.c_uint32, C.c_uint32]
 hip.acn_shard_tile_count.restype = C.c_size_t

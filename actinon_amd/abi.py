@@ -153,6 +153,7 @@ class ShadowHistoryParams(C.Structure):
 # the stage-runner test seam (acn_run_stage): stages, option bits, limits
 ACN_STAGE_SHADE_HITS, ACN_STAGE_SHADE, ACN_STAGE_HARD_SHADOW, ACN_STAGE_HARD_PATH = 0, 1, 2, 3
 ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_LEAF_LIGHTS, ACN_STAGE_NO_EMIT_TERMS = 1, 2, 4
+ACN_STAGE_COUNT_WORK = 16       # both seams: the counting kernel variants; acn_stage_last_counters returns their work counters
 ACN_STAGE_MAX_RECORDS, ACN_STAGE_MAX_SAMPLES, ACN_STAGE_MAX_DEPTH = 1 << 20, 1 << 16, 1 << 20
 ACN_STAGE_INFO_WORDS = 10
 # the walk of a level alone (acn_run_stage_walk)

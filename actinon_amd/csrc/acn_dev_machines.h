@@ -272,7 +272,9 @@ DEV double obj_ray_hit_dev( SR sc, int root, V3 rp, V3 rd, bool want_nor, V3* ou
                 }
                 else if( pc == 2 )
                 {
-                    cnt->cost( 2 * ACN_F_PAIR_STEP );
+                    /* a step per candidate looked at, as objects.c:1057-1092 takes them: the first always, the second only when the
+                     * first is not taken and a2 is finite (booked inside that test's condition below) */
+                    cnt->cost( ACN_F_PAIR_STEP );
                     double a1 = cur_a, a2 = ret_a;
                     if( a1 < a2 && obj_side_dev( sc, fn->child1, ray_pos( cur_rp, rd, a1 ), cnt ) == want )
                     {
@@ -282,7 +284,7 @@ DEV double obj_ray_hit_dev( SR sc, int root, V3 rp, V3 rd, bool want_nor, V3* ou
                     {
                         ret_a = F3_INF;
                     }
-                    else if( obj_side_dev( sc, fn->child0, ray_pos( cur_rp, rd, a2 ), cnt ) == want )
+                    else if( ( cnt->cost( ACN_F_PAIR_STEP ), obj_side_dev( sc, fn->child0, ray_pos( cur_rp, rd, a2 ), cnt ) ) == want )
                     {
                         /* ret_a = a2, ret_n = n2 already */
                     }

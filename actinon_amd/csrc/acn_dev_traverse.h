@@ -216,7 +216,14 @@ DEV double element_hit( const SC& sc, int e, V3 rp, V3 rd, V3* nor, int* hit_obj
     }
     *hit_obj = e;
     bool env = node_has_env( n );
-    if( pre && env && !env_ray_hits( n, rp, rd, cnt ) ) { cnt->inc( CNT_OBJ_HIT ); return F3_INF; }
+    /* the envelope pre-test.  An element that goes on to a machine has the test redone, and booked, there: here only its miss is an
+     * event of the reference (objects.c:264), so the test itself runs without the counters */
+    if( pre && env && !( type > ACN_SQUAROID ? env_ray_hits( n, rp, rd, ACN_NO_CNT ) : env_ray_hits( n, rp, rd, cnt ) ) )
+    {
+        if( type > ACN_SQUAROID ) cnt->cost( ACN_F_ENV_MISS );
+        cnt->inc( CNT_OBJ_HIT );
+        return F3_INF;
+    }
     if( type > ACN_SQUAROID )
     {
 #ifdef ACN_PRUNE_CHECK

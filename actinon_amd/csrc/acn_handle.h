@@ -360,6 +360,7 @@ struct acn_scene_handle
     DevBuf< double > d_lens_rad;                    /* ... their radiance [ 3 ], grown by the calls that render, */
     DevBuf< double > d_lens_surf;                   /* ... and their surface records [ 16 ], grown by the calls that take records */
     DevBuf< unsigned long long > d_select_tiles;    /* acn_select_above*: the counts per tile and their total */
+    unsigned long long stage_counters[ CNT_N + 2 ] = {};   /* acn_stage_last_counters: the last stage call's (zero without ACN_STAGE_COUNT_WORK) */
     std::vector< std::unique_ptr< acn_frame > > frames;   /* acn_frame_create: what acn_frame_free has not released goes with the handle */
 };
 

@@ -155,7 +155,17 @@ void k_hard_shadow( ACN_SCENE_PARAMS, HardShadow* __restrict__ recs, uint32_t ca
             ACN_LAP( PH_ROOT_LEAF );
             /* what the ray carries is read only now, so that it does not occupy registers across the machine */
             asm volatile( "" ::: "memory" );
-            if( !occ ) { cnt.cost( ACN_F_DIRECT_TAIL ); pixel_add( accum, sc.flags, recs[ index ].pixel, recs[ index ].contrib ); }
+            if constexpr( COUNT )
+            {
+                /* the tail of scene.c:571-574 belongs to a direct-light sample of k_shade: a resume word, bit 0 clear, the light's
+                 * distance as its limit.  A probe stands for a background term, for which the reference books nothing: the specular
+                 * ones carry bit 0 or no resume word, k_shade's dark path rays the path limit.  The record has no field that says
+                 * which it is, so this is a rule of thumb: a direct sample whose light lies at exactly shade_path_limit (one double)
+                 * would be taken for a probe and lose its 23 flop */
+                const double path_limit = shade_path_limit( sc.prm.max_path_length );
+                if( !occ && ( pad & ( 1u | ACN_RESUME_FLAG ) ) == ACN_RESUME_FLAG && limit != path_limit ) cnt.cost( ACN_F_DIRECT_TAIL );
+            }
+            if( !occ ) pixel_add( accum, sc.flags, recs[ index ].pixel, recs[ index ].contrib );
             ACN_LAP( PH_SHADE );
         }
     }

@@ -235,11 +235,7 @@ DEV uint64_t shade_sample_count( double per_unit, double diffuse_intensity )
     const uint64_t n = ( uint64_t )( per_unit * diffuse_intensity );
     return n == 0 ? ( uint64_t )1 : n;
 }
-/* "a < max_path_length" as the any-hit limit "a <= path_limit": the largest double below it */
-DEV double shade_path_limit( double max_path_length )
-{
-    return max_path_length < F3_INF ? acn_bits_f64( acn_f64_bits( max_path_length ) - 1ull ) : F3_BIG;
-}
+/* (shade_path_limit, the any-hit limit of a dark path ray: acn_queues.h, beside F3_BIG: k_hard_shadow reads it too) */
 
 /* LEAF_LIGHTS: every light is a plane / sphere / squaroid-free leaf, so the kernel contains no call into the CSG
  * machine at all (the usual case); otherwise the light hit goes through the generic element test.

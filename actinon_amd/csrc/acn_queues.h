@@ -287,6 +287,11 @@ struct WalkSink
  * background term added if nothing is hit (k_hard_shadow).  Same value, same fixed-point sum.
  * limit: hits at or beyond it do not count; F3_BIG = the largest finite double stands for "any finite hit". */
 #define F3_BIG 1.7976931348623157e308
+/* (k_shade writes it into its dark path rays' probes, k_hard_shadow< COUNT > tells them by it)  "a < max_path_length" as the any-hit limit "a <= path_limit": the largest double below it */
+DEV double shade_path_limit( double max_path_length )
+{
+    return max_path_length < F3_INF ? acn_bits_f64( acn_f64_bits( max_path_length ) - 1ull ) : F3_BIG;
+}
 /* the record of a probe into its slot of the level's hard-shadow queue, or the overflow flag */
 DEV void probe_store( const TaskQ& tq, uint32_t slot, V3 p, V3 d, double limit, V3 contrib, uint32_t pixel, uint32_t flags )
 {

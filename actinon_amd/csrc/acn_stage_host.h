@@ -78,7 +78,7 @@ static inline int acn_stage_check( bool have_handle, const acn_stage_args* a, co
     if( !have_handle ) { *msg = "null argument: handle"; return ACN_ERR_ARG; }
     if( !a || !caps ) { *msg = "null argument: acn_stage_args / acn_stage_caps"; return ACN_ERR_ARG; }
     if( a->stage >= ACN_STAGE_N ) { *msg = "unknown stage " + std::to_string( a->stage ); return ACN_ERR_ARG; }
-    if( a->flags & ~( ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_LEAF_LIGHTS | ACN_STAGE_NO_EMIT_TERMS ) ) { *msg = "unknown acn_stage_args.flags bits"; return ACN_ERR_ARG; }
+    if( a->flags & ~( ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_LEAF_LIGHTS | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_COUNT_WORK ) ) { *msg = "unknown acn_stage_args.flags bits"; return ACN_ERR_ARG; }
     if( !a->in ) { *msg = "null argument: in"; return ACN_ERR_ARG; }
     if( a->n == 0 || a->n > ACN_STAGE_MAX_RECORDS ) { *msg = "n " + std::to_string( a->n ) + " is outside 1 .. 2^20 records"; return ACN_ERR_ARG; }
     const bool shade = a->stage == ACN_STAGE_SHADE;
@@ -173,7 +173,7 @@ static inline int acn_stage_walk_check( bool have_handle, const acn_stage_walk_a
     if( !have_handle ) { *msg = "null argument: handle"; return ACN_ERR_ARG; }
     if( !a || !caps ) { *msg = "null argument: acn_stage_walk_args / acn_stage_caps"; return ACN_ERR_ARG; }
     if( a->stage != ACN_STAGE_WALK ) { *msg = "stage " + std::to_string( a->stage ) + " is not ACN_STAGE_WALK"; return ACN_ERR_ARG; }
-    if( a->flags & ~( ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES ) ) { *msg = "unknown acn_stage_walk_args.flags bits"; return ACN_ERR_ARG; }
+    if( a->flags & ~( ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES | ACN_STAGE_COUNT_WORK ) ) { *msg = "unknown acn_stage_walk_args.flags bits"; return ACN_ERR_ARG; }
     if( a->camera ? a->in != nullptr : a->pos_xy != nullptr ) { *msg = "both input forms: rays and the camera form"; return ACN_ERR_ARG; }
     if( !a->camera && !a->in ) { *msg = "neither input form: null argument in without the camera form"; return ACN_ERR_ARG; }
     if( a->n == 0 || a->n > ACN_STAGE_MAX_RECORDS ) { *msg = "n " + std::to_string( a->n ) + " is outside 1 .. 2^20 records"; return ACN_ERR_ARG; }

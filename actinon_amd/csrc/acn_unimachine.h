@@ -346,7 +346,7 @@ DEV double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, CT* c
                     const bool p2 = phase == 2u;
                     const bool walking = !p2 && fin && UF_MODE( cur_w ) == 1u;
                     const double a = ret_a;                             /* phase 2: a2 | walk: the step */
-                    if( p2 ? fin : walking ) cnt->cost( p2 ? 2 * ACN_F_PAIR_STEP : ACN_F_PAIR_STEP );
+                    if( p2 ? fin : walking ) cnt->cost( ACN_F_PAIR_STEP );   /* phase 2: the first candidate; the second is booked where it is looked at (m1 below) */
                     const bool wq = walking && a < F3_INF;
                     V3 pos0, pos1;
                     bool m0, m1;
@@ -363,7 +363,7 @@ DEV double obj_ray_hit_uni( SR sc, int root, V3 rp_in, V3 rd, V3* out_nor, CT* c
                     int s0 = 0, s1 = 0;
                     for( int k = 0; k < 2; k++ )
                     {
-                        if( k == 1 && p2 ) m1 = fin && !( m0 && s0 == want ) && a < F3_INF;
+                        if( k == 1 && p2 ) { m1 = fin && !( m0 && s0 == want ) && a < F3_INF; if( m1 ) cnt->cost( ACN_F_PAIR_STEP ); }
                         const bool m = k ? m1 : m0;
                         if( wave_any( m ) )
                         {

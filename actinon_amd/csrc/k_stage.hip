@@ -96,7 +96,7 @@ struct StageLevel
         q.grid = cap.grid; q.shade_grid = cap.grid; q.walk_grid = cap.grid;
         q.fetch_walk = h->tun.fetch_walk; q.fetch_hard = h->tun.fetch_hard; q.fetch_shade = h->tun.fetch_shade; q.private_limit = h->tun.private_limit;
         q.shard_rank = 0u; q.shard_world = 1u; q.emit_terms = flags & ACN_STAGE_NO_EMIT_TERMS ? 0u : 1u;
-        f.count = false; f.lds_nodes = h->scene.lds_bytes != 0 && !( flags & ACN_STAGE_GLOBAL_NODES );
+        f.count = ( flags & ACN_STAGE_COUNT_WORK ) != 0; f.lds_nodes = h->scene.lds_bytes != 0 && !( flags & ACN_STAGE_GLOBAL_NODES );
         f.leaf_lights = h->scene.leaf_lights && !( flags & ACN_STAGE_NO_LEAF_LIGHTS );
         f.prune = h->scene.prune && !( flags & ACN_STAGE_NO_PRUNE );
         DevScene dev = h->dev;
@@ -104,14 +104,16 @@ struct StageLevel
         s = scene_args( dev, h->scene );
         return ACN_OK;
     }
-    /* seam: the call's name; cause: what an overflow of this seam's queues means */
-    int finish( hipStream_t stream, uint32_t* out_counts, const char* seam, const char* cause )
+    /* seam: the call's name; cause: what an overflow of this seam's queues means.  work: where the launch's work counters go (the
+     * handle's, for acn_stage_last_counters: never what acn_last_counters reads) */
+    int finish( hipStream_t stream, uint32_t* out_counts, unsigned long long* work, const char* seam, const char* cause )
     {
         HIP_TRY( hipGetLastError() );
         HIP_TRY( hipStreamSynchronize( stream ) );
         uint32_t counts[ QC_N ];
         int st = DevCopies::fetch( counts, d_counts, sizeof( counts ) );
         if( st != ACN_OK ) return st;
+        if( ( st = DevCopies::fetch( work, d_counters, sizeof( unsigned long long ) * ( CNT_N + 2 ) ) ) != ACN_OK ) return st;
         if( out_counts ) memcpy( out_counts, counts, sizeof( counts ) );
         if( counts[ QC_FLAGS ] & ( ACN_FLAGS_CHUNK_LOST | ACN_FLAG_STACK_OVERFLOW ) )
             return fail( ACN_ERR_DEVICE, std::string( seam ) + ": the kernel raised overflow flags " + std::to_string( counts[ QC_FLAGS ] ) + ": " + cause );
@@ -128,6 +130,7 @@ struct StageLevel
 extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, const acn_stage_out* out )
 {
     acn_stage_caps cap;
+    if( h ) memset( h->stage_counters, 0, sizeof( h->stage_counters ) );   /* "of the last stage call": one that is refused or fails reports none */
     int st = acn_stage_plan( h, a, &cap );
     if( st != ACN_OK ) return st;
     if( !out ) return fail( ACN_ERR_ARG, "acn_run_stage: null argument: out" );
@@ -156,14 +159,21 @@ extern "C" int acn_run_stage( acn_scene_handle* h, const acn_stage_args* a, cons
     if( shade )      launch_shade( lv.f, q, c.stream, lv.s, d_accum, lv.d_counters );
     else if( hs_in ) acn_launch_hard_shadow( lv.f, q, machine_lds_bytes( h->scene ), c.stream, lv.s, d_accum, lv.d_counters );
     else if( hp_in ) acn_launch_hard_path( lv.f, q, machine_lds_bytes( h->scene ), c.stream, lv.s, d_accum, lv.d_counters );
-    else             acn_launch_shade_hits( false, q, c.stream, lv.s, d_accum, lv.d_counters );
-    if( ( st = lv.finish( c.stream, out->counts, "acn_run_stage", "a queue the plan sized was too small" ) ) != ACN_OK ) return st;
+    else             acn_launch_shade_hits( lv.f.count, q, c.stream, lv.s, d_accum, lv.d_counters );
+    if( ( st = lv.finish( c.stream, out->counts, h->stage_counters, "acn_run_stage", "a queue the plan sized was too small" ) ) != ACN_OK ) return st;
     return StageLevel::fetch( {
         { split ? out->tasks : nullptr, lv.tasks },
         { split ? ( void* )out->idx[ 0 ] : nullptr, lv.idx[ 0 ] }, { split ? ( void* )out->idx[ 1 ] : nullptr, lv.idx[ 1 ] },
         { split ? ( void* )out->idx[ 2 ] : nullptr, lv.idx[ 2 ] }, { split ? ( void* )out->idx[ 3 ] : nullptr, lv.idx[ 3 ] },
         { split ? out->rays : nullptr, lv.rays[ 0 ] }, { shade || hp_in ? out->children : nullptr, lv.children },
         { shade || split || hs_in ? out->hard_shadow : nullptr, lv.hard_shadow }, { shade ? out->hard_path : nullptr, lv.hard_path }, { out->accum, lv.accum } } );
+}
+
+extern "C" int acn_stage_last_counters( acn_scene_handle* h, uint64_t* out, int n )
+{
+    if( !h || !out || n < 0 || n > CNT_N + 2 ) return fail( ACN_ERR_ARG, "acn_stage_last_counters: bad argument" );
+    for( int k = 0; k < n; k++ ) out[ k ] = h->stage_counters[ k ];
+    return ACN_OK;
 }
 
 /* ---- the walk ---- */
@@ -178,6 +188,7 @@ extern "C" int acn_stage_walk_plan( acn_scene_handle* h, const acn_stage_walk_ar
 extern "C" int acn_run_stage_walk( acn_scene_handle* h, const acn_stage_walk_args* a, const acn_stage_out* out )
 {
     acn_stage_caps cap;
+    if( h ) memset( h->stage_counters, 0, sizeof( h->stage_counters ) );
     int st = acn_stage_walk_plan( h, a, &cap );
     if( st != ACN_OK ) return st;
     if( !out ) return fail( ACN_ERR_ARG, "acn_run_stage_walk: null argument: out" );
@@ -210,7 +221,7 @@ extern "C" int acn_run_stage_walk( acn_scene_handle* h, const acn_stage_walk_arg
         acn_launch_walk( lv.f, q, w, c.stream, lv.s );
         HIP_TRY( hipGetLastError() );
     }
-    if( ( st = lv.finish( c.stream, out->counts, "acn_run_stage_walk", "room_rays is below what the walk traced" ) ) != ACN_OK ) return st;
+    if( ( st = lv.finish( c.stream, out->counts, h->stage_counters, "acn_run_stage_walk", "room_rays is below what the walk traced" ) ) != ACN_OK ) return st;
     return StageLevel::fetch( {
         { out->tasks, lv.tasks },
         { ( void* )out->idx[ 0 ], lv.idx[ 0 ] }, { ( void* )out->idx[ 1 ], lv.idx[ 1 ] }, { ( void* )out->idx[ 2 ], lv.idx[ 2 ] }, { ( void* )out->idx[ 3 ], lv.idx[ 3 ] },

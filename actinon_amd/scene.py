@@ -402,12 +402,19 @@ class Handle:
         check(hip.acn_last_stage_ms(self.h, buf, len(self.STAGES)), "acn_last_stage_ms")
         return dict(zip(self.STAGES, [float(v) for v in buf]))
 
+    COUNTERS = ["trans_rays", "shadow_rays", "obj_hits", "lum_calls", "cap_samples", "side_calls", "sdf_evals",
+                "overflows", "flop", "transcendentals"]
+
     def last_counters(self):
-        names = ["trans_rays", "shadow_rays", "obj_hits", "lum_calls", "cap_samples", "side_calls", "sdf_evals",
-                 "overflows", "flop", "transcendentals"]
         buf = (C.c_uint64 * 10)()
         check(hip.acn_last_counters(self.h, buf, 10), "acn_last_counters")
-        return dict(zip(names, [int(v) for v in buf]))
+        return dict(zip(self.COUNTERS, [int(v) for v in buf]))
+
+    def stage_last_counters(self):
+        """The work counters of the last stage call (run_stage / run_stage_walk with count_work), named as last_counters names them."""
+        buf = (C.c_uint64 * 10)()
+        check(hip.acn_stage_last_counters(self.h, buf, 10), "acn_stage_last_counters")
+        return dict(zip(self.COUNTERS, [int(v) for v in buf]))
 
     PHASES = ["other", "light", "root_leaf", "prune", "m_leaf", "m_pair", "m_frame", "m_side", "shade", "compound", "fetch",
               "tail", "light_setup", "path_setup"]   # the last two: k_shade alone (machine tallies in the other kernels' slots)
@@ -1156,7 +1163,8 @@ class Handle:
                 "nodes": int(w[7]), "lights": int(w[8]), "prune": bool(w[9] & 1), "leaf_lights": bool(w[9] & 2), "lds_nodes": bool(w[9] & 4)}
         return info
 
-    def run_stage(self, stage, records, index=None, cls=0, shard_rank=0, shard_world=1, prune=True, leaf_lights=True, emit_terms=True, grid=0):
+    def run_stage(self, stage, records, index=None, cls=0, shard_rank=0, shard_world=1, prune=True, leaf_lights=True, emit_terms=True, grid=0,
+                  count_work=False):
         """Runs one production shading kernel on `records` and returns everything it wrote as a dict of numpy arrays.
         stage "shade_hits": records are "hit" records (pixel = own index, or STAGE_INVALID); returns tasks, idx (four lists), rays,
         hard_shadow (the probes), counts, flags, accum.  stage "shade": records are "task" records, index the uint32 list the kernel of
@@ -1164,7 +1172,8 @@ class Handle:
         records are the queue of k_hard_shadow / k_hard_path as the kernel meets it, dead slots (pixel STAGE_INVALID) included, on
         `grid` workgroups (0: one per 256 records); returns counts, flags, accum, the queue slot for slot as "hard_shadow" left it, and
         children for "hard_path".  Queues come back up to their
-        high-water mark with the dead slots (pixel STAGE_INVALID) taken out; accum is [n, 3] int64 in units of 2^-40."""
+        high-water mark with the dead slots (pixel STAGE_INVALID) taken out; accum is [n, 3] int64 in units of 2^-40.
+        count_work: the counting variant of the kernel runs, and "counters" holds its work counters under the names of last_counters."""
         info = self.stage_info()
         for k, dt in self.STAGE_RECORDS.items():
             assert dt.itemsize == info["sizeof"][k], (k, dt.itemsize, info["sizeof"][k])
@@ -1175,7 +1184,7 @@ class Handle:
         a = abi.StageArgs()
         a.stage = code
         a.flags = ((0 if prune else abi.ACN_STAGE_NO_PRUNE) | (0 if leaf_lights else abi.ACN_STAGE_NO_LEAF_LIGHTS)
-                   | (0 if emit_terms else abi.ACN_STAGE_NO_EMIT_TERMS))
+                   | (0 if emit_terms else abi.ACN_STAGE_NO_EMIT_TERMS) | (abi.ACN_STAGE_COUNT_WORK if count_work else 0))
         a.cls, a.shard_rank, a.shard_world, a.n = int(grid if hard else cls), int(shard_rank), int(shard_world), rec.shape[0]
         a.input = rec.ctypes.data
         ix = None
@@ -1206,6 +1215,8 @@ class Handle:
         c = bufs["counts"]
         live = lambda q, mark: q[:mark][q["pixel"][:mark] != self.STAGE_INVALID]   # noqa: E731
         res = {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps}
+        if count_work:
+            res["counters"] = self.stage_last_counters()
         if not hard:
             res["hard_shadow"] = live(bufs["hard_shadow"], c[self.QC["hard_shadow"]])
         elif stage == "hard_shadow":
@@ -1221,12 +1232,13 @@ class Handle:
         return res
 
     def run_stage_walk(self, rays=None, pos_xy=None, n=None, first_pixel=0, room_rays=None, passes=1, private_limit=0xFFFFFFFF, stack_cap=512,
-                       stack_use=0, fetch=64, grid=0, prune=True, lds=True, emit_terms=True, flags=None):
+                       stack_use=0, fetch=64, grid=0, prune=True, lds=True, emit_terms=True, flags=None, count_work=False):
         """The specular walk of one path level alone (acn_run_stage_walk): `passes` launches of k_walk as the pipeline runner enqueues
         them.  rays: "ray" records (pixel = own index, or STAGE_INVALID), generation 0 of the level; or the camera form: pos_xy [n, 2],
         or n pixel centres of the raster from first_pixel.  room_rays: the rays the walk traces in all, by the caller's model.  Returns
         tasks, idx (four lists), hard_shadow (the probes), counts, flags, accum [n, 3] int64, and rays: what the last pass left for a
-        generation no launch reads (dead slots taken out), and gen: the generation marks QC_GEN + 0 .. passes."""
+        generation no launch reads (dead slots taken out), and gen: the generation marks QC_GEN + 0 .. passes.  count_work: the
+        counting variant of k_walk runs, and "counters" holds the work counters of all passes under the names of last_counters."""
         info = self.stage_info()
         R = self.STAGE_RECORDS
         for k, dt in R.items():
@@ -1235,6 +1247,7 @@ class Handle:
         a.stage = abi.ACN_STAGE_WALK
         a.flags = ((0 if prune else abi.ACN_STAGE_NO_PRUNE) | (0 if lds else abi.ACN_STAGE_GLOBAL_NODES)
                    | (0 if emit_terms else abi.ACN_STAGE_NO_EMIT_TERMS)) if flags is None else int(flags)
+        a.flags |= abi.ACN_STAGE_COUNT_WORK if count_work else 0
         rec = pos = None
         if rays is not None:
             rec = np.ascontiguousarray(rays, dtype=R["ray"])
@@ -1263,10 +1276,13 @@ class Handle:
         c = bufs["counts"]
         live = lambda q, mark: q[:mark][q["pixel"][:mark] != self.STAGE_INVALID]   # noqa: E731
         gen = c[self.QC["gen0"]:self.QC["gen0"] + a.passes + 1].copy()
-        return {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps, "gen": gen,
-                "hard_shadow": live(bufs["hard_shadow"], c[self.QC["hard_shadow"]]), "tasks": bufs["tasks"][:c[self.QC["tasks"]]],
-                "rays": live(bufs["rays"], gen[a.passes]),
-                "idx": [l[:c[self.QC["class0"] + k]][l[:c[self.QC["class0"] + k]] != self.STAGE_INVALID] for k, l in enumerate(idx)]}
+        res = {"counts": c, "flags": int(c[self.QC["flags"]]), "accum": bufs["accum"], "caps": caps, "gen": gen,
+               "hard_shadow": live(bufs["hard_shadow"], c[self.QC["hard_shadow"]]), "tasks": bufs["tasks"][:c[self.QC["tasks"]]],
+               "rays": live(bufs["rays"], gen[a.passes]),
+               "idx": [l[:c[self.QC["class0"] + k]][l[:c[self.QC["class0"] + k]] != self.STAGE_INVALID] for k, l in enumerate(idx)]}
+        if count_work:
+            res["counters"] = self.stage_last_counters()
+        return res
 
 
 class Surface:

@@ -1328,12 +1328,21 @@ enum acn_stage { ACN_STAGE_SHADE_HITS = 0, ACN_STAGE_SHADE = 1, ACN_STAGE_HARD_S
 #define ACN_STAGE_NO_PRUNE       1u
 #define ACN_STAGE_NO_LEAF_LIGHTS 2u
 #define ACN_STAGE_NO_EMIT_TERMS  4u
+/* ( 8u: ACN_STAGE_GLOBAL_NODES, the walk's ) */
+/* ACN_STAGE_COUNT_WORK (acn_run_stage and acn_run_stage_walk): the launch runs the counting variant of its kernel, the one a handle
+ * uploaded with ACN_OPT_COUNT_WORK runs in a render call; what it writes is what the plain variant writes.  acn_stage_last_counters
+ * then returns the launch's first 10 work counters in the order of acn_last_counters (trans rays, shadow rays, object hits, lum calls,
+ * cap samples, side calls, SDF evaluations, overflows, flop, transcendentals): of the last stage call of the handle, all zero if that
+ * call ran without the flag.  n <= 10.  Isolation: a stage call, counting or not, moves nothing a render call reports --
+ * acn_last_counters, acn_last_stage_ms and acn_last_kernel_ms stay what the last render call left. */
+#define ACN_STAGE_COUNT_WORK    16u
+int acn_stage_last_counters( acn_scene_handle* h, uint64_t* out, int n );
 #define ACN_STAGE_MAX_RECORDS ( 1u << 20 )
 #define ACN_STAGE_MAX_SAMPLES ( 1u << 16 )
 #define ACN_STAGE_MAX_DEPTH   ( 1 << 20 )
 typedef struct acn_stage_args
 {
-    uint32_t stage, flags;              /* ACN_STAGE_*, ACN_STAGE_NO_* */
+    uint32_t stage, flags;              /* ACN_STAGE_*, ACN_STAGE_NO_* | ACN_STAGE_COUNT_WORK */
     uint32_t cls;                       /* SHADE: size class; HARD_*: workgroups, 0 = by n */
     uint32_t shard_rank, shard_world;   /* SHADE; shard_world 0 reads as 1 */
     uint32_t n, n_index;                /* input records; SHADE: entries of index */
@@ -1377,7 +1386,7 @@ int acn_run_stage( acn_scene_handle* h, const acn_stage_args* args, const acn_st
  * and cap_hard_path are 0, chunk is the reservation).  A raised overflow flag is ACN_ERR_DEVICE.
  * ACN_ERR_ARG before anything is launched, acn_last_error set: a null handle, args or caps; stage not ACN_STAGE_WALK; a flag other
  * than ACN_STAGE_NO_PRUNE, ACN_STAGE_NO_EMIT_TERMS, ACN_STAGE_GLOBAL_NODES (the node array read from global memory on a handle that
- * stages it in LDS, as ACN_QUERY_GLOBAL_NODES); both input forms or neither; n outside 1 .. ACN_STAGE_MAX_RECORDS; passes outside
+ * stages it in LDS, as ACN_QUERY_GLOBAL_NODES), ACN_STAGE_COUNT_WORK; both input forms or neither; n outside 1 .. ACN_STAGE_MAX_RECORDS; passes outside
  * 1 .. ACN_MAX_WALK_PASSES (32); stack_cap outside 1 .. ACN_STAGE_WALK_MAX_STACK; stack_use above stack_cap (0: stack_cap); fetch
  * outside 64 .. ACN_STAGE_MAX_RECORDS; grid above 64 (0: one workgroup per 256 input slots); room_rays below n or so large that a
  * queue would exceed 2^26 records; a live ray whose pixel is not < n, whose origin, direction or T is not finite, whose direction
@@ -1388,7 +1397,7 @@ int acn_run_stage( acn_scene_handle* h, const acn_stage_args* args, const acn_st
 #define ACN_STAGE_WALK_MAX_STACK 4096u
 typedef struct acn_stage_walk_args
 {
-    uint32_t stage, flags;              /* ACN_STAGE_WALK; ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES */
+    uint32_t stage, flags;              /* ACN_STAGE_WALK; ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES | ACN_STAGE_COUNT_WORK */
     uint32_t n;                         /* input rays (dead slots included), or positions of the camera form */
     uint32_t camera;                    /* != 0: the camera form */
     uint32_t passes, private_limit;     /* launches of k_walk; generations of at most private_limit rays run on private stacks */

@@ -90,6 +90,8 @@ static int shard_skips_sample( const ctx_t* c, uint64_t j, uint64_t n )
  * algorithm as by the instrumented device kernels */
 #include "../actinon_amd/csrc/acn_costs.h"
 #define COST( c, f, t ) do { if( ( c )->cnt ) { ( c )->cnt[ ORC_N_FLOP ] += ( f ); ( c )->cnt[ ORC_N_TRANSC ] += ( t ); } } while( 0 )
+/* an event of scene_lum itself or of the camera ray: in F_alg / T_alg and in their shading part (ORC_N_FLOP_SHADE, acn_oracle.h) */
+#define COST_SHADE( c, f, t ) do { COST( c, f, t ); if( ( c )->cnt ) { ( c )->cnt[ ORC_N_FLOP_SHADE ] += ( f ); ( c )->cnt[ ORC_N_TRANSC_SHADE ] += ( t ); } } while( 0 )
 
 static double f3_sqr( double a ) { return a * a; }
 static double f3_max( double a, double b ) { return a > b ? a : b; }
@@ -868,7 +870,7 @@ static double scene_trans_hit( ctx_t* c, const ray_t* r, trans_t* trans )
 static double oren_nayar_weight( ctx_t* c, double weight, double theta_i, double on_a, double on_b, v3 out_d, v3 nor, v3 ray_prj )
 {
     COUNT( c, ORC_N_OREN_NAYAR );
-    COST( c, ACN_F_OREN_NAYAR, ACN_T_OREN_NAYAR );
+    COST_SHADE( c, ACN_F_OREN_NAYAR, ACN_T_OREN_NAYAR );
     double theta_r = M_ACOS( weight );
     double cos_phi = -v3_mlv( v3_of_length( v3_orthogonal_projection( out_d, nor ), 1.0 ), ray_prj );
     return weight *
@@ -900,7 +902,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     v3 lum = { 0, 0, 0 };
     if( depth == 0 || intensity < scene->trace_min_intensity ) return lum;
     COUNT( c, ORC_N_LUM );
-    COST( c, ACN_F_LUM_FIXED, 0 );
+    COST_SHADE( c, ACN_F_LUM_FIXED, 0 );
 
     v3 pos = ray_pos( ray, offs );
     const acn_node* enter_obj = trans->enter_obj >= 0 ? &nodes[ trans->enter_obj ] : NULL;
@@ -910,7 +912,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     {
         double diff_sqr = v3_diff_sqr( pos, v3_ld( enter_obj->pos ) );
         double light_intensity = ( diff_sqr > 0 ) ? ( enter_obj->radiance / diff_sqr ) : F3_MAG;
-        COST( c, ACN_F_EMISSION, 0 );
+        COST_SHADE( c, ACN_F_EMISSION, 0 );
         if( shard_skips_terms( c ) ) return lum;
         lum = v3_mlf( obj_color( c->sc, enter_obj, pos ), light_intensity * intensity );
         if( c->tap ) { double* r = tap_row( c, ACN_ORACLE_TAP_EMISSION ); TAP_V3( r + 1, lum ); r[ 4 ] = diff_sqr; r[ 5 ] = light_intensity; }
@@ -963,7 +965,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     if( fresnel_reflectivity > 0 && intensity >= scene->trace_min_intensity )
     {
         COUNT( c, ORC_N_FRESNEL );
-        COST( c, ACN_F_FRESNEL_REFL, 0 );
+        COST_SHADE( c, ACN_F_FRESNEL_REFL, 0 );
         ray_t out;
         out.p = pos;
         double reflectance = fresnel_reflection( ray->d, trans->exit_nor, trans_refractive_index, &out.d ) * fresnel_reflectivity;
@@ -989,7 +991,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     {
         ray_t out;
         out.p = pos;
-        COST( c, ACN_F_REFLECTION, 0 );
+        COST_SHADE( c, ACN_F_REFLECTION, 0 );
         out.d = v3_reflection( ray->d, trans->exit_nor );
         trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
         double a;
@@ -1015,7 +1017,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     {
         double diffuse_intensity = intensity * diffuse_reflectivity;
         ray_t surface = { pos, v3_neg( trans->exit_nor ) };
-        COST( c, ACN_F_SHADE_DIFFUSE + ACN_F_SEED, ACN_T_SHADE_DIFFUSE + ACN_T_SEED );
+        COST_SHADE( c, ACN_F_SHADE_DIFFUSE + ACN_F_SEED, ACN_T_SHADE_DIFFUSE + ACN_T_SEED );
 
         double theta_i = M_ACOS( -v3_mlv( ray->d, surface.d ) );
         v3 ray_projection = v3_of_length( v3_orthogonal_projection( ray->d, surface.d ), 1.0 );
@@ -1037,7 +1039,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
             ray_t out = surface;
             int light_idx = c->sc->elems[ light->child0 + i ];
             const acn_node* light_src = &nodes[ light_idx ];
-            COST( c, ACN_F_FOV + ACN_F_FRAME, 0 );
+            COST_SHADE( c, ACN_F_FOV + ACN_F_FRAME, 0 );
             cone_t fov_to_src = obj_fov( light_src, pos );
             m3 src_con = m3_transposed( m3_con_z( fov_to_src.ray.d ) );
             double cyl_hgt = 1 - fov_to_src.cos_rs; /* areal_coverage vectors.h:362 */
@@ -1053,7 +1055,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
             for( uint64_t j = 0; j < direct_samples; j++ )
             {
                 COUNT( c, ORC_N_CAP_SAMPLE );
-                COST( c, ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
+                COST_SHADE( c, ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
                 out.d = m3_mlv( &src_con, v3_random_sphere_cap( &rv, cyl_hgt ) );
                 if( shard_skips_sample( c, j, direct_samples ) ) continue;   /* the draws were made: the stream stays in step */
                 double weight = v3_mlv( out.d, surface.d );
@@ -1069,14 +1071,14 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
                 if( tr ) tr[ 7 ] = a;
                 if( a >= F3_INF ) continue;
 
-                if( on_b > 0 ) weight = oren_nayar_weight( c, weight, theta_i, on_a, on_b, out.d, surface.d, ray_projection );
+                if( on_b > 0 ) { COUNT( c, ORC_N_OREN_NAYAR_DIRECT ); weight = oren_nayar_weight( c, weight, theta_i, on_a, on_b, out.d, surface.d, ray_projection ); }
                 if( tr ) { tr[ 8 ] = weight; tr[ 9 ] = 1; }
 
                 COUNT( c, ORC_N_SHADOW_RAY );
                 if( compound_ray_hit( c, c->sc->matter_root, &out, NULL, NULL ) > a )
                 {
                     if( tr ) tr[ 9 ] = 0;
-                    COST( c, ACN_F_DIRECT_TAIL, 0 );
+                    COST_SHADE( c, ACN_F_DIRECT_TAIL, 0 );
                     v3 hit_pos = ray_pos( &out, a );
                     double diff_sqr = v3_diff_sqr( hit_pos, v3_ld( light_src->pos ) );
                     double local_intensity = ( diff_sqr > 0 ) ? ( light_src->radiance / diff_sqr ) : F3_MAG;
@@ -1092,7 +1094,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
         {
             v3 cl_sum = { 0, 0, 0 };
             ray_t out = surface;
-            COST( c, ACN_F_FRAME, 0 );
+            COST_SHADE( c, ACN_F_FRAME, 0 );
             m3 out_con = m3_transposed( m3_con_z( surface.d ) );
 
             uint64_t path_samples = ( uint64_t )( scene->path_samples * diffuse_intensity );
@@ -1102,7 +1104,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
             for( uint64_t i = 0; i < path_samples; i++ )
             {
                 COUNT( c, ORC_N_CAP_SAMPLE );
-                COST( c, ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
+                COST_SHADE( c, ACN_F_CAP_SAMPLE, ACN_T_CAP_SAMPLE );
                 out.d = m3_mlv( &out_con, v3_random_sphere_cap( &rv, 1.0 ) );
                 if( shard_skips_sample( c, i, path_samples ) ) continue;
                 double weight = v3_mlv( out.d, surface.d );
@@ -1113,9 +1115,9 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
                     tr[ 1 ] = ( double )i; TAP_V3( tr + 2, out.d ); tr[ 5 ] = weight; tr[ 7 ] = F3_INF; tr[ 11 ] = -1; tr[ 12 ] = -1;
                 }
                 if( weight <= 0 ) continue;
-                COST( c, ACN_F_PATH_TAIL, 0 );
+                COST_SHADE( c, ACN_F_PATH_TAIL, 0 );
 
-                if( on_b > 0 ) weight = oren_nayar_weight( c, weight, theta_i, on_a, on_b, out.d, surface.d, ray_projection );
+                if( on_b > 0 ) { COUNT( c, ORC_N_OREN_NAYAR_PATH ); weight = oren_nayar_weight( c, weight, theta_i, on_a, on_b, out.d, surface.d, ray_projection ); }
 
                 trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
                 double a = compound_ray_trans_hit( c, c->sc->matter_root, &out, &trans_l );
@@ -1154,7 +1156,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     {
         ray_t out;
         out.p = ray_pos( ray, offs + 2.0 * F3_EPS );
-        COST( c, ACN_F_FRESNEL_REFR, 0 );
+        COST_SHADE( c, ACN_F_FRESNEL_REFR, 0 );
         fresnel_refraction( ray->d, trans->exit_nor, trans_refractive_index, &out.d );
 
         trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
@@ -1175,7 +1177,7 @@ static v3 scene_lum( ctx_t* c, const ray_t* ray, double offs, trans_t* trans, ui
     /* exiting object :656-664 */
     if( exit_obj )
     {
-        if( offs > 0 ) COST( c, ACN_F_ABSORB, ACN_T_ABSORB );
+        if( offs > 0 ) COST_SHADE( c, ACN_F_ABSORB, ACN_T_ABSORB );
         double rf = offs > 0 ? M_POW( exit_obj->transparency[ 0 ], offs ) : 1.0;
         double gf = offs > 0 ? M_POW( exit_obj->transparency[ 1 ], offs ) : 1.0;
         double bf = offs > 0 ? M_POW( exit_obj->transparency[ 2 ], offs ) : 1.0;
@@ -1229,7 +1231,7 @@ static v3 sample_position( ctx_t* c, const camera_t* cam, double monitor_x, doub
     ray_t ray;
     ray.p = v3_ld( s->camera_position );
     ray.d = m3_mlv( &cam->camera_rotation, d );
-    COST( c, ACN_F_CAMERA_RAY, 0 );
+    COST_SHADE( c, ACN_F_CAMERA_RAY, 0 );
 
     v3 out_clr = shard_skips_terms( c ) ? V( 0, 0, 0 ) : v3_ld( s->background_color );
     trans_t trans_l = { { 0, 0, 0 }, -1, -1 };
@@ -1327,15 +1329,24 @@ static void* farm_func( void* arg )
     return NULL;
 }
 
+/* The two entry points that existed before the counters were split fill the 18 words their callers' buffers have (up to ORC_N_TRANSC);
+ * acn_oracle_render_positions_work takes the length of the caller's buffer and fills up to ORC_N_COUNTERS words of it. */
 int acn_oracle_render_positions( const acn_flat_scene* scene, const double* pos_xy, size_t n, double* out_rgb,
                                  uint32_t flags, int threads, uint64_t* counters )
 {
-    return acn_oracle_render_positions_shard( scene, pos_xy, n, out_rgb, flags, threads, counters, 0, 1 );
+    return acn_oracle_render_positions_work( scene, pos_xy, n, out_rgb, flags, threads, counters, ORC_N_TRANSC + 1, 0, 1 );
 }
 
 int acn_oracle_render_positions_shard( const acn_flat_scene* scene, const double* pos_xy, size_t n, double* out_rgb,
                                        uint32_t flags, int threads, uint64_t* counters, uint32_t rank, uint32_t world )
 {
+    return acn_oracle_render_positions_work( scene, pos_xy, n, out_rgb, flags, threads, counters, ORC_N_TRANSC + 1, rank, world );
+}
+
+int acn_oracle_render_positions_work( const acn_flat_scene* scene, const double* pos_xy, size_t n, double* out_rgb, uint32_t flags,
+                                      int threads, uint64_t* counters, size_t n_counters, uint32_t rank, uint32_t world )
+{
+    if( n_counters > ORC_N_COUNTERS ) n_counters = ORC_N_COUNTERS;
     if( world > 1 && ( rank >= world || !( flags & ACN_OPT_LINEAR_OUT ) ) ) return ACN_ERR_ARG;   /* partial sums are linear */
     int st = validate( scene );
     if( st != ACN_OK ) return st;
@@ -1366,8 +1377,8 @@ int acn_oracle_render_positions_shard( const acn_flat_scene* scene, const double
     }
     if( counters )
     {
-        memset( counters, 0, sizeof( uint64_t ) * ORC_N_COUNTERS );
-        for( int t = 0; t < threads; t++ ) for( int k = 0; k < ORC_N_COUNTERS; k++ ) counters[ k ] += farms[ t ].cnt[ k ];
+        memset( counters, 0, sizeof( uint64_t ) * n_counters );
+        for( int t = 0; t < threads; t++ ) for( size_t k = 0; k < n_counters; k++ ) counters[ k ] += farms[ t ].cnt[ k ];
     }
     free( th );
     free( farms );
@@ -1514,6 +1525,7 @@ typedef struct
     double* out;
     size_t* index;
     pthread_mutex_t* mutex;
+    uint64_t* counters;   /* nullable: every thread adds its own tallies under the mutex when it ends */
 } query_farm_t;
 
 static void query_one( ctx_t* c, int op, int32_t node, const double* r, double limit, double* o )
@@ -1546,7 +1558,8 @@ static void query_one( ctx_t* c, int op, int32_t node, const double* r, double l
 static void* query_farm_func( void* arg )
 {
     query_farm_t* f = arg;
-    ctx_t c = { f->sc, NULL, 0, 1, 0 };
+    uint64_t cnt[ ORC_N_COUNTERS ] = { 0 };
+    ctx_t c = { f->sc, f->counters ? cnt : NULL, 0, 1, 0 };
     for( ;; )
     {
         pthread_mutex_lock( f->mutex );
@@ -1558,11 +1571,23 @@ static void* query_farm_func( void* arg )
         for( size_t i = first; i < last; i++ )
             query_one( &c, f->op, f->node, f->rays + 6 * i, f->limits ? f->limits[ i ] : F3_INF, f->out + ACN_ORACLE_QUERY_STRIDE * i );
     }
+    if( f->counters )
+    {
+        pthread_mutex_lock( f->mutex );
+        for( int k = 0; k < ORC_N_COUNTERS; k++ ) f->counters[ k ] += cnt[ k ];
+        pthread_mutex_unlock( f->mutex );
+    }
     return NULL;
 }
 
 int acn_oracle_query_rays( const acn_flat_scene* scene, int op, int32_t node, const double* rays, size_t n, const double* limits,
                            double* out, int threads )
+{
+    return acn_oracle_query_rays_counted( scene, op, node, rays, n, limits, out, threads, NULL );
+}
+
+int acn_oracle_query_rays_counted( const acn_flat_scene* scene, int op, int32_t node, const double* rays, size_t n, const double* limits,
+                                   double* out, int threads, uint64_t* counters )
 {
     int st = validate( scene );
     if( st != ACN_OK ) return st;
@@ -1575,7 +1600,7 @@ int acn_oracle_query_rays( const acn_flat_scene* scene, int op, int32_t node, co
     if( threads > 256 ) threads = 256;
     size_t index = 0;
     pthread_mutex_t mutex = PTHREAD_MUTEX_INITIALIZER;
-    query_farm_t f = { scene, op, node, rays, limits, n, out, &index, &mutex };
+    query_farm_t f = { scene, op, node, rays, limits, n, out, &index, &mutex, counters };
     if( threads == 1 ) query_farm_func( &f );
     else
     {
@@ -1606,5 +1631,20 @@ int acn_oracle_shade_point( const acn_flat_scene* scene, const double* hit, doub
     v3 lum = scene_lum( &c, &ray, hit[ 6 ], &trans, ( uint64_t )hit[ 12 ], hit[ 13 ] );
     if( out_lum3 ) st3( out_lum3, lum );
     *n_rows = tap.n;
+    return 0;
+}
+
+int acn_oracle_shade_point_counters( const acn_flat_scene* scene, const double* hit, uint64_t* counters )
+{
+    if( !scene || !hit || !counters ) return -1;
+    int st = validate( scene );
+    if( st ) return st;
+    const int exit_obj = ( int )hit[ 10 ], enter_obj = ( int )hit[ 11 ];
+    if( exit_obj < -1 || exit_obj >= ( int )scene->n_nodes || enter_obj < -1 || enter_obj >= ( int )scene->n_nodes || hit[ 12 ] < 0 ) return -1;
+    tap_t tap = { NULL, 0, 0, { 0 } };
+    ctx_t c = { scene, counters, 0, 1, 0, &tap };
+    ray_t ray = { v3_ld( hit ), v3_ld( hit + 3 ) };
+    trans_t trans = { v3_ld( hit + 7 ), exit_obj, enter_obj };
+    scene_lum( &c, &ray, hit[ 6 ], &trans, ( uint64_t )hit[ 12 ], hit[ 13 ] );
     return 0;
 }

@@ -54,6 +54,11 @@ int main()
         { acn_stage_args b = a; b.stage = ACN_STAGE_N; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "stage" ) ); }
         { acn_stage_args b = a; b.flags = 8; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "flags" ) ); }
         { acn_stage_args b = a; b.flags = 7; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_OK ); }
+        /* bit 16, ACN_STAGE_COUNT_WORK: the counting variants, alone and beside the others; the walk's bit 8 stays refused beside it, and bit 32 is unknown */
+        { acn_stage_args b = a; b.flags = ACN_STAGE_COUNT_WORK; EXPECT( ACN_STAGE_COUNT_WORK == 16u && acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_OK ); }
+        { acn_stage_args b = a; b.flags = 7 | ACN_STAGE_COUNT_WORK; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_OK ); }
+        { acn_stage_args b = a; b.flags = 8 | ACN_STAGE_COUNT_WORK; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "flags" ) ); }
+        { acn_stage_args b = a; b.flags = 32; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "flags" ) ); }
         { acn_stage_args b = a; b.in = nullptr; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "in" ) ); }
         { acn_stage_args b = a; b.n = 0; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "records" ) ); }
         { acn_stage_args b = a; b.n = ACN_STAGE_MAX_RECORDS + 1; EXPECT( acn_stage_check( true, &b, sc, &caps, &msg ) == ACN_ERR_ARG && says( msg, "records" ) ); }

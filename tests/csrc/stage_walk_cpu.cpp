@@ -51,7 +51,7 @@ int main()
     { acn_stage_walk_args b = a; b.passes = 32; b.grid = 3; EXPECT( acn_stage_walk_check( true, &b, sc, &caps, &msg ) == ACN_OK );
       EXPECT( caps.grid == 3 && caps.cap_rays == 100 + 768 && caps.cap_tasks == 100 + 32 * 768 && caps.cap_hard_shadow == 300 + 32 * 768 ); }
     { acn_stage_walk_args b = a; b.grid = 64; b.stack_cap = ACN_STAGE_WALK_MAX_STACK; b.stack_use = b.stack_cap; b.fetch = ACN_STAGE_MAX_RECORDS; b.private_limit = 0;
-      b.flags = ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES;
+      b.flags = ACN_STAGE_NO_PRUNE | ACN_STAGE_NO_EMIT_TERMS | ACN_STAGE_GLOBAL_NODES | ACN_STAGE_COUNT_WORK;
       EXPECT( acn_stage_walk_check( true, &b, sc, &caps, &msg ) == ACN_OK && caps.grid == 64 ); }
     { acn_stage_walk_args b = a; b.stack_cap = 1; b.stack_use = 1; EXPECT( acn_stage_walk_check( true, &b, sc, &caps, &msg ) == ACN_OK ); }
     { acn_stage_walk_args b = a; b.room_rays = 6; EXPECT( acn_stage_walk_check( true, &b, sc, &caps, &msg ) == ACN_OK && caps.cap_rays == 6 + 256 ); }
@@ -88,7 +88,9 @@ int main()
     };
     { acn_stage_walk_args b = a; b.stage = ACN_STAGE_SHADE_HITS; EXPECT( refused_args( b, "ACN_STAGE_WALK" ) ); }
     { acn_stage_walk_args b = a; b.flags = ACN_STAGE_NO_LEAF_LIGHTS; EXPECT( refused_args( b, "flags" ) ); }
-    { acn_stage_walk_args b = a; b.flags = 16; EXPECT( refused_args( b, "flags" ) ); }
+    { acn_stage_walk_args b = a; b.flags = ACN_STAGE_COUNT_WORK; EXPECT( acn_stage_walk_check( true, &b, sc, &caps, &msg ) == ACN_OK ); }   /* bit 16: the counting variants */
+    { acn_stage_walk_args b = a; b.flags = 32; EXPECT( refused_args( b, "flags" ) ); }
+    { acn_stage_walk_args b = a; b.flags = ACN_STAGE_COUNT_WORK | ACN_STAGE_NO_LEAF_LIGHTS; EXPECT( refused_args( b, "flags" ) ); }
     { acn_stage_walk_args b = a; b.in = nullptr; EXPECT( refused_args( b, "neither input form" ) ); }
     { std::vector< double > pos( 12, 0.5 ); acn_stage_walk_args b = a; b.pos_xy = pos.data(); EXPECT( refused_args( b, "both input forms" ) ); }
     { acn_stage_walk_args b = a; b.n = 0; EXPECT( refused_args( b, "records" ) ); }

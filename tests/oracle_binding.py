@@ -8,7 +8,10 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 COUNTER_NAMES = ["lum", "trans_ray", "shadow_ray", "obj_hit", "env_test", "plane_hit", "sphere_hit", "squaroid_hit",
-                 "sdf_ray", "sdf_eval", "pair_hit", "side", "cap_sample", "oren_nayar", "fresnel", "node_visit", "flop", "transc"]
+                 "sdf_ray", "sdf_eval", "pair_hit", "side", "cap_sample", "oren_nayar", "fresnel", "node_visit", "flop", "transc",
+                 # appended (oracle/acn_oracle.h): the two loops of scene_s_lum apart, and the part of flop / transc that scene_s_lum
+                 # and the camera ray book themselves -- what is left, flop - flop_shade, is geometry
+                 "oren_nayar_direct", "oren_nayar_path", "flop_shade", "transc_shade"]
 
 
 class Oracle:
@@ -22,6 +25,7 @@ class Oracle:
         vp = C.c_void_p
         L.acn_oracle_render_positions.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, vp]
         L.acn_oracle_render_positions_shard.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, vp, C.c_uint32, C.c_uint32]
+        L.acn_oracle_render_positions_work.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, vp, C.c_size_t, C.c_uint32, C.c_uint32]
         L.acn_oracle_estimate_envelope.argtypes = [vp, C.c_int32, C.c_uint64, C.c_uint32, C.c_double, vp]
         L.acn_oracle_sphere_ray_hit.argtypes = [vp, C.c_double, vp, vp, vp]
         L.acn_oracle_sphere_ray_hit.restype = C.c_double
@@ -42,6 +46,8 @@ class Oracle:
         L.acn_oracle_sphere_cap.restype = None
         L.acn_oracle_query_rays.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, C.c_int]
         L.acn_oracle_shade_point.argtypes = [vp, vp, vp, C.c_size_t, vp, vp]
+        L.acn_oracle_query_rays_counted.argtypes = [vp, C.c_int, C.c_int32, vp, C.c_size_t, vp, vp, C.c_int, vp]
+        L.acn_oracle_shade_point_counters.argtypes = [vp, vp, vp]
 
     def math_mode(self):
         return self.lib.acn_oracle_math_mode()
@@ -53,8 +59,8 @@ class Oracle:
         cnt = (C.c_uint64 * len(COUNTER_NAMES))() if counters else None
         threads = threads or os.cpu_count() or 1
         rank, world = shard if shard else (0, 1)
-        st = self.lib.acn_oracle_render_positions_shard(C.addressof(flat.c), pos.ctypes.data, pos.shape[0], out.ctypes.data,
-                                                        1 if linear else 0, threads, cnt, rank, world)
+        st = self.lib.acn_oracle_render_positions_work(C.addressof(flat.c), pos.ctypes.data, pos.shape[0], out.ctypes.data,
+                                                       1 if linear else 0, threads, cnt, len(COUNTER_NAMES), rank, world)
         if st != 0:
             raise RuntimeError(f"oracle status {st}")
         if counters:
@@ -119,15 +125,19 @@ class Oracle:
 
     QUERY_OPS = {"obj_ray_hit": 0, "obj_side": 1, "compound_ray_hit": 2, "trans_hit": 3, "occluded": 4}
 
-    def query_rays(self, flat, op, node, rays, limits=None, threads=16):
-        """acn_oracle_query_rays: [n, 8] results of the one-ray function `op` for rays [n, 6] (origin, direction)."""
+    def query_rays(self, flat, op, node, rays, limits=None, threads=16, counters=False):
+        """acn_oracle_query_rays: [n, 8] results of the one-ray function `op` for rays [n, 6] (origin, direction).  counters: also
+        the oracle's event counters of exactly these calls, as a dict (COUNTER_NAMES)."""
         r = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
         lim = None if limits is None else np.ascontiguousarray(limits, dtype=np.float64).reshape(-1)
         out = np.zeros((max(r.shape[0], 1), 8), dtype=np.float64)
-        st = self.lib.acn_oracle_query_rays(C.addressof(flat.c), self.QUERY_OPS[op], int(node), r.ctypes.data, r.shape[0],
-                                            None if lim is None else lim.ctypes.data, out.ctypes.data, min(threads, 16))
+        cnt = (C.c_uint64 * len(COUNTER_NAMES))() if counters else None
+        st = self.lib.acn_oracle_query_rays_counted(C.addressof(flat.c), self.QUERY_OPS[op], int(node), r.ctypes.data, r.shape[0],
+                                                    None if lim is None else lim.ctypes.data, out.ctypes.data, min(threads, 16), cnt)
         if st != 0:
             raise RuntimeError(f"oracle status {st}")
+        if counters:
+            return out[:r.shape[0]], dict(zip(COUNTER_NAMES, [int(v) for v in cnt]))
         return out[:r.shape[0]]
 
     def obj_ray_hits(self, flat, node, rays, threads=16):
@@ -166,3 +176,13 @@ class Oracle:
             if n.value <= room:
                 return rows[:n.value], lum
             room = n.value
+
+    def shade_point_counters(self, flat, hit):
+        """the oracle's event counters (COUNTER_NAMES) of the scene_s_lum call shade_point taps: its own events, and the geometry of
+        its two sample loops (light hits, shadow rays, path transition hits); no specular child is traced"""
+        hit = np.ascontiguousarray(hit, dtype=np.float64).reshape(14)
+        cnt = (C.c_uint64 * len(COUNTER_NAMES))()
+        st = self.lib.acn_oracle_shade_point_counters(C.addressof(flat.c), hit.ctypes.data, cnt)
+        if st != 0:
+            raise RuntimeError(f"oracle status {st}")
+        return dict(zip(COUNTER_NAMES, [int(v) for v in cnt]))

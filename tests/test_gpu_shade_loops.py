@@ -425,3 +425,4 @@ def test_count_variant_tallies(oracle):
     assert g["lum_calls"] == c["lum"] and g["cap_samples"] == c["cap_sample"]
     assert g["shadow_rays"] == c["shadow_ray"] and g["trans_rays"] == c["trans_ray"]
     assert g["overflows"] == 0
+    M.frame_work_identities(g, c)                              # transcendentals as an identity, flop from its shading part up

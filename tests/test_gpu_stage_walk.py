@@ -323,7 +323,7 @@ def test_refusals_before_any_launch(case_a):
         assert refused(bad), (field, value)
     for kw in (dict(passes=0), dict(passes=A.abi.ACN_MAX_WALK_PASSES + 1), dict(stack_cap=0), dict(stack_cap=A.abi.ACN_STAGE_WALK_MAX_STACK + 1),
                dict(stack_cap=64, stack_use=65), dict(fetch=63), dict(fetch=(1 << 20) + 1), dict(grid=65), dict(room_rays=7), dict(room_rays=1 << 26),
-               dict(flags=16), dict(flags=A.abi.ACN_STAGE_NO_LEAF_LIGHTS), dict(pos_xy=np.zeros((8, 2))), dict(n=8)):
+               dict(flags=32), dict(flags=A.abi.ACN_STAGE_COUNT_WORK | A.abi.ACN_STAGE_NO_LEAF_LIGHTS), dict(flags=A.abi.ACN_STAGE_NO_LEAF_LIGHTS), dict(pos_xy=np.zeros((8, 2))), dict(n=8)):
         assert refused(**kw), kw
     # neither form, and the raw entry points with null arguments
     a, caps, o = A.abi.StageWalkArgs(), A.abi.StageCaps(), A.abi.StageOut()

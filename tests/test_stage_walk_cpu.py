@@ -39,8 +39,12 @@ def test_binding_names_the_walk_stage_as_the_header_does():
         assert m and int(m.group(1)) == getattr(A.abi, name), name
     assert re.search(r"#define ACN_MAX_WALK_PASSES (\d+)", counts).group(1) == str(A.abi.ACN_MAX_WALK_PASSES)
     # the flags of the walk are distinct bits beside the stage runner's
-    bits = (A.abi.ACN_STAGE_NO_PRUNE, A.abi.ACN_STAGE_NO_LEAF_LIGHTS, A.abi.ACN_STAGE_NO_EMIT_TERMS, A.abi.ACN_STAGE_GLOBAL_NODES)
-    assert sorted(bits) == [1, 2, 4, 8]
+    bits = (A.abi.ACN_STAGE_NO_PRUNE, A.abi.ACN_STAGE_NO_LEAF_LIGHTS, A.abi.ACN_STAGE_NO_EMIT_TERMS, A.abi.ACN_STAGE_GLOBAL_NODES,
+            A.abi.ACN_STAGE_COUNT_WORK)
+    assert sorted(bits) == [1, 2, 4, 8, 16]
+    m = re.search(r"#define ACN_STAGE_COUNT_WORK\s+(\d+)u", header)
+    assert m and int(m.group(1)) == A.abi.ACN_STAGE_COUNT_WORK
+    assert "int acn_stage_last_counters( acn_scene_handle* h, uint64_t* out, int n );" in header
     # the struct, field for field in the header's order
     body = re.search(r"typedef struct acn_stage_walk_args\s*\{(.*?)\}\s*acn_stage_walk_args;", header, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)

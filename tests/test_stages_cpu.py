@@ -4,6 +4,7 @@ import os
 import subprocess
 
 import numpy as np
+import pytest
 
 import actinon_amd as A
 import ray_sets as R
@@ -289,3 +290,37 @@ def test_closed_form_weight_contract(oracle, detmath_cpu):
     for name, sel in regions.items():
         assert sel.sum() > 500, (name, sel.sum())
         assert quot[sel].max() <= CLOSED_FORM_K[name], (name, quot[sel].max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the work ledger (shade_model.ledger, ledger_hit): the model of what a scene_s_lum call books, against the oracle's own books
+
+@pytest.mark.parametrize("name", ["primitives_path", "wine_glass_c2"])
+def test_ledger_sums_to_the_oracles_counters(oracle, name):
+    """The ledgers of every tap of a small frame, with scene_lum's recursion made from the rows (shade_model.frame_ledger), add up to
+    the counters Oracle.render_positions returns for the same positions.  Before the device's differences are applied the model is
+    the oracle's own bookkeeping read off its rows, so this is an identity: no tolerance.  The costs come from acn_costs.h."""
+    import scenes_util as S
+    sc, flat = S.build(name)
+    pos = S.positions(flat)
+    pos = pos[::-(-len(pos) // 200)]
+    assert 150 <= len(pos) <= 200
+    _, c = oracle.render_positions(flat, pos, counters=True)
+    m = M.frame_ledger(oracle, flat, pos)
+    assert c["flop_shade"] > 100000 and c["transc_shade"] > 10000 and c["oren_nayar_direct"] > 0 and c["oren_nayar_path"] > 0
+    for ours, theirs in (("flop_shade", "flop_shade"), ("transc_shade", "transc_shade"), ("cap_sample", "cap_sample"), ("shadow_ray", "shadow_ray"),
+                         ("lum", "lum"), ("trans_ray", "trans_ray"), ("oren_nayar_direct", "oren_nayar_direct"), ("oren_nayar_path", "oren_nayar_path")):
+        assert m[ours] == c[theirs], (ours, m[ours], c[theirs])
+    # the split itself: the two loops add up, and the shading part is a part
+    assert c["oren_nayar_direct"] + c["oren_nayar_path"] == c["oren_nayar"]
+    assert c["flop_shade"] < c["flop"] and c["transc_shade"] <= c["transc"]
+
+
+def test_ledger_reads_the_cost_table():
+    """the numbers are the header's: every event the ledger prices is a line of acn_costs.h"""
+    C = M.costs()
+    for k in ("F_LUM_FIXED", "F_EMISSION", "F_ABSORB", "T_ABSORB", "F_FRESNEL_REFL", "F_FRESNEL_REFR", "F_REFLECTION", "F_SHADE_DIFFUSE", "T_SHADE_DIFFUSE",
+              "F_SEED", "T_SEED", "F_FOV", "F_FRAME", "F_CAP_SAMPLE", "T_CAP_SAMPLE", "F_OREN_NAYAR", "T_OREN_NAYAR", "F_OREN_NAYAR_DIRECT", "F_DIRECT_TAIL",
+              "F_PATH_TAIL", "F_CAMERA_RAY"):
+        assert C[k] > 0, k
+    assert "T_OREN_NAYAR_DIRECT" not in C           # the closed form has no transcendental: DEVICE_DIRECT_WEIGHT

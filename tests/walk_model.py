@@ -85,3 +85,30 @@ def walk(oracle, flat, rays, records, n=None, emit_terms=True, memo=None):
                 w.clamped += int(clamp)
         gen = nxt
     return w
+
+
+def ledger(oracle, flat, rays, records):
+    """What k_walk< COUNT > books for the walk from `rays`, all generations (shade_model.ledger_hit with the device's differences), and
+    the rays [m, 6] it traces: (ledger, traced).  One scene_s_trans_hit per ray -- two compound_s_ray_trans_hit calls -- and shade_hit
+    for every hit; a dead child stands for two more (DEVICE_DEAD_CHILD)."""
+    prm = flat.params
+    gen = [r for r in np.asarray(rays, dtype=records["ray"]) if r["pixel"] != INVALID]
+    parts, traced, trans = [], [], 0
+    while gen:
+        nxt = []
+        for r in gen:
+            traced.append(np.concatenate([r["p"], r["d"]]))
+            trans += 2
+            a, nor, ex, en = oracle.trans_hit(flat, r["p"], r["d"])
+            if not a < np.inf:
+                continue
+            hit = np.zeros((), dtype=records["hit"])
+            hit["p"], hit["d"], hit["offs"], hit["exit_nor"], hit["T"], hit["intensity"] = r["p"], r["d"], a, nor, r["T"], r["intensity"]
+            hit["exit_obj"], hit["enter_obj"], hit["depth"], hit["pixel"] = ex, en, r["depth"], r["pixel"]
+            rows = oracle.shade_point(flat, M.tap_input(hit))[0]
+            parts.append(M.ledger_hit(rows, a, prm, device=True))
+            nxt += M.split_expected(rows, hit, prm, records)[0]
+        gen = nxt
+    out = M.add_ledgers(parts)
+    out["trans_ray"] += trans
+    return out, np.array(traced).reshape(-1, 6)
